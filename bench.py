@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the patch-graph attention head on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode topk|adaptive] [--k 8] [--size 256] [--batch 1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode topk|adaptive] [--k 8] [--size 256] [--batch 1] [--dump-outputs DIR]
 
 A "step" is one forward of one ``CE`` head (prologue convolutions + the whole HIP block) over one batch
 of synthetic feature maps ``[batch,64,size,size]`` that is already resident in HBM.  Default workload =
@@ -85,7 +85,44 @@ def parse():
     ap.add_argument("--stub", action="store_true",
                     help="launcher self-test: the same spawn / rendezvous / barrier / MAX-over-ranks / one-JSON-line protocol with "
                          "a trivial CPU step on the gloo backend (tests/test_bench_spawn.py); not a measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32, at most "
+                         "64 MB in all (a fixed seeded sample of larger outputs); the same arguments give the same inputs, so two builds "
+                         "can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 60 * 10**6       # --dump-outputs: array data of all files together (the .npy headers stay well inside 64 MB)
+DUMP_WHOLE_BYTES = 2**20          # arrays up to this size are always written whole
+DUMP_SAMPLE_SEED = 2024
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: write each tensor of ``arrays`` (name -> tensor on any device) as ``out_dir/<name>.npy``, float32 (float64
+    stays float64).  When all of them together exceed DUMP_MAX_BYTES, every array larger than DUMP_WHOLE_BYTES is replaced by the
+    same share of its elements, taken at seeded positions of the flattened array (sorted; the same positions for the same shape in
+    every run).  Returns {name: {"shape": the array's shape, "saved": the saved shape}} for the result line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {n: (t.detach().double() if t.dtype == torch.float64 else t.detach().float()) for n, t in arrays.items()}
+    sizes = {n: t.numel() * t.element_size() for n, t in arrays.items()}
+    large = sum(s for s in sizes.values() if s > DUMP_WHOLE_BYTES)
+    budget = DUMP_MAX_BYTES - (sum(sizes.values()) - large)
+    meta = {}
+    for name, t in arrays.items():
+        if sizes[name] > DUMP_WHOLE_BYTES and large > budget:
+            n = t.numel()
+            rng = np.random.default_rng([DUMP_SAMPLE_SEED, n])
+            pos = np.unique(rng.integers(0, n, size=max(1, n * budget // large)))
+            arr = t.reshape(-1)[torch.from_numpy(pos).to(t.device)].cpu().numpy()
+        else:
+            arr = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        meta[name] = {"shape": list(t.shape), "saved": list(arr.shape)}
+    return meta
 
 
 def rank_devices(dist, name):
@@ -715,7 +752,8 @@ def train_bench(args, dev, dist, world, rank):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(step(hr)[0])
+        last = step(hr)                       # (loss, psnr) as device scalars
+        losses.append(last[0])
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -760,6 +798,8 @@ def train_bench(args, dev, dist, world, rank):
                                          "latency terms ignored -- an expectation, NOT a measurement: no multi-GPU node was available to "
                                          "this repository's rounds; `allreduce_ms` above is the live figure of THIS run's world size"},
                 "loss_first_last": [float(losses[0]), float(losses[-1])] if losses else None}
+        if args.dump_outputs:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, {"loss": last[0], "psnr": last[1]})
         print(json.dumps(line))
 
 
@@ -824,6 +864,7 @@ def main():
 
     prof = ops.StageProfile(max(args.steps, 1))
     heads_per_step = 1
+    last = {}                                 # the output of the latest step (a fresh tensor per call)
     if args.stage:
         heads_per_step = 4
         heads = [ce]
@@ -848,12 +889,13 @@ def main():
             out, inf = ops.ces_stage_forward(x, prm, mix_w, mix_b, mode=mode, k=ce.select_k, workspace=ws_stage, profile=profile,
                                              weights_packed=packed)
             assert out is not None, "dense neighbourhoods: the stage entry point handed the call back"
+            last["out"] = out
             info_box["info"] = inf
             info_box["ws_ptr"] = ws_stage.peek(x.device).data_ptr()
     else:
         def step(profile=None):
             ce.profile = profile
-            ce(x)
+            last["out"] = ce(x)
     with torch.no_grad():
         # the COLD figure first (what --prewarm 0 reports): W warm-up steps on a GPU that sat idle while the case was built, then K
         # timed steps -- kept beside the sustained figure in the line ("ms_per_step_cold")
@@ -882,6 +924,7 @@ def main():
         if dist is not None:
             dist.barrier()
         elapsed = time.perf_counter() - t0
+        timed_out = last["out"]               # what the last timed step returned (the passes below leave it alone)
         dominant_ms = [c[6 if dense_regime else 4] for c in prof.read()]
         prof.select_stage(-1)
         for _ in range(min(args.steps, 20)):
@@ -1022,6 +1065,8 @@ def main():
             line["cpu_baseline"] = cpu_baseline(args, params, mode, k, x_cpu=x[:1].cpu(), hip_out=hip_out)
             if "parity_err" in line["cpu_baseline"]:
                 line["parity_err"] = line["cpu_baseline"]["parity_err"]
+        if args.dump_outputs:
+            line["dump_outputs"] = dump_outputs(args.dump_outputs, {"out": timed_out})
         print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()
