@@ -26,17 +26,17 @@ __global__ void retag_kernel(int32_t* word, int32_t* veto, int32_t tag) {
     if (veto != nullptr && *veto == tag) *veto = STALE_TAG;
 }
 
-// Top-k threshold policy words of a workspace (stats[9] policy, stats[10] gate, stats[12] owner cookie).  A call that is not
+// Top-k threshold policy words of a workspace (STAT_POLICY, STAT_GATE, STAT_OWNER).  A call that is not
 // "prepared" (first call, another shape, a train / eval alternation) used to clear the policy: a module that alternates between
 // two shapes forgot "tight" on every call and paid sampled pass + policy kernel + tight re-run each time.  The learnt word now
 // survives as long as the workspace still carries the cookie of this very geometry (a fresh or re-used buffer does not).
 __global__ void policy_init_kernel(int64_t* stats, int64_t cookie, int32_t start_tight) {
-    if (stats[12] != cookie) { stats[9] = start_tight; stats[12] = cookie; }
-    // [13]: sticky "a DAGL_FLAG_NO_REDO call went unserved" -- only prepared (weights-packed) calls set or report it, and this kernel runs
+    if (stats[STAT_OWNER] != cookie) { stats[STAT_POLICY] = start_tight; stats[STAT_OWNER] = cookie; }
+    // sticky "a DAGL_FLAG_NO_REDO call went unserved" -- only prepared (weights-packed) calls set or report it, and this kernel runs
     // on the non-prepared ones: cleared every time, so that a workspace handed on by torch's caching allocator, or shared by modules of
     // one shape (the cookie hashes the geometry, not the owner), cannot pass a stale bit to CE.range_ok()
-    stats[13] = 0;
-    stats[10] = 0;
+    stats[STAT_NO_REDO_STICKY] = 0;
+    stats[STAT_GATE] = 0;
 }
 
 void set_error(const char* fmt, ...) {
@@ -133,7 +133,7 @@ struct Plan {
     // byte offsets into the workspace
     size_t o_b1p, o_b2p, o_wp1, o_wp2, o_x, o_wq, o_xh, o_wqh, o_colsum, o_mt, o_cnt, o_segcnt, o_segoff, o_rowoff,
         o_deg, o_stats, o_lidx, o_lval, o_cidx, o_cval, o_nbidx, o_nbwgt, o_nbcnt, o_agg, o_gmax, o_theta, o_smax, o_traw, o_scand, o_spill, o_spillcnt,
-        o_scandv, o_ssegcnt, o_redo, o_ovflist, o_heavy, o_ovfq, o_ovfscores, o_ovfpart, o_thr, o_bias, o_thrpart, o_maphi, o_maplo, o_maphi2, o_maplo2, o_b1amax, o_wp1h, o_wp2h, o_convw, o_colpart, o_end;
+        o_redo, o_ovflist, o_heavy, o_ovfq, o_ovfscores, o_ovfpart, o_thr, o_bias, o_thrpart, o_maphi, o_maplo, o_maphi2, o_maplo2, o_b1amax, o_wp1h, o_wp2h, o_convw, o_colpart, o_end;
 };
 
 static bool g_N_small(int H, int W);
@@ -148,6 +148,7 @@ constexpr int SCREEN_CAPSEG = 16;
 static bool g_N_small(int H, int W) { return (int64_t)H * W < SCREEN_MIN_KEYS; }
 
 static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool core = false) {
+    p = Plan{};                     // (offsets of regions this plan does not carve stay 0)
     const int mode = mode_flags & 0xff;
     const bool exact = (mode_flags & DAGL_FLAG_EXACT_SCAN) != 0;
     DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "dagl: bad shape B=%d H=%d W=%d", B, H, W);
@@ -264,15 +265,11 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
     p.o_segoff = carve(off, BL * p.splits * 2 * sizeof(int32_t));
     p.o_rowoff = carve(off, (BL + 1) * sizeof(int64_t));
     p.o_deg = carve(off, BL * sizeof(int32_t));
-    p.o_stats = carve(off, 16 * sizeof(int64_t));         // [0..3] per-call counters, [4] range word, [5] tag of the last completed call,
-                                                          // [6] redone rows, [7] their edges, [8] veto word (DAGL_FLAG_NO_WAIT),
-                                                          // [9] top-k threshold policy (sticky), [10] gate of the in-call re-run
+    p.o_stats = carve(off, STAT_WORDS * sizeof(int64_t));     // (StatWord, dagl_common.h)
     if (mode == DAGL_MODE_ADAPTIVE) {
         p.o_lidx = carve(off, BL * DAGL_FAST_CAP * sizeof(int32_t));
         p.o_lval = carve(off, BL * DAGL_FAST_CAP * sizeof(float));
-        p.o_cidx = p.o_cval = 0;
     } else {
-        p.o_lidx = p.o_lval = 0;
         p.o_cidx = carve(off, BL * p.splits * 2 * p.kslots * sizeof(int32_t));
         p.o_cval = carve(off, BL * p.splits * 2 * p.kslots * sizeof(float));
     }
@@ -283,7 +280,6 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
     p.o_thr = carve(off, BL * sizeof(float));
     p.o_bias = carve(off, BL * sizeof(float));
     p.o_thrpart = carve(off, 8 * BL * sizeof(float));                       // prologue: partial thr/bias sums of 4 channel groups
-    p.o_maphi = p.o_maplo = p.o_maphi2 = p.o_maplo2 = p.o_b1amax = p.o_wp1h = p.o_wp2h = p.o_convw = p.o_colpart = 0;
     if (!exact) {
         p.o_maphi = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
         p.o_maplo = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
@@ -297,7 +293,6 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
         p.o_convw = carve(off, 4 * CONV_W16_BYTES);                                       // packed g / theta weights per head
         p.o_colpart = carve(off, (size_t)B * project16_key_blocks(g) * 224 * sizeof(float));
     }
-    p.o_xh = p.o_wqh = p.o_gmax = p.o_theta = p.o_smax = p.o_traw = p.o_spill = p.o_spillcnt = p.o_scand = p.o_scandv = p.o_ssegcnt = p.o_redo = 0;
     if (p.screen) {
         p.o_xh = carve(off, (size_t)B * feat_rows_h(g.N) * DSH * sizeof(uint16_t));
         p.o_wqh = carve(off, (size_t)B * feat_rows_h(g.L) * DSH * sizeof(uint16_t));
@@ -305,16 +300,16 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
         p.o_gmax = carve(off, BL * p.s_splits * 2 * p.s_gkeep * sizeof(float));
         p.o_theta = carve(off, BL * sizeof(float));
         p.o_scand = carve(off, BL * p.s_splits * 2 * p.capseg_alloc * sizeof(int2));     // candidate records (count in slot 0)
-        p.o_spill = p.o_spillcnt = 0;
         if (mode != DAGL_MODE_ADAPTIVE) {       // top-k modes: a query's shared area behind its segments (ScreenArgs::spill)
             p.o_spill = carve(off, BL * SCREEN_SPILL * sizeof(int2));
             p.o_spillcnt = carve(off, BL * sizeof(unsigned));
         }
-        p.o_smax = (mode == DAGL_MODE_ADAPTIVE) ? carve(off, BL * sizeof(float)) : 0;      // dense formulation: the rows' shifts (as scores)
-        p.o_traw = (mode == DAGL_MODE_ADAPTIVE) ? carve(off, BL * sizeof(float)) : 0;      // ... and their largest sampled screened scores
+        if (mode == DAGL_MODE_ADAPTIVE) {
+            p.o_smax = carve(off, BL * sizeof(float));       // dense formulation: the rows' shifts (as scores)
+            p.o_traw = carve(off, BL * sizeof(float));       // ... and their largest sampled screened scores
+        }
         p.o_redo = carve(off, (size_t)B * n_qgroups * sizeof(int32_t));
     }
-    p.ovf_cap = 0; p.o_ovflist = p.o_heavy = p.o_ovfq = p.o_ovfscores = p.o_ovfpart = 0;
     if (p.screen && mode == DAGL_MODE_ADAPTIVE && !core) {
         p.ovf_cap = overflow_cap(g.N, B);
         p.o_ovflist = carve(off, (size_t)p.ovf_cap * sizeof(int32_t));
@@ -343,6 +338,31 @@ static int check_device() {
     return DAGL_OK;
 }
 
+// the streamed dense formulation's workspace (dense.hip), carved behind the plan: the end of it, and its offset
+static size_t dense_ws_end(const Plan& p, size_t* o_dense = nullptr) {
+    size_t off = p.o_end;
+    const size_t o = carve(off, dense_workspace_bytes(p.B, p.g));
+    if (o_dense) *o_dense = o;
+    return off;
+}
+
+// every field of a call's info "not known" but the workspace it needs and the path
+static void reset_info(dagl_ce_info* info, int64_t required_bytes, int path) {
+    if (!info) return;
+    info->required_bytes = required_bytes; info->total_edges = -1; info->max_degree = -1; info->redone_queries = -1;
+    info->path = path; info->range_fallback = 0; info->dense_rerun_blocks = 0;
+}
+
+static int32_t* stat32(int64_t* stats, StatWord w) { return reinterpret_cast<int32_t*>(stats + w); }
+
+// ---- one block forward: what an entry point asks for, the state of the call, its stages in launch order ----------------------
+
+struct MapsIn {                  // input of dagl_ce_forward*: the conv outputs (all device pointers)
+    const float *b1, *b2;        // [B,16,H,W] key / query map, value map
+    const float *thr, *bias;     // [B,L] (adaptive modes)
+    const float *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+};
+
 struct FusedIn {                 // input of the fused-prologue entry points (all device pointers), one per head
     const float* x;              // [B,64,H,W] (shared by the heads of a stage)
     const float *g_w, *g_b, *th_w, *th_b, *thr_w, *thr_b, *bias_w, *bias_b;
@@ -351,631 +371,745 @@ struct FusedIn {                 // input of the fused-prologue entry points (al
 
 struct CoreIn {                  // training entry point: features given, neighbour lists handed back for the backward
     const float* wq_rows; const float* x_rows;                   // [B,L,196], [B,N,196] dense rows (post-ReLU)
+    const float* b2; const float* thr; const float* bias;        // [B,16,H,W] value map; [B,L] (adaptive modes)
     int32_t* nb_idx; float* nb_wgt; float* nb_s; int32_t* nb_cnt; // [B,L,width] x3, [B,L]
     float* mu;                                                   // [B,L] row means of S (adaptive modes)
     float* lse;                                                  // dense core (streamed dense formulation): [B,L,2] = {softmax shift M, sum Z};
                                                                  // the list outputs are then unused (null)
 };
 
-static int ce_forward_impl(hipStream_t s, int B, int H, int W, const float* b1, const float* b2, const float* thr,
-                           const float* bias, const float* fc1_w, const float* fc1_b, const float* fc2_w,
-                           const float* fc2_b, int mode_flags, int k, float* out, void* ws, size_t ws_bytes,
-                           dagl_ce_info* info, int32_t* dbg_deg, float* dbg_rowsum, float* dbg_agg,
-                           Profile* prof = nullptr, const FusedIn* fin = nullptr, int heads = 1,
-                           const CoreIn* core = nullptr) {
-    // heads > 1 (stage entry point): `B` counts head x image pairs, batch entry = head * (B / heads) + image; fin[h]
-    // carries head h's weights, `out` is the [B/heads, heads*16, H, W] concat map
-    Plan p;
-    int rc = make_plan(B, H, W, mode_flags, k, p, core != nullptr);
-    if (rc) return rc;
-    const int mode = p.mode;
-    k = p.k;                                                     // (clamped to the number of keys)
-    if (info) { info->required_bytes = (int64_t)p.o_end; info->total_edges = -1; info->max_degree = -1; info->path = 0;
-                info->redone_queries = -1; info->range_fallback = 0; info->dense_rerun_blocks = 0; }
-    DAGL_REQUIRE(out && (core || (fc1_w && fc1_b && fc2_w && fc2_b)), "dagl_ce_forward: null tensor pointer");
-    if (core) {
-        DAGL_REQUIRE(core->wq_rows && core->x_rows && b2 && (core->lse || (core->nb_idx && core->nb_wgt && core->nb_s && core->nb_cnt)),
+struct ForwardRequest {
+    hipStream_t s;
+    int B, H, W, mode_flags, k;
+    float* out; void* ws; size_t ws_bytes; dagl_ce_info* info;
+    // the input: exactly one of the three
+    const MapsIn* maps = nullptr;
+    const FusedIn* fin = nullptr;
+    int heads = 1;               // > 1 (stage entry point): `B` counts head x image pairs, batch entry = head * (B / heads) + image;
+                                 // fin[h] carries head h's weights, `out` is the [B/heads, heads*16, H, W] concat map
+    const CoreIn* core = nullptr;
+    int32_t* dbg_deg = nullptr; float* dbg_rowsum = nullptr; float* dbg_agg = nullptr;     // debug entry point
+    Profile* prof = nullptr;
+    ForwardRequest(void* stream, int B_, int H_, int W_, int mode_flags_, int k_, float* out_, void* ws_, size_t ws_bytes_,
+                   dagl_ce_info* info_)
+        : s((hipStream_t)stream), B(B_), H(H_), W(W_), mode_flags(mode_flags_), k(k_), out(out_), ws(ws_), ws_bytes(ws_bytes_),
+          info(info_) {}
+};
+
+// the request's pointers and workspace, checked against its plan before anything reaches the device
+static int check_request(const ForwardRequest& r, const Plan& p) {
+    const bool thresholds = p.mode != DAGL_MODE_TOPK;          // the adaptive modes take per-query thresholds and biases
+    if (const CoreIn* c = r.core) {
+        DAGL_REQUIRE(r.out, "dagl_ce_forward: null tensor pointer");
+        DAGL_REQUIRE(c->wq_rows && c->x_rows && c->b2 && (c->lse || (c->nb_idx && c->nb_wgt && c->nb_s && c->nb_cnt)),
                      "dagl_ce_core_forward: null tensor pointer");
-        if (mode != DAGL_MODE_TOPK) DAGL_REQUIRE(thr && bias && core->mu, "dagl_ce_core_forward: thr/bias/mu required in adaptive modes");
-    } else if (fin) {
-        DAGL_REQUIRE(fin->x && fin->g_w && fin->g_b && fin->th_w && fin->th_b, "dagl_ce_forward_fused: null tensor pointer");
-        if (mode != DAGL_MODE_TOPK)
-            DAGL_REQUIRE(fin->thr_w && fin->thr_b && fin->bias_w && fin->bias_b, "dagl_ce_forward_fused: thr/bias heads required in adaptive modes");
+        if (thresholds) DAGL_REQUIRE(c->thr && c->bias && c->mu, "dagl_ce_core_forward: thr/bias/mu required in adaptive modes");
+    } else if (const FusedIn* f = r.fin) {
+        DAGL_REQUIRE(r.out && f->fc1_w && f->fc1_b && f->fc2_w && f->fc2_b, "dagl_ce_forward: null tensor pointer");
+        DAGL_REQUIRE(f->x && f->g_w && f->g_b && f->th_w && f->th_b, "dagl_ce_forward_fused: null tensor pointer");
+        if (thresholds)
+            DAGL_REQUIRE(f->thr_w && f->thr_b && f->bias_w && f->bias_b, "dagl_ce_forward_fused: thr/bias heads required in adaptive modes");
     } else {
-        DAGL_REQUIRE(b1 && b2, "dagl_ce_forward: null tensor pointer");
-        if (mode != DAGL_MODE_TOPK) DAGL_REQUIRE(thr && bias, "dagl_ce_forward: thr/bias required in adaptive modes");
+        const MapsIn* m = r.maps;
+        DAGL_REQUIRE(r.out && m->fc1_w && m->fc1_b && m->fc2_w && m->fc2_b, "dagl_ce_forward: null tensor pointer");
+        DAGL_REQUIRE(m->b1 && m->b2, "dagl_ce_forward: null tensor pointer");
+        if (thresholds) DAGL_REQUIRE(m->thr && m->bias, "dagl_ce_forward: thr/bias required in adaptive modes");
     }
-    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "dagl_ce_forward: workspace must be 256-byte aligned");
-    if (ws_bytes < p.o_end) {
-        set_error("dagl_ce_forward: workspace %zu B < required %zu B", ws_bytes, p.o_end);
+    DAGL_REQUIRE(r.ws != nullptr && ((uintptr_t)r.ws % 256) == 0, "dagl_ce_forward: workspace must be 256-byte aligned");
+    if (r.ws_bytes < p.o_end) {
+        set_error("dagl_ce_forward: workspace %zu B < required %zu B", r.ws_bytes, p.o_end);
         return DAGL_ERR_WORKSPACE;
     }
-    const Grid& g = p.g;
-    const size_t BL = (size_t)B * g.L;
-    const int n_qgroups = (g.L + 127) / 128;
+    return DAGL_OK;
+}
 
-    float* b1p = at<float>(ws, p.o_b1p);
-    float* b2p = at<float>(ws, p.o_b2p);
-    float* wp1 = at<float>(ws, p.o_wp1);
-    float* wp2 = at<float>(ws, p.o_wp2);
-    float* X = at<float>(ws, p.o_x);
-    float* Wq = at<float>(ws, p.o_wq);
-    uint16_t* Xh = p.screen ? at<uint16_t>(ws, p.o_xh) : nullptr;
-    uint16_t* Wqh = p.screen ? at<uint16_t>(ws, p.o_wqh) : nullptr;
-    double* colsum = at<double>(ws, p.o_colsum);
-    float* mt = at<float>(ws, p.o_mt);
-    int32_t* cnt = at<int32_t>(ws, p.o_cnt);
-    int32_t* segcnt = at<int32_t>(ws, p.o_segcnt);
-    int32_t* segrel = at<int32_t>(ws, p.o_segoff);
-    int64_t* rowoff = at<int64_t>(ws, p.o_rowoff);
-    int32_t* deg = at<int32_t>(ws, p.o_deg);
-    int64_t* stats = at<int64_t>(ws, p.o_stats);
-    int32_t* nbidx = core ? core->nb_idx : at<int32_t>(ws, p.o_nbidx);
-    float* nbwgt = core ? core->nb_wgt : at<float>(ws, p.o_nbwgt);
-    int32_t* nbcnt = core ? core->nb_cnt : at<int32_t>(ws, p.o_nbcnt);
-    float* agg = at<float>(ws, p.o_agg);
-
-    // range guard of the split-fp16 kernels (dagl_common.h RangeTag); the fp32 path and the training entry point have no
-    // such range
-    RangeTag rt;
-    // (round 6: the fp32 path too -- it has no range, but a NaN feature must not become a 0 behind its ReLU, nor an inf-poisoned key drop out
-    // of the selection: dagl.py:207-275 returns NaN for a non-finite input, and so does every path here; project.hip sets the word)
-    {                               // (training entry points: the streamed dense core splits the features into fp16 halves too, and
-                                    //  non-finite feature rows -- a poisoned projection upstream -- must not vanish in the selection)
-        rt.word = reinterpret_cast<int32_t*>(stats + 4); rt.done = reinterpret_cast<int32_t*>(stats + 5); rt.tag = next_call_tag();
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-        if (cap == hipStreamCaptureStatusActive) {
-            hipLaunchKernelGGL(retag_kernel, dim3(1), dim3(1), 0, s, rt.word,
-                               mode == DAGL_MODE_ADAPTIVE ? reinterpret_cast<int32_t*>(stats + 8) : nullptr, rt.tag);
-            DAGL_LAUNCH_CHECK("retag_kernel");
-        }
-    }
-
-    // ---- stage 0: layout: zero-bordered NHWC maps, packed fc weights ------------------------------------
-    prof_mark(prof, s, 0);
-    ThrHeadSet thr_all = {};
-    bool thr_in_proj = false;
-    const int imgs = B / heads;
+// One forward call: its plan, the workspace carve resolved to pointers, and what its stages share.  Built once per call.
+struct Call {
+    const ForwardRequest& r;
+    const Plan& p;
+    const Grid& g;
+    hipStream_t s;
+    int B, mode, k, heads;
+    size_t BL;
+    int n_qgroups;                                   // query groups of 128 per image (the fp32 scan's redo unit)
+    const FusedIn* fin; const CoreIn* core;
+    const float *fc1_w, *fc1_b, *fc2_w, *fc2_b;      // head 0's fc weights (null on the training entry point)
+    const float *thr, *bias;                         // per-query heads: the caller's, or the fused prologue's in the workspace
+    float *b1p, *b2p, *wp1, *wp2, *X, *Wq, *mt, *agg;
+    uint16_t *Xh, *Wqh;                              // bf16 features (screen)
+    double* colsum;
+    int64_t* stats;                                  // statistics block (StatWord)
+    int32_t* redo;                                   // screen: query groups the fp32 scan redoes
+    int32_t* nbidx; float* nbwgt; int32_t* nbcnt;    // neighbour lists: the workspace's, or the training entry point's outputs
+    RangeTag rt;                                     // range guard of the split-fp16 kernels (dagl_common.h)
     // "prepared": the caller vouches that this workspace last served an identical call (same geometry, mode, weights):
     // packed weights, the maps' zero borders and the zero guard rows of the feature matrices are still in place, and
     // the few per-call counters are cleared by the prologue kernel itself -- three launches fewer
-    const bool prepared = fin && p.split16 && (mode_flags & DAGL_FLAG_WEIGHTS_PACKED);
-    if (rt.word != nullptr && !prepared) DAGL_HIP_TRY(hipMemsetAsync(stats + 4, 0, 2 * sizeof(int64_t), s));   // fresh workspace
-    if (!prepared && mode == DAGL_MODE_ADAPTIVE) DAGL_HIP_TRY(hipMemsetAsync(stats + 8, 0, sizeof(int64_t), s));
-    // top-k modes behind the screen: the threshold policy lives in the workspace (include/dagl_ce.h DAGL_FLAG_TIGHT_TOPK); a cold
-    // workspace starts with the sampled threshold and a closed gate
-    const bool topk_policy = p.screen && mode != DAGL_MODE_ADAPTIVE && !(mode_flags & (DAGL_FLAG_TIGHT_TOPK | DAGL_FLAG_SAMPLED_TOPK)) &&
-                             p.capseg_tight > 0 && (p.capseg_tight != p.capseg || p.s_sample_tight != p.s_sample);
-    int32_t* policy_w = reinterpret_cast<int32_t*>(stats + 9);
-    int32_t* gate_w = reinterpret_cast<int32_t*>(stats + 10);
-    if (p.screen && mode != DAGL_MODE_ADAPTIVE && !prepared) {
-        // (forced thresholds -- DAGL_FLAG_TIGHT_TOPK / _SAMPLED_TOPK -- do not read the policy word; the cookie and the sticky words are kept all the same)
-        // maps of up to 16 384 keys (128^2; the 72 x 72 leaf tiles of the tiled driver) START on the tight threshold: there it costs
-        // nothing measurable on synthetic maps (sampling every second key tile of <= 256 is a few steps) and its better threshold
+    bool prepared;
+    bool topk_policy;                                // top-k modes behind the screen: the threshold policy lives in the workspace
+    bool fused_theta;                                // the adaptive screen's threshold comes out of query_thresholds_kernel
+    bool no_wait, no_redo;                           // DAGL_FLAG_NO_WAIT / _NO_REDO honoured on this call
+    int q_tiled;                                     // the projection writes the bf16 queries in the screen's fragment order
+    long long ovf_edge_limit;
+    ThrHeadSet thr_all; bool thr_in_proj;            // fused entry points: the thr / bias heads' blocks ride in the projection's launch
+    Split16Out split_out; const Split16Out* split_p; // DAGL_FLAG_DENSE_HINT: the projection also writes dense.hip's split features
+    // set by the stages
+    SelectArgs sa; EdgeArgs ea; AggArgs ag;
+    bool ovf_active = false;         // set once the refine kernel has listed its overflowed queries (adaptive, screened)
+    bool agg_done = false;           // the gather + weighted sum over the lists ran inside the overflow launches (adaptive, screened)
+    bool left_range = false;         // a statistics read-back found this call's tag in the range word
+
+    Call(const ForwardRequest& r_, const Plan& p_);
+};
+
+Call::Call(const ForwardRequest& r_, const Plan& p_) : r(r_), p(p_), g(p_.g) {
+    void* ws = r.ws;
+    const int flags = r.mode_flags;
+    s = r.s; B = r.B; mode = p.mode; k = p.k; heads = r.heads;            // (k clamped to the number of keys)
+    BL = (size_t)B * g.L;
+    n_qgroups = (g.L + 127) / 128;
+    fin = r.fin; core = r.core;
+    fc1_w = fin ? fin->fc1_w : core ? nullptr : r.maps->fc1_w;
+    fc1_b = fin ? fin->fc1_b : core ? nullptr : r.maps->fc1_b;
+    fc2_w = fin ? fin->fc2_w : core ? nullptr : r.maps->fc2_w;
+    fc2_b = fin ? fin->fc2_b : core ? nullptr : r.maps->fc2_b;
+    thr = fin ? at<float>(ws, p.o_thr) : core ? core->thr : r.maps->thr;
+    bias = fin ? at<float>(ws, p.o_bias) : core ? core->bias : r.maps->bias;
+    b1p = at<float>(ws, p.o_b1p); b2p = at<float>(ws, p.o_b2p);
+    wp1 = at<float>(ws, p.o_wp1); wp2 = at<float>(ws, p.o_wp2);
+    X = at<float>(ws, p.o_x); Wq = at<float>(ws, p.o_wq);
+    mt = at<float>(ws, p.o_mt); agg = at<float>(ws, p.o_agg);
+    Xh = p.screen ? at<uint16_t>(ws, p.o_xh) : nullptr;
+    Wqh = p.screen ? at<uint16_t>(ws, p.o_wqh) : nullptr;
+    colsum = at<double>(ws, p.o_colsum);
+    stats = at<int64_t>(ws, p.o_stats);
+    redo = p.screen ? at<int32_t>(ws, p.o_redo) : nullptr;
+    nbidx = core ? core->nb_idx : at<int32_t>(ws, p.o_nbidx);
+    nbwgt = core ? core->nb_wgt : at<float>(ws, p.o_nbwgt);
+    nbcnt = core ? core->nb_cnt : at<int32_t>(ws, p.o_nbcnt);
+    // (every path has the guard: the fp32 path has no range, but a NaN feature must not become a 0 behind its ReLU, nor an
+    // inf-poisoned key drop out of the selection -- dagl.py:207-275 returns NaN for a non-finite input, and so does every path here;
+    // the training entry points: the streamed dense core splits the features into fp16 halves too)
+    rt.word = stat32(stats, STAT_RANGE); rt.done = stat32(stats, STAT_DONE); rt.tag = next_call_tag();
+
+    const bool dbg = r.dbg_deg || r.dbg_rowsum || r.dbg_agg;
+    prepared = fin && p.split16 && (flags & DAGL_FLAG_WEIGHTS_PACKED);
+    topk_policy = p.screen && mode != DAGL_MODE_ADAPTIVE && !(flags & (DAGL_FLAG_TIGHT_TOPK | DAGL_FLAG_SAMPLED_TOPK)) &&
+                  p.capseg_tight > 0 && (p.capseg_tight != p.capseg || p.s_sample_tight != p.s_sample);
+    fused_theta = p.screen && mode == DAGL_MODE_ADAPTIVE;
+    no_wait = (flags & DAGL_FLAG_NO_WAIT) && p.ovf_cap > 0 && !dbg && !core && heads == 1;
+    no_redo = p.screen && (flags & DAGL_FLAG_NO_REDO) && fin && heads == 1 && !core && !dbg;
+    q_tiled = (p.screen && p.split16 && !core) ? 1 : 0;
+    // the per-query redo gathers one value patch per edge of a flagged row (~1 ns each), the dense formulation costs ~9 ps per
+    // (query, key) PAIR whatever the mask: a call whose flagged rows hold more than 1/96 of all pairs goes dense
+    ovf_edge_limit = (long long)((double)BL * (double)g.N / 96.0);
+    // the thr / bias heads' partial sums are first read by query_thresholds_kernel, behind the projection: on the split-fp16 path their
+    // blocks ride in the projection's launch (round 5; 13 us of every adaptive-mode call as a launch of their own)
+    thr_all = {};
+    thr_in_proj = false;
+    if (fin && mode != DAGL_MODE_TOPK) {
+        for (int h = 0; h < heads; ++h) { thr_all.x[h] = fin[h].x; thr_all.thr_w[h] = fin[h].thr_w; thr_all.bias_w[h] = fin[h].bias_w; }
+        thr_all.imgs = B / heads;
+        thr_in_proj = p.split16 && thr_bias4_ok(g, thr_all, heads);
+    }
+    // a call that goes straight to the streamed dense formulation (DAGL_FLAG_DENSE_HINT): the projection writes the split-fp16
+    // features dense.hip consumes as well -- no separate splitting pass over the fp32 rows
+    split_p = nullptr;
+    if (!core && p.split16 && p.screen && mode == DAGL_MODE_ADAPTIVE && (flags & DAGL_FLAG_DENSE_HINT)) {
+        size_t o_dn = 0;
+        if (r.ws_bytes >= dense_ws_end(p, &o_dn)) { split_out = dense_split_buffers(at<char>(ws, o_dn), B, g); split_p = &split_out; }
+    }
+}
+
+static inline void mark(const Call& c, int stage_boundary) { prof_mark(c.r.prof, c.s, stage_boundary); }
+
+// ---- stage 0: layout: zero-bordered NHWC maps, packed fc weights ------------------------------------
+
+// the fused entry points: the g / theta / thr / bias convolutions of every head (prologue.hip); on the split-fp16 path the key /
+// query map leaves them as fp16 halves only
+static int prologue_fused(Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; const FusedIn* fin = c.fin; void* ws = c.r.ws;
+    const int heads = c.heads, imgs = c.B / heads;
+    const bool thr_heads = c.mode != DAGL_MODE_TOPK;
+    const size_t map_f = (size_t)imgs * g.Hp * g.Wp * CH;
+    const bool conv_merged = heads > 1 && p.split16;       // a stage's heads: their g / theta convolutions are ONE launch
+    // a prepared call's per-call counters and redo flags are cleared by the first block of the conv kernel
+    uint32_t* clear_stats = c.prepared ? reinterpret_cast<uint32_t*>(c.stats) : nullptr;
+    const int clear_stats_words = c.prepared ? 2 * STAT_N_COUNTERS : 0;
+    uint32_t* clear_redo = (c.prepared && p.screen) ? reinterpret_cast<uint32_t*>(c.redo) : nullptr;
+    const int clear_redo_words = (c.prepared && p.screen) ? c.B * c.n_qgroups : 0;
+    uint16_t* map_hi = p.split16 ? at<uint16_t>(ws, p.o_maphi) : nullptr;
+    uint16_t* map_lo = p.split16 ? at<uint16_t>(ws, p.o_maplo) : nullptr;
+    float* thr_part = at<float>(ws, p.o_thrpart);
+    // the map's two tiers (B1Tiers): all heads of the call share the slot array, [head][blocks of that head]
+    B1Tiers tiers_all;
+    if (p.split16) {
+        tiers_all.hi2 = at<uint16_t>(ws, p.o_maphi2); tiers_all.lo2 = at<uint16_t>(ws, p.o_maplo2);
+        tiers_all.amax = at<float>(ws, p.o_b1amax); tiers_all.slots = conv16_blocks_per_head(g, heads, imgs);
+    }
+    int rc;
+    for (int hd = 0; hd < heads; ++hd) {
+        const FusedIn& f = fin[hd];
+        unsigned char* convw = p.split16 ? at<unsigned char>(ws, p.o_convw) + (size_t)hd * CONV_W16_BYTES : nullptr;
+        if (convw && !(c.r.mode_flags & DAGL_FLAG_WEIGHTS_PACKED) && (rc = launch_pack_conv_weight16(c.s, f.g_w, f.th_w, convw))) return rc;
+        if (conv_merged && hd == heads - 1) {
+            ConvHeadSet hs = {};
+            for (int h2 = 0; h2 < heads; ++h2) {
+                hs.x[h2] = fin[h2].x; hs.w[h2] = at<unsigned char>(ws, p.o_convw) + (size_t)h2 * CONV_W16_BYTES;
+                hs.gb[h2] = fin[h2].g_b; hs.tb[h2] = fin[h2].th_b;
+            }
+            hs.imgs = imgs;
+            hs.tiers = tiers_all;
+            if ((rc = launch_conv_pair16_heads(c.s, heads, imgs, g, hs, c.b2p, map_hi, map_lo, clear_stats, clear_stats_words, clear_redo,
+                                               clear_redo_words, c.rt))) return rc;
+            if (thr_heads && !c.thr_in_proj && (rc = launch_thr_bias_heads(c.s, heads, imgs, g, c.thr_all, thr_part))) return rc;
+        }
+        // default path: the key/query map is only ever consumed as split fp16 (project16), so the prologue
+        // writes the hi / lo maps itself and no fp32 copy exists
+        B1Tiers tiers_hd;
+        const bool first = hd == 0;
+        if ((rc = launch_prologue(c.s, imgs, g, f.x, f.g_w, f.g_b, f.th_w, f.th_b, f.thr_w, f.thr_b, f.bias_w, f.bias_b,
+                                  p.split16 ? nullptr : c.b1p + hd * map_f, c.b2p + hd * map_f,
+                                  (thr_heads && !c.thr_in_proj) ? at<float>(ws, p.o_thr) + (size_t)hd * imgs * g.L : nullptr,
+                                  at<float>(ws, p.o_bias) + (size_t)hd * imgs * g.L,
+                                  p.split16 ? map_hi + hd * map_f : nullptr, p.split16 ? map_lo + hd * map_f : nullptr,
+                                  thr_part + (size_t)hd * 8 * imgs * g.L, c.prepared, /*defer_thr_reduce=*/thr_heads,
+                                  first ? clear_stats : nullptr, first ? clear_stats_words : 0,
+                                  first ? clear_redo : nullptr, first ? clear_redo_words : 0, c.rt, convw, conv_merged,
+                                  p.split16 ? &(tiers_hd = B1Tiers{tiers_all.hi2 + hd * map_f, tiers_all.lo2 + hd * map_f, tiers_all.amax, tiers_all.slots}) : nullptr))) return rc;
+    }
+    return DAGL_OK;
+}
+
+// the fc weights packed for the projection (and dagl_ce_forward's key / query map split into fp16 halves)
+static int pack_fc_weights(Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws;
+    const bool packed = (c.r.mode_flags & DAGL_FLAG_WEIGHTS_PACKED) != 0;
+    int rc;
+    if (!p.split16) {
+        DAGL_REQUIRE(c.heads == 1, "dagl: the stage entry point needs the default (screened) scan");
+        if (packed) return DAGL_OK;
+        if ((rc = launch_pack_fc_weight(c.s, c.fc1_w, c.wp1))) return rc;
+        return launch_pack_fc_weight(c.s, c.fc2_w, c.wp2);
+    }
+    uint16_t* wp1h = at<uint16_t>(ws, p.o_wp1h);
+    uint16_t* wp2h = at<uint16_t>(ws, p.o_wp2h);
+    if (!c.fin)                                              // stock-conv entry point: split the padded fp32 map
+        if ((rc = launch_split_map(c.s, (size_t)c.B * g.Hp * g.Wp * CH, c.b1p, at<uint16_t>(ws, p.o_maphi), at<uint16_t>(ws, p.o_maplo),
+                                   c.rt))) return rc;
+    for (int hd = 0; hd < c.heads && !packed; ++hd) {
+        if ((rc = launch_pack_fc_weight16(c.s, c.fin ? c.fin[hd].fc1_w : c.fc1_w, wp1h + (size_t)hd * P16_PACKED_HALFS))) return rc;
+        if ((rc = launch_pack_fc_weight16(c.s, c.fin ? c.fin[hd].fc2_w : c.fc2_w, wp2h + (size_t)hd * P16_PACKED_HALFS))) return rc;
+    }
+    return DAGL_OK;
+}
+
+static int stage_layout(Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g;
+    hipStream_t s = c.s;
+    int rc;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    if (cap == hipStreamCaptureStatusActive) {
+        hipLaunchKernelGGL(retag_kernel, dim3(1), dim3(1), 0, s, c.rt.word,
+                           c.mode == DAGL_MODE_ADAPTIVE ? stat32(c.stats, STAT_VETO) : nullptr, c.rt.tag);
+        DAGL_LAUNCH_CHECK("retag_kernel");
+    }
+    mark(c, 0);
+    if (!c.prepared) DAGL_HIP_TRY(hipMemsetAsync(c.stats + STAT_RANGE, 0, 2 * sizeof(int64_t), s));   // fresh workspace: range, done
+    if (!c.prepared && c.mode == DAGL_MODE_ADAPTIVE) DAGL_HIP_TRY(hipMemsetAsync(c.stats + STAT_VETO, 0, sizeof(int64_t), s));
+    if (p.screen && c.mode != DAGL_MODE_ADAPTIVE && !c.prepared) {
+        // (include/dagl_ce.h DAGL_FLAG_TIGHT_TOPK; forced thresholds -- DAGL_FLAG_TIGHT_TOPK / _SAMPLED_TOPK -- do not read the policy
+        // word; the cookie and the sticky words are kept all the same).  A cold workspace starts with the sampled threshold and a closed
+        // gate -- but maps of up to 16 384 keys (128^2; the 72 x 72 leaf tiles of the tiled driver) START on the tight threshold: there it
+        // costs nothing measurable on synthetic maps (sampling every second key tile of <= 256 is a few steps) and its better threshold
         // saves 12 % on natural-image leaf tiles even when nothing overflows (0.64 against 0.73 ms per batch of 64 tiles,
         // profiles/r04_topk_policy_real_features.log).  The word is kept while the workspace carries this geometry's cookie.
         uint64_t ck = 0x5DA6ull;
-        for (const int v : {B, H, W, mode, k, p.s_splits, p.capseg, p.capseg_tight}) ck = ck * 0x100000001B3ull ^ (uint64_t)(uint32_t)v;
-        hipLaunchKernelGGL(policy_init_kernel, dim3(1), dim3(1), 0, s, stats, (int64_t)(ck | 1ull), g.N <= 16384 ? 1 : 0);
+        for (const int v : {c.B, c.r.H, c.r.W, c.mode, c.k, p.s_splits, p.capseg, p.capseg_tight}) ck = ck * 0x100000001B3ull ^ (uint64_t)(uint32_t)v;
+        hipLaunchKernelGGL(policy_init_kernel, dim3(1), dim3(1), 0, s, c.stats, (int64_t)(ck | 1ull), g.N <= 16384 ? 1 : 0);
         DAGL_LAUNCH_CHECK("policy_init_kernel");
     }
-    if (core) {
-        if ((rc = launch_pad_nhwc(s, B, H, W, b2, b2p))) return rc;
-    } else if (fin) {
-        float* thr_ws = at<float>(ws, p.o_thr);
-        float* bias_ws = at<float>(ws, p.o_bias);
-        const bool thr_heads = (mode != DAGL_MODE_TOPK);
-        const size_t map_f = (size_t)imgs * g.Hp * g.Wp * CH;
-        const bool conv_merged = heads > 1 && p.split16;       // a stage's heads: their g / theta convolutions are ONE launch
-        // the thr / bias heads' partial sums are first read by query_thresholds_kernel, behind the projection: on the split-fp16 path their
-        // blocks ride in the projection's launch (round 5; 13 us of every adaptive-mode call as a launch of their own)
-        if (thr_heads) {
-            for (int h2 = 0; h2 < heads; ++h2) { thr_all.x[h2] = fin[h2].x; thr_all.thr_w[h2] = fin[h2].thr_w; thr_all.bias_w[h2] = fin[h2].bias_w; }
-            thr_all.imgs = imgs;
-            thr_in_proj = p.split16 && thr_bias4_ok(g, thr_all, heads);
-        }
-        // the map's two tiers (B1Tiers): all heads of the call share the slot array, [head][blocks of that head]
-        B1Tiers tiers_all;
-        if (p.split16) {
-            tiers_all.hi2 = at<uint16_t>(ws, p.o_maphi2); tiers_all.lo2 = at<uint16_t>(ws, p.o_maplo2);
-            tiers_all.amax = at<float>(ws, p.o_b1amax); tiers_all.slots = conv16_blocks_per_head(g, heads, imgs);
-        }
-        for (int hd = 0; hd < heads; ++hd) {
-            const FusedIn& f = fin[hd];
-            B1Tiers tiers_hd;
-            unsigned char* convw = p.split16 ? at<unsigned char>(ws, p.o_convw) + (size_t)hd * CONV_W16_BYTES : nullptr;
-            if (convw && !(mode_flags & DAGL_FLAG_WEIGHTS_PACKED) && (rc = launch_pack_conv_weight16(s, f.g_w, f.th_w, convw))) return rc;
-            if (conv_merged && hd == heads - 1) {
-                ConvHeadSet hs = {};
-                for (int h2 = 0; h2 < heads; ++h2) {
-                    hs.x[h2] = fin[h2].x; hs.w[h2] = at<unsigned char>(ws, p.o_convw) + (size_t)h2 * CONV_W16_BYTES;
-                    hs.gb[h2] = fin[h2].g_b; hs.tb[h2] = fin[h2].th_b;
-                }
-                hs.imgs = imgs;
-                hs.tiers = tiers_all;
-                if ((rc = launch_conv_pair16_heads(s, heads, imgs, g, hs, b2p, at<uint16_t>(ws, p.o_maphi), at<uint16_t>(ws, p.o_maplo),
-                                                   prepared ? reinterpret_cast<uint32_t*>(stats) : nullptr, prepared ? 8 : 0,
-                                                   (prepared && p.screen) ? reinterpret_cast<uint32_t*>(at<int32_t>(ws, p.o_redo)) : nullptr,
-                                                   (prepared && p.screen) ? B * n_qgroups : 0, rt))) return rc;
-                if (thr_heads && !thr_in_proj) {
-                    ThrHeadSet th = {};
-                    for (int h2 = 0; h2 < heads; ++h2) { th.x[h2] = fin[h2].x; th.thr_w[h2] = fin[h2].thr_w; th.bias_w[h2] = fin[h2].bias_w; }
-                    th.imgs = imgs;
-                    if ((rc = launch_thr_bias_heads(s, heads, imgs, g, th, at<float>(ws, p.o_thrpart)))) return rc;
-                }
-            }
-            // default path: the key/query map is only ever consumed as split fp16 (project16), so the prologue
-            // writes the hi / lo maps itself and no fp32 copy exists
-            if ((rc = launch_prologue(s, imgs, g, f.x, f.g_w, f.g_b, f.th_w, f.th_b, f.thr_w, f.thr_b, f.bias_w, f.bias_b,
-                                      p.split16 ? nullptr : b1p + hd * map_f, b2p + hd * map_f,
-                                      (thr_heads && !thr_in_proj) ? thr_ws + (size_t)hd * imgs * g.L : nullptr,
-                                      bias_ws + (size_t)hd * imgs * g.L,
-                                      p.split16 ? at<uint16_t>(ws, p.o_maphi) + hd * map_f : nullptr,
-                                      p.split16 ? at<uint16_t>(ws, p.o_maplo) + hd * map_f : nullptr,
-                                      at<float>(ws, p.o_thrpart) + (size_t)hd * 8 * imgs * g.L,
-                                      prepared, /*defer_thr_reduce=*/thr_heads,
-                                      (prepared && hd == 0) ? reinterpret_cast<uint32_t*>(stats) : nullptr,
-                                      (prepared && hd == 0) ? 8 : 0,
-                                      (prepared && hd == 0 && p.screen) ? reinterpret_cast<uint32_t*>(at<int32_t>(ws, p.o_redo)) : nullptr,
-                                      (prepared && hd == 0 && p.screen) ? B * n_qgroups : 0, rt, convw, conv_merged,
-                                      p.split16 ? &(tiers_hd = B1Tiers{tiers_all.hi2 + hd * map_f, tiers_all.lo2 + hd * map_f, tiers_all.amax, tiers_all.slots}) : nullptr))) return rc;
-        }
-        thr = thr_ws; bias = bias_ws;
+    if (c.core) {                       // (nothing to pack: the projections were done by the caller, under autograd)
+        if ((rc = launch_pad_nhwc(s, c.B, g.H, g.W, c.core->b2, c.b2p))) return rc;
     } else {
-        if ((rc = launch_pad_nhwc(s, B, H, W, b1, b1p))) return rc;
-        if ((rc = launch_pad_nhwc(s, B, H, W, b2, b2p))) return rc;
-    }
-    uint16_t *map_hi = nullptr, *map_lo = nullptr, *wp1h = nullptr, *wp2h = nullptr;
-    if (core) {
-        // nothing to pack: the projections were done by the caller (under autograd)
-    } else if (p.split16) {
-        map_hi = at<uint16_t>(ws, p.o_maphi); map_lo = at<uint16_t>(ws, p.o_maplo);
-        wp1h = at<uint16_t>(ws, p.o_wp1h); wp2h = at<uint16_t>(ws, p.o_wp2h);
-        if (!fin)                                                // stock-conv entry point: split the padded fp32 map
-            if ((rc = launch_split_map(s, (size_t)B * g.Hp * g.Wp * CH, b1p, map_hi, map_lo, rt))) return rc;
-        for (int hd = 0; hd < heads && !(mode_flags & DAGL_FLAG_WEIGHTS_PACKED); ++hd) {
-            if ((rc = launch_pack_fc_weight16(s, fin ? fin[hd].fc1_w : fc1_w, wp1h + (size_t)hd * P16_PACKED_HALFS))) return rc;
-            if ((rc = launch_pack_fc_weight16(s, fin ? fin[hd].fc2_w : fc2_w, wp2h + (size_t)hd * P16_PACKED_HALFS))) return rc;
+        if (c.fin) {
+            if ((rc = prologue_fused(c))) return rc;
+        } else {
+            if ((rc = launch_pad_nhwc(s, c.B, g.H, g.W, c.r.maps->b1, c.b1p))) return rc;
+            if ((rc = launch_pad_nhwc(s, c.B, g.H, g.W, c.r.maps->b2, c.b2p))) return rc;
         }
-    } else {
-        DAGL_REQUIRE(heads == 1, "dagl: the stage entry point needs the default (screened) scan");
-        if (!(mode_flags & DAGL_FLAG_WEIGHTS_PACKED)) {
-            if ((rc = launch_pack_fc_weight(s, fc1_w, wp1))) return rc;
-            if ((rc = launch_pack_fc_weight(s, fc2_w, wp2))) return rc;
-        }
-    }
-    const int q_tiled = (p.screen && p.split16 && !core) ? 1 : 0;   // the projection writes the bf16 queries in the screen's fragment order
-    // a call that goes straight to the streamed dense formulation (DAGL_FLAG_DENSE_HINT): the projection writes the split-fp16
-    // features dense.hip consumes as well -- no separate splitting pass over the fp32 rows
-    Split16Out split_out;
-    const Split16Out* split_p = nullptr;
-    if (!core && p.split16 && p.screen && mode == DAGL_MODE_ADAPTIVE && (mode_flags & DAGL_FLAG_DENSE_HINT)) {
-        size_t off_dn = p.o_end;
-        const size_t o_dn = carve(off_dn, dense_workspace_bytes(B, g));
-        if (ws_bytes >= off_dn) { split_out = dense_split_buffers(at<char>(ws, o_dn), B, g); split_p = &split_out; }
+        if ((rc = pack_fc_weights(c))) return rc;
     }
     ZeroList zl;
-    if (split_p) dense_guard_rows(zl, B, g, split_out);
-    if (prepared && split_p) { if ((rc = launch_zero_regions(s, zl))) return rc; }
-    if (!prepared) {   // rows past the last patch (partial tile + guard tile) are streamed by the scans: keep them zero
+    if (c.split_p) dense_guard_rows(zl, c.B, g, c.split_out);
+    if (c.prepared && c.split_p) { if ((rc = launch_zero_regions(s, zl))) return rc; }
+    if (!c.prepared) {   // rows past the last patch (partial tile + guard tile) are streamed by the scans: keep them zero
         const int rx = feat_rows(g.N), rq = feat_rows(g.L);
         const int hx = feat_rows_h(g.N), hq = feat_rows_h(g.L);
-        zl.add(X + (size_t)g.N * DS, (size_t)(rx - g.N) * DS * sizeof(float), B, (size_t)rx * DS * sizeof(float));
-        zl.add(Wq + (size_t)g.L * DS, (size_t)(rq - g.L) * DS * sizeof(float), B, (size_t)rq * DS * sizeof(float));
+        zl.add(c.X + (size_t)g.N * DS, (size_t)(rx - g.N) * DS * sizeof(float), c.B, (size_t)rx * DS * sizeof(float));
+        zl.add(c.Wq + (size_t)g.L * DS, (size_t)(rq - g.L) * DS * sizeof(float), c.B, (size_t)rq * DS * sizeof(float));
         if (p.screen) {
-            zl.add(Xh + (size_t)g.N * DSH, (size_t)(hx - g.N) * DSH * sizeof(uint16_t), B, (size_t)hx * DSH * sizeof(uint16_t));
+            zl.add(c.Xh + (size_t)g.N * DSH, (size_t)(hx - g.N) * DSH * sizeof(uint16_t), c.B, (size_t)hx * DSH * sizeof(uint16_t));
             // (from the last PARTIAL 32-query tile on: in the fragment order its unused rows sit between the used ones)
             const int lq = g.L & ~31;
-            zl.add(Wqh + (size_t)lq * DSH, (size_t)(hq - lq) * DSH * sizeof(uint16_t), B, (size_t)hq * DSH * sizeof(uint16_t));
+            zl.add(c.Wqh + (size_t)lq * DSH, (size_t)(hq - lq) * DSH * sizeof(uint16_t), c.B, (size_t)hq * DSH * sizeof(uint16_t));
         }
-        zl.add(colsum, align_up((size_t)B * DS * sizeof(double), 16));
-        zl.add(stats, 4 * sizeof(int64_t));
-        if (p.screen) zl.add(at<int32_t>(ws, p.o_redo), align_up((size_t)B * n_qgroups * sizeof(int32_t), 16));
+        zl.add(c.colsum, align_up((size_t)c.B * DS * sizeof(double), 16));
+        zl.add(c.stats, STAT_N_COUNTERS * sizeof(int64_t));
+        if (p.screen) zl.add(c.redo, align_up((size_t)c.B * c.n_qgroups * sizeof(int32_t), 16));
         if ((rc = launch_zero_regions(s, zl))) return rc;
     }
-
-    // ---- stage 1: both projections, one launch -------------------------------------------------------------
-    prof_mark(prof, s, 1);
-    if (core) {
-        if ((rc = launch_rows_to_feat(s, B, g.N, core->x_rows, X, Xh, rt))) return rc;
-        if ((rc = launch_rows_to_feat(s, B, g.L, core->wq_rows, Wq, Wqh, rt))) return rc;
-        if (mode != DAGL_MODE_TOPK)
-            if ((rc = launch_colsum_rows(s, B, g.N, core->x_rows, colsum))) return rc;
-    } else if (p.split16) {
-        B1Tiers tiers_fused;               // (the fused entry points: conv_pair16_kernel wrote both tiers; dagl_ce_forward's split_map_kernel only the fine one)
-        if (fin) {
-            tiers_fused.hi2 = at<uint16_t>(ws, p.o_maphi2); tiers_fused.lo2 = at<uint16_t>(ws, p.o_maplo2);
-            tiers_fused.amax = at<float>(ws, p.o_b1amax); tiers_fused.slots = conv16_blocks_per_head(g, heads, B / heads);
-        }
-        const float* b1s[4]; const float* b2s[4];
-        for (int hd = 0; hd < 4; ++hd) {
-            b1s[hd] = (fin && hd < heads) ? fin[hd].fc1_b : fc1_b;
-            b2s[hd] = (fin && hd < heads) ? fin[hd].fc2_b : fc2_b;
-        }
-        if ((rc = launch_project16(s, B, g, 3, map_hi, map_lo, wp2h, b2s, X, (mode == DAGL_MODE_TOPK) ? nullptr : colsum,
-                                   at<float>(ws, p.o_colpart), wp1h, b1s,
-                                   Wq, Xh, Wqh, heads, rt, q_tiled, split_p,
-                                   thr_in_proj ? &thr_all : nullptr, thr_in_proj ? B : 0, thr_in_proj ? at<float>(ws, p.o_thrpart) : nullptr,
-                                   fin ? &tiers_fused : nullptr))) return rc;
-    } else {
-        if ((rc = launch_project(s, B, g, 3, b1p, wp2, fc2_b, X, colsum, wp1, fc1_b, Wq, Xh, Wqh, rt))) return rc;
-    }
-
-    // ---- stage 2: adaptive thresholds ----------------------------------------------------------------------
-    bool fused_theta = false;
-    prof_mark(prof, s, 2);
-    SelectArgs sa;
-    memset(&sa, 0, sizeof(sa));
-    sa.B = B; sa.L = g.L; sa.N = g.N; sa.W = g.W; sa.wq = Wq; sa.x = X; sa.mode = mode; sa.k = k;
-    sa.splits = p.splits; sa.tiles_per_split = p.tiles_per_split;
-    EdgeArgs ea;
-    memset(&ea, 0, sizeof(ea));
-    ea.B = B; ea.L = g.L; ea.N = g.N; ea.mode = mode; ea.k = k; ea.splits = p.splits;
-    ea.nb_idx = nbidx; ea.nb_wgt = nbwgt; ea.nb_cnt = nbcnt; ea.width = p.width;
-    ea.nb_s = core ? core->nb_s : nullptr;
-    AggArgs ag;
-    memset(&ag, 0, sizeof(ag));
-    ag.B = B; ag.g = g; ag.b2p = b2p; ag.nb_idx = nbidx; ag.nb_wgt = nbwgt; ag.nb_cnt = nbcnt; ag.width = p.width;
-    ag.agg = agg;
-    if (mode != DAGL_MODE_TOPK) {
-        ThrFuse tf;
-        if (fin) {                                   // finish the thr / bias heads here (their partial sums are per head)
-            tf.part = at<float>(ws, p.o_thrpart); tf.imgs_per_head = imgs;
-            for (int hd = 0; hd < heads; ++hd) { tf.thr_b[hd] = fin[hd].thr_b; tf.bias_b[hd] = fin[hd].bias_b; }
-            tf.thr_out = at<float>(ws, p.o_thr); tf.bias_out = at<float>(ws, p.o_bias);
-        } else {
-            tf.bias_out = const_cast<float*>(bias);   // read only in this case
-        }
-        fused_theta = p.screen && mode == DAGL_MODE_ADAPTIVE;
-        if (fused_theta) tf.theta_out = at<float>(ws, p.o_theta);
-        if (p.screen && mode == DAGL_MODE_ADAPTIVE) tf.zero_out = at<float>(ws, p.o_traw);     // (run_dense's sampled pass takes maxima into it)
-        if ((rc = launch_query_thresholds(s, B, g.L, g.N, Wq, colsum, thr, mt, core ? core->mu : nullptr, &tf))) return rc;
-        sa.mt = mt; sa.bs = bias; ea.mt = mt; ea.bs = bias;
-    }
-
-    bool agg_done = false;           // the gather + weighted sum over the lists ran inside the overflow launches (adaptive, screened)
-    bool ovf_active = false;         // set once the refine kernel has listed its overflowed queries (adaptive, screened)
-    // the statistics read-back of the adaptive modes also carries the range word: a call that left the split-fp16 range is
-    // re-run on the fp32 path right here (same arguments, DAGL_FLAG_EXACT_SCAN); without a read-back (top-k modes) the
-    // poisoned output and dagl_ce_range_check report it
-    auto rerun_exact = [&]() -> int {
-        if (mode_flags & DAGL_FLAG_EXACT_SCAN) {      // already the fp32 path: the word was set by a NON-FINITE feature (round 6), the output is
-            if (info) info->range_fallback = 1;       // NaN-filled as the reference's would be; nothing to re-run
-            return DAGL_OK;
-        }
-        if (heads > 1) {            // stage entry point: no fp32 form of the four-head launch set; hand the call back (per-head path)
-            if (info) { info->required_bytes = -1; info->range_fallback = 1; }
-            set_error("dagl_ces_stage_forward: an operand left the split-fp16 range: use the per-head entry point");
-            return DAGL_ERR_WORKSPACE;
-        }
-        if (info) info->range_fallback = 1;
-        const int rc2 = ce_forward_impl(s, B, H, W, b1, b2, fin ? nullptr : thr, fin ? nullptr : bias, fc1_w, fc1_b, fc2_w, fc2_b,
-                                        (mode_flags | DAGL_FLAG_EXACT_SCAN) & ~(DAGL_FLAG_WEIGHTS_PACKED | DAGL_FLAG_DENSE_HINT), k, out,
-                                        ws, ws_bytes, info, dbg_deg, dbg_rowsum, dbg_agg, nullptr, fin, heads, nullptr);
-        if (info) info->range_fallback = 1;
-        return rc2;
-    };
-    // the per-query redo gathers one value patch per edge of a flagged row (~1 ns each), the dense formulation costs ~9 ps per
-    // (query, key) PAIR whatever the mask: a call whose flagged rows hold more than 1/96 of all pairs goes dense
-    const long long ovf_edge_limit = (long long)((double)BL * (double)g.N / 96.0);
-    auto overflow_args = [&]() {
-        OvfArgs oa;
-        memset(&oa, 0, sizeof(oa));
-        oa.B = B; oa.g = g; oa.x = X; oa.rows_x = feat_rows(g.N);
-        oa.mt = mt; oa.bs = bias; oa.b2p = b2p; oa.list = at<int32_t>(ws, p.o_ovflist);
-        oa.count = reinterpret_cast<const int32_t*>(stats + 3); oa.cap = p.ovf_cap;
-        oa.qrows = at<float>(ws, p.o_ovfq); oa.scores = at<float>(ws, p.o_ovfscores); oa.ldn = (g.N + 31) / 32 * 32; oa.part = at<float>(ws, p.o_ovfpart);
-        oa.agg = agg; oa.nb_cnt = nbcnt; oa.dbg_deg = dbg_deg; oa.dbg_rowsum = dbg_rowsum;
-        oa.edges_run = stats;            // (stats[0]: zero since the start of the call, overwritten with the total by the statistics block)
-        oa.flagged_edges = stats + 7; oa.edge_limit = ovf_edge_limit;
-        return oa;
-    };
-    auto run_tail = [&](const AggArgs& ag2) -> int {
-        int r;
-        if (dbg_deg || dbg_rowsum)
-            if ((r = launch_row_stats(s, BL, ag2.nb_wgt, ag2.nb_cnt, ag2.row_off, ag2.width, dbg_deg, dbg_rowsum))) return r;
-        prof_mark(prof, s, 6);
-        // short fixed-width lists and nobody asking for the aggregated rows: gather, weighted sum and fold in one kernel
-        if (mode != DAGL_MODE_ADAPTIVE && ag2.row_off == nullptr && !ovf_active && !dbg_agg && !core) {
-            if ((r = launch_aggregate_fold(s, ag2, out, heads, rt))) return r;
-            prof_mark(prof, s, 7);                              // (the whole tail is booked on the gather stage)
-            prof_mark(prof, s, 8);
-            return DAGL_OK;
-        }
-        // (the few queries whose neighbourhood overflowed the lists are redone one by one, dense rows, overflow.hip; the list gather
-        // skips them.  A call that does not wait had both done in the overflow launches; one that waits has its statistics on their
-        // way to the host by now and queues the gathers here, under the round trip)
-        if (!agg_done) {
-            if ((r = launch_aggregate_direct(s, ag2))) return r;
-            if (ovf_active) {           // (a call that waited for its verdict: the flagged rows' gathers behind the read-back)
-                OvfArgs oa = overflow_args();
-                oa.edges_run = nullptr;                     // (their edges are known: ovf_attend_kernel looks at flagged_edges)
-                if ((r = launch_overflow_apply(s, oa))) return r;
-            }
-        }
-        prof_mark(prof, s, 7);
-        if (dbg_agg) DAGL_HIP_TRY(hipMemcpyAsync(dbg_agg, agg, BL * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if ((r = launch_fold(s, B, g, agg, out, heads, rt))) return r;
-        prof_mark(prof, s, 8);
-        return DAGL_OK;
-    };
-
-    if (p.wide) {
-        // fixed-k neighbourhoods wider than the lists: scores, k-th largest, mask, softmax and weighted sum row by row
-        prof_mark(prof, s, 3); prof_mark(prof, s, 4); prof_mark(prof, s, 5);
-        if (heads > 1) { set_error("dagl_ces_stage_forward: k=%d > %d: use the per-head entry point", k, DAGL_MAX_TOPK); return DAGL_ERR_UNSUPPORTED; }
-        if ((rc = launch_topk_wide(s, B, g, mode, p.k, Wq, X, mt, bias, b2p, at<char>(ws, p.o_wide), agg, deg, dbg_rowsum, rt))) return rc;
-        prof_mark(prof, s, 6);
-        if (dbg_deg) DAGL_HIP_TRY(hipMemcpyAsync(dbg_deg, deg, BL * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        if (dbg_agg) DAGL_HIP_TRY(hipMemcpyAsync(dbg_agg, agg, BL * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-        prof_mark(prof, s, 7);
-        if ((rc = launch_fold(s, B, g, agg, out, heads, rt))) return rc;
-        prof_mark(prof, s, 8);
-        if (info) {
-            if ((rc = launch_degree_stats(s, BL, deg, stats))) return rc;
-            int64_t hs[5] = {0, 0, 0, 0, 0};
-            if ((rc = read_back(s, stats, 5, hs))) return rc;
-            if (rt.word != nullptr && (int32_t)hs[4] == rt.tag) return rerun_exact();
-            info->path = 6; info->total_edges = hs[0]; info->max_degree = (int32_t)hs[1];
-        }
-        if (prof && prof->n_calls < prof->max_calls) ++prof->n_calls;
-        return DAGL_OK;
-    }
-
-    // ---- stages 3-5: neighbour selection + edge softmax ------------------------------------------------------
-    bool need_exact = !p.screen;
-    int32_t* redo = nullptr;
-    if (p.screen) {
-        ScreenArgs sc;
-        memset(&sc, 0, sizeof(sc));
-        sc.B = B; sc.L = g.L; sc.N = g.N; sc.mode = mode; sc.wqh = Wqh; sc.xh = Xh; sc.q_tiled = q_tiled;
-        sc.rows_qh = feat_rows_h(g.L); sc.rows_xh = feat_rows_h(g.N);
-        sc.splits = p.s_splits; sc.steps_per_split = p.s_steps_per_split; sc.n_steps = p.s_steps; sc.sample = p.s_sample; sc.qblock = p.s_qblock;
-        sc.gmax = at<float>(ws, p.o_gmax); sc.gkeep = p.s_gkeep; sc.theta = at<float>(ws, p.o_theta); sc.mt = mt; sc.bs = bias;
-        sc.capseg = p.capseg; sc.cand = at<int2>(ws, p.o_scand);
-        if (mode != DAGL_MODE_ADAPTIVE) { sc.spill = at<int2>(ws, p.o_spill); sc.spill_cnt = at<unsigned>(ws, p.o_spillcnt); }
-        if (topk_policy) { sc.policy = policy_w; sc.sample_tight = p.s_sample_tight; sc.capseg_tight = p.capseg_tight; }
-        redo = at<int32_t>(ws, p.o_redo);
-#ifdef DAGL_ABLATION
-        { static const int var = [] { const char* e = getenv("DAGL_SCREEN_VARIANT"); return e ? atoi(e) : 0; }(); sc.variant = var; }
-#endif
-        // most queries keep more keys than the screen has candidate slots for: the dense regime.  Lists are pointless
-        // there; stream the dense formulation instead (dense.hip).  Reached after the screen found out, or directly when
-        // the caller passes DAGL_FLAG_DENSE_HINT (its previous call on this module ended here): always correct, only
-        // slower than the lists when the neighbourhoods are in fact sparse.
-        auto run_dense = [&](bool features_split) -> int {
-            size_t off = p.o_end;
-            const size_t o_dn = carve(off, dense_workspace_bytes(B, g));
-            if (info) { info->required_bytes = (int64_t)off; info->path = 4; }
-            if (core && !core->lse) {
-                if (info) info->required_bytes = -1;
-                set_error("dagl_ce_core_forward: dense neighbourhoods (most queries keep more than %d keys) do not fit fixed-width lists: "
-                          "use dagl_ce_core_dense_forward", DAGL_FAST_CAP);
-                return DAGL_ERR_UNSUPPORTED;
-            }
-            if (ws_bytes < off) {
-                set_error("dagl_ce_forward: dense neighbourhoods need workspace %zu B, have %zu B", off, ws_bytes);
-                return DAGL_ERR_WORKSPACE;
-            }
-            // the softmax's shift, known up front: every row's largest score, exactly -- a top-1 screen (sampled pass -> theta = the
-            // largest sampled S~ less the band -> filter pass) and the exact scores of its few candidates (rowmax_exact_kernel).  Up to
-            // round 4: an upper bound from one full bf16 scan, whose 1.6 % became > 18 units of a logit beyond ~580 and sent whole
-            // blocks through dense_attend_kernel a second time (every block of bench.py's default map: 1.52 ms for 0.81)
-            ScreenArgs s1 = sc;
-            s1.mode = DAGL_MODE_TOPK; s1.mt = nullptr; s1.bs = nullptr; s1.policy = nullptr; s1.gate = nullptr;
-            s1.spill = nullptr; s1.spill_cnt = nullptr; s1.seg_max = 1;      // (no spill: a row with more candidates than slots keeps its upper bound)
-            s1.theta_max = at<int>(ws, p.o_traw); s1.theta = at<float>(ws, p.o_traw);     // (zeroed by query_thresholds_kernel)
-            if ((rc = launch_screen(s, s1, 0))) return rc;
-            if ((rc = launch_screen(s, s1, 1))) return rc;
-            float* smax = at<float>(ws, p.o_smax);
-            RefineArgs r1;
-            memset(&r1, 0, sizeof(r1));
-            r1.B = B; r1.L = g.L; r1.N = g.N; r1.mode = DAGL_MODE_TOPK; r1.k = 1; r1.splits = p.s_splits; r1.capseg = p.capseg;
-            r1.wq = Wq; r1.x = X; r1.rows_q = feat_rows(g.L); r1.rows_x = feat_rows(g.N);
-            r1.cand = s1.cand; r1.theta = s1.theta; r1.mt = mt; r1.bs = bias;
-            if ((rc = launch_rowmax_exact(s, r1, smax))) return rc;
-            prof_mark(prof, s, 6);          // (stage "gather" of a dense call = value-map split + dense_attend_kernel + combine)
-            if ((rc = launch_dense_attend(s, B, g, Wq, X, mt, bias, smax, b2p, at<char>(ws, o_dn), agg, dbg_deg, dbg_rowsum, stats, rt,
-                                          core ? core->lse : nullptr, features_split, info != nullptr))) return rc;
-            prof_mark(prof, s, 7);
-            if (dbg_agg) DAGL_HIP_TRY(hipMemcpyAsync(dbg_agg, agg, BL * P * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if ((rc = launch_fold(s, B, g, agg, out, heads, rt))) return rc;
-            prof_mark(prof, s, 8);
-            if (info) {
-                int64_t hd[DENSE_RERUN_STAT + 1] = {0};
-                if ((rc = read_back(s, stats, DENSE_RERUN_STAT + 1, hd))) return rc;
-                if (rt.word != nullptr && (int32_t)hd[4] == rt.tag) {
-                    if (core) { info->range_fallback = 1; return DAGL_OK; }      // (output NaN-filled; dagl_ce_core_dense_forward re-runs the GEMM form)
-                    return rerun_exact();
-                }
-                info->total_edges = hd[0]; info->max_degree = (int32_t)hd[1];
-                info->redone_queries = hd[2];                       // queries whose degree exceeds the lists' width
-                info->dense_rerun_blocks = (int32_t)hd[DENSE_RERUN_STAT];       // blocks of 64 queries dense_attend_kernel ran a second time
-            }
-            if (prof && prof->n_calls < prof->max_calls) ++prof->n_calls;
-            return DAGL_OK;
-        };
-        if (mode == DAGL_MODE_ADAPTIVE && (mode_flags & DAGL_FLAG_DENSE_HINT) && (!core || core->lse)) {
-            prof_mark(prof, s, 3); prof_mark(prof, s, 4); prof_mark(prof, s, 5);
-            return run_dense(split_p != nullptr);
-        }
-        prof_mark(prof, s, 3);
-        if (mode != DAGL_MODE_ADAPTIVE) {                       // top-k threshold from the sampling pass
-            if ((rc = launch_screen(s, sc, 0))) return rc;
-            if ((rc = launch_screen_theta(s, (int)BL, p.s_splits * 2 * p.s_gkeep, k, sc.gmax, at<float>(ws, p.o_theta), nullptr, sc.spill_cnt))) return rc;
-        }
-        if (mode != DAGL_MODE_TOPK && !fused_theta)             // adaptive threshold; the intersection mode takes the larger
-            if ((rc = launch_adaptive_theta(s, BL, mt, bias, at<float>(ws, p.o_theta), mode == DAGL_MODE_ADAPTIVE_TOPK))) return rc;
-        prof_mark(prof, s, 4);
-        if ((rc = launch_screen(s, sc, 1))) return rc;
-        prof_mark(prof, s, 5);
-        RefineArgs ra;
-        memset(&ra, 0, sizeof(ra));
-        ra.B = B; ra.L = g.L; ra.N = g.N; ra.mode = mode; ra.k = k; ra.splits = p.s_splits; ra.capseg = p.capseg;
-        ra.width = p.width; ra.wq = Wq; ra.x = X; ra.rows_q = feat_rows(g.L); ra.rows_x = feat_rows(g.N);
-        ra.mt = mt; ra.bs = bias; ra.cand = sc.cand; ra.theta = sc.theta; ra.spill = sc.spill; ra.spill_cnt = sc.spill_cnt;
-        ra.nb_idx = nbidx; ra.nb_wgt = nbwgt; ra.nb_cnt = nbcnt; ra.redo_flags = redo; ra.n_qgroups_exact = n_qgroups;
-        ra.stats = stats; ra.nb_s = core ? core->nb_s : nullptr;
-        if (p.ovf_cap > 0) {
-            ra.ovf_list = at<int32_t>(ws, p.o_ovflist); ra.ovf_count = reinterpret_cast<int32_t*>(stats + 3); ra.ovf_cap = p.ovf_cap;
-            ra.ovf_qrows = at<float>(ws, p.o_ovfq);
-            ra.heavy_list = at<int32_t>(ws, p.o_heavy); ra.heavy_count = reinterpret_cast<int32_t*>(stats + 3) + 1;   // (cleared with the counters)
-            ovf_active = true;
-        }
-        if (topk_policy) { ra.policy = policy_w; ra.capseg_tight = p.capseg_tight; }
-        if ((rc = launch_refine(s, ra))) return rc;
-        if (topk_policy && !prepared) {
-            // cold workspace: did the sampled threshold overflow most queries' slots (natural-image features)?  Then the policy word
-            // flips here and sampling, threshold, filter and refine run once more, tight, in this very call -- four launches that
-            // exit at once otherwise -- instead of every query group taking the fp32 redo pass (2.7 ms at 256^2)
-            if ((rc = launch_topk_policy(s, stats, policy_w, gate_w, redo, (int)(B * n_qgroups), (long long)BL))) return rc;
-            ScreenArgs sc2 = sc; sc2.gate = gate_w;
-            if ((rc = launch_screen(s, sc2, 0))) return rc;
-            if ((rc = launch_screen_theta(s, (int)BL, p.s_splits * 2 * p.s_gkeep, k, sc2.gmax, at<float>(ws, p.o_theta), gate_w, sc2.spill_cnt))) return rc;
-            // (the intersection mode takes the larger of the two thresholds: max(adaptive, theta) is idempotent, so the ungated
-            // kernel is harmless when the re-run did not run)
-            if (mode != DAGL_MODE_TOPK && !fused_theta)
-                if ((rc = launch_adaptive_theta(s, BL, mt, bias, at<float>(ws, p.o_theta), true))) return rc;
-            if ((rc = launch_screen(s, sc2, 1))) return rc;
-            RefineArgs ra2 = ra; ra2.gate = gate_w;
-            if ((rc = launch_refine(s, ra2))) return rc;
-        }
-        if (info) info->path = 3;
-        if (mode == DAGL_MODE_ADAPTIVE) {
-            // Dense neighbourhoods need host-side CSR sizing, so the verdict must be read back.  Everything it consists of
-            // is known once the flagged queries' chunk statistics exist (their true degrees): the copy is queued there,
-            // the optimistic gather, the flagged rows' weighted sums and the fold behind it, and the host waits for the
-            // copy alone -- the device works through the round trip and through the caller's next launches.
-            // DAGL_FLAG_NO_WAIT: the verdict is formed on the device, the call returns without reading it (no host round trip:
-            // the adaptive forward can be captured into a HIP graph); an unserved call is NaN-filled, never wrong
-            const bool no_wait = (mode_flags & DAGL_FLAG_NO_WAIT) && ovf_active && !dbg_deg && !dbg_rowsum && !dbg_agg && !core && heads == 1;
-            if (no_wait) {
-                if (rt.tag == 0) rt.tag = next_call_tag();
-                rt.veto = reinterpret_cast<const int32_t*>(stats + 8);
-            }
-            if (ovf_active) {           // the flagged rows redone (three launches that exit at once when there are none) + the call's statistics
-                const OvfArgs oa = overflow_args();
-                // (a call that does not wait shares the scores' launch with the gather over the lists; one that waits keeps the gather
-                // behind the read-back: the host round trip runs under it)
-                if ((rc = launch_overflow_rows(s, oa, no_wait ? &ag : nullptr, BL, stats, no_wait ? reinterpret_cast<int32_t*>(stats + 8) : nullptr,
-                                               rt.tag))) return rc;
-                agg_done = no_wait;
-            } else {
-                if ((rc = launch_degree_stats(s, BL, nbcnt, stats))) return rc;
-            }
-            if (no_wait) {
-                if ((rc = run_tail(ag))) return rc;
-                if (prof && prof->n_calls < prof->max_calls) ++prof->n_calls;
-                return DAGL_OK;                                  // info: path 3, statistics not read (-1)
-            }
-            bool pending = false;
-            if ((rc = read_back_begin(s, stats, 8, &pending))) return rc;
-            if ((rc = run_tail(ag))) return rc;
-            int64_t hs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            if ((rc = read_back_end(s, stats, 8, pending, hs))) return rc;
-            if (rt.word != nullptr && (int32_t)hs[4] == rt.tag) {
-                if (core) { if (info) info->range_fallback = 1; return DAGL_OK; }   // (training entry point: non-finite features; out is NaN-filled)
-                return rerun_exact();
-            }
-            if (info) info->redone_queries = hs[2];
-            // most queries overflow, or the flagged rows are too heavy to redo one by one (the attend kernels saw the same
-            // word and left them alone): dense regime
-            const bool heavy_rows = ovf_active && hs[2] > 0 && hs[2] <= p.ovf_cap && hs[7] > ovf_edge_limit;
-            const bool mostly = hs[2] * 2 > (int64_t)BL || heavy_rows;
-            if (hs[2] == 0 || (!mostly && ovf_active && hs[2] <= p.ovf_cap)) {   // (few overflowed queries: redone in-stream)
-                if (info) { info->total_edges = hs[0]; info->max_degree = (int32_t)hs[1]; }
-                if (prof && prof->n_calls < prof->max_calls) ++prof->n_calls;
-                return DAGL_OK;
-            }
-            ovf_active = false; agg_done = false;
-            if (mostly) return run_dense(false);
-            need_exact = true;                                   // redo everything with the fp32 scan (CSR capable)
-        } else {
-            // top-k modes: query groups whose candidate slots overflowed are redone by the fp32 scan below; it
-            // exits at once for every other group, so no host round trip is needed
-            sa.run_flags = redo; ea.run_flags = redo; sa.run_count = stats + 2; ea.run_count = stats + 2;
-            need_exact = true;
-            if (info && (dbg_deg || dbg_rowsum || dbg_agg)) {        // debug entry point: report the overflow count
-                int64_t hs[4] = {0, 0, 0, 0};
-                if ((rc = read_back(s, stats, 4, hs))) return rc;
-                info->redone_queries = hs[2];
-            }
-        }
-    } else {
-        prof_mark(prof, s, 3);
-        prof_mark(prof, s, 4);
-    }
-
-    if (need_exact) {
-        if (mode == DAGL_MODE_ADAPTIVE) {
-            int32_t* lidx = at<int32_t>(ws, p.o_lidx);
-            float* lval = at<float>(ws, p.o_lval);
-            DAGL_HIP_TRY(hipMemsetAsync(cnt, 0, BL * sizeof(int32_t), s));
-            sa.cnt = cnt; sa.seg_cnt = segcnt; sa.list_idx = lidx; sa.list_val = lval;
-            if ((rc = launch_score_select(s, sa, 0))) return rc;
-            if (!p.screen) prof_mark(prof, s, 5);
-            if ((rc = launch_row_degree(s, (int)BL, p.splits * 2, segcnt, segrel, deg, stats))) return rc;
-            int64_t hstats[2] = {0, 0};
-            if ((rc = read_back(s, stats, 2, hstats))) return rc;
-            if (info) { info->total_edges = hstats[0]; info->max_degree = (int32_t)hstats[1]; info->path = 0; }
-            if (hstats[1] <= DAGL_FAST_CAP) {
-                ea.cnt = deg; ea.list_idx = lidx; ea.list_val = lval; ea.row_off = nullptr;
-                if ((rc = launch_edge_softmax(s, ea))) return rc;
-            } else {
-                // two-pass CSR: exact degrees are known, refill deterministically at per-lane cursors
-                size_t off = p.o_end;
-                const size_t e = (size_t)hstats[0];
-                const size_t o_ci = carve(off, e * sizeof(int32_t));
-                const size_t o_cv = carve(off, e * sizeof(float));
-                const size_t o_ni = carve(off, e * sizeof(int32_t));
-                const size_t o_nw = carve(off, e * sizeof(float));
-                if (info) { info->required_bytes = (int64_t)off; info->path = 1; }
-                if (core) {
-                    if (info) info->required_bytes = -1;
-                    set_error("dagl_ce_core_forward: dense neighbourhoods (max degree %lld > %d) do not fit fixed-width lists: "
-                              "use dagl_ce_core_dense_forward", (long long)hstats[1], DAGL_FAST_CAP);
-                    return DAGL_ERR_UNSUPPORTED;
-                }
-                if (ws_bytes < off) {
-                    set_error("dagl_ce_forward: dense neighbourhoods (max degree %lld, %lld edges) need workspace %zu B, have %zu B",
-                              (long long)hstats[1], (long long)hstats[0], off, ws_bytes);
-                    return DAGL_ERR_WORKSPACE;
-                }
-                if ((rc = launch_row_scan(s, (int)BL, deg, rowoff))) return rc;
-                sa.list_idx = at<int32_t>(ws, o_ci); sa.list_val = at<float>(ws, o_cv); sa.seg_rel = segrel; sa.row_off = rowoff;
-                if ((rc = launch_score_select(s, sa, 1))) return rc;
-                ea.cnt = deg; ea.list_idx = sa.list_idx; ea.list_val = sa.list_val; ea.row_off = rowoff;
-                ea.nb_idx = at<int32_t>(ws, o_ni); ea.nb_wgt = at<float>(ws, o_nw);
-                if ((rc = launch_edge_softmax(s, ea))) return rc;
-                ag.nb_idx = ea.nb_idx; ag.nb_wgt = ea.nb_wgt; ag.row_off = rowoff;
-            }
-        } else {
-            sa.cand_idx = at<int32_t>(ws, p.o_cidx); sa.cand_val = at<float>(ws, p.o_cval);
-            ea.cand_idx = sa.cand_idx; ea.cand_val = sa.cand_val;
-            // DAGL_FLAG_NO_REDO: the caller has seen this workspace's recent calls without redo work and does without the launch (4.7 us
-            // that find nothing); a call that flagged a group after all is NaN-filled by the gather kernel and reported (sticky)
-            const bool no_redo = p.screen && (mode_flags & DAGL_FLAG_NO_REDO) && fin && heads == 1 && !core && !dbg_deg && !dbg_rowsum && !dbg_agg;
-            if (no_redo) {
-                ag.unserved = stats + 2; ag.unserved_sticky = reinterpret_cast<int32_t*>(stats + 13);
-            } else if (p.screen) {
-                // redo pass behind the screen: scan + merge of the flagged groups in one launch (exits after one load when nothing
-                // is flagged); its grid barrier counts in stats[3] (cleared with the call's counters, unused by the top-k modes)
-                if ((rc = launch_topk_redo(s, sa, ea, mode == DAGL_MODE_TOPK ? 2 : 3, reinterpret_cast<unsigned*>(stats + 3),
-                                           topk_policy ? policy_w : nullptr))) return rc;
-            } else {
-                if ((rc = launch_score_select(s, sa, mode == DAGL_MODE_TOPK ? 2 : 3))) return rc;
-                prof_mark(prof, s, 5);
-                if ((rc = launch_edge_softmax(s, ea))) return rc;
-            }
-            if (info && !p.screen) { info->path = 2; info->max_degree = k; }
-        }
-    }
-
-    // ---- stages 6-7: gather + weighted sum, fold ---------------------------------------------------------------
-    if ((rc = run_tail(ag))) return rc;
-    if (prof && prof->n_calls < prof->max_calls) ++prof->n_calls;
     return DAGL_OK;
+}
+
+// ---- stage 1: both projections, one launch -------------------------------------------------------------
+static int stage_project(Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws;
+    int rc;
+    mark(c, 1);
+    if (c.core) {
+        if ((rc = launch_rows_to_feat(c.s, c.B, g.N, c.core->x_rows, c.X, c.Xh, c.rt))) return rc;
+        if ((rc = launch_rows_to_feat(c.s, c.B, g.L, c.core->wq_rows, c.Wq, c.Wqh, c.rt))) return rc;
+        return c.mode != DAGL_MODE_TOPK ? launch_colsum_rows(c.s, c.B, g.N, c.core->x_rows, c.colsum) : DAGL_OK;
+    }
+    if (!p.split16) return launch_project(c.s, c.B, g, 3, c.b1p, c.wp2, c.fc2_b, c.X, c.colsum, c.wp1, c.fc1_b, c.Wq, c.Xh, c.Wqh, c.rt);
+    B1Tiers tiers_fused;               // (the fused entry points: conv_pair16_kernel wrote both tiers; dagl_ce_forward's split_map_kernel only the fine one)
+    if (c.fin) {
+        tiers_fused.hi2 = at<uint16_t>(ws, p.o_maphi2); tiers_fused.lo2 = at<uint16_t>(ws, p.o_maplo2);
+        tiers_fused.amax = at<float>(ws, p.o_b1amax); tiers_fused.slots = conv16_blocks_per_head(g, c.heads, c.B / c.heads);
+    }
+    const float* b1s[4]; const float* b2s[4];
+    for (int hd = 0; hd < 4; ++hd) {
+        b1s[hd] = (c.fin && hd < c.heads) ? c.fin[hd].fc1_b : c.fc1_b;
+        b2s[hd] = (c.fin && hd < c.heads) ? c.fin[hd].fc2_b : c.fc2_b;
+    }
+    return launch_project16(c.s, c.B, g, 3, at<uint16_t>(ws, p.o_maphi), at<uint16_t>(ws, p.o_maplo), at<uint16_t>(ws, p.o_wp2h), b2s, c.X,
+                            (c.mode == DAGL_MODE_TOPK) ? nullptr : c.colsum, at<float>(ws, p.o_colpart), at<uint16_t>(ws, p.o_wp1h), b1s,
+                            c.Wq, c.Xh, c.Wqh, c.heads, c.rt, c.q_tiled, c.split_p,
+                            c.thr_in_proj ? &c.thr_all : nullptr, c.thr_in_proj ? c.B : 0, c.thr_in_proj ? at<float>(ws, p.o_thrpart) : nullptr,
+                            c.fin ? &tiers_fused : nullptr);
+}
+
+// ---- stage 2: adaptive thresholds ----------------------------------------------------------------------
+static int stage_thresholds(Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws;
+    mark(c, 2);
+    SelectArgs& sa = c.sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.B = c.B; sa.L = g.L; sa.N = g.N; sa.W = g.W; sa.wq = c.Wq; sa.x = c.X; sa.mode = c.mode; sa.k = c.k;
+    sa.splits = p.splits; sa.tiles_per_split = p.tiles_per_split;
+    EdgeArgs& ea = c.ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.B = c.B; ea.L = g.L; ea.N = g.N; ea.mode = c.mode; ea.k = c.k; ea.splits = p.splits;
+    ea.nb_idx = c.nbidx; ea.nb_wgt = c.nbwgt; ea.nb_cnt = c.nbcnt; ea.width = p.width;
+    ea.nb_s = c.core ? c.core->nb_s : nullptr;
+    AggArgs& ag = c.ag;
+    memset(&ag, 0, sizeof(ag));
+    ag.B = c.B; ag.g = g; ag.b2p = c.b2p; ag.nb_idx = c.nbidx; ag.nb_wgt = c.nbwgt; ag.nb_cnt = c.nbcnt; ag.width = p.width;
+    ag.agg = c.agg;
+    if (c.mode == DAGL_MODE_TOPK) return DAGL_OK;
+    ThrFuse tf;
+    if (c.fin) {                                 // finish the thr / bias heads here (their partial sums are per head)
+        tf.part = at<float>(ws, p.o_thrpart); tf.imgs_per_head = c.B / c.heads;
+        for (int hd = 0; hd < c.heads; ++hd) { tf.thr_b[hd] = c.fin[hd].thr_b; tf.bias_b[hd] = c.fin[hd].bias_b; }
+        tf.thr_out = at<float>(ws, p.o_thr); tf.bias_out = at<float>(ws, p.o_bias);
+    } else {
+        tf.bias_out = const_cast<float*>(c.bias);   // read only in this case
+    }
+    if (c.fused_theta) {
+        tf.theta_out = at<float>(ws, p.o_theta);
+        tf.zero_out = at<float>(ws, p.o_traw);      // (select_dense's sampled pass takes maxima into it)
+    }
+    const int rc = launch_query_thresholds(c.s, c.B, g.L, g.N, c.Wq, c.colsum, c.thr, c.mt, c.core ? c.core->mu : nullptr, &tf);
+    sa.mt = c.mt; sa.bs = c.bias; ea.mt = c.mt; ea.bs = c.bias;
+    return rc;
+}
+
+// ---- stages 6-7: gather + weighted sum, fold ---------------------------------------------------------------
+
+// the end of every path: the aggregated rows (the debug entry point: a copy of them) folded into the output map
+static int fold_out(Call& c) {
+    mark(c, 7);
+    if (c.r.dbg_agg) DAGL_HIP_TRY(hipMemcpyAsync(c.r.dbg_agg, c.agg, c.BL * P * sizeof(float), hipMemcpyDeviceToDevice, c.s));
+    const int rc = launch_fold(c.s, c.B, c.g, c.agg, c.r.out, c.heads, c.rt);
+    if (rc == DAGL_OK) mark(c, 8);
+    return rc;
+}
+
+// arguments of the per-query redo of the rows that overflowed the screened adaptive lists (overflow.hip)
+static OvfArgs overflow_args(const Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws;
+    OvfArgs oa;
+    memset(&oa, 0, sizeof(oa));
+    oa.B = c.B; oa.g = g; oa.x = c.X; oa.rows_x = feat_rows(g.N);
+    oa.mt = c.mt; oa.bs = c.bias; oa.b2p = c.b2p; oa.list = at<int32_t>(ws, p.o_ovflist);
+    oa.count = stat32(c.stats, STAT_OVF_COUNT); oa.cap = p.ovf_cap;
+    oa.qrows = at<float>(ws, p.o_ovfq); oa.scores = at<float>(ws, p.o_ovfscores); oa.ldn = (g.N + 31) / 32 * 32; oa.part = at<float>(ws, p.o_ovfpart);
+    oa.agg = c.agg; oa.nb_cnt = c.nbcnt; oa.dbg_deg = c.r.dbg_deg; oa.dbg_rowsum = c.r.dbg_rowsum;
+    oa.edges_run = c.stats + STAT_EDGES;     // (zero since the start of the call, overwritten with the total by the statistics block)
+    oa.flagged_edges = c.stats + STAT_REDONE_EDGES; oa.edge_limit = c.ovf_edge_limit;
+    return oa;
+}
+
+static int stage_tail(Call& c) {
+    const ForwardRequest& r = c.r; const AggArgs& ag = c.ag;
+    int rc;
+    if (r.dbg_deg || r.dbg_rowsum)
+        if ((rc = launch_row_stats(c.s, c.BL, ag.nb_wgt, ag.nb_cnt, ag.row_off, ag.width, r.dbg_deg, r.dbg_rowsum))) return rc;
+    mark(c, 6);
+    // short fixed-width lists and nobody asking for the aggregated rows: gather, weighted sum and fold in one kernel
+    if (c.mode != DAGL_MODE_ADAPTIVE && ag.row_off == nullptr && !c.ovf_active && !r.dbg_agg && !c.core) {
+        if ((rc = launch_aggregate_fold(c.s, ag, r.out, c.heads, c.rt))) return rc;
+        mark(c, 7);                              // (the whole tail is booked on the gather stage)
+        mark(c, 8);
+        return DAGL_OK;
+    }
+    // (the few queries whose neighbourhood overflowed the lists are redone one by one, dense rows, overflow.hip; the list gather
+    // skips them.  A call that does not wait had both done in the overflow launches; one that waits has its statistics on their
+    // way to the host by now and queues the gathers here, under the round trip)
+    if (!c.agg_done) {
+        if ((rc = launch_aggregate_direct(c.s, ag))) return rc;
+        if (c.ovf_active) {           // (a call that waited for its verdict: the flagged rows' gathers behind the read-back)
+            OvfArgs oa = overflow_args(c);
+            oa.edges_run = nullptr;                     // (their edges are known: ovf_attend_kernel looks at flagged_edges)
+            if ((rc = launch_overflow_apply(c.s, oa))) return rc;
+        }
+    }
+    return fold_out(c);
+}
+
+// ---- stages 3-5: neighbour selection + edge softmax, one function per path ----------------------------------
+
+// a read-back of the first n (> STAT_RANGE) statistics words; the range word tells whether the call left the split-fp16 range
+static int read_stats(Call& c, int n, int64_t* hs) {
+    const int rc = read_back(c.s, c.stats, n, hs);
+    c.left_range = rc == DAGL_OK && (int32_t)hs[STAT_RANGE] == c.rt.tag;
+    return rc;
+}
+
+// path 6: top-k modes with neighbourhoods wider than the lists -- scores, k-th largest, mask, softmax and weighted sum row by row
+static int select_wide(Call& c) {
+    dagl_ce_info* info = c.r.info;
+    int rc;
+    mark(c, 3); mark(c, 4); mark(c, 5);
+    if (c.heads > 1) { set_error("dagl_ces_stage_forward: k=%d > %d: use the per-head entry point", c.k, DAGL_MAX_TOPK); return DAGL_ERR_UNSUPPORTED; }
+    int32_t* deg = at<int32_t>(c.r.ws, c.p.o_deg);
+    if ((rc = launch_topk_wide(c.s, c.B, c.g, c.mode, c.k, c.Wq, c.X, c.mt, c.bias, c.b2p, at<char>(c.r.ws, c.p.o_wide), c.agg, deg,
+                               c.r.dbg_rowsum, c.rt))) return rc;
+    mark(c, 6);
+    if (c.r.dbg_deg) DAGL_HIP_TRY(hipMemcpyAsync(c.r.dbg_deg, deg, c.BL * sizeof(int32_t), hipMemcpyDeviceToDevice, c.s));
+    if ((rc = fold_out(c))) return rc;
+    if (!info) return DAGL_OK;
+    if ((rc = launch_degree_stats(c.s, c.BL, deg, c.stats))) return rc;
+    int64_t hs[STAT_RANGE + 1] = {0};
+    if ((rc = read_stats(c, STAT_RANGE + 1, hs)) || c.left_range) return rc;
+    info->path = 6; info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
+    return DAGL_OK;
+}
+
+static ScreenArgs screen_args(const Call& c) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws;
+    ScreenArgs sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.B = c.B; sc.L = g.L; sc.N = g.N; sc.mode = c.mode; sc.wqh = c.Wqh; sc.xh = c.Xh; sc.q_tiled = c.q_tiled;
+    sc.rows_qh = feat_rows_h(g.L); sc.rows_xh = feat_rows_h(g.N);
+    sc.splits = p.s_splits; sc.steps_per_split = p.s_steps_per_split; sc.n_steps = p.s_steps; sc.sample = p.s_sample; sc.qblock = p.s_qblock;
+    sc.gmax = at<float>(ws, p.o_gmax); sc.gkeep = p.s_gkeep; sc.theta = at<float>(ws, p.o_theta); sc.mt = c.mt; sc.bs = c.bias;
+    sc.capseg = p.capseg; sc.cand = at<int2>(ws, p.o_scand);
+    if (c.mode != DAGL_MODE_ADAPTIVE) { sc.spill = at<int2>(ws, p.o_spill); sc.spill_cnt = at<unsigned>(ws, p.o_spillcnt); }
+    if (c.topk_policy) { sc.policy = stat32(c.stats, STAT_POLICY); sc.sample_tight = p.s_sample_tight; sc.capseg_tight = p.capseg_tight; }
+#ifdef DAGL_ABLATION
+    { static const int var = [] { const char* e = getenv("DAGL_SCREEN_VARIANT"); return e ? atoi(e) : 0; }(); sc.variant = var; }
+#endif
+    return sc;
+}
+
+// path 4: most queries keep more keys than the screen has candidate slots for -- the dense regime.  Lists are pointless there;
+// the dense formulation is streamed instead (dense.hip).  Reached after the screen found out, or directly when the caller passes
+// DAGL_FLAG_DENSE_HINT (its previous call on this module ended here): always correct, only slower than the lists when the
+// neighbourhoods are in fact sparse.
+static int select_dense(Call& c, bool features_split) {
+    const Plan& p = c.p; const Grid& g = c.g; void* ws = c.r.ws; dagl_ce_info* info = c.r.info;
+    size_t o_dn = 0;
+    const size_t end = dense_ws_end(p, &o_dn);
+    if (info) { info->required_bytes = (int64_t)end; info->path = 4; }
+    if (c.core && !c.core->lse) {
+        if (info) info->required_bytes = -1;
+        set_error("dagl_ce_core_forward: dense neighbourhoods (most queries keep more than %d keys) do not fit fixed-width lists: "
+                  "use dagl_ce_core_dense_forward", DAGL_FAST_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    if (c.r.ws_bytes < end) {
+        set_error("dagl_ce_forward: dense neighbourhoods need workspace %zu B, have %zu B", end, c.r.ws_bytes);
+        return DAGL_ERR_WORKSPACE;
+    }
+    // the softmax's shift, known up front: every row's largest score, exactly -- a top-1 screen (sampled pass -> theta = the
+    // largest sampled S~ less the band -> filter pass) and the exact scores of its few candidates (rowmax_exact_kernel).  Up to
+    // round 4: an upper bound from one full bf16 scan, whose 1.6 % became > 18 units of a logit beyond ~580 and sent whole
+    // blocks through dense_attend_kernel a second time (every block of bench.py's default map: 1.52 ms for 0.81)
+    ScreenArgs s1 = screen_args(c);
+    s1.mode = DAGL_MODE_TOPK; s1.mt = nullptr; s1.bs = nullptr; s1.policy = nullptr; s1.gate = nullptr;
+    s1.spill = nullptr; s1.spill_cnt = nullptr; s1.seg_max = 1;      // (no spill: a row with more candidates than slots keeps its upper bound)
+    s1.theta_max = at<int>(ws, p.o_traw); s1.theta = at<float>(ws, p.o_traw);     // (zeroed by query_thresholds_kernel)
+    int rc;
+    if ((rc = launch_screen(c.s, s1, 0))) return rc;
+    if ((rc = launch_screen(c.s, s1, 1))) return rc;
+    float* smax = at<float>(ws, p.o_smax);
+    RefineArgs r1;
+    memset(&r1, 0, sizeof(r1));
+    r1.B = c.B; r1.L = g.L; r1.N = g.N; r1.mode = DAGL_MODE_TOPK; r1.k = 1; r1.splits = p.s_splits; r1.capseg = p.capseg;
+    r1.wq = c.Wq; r1.x = c.X; r1.rows_q = feat_rows(g.L); r1.rows_x = feat_rows(g.N);
+    r1.cand = s1.cand; r1.theta = s1.theta; r1.mt = c.mt; r1.bs = c.bias;
+    if ((rc = launch_rowmax_exact(c.s, r1, smax))) return rc;
+    mark(c, 6);          // (stage "gather" of a dense call = value-map split + dense_attend_kernel + combine)
+    if ((rc = launch_dense_attend(c.s, c.B, g, c.Wq, c.X, c.mt, c.bias, smax, c.b2p, at<char>(ws, o_dn), c.agg, c.r.dbg_deg,
+                                  c.r.dbg_rowsum, c.stats, c.rt, c.core ? c.core->lse : nullptr, features_split, info != nullptr))) return rc;
+    if ((rc = fold_out(c))) return rc;
+    if (!info) return DAGL_OK;
+    int64_t hs[STAT_DENSE_RERUN + 1] = {0};
+    if ((rc = read_stats(c, STAT_DENSE_RERUN + 1, hs)) || c.left_range) return rc;
+    info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
+    info->redone_queries = hs[STAT_FLAGGED];                          // queries whose degree exceeds the lists' width
+    info->dense_rerun_blocks = (int32_t)hs[STAT_DENSE_RERUN];         // blocks of 64 queries dense_attend_kernel ran a second time
+    return DAGL_OK;
+}
+
+// paths 0 / 1, adaptive mode: one fp32 scan into per-lane lists; a degree beyond them takes the two-pass CSR form (1)
+static int scan_adaptive(Call& c) {
+    const Plan& p = c.p; void* ws = c.r.ws; dagl_ce_info* info = c.r.info;
+    SelectArgs& sa = c.sa; EdgeArgs& ea = c.ea;
+    int32_t* lidx = at<int32_t>(ws, p.o_lidx);
+    float* lval = at<float>(ws, p.o_lval);
+    int32_t* cnt = at<int32_t>(ws, p.o_cnt);
+    int32_t* segcnt = at<int32_t>(ws, p.o_segcnt);
+    int32_t* segrel = at<int32_t>(ws, p.o_segoff);
+    int32_t* deg = at<int32_t>(ws, p.o_deg);
+    int rc;
+    DAGL_HIP_TRY(hipMemsetAsync(cnt, 0, c.BL * sizeof(int32_t), c.s));
+    sa.cnt = cnt; sa.seg_cnt = segcnt; sa.list_idx = lidx; sa.list_val = lval;
+    if ((rc = launch_score_select(c.s, sa, 0))) return rc;
+    if (!p.screen) mark(c, 5);
+    if ((rc = launch_row_degree(c.s, (int)c.BL, p.splits * 2, segcnt, segrel, deg, c.stats))) return rc;
+    int64_t hs[STAT_MAX_DEGREE + 1] = {0};
+    if ((rc = read_back(c.s, c.stats, STAT_MAX_DEGREE + 1, hs))) return rc;
+    const int64_t edges = hs[STAT_EDGES], max_deg = hs[STAT_MAX_DEGREE];
+    if (info) { info->total_edges = edges; info->max_degree = (int32_t)max_deg; info->path = 0; }
+    if (max_deg <= DAGL_FAST_CAP) {
+        ea.cnt = deg; ea.list_idx = lidx; ea.list_val = lval; ea.row_off = nullptr;
+        return launch_edge_softmax(c.s, ea);
+    }
+    // two-pass CSR: exact degrees are known, refill deterministically at per-lane cursors
+    size_t off = p.o_end;
+    const size_t e = (size_t)edges;
+    const size_t o_ci = carve(off, e * sizeof(int32_t));
+    const size_t o_cv = carve(off, e * sizeof(float));
+    const size_t o_ni = carve(off, e * sizeof(int32_t));
+    const size_t o_nw = carve(off, e * sizeof(float));
+    if (info) { info->required_bytes = (int64_t)off; info->path = 1; }
+    if (c.core) {
+        if (info) info->required_bytes = -1;
+        set_error("dagl_ce_core_forward: dense neighbourhoods (max degree %lld > %d) do not fit fixed-width lists: "
+                  "use dagl_ce_core_dense_forward", (long long)max_deg, DAGL_FAST_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    if (c.r.ws_bytes < off) {
+        set_error("dagl_ce_forward: dense neighbourhoods (max degree %lld, %lld edges) need workspace %zu B, have %zu B",
+                  (long long)max_deg, (long long)edges, off, c.r.ws_bytes);
+        return DAGL_ERR_WORKSPACE;
+    }
+    int64_t* rowoff = at<int64_t>(ws, p.o_rowoff);
+    if ((rc = launch_row_scan(c.s, (int)c.BL, deg, rowoff))) return rc;
+    sa.list_idx = at<int32_t>(ws, o_ci); sa.list_val = at<float>(ws, o_cv); sa.seg_rel = segrel; sa.row_off = rowoff;
+    if ((rc = launch_score_select(c.s, sa, 1))) return rc;
+    ea.cnt = deg; ea.list_idx = sa.list_idx; ea.list_val = sa.list_val; ea.row_off = rowoff;
+    ea.nb_idx = at<int32_t>(ws, o_ni); ea.nb_wgt = at<float>(ws, o_nw);
+    if ((rc = launch_edge_softmax(c.s, ea))) return rc;
+    c.ag.nb_idx = ea.nb_idx; c.ag.nb_wgt = ea.nb_wgt; c.ag.row_off = rowoff;
+    return DAGL_OK;
+}
+
+// path 2, top-k modes: per-lane top-k lists of the fp32 scan; behind the screen only the query groups it flagged
+static int scan_topk(Call& c) {
+    const Plan& p = c.p; void* ws = c.r.ws;
+    SelectArgs& sa = c.sa; EdgeArgs& ea = c.ea;
+    int rc;
+    sa.cand_idx = at<int32_t>(ws, p.o_cidx); sa.cand_val = at<float>(ws, p.o_cval);
+    ea.cand_idx = sa.cand_idx; ea.cand_val = sa.cand_val;
+    if (c.no_redo) {
+        // DAGL_FLAG_NO_REDO: the caller has seen this workspace's recent calls without redo work and does without the launch (4.7 us
+        // that find nothing); a call that flagged a group after all is NaN-filled by the gather kernel and reported (sticky)
+        c.ag.unserved = c.stats + STAT_FLAGGED; c.ag.unserved_sticky = stat32(c.stats, STAT_NO_REDO_STICKY);
+    } else if (p.screen) {
+        // redo pass behind the screen: scan + merge of the flagged groups in one launch (exits after one load when nothing
+        // is flagged); its grid barrier counts in STAT_OVF_COUNT (cleared with the call's counters, unused by the top-k modes)
+        if ((rc = launch_topk_redo(c.s, sa, ea, c.mode == DAGL_MODE_TOPK ? 2 : 3, reinterpret_cast<unsigned*>(c.stats + STAT_OVF_COUNT),
+                                   c.topk_policy ? stat32(c.stats, STAT_POLICY) : nullptr))) return rc;
+    } else {
+        if ((rc = launch_score_select(c.s, sa, c.mode == DAGL_MODE_TOPK ? 2 : 3))) return rc;
+        mark(c, 5);
+        if ((rc = launch_edge_softmax(c.s, ea))) return rc;
+    }
+    if (c.r.info && !p.screen) { c.r.info->path = 2; c.r.info->max_degree = c.k; }
+    return DAGL_OK;
+}
+
+// the fp32 scan (select.hip) and the tail: every call without the screen, and the screened calls it redoes
+static int select_scan(Call& c) {
+    const int rc = (c.mode == DAGL_MODE_ADAPTIVE) ? scan_adaptive(c) : scan_topk(c);
+    return rc ? rc : stage_tail(c);
+}
+
+// The adaptive mode's verdict on a screened call.  Dense neighbourhoods need host-side CSR sizing, so the verdict must be read
+// back.  Everything it consists of is known once the flagged queries' chunk statistics exist (their true degrees): the copy is
+// queued there, the optimistic gather, the flagged rows' weighted sums and the fold behind it, and the host waits for the copy
+// alone -- the device works through the round trip and through the caller's next launches.
+// DAGL_FLAG_NO_WAIT: the verdict is formed on the device, the call returns without reading it (no host round trip: the adaptive
+// forward can be captured into a HIP graph); an unserved call is NaN-filled, never wrong
+static int screened_verdict(Call& c) {
+    const Plan& p = c.p; dagl_ce_info* info = c.r.info;
+    int rc;
+    if (c.no_wait) c.rt.veto = stat32(c.stats, STAT_VETO);
+    if (c.ovf_active) {           // the flagged rows redone (three launches that exit at once when there are none) + the call's statistics
+        // (a call that does not wait shares the scores' launch with the gather over the lists; one that waits keeps the gather
+        // behind the read-back: the host round trip runs under it)
+        if ((rc = launch_overflow_rows(c.s, overflow_args(c), c.no_wait ? &c.ag : nullptr, c.BL, c.stats,
+                                       c.no_wait ? stat32(c.stats, STAT_VETO) : nullptr, c.rt.tag))) return rc;
+        c.agg_done = c.no_wait;
+    } else {
+        if ((rc = launch_degree_stats(c.s, c.BL, c.nbcnt, c.stats))) return rc;
+    }
+    if (c.no_wait) return stage_tail(c);                 // info: path 3, statistics not read (-1)
+    constexpr int n = STAT_REDONE_EDGES + 1;
+    int64_t hs[n] = {0};
+    bool pending = false;
+    if ((rc = read_back_begin(c.s, c.stats, n, &pending))) return rc;
+    if ((rc = stage_tail(c))) return rc;
+    if ((rc = read_back_end(c.s, c.stats, n, pending, hs))) return rc;
+    if ((c.left_range = (int32_t)hs[STAT_RANGE] == c.rt.tag)) return DAGL_OK;
+    const int64_t flagged = hs[STAT_FLAGGED];
+    if (info) info->redone_queries = flagged;
+    // most queries overflow, or the flagged rows are too heavy to redo one by one (the attend kernels saw the same
+    // word and left them alone): dense regime
+    const bool heavy_rows = c.ovf_active && flagged > 0 && flagged <= p.ovf_cap && hs[STAT_REDONE_EDGES] > c.ovf_edge_limit;
+    const bool mostly = flagged * 2 > (int64_t)c.BL || heavy_rows;
+    if (flagged == 0 || (!mostly && c.ovf_active && flagged <= p.ovf_cap)) {   // (few overflowed queries: redone in-stream)
+        if (info) { info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE]; }
+        return DAGL_OK;
+    }
+    c.ovf_active = false; c.agg_done = false;
+    if (mostly) return select_dense(c, false);
+    return select_scan(c);                               // redo everything with the fp32 scan (CSR capable)
+}
+
+// path 3: bf16 screen + exact refine (screen.hip)
+static int select_screened(Call& c) {
+    const Plan& p = c.p; void* ws = c.r.ws; dagl_ce_info* info = c.r.info;
+    int rc;
+    if (c.mode == DAGL_MODE_ADAPTIVE && (c.r.mode_flags & DAGL_FLAG_DENSE_HINT) && (!c.core || c.core->lse)) {
+        mark(c, 3); mark(c, 4); mark(c, 5);
+        return select_dense(c, c.split_p != nullptr);
+    }
+    const ScreenArgs sc = screen_args(c);
+    float* theta = at<float>(ws, p.o_theta);
+    int32_t* policy = stat32(c.stats, STAT_POLICY);
+    mark(c, 3);
+    if (c.mode != DAGL_MODE_ADAPTIVE) {                     // top-k threshold from the sampling pass
+        if ((rc = launch_screen(c.s, sc, 0))) return rc;
+        if ((rc = launch_screen_theta(c.s, (int)c.BL, p.s_splits * 2 * p.s_gkeep, c.k, sc.gmax, theta, nullptr, sc.spill_cnt))) return rc;
+    }
+    if (c.mode != DAGL_MODE_TOPK && !c.fused_theta)         // adaptive threshold; the intersection mode takes the larger
+        if ((rc = launch_adaptive_theta(c.s, c.BL, c.mt, c.bias, theta, c.mode == DAGL_MODE_ADAPTIVE_TOPK))) return rc;
+    mark(c, 4);
+    if ((rc = launch_screen(c.s, sc, 1))) return rc;
+    mark(c, 5);
+    RefineArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.B = c.B; ra.L = c.g.L; ra.N = c.g.N; ra.mode = c.mode; ra.k = c.k; ra.splits = p.s_splits; ra.capseg = p.capseg;
+    ra.width = p.width; ra.wq = c.Wq; ra.x = c.X; ra.rows_q = feat_rows(c.g.L); ra.rows_x = feat_rows(c.g.N);
+    ra.mt = c.mt; ra.bs = c.bias; ra.cand = sc.cand; ra.theta = sc.theta; ra.spill = sc.spill; ra.spill_cnt = sc.spill_cnt;
+    ra.nb_idx = c.nbidx; ra.nb_wgt = c.nbwgt; ra.nb_cnt = c.nbcnt; ra.redo_flags = c.redo; ra.n_qgroups_exact = c.n_qgroups;
+    ra.stats = c.stats; ra.nb_s = c.core ? c.core->nb_s : nullptr;
+    if (p.ovf_cap > 0) {
+        ra.ovf_list = at<int32_t>(ws, p.o_ovflist); ra.ovf_count = stat32(c.stats, STAT_OVF_COUNT); ra.ovf_cap = p.ovf_cap;
+        ra.ovf_qrows = at<float>(ws, p.o_ovfq);
+        ra.heavy_list = at<int32_t>(ws, p.o_heavy); ra.heavy_count = stat32(c.stats, STAT_OVF_COUNT) + 1;   // (cleared with the counters)
+        c.ovf_active = true;
+    }
+    if (c.topk_policy) { ra.policy = policy; ra.capseg_tight = p.capseg_tight; }
+    if ((rc = launch_refine(c.s, ra))) return rc;
+    if (c.topk_policy && !c.prepared) {
+        // cold workspace: did the sampled threshold overflow most queries' slots (natural-image features)?  Then the policy word
+        // flips here and sampling, threshold, filter and refine run once more, tight, in this very call -- four launches that
+        // exit at once otherwise -- instead of every query group taking the fp32 redo pass (2.7 ms at 256^2)
+        int32_t* gate = stat32(c.stats, STAT_GATE);
+        if ((rc = launch_topk_policy(c.s, c.stats, policy, gate, c.redo, (int)(c.B * c.n_qgroups), (long long)c.BL))) return rc;
+        ScreenArgs sc2 = sc; sc2.gate = gate;
+        if ((rc = launch_screen(c.s, sc2, 0))) return rc;
+        if ((rc = launch_screen_theta(c.s, (int)c.BL, p.s_splits * 2 * p.s_gkeep, c.k, sc2.gmax, theta, gate, sc2.spill_cnt))) return rc;
+        // (the intersection mode takes the larger of the two thresholds: max(adaptive, theta) is idempotent, so the ungated
+        // kernel is harmless when the re-run did not run)
+        if (c.mode != DAGL_MODE_TOPK && !c.fused_theta)
+            if ((rc = launch_adaptive_theta(c.s, c.BL, c.mt, c.bias, theta, true))) return rc;
+        if ((rc = launch_screen(c.s, sc2, 1))) return rc;
+        RefineArgs ra2 = ra; ra2.gate = gate;
+        if ((rc = launch_refine(c.s, ra2))) return rc;
+    }
+    if (info) info->path = 3;
+    if (c.mode == DAGL_MODE_ADAPTIVE) return screened_verdict(c);
+    // top-k modes: query groups whose candidate slots overflowed are redone by the fp32 scan; it exits at once for every other
+    // group, so no host round trip is needed
+    c.sa.run_flags = c.redo; c.ea.run_flags = c.redo; c.sa.run_count = c.stats + STAT_FLAGGED; c.ea.run_count = c.stats + STAT_FLAGGED;
+    if (info && (c.r.dbg_deg || c.r.dbg_rowsum || c.r.dbg_agg)) {        // debug entry point: report the overflow count
+        int64_t hs[STAT_N_COUNTERS] = {0};
+        if ((rc = read_back(c.s, c.stats, STAT_N_COUNTERS, hs))) return rc;
+        info->redone_queries = hs[STAT_FLAGGED];
+    }
+    return select_scan(c);
+}
+
+// One forward: plan, checks, stages.  `left_range`: a statistics read-back found that an operand left the split-fp16 range
+static int forward_once(const ForwardRequest& r, bool& left_range) {
+    Plan p;
+    int rc = make_plan(r.B, r.H, r.W, r.mode_flags, r.k, p, r.core != nullptr);
+    if (rc) return rc;
+    reset_info(r.info, (int64_t)p.o_end, 0);
+    if ((rc = check_request(r, p))) return rc;
+    Call c(r, p);
+    if ((rc = stage_layout(c)) || (rc = stage_project(c)) || (rc = stage_thresholds(c))) return rc;
+    if (p.wide) rc = select_wide(c);
+    else if (p.screen) rc = select_screened(c);
+    else { mark(c, 3); mark(c, 4); rc = select_scan(c); }
+    left_range = c.left_range;
+    return rc;
+}
+
+// Every forward entry point ends here: the profile counts the call, and a call that left the split-fp16 range -- which only the
+// statistics read-backs see; without one the poisoned output and dagl_ce_range_check report it -- is re-run once on the fp32 path
+// (same arguments, DAGL_FLAG_EXACT_SCAN).  Neither a fallback call nor its re-run is counted.
+static int ce_forward(const ForwardRequest& r) {
+    bool left_range = false;
+    int rc = forward_once(r, left_range);
+    if (rc != DAGL_OK) return rc;
+    if (!left_range) {
+        if (r.prof && r.prof->n_calls < r.prof->max_calls) ++r.prof->n_calls;
+        return DAGL_OK;
+    }
+    if (r.info) r.info->range_fallback = 1;
+    // the training entry point: non-finite features, `out` NaN-filled (dagl_ce_core_dense_forward re-runs the GEMM form).  Already the
+    // fp32 path: the word was set by a NON-FINITE feature (round 6), the output is NaN-filled as the reference's would be.  Nothing to re-run
+    if (r.core || (r.mode_flags & DAGL_FLAG_EXACT_SCAN)) return DAGL_OK;
+    if (r.heads > 1) {            // stage entry point: no fp32 form of the four-head launch set; hand the call back (per-head path)
+        if (r.info) r.info->required_bytes = -1;
+        set_error("dagl_ces_stage_forward: an operand left the split-fp16 range: use the per-head entry point");
+        return DAGL_ERR_WORKSPACE;
+    }
+    ForwardRequest exact = r;
+    exact.mode_flags = (r.mode_flags | DAGL_FLAG_EXACT_SCAN) & ~(DAGL_FLAG_WEIGHTS_PACKED | DAGL_FLAG_DENSE_HINT);
+    exact.prof = nullptr;
+    rc = forward_once(exact, left_range);      // (left_range again: a non-finite input -- the output is NaN-filled)
+    if (r.info) r.info->range_fallback = 1;
+    return rc;
 }
 
 }  // namespace dagl
@@ -1000,16 +1134,21 @@ int dagl_ce_forward(void* stream, int B, int H, int W, const float* b1, const fl
                     const float* bias, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                     const float* fc2_b, int mode, int k, float* out, void* workspace, size_t ws_bytes,
                     dagl_ce_info* info) {
-    return ce_forward_impl((hipStream_t)stream, B, H, W, b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode, k, out,
-                           workspace, ws_bytes, info, nullptr, nullptr, nullptr);
+    const MapsIn in{b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b};
+    ForwardRequest r(stream, B, H, W, mode, k, out, workspace, ws_bytes, info);
+    r.maps = &in;
+    return ce_forward(r);
 }
 
 int dagl_ce_forward_debug(void* stream, int B, int H, int W, const float* b1, const float* b2, const float* thr,
                           const float* bias, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                           const float* fc2_b, int mode, int k, float* out, void* workspace, size_t ws_bytes,
                           dagl_ce_info* info, int32_t* deg_out, float* rowsum_out, float* agg_out) {
-    return ce_forward_impl((hipStream_t)stream, B, H, W, b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode, k, out,
-                           workspace, ws_bytes, info, deg_out, rowsum_out, agg_out);
+    const MapsIn in{b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b};
+    ForwardRequest r(stream, B, H, W, mode, k, out, workspace, ws_bytes, info);
+    r.maps = &in;
+    r.dbg_deg = deg_out; r.dbg_rowsum = rowsum_out; r.dbg_agg = agg_out;
+    return ce_forward(r);
 }
 
 int dagl_profile_create(int max_calls, dagl_profile** out) {
@@ -1076,8 +1215,11 @@ int dagl_ce_forward_profiled(void* stream, int B, int H, int W, const float* b1,
                              const float* bias, const float* fc1_w, const float* fc1_b, const float* fc2_w,
                              const float* fc2_b, int mode, int k, float* out, void* workspace, size_t ws_bytes,
                              dagl_ce_info* info, dagl_profile* prof) {
-    return ce_forward_impl((hipStream_t)stream, B, H, W, b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode, k, out,
-                           workspace, ws_bytes, info, nullptr, nullptr, nullptr, reinterpret_cast<Profile*>(prof));
+    const MapsIn in{b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b};
+    ForwardRequest r(stream, B, H, W, mode, k, out, workspace, ws_bytes, info);
+    r.maps = &in;
+    r.prof = reinterpret_cast<Profile*>(prof);
+    return ce_forward(r);
 }
 
 int dagl_ce_forward_fused(void* stream, int B, int H, int W, const float* x, const float* g_w, const float* g_b,
@@ -1085,10 +1227,11 @@ int dagl_ce_forward_fused(void* stream, int B, int H, int W, const float* x, con
                           const float* bias_w, const float* bias_b, const float* fc1_w, const float* fc1_b,
                           const float* fc2_w, const float* fc2_b, int mode, int k, float* out, void* workspace,
                           size_t ws_bytes, dagl_ce_info* info, dagl_profile* prof) {
-    FusedIn fin{x, g_w, g_b, theta_w, theta_b, thr_w, thr_b, bias_w, bias_b, fc1_w, fc1_b, fc2_w, fc2_b};
-    return ce_forward_impl((hipStream_t)stream, B, H, W, nullptr, nullptr, nullptr, nullptr, fc1_w, fc1_b, fc2_w, fc2_b,
-                           mode, k, out, workspace, ws_bytes, info, nullptr, nullptr, nullptr,
-                           reinterpret_cast<Profile*>(prof), &fin);
+    const FusedIn fin{x, g_w, g_b, theta_w, theta_b, thr_w, thr_b, bias_w, bias_b, fc1_w, fc1_b, fc2_w, fc2_b};
+    ForwardRequest r(stream, B, H, W, mode, k, out, workspace, ws_bytes, info);
+    r.fin = &fin;
+    r.prof = reinterpret_cast<Profile*>(prof);
+    return ce_forward(r);
 }
 
 size_t dagl_ces_stage_workspace_bytes(int B, int H, int W, int mode, int k) {
@@ -1121,9 +1264,10 @@ int dagl_ces_stage_forward(void* stream, int B, int H, int W, const float* x, co
     }
     float* cat = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.o_end);       // [B,64,H,W]
     // a dense adaptive neighbourhood asks for more workspace than planned: give the block everything up to the concat map
-    rc = ce_forward_impl((hipStream_t)stream, 4 * B, H, W, nullptr, nullptr, nullptr, nullptr, fin[0].fc1_w, fin[0].fc1_b,
-                         fin[0].fc2_w, fin[0].fc2_b, mode, k, cat, workspace, p.o_end, info, nullptr, nullptr, nullptr,
-                         reinterpret_cast<Profile*>(prof), fin, 4);
+    ForwardRequest r(stream, 4 * B, H, W, mode, k, cat, workspace, p.o_end, info);
+    r.fin = fin; r.heads = 4;
+    r.prof = reinterpret_cast<Profile*>(prof);
+    rc = ce_forward(r);
     if (rc) {
         if (rc == DAGL_ERR_WORKSPACE && info) info->required_bytes = -1;    // dense neighbourhoods: use the per-head entry point
         return rc;
@@ -1140,23 +1284,22 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
     DAGL_REQUIRE(ws_bytes >= p.o_end && ((uintptr_t)workspace % 256) == 0, "dagl_ce_range_check: not the workspace of such a call");
     *violated = 0;
     if (mode & DAGL_FLAG_EXACT_SCAN) return DAGL_OK;                      // the fp32 path has no such range (and always waits)
-    // ONE read-back (one synchronisation) of stats[2..13]: [2] flagged queries of the last call, [4] range word, [8] veto word, [9] top-k
-    // policy, [13] unserved DAGL_FLAG_NO_REDO call
-    int64_t hw[12] = {0};
+    // ONE read-back (one synchronisation) of the statistics words STAT_FLAGGED .. STAT_NO_REDO_STICKY
+    int64_t hw[STAT_WORDS] = {0};
     int64_t* st = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + p.o_stats);
-    if ((rc = read_back((hipStream_t)stream, st + 2, 12, hw))) return rc;
+    if ((rc = read_back((hipStream_t)stream, st + STAT_FLAGGED, STAT_NO_REDO_STICKY + 1 - STAT_FLAGGED, hw + STAT_FLAGGED))) return rc;
     const bool topk_screen = (mode & 0xff) != DAGL_MODE_ADAPTIVE && p.screen;
     // sticky: the word keeps the tag of the last call that left the range until it is read here (calls that reuse a
     // prepared workspace do not clear it), so a poll every n-th call sees a violation of ANY call since the last poll
-    if ((int32_t)hw[2] != 0) { *violated |= 1; DAGL_HIP_TRY(hipMemsetAsync(st + 4, 0, sizeof(int64_t), (hipStream_t)stream)); }
+    if ((int32_t)hw[STAT_RANGE] != 0) { *violated |= 1; DAGL_HIP_TRY(hipMemsetAsync(st + STAT_RANGE, 0, sizeof(int64_t), (hipStream_t)stream)); }
     // bit 2 (not sticky: the count is cleared by every call): the last call's redo pass of the top-k modes had work
-    if (topk_screen && hw[0] > 0) *violated |= 4;
-    if (topk_screen && (int32_t)hw[7] != 0) *violated |= 8;            // bit 3: the workspace's threshold policy word says "tight"
+    if (topk_screen && hw[STAT_FLAGGED] > 0) *violated |= 4;
+    if (topk_screen && (int32_t)hw[STAT_POLICY] != 0) *violated |= 8;            // bit 3: the workspace's threshold policy word says "tight"
     // bit 4 (sticky): a DAGL_FLAG_NO_REDO call had flagged groups (its output is NaN-filled)
-    if (topk_screen && (int32_t)hw[11] != 0) { *violated |= 16; DAGL_HIP_TRY(hipMemsetAsync(st + 13, 0, sizeof(int64_t), (hipStream_t)stream)); }
+    if (topk_screen && (int32_t)hw[STAT_NO_REDO_STICKY] != 0) { *violated |= 16; DAGL_HIP_TRY(hipMemsetAsync(st + STAT_NO_REDO_STICKY, 0, sizeof(int64_t), (hipStream_t)stream)); }
     // bit 1: a DAGL_FLAG_NO_WAIT call was not served in-stream (likewise sticky)
-    if ((mode & 0xff) == DAGL_MODE_ADAPTIVE && (int32_t)hw[6] != 0) {
-        *violated |= 2; DAGL_HIP_TRY(hipMemsetAsync(st + 8, 0, sizeof(int64_t), (hipStream_t)stream));
+    if ((mode & 0xff) == DAGL_MODE_ADAPTIVE && (int32_t)hw[STAT_VETO] != 0) {
+        *violated |= 2; DAGL_HIP_TRY(hipMemsetAsync(st + STAT_VETO, 0, sizeof(int64_t), (hipStream_t)stream));
     }
     return DAGL_OK;
 }
@@ -1173,9 +1316,10 @@ int dagl_ce_core_forward(void* stream, int B, int H, int W, const float* wq_rows
                          const float* thr, const float* bias, int mode, int k, float* out, int32_t* nb_idx,
                          float* nb_wgt, float* nb_s, int32_t* nb_cnt, float* mu, void* workspace, size_t ws_bytes,
                          dagl_ce_info* info) {
-    CoreIn core{wq_rows, x_rows, nb_idx, nb_wgt, nb_s, nb_cnt, mu, nullptr};
-    return ce_forward_impl((hipStream_t)stream, B, H, W, nullptr, b2, thr, bias, nullptr, nullptr, nullptr, nullptr, mode,
-                           k, out, workspace, ws_bytes, info, nullptr, nullptr, nullptr, nullptr, nullptr, 1, &core);
+    const CoreIn core{wq_rows, x_rows, b2, thr, bias, nb_idx, nb_wgt, nb_s, nb_cnt, mu, nullptr};
+    ForwardRequest r(stream, B, H, W, mode, k, out, workspace, ws_bytes, info);
+    r.core = &core;
+    return ce_forward(r);
 }
 
 static size_t backward_offsets(int B, const Grid& g, int width, size_t o[13], size_t* sort_temp) {
@@ -1256,9 +1400,7 @@ static bool dense_core_streamed(int H, int W) { return (int64_t)H * W >= SCREEN_
 static size_t dense_core_streamed_bytes(int B, int H, int W) {
     Plan p;
     if (make_plan(B, H, W, DAGL_MODE_ADAPTIVE | DAGL_FLAG_DENSE_HINT, 0, p, true)) return 0;
-    size_t off = p.o_end;
-    (void)carve(off, dense_workspace_bytes(B, p.g));
-    return off;
+    return dense_ws_end(p);
 }
 
 size_t dagl_ce_core_dense_workspace_bytes(int B, int H, int W, int backward) {
@@ -1279,17 +1421,16 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
     hipStream_t s = (hipStream_t)stream;
     bool left_range = false;
     if (dense_core_streamed(H, W) && !(flags & DAGL_FLAG_EXACT_SCAN)) {
-        CoreIn core{wq_rows, x_rows, nullptr, nullptr, nullptr, nullptr, mu, lse};
-        const int rc0 = ce_forward_impl(s, B, H, W, nullptr, b2, thr, bias, nullptr, nullptr, nullptr, nullptr,
-                                        DAGL_MODE_ADAPTIVE | DAGL_FLAG_DENSE_HINT, 0, out, workspace, ws_bytes, info, nullptr, nullptr,
-                                        nullptr, nullptr, nullptr, 1, &core);
+        const CoreIn core{wq_rows, x_rows, b2, thr, bias, nullptr, nullptr, nullptr, nullptr, mu, lse};
+        ForwardRequest r(stream, B, H, W, DAGL_MODE_ADAPTIVE | DAGL_FLAG_DENSE_HINT, 0, out, workspace, ws_bytes, info);
+        r.core = &core;
+        const int rc0 = ce_forward(r);
         // a feature outside the split-fp16 range (|feature| >= 937): the streamed kernels NaN-filled `out`; a call that reads
         // its statistics back (info != NULL) notices and is re-run right here in the fp32 GEMM form, which has no such range
         if (rc0 != DAGL_OK || info == nullptr || !info->range_fallback) return rc0;
         left_range = true;
     }
-    if (info) { info->required_bytes = (int64_t)dense_train_workspace_bytes(B, g, false); info->total_edges = -1;
-                info->max_degree = -1; info->redone_queries = -1; info->path = 5; info->range_fallback = 0; info->dense_rerun_blocks = 0; }
+    reset_info(info, (int64_t)dense_train_workspace_bytes(B, g, false), 5);
     // the two statistics words live at the very end of the caller's buffer (past the plan)
     const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
     if (ws_bytes < need) { set_error("dagl_ce_core_dense_forward: workspace %zu B < required %zu B", ws_bytes, need);
@@ -1299,9 +1440,9 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
                                         info ? stats : nullptr);
     if (rc) return rc;
     if (info) {
-        int64_t hs[2] = {0, 0};
-        if ((rc = read_back(s, stats, 2, hs))) return rc;
-        info->total_edges = hs[0]; info->max_degree = (int32_t)hs[1];
+        int64_t hs[STAT_MAX_DEGREE + 1] = {0};
+        if ((rc = read_back(s, stats, STAT_MAX_DEGREE + 1, hs))) return rc;
+        info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
         info->range_fallback = left_range ? 1 : 0;
     }
     return DAGL_OK;
@@ -1330,8 +1471,7 @@ int dagl_ce_core_wide_forward(void* stream, int B, int H, int W, int mode, int k
     const Grid g = make_grid(H, W);
     if (k > g.N) k = g.N;                                              // top_k = min(num_edge, N)
     const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
-    if (info) { info->required_bytes = (int64_t)need; info->total_edges = -1; info->max_degree = -1; info->redone_queries = -1;
-                info->path = 5; info->range_fallback = 0; info->dense_rerun_blocks = 0; }
+    reset_info(info, (int64_t)need, 5);
     if (ws_bytes < need) { set_error("dagl_ce_core_wide_forward: workspace %zu B < required %zu B", ws_bytes, need); return DAGL_ERR_WORKSPACE; }
     hipStream_t s = (hipStream_t)stream;
     int64_t* stats = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + need - 256);
@@ -1340,9 +1480,9 @@ int dagl_ce_core_wide_forward(void* stream, int B, int H, int W, int mode, int k
                                         workspace, need - 256, info ? stats : nullptr, mode, k);
     if (rc) return rc;
     if (info) {
-        int64_t hs[2] = {0, 0};
-        if ((rc = read_back(s, stats, 2, hs))) return rc;
-        info->total_edges = hs[0]; info->max_degree = (int32_t)hs[1];
+        int64_t hs[STAT_MAX_DEGREE + 1] = {0};
+        if ((rc = read_back(s, stats, STAT_MAX_DEGREE + 1, hs))) return rc;
+        info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
     }
     return DAGL_OK;
 }

@@ -291,6 +291,28 @@ struct RangeTag {
 };
 constexpr float RANGE_LIMIT = 60000.0f;
 
+// The statistics block of a forward's workspace: 16 int64 words at Plan::o_stats (capi.hip).  The first STAT_N_COUNTERS words
+// are the per-call counters, cleared at the start of every call; the others outlive the call.  The int32 words (range, done,
+// veto, policy, gate, sticky) use the low half of their int64 word.
+enum StatWord : int {
+    STAT_EDGES = 0,            // total edges of the call
+    STAT_MAX_DEGREE = 1,       // largest degree
+    STAT_FLAGGED = 2,          // queries the refine kernels flagged (overflowed slots or lists); the dense formulation: rows beyond the lists' width
+    STAT_OVF_COUNT = 3,        // adaptive: [int32] overflowed queries listed, [int32] heavy queries listed; top-k: the redo pass's grid barrier
+    STAT_N_COUNTERS = 4,
+    STAT_RANGE = 4,            // RangeTag::word: tag of the last call that left the split-fp16 range (sticky)
+    STAT_DONE = 5,             // RangeTag::done: tag of the last completed call
+    STAT_REDONE_ROWS = 6,      // (redone rows: not written today)
+    STAT_REDONE_EDGES = 7,     // edges of the flagged rows (OvfArgs::flagged_edges)
+    STAT_VETO = 8,             // DAGL_FLAG_NO_WAIT: tag of the last call not served in-stream (sticky)
+    STAT_POLICY = 9,           // top-k threshold policy: 1 = tight (sticky while the owner cookie matches)
+    STAT_GATE = 10,            // gate of the in-call tight re-run
+    STAT_DENSE_RERUN = 11,     // blocks of 64 queries dense_attend_kernel ran a second time
+    STAT_OWNER = 12,           // cookie of the geometry that owns the policy word
+    STAT_NO_REDO_STICKY = 13,  // a DAGL_FLAG_NO_REDO call went unserved (sticky)
+    STAT_WORDS = 16
+};
+
 struct Grid {            // geometry of one image
     int H, W;            // feature map
     int Hp, Wp;          // padded map (H+6, W+6)
@@ -553,7 +575,7 @@ struct RefineArgs {
     int32_t* nb_idx; float* nb_wgt; int32_t* nb_cnt;
     int32_t* redo_flags;            // [B, n_qgroups_exact]: query groups (of 128) the exact kernel must redo
     int n_qgroups_exact;
-    int64_t* stats;                 // [3]: total edges, max degree, overflowed queries
+    int64_t* stats;                 // statistics block (StatWord): STAT_FLAGGED counts the overflowed queries
     int32_t* ovf_list; int32_t* ovf_count; int ovf_cap;    // adaptive mode: overflowed queries are listed for the per-query redo
     float* ovf_qrows;               // ... and their feature rows copied to [ovf_cap, DS] (OvfArgs::qrows)
     float* nb_s;                    // optional [B,L,width]: raw scores of the kept neighbours (saved for backward)
@@ -568,7 +590,7 @@ int launch_refine(hipStream_t s, const RefineArgs& a);
 int launch_rowmax_exact(hipStream_t s, const RefineArgs& a, float* smax);
 int refine_heavy_cap();
 int launch_degree_stats(hipStream_t s, size_t n_rows, const int32_t* nb_cnt, int64_t* stats,
-                        int count_over = 0 /* > 0: stats[2] = rows with a larger degree */);
+                        int count_over = 0 /* > 0: STAT_FLAGGED = rows with a larger degree */);
 
 // per-query dense redo of the queries that overflowed the screened adaptive lists (overflow.hip)
 struct OvfArgs {
@@ -589,7 +611,7 @@ constexpr int OVF_CHUNKS = 32;                                 // = ROW_CHUNKS, 
 constexpr int OVF_PART_FLOATS = P + 8;                         // weighted sum (784) + {max logit, count, z (double), -}
 // flagged rows: scores, masks, weighted sums, combined rows -- and, sharing a launch with the scores, the gather + weighted sum
 // over every query's list (`ag`: what launch_aggregate_direct does; flagged rows are skipped); then total edges / largest degree
-// of the call (stats[0], [1]) and, for the calls that do not wait, *veto = tag when the host would have had to send the call elsewhere
+// of the call (STAT_EDGES, STAT_MAX_DEGREE) and, for the calls that do not wait, *veto = tag when the host would have had to send the call elsewhere
 struct AggArgs;
 int launch_overflow_rows(hipStream_t s, const OvfArgs& a, const AggArgs* ag /* null: the caller gathers, then launch_overflow_apply */,
                          size_t n_rows, int64_t* stats, int32_t* veto = nullptr, int32_t tag = 0);
@@ -619,7 +641,7 @@ int launch_feat_split(hipStream_t s, int B, int rows, int rows_in, int rows_out,
 
 
 int launch_row_degree(hipStream_t s, int n_rows, int splits2, const int32_t* seg_cnt, int32_t* seg_rel,
-                      int32_t* deg, int64_t* stats /* [2]: total edges, max degree */);
+                      int32_t* deg, int64_t* stats /* STAT_EDGES, STAT_MAX_DEGREE */);
 int launch_row_scan(hipStream_t s, int n_rows, const int32_t* deg, int64_t* row_off);
 int topk_slots(int k);
 
@@ -636,7 +658,7 @@ struct DenseArgs {
     float* part_acc; float* part_m; double* part_z; int32_t* part_deg;   // per (split, query) partial results
     float* m_exact; int32_t* redo_blk; int pass;               // [B,L] exact largest logit of a row (written by the first combine), [B, ceil(L/64)]
                                                                // blocks of 64 queries to run again with it as their shift; pass 0 | 1
-    int32_t* redo_count;                                       // how many blocks the first combine flagged (stats[DENSE_RERUN_STAT])
+    int32_t* redo_count;                                       // how many blocks the first combine flagged (STAT_DENSE_RERUN)
     int variant;                                               // debug ablations (DAGL_DENSE_VARIANT): 1 no A V, 2 no S, 4 no staging, 16 constant
                                                                // weights, 32 no zero-granule skip, 64 phase clocks
     unsigned* phase_out;                                       // ablation builds: [blocks][8 waves][8] shader clocks per phase, or null
@@ -644,13 +666,12 @@ struct DenseArgs {
 size_t dense_workspace_bytes(int B, const Grid& g);
 Split16Out dense_split_buffers(void* dense_ws, int B, const Grid& g);    // where launch_dense_attend expects the split features
 void dense_guard_rows(ZeroList& zl, int B, const Grid& g, const Split16Out& so);   // the rows past N / L (guard tiles) must be zero
-constexpr int DENSE_RERUN_STAT = 11;                                     // word of the call's statistics block that counts the re-run blocks
 int launch_dense_attend(hipStream_t s, int B, const Grid& g, const float* wq, const float* x, const float* mt,
                         const float* bs, const float* smax, const float* b2p, void* ws, float* agg, int32_t* deg_out,
-                        float* rowsum_out, int64_t* stats /* [0] += edges, [1] = max degree */, RangeTag range = RangeTag(),
+                        float* rowsum_out, int64_t* stats /* the statistics block (StatWord) */, RangeTag range = RangeTag(),
                         float* lse_out = nullptr /* [B,L,2] {shift M, sum Z} for the backward */,
                         bool features_split = false /* the projection already wrote dense_split_buffers() */,
-                        bool want_stats = true /* stats[0..2]: total edges, largest degree, rows beyond the lists' width */);
+                        bool want_stats = true /* STAT_EDGES, STAT_MAX_DEGREE, STAT_FLAGGED */);
 
 // graph-core backward (backward.hip)
 struct BwdArgs {

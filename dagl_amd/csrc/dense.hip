@@ -958,7 +958,7 @@ int launch_dense_attend(hipStream_t s, int B, const Grid& g, const float* wq, co
     const DnCarve c = dn_carve(ws, B, g);
     a.part_acc = c.part_acc; a.part_m = c.part_m; a.part_z = c.part_z; a.part_deg = c.part_deg;
     a.m_exact = c.m_exact; a.redo_blk = c.redo_blk; a.pass = 0;
-    a.redo_count = reinterpret_cast<int32_t*>(stats + DENSE_RERUN_STAT);
+    a.redo_count = reinterpret_cast<int32_t*>(stats + STAT_DENSE_RERUN);
     uint16_t *xh = c.xh, *xl = c.xl, *qh = c.qh, *ql = c.ql, *vh = c.vh, *vl = c.vl;
     a.v_hi = vh; a.v_lo = vl;
     a.x_hi = xh; a.x_lo = xl; a.wq_hi = qh; a.wq_lo = ql;

@@ -197,12 +197,12 @@ __global__ __launch_bounds__(256) void ovf_combine_kernel(OvfArgs a, size_t n_ro
         if (tid == 0) {
             long long t = 0, f = 0; long long m = 0;
             for (int w = 0; w < 4; ++w) { t += sh_l[w][0]; m = max(m, sh_l[w][1]); f += sh_l[w][2]; }
-            stats[0] = t; stats[1] = m;
+            stats[STAT_EDGES] = t; stats[STAT_MAX_DEGREE] = m;
             if (a.flagged_edges != nullptr) *a.flagged_edges = f;       // what redoing the flagged rows one by one gathers
             if (veto != nullptr) {
                 // the host's verdict (capi.hip, adaptive mode) formed here for the calls that do not wait for it: were the overflowed
                 // queries all redone in-stream?  If not, the fold NaN-fills this call's output and dagl_ce_range_check reports it.
-                const long long ov = stats[2];
+                const long long ov = stats[STAT_FLAGGED];
                 const bool heavy = ov > 0 && ov <= a.cap && f > a.edge_limit;
                 const bool mostly = ov * 2 > (long long)n_rows || heavy;
                 const bool served = ov == 0 || (!mostly && ov <= a.cap);

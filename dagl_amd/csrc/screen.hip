@@ -1457,7 +1457,7 @@ __device__ __forceinline__ void refine_query(const RefineArgs& a, const size_t q
         if (overflow) {
             const size_t qg = (size_t)b * a.n_qgroups_exact + (size_t)(ql - (size_t)b * a.L) / 128;
             a.redo_flags[qg] = 1;
-            atomicAdd(reinterpret_cast<unsigned long long*>(&a.stats[2]), 1ull);
+            atomicAdd(reinterpret_cast<unsigned long long*>(&a.stats[STAT_FLAGGED]), 1ull);
             if (a.ovf_list != nullptr) {                  // adaptive: this query is redone on its own (overflow.hip)
                 ovf_pos = atomicAdd(a.ovf_count, 1);
                 if (ovf_pos < a.ovf_cap) a.ovf_list[ovf_pos] = (int32_t)ql;
@@ -1623,8 +1623,8 @@ int launch_rowmax_exact(hipStream_t s, const RefineArgs& a, float* smax) {
 }
 
 // total / max degree over all queries: one block (a same-address atomic per query would serialise ~12 ns each)
-// stats[0] = total edges, stats[1] = largest degree; count_over > 0: stats[2] = rows whose degree exceeds it (the dense
-// formulation's count of the queries that would not fit the neighbour lists)
+// STAT_EDGES, STAT_MAX_DEGREE; count_over > 0: STAT_FLAGGED = rows whose degree exceeds it (the dense formulation's count of
+// the queries that would not fit the neighbour lists)
 __global__ __launch_bounds__(1024) void degree_stats_kernel(size_t n_rows, const int32_t* __restrict__ nb_cnt,
                                                             int64_t* __restrict__ stats, int count_over) {
     __shared__ long long ssum[16];
@@ -1640,8 +1640,8 @@ __global__ __launch_bounds__(1024) void degree_stats_kernel(size_t n_rows, const
     if (threadIdx.x == 0) {
         long long t = 0; int m = 0, ov = 0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { t += ssum[w]; m = max(m, smax[w]); ov += sover[w]; }
-        stats[0] = t; stats[1] = m;
-        if (count_over > 0) stats[2] = ov;
+        stats[STAT_EDGES] = t; stats[STAT_MAX_DEGREE] = m;
+        if (count_over > 0) stats[STAT_FLAGGED] = ov;
     }
 }
 
@@ -1680,7 +1680,7 @@ __global__ __launch_bounds__(256) void topk_policy_kernel(int64_t* stats, int32_
     __shared__ int go, n_groups;
     if (threadIdx.x == 0) n_groups = 0;
     __syncthreads();
-    if (*policy == 0 && stats[2] > 0) {
+    if (*policy == 0 && stats[STAT_FLAGGED] > 0) {
         int loc = 0;
         for (int e = threadIdx.x; e < n_flags; e += blockDim.x) loc += redo_flags[e] != 0 ? 1 : 0;
         if (loc) atomicAdd(&n_groups, loc);
@@ -1692,7 +1692,7 @@ __global__ __launch_bounds__(256) void topk_policy_kernel(int64_t* stats, int32_
     if (!go) return;
     for (int e = threadIdx.x; e < n_flags; e += blockDim.x) redo_flags[e] = 0;
     __syncthreads();
-    if (threadIdx.x == 0) { stats[0] = 0; stats[1] = 0; stats[2] = 0; *policy = 1; *gate = 1; }
+    if (threadIdx.x == 0) { stats[STAT_EDGES] = 0; stats[STAT_MAX_DEGREE] = 0; stats[STAT_FLAGGED] = 0; *policy = 1; *gate = 1; }
 }
 
 int launch_topk_policy(hipStream_t s, int64_t* stats, int32_t* policy, int32_t* gate, int32_t* redo_flags, int n_flags, long long n_queries) {

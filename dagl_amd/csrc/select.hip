@@ -447,8 +447,8 @@ __global__ __launch_bounds__(256) void row_degree_kernel(int n_rows, int s2, con
     }
     if (lane == 0) {
         deg[row] = run;
-        atomicAdd(&stats[0], (unsigned long long)run);
-        atomicMax(&stats[1], (unsigned long long)run);
+        atomicAdd(&stats[STAT_EDGES], (unsigned long long)run);
+        atomicMax(&stats[STAT_MAX_DEGREE], (unsigned long long)run);
     }
 }
 

@@ -54,6 +54,85 @@ def test_host_side_argument_errors(lib_path):
     assert lib.dagl_feat_rows(100) == 160
 
 
+_FAKE = 0x10000           # a fake device pointer: every call below is rejected before anything reaches the device
+_WS = 0x100000            # a 256-byte aligned fake workspace
+_FORWARD_ENTRIES = ("dagl_ce_forward", "dagl_ce_forward_debug", "dagl_ce_forward_profiled", "dagl_ce_forward_fused",
+                    "dagl_ces_stage_forward", "dagl_ce_core_forward", "dagl_ce_core_dense_forward")
+_FIRST_INPUT = {"dagl_ce_forward": "b1", "dagl_ce_forward_debug": "b1", "dagl_ce_forward_profiled": "b1",
+                "dagl_ce_forward_fused": "x", "dagl_ces_stage_forward": "x", "dagl_ce_core_forward": "wq_rows",
+                "dagl_ce_core_dense_forward": "wq_rows"}
+_THRESHOLD_INPUT = {"dagl_ce_forward_fused": "thr_w", "dagl_ces_stage_forward": "thr_w", "dagl_ce_core_forward": "mu",
+                    "dagl_ce_core_dense_forward": "mu"}
+
+
+def _forward_call(lib, entry, H, W, mode, k, ws, ws_bytes, info, null=()):
+    """One call of a forward entry point on fake pointers; the inputs named in ``null`` are null."""
+    import ctypes as C
+    from dagl_amd import _lib
+    p = lambda name: None if name in null else _FAKE
+    head = (None, 1, H, W)
+    if entry in ("dagl_ce_forward", "dagl_ce_forward_debug", "dagl_ce_forward_profiled"):
+        extra = {"dagl_ce_forward": (), "dagl_ce_forward_debug": (None, None, None), "dagl_ce_forward_profiled": (None,)}[entry]
+        return getattr(lib, entry)(*head, p("b1"), p("b2"), p("thr"), p("bias"), p("fc1_w"), p("fc1_b"), p("fc2_w"), p("fc2_b"),
+                                   mode, k, p("out"), ws, ws_bytes, C.byref(info), *extra)
+    weights = [p(n) for n in ("g_w", "g_b", "theta_w", "theta_b", "thr_w", "thr_b", "bias_w", "bias_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b")]
+    if entry == "dagl_ce_forward_fused":
+        return lib.dagl_ce_forward_fused(*head, p("x"), *weights, mode, k, p("out"), ws, ws_bytes, C.byref(info), None)
+    if entry == "dagl_ces_stage_forward":
+        heads = (_lib.CeWeights * 4)(*[_lib.CeWeights(*weights) for _ in range(4)])
+        return lib.dagl_ces_stage_forward(*head, p("x"), heads, p("mix_w"), p("mix_b"), mode, k, p("out"), ws, ws_bytes, C.byref(info), None)
+    if entry == "dagl_ce_core_forward":
+        return lib.dagl_ce_core_forward(*head, p("wq_rows"), p("x_rows"), p("b2"), p("thr"), p("bias"), mode, k, p("out"), p("nb_idx"),
+                                        p("nb_wgt"), p("nb_s"), p("nb_cnt"), p("mu"), ws, ws_bytes, C.byref(info))
+    return lib.dagl_ce_core_dense_forward(*head, 0, p("wq_rows"), p("x_rows"), p("b2"), p("thr"), p("bias"), p("out"), p("lse"),
+                                          p("mu"), ws, ws_bytes, C.byref(info))
+
+
+def forward_rejections(lib, entry):
+    """Every rejection a forward entry point makes before it touches the device -- null pointers, a misaligned workspace, a
+    workspace one byte short -- over screened / unscreened maps and the adaptive / top-k modes:
+    [(case, rc, dagl_last_error, info fields)]."""
+    from dagl_amd import _lib
+    rows = []
+    for H, W in ((64, 64), (45, 45)):
+        for mode, k in ((0, 0), (1, 8)):
+            cases = [("null out", _WS, 1 << 40, ("out",)), ("null input", _WS, 1 << 40, (_FIRST_INPUT[entry],)),
+                     ("misaligned workspace", _WS + 8, 1 << 40, ()), ("no workspace", _WS, 0, ())]
+            if mode == 0:
+                cases.append(("null threshold input", _WS, 1 << 40, (_THRESHOLD_INPUT.get(entry, "thr"),)))
+            for case, ws, ws_bytes, null in cases:
+                info = _lib.CeInfo(*([77] * 7))
+                rc = _forward_call(lib, entry, H, W, mode, k, ws, ws_bytes, info, null)
+                rows.append(((case, H, W, mode), rc, lib.dagl_last_error(), tuple(getattr(info, n) for n, _ in _lib.CeInfo._fields_)))
+                if case == "no workspace":        # the size it reported, one byte short
+                    short = rows[-1][3][0] - 1
+                    info = _lib.CeInfo(*([77] * 7))
+                    rc = _forward_call(lib, entry, H, W, mode, k, _WS, short, info)
+                    rows.append((("one byte short", H, W, mode), rc, lib.dagl_last_error(),
+                                 tuple(getattr(info, n) for n, _ in _lib.CeInfo._fields_)))
+    return rows
+
+
+@pytest.mark.parametrize("entry", _FORWARD_ENTRIES)
+def test_host_side_forward_rejections(lib_path, entry):
+    """The forward entry points check their pointers and workspace before anything reaches the device: error codes, messages and
+    the workspace size they report."""
+    from dagl_amd import _lib
+    rows = forward_rejections(_lib.load(), entry)
+    for (case, H, W, mode), rc, err, info in rows:
+        what = (entry, case, H, W, mode, err)
+        if case in ("no workspace", "one byte short"):
+            assert rc == _lib.ERR_WORKSPACE, what
+            assert b"workspace" in err and info[0] > 0, what
+        else:
+            assert rc == -1, what
+            assert (b"aligned" in err) if case == "misaligned workspace" else (b"null" in err or b"bad argument" in err
+                                                                               or b"required" in err), what
+    short = [r for r in rows if r[0][0] == "one byte short"]
+    full = [r for r in rows if r[0][0] == "no workspace"]
+    assert [r[3][0] for r in short] == [r[3][0] for r in full]       # one byte short of the size it asked for: the same answer
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from dagl_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
