@@ -220,7 +220,7 @@ __global__ __launch_bounds__(256, MLOOP ? 2 : (CHUNK ? 3 : 4)) void gemm32_kerne
                 float* c = C + (long long)m * g.ldc + n;
                 float v = g.alpha * acc[a][b][r] + bv;
                 if (g.beta != 0.f) v += g.beta * *c;
-                if (g.relu) v = v > 0.f ? v : 0.f;
+                if (g.relu) v = !(v <= 0.f) ? v : 0.f;     // (torch.relu: NaN stays NaN; the same bits for every other value, -0 included)
                 *c = v;
             }
         }
@@ -240,7 +240,7 @@ __global__ void gemm32_reduce_kernel(int slices, int M, int N, const float* __re
     v = alpha * v + (bias ? bias[n] : 0.f);
     float* c = C + (long long)m * ldc + n;
     if (beta != 0.f) v += beta * *c;
-    if (relu) v = v > 0.f ? v : 0.f;
+    if (relu) v = !(v <= 0.f) ? v : 0.f;
     *c = v;
 }
 

@@ -172,10 +172,21 @@ __device__ __forceinline__ float gen_logit(float s, int j, float mtq, float bsq,
     return pass ? __fmul_rn(__fmul_rn(s, m), scale) : 0.f;            // (S m) softmax_scale, dagl.py:259-260
 }
 
+// whether key j makes the reference's softmax row NaN: its logit S m softmax_scale is taken over ALL keys (dagl.py:259), so a
+// non-finite score poisons the row even where the mask is 0 (inf x 0, NaN x 0), and so does a mask value relu(m) that is NaN
+// (relu(NaN) != 0 passes the adaptive test, dagl.py:257) or +inf
+template <int MODE>
+__device__ __forceinline__ bool gen_nonfinite(float s, float mtq, float bsq) {
+    bool bad = !(fabsf(s) < __builtin_inff());
+    if (MODE != 1) bad = bad || !(((s - mtq) + bsq) < __builtin_inff());
+    return bad;
+}
+
 // one block per query row of the chunk: S row -> A row in place
 // (abuf != sbuf: the differentiable path keeps S for its backward)
 // LIST (fixed-k modes, k <= GEN_LIST_MAX): instead of the A row, the row's neighbours as a list of k (key, weight) pairs in key order,
-// empty slots = -1 -- the weighted sum of dagl.py:263-264 is then a gather over k value rows (gather_rows_kernel), not an [Lc,N] x [N,P] product
+// empty slots = -1 -- the weighted sum of dagl.py:263-264 is then a gather over k value rows (gather_rows_kernel), not an [Lc,N] x [N,P] product.
+// A row the reference turns into NaN (gen_nonfinite) gets NaN weights throughout (the list: keys 0..k-1, each with a NaN weight).
 constexpr int GEN_LIST_MAX = GEN_LIST_CAP_WORDS;
 template <int MODE, bool LIST = false>
 __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long ldn, int L, int l0, int b, int k, float scale,
@@ -222,12 +233,16 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
         }
     }
     float mx = -__builtin_inff(); int cnt = 0;                     // the softmax runs over ALL keys: a masked key's logit is 0 (dagl.py:259: yi * mask)
+    bool bad = false;
     for (int j = tid; j < N; j += 256) {
         bool pass;
         const float l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
         cnt += pass ? 1 : 0;
         mx = fmaxf(mx, l);
+        bad = bad || gen_nonfinite<MODE>(row[j], mtq, bsq);
     }
+    const bool row_nan = __syncthreads_or(bad) != 0;
+    const float qnan = __int_as_float(0x7fc00000);
     const float M = gen_block_max(mx, shf);
     double z = 0.0;
     for (int j = tid; j < N; j += 256) {
@@ -236,7 +251,9 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
         z += (double)expf(l - M);
     }
     const float invz = (float)(1.0 / gen_block_sum(z, shd));
-    if (LIST) {
+    if (LIST && row_nan) {
+        for (int e = tid; e < k; e += 256) { nb_idx[(size_t)lr * k + e] = e; nb_wgt[(size_t)lr * k + e] = qnan; }
+    } else if (LIST) {
         // ordered compaction of the (at most k) passing keys: positions by ballot + wave offsets, no atomics -- the list (and with it the
         // gather's summation order) is the same on every run
         int32_t* li = nb_idx + (size_t)lr * k;
@@ -264,6 +281,10 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
             const float l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
             arow[j] = pass ? expf(l - M) * invz : 0.f;             // softmax * mask_b, dagl.py:260-261
         }
+        // (a loop of its own: folded into the select above, the compiler fused "l - M" into an FMA there, and the finite rows' weights
+        // no longer used the z sum's rounding of l)
+        if (row_nan)
+            for (int j = tid; j < N; j += 256) arow[j] = qnan;
         for (int j = N + tid; j < ldn; j += 256) arow[j] = 0.f;
     }
     const double Cn = gen_block_sum((double)cnt, shd);

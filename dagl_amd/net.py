@@ -63,7 +63,10 @@ class CES(nn.Module):
         k_eff = 0 if mode in (None, "adaptive") else min(int(heads[0].select_k), x.shape[-2] * x.shape[-1])
         # (an eval() stage fed a constant input under an autograd-enabled test loop counts as "no gradient wanted", like CE)
         no_grad = not torch.is_grad_enabled() or (not self.training and not x.requires_grad)
-        if self.fuse_stage and all(isinstance(hd, CE) for hd in heads) and x.is_cuda and x.dtype == torch.float32 \
+        # the fused launch set has the default head compiled in: a head with another patch geometry or input width, or a subclass
+        # with a forward of its own, goes head by head
+        if self.fuse_stage and all(isinstance(hd, CE) and not hd._generic and hd.in_channels == 64 and type(hd).forward is CE.forward
+                                   for hd in heads) and x.is_cuda and x.dtype == torch.float32 \
                 and no_grad and len({(hd.select_mode, hd.select_k, hd.scan) for hd in heads}) == 1 \
                 and heads[0].scan == "screened" and self._skip_fused[s] == 0 and 0 <= k_eff <= MAX_TOPK \
                 and all(float(hd.softmax_scale) == 10.0 for hd in heads) \

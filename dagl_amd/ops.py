@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import DS, MODES, P, DaglError, check
+from ._lib import D, DS, MODES, P, DaglError, check
 
 
 # A/B switch (tests, bench.py --dense-backward fp32): the dense graph core's backward with its five matrix products on the fp32
@@ -541,20 +541,30 @@ def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: i
                       weights_packed: bool = False, tight_topk: bool = False, sampled_topk: bool = False):
     """One CES stage in one launch set: ``conv1x1(cat(head_1(x)..head_4(x))) + x`` (dagl.py:114,116,118).
     ``head_params``: four dicts (state_dict names -> contiguous fp32 GPU tensors).  Returns (out [B,64,H,W], info), or
-    (None, info) when a dense adaptive neighbourhood needs the per-head path."""
-    lib = _lib.load()
+    (None, info) when a dense adaptive neighbourhood needs the per-head path.  The library reads the default head's weights
+    (ksize 7, inter_channels 16) through raw pointers: every tensor's shape is checked here first."""
     if mode not in MODES:
         raise DaglError(f"unknown mode {mode!r}")
     _need(x, "x"); _need(mix_w, "mix_w"); _need(mix_b, "mix_b")
     B, c, H, W = x.shape
     if c != 64 or len(head_params) != 4:
         raise DaglError("ces_stage_forward: x must be [B,64,H,W] and there must be four heads")
+    if tuple(mix_w.shape) != (64, 64, 1, 1) or tuple(mix_b.shape) != (64,):
+        raise DaglError(f"ces_stage_forward: mix_w is {tuple(mix_w.shape)}, mix_b {tuple(mix_b.shape)}; expected (64, 64, 1, 1) and (64,)")
+    want = {"g.weight": (16, 64, 3, 3), "g.bias": (16,), "theta.weight": (16, 64, 1, 1), "theta.bias": (16,),
+            "thr_conv.weight": (1, 64, 7, 7), "thr_conv.bias": (1,), "bias_conv.weight": (1, 64, 7, 7), "bias_conv.bias": (1,),
+            "fc1.0.weight": (D, P), "fc1.0.bias": (D,), "fc2.0.weight": (D, P), "fc2.0.bias": (D,)}
     arr = (_lib.CeWeights * 4)()
     for h, prm in enumerate(head_params):
         for field, name in zip([f for f, _ in _lib.CeWeights._fields_], _lib.CeWeights.NAMES):
+            if name not in prm:
+                raise DaglError(f"ces_stage_forward: head {h} has no {name}")
             t = prm[name]
             _need(t, name)
+            if tuple(t.shape) != want[name]:
+                raise DaglError(f"ces_stage_forward: head {h} {name} is {tuple(t.shape)}, expected {want[name]}")
             setattr(arr[h], field, t.data_ptr())
+    lib = _lib.load()
     ws = workspace if workspace is not None else Workspace()
     need = lib.dagl_ces_stage_workspace_bytes(B, H, W, MODES[mode], int(k))
     if need == 0:

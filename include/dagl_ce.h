@@ -507,7 +507,9 @@ int dagl_scores_dense(void* stream, int B, int L, int N, const float* wq, const 
  *   DAGL_MODE_TOPK), fc1_w / fc2_w [P/4, P] over Unfold's (c,kh,kw) patch order with P = ksize^2 c -- the state_dict's own
  *   layouts, nothing pre-packed;  out [B,c,H,W];  degree [B*L] int32 or NULL (neighbours per query);  Cin and c multiples of 4.
  *   softmax_scale: dagl.py:175 (10 by default), any positive value.  k: the fixed-k modes' num_edge (min(k, N) keys are kept).
- * A geometry whose F.fold block grid does not hold exactly the L query patches raises in the reference; here DAGL_ERR_INVALID.  */
+ * A geometry whose F.fold block grid does not hold exactly the L query patches raises in the reference; here DAGL_ERR_INVALID.
+ * Non-finite input: a query whose score row holds a NaN / inf score, or a NaN / +inf mask value, gets NaN weights for every key,
+ * as the reference's softmax over all keys does (so a NaN or inf pixel makes its whole image NaN); the ReLUs keep NaN.  */
 size_t dagl_ce_generic_workspace_bytes(int B, int Cin, int H, int W, int ksize, int stride_1, int stride_2, int inter_channels);
 int dagl_ce_generic_forward(void* stream, int B, int Cin, int H, int W, int ksize, int stride_1, int stride_2, int inter_channels,
                             float softmax_scale, int mode, int k, const float* x,
