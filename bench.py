@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the patch-graph attention head on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode topk|adaptive] [--k 8] [--size 256] [--batch 1] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode topk|adaptive] [--k 8] [--size 256] [--batch 1] [--dump-outputs DIR] [--full]
 
 A "step" is one forward of one ``CE`` head (prologue convolutions + the whole HIP block) over one batch
 of synthetic feature maps ``[batch,64,size,size]`` that is already resident in HBM.  Default workload =
@@ -12,14 +12,18 @@ its own N ranks (dagl_amd/launch.py: re-executes itself with RANK / LOCAL_RANK /
 rank 0 prints); launched under ``python -m torch.distributed.run --nproc-per-node N`` it uses the ranks it is
 given.  The line carries ``n_ranks_seen`` (the process group's own world size) and every rank's device name.
 
-Rank 0 prints ONE JSON line: whole-job query-patches/s, plus
+A plain run sets up, warms up (W + K untimed steps, --prewarm seconds of passes, W steps), times the K steps, writes
+--dump-outputs and prints the line.  Rank 0 prints ONE JSON line: whole-job query-patches/s, plus
   roofline      the dominant kernel (screen_kernel<1>: the full L x N similarity scan + candidate filter on the
                 bf16 matrix cores, v_mfma_f32_32x32x16_bf16; the fp32-MFMA score_select_kernel with --scan exact):
                 algorithmic FLOP per launch / its mean duration, measured live with hipEvents at the stage
                 boundaries of the very steps that are timed (dagl_profile_*, recorded on the launch stream)
-  roofline_gather  the stand-alone gather/weighted-sum kernel over materialised value rows (HBM bound,
+  roofline_gather  (--full) the stand-alone gather/weighted-sum kernel over materialised value rows (HBM bound,
                 algorithmic bytes (k+1)*4P+8k per query) and the fused in-block gather
-  cpu_baseline  the dense CPU oracle (a port of the reference's algorithm) timed on this box's host cores
+  cpu_baseline  (--full) the dense CPU oracle (a port of the reference's algorithm) timed on the host's cores
+``--full`` runs every other leg that takes runs of its own as well: the cold figure (``ms_per_step_cold``), the stage profile
+(``stage_ms``), ``roofline.sustained``, ``quality``, ``extra_configs``; with --train the GEMM ``roofline`` and ``allreduce_ms``.
+A plain run does not measure them.
 """
 from __future__ import annotations
 
@@ -74,14 +78,18 @@ def parse():
     ap.add_argument("--fseed", type=int, default=None, help="seed of the synthetic feature maps (+ rank); default: the per-rank stream of seed 100")
     ap.add_argument("--prewarm", type=float, default=0.5,
                     help="seconds of untimed passes before the W warm-up steps (clock ramp of an idle GPU); 0 = none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-quality", action="store_true", help="skip the Set12 sigma=50 PSNR-delta leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every leg that takes runs of its own (cold figure, stage profile, sustained matrix "
+                         "rate, stand-alone gather, quality, extra configurations, CPU baseline; --train: GEMM roofline, all-reduce); "
+                         "a plain run only warms up, times the steps, dumps and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU-baseline leg")
+    ap.add_argument("--no-quality", action="store_true", help="--full: skip the Set12 sigma=50 PSNR-delta leg")
     ap.add_argument("--miopen-probe-limit", type=float, default=75.0,
                     help="seconds a child process may take to start and run its first stock convolutions (usually ~12) before the legs that run "
                          "the trunk (quality, Set12 features, training steps) are skipped with a note (a cold MIOpen on slow storage: minutes)")
     ap.add_argument("--cpu-size", type=int, default=0, help="feature-map size of the CPU-baseline sample (default: --size)")
     ap.add_argument("--cpu-runs", type=int, default=5, help="timed forwards of the CPU baseline (median reported)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs block (other BASELINE configs, short runs)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra_configs block (other BASELINE configs, short runs)")
     ap.add_argument("--stub", action="store_true",
                     help="launcher self-test: the same spawn / rendezvous / barrier / MAX-over-ranks / one-JSON-line protocol with "
                          "a trivial CPU step on the gloo backend (tests/test_bench_spawn.py); not a measurement")
@@ -761,7 +769,7 @@ def train_bench(args, dev, dist, world, rank):
     devices = rank_devices(dist, torch.cuda.get_device_name(dev))
     n_par = sum(p.numel() for p in net.parameters() if p.requires_grad)
     allreduce_ms = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the collective on its own (outside the timed steps): one all-reduce of a gradient-sized fp32 buffer over RCCL
         flat = torch.zeros(n_par, device=dev)
         for _ in range(3):
@@ -782,7 +790,7 @@ def train_bench(args, dev, dist, world, rank):
                                        f"{args.crop},{args.crop}] per GPU, MSE(sum)/(2B) loss, Adam, gradients of "
                                        f"{n_par} parameters all-reduced over RCCL",
                            "parallelism": f"ddp{world}", "select_mode": args.mode, "k": args.k, "batch_per_gpu": B},
-                "roofline": gemm_roofline(dev, B, args.crop), "cpu_baseline": None,
+                "full": args.full, "cpu_baseline": None,
                 "allreduce_ms": allreduce_ms, "allreduce_bytes": 4 * n_par if dist is not None else None,
                 "ddp": {"what": "dagl_amd.train.wrap_ddp: torch DistributedDataParallel over RCCL, one process per GPU",
                         "bucket_cap_mb": 12, "gradient_as_bucket_view": True, "broadcast_buffers": False,
@@ -798,6 +806,8 @@ def train_bench(args, dev, dist, world, rank):
                                          "latency terms ignored -- an expectation, NOT a measurement: no multi-GPU node was available to "
                                          "this repository's rounds; `allreduce_ms` above is the live figure of THIS run's world size"},
                 "loss_first_last": [float(losses[0]), float(losses[-1])] if losses else None}
+        if args.full:
+            line["roofline"] = gemm_roofline(dev, B, args.crop)
         if args.dump_outputs:
             line["dump_outputs"] = dump_outputs(args.dump_outputs, {"loss": last[0], "psnr": last[1]})
         print(json.dumps(line))
@@ -898,7 +908,9 @@ def main():
             last["out"] = ce(x)
     with torch.no_grad():
         # the COLD figure first (what --prewarm 0 reports): W warm-up steps on a GPU that sat idle while the case was built, then K
-        # timed steps -- kept beside the sustained figure in the line ("ms_per_step_cold")
+        # timed steps -- kept beside the sustained figure in the --full line ("ms_per_step_cold").  A plain run makes the same
+        # passes without reporting them: ms_per_step has always been measured after them (without them it came out ~1 % lower,
+        # 0.2272 against 0.2292 ms over 7 interleaved runs each at --steps 20 --warmup 5)
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -926,21 +938,23 @@ def main():
         elapsed = time.perf_counter() - t0
         timed_out = last["out"]               # what the last timed step returned (the passes below leave it alone)
         dominant_ms = [c[6 if dense_regime else 4] for c in prof.read()]
-        prof.select_stage(-1)
-        for _ in range(min(args.steps, 20)):
-            step(prof)
-        torch.cuda.synchronize()
+        stage_ms = []
+        if args.full:
+            prof.select_stage(-1)
+            for _ in range(min(args.steps, 20)):
+                step(prof)
+            torch.cuda.synchronize()
+            stage_ms = prof.read()
         ce.profile = None
     elapsed = reduce_max_seconds(elapsed, dist, dev)
     devices = rank_devices(dist, torch.cuda.get_device_name(dev))
-    stage_ms = prof.read()
     info = info_box["info"] if args.stage else ce.last_info
 
     # stand-alone gather kernel over materialised value rows (rank 0 only; outside the timed region).  The launches rotate
     # over GATHER_SETS distinct (idx, wgt, rows, out) sets: 4 x (205 MB of rows + 12.8 MB out) = 0.87 GB at 256^2, more than
     # three times the 256 MiB Infinity Cache, so no launch finds its rows on the die from the previous one.
     gather = None
-    if rank == 0:
+    if rank == 0 and args.full:
         GATHER_SETS = 4
         with torch.no_grad():
             pf = ce._params_f32()                                   # (the library's own prologue: no MIOpen kernel in the profile of this command)
@@ -1007,7 +1021,7 @@ def main():
             roofline["traffic_source"] = TRAFFIC_SOURCE
         if gather is not None and gather.get("traffic") is not None:
             gather["traffic_source"] = TRAFFIC_SOURCE
-        if screened:
+        if screened and args.full:
             roofline["sustained"] = mfma_sustained(dev, peak)
             if roofline["sustained"]:
                 roofline["frac_of_sustained"] = ach / roofline["sustained"]["mfma_only_tflops"]
@@ -1026,8 +1040,7 @@ def main():
             "value": total_patches / elapsed, "unit": "patches/s", "n_gpus": world,
             "n_ranks_seen": dist.get_world_size() if dist is not None else 1, "devices": devices, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / max(args.steps, 1) * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "ms_per_step_cold": cold_ms,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "prewarm": {"seconds": args.prewarm, "untimed_steps": prewarm_steps,
                         "note": "untimed passes of the same step before the W warm-up steps: an idle GPU runs its first tens "
                                 "of ms below the sustained clock (--prewarm 0 shows the cold figure)"},
@@ -1041,25 +1054,27 @@ def main():
                        "selection_path": (info or {}).get("path"), "max_degree": (info or {}).get("max_degree")},
             "roofline": roofline,
             "roofline_gather": gather,
-            "stage_ms": {STAGE_NAMES[i]: float(mean_ms[i]) for i in range(8)},
-            "stage_ms_note": "separate instrumented pass after the timed steps (nine event records per call add ~35 us)",
-            "hip_block_ms": float(mean_ms.sum()),
         }
+        if args.full:
+            line["ms_per_step_cold"] = cold_ms
+            line["stage_ms"] = {STAGE_NAMES[i]: float(mean_ms[i]) for i in range(8)}
+            line["stage_ms_note"] = "separate instrumented pass after the timed steps (nine event records per call add ~35 us)"
+            line["hip_block_ms"] = float(mean_ms.sum())
         # The optional legs below run the trunk's stock convolutions (MIOpen).  On a box whose MIOpen start-up is slow (cold kernel
         # database on slow storage: one pool box in round 6 spent 313 s in the quality leg that takes 4.6 s elsewhere) they would
         # turn a two-minute command into ten: one probe convolution decides.
         trunk_ok, probe_s = True, 0.0
-        if world == 1 and not args.stage and not (args.no_quality and args.no_extra):
+        if world == 1 and args.full and not args.stage and not (args.no_quality and args.no_extra):
             probe_s = miopen_probe_seconds(dev, args.miopen_probe_limit)
             trunk_ok = probe_s != float("inf")
             line["miopen_probe_s"] = probe_s if trunk_ok else None
-        if world == 1 and not args.no_quality and not args.stage:
+        if world == 1 and args.full and not args.no_quality and not args.stage:
             line["quality"] = quality_leg(dev) if trunk_ok else {
                 "skipped": f"a child process was not through its first stock convolutions after {args.miopen_probe_limit:.0f} s: MIOpen is cold on "
                            "this box; tests/test_gpu_set12_psnr.py asserts the same figure (max |delta PSNR| <= 0.02 dB)"}
-        if world == 1 and not args.no_extra and not args.stage and (H, mode, k, B) == (256, "topk", 8, 1):
+        if world == 1 and args.full and not args.no_extra and not args.stage and (H, mode, k, B) == (256, "topk", 8, 1):
             line["extra_configs"] = extra_configs(dev, trunk_ok=trunk_ok)
-        if world == 1 and not args.no_cpu_baseline and not args.stage:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.stage:
             with torch.no_grad():
                 hip_out = ce(x[:1]).cpu()
             line["cpu_baseline"] = cpu_baseline(args, params, mode, k, x_cpu=x[:1].cpu(), hip_out=hip_out)

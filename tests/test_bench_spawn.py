@@ -80,7 +80,7 @@ def test_more_gpus_than_visible_is_refused_with_a_clear_message():
 @pytest.mark.parametrize("train", [False, True])
 def test_gpu_spawn_path_through_rccl_at_one_rank(train):
     cmd = [sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1"]
-    cmd += ["--train", "--batch", "2", "--crop", "64"] if train else ["--size", "64", "--no-quality", "--no-cpu-baseline", "--no-extra"]
+    cmd += ["--train", "--batch", "2", "--crop", "64", "--full"] if train else ["--size", "64", "--no-quality", "--no-cpu-baseline", "--no-extra"]
     r = subprocess.run(cmd, env=_clean_env(DAGL_BENCH_FORCE_SPAWN="1", HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True,
                        text=True, timeout=900, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -379,7 +379,7 @@ def test_config5_rccl_process_group_on_one_gpu():
     env = dict(os.environ, DAGL_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", RANK="0",
                LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--train", "--steps", "2", "--warmup", "1",
-                        "--batch", "4", "--crop", "64"], env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
+                        "--batch", "4", "--crop", "64", "--full"], env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["config"]["parallelism"] == "ddp1" and line["allreduce_ms"] is not None and line["allreduce_ms"] > 0

@@ -2,11 +2,12 @@
 # Run ON THE GPU BOX: the two SQ counter passes of the default benchmark, per-kernel means printed for kernels matching $2.
 #   tools/pmc_sq.sh <tag> <kernel substring> [extra bench args]
 set -u
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; PAT=$2; shift 2
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-quality --no-extra $*"
+CMD="python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-quality --no-extra $*"
 timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $OUT/sq -o k -- $CMD > $OUT/sq.log 2>&1
 timeout 600 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU --kernel-trace --output-format csv -d $OUT/sq2 -o k -- $CMD > $OUT/sq2.log 2>&1
 python - <<PY
