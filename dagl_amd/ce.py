@@ -26,118 +26,94 @@ from .synth import same_pad_amounts
 
 
 class _GraphCore(torch.autograd.Function):
-    """dagl.py:250-272 as one differentiable op: HIP forward (``dagl_ce_core_forward``) keeps each query's neighbour
-    list, HIP backward (``dagl_ce_core_backward``) returns the gradients autograd would derive from the dense form."""
+    """dagl.py:250-272 as one differentiable op.  ``route`` = (forward, backward), the pair of HIP entry points the call took
+    (``_lists_route`` .. ``_generic_route``): ``forward(wq_rows, x_rows, b2, thr, bias) -> (out, saved, info | None)`` and
+    ``backward(d_out, wq_rows, x_rows, b2, thr, bias, *saved) -> (d_wq_rows, d_x_rows, d_b2, d_thr, d_bias)``.  ``thr`` /
+    ``bias`` are None in mode "topk"; ``sink`` (a dict or None) takes the forward's info when it has one."""
 
     @staticmethod
-    def forward(ctx, wq_rows, x_rows, b2, thr, bias, mode, k, exact_scan, ws_f, ws_b, sink):
+    def forward(ctx, wq_rows, x_rows, b2, thr, bias, route, sink):
         wq_rows, x_rows, b2 = wq_rows.contiguous(), x_rows.contiguous(), b2.contiguous()
-        adaptive = mode != "topk"
-        thr_c = thr.contiguous() if adaptive else None
-        bias_c = bias.contiguous() if adaptive else None
-        out, saved = ops.ce_core_forward(wq_rows, x_rows, b2, thr_c, bias_c, mode=mode, k=k, workspace=ws_f,
-                                         exact_scan=exact_scan)
-        ctx.mode, ctx.k, ctx.ws_b, ctx.adaptive = mode, k, ws_b, adaptive
-        ctx.thr_shape = thr.shape if adaptive else None
-        tensors = [wq_rows, x_rows, b2, saved["nb_idx"], saved["nb_wgt"], saved["nb_s"], saved["nb_cnt"]]
-        if adaptive:
-            tensors += [thr_c, bias_c, saved["mu"]]
-        ctx.save_for_backward(*tensors)
-        if sink is not None:
-            sink.update(saved["info"])
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        t = ctx.saved_tensors
-        wq_rows, x_rows, b2, nb_idx, nb_wgt, nb_s, nb_cnt = t[:7]
-        thr, bias, mu = (t[7], t[8], t[9]) if ctx.adaptive else (None, None, None)
-        saved = dict(nb_idx=nb_idx, nb_wgt=nb_wgt, nb_s=nb_s, nb_cnt=nb_cnt, mu=mu)
-        d_wq, d_x, d_b2, d_thr, d_bias = ops.ce_core_backward(d_out.contiguous().float(), wq_rows, x_rows, b2, thr, bias,
-                                                              saved, mode=ctx.mode, k=ctx.k, workspace=ctx.ws_b)
-        if ctx.adaptive:
-            d_thr, d_bias = d_thr.view(ctx.thr_shape), d_bias.view(ctx.thr_shape)
-        return d_wq, d_x, d_b2, d_thr, d_bias, None, None, None, None, None, None
-
-
-class _GraphCoreDense(torch.autograd.Function):
-    """dagl.py:250-272 for dense neighbourhoods (adaptive masks that keep more keys than a fixed-width list holds --
-    default-initialised heads keep ~95 %): the dense formulation (``dagl_ce_core_dense_forward`` / ``_backward``): the forward
-    on the streamed split-fp16 kernel, the backward's matrix products on the fp16 matrix cores with split operands
-    (``exact``: both on the fp32 matrix cores; dense_train.hip)."""
-
-    @staticmethod
-    def forward(ctx, wq_rows, x_rows, b2, thr, bias, ws_f, ws_b, sink, want_info, exact=False):
-        wq_rows, x_rows, b2 = wq_rows.contiguous(), x_rows.contiguous(), b2.contiguous()
-        thr_c, bias_c = thr.contiguous(), bias.contiguous()
-        out, saved = ops.ce_core_dense_forward(wq_rows, x_rows, b2, thr_c, bias_c, workspace=ws_f, want_info=want_info,
-                                               exact=exact)
-        ctx.ws_b, ctx.thr_shape, ctx.exact = ws_b, thr.shape, bool(exact)
-        ctx.save_for_backward(wq_rows, x_rows, b2, thr_c, bias_c, saved["lse"], saved["mu"])
-        if sink is not None and saved["info"] is not None:
-            sink.update(saved["info"])
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        wq_rows, x_rows, b2, thr, bias, lse, mu = ctx.saved_tensors
-        d_wq, d_x, d_b2, d_thr, d_bias = ops.ce_core_dense_backward(d_out.contiguous().float(), wq_rows, x_rows, b2, thr, bias,
-                                                                    dict(lse=lse, mu=mu), workspace=ctx.ws_b, exact=ctx.exact)
-        return d_wq, d_x, d_b2, d_thr.view(ctx.thr_shape), d_bias.view(ctx.thr_shape), None, None, None, None, None
-
-
-class _GraphCoreGeneric(torch.autograd.Function):
-    """dagl.py:250-272 under autograd for a module built with a non-default patch geometry (``dagl_ce_generic_core_forward`` /
-    ``_backward``, csrc/generic.hip): the dense formulation on the fp32 matrix cores, S and A recomputed chunk by chunk in the backward."""
-
-    @staticmethod
-    def forward(ctx, wq_rows, x_rows, b2p, thr, bias, geom, mode, k, scale, ws_f, ws_b):
-        H, W, ks, s1, s2 = geom
-        heads = mode != "topk"
-        wq_rows, x_rows, b2p = wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous()
-        thr_c, bias_c = (thr.contiguous(), bias.contiguous()) if heads else (None, None)
-        out = ops.ce_generic_core_forward(wq_rows, x_rows, b2p, thr_c, bias_c, H, W, ks, s1, s2, mode=mode, k=k, softmax_scale=scale, workspace=ws_f)
-        ctx.geom, ctx.mode, ctx.k, ctx.scale, ctx.ws_b, ctx.heads = geom, mode, k, scale, ws_b, heads
-        ctx.save_for_backward(*([wq_rows, x_rows, b2p] + ([thr_c, bias_c] if heads else [])))
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        wq_rows, x_rows, b2p, *tb = ctx.saved_tensors
-        thr, bias = tb if ctx.heads else (None, None)
-        H, W, ks, s1, s2 = ctx.geom
-        d_wq, d_x, d_b2p, d_thr, d_bias = ops.ce_generic_core_backward(d_out.contiguous().float(), wq_rows, x_rows, b2p, thr, bias, H, W, ks, s1, s2,
-                                                                       mode=ctx.mode, k=ctx.k, softmax_scale=ctx.scale, workspace=ctx.ws_b)
-        return d_wq, d_x, d_b2p, d_thr, d_bias, None, None, None, None, None, None
-
-
-class _GraphCoreWide(torch.autograd.Function):
-    """dagl.py:250-272 in the top-k modes when min(k, N) exceeds the lists' width (the fixed-k variant takes any num_edge,
-    GReccR2b_3mh_1-checkpoint.py:242-250; CA_model-checkpoint.py:134-143 uses 500): the dense formulation with the row-wise
-    selection of the k best scores as its mask (``dagl_ce_core_wide_forward`` / ``_backward``; dense_train.hip, wide_select.h)."""
-
-    @staticmethod
-    def forward(ctx, wq_rows, x_rows, b2, thr, bias, mode, k, ws_f, ws_b, sink):
-        wq_rows, x_rows, b2 = wq_rows.contiguous(), x_rows.contiguous(), b2.contiguous()
-        heads = mode != "topk"
-        thr_c, bias_c = (thr.contiguous(), bias.contiguous()) if heads else (None, None)
-        out, info = ops.ce_core_wide_forward(wq_rows, x_rows, b2, thr_c, bias_c, mode, k, workspace=ws_f, want_info=sink is not None)
-        ctx.ws_b, ctx.mode, ctx.k, ctx.heads = ws_b, mode, k, heads
-        ctx.thr_shape = thr.shape if heads else None
-        ctx.save_for_backward(*([wq_rows, x_rows, b2] + ([thr_c, bias_c] if heads else [])))
+        thr_c = thr.contiguous() if thr is not None else None
+        bias_c = bias.contiguous() if bias is not None else None
+        out, saved, info = route[0](wq_rows, x_rows, b2, thr_c, bias_c)
+        ctx.backward_fn, ctx.thr_shape = route[1], thr.shape if thr is not None else None
+        ctx.save_for_backward(wq_rows, x_rows, b2, thr_c, bias_c, *saved)
         if sink is not None and info is not None:
             sink.update(info)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        wq_rows, x_rows, b2, *tb = ctx.saved_tensors
-        thr, bias = tb if ctx.heads else (None, None)
-        d_wq, d_x, d_b2, d_thr, d_bias = ops.ce_core_wide_backward(d_out.contiguous().float(), wq_rows, x_rows, b2, thr, bias,
-                                                                   ctx.mode, ctx.k, workspace=ctx.ws_b)
-        if ctx.heads:
+        d_wq, d_x, d_b2, d_thr, d_bias = ctx.backward_fn(d_out.contiguous().float(), *ctx.saved_tensors)
+        if ctx.thr_shape is not None:
             d_thr, d_bias = d_thr.view(ctx.thr_shape), d_bias.view(ctx.thr_shape)
-        return d_wq, d_x, d_b2, d_thr, d_bias, None, None, None, None, None
+        return d_wq, d_x, d_b2, d_thr, d_bias, None, None
+
+
+def _lists_route(mode, k, exact_scan, ws_f, ws_b):
+    """Each query's neighbour list (``dagl_ce_core_forward`` / ``_backward``): the backward returns the gradients autograd would
+    derive from the dense form."""
+    def forward(wq_rows, x_rows, b2, thr, bias):
+        out, s = ops.ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode=mode, k=k, workspace=ws_f, exact_scan=exact_scan)
+        return out, (s["nb_idx"], s["nb_wgt"], s["nb_s"], s["nb_cnt"], s["mu"]), s["info"]
+
+    def backward(d_out, wq_rows, x_rows, b2, thr, bias, nb_idx, nb_wgt, nb_s, nb_cnt, mu):
+        saved = dict(nb_idx=nb_idx, nb_wgt=nb_wgt, nb_s=nb_s, nb_cnt=nb_cnt, mu=mu)
+        return ops.ce_core_backward(d_out, wq_rows, x_rows, b2, thr, bias, saved, mode=mode, k=k, workspace=ws_b)
+    return forward, backward
+
+
+def _dense_route(want_info, exact, ws_f, ws_b):
+    """Dense neighbourhoods (adaptive masks that keep more keys than a fixed-width list holds -- default-initialised heads keep
+    ~95 %): the dense formulation (``dagl_ce_core_dense_forward`` / ``_backward``): the forward on the streamed split-fp16 kernel,
+    the backward's matrix products on the fp16 matrix cores with split operands (``exact``: both on the fp32 matrix cores;
+    dense_train.hip).  Statistics only with ``want_info`` (a host synchronisation)."""
+    def forward(wq_rows, x_rows, b2, thr, bias):
+        out, s = ops.ce_core_dense_forward(wq_rows, x_rows, b2, thr, bias, workspace=ws_f, want_info=want_info, exact=exact)
+        return out, (s["lse"], s["mu"]), s["info"]
+
+    def backward(d_out, wq_rows, x_rows, b2, thr, bias, lse, mu):
+        return ops.ce_core_dense_backward(d_out, wq_rows, x_rows, b2, thr, bias, dict(lse=lse, mu=mu), workspace=ws_b, exact=exact)
+    return forward, backward
+
+
+def _wide_route(mode, k, want_info, ws_f, ws_b):
+    """The top-k modes when min(k, N) exceeds the lists' width (the fixed-k variant takes any num_edge,
+    GReccR2b_3mh_1-checkpoint.py:242-250; CA_model-checkpoint.py:134-143 uses 500): the dense formulation with the row-wise
+    selection of the k best scores as its mask (``dagl_ce_core_wide_forward`` / ``_backward``; dense_train.hip, wide_select.h)."""
+    def forward(wq_rows, x_rows, b2, thr, bias):
+        out, info = ops.ce_core_wide_forward(wq_rows, x_rows, b2, thr, bias, mode, k, workspace=ws_f, want_info=want_info)
+        return out, (), info
+
+    def backward(d_out, wq_rows, x_rows, b2, thr, bias):
+        return ops.ce_core_wide_backward(d_out, wq_rows, x_rows, b2, thr, bias, mode, k, workspace=ws_b)
+    return forward, backward
+
+
+def _generic_route(geom, mode, k, scale, ws_f, ws_b):
+    """A module built with a non-default patch geometry ``geom`` = (H, W, ksize, stride_1, stride_2)
+    (``dagl_ce_generic_core_forward`` / ``_backward``, csrc/generic.hip): the dense formulation on the fp32 matrix cores, S and A
+    recomputed chunk by chunk in the backward; ``b2`` is the zero-bordered NHWC value map."""
+    def forward(wq_rows, x_rows, b2p, thr, bias):
+        return ops.ce_generic_core_forward(wq_rows, x_rows, b2p, thr, bias, *geom, mode=mode, k=k, softmax_scale=scale,
+                                           workspace=ws_f), (), None
+
+    def backward(d_out, wq_rows, x_rows, b2p, thr, bias):
+        return ops.ce_generic_core_backward(d_out, wq_rows, x_rows, b2p, thr, bias, *geom, mode=mode, k=k, softmax_scale=scale,
+                                            workspace=ws_b)
+    return forward, backward
+
+
+_CONV_WEIGHTS = ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight")
+
+
+def _pad_channels4(t):
+    """Zero channels along dim -3 -- the channels of a map [B,C,H,W], the input channels of a convolution weight [O,C,kh,kw] -- up to
+    a multiple of 4: the library's unfold and prologue kernels work on float4 channel groups; zero channels with zero weight columns
+    change nothing (under autograd the pad's backward slices them off)."""
+    padc = (-t.shape[-3]) % 4
+    return F.pad(t, (0, 0, 0, 0, 0, padc)) if padc else t
 
 
 class _EvalLazyGrad(torch.autograd.Function):
@@ -334,11 +310,12 @@ class CE(nn.Module):
             return 1.0
         return r if self.select_mode == "topk" else math.sqrt(r)
 
-    def _params_f32(self):
+    def _params_f32(self, scaled: bool = True):
         """The block's parameters as contiguous fp32 tensors.  fp32 modules: the parameters themselves.  ``model.half()`` /
         ``.bfloat16()`` modules (the reference's ``--precision half`` test path, DN_Gray/model/__init__.py:98-99,
         option.py:76-78): converted once and kept until the parameter changes (storage or version counter) -- the block
-        computes in fp32 on the values the half-precision weights hold."""
+        computes in fp32 on the values the half-precision weights hold.  ``scaled``: fc1 and the bias head carry the factor of
+        ``_scale_c`` (the generic route hands ``softmax_scale`` to its kernel instead)."""
         out = {}
         for n, p in self.named_parameters():
             if n.startswith("W."):
@@ -355,6 +332,8 @@ class CE(nn.Module):
                 hit = (tag, t.float().contiguous())
                 self._f32_cache[n] = hit
             out[n] = hit[1]
+        if not scaled:
+            return out
         c = self._scale_c()
         if c == 1.0:
             self._scaled_cache = {}
@@ -370,6 +349,13 @@ class CE(nn.Module):
                     self._scaled_cache[n] = hit
                 out[n] = hit[1]
         return out
+
+    def _topk_threshold(self):
+        """``topk_threshold`` as the (tight_topk, sampled_topk) pair of the ``ops`` entry points, which apply it to the top-k modes
+        behind the screen only."""
+        if self.topk_threshold not in ("auto", "full", "sparse"):
+            raise DaglError(f"CE.topk_threshold {self.topk_threshold!r}: expected 'auto', 'full' or 'sparse'")
+        return self.topk_threshold == "full", self.topk_threshold == "sparse"
 
     def _prologue(self, b):
         """The four prologue convolutions of dagl.py:208-215 as stock torch ops (MIOpen) -- kept for the
@@ -404,11 +390,10 @@ class CE(nn.Module):
         # call of the library's fp32 prologue kernels, layer-by-layer unfold / GEMM backward (train_ops._PrologueConvs)
         thr = bias = None
         convs = (self.g, self.theta, self.thr_conv, self.bias_conv)
-        padc = (-self.in_channels) % 4                  # (float4 channel groups: zero channels, zero weight columns -- autograd slices them off)
-        if padc:
+        if self.in_channels % 4:
             from types import SimpleNamespace
-            b = F.pad(b, (0, 0, 0, 0, 0, padc))
-            convs = tuple(SimpleNamespace(weight=F.pad(m.weight, (0, 0, 0, 0, 0, padc)), bias=m.bias) for m in convs)
+            b = _pad_channels4(b)
+            convs = tuple(SimpleNamespace(weight=_pad_channels4(m.weight), bias=m.bias) for m in convs)
         if self.select_mode != "topk":                 # (the fixed-k variant has no threshold heads)
             b1p, b2p, thr, bias = T.prologue_convs(b, *convs, fast=self.scan != "exact")
         else:
@@ -426,31 +411,33 @@ class CE(nn.Module):
                 bias = bias * sc
         info = {}
         self._pack_key = None          # the shared workspace is reused with another layout
-        out = None
+        exact, ws = self.scan == "exact", (self._ws, self._ws_bwd)
+
+        def core(route):
+            return _GraphCore.apply(wq_rows, x_rows, b2, thr, bias, route, info)
+
         k_eff = min(int(self.select_k), H * W) if self.select_mode != "adaptive" else 0
         if k_eff > MAX_TOPK:
             # more neighbours than the lists hold: the dense formulation with the row-wise selection as its mask
             want = self._wide_calls % 64 == 0           # (statistics cost a host synchronisation: every 64th call)
             self._wide_calls += 1
-            out = _GraphCoreWide.apply(wq_rows, x_rows, b2, thr, bias, self.select_mode, k_eff, self._ws, self._ws_bwd,
-                                       info if want else None)
+            out = core(_wide_route(self.select_mode, k_eff, want, *ws))
         elif self.select_mode == "adaptive" and self._train_dense:
             # the last training call met dense neighbourhoods: start in the dense formulation; every 16th call reads the
             # degrees back (one host synchronisation) to notice when the masks have become sparse enough for the lists
             self._train_dense_calls += 1
             probe = self._train_dense_calls % 16 == 1
-            out = _GraphCoreDense.apply(wq_rows, x_rows, b2, thr, bias, self._ws, self._ws_bwd, info, probe, self.scan == "exact")
+            out = core(_dense_route(probe, exact, *ws))
             if probe and 0 <= info.get("max_degree", -1) <= FAST_CAP:
                 self._train_dense = False
         else:
             try:
-                out = _GraphCore.apply(wq_rows, x_rows, b2, thr, bias, self.select_mode, min(int(self.select_k), H * W), self.scan == "exact",
-                                       self._ws, self._ws_bwd, info)
+                out = core(_lists_route(self.select_mode, min(int(self.select_k), H * W), exact, *ws))
             except DaglError as e:
                 if self.select_mode != "adaptive" or e.code != ERR_UNSUPPORTED:
                     raise
                 self._train_dense, self._train_dense_calls = True, 1
-                out = _GraphCoreDense.apply(wq_rows, x_rows, b2, thr, bias, self._ws, self._ws_bwd, info, True, self.scan == "exact")
+                out = core(_dense_route(True, exact, *ws))
         if info:
             self.last_info = info
         # range guard of the training path: its split-fp16 forward kernels (the two patch projections: |b1| < 4094, |w_fc| < 64; the
@@ -483,7 +470,7 @@ class CE(nn.Module):
             k_eff = min(int(self.select_k), b.shape[2] * b.shape[3])
             # k_eff > MAX_TOPK (include/dagl_ce.h DAGL_MAX_TOPK): no per-query lists -- the inference entry points take every
             # query's score row in the dense form (csrc/topk_wide.hip), the differentiable path the dense formulation with the
-            # row-wise selection as its mask (_GraphCoreWide)
+            # row-wise selection as its mask (_wide_route)
         in_dtype = b.dtype
         if in_dtype in (torch.bfloat16, torch.float16):
             # reduced-precision feature maps (BASELINE config 3): the block itself computes in fp32 with the bf16
@@ -497,40 +484,29 @@ class CE(nn.Module):
         # RR / CES the block's input then "requires grad" although nobody will ask for one.  Such a call keeps its place in
         # the autograd graph (_EvalLazyGrad): should a backward arrive after all, it recomputes the block on the
         # differentiable path then -- same gradients, paid only when used.
+        grad = torch.is_grad_enabled()
         if self._generic:
-            if torch.is_grad_enabled() and (b.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+            if grad and (b.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
                 out = self._forward_train_generic(b.contiguous(), k_eff)
             else:
                 out = self._forward_infer_generic(b, k_eff)
-            return out if in_dtype == torch.float32 else out.to(in_dtype)
-        if torch.is_grad_enabled():
-            if self.training and (b.requires_grad or any(p.requires_grad for p in self.parameters())):
-                out = self._forward_train(b.contiguous())
-                return out if in_dtype == torch.float32 else out.to(in_dtype)
-            if b.requires_grad:
-                ps = [p for p in self.parameters() if p.requires_grad]
-                out = _EvalLazyGrad.apply(self, k_eff, len(ps), b.contiguous(), *ps)
-                return out if in_dtype == torch.float32 else out.to(in_dtype)
-        out = self._forward_infer(b, k_eff)
+        elif grad and self.training and (b.requires_grad or any(p.requires_grad for p in self.parameters())):
+            out = self._forward_train(b.contiguous())
+        elif grad and b.requires_grad:
+            ps = [p for p in self.parameters() if p.requires_grad]
+            out = _EvalLazyGrad.apply(self, k_eff, len(ps), b.contiguous(), *ps)
+        else:
+            out = self._forward_infer(b, k_eff)
         return out if in_dtype == torch.float32 else out.to(in_dtype)
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """A module built with non-default ``ksize / stride_1 / stride_2 / inter_channels`` (dagl.py:175-176): the whole method through
         ``dagl_ce_generic_forward`` (csrc/generic.hip).  ``softmax_scale`` goes to the kernel as it is (no scaled parameter copies);
         an input width that is not a multiple of 4 gets zero channels (and zero weight columns), which change nothing."""
-        p = {}
-        for n, t in self.named_parameters():
-            if n.startswith("W."):
-                continue
-            t = t.detach()
-            if t.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-                raise DaglError(f"CE: parameter {n} has dtype {t.dtype}; fp32, fp16 or bf16 expected")
-            p[n] = t.float().contiguous()
-        padc = (-self.in_channels) % 4
-        if padc:
-            b = F.pad(b, (0, 0, 0, 0, 0, padc))
-            for n in ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight"):
-                p[n] = F.pad(p[n], (0, 0, 0, 0, 0, padc)).contiguous()
+        p = self._params_f32(scaled=False)
+        b = _pad_channels4(b)
+        for n in _CONV_WEIGHTS:
+            p[n] = _pad_channels4(p[n])
         with torch.no_grad():
             out, deg = ops.ce_forward_generic(b.contiguous(), p, self.ksize, self.stride_1, self.stride_2, self.inter_channels,
                                               mode=self.select_mode, k=k_eff, softmax_scale=float(self.softmax_scale),
@@ -543,7 +519,7 @@ class CE(nn.Module):
     def _forward_train_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """Differentiable route of a module with a non-default patch geometry: every convolution / Linear-over-patches as unfold + fp32
         matrix-core product with explicit adjoints (train_ops.patch_linear: any window, stride, channel count), the graph core as
-        ``_GraphCoreGeneric``.  Layout plumbing (NCHW -> zero-bordered NHWC) is torch's: autograd carries it."""
+        ``_generic_route``.  Layout plumbing (NCHW -> zero-bordered NHWC) is torch's: autograd carries it."""
         from . import train_ops as T
         if any(p.dtype != torch.float32 for p in self.parameters()):
             raise DaglError("CE: the differentiable path needs fp32 parameters")
@@ -554,13 +530,11 @@ class CE(nn.Module):
         t1, l1 = same_pad_amounts(H, ks, s1)[0], same_pad_amounts(W, ks, s1)[0]
         t2, l2 = same_pad_amounts(H, ks, s2)[0], same_pad_amounts(W, ks, s2)[0]
         Lh, Lw, Nh, Nw = -(-H // s1), -(-W // s1), -(-H // s2), -(-W // s2)
-        padc = (-Cin) % 4                             # float4 channel groups: zero channels, zero weight columns
         def wrows(m):
-            w = F.pad(m.weight, (0, 0, 0, 0, 0, padc)) if padc else m.weight
-            return T.conv_weight_rows(w)
+            return T.conv_weight_rows(_pad_channels4(m.weight))
         def nhwc_bordered(t_nchw):                    # [B,C,H,W] -> zero-bordered NHWC (border pg)
             return F.pad(t_nchw.permute(0, 2, 3, 1), (0, 0, pg, pg, pg, pg)).contiguous()
-        xp = nhwc_bordered(F.pad(b, (0, 0, 0, 0, 0, padc)) if padc else b)
+        xp = nhwc_bordered(_pad_channels4(b))
         heads = self.select_mode != "topk"
         b1 = T.patch_linear(xp, wrows(self.g), self.g.bias, 3, 1, pg - 1, pg - 1, H, W, allow_fast=False)             # [B, H*W, c]   dagl.py:208
         b2 = T.patch_linear(xp, wrows(self.theta), self.theta.bias, 1, 1, pg, pg, H, W, allow_fast=False)               # dagl.py:209
@@ -576,8 +550,8 @@ class CE(nn.Module):
                                 relu=True, allow_fast=False)                                                           # dagl.py:249
         self._last_call = None
         self._pack_key = None
-        return _GraphCoreGeneric.apply(wq_rows, x_rows, b2p, thr, bias, (H, W, ks, s1, s2), self.select_mode, k_eff,
-                                       float(self.softmax_scale), self._ws, self._ws_bwd)
+        route = _generic_route((H, W, ks, s1, s2), self.select_mode, k_eff, float(self.softmax_scale), self._ws, self._ws_bwd)
+        return _GraphCore.apply(wq_rows, x_rows, b2p, thr, bias, route, None)
 
     def _forward_infer_any_width(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """``CE(in_channels = n_feats)`` for n_feats != 64 (CES builds every head that way, dagl.py:94-109; ``--n_feats``,
@@ -588,26 +562,19 @@ class CE(nn.Module):
         from . import train_ops as T
         p = self._params_f32()
         heads = self.select_mode != "topk"
-        padc = (-self.in_channels) % 4          # the library's unfold works on float4 channel groups: zero channels change nothing
-        if padc:
-            b = F.pad(b, (0, 0, 0, 0, 0, padc))
-            p = dict(p)
-            for n in ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight"):
-                p[n] = F.pad(p[n], (0, 0, 0, 0, 0, padc)).contiguous()
+        b = _pad_channels4(b)
+        for n in _CONV_WEIGHTS:
+            p[n] = _pad_channels4(p[n])
         hw = (p["thr_conv.weight"], p["thr_conv.bias"], p["bias_conv.weight"], p["bias_conv.bias"]) if heads else (None,) * 4
         b1p, b2p, thr, bias = T.prologue_forward_any_width(b.contiguous(), p["g.weight"], p["g.bias"], p["theta.weight"],
                                                            p["theta.bias"], *hw)
         H, W = b.shape[-2:]
         b1 = b1p[:, T.PAD:T.PAD + H, T.PAD:T.PAD + W, :].permute(0, 3, 1, 2).contiguous()
         b2 = b2p[:, T.PAD:T.PAD + H, T.PAD:T.PAD + W, :].permute(0, 3, 1, 2).contiguous()
-        if self.topk_threshold not in ("auto", "full", "sparse"):
-            raise DaglError(f"CE.topk_threshold {self.topk_threshold!r}: expected 'auto', 'full' or 'sparse'")
-        topk_screen = self.select_mode != "adaptive" and self.scan != "exact"
+        tight, sampled = self._topk_threshold()
         out, info = ops.ce_forward(b1, b2, thr, bias, p["fc1.0.weight"], p["fc1.0.bias"], p["fc2.0.weight"], p["fc2.0.bias"],
                                    mode=self.select_mode, k=k_eff, workspace=self._ws, return_info=True,
-                                   exact_scan=(self.scan == "exact"), profile=self.profile,
-                                   tight_topk=topk_screen and self.topk_threshold == "full",
-                                   sampled_topk=topk_screen and self.topk_threshold == "sparse")
+                                   exact_scan=(self.scan == "exact"), profile=self.profile, tight_topk=tight, sampled_topk=sampled)
         self._last_call = None                     # (this entry point reads its statistics back every call: nothing to poll)
         self.last_info = info
         if info.get("range_fallback"):
@@ -638,8 +605,7 @@ class CE(nn.Module):
             self._served_streak = self._served_streaks.get(self._served_shape, 0)
         no_wait = (self.select_mode == "adaptive" and self.scan != "exact" and not hint and self.adaptive_sync == "auto"
                    and self._served_streak >= 4 and key == self._pack_key and self.profile is None)
-        if self.topk_threshold not in ("auto", "full", "sparse"):
-            raise DaglError(f"CE.topk_threshold {self.topk_threshold!r}: expected 'auto', 'full' or 'sparse'")
+        tight, sampled = self._topk_threshold()
         topk_screen = self.select_mode != "adaptive" and self.scan != "exact"
         if self.topk_redo not in ("auto", "always"):
             raise DaglError(f"CE.topk_redo {self.topk_redo!r}: expected 'auto' or 'always'")
@@ -658,9 +624,8 @@ class CE(nn.Module):
         out, info = ops.ce_forward_fused(b.contiguous(), params, mode=self.select_mode, k=k_eff,
                                          workspace=self._ws, profile=self.profile,
                                          exact_scan=(self.scan == "exact"), weights_packed=(key == self._pack_key),
-                                         dense_hint=hint, want_info=want_info, no_wait=no_wait,
-                                         tight_topk=topk_screen and self.topk_threshold == "full",
-                                         sampled_topk=topk_screen and self.topk_threshold == "sparse", no_redo=no_redo)
+                                         dense_hint=hint, want_info=want_info, no_wait=no_wait, tight_topk=tight,
+                                         sampled_topk=sampled, no_redo=no_redo)
         self._pack_key = key[:-1] + (self._ws.peek(b.device).data_ptr(),)
         self._last_call = (tuple(b.shape), b.device)
         if no_wait:

@@ -74,6 +74,34 @@ def _need(t: torch.Tensor, name: str, dtype=torch.float32):
     return t
 
 
+def _check_mode(mode: str):
+    if mode not in MODES:
+        raise DaglError(f"unknown mode {mode!r}")
+
+
+def _ptr(t, used: bool = True):
+    """Device pointer of an operand the call may go without: NULL when ``t`` is None or not ``used``."""
+    return t.data_ptr() if used and t is not None else None
+
+
+def _topk_flags(mode: str, exact_scan: bool, tight_topk: bool, sampled_topk: bool) -> int:
+    """DAGL_FLAG_TIGHT_TOPK / DAGL_FLAG_SAMPLED_TOPK: only the top-k modes behind the screen have a candidate threshold."""
+    if mode == "adaptive" or exact_scan:
+        return 0
+    return _lib.FLAG_TIGHT_TOPK if tight_topk else (_lib.FLAG_SAMPLED_TOPK if sampled_topk else 0)
+
+
+def _info_dict(info, drop=(), **fixed) -> dict:
+    """A call's ``CeInfo`` as a dict without the keys in ``drop``; ``fixed`` gives the values an entry point reports itself."""
+    d = dict(required_bytes=info.required_bytes, total_edges=info.total_edges, max_degree=info.max_degree, path=info.path,
+             redone_queries=info.redone_queries, range_fallback=info.range_fallback, dense_rerun_blocks=info.dense_rerun_blocks)
+    for n in drop:
+        del d[n]
+    if fixed:
+        d.update(fixed)
+    return d
+
+
 def query_grid(H: int, W: int):
     return -(-H // 4), -(-W // 4)
 
@@ -113,8 +141,7 @@ def project_patches(map_nhwc: torch.Tensor, w_packed: torch.Tensor, fc_bias: tor
     feat = torch.empty(B, ra, DS, device=map_nhwc.device, dtype=torch.float32)
     colsum = torch.empty(B, DS, device=map_nhwc.device, dtype=torch.float64) if (want_colsum and not queries) else None
     check(lib.dagl_project_patches(_stream(), B, H, W, int(queries), map_nhwc.data_ptr(), w_packed.data_ptr(),
-                                   fc_bias.data_ptr(), feat.data_ptr(),
-                                   colsum.data_ptr() if colsum is not None else None), "dagl_project_patches")
+                                   fc_bias.data_ptr(), feat.data_ptr(), _ptr(colsum)), "dagl_project_patches")
     return feat, colsum
 
 
@@ -240,6 +267,19 @@ class Workspace:
         return b
 
 
+def _aligned(buf: torch.Tensor):
+    base = buf.data_ptr()
+    a = (base + 255) // 256 * 256
+    return a, buf.numel() - (a - base)
+
+
+def _region(workspace: "Workspace | None", nbytes: int, device):
+    """(buffer, 256-byte aligned pointer, bytes from there) of at least ``nbytes`` in ``workspace`` (a throwaway one when None).
+    The caller keeps the buffer referenced until its launch is queued."""
+    buf = (workspace if workspace is not None else Workspace()).get(nbytes, device)
+    return (buf,) + _aligned(buf)
+
+
 @_on_device
 def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adaptive", k: int = 0,
                workspace: "Workspace | None" = None, return_info: bool = False, debug: bool = False,
@@ -248,8 +288,7 @@ def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adapt
     """Everything of CE.forward after its prologue convolutions (dagl.py:216-274) -> [B,16,H,W].  ``tight_topk`` /
     ``sampled_topk``: DAGL_FLAG_TIGHT_TOPK / DAGL_FLAG_SAMPLED_TOPK (top-k modes behind the screen), as in ``ce_forward_fused``."""
     lib = _lib.load()
-    if mode not in MODES:
-        raise DaglError(f"unknown mode {mode!r}")
+    _check_mode(mode)
     for n, t in (("b1", b1), ("b2", b2), ("fc1_w", fc1_w), ("fc1_b", fc1_b), ("fc2_w", fc2_w), ("fc2_b", fc2_b)):
         _need(t, n)
     B, c, H, W = b1.shape
@@ -262,13 +301,11 @@ def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adapt
         _need(thr, "thr"); _need(bias, "bias")
         if thr.numel() != B * Lh * Lw or bias.numel() != B * Lh * Lw:
             raise DaglError("ce_forward: thr/bias must hold B*L values")
-    ws = workspace if workspace is not None else Workspace()
     mode_flags = MODES[mode] | (_lib.FLAG_EXACT_SCAN if exact_scan else 0)
     need = lib.dagl_ce_workspace_bytes(B, H, W, mode_flags, int(k))
     if need == 0:
         check(-1, "dagl_ce_workspace_bytes")
-    if mode != "adaptive" and not exact_scan:
-        mode_flags |= _lib.FLAG_TIGHT_TOPK if tight_topk else (_lib.FLAG_SAMPLED_TOPK if sampled_topk else 0)
+    mode_flags |= _topk_flags(mode, exact_scan, tight_topk, sampled_topk)
     out = torch.empty(B, 16, H, W, device=b1.device, dtype=torch.float32)
     info = _lib.CeInfo()
     rc = 0
@@ -279,14 +316,10 @@ def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adapt
                    rowsum=torch.empty(B, L, device=b1.device, dtype=torch.float32),
                    agg=torch.empty(B, L, P, device=b1.device, dtype=torch.float32))
     for _attempt in range(2):
-        buf = ws.get(need, b1.device)
-        base = buf.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        args = (_stream(), B, H, W, b1.data_ptr(), b2.data_ptr(),
-                thr.data_ptr() if thr is not None else None,
-                bias.data_ptr() if bias is not None else None,
+        buf, a, nbytes = _region(workspace, need, b1.device)
+        args = (_stream(), B, H, W, b1.data_ptr(), b2.data_ptr(), _ptr(thr), _ptr(bias),
                 fc1_w.data_ptr(), fc1_b.data_ptr(), fc2_w.data_ptr(), fc2_b.data_ptr(),
-                mode_flags, int(k), out.data_ptr(), aligned, buf.numel() - (aligned - base), C.byref(info))
+                mode_flags, int(k), out.data_ptr(), a, nbytes, C.byref(info))
         if profile is not None:
             rc = lib.dagl_ce_forward_profiled(*args, profile._h)
         elif dbg is None:
@@ -299,9 +332,7 @@ def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adapt
             continue
         break
     check(rc, "dagl_ce_forward")
-    meta = dict(required_bytes=info.required_bytes, total_edges=info.total_edges,
-                max_degree=info.max_degree, path=info.path, redone_queries=info.redone_queries,
-                range_fallback=info.range_fallback, dense_rerun_blocks=info.dense_rerun_blocks)
+    meta = _info_dict(info)
     if dbg is not None:
         meta.update(dbg)
     if return_info or debug:
@@ -316,8 +347,7 @@ def ce_forward_generic(x, params: dict, ksize: int, stride_1: int, stride_2: int
     stride_2 and inter_channels constructor arguments): x [B,Cin,H,W] fp32 -> [B,inter_channels,H,W].  ``params`` = the block's
     state_dict tensors under their own names (fp32, on the device); Cin and inter_channels multiples of 4."""
     lib = _lib.load()
-    if mode not in MODES:
-        raise DaglError(f"unknown mode {mode!r}")
+    _check_mode(mode)
     _need(x, "x")
     B, Cin, H, W = x.shape
     c, ks = int(inter_channels), int(ksize)
@@ -334,17 +364,13 @@ def ce_forward_generic(x, params: dict, ksize: int, stride_1: int, stride_2: int
     if need == 0:
         raise DaglError(f"ce_forward_generic: unsupported shape / geometry B={B} Cin={Cin} H={H} W={W} ksize={ks} "
                         f"strides=({stride_1},{stride_2}) inter_channels={c}")
-    ws = workspace if workspace is not None else Workspace()
-    buf = ws.get(need, x.device)
+    buf, _, _ = _region(workspace, need, x.device)             # (the generic entry points take the buffer as it is)
     out = torch.empty(B, c, H, W, device=x.device, dtype=torch.float32)
     L = (-(-H // int(stride_1))) * (-(-W // int(stride_1)))
     deg = torch.empty(B, L, device=x.device, dtype=torch.int32) if want_degree else None
-    ptr = lambda n: params[n].data_ptr() if n in want else None
     check(lib.dagl_ce_generic_forward(_stream(), B, Cin, H, W, ks, int(stride_1), int(stride_2), c, float(softmax_scale), MODES[mode], int(k),
-                                      x.data_ptr(), ptr("g.weight"), ptr("g.bias"), ptr("theta.weight"), ptr("theta.bias"),
-                                      ptr("thr_conv.weight"), ptr("thr_conv.bias"), ptr("bias_conv.weight"), ptr("bias_conv.bias"),
-                                      ptr("fc1.0.weight"), ptr("fc1.0.bias"), ptr("fc2.0.weight"), ptr("fc2.0.bias"),
-                                      out.data_ptr(), deg.data_ptr() if deg is not None else None, buf.data_ptr(), buf.numel()),
+                                      x.data_ptr(), *(_ptr(params.get(n), n in want) for n in _lib.CeWeights.NAMES),
+                                      out.data_ptr(), _ptr(deg), buf.data_ptr(), buf.numel()),
           "dagl_ce_generic_forward")
     return (out, deg) if want_degree else out
 
@@ -375,14 +401,12 @@ def ce_generic_core_forward(wq_rows, x_rows, b2p, thr, bias, H: int, W: int, ksi
     if heads:
         _need(thr, "thr"); _need(bias, "bias")
     need = lib.dagl_ce_generic_core_workspace_bytes(B, H, W, int(ksize), int(stride_1), int(stride_2), c, 0)
-    ws = workspace if workspace is not None else Workspace()
-    buf = ws.get(need, b2p.device)
+    buf, _, _ = _region(workspace, need, b2p.device)
     out = torch.empty(B, c, H, W, device=b2p.device, dtype=torch.float32)
     deg = torch.empty(B, L, device=b2p.device, dtype=torch.int32) if want_degree else None
     check(lib.dagl_ce_generic_core_forward(_stream(), B, H, W, int(ksize), int(stride_1), int(stride_2), c, float(softmax_scale), MODES[mode], int(k),
-                                           wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), thr.data_ptr() if heads else None,
-                                           bias.data_ptr() if heads else None, out.data_ptr(), deg.data_ptr() if deg is not None else None,
-                                           buf.data_ptr(), buf.numel()), "dagl_ce_generic_core_forward")
+                                           wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), _ptr(thr, heads), _ptr(bias, heads),
+                                           out.data_ptr(), _ptr(deg), buf.data_ptr(), buf.numel()), "dagl_ce_generic_core_forward")
     return (out, deg) if want_degree else out
 
 
@@ -395,15 +419,14 @@ def ce_generic_core_backward(d_out, wq_rows, x_rows, b2p, thr, bias, H: int, W: 
     B, c = b2p.shape[0], b2p.shape[3]
     heads = mode != "topk"
     need = lib.dagl_ce_generic_core_workspace_bytes(B, H, W, int(ksize), int(stride_1), int(stride_2), c, 1)
-    ws = workspace if workspace is not None else Workspace()
-    buf = ws.get(need, b2p.device)
+    buf, _, _ = _region(workspace, need, b2p.device)
     d_wq, d_x, d_b2p = torch.empty_like(wq_rows), torch.empty_like(x_rows), torch.empty_like(b2p)
     d_thr = torch.empty_like(thr) if heads else None
     d_bias = torch.empty_like(bias) if heads else None
     check(lib.dagl_ce_generic_core_backward(_stream(), B, H, W, int(ksize), int(stride_1), int(stride_2), c, float(softmax_scale), MODES[mode], int(k),
-                                            wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), thr.data_ptr() if heads else None,
-                                            bias.data_ptr() if heads else None, d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(), d_b2p.data_ptr(),
-                                            d_thr.data_ptr() if heads else None, d_bias.data_ptr() if heads else None, buf.data_ptr(), buf.numel()),
+                                            wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), _ptr(thr, heads), _ptr(bias, heads),
+                                            d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(), d_b2p.data_ptr(), _ptr(d_thr), _ptr(d_bias),
+                                            buf.data_ptr(), buf.numel()),
           "dagl_ce_generic_core_backward")
     return d_wq, d_x, d_b2p, d_thr, d_bias
 
@@ -425,21 +448,21 @@ def ce_prologue(x, g_w, g_b, theta_w, theta_b, thr_w=None, thr_b=None, bias_w=No
     if heads:
         for n, t in (("thr_w", thr_w), ("thr_b", thr_b), ("bias_w", bias_w), ("bias_b", bias_b)):
             _need(t, n)
-    p = lambda t: t.data_ptr() if t is not None else None
     if fast:
         # g / theta on the fp16 matrix cores with split operands (conv_pair16_kernel, the inference path's kernel, fp32 map out)
         lib = _lib.load()
         need = lib.dagl_ce_prologue16_scratch_bytes(B, H, W)
         scratch = torch.empty(need + 256, device=x.device, dtype=torch.uint8)
-        base = (scratch.data_ptr() + 255) // 256 * 256
+        base, _ = _aligned(scratch)
         check(lib.dagl_ce_prologue16(_stream(), B, H, W, x.data_ptr(), g_w.data_ptr(), g_b.data_ptr(), theta_w.data_ptr(), theta_b.data_ptr(),
-                                     p(thr_w), p(thr_b), p(bias_w), p(bias_b), b1p.data_ptr(), b2p.data_ptr(), p(thr), p(bias), base, need),
+                                     _ptr(thr_w), _ptr(thr_b), _ptr(bias_w), _ptr(bias_b), b1p.data_ptr(), b2p.data_ptr(), _ptr(thr),
+                                     _ptr(bias), base, need),
               "dagl_ce_prologue16")
         return b1p, b2p, thr, bias
     scratch = torch.empty(8 * B * Lh * Lw, device=x.device, dtype=torch.float32) if heads else None
     check(_lib.load().dagl_ce_prologue(_stream(), B, H, W, x.data_ptr(), g_w.data_ptr(), g_b.data_ptr(),
-                                       theta_w.data_ptr(), theta_b.data_ptr(), p(thr_w), p(thr_b), p(bias_w), p(bias_b),
-                                       b1p.data_ptr(), b2p.data_ptr(), p(thr), p(bias), p(scratch)), "dagl_ce_prologue")
+                                       theta_w.data_ptr(), theta_b.data_ptr(), _ptr(thr_w), _ptr(thr_b), _ptr(bias_w), _ptr(bias_b),
+                                       b1p.data_ptr(), b2p.data_ptr(), _ptr(thr), _ptr(bias), _ptr(scratch)), "dagl_ce_prologue")
     return b1p, b2p, thr, bias
 
 
@@ -460,34 +483,27 @@ def ce_forward_fused(x, params: dict, mode: str = "adaptive", k: int = 0, worksp
     ``no_redo`` (top-k modes, DAGL_FLAG_NO_REDO): the fp32 redo pass behind the refine kernel is not queued; a call that flagged a
     query group anyway is NaN-filled and ``ce_range_check`` reports it (bit 4, sticky)."""
     lib = _lib.load()
-    if mode not in MODES:
-        raise DaglError(f"unknown mode {mode!r}")
+    _check_mode(mode)
     _need(x, "x")
     B, c, H, W = x.shape
     if c != 64:
         raise DaglError("ce_forward_fused: 64 input channels expected")
-    names = ["g.weight", "g.bias", "theta.weight", "theta.bias", "thr_conv.weight", "thr_conv.bias",
-             "bias_conv.weight", "bias_conv.bias", "fc1.0.weight", "fc1.0.bias", "fc2.0.weight", "fc2.0.bias"]
-    ptrs = []
-    for n in names:
-        t = params[n]
-        _need(t, n)
-        ptrs.append(t.data_ptr())
+    ptrs = [_need(params[n], n).data_ptr() for n in _lib.CeWeights.NAMES]
     ws = workspace if workspace is not None else Workspace()
     mode_flags = MODES[mode] | (_lib.FLAG_EXACT_SCAN if exact_scan else 0)
     need = lib.dagl_ce_workspace_bytes(B, H, W, mode_flags, int(k))
     if need == 0:
         check(-1, "dagl_ce_workspace_bytes")
-    if weights_packed and ws.peek(x.device) is not None and ws.peek(x.device).numel() >= need + 256:
+    held = ws.peek(x.device)
+    if weights_packed and held is not None and held.numel() >= need + 256:
         mode_flags |= _lib.FLAG_WEIGHTS_PACKED           # same buffer as last time: the packed weights are still in it
     if dense_hint and mode == "adaptive" and not exact_scan:
         mode_flags |= _lib.FLAG_DENSE_HINT
-        if ws.peek(x.device) is not None:
-            need = max(need, ws.peek(x.device).numel() - 4096)      # keep the (larger) buffer the dense path asked for earlier
-    if mode != "adaptive" and not exact_scan:
-        mode_flags |= _lib.FLAG_TIGHT_TOPK if tight_topk else (_lib.FLAG_SAMPLED_TOPK if sampled_topk else 0)
-        if no_redo and (mode_flags & _lib.FLAG_WEIGHTS_PACKED):
-            mode_flags |= _lib.FLAG_NO_REDO
+        if held is not None:
+            need = max(need, held.numel() - 4096)      # keep the (larger) buffer the dense path asked for earlier
+    mode_flags |= _topk_flags(mode, exact_scan, tight_topk, sampled_topk)
+    if no_redo and mode != "adaptive" and not exact_scan and (mode_flags & _lib.FLAG_WEIGHTS_PACKED):
+        mode_flags |= _lib.FLAG_NO_REDO
     quiet = dense_hint and not want_info
     if no_wait and mode == "adaptive" and not exact_scan and not dense_hint and H * W >= 2048:
         mode_flags |= _lib.FLAG_NO_WAIT
@@ -496,12 +512,9 @@ def ce_forward_fused(x, params: dict, mode: str = "adaptive", k: int = 0, worksp
     info = _lib.CeInfo()
     rc = 0
     for _attempt in range(3):
-        buf = ws.get(need, x.device)
-        base = buf.data_ptr()
-        aligned = (base + 255) // 256 * 256
-        rc = lib.dagl_ce_forward_fused(_stream(), B, H, W, x.data_ptr(), *ptrs, mode_flags, int(k), out.data_ptr(),
-                                       aligned, buf.numel() - (aligned - base), None if quiet else C.byref(info),
-                                       profile._h if profile is not None else None)
+        buf, a, nbytes = _region(ws, need, x.device)
+        rc = lib.dagl_ce_forward_fused(_stream(), B, H, W, x.data_ptr(), *ptrs, mode_flags, int(k), out.data_ptr(), a, nbytes,
+                                       None if quiet else C.byref(info), profile._h if profile is not None else None)
         if rc == _lib.ERR_WORKSPACE and quiet:
             quiet = False                                # ask again, this time for the size
             continue
@@ -511,11 +524,7 @@ def ce_forward_fused(x, params: dict, mode: str = "adaptive", k: int = 0, worksp
             continue
         break
     check(rc, "dagl_ce_forward_fused")
-    if quiet:
-        return out, None
-    return out, dict(required_bytes=info.required_bytes, total_edges=info.total_edges,
-                     max_degree=info.max_degree, path=info.path, redone_queries=info.redone_queries,
-                     range_fallback=info.range_fallback, dense_rerun_blocks=info.dense_rerun_blocks)
+    return out, None if quiet else _info_dict(info)
 
 
 def ce_range_check(shape, mode: str, k: int, workspace: "Workspace", device) -> int:
@@ -543,8 +552,7 @@ def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: i
     ``head_params``: four dicts (state_dict names -> contiguous fp32 GPU tensors).  Returns (out [B,64,H,W], info), or
     (None, info) when a dense adaptive neighbourhood needs the per-head path.  The library reads the default head's weights
     (ksize 7, inter_channels 16) through raw pointers: every tensor's shape is checked here first."""
-    if mode not in MODES:
-        raise DaglError(f"unknown mode {mode!r}")
+    _check_mode(mode)
     _need(x, "x"); _need(mix_w, "mix_w"); _need(mix_b, "mix_b")
     B, c, H, W = x.shape
     if c != 64 or len(head_params) != 4:
@@ -565,33 +573,20 @@ def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: i
                 raise DaglError(f"ces_stage_forward: head {h} {name} is {tuple(t.shape)}, expected {want[name]}")
             setattr(arr[h], field, t.data_ptr())
     lib = _lib.load()
-    ws = workspace if workspace is not None else Workspace()
     need = lib.dagl_ces_stage_workspace_bytes(B, H, W, MODES[mode], int(k))
     if need == 0:
         check(-1, "dagl_ces_stage_workspace_bytes")
     out = torch.empty(B, 64, H, W, device=x.device, dtype=torch.float32)
     info = _lib.CeInfo()
-    buf = ws.get(need, x.device)
-    base = buf.data_ptr()
-    aligned = (base + 255) // 256 * 256
-    rc = lib.dagl_ces_stage_forward(_stream(), B, H, W, x.data_ptr(), arr, mix_w.data_ptr(), mix_b.data_ptr(),
-                                    MODES[mode] | (_lib.FLAG_WEIGHTS_PACKED if weights_packed else 0) |
-                                    ((_lib.FLAG_TIGHT_TOPK if tight_topk else (_lib.FLAG_SAMPLED_TOPK if sampled_topk else 0))
-                                     if mode != "adaptive" else 0), int(k),
-                                    out.data_ptr(), aligned, buf.numel() - (aligned - base),
-                                    C.byref(info), profile._h if profile is not None else None)
-    meta = dict(required_bytes=info.required_bytes, total_edges=info.total_edges, max_degree=info.max_degree,
-                path=info.path, redone_queries=info.redone_queries)
+    buf, a, nbytes = _region(workspace, need, x.device)
+    flags = MODES[mode] | (_lib.FLAG_WEIGHTS_PACKED if weights_packed else 0) | _topk_flags(mode, False, tight_topk, sampled_topk)
+    rc = lib.dagl_ces_stage_forward(_stream(), B, H, W, x.data_ptr(), arr, mix_w.data_ptr(), mix_b.data_ptr(), flags, int(k),
+                                    out.data_ptr(), a, nbytes, C.byref(info), profile._h if profile is not None else None)
+    meta = _info_dict(info, drop=("range_fallback", "dense_rerun_blocks"))
     if rc == _lib.ERR_WORKSPACE and info.required_bytes == -1:
         return None, meta
     check(rc, "dagl_ces_stage_forward")
     return out, meta
-
-
-def _aligned(buf: torch.Tensor):
-    base = buf.data_ptr()
-    a = (base + 255) // 256 * 256
-    return a, buf.numel() - (a - base)
 
 
 @_on_device
@@ -600,8 +595,7 @@ def ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode: str = "adaptive", k: i
     """Graph core with the projections given (training path, include/dagl_ce.h ``dagl_ce_core_forward``):
     wq_rows [B,L,196], x_rows [B,N,196], b2 [B,16,H,W], thr/bias [B,L] -> (out [B,16,H,W], saved lists dict)."""
     lib = _lib.load()
-    if mode not in MODES:
-        raise DaglError(f"unknown mode {mode!r}")
+    _check_mode(mode)
     for n, t in (("wq_rows", wq_rows), ("x_rows", x_rows), ("b2", b2)):
         _need(t, n)
     B, c, H, W = b2.shape
@@ -622,7 +616,6 @@ def ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode: str = "adaptive", k: i
     need = lib.dagl_ce_workspace_bytes(B, H, W, mode_flags, int(k))
     if need == 0:
         check(-1, "dagl_ce_workspace_bytes")
-    ws = workspace if workspace is not None else Workspace()
     dev = b2.device
     out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32)
     saved = dict(nb_idx=torch.zeros(B, L, width, device=dev, dtype=torch.int32),
@@ -631,16 +624,13 @@ def ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode: str = "adaptive", k: i
                  nb_cnt=torch.zeros(B, L, device=dev, dtype=torch.int32),
                  mu=torch.zeros(B, L, device=dev, dtype=torch.float32) if adaptive else None)
     info = _lib.CeInfo()
-    a, nbytes = _aligned(ws.get(need, dev))
+    buf, a, nbytes = _region(workspace, need, dev)
     rc = lib.dagl_ce_core_forward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2.data_ptr(),
-                                  thr.data_ptr() if adaptive else None, bias.data_ptr() if adaptive else None,
-                                  mode_flags, int(k), out.data_ptr(), saved["nb_idx"].data_ptr(),
-                                  saved["nb_wgt"].data_ptr(), saved["nb_s"].data_ptr(), saved["nb_cnt"].data_ptr(),
-                                  saved["mu"].data_ptr() if adaptive else None, a, nbytes, C.byref(info))
+                                  _ptr(thr, adaptive), _ptr(bias, adaptive), mode_flags, int(k), out.data_ptr(),
+                                  saved["nb_idx"].data_ptr(), saved["nb_wgt"].data_ptr(), saved["nb_s"].data_ptr(),
+                                  saved["nb_cnt"].data_ptr(), _ptr(saved["mu"]), a, nbytes, C.byref(info))
     check(rc, "dagl_ce_core_forward")
-    saved["info"] = dict(total_edges=info.total_edges, max_degree=info.max_degree, path=info.path,
-                         redone_queries=info.redone_queries, range_fallback=info.range_fallback,
-                         dense_rerun_blocks=info.dense_rerun_blocks)
+    saved["info"] = _info_dict(info, drop=("required_bytes",))
     return out, saved
 
 
@@ -658,20 +648,18 @@ def ce_core_backward(d_out, wq_rows, x_rows, b2, thr, bias, saved: dict, mode: s
     need = lib.dagl_ce_core_backward_workspace_bytes(B, H, W, MODES[mode], int(k))
     if need == 0:
         check(-1, "dagl_ce_core_backward_workspace_bytes")
-    ws = workspace if workspace is not None else Workspace()
     dev = b2.device
     d_wq = torch.empty_like(wq_rows)
     d_x = torch.empty_like(x_rows)
     d_b2 = torch.empty_like(b2)
     d_thr = torch.empty(B, wq_rows.shape[1], device=dev, dtype=torch.float32) if adaptive else None
     d_bias = torch.empty_like(d_thr) if adaptive else None
-    a, nbytes = _aligned(ws.get(need, dev))
-    p = lambda t: t.data_ptr() if t is not None else None
+    buf, a, nbytes = _region(workspace, need, dev)
     rc = lib.dagl_ce_core_backward(_stream(), B, H, W, MODES[mode], int(k), wq_rows.data_ptr(), x_rows.data_ptr(),
-                                   b2.data_ptr(), p(thr) if adaptive else None, p(bias) if adaptive else None,
+                                   b2.data_ptr(), _ptr(thr, adaptive), _ptr(bias, adaptive),
                                    saved["nb_idx"].data_ptr(), saved["nb_wgt"].data_ptr(), saved["nb_s"].data_ptr(),
-                                   saved["nb_cnt"].data_ptr(), p(saved["mu"]), d_out.data_ptr(), d_wq.data_ptr(),
-                                   d_x.data_ptr(), d_b2.data_ptr(), p(d_thr), p(d_bias), a, nbytes)
+                                   saved["nb_cnt"].data_ptr(), _ptr(saved["mu"]), d_out.data_ptr(), d_wq.data_ptr(),
+                                   d_x.data_ptr(), d_b2.data_ptr(), _ptr(d_thr), _ptr(d_bias), a, nbytes)
     check(rc, "dagl_ce_core_backward")
     return d_wq, d_x, d_b2, d_thr, d_bias
 
@@ -708,8 +696,7 @@ def gemm_f32(A: torch.Tensor, B: torch.Tensor, a_k_contiguous: bool = True, b_k_
     check(lib.dagl_gemm_f32(_stream(), nb, M, N, K, A.data_ptr(), A.shape[2], A.shape[1] * A.shape[2],
                             int(a_k_contiguous), B.data_ptr(), B.shape[2], B.shape[1] * B.shape[2],
                             int(b_k_contiguous), out.data_ptr(), N, M * N, float(alpha), float(beta),
-                            bias.data_ptr() if bias is not None else None, int(relu), int(chunk_tiles),
-                            scratch.data_ptr() if scratch is not None else None), "dagl_gemm_f32")
+                            _ptr(bias), int(relu), int(chunk_tiles), _ptr(scratch)), "dagl_gemm_f32")
     return out[0] if squeeze and out.dim() == 3 else out
 
 
@@ -729,19 +716,17 @@ def ce_core_dense_forward(wq_rows, x_rows, b2, thr, bias, workspace: "Workspace 
             or bias.numel() != B * L:
         raise DaglError("ce_core_dense_forward: expected wq_rows [B,L,196], x_rows [B,H*W,196], b2 [B,16,H,W], thr/bias [B,L]")
     need = lib.dagl_ce_core_dense_workspace_bytes(B, H, W, 0) + 256
-    ws = workspace if workspace is not None else Workspace()
     dev = b2.device
     out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32)
     lse = torch.empty(B, L, 2, device=dev, dtype=torch.float32)
     mu = torch.empty(B, L, device=dev, dtype=torch.float32)
     info = _lib.CeInfo()
-    a, nbytes = _aligned(ws.get(need, dev))
+    buf, a, nbytes = _region(workspace, need, dev)
     check(lib.dagl_ce_core_dense_forward(_stream(), B, H, W, _lib.FLAG_EXACT_SCAN if exact else 0, wq_rows.data_ptr(),
                                          x_rows.data_ptr(), b2.data_ptr(), thr.data_ptr(), bias.data_ptr(), out.data_ptr(),
                                          lse.data_ptr(), mu.data_ptr(), a, nbytes, C.byref(info) if want_info else None),
           "dagl_ce_core_dense_forward")
-    meta = dict(total_edges=info.total_edges, max_degree=info.max_degree, path=5, redone_queries=-1,
-                range_fallback=info.range_fallback, dense_rerun_blocks=info.dense_rerun_blocks) if want_info else None
+    meta = _info_dict(info, drop=("required_bytes",), path=5, redone_queries=-1) if want_info else None
     return out, dict(lse=lse, mu=mu, info=meta)
 
 
@@ -756,12 +741,11 @@ def ce_core_dense_backward(d_out, wq_rows, x_rows, b2, thr, bias, saved: dict, w
         _need(t, n)
     B, _, H, W = b2.shape
     need = lib.dagl_ce_core_dense_workspace_bytes(B, H, W, 1)
-    ws = workspace if workspace is not None else Workspace()
     dev = b2.device
     d_wq, d_x, d_b2 = torch.empty_like(wq_rows), torch.empty_like(x_rows), torch.empty_like(b2)
     d_thr = torch.empty(B, wq_rows.shape[1], device=dev, dtype=torch.float32)
     d_bias = torch.empty_like(d_thr)
-    a, nbytes = _aligned(ws.get(need, dev))
+    buf, a, nbytes = _region(workspace, need, dev)
     check(lib.dagl_ce_core_dense_backward(_stream(), B, H, W, _lib.FLAG_EXACT_SCAN if exact else 0, wq_rows.data_ptr(), x_rows.data_ptr(), b2.data_ptr(),
                                           thr.data_ptr(), bias.data_ptr(), saved["lse"].data_ptr(), saved["mu"].data_ptr(),
                                           d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(), d_b2.data_ptr(),
@@ -787,17 +771,15 @@ def ce_core_wide_forward(wq_rows, x_rows, b2, thr, bias, mode: str, k: int, work
     if c != 16 or tuple(wq_rows.shape) != (B, L, 196) or tuple(x_rows.shape) != (B, N, 196):
         raise DaglError("ce_core_wide_forward: expected wq_rows [B,L,196], x_rows [B,H*W,196], b2 [B,16,H,W]")
     need = lib.dagl_ce_core_dense_workspace_bytes(B, H, W, 0) + 256
-    ws = workspace if workspace is not None else Workspace()
     out = torch.empty(B, 16, H, W, device=b2.device, dtype=torch.float32)
     info = _lib.CeInfo()
-    a, nbytes = _aligned(ws.get(need, b2.device))
+    buf, a, nbytes = _region(workspace, need, b2.device)
     heads = mode != "topk"
     check(lib.dagl_ce_core_wide_forward(_stream(), B, H, W, MODES[mode], int(k), wq_rows.data_ptr(), x_rows.data_ptr(), b2.data_ptr(),
-                                        thr.data_ptr() if heads else None, bias.data_ptr() if heads else None, out.data_ptr(),
+                                        _ptr(thr, heads), _ptr(bias, heads), out.data_ptr(),
                                         a, nbytes, C.byref(info) if want_info else None), "dagl_ce_core_wide_forward")
-    meta = dict(total_edges=info.total_edges, max_degree=info.max_degree, path=5, redone_queries=-1,
-                range_fallback=0) if want_info else None
-    return out, meta
+    return out, _info_dict(info, drop=("required_bytes", "dense_rerun_blocks"), path=5, redone_queries=-1,
+                           range_fallback=0) if want_info else None
 
 
 @_on_device
@@ -805,20 +787,18 @@ def ce_core_wide_backward(d_out, wq_rows, x_rows, b2, thr, bias, mode: str, k: i
     """Gradients of ``ce_core_wide_forward`` (``dagl_ce_core_wide_backward``) -> (d_wq_rows, d_x_rows, d_b2, d_thr, d_bias);
     the last two are None in mode "topk" (a 0/1 mask has no threshold heads)."""
     lib = _lib.load()
-    for n, t in (("d_out", d_out), ("wq_rows", wq_rows), ("x_rows", x_rows), ("b2", b2)):
+    heads = mode != "topk"
+    for n, t in (("d_out", d_out), ("wq_rows", wq_rows), ("x_rows", x_rows), ("b2", b2)) + \
+            ((("thr", thr), ("bias", bias)) if heads else ()):
         _need(t, n)
     B, _, H, W = b2.shape
     need = lib.dagl_ce_core_dense_workspace_bytes(B, H, W, 1)
-    ws = workspace if workspace is not None else Workspace()
     dev = b2.device
-    heads = mode != "topk"
     d_wq, d_x, d_b2 = torch.empty_like(wq_rows), torch.empty_like(x_rows), torch.empty_like(b2)
     d_thr = torch.empty(B, wq_rows.shape[1], device=dev, dtype=torch.float32) if heads else None
     d_bias = torch.empty_like(d_thr) if heads else None
-    a, nbytes = _aligned(ws.get(need, dev))
+    buf, a, nbytes = _region(workspace, need, dev)
     check(lib.dagl_ce_core_wide_backward(_stream(), B, H, W, MODES[mode], int(k), wq_rows.data_ptr(), x_rows.data_ptr(), b2.data_ptr(),
-                                         thr.data_ptr() if heads else None, bias.data_ptr() if heads else None, d_out.data_ptr(),
-                                         d_wq.data_ptr(), d_x.data_ptr(), d_b2.data_ptr(),
-                                         d_thr.data_ptr() if heads else None, d_bias.data_ptr() if heads else None, a, nbytes),
-          "dagl_ce_core_wide_backward")
+                                         _ptr(thr, heads), _ptr(bias, heads), d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(),
+                                         d_b2.data_ptr(), _ptr(d_thr), _ptr(d_bias), a, nbytes), "dagl_ce_core_wide_backward")
     return d_wq, d_x, d_b2, d_thr, d_bias
