@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdagl_ce.so")
 MODE_ADAPTIVE, MODE_TOPK, MODE_ADAPTIVE_TOPK = 0, 1, 2
 MODES = {"adaptive": MODE_ADAPTIVE, "topk": MODE_TOPK, "adaptive_topk": MODE_ADAPTIVE_TOPK}
 MAX_TOPK = 64
-ABI_VERSION = 406          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
+ABI_VERSION = 407          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
 FAST_CAP = 64
 P = 784
 D = 196
@@ -126,6 +126,13 @@ SIGNATURES = {
     "dagl_ce_generic_core_workspace_bytes": (_sz, [_i] * 8),
     "dagl_ce_generic_core_forward": (_i, [_vp] + [_i] * 7 + [C.c_float, _i, _i] + [_vp] * 8 + [_sz]),
     "dagl_ce_generic_core_backward": (_i, [_vp] + [_i] * 7 + [C.c_float, _i, _i] + [_vp] * 12 + [_sz]),
+    "dagl_trunk_packed_floats": (_sz, [_i] * 4),
+    "dagl_trunk_pack_weights": (_i, [_vp] + [_i] * 4 + [_vp, _vp]),
+    "dagl_trunk_conv_forward": (_i, [_vp] + [_i] * 6 + [_vp] * 5 + [C.c_float, _vp, _vp]),
+    "dagl_trunk_input_grad_blocks": (_i, [_i] * 3),
+    "dagl_trunk_conv_input_grad": (_i, [_vp] + [_i] * 6 + [_vp, _vp, C.c_float] + [_vp] * 5),
+    "dagl_trunk_weight_grad_scratch_bytes": (_sz, [_i] * 6),
+    "dagl_trunk_conv_weight_grad": (_i, [_vp] + [_i] * 6 + [_vp, _vp, C.c_float, _vp, _vp, _vp, _i, _vp, _vp, _sz]),
 }
 
 _lib = None

@@ -3,7 +3,8 @@ HIP block can be exercised the way the reference exercises ``CE``: inside the 3-
 of the EDSR-style trunk ``RR`` and under the recursive 4-way tiling of ``forward_chop``.
 
 Everything here except ``CE`` and the ResBlocks' PReLU (train_ops.PReLU: torch's backward for it was a sixth of the training
-step) is stock PyTorch-ROCm convolutions.  Module / parameter names and registration order
+step) is stock PyTorch-ROCm convolutions -- unless the model is converted with ``trunk.convert``, which moves every trunk
+convolution (and the ResBlocks as fused two-launch blocks) onto the library.  Module / parameter names and registration order
 follow the reference (``RR`` DN_Gray/model/dagl.py:11-54, ``CES`` :74-119, ``ResBlock`` DN_Gray/model/common.py:59-79),
 so a reference ``state_dict`` loads strictly.
 """
@@ -16,6 +17,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import trunk
 from .ce import CE
 
 
@@ -33,6 +35,9 @@ class ResBlock(nn.Module):
         self.res_scale = res_scale
 
     def forward(self, x):
+        c1, act, c2 = self.body
+        if trunk.fused_resblock_ok(c1, act, c2):
+            return trunk.resblock(x, c1, act, c2, self.res_scale)     # converted (trunk.convert): two launches, own autograd op
         return self.body(x).mul(self.res_scale) + x
 
 

@@ -802,3 +802,95 @@ def ce_core_wide_backward(d_out, wq_rows, x_rows, b2, thr, bias, mode: str, k: i
                                          _ptr(thr, heads), _ptr(bias, heads), d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(),
                                          d_b2.data_ptr(), _ptr(d_thr), _ptr(d_bias), a, nbytes), "dagl_ce_core_wide_backward")
     return d_wq, d_x, d_b2, d_thr, d_bias
+
+
+# ---- the residual trunk's convolutions (include/dagl_ce.h: dagl_trunk_*) -------------------------------------------------------
+def _trunk_geom(t: torch.Tensor, name: str):
+    _need(t, name)
+    if t.dim() != 4:
+        raise DaglError(f"{name}: [B,C,H,W] expected, got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+@_on_device
+def trunk_pack_weights(w: torch.Tensor, transposed: bool = False) -> torch.Tensor:
+    """conv weight [Cout,Cin,k,k] -> the fragment layout of the trunk kernels (``transposed``: the input gradient's)."""
+    Cout, Cin, kh, kw = _trunk_geom(w, "weight")
+    if kh != kw:
+        raise DaglError("trunk_pack_weights: square kernels only")
+    lib = _lib.load()
+    n = lib.dagl_trunk_packed_floats(Cin, Cout, kh, int(transposed))
+    if n == 0:
+        raise DaglError(f"trunk_pack_weights: unsupported layer {Cin}->{Cout} {kh}x{kw}")
+    out = torch.empty(n, device=w.device, dtype=torch.float32)
+    check(lib.dagl_trunk_pack_weights(_stream(), Cin, Cout, kh, int(transposed), w.data_ptr(), out.data_ptr()), "dagl_trunk_pack_weights")
+    return out
+
+
+@_on_device
+def trunk_conv_forward(x: torch.Tensor, packed: torch.Tensor, bias, Cout: int, ksize: int, slope=None, want_pre: bool = False,
+                       res_scale: float = 1.0, residual=None):
+    """conv(x) (+ bias) [-> PReLU(slope)] [-> * res_scale + residual] -> (out [B,Cout,H,W], pre-activation or None)."""
+    B, Cin, H, W = _trunk_geom(x, "x")
+    _need(packed, "packed")
+    if bias is not None:
+        _need(bias, "bias")
+    if slope is not None:
+        _need(slope, "slope")
+    if residual is not None and _trunk_geom(residual, "residual") != (B, Cout, H, W):
+        raise DaglError("trunk_conv_forward: residual shape mismatch")
+    if want_pre and slope is None:
+        raise DaglError("trunk_conv_forward: the pre-activation needs the PReLU slope")
+    out = torch.empty(B, Cout, H, W, device=x.device, dtype=torch.float32)
+    pre = torch.empty_like(out) if want_pre else None
+    check(_lib.load().dagl_trunk_conv_forward(_stream(), B, Cin, Cout, H, W, ksize, x.data_ptr(), packed.data_ptr(), _ptr(bias),
+                                              _ptr(slope), _ptr(pre), float(res_scale), _ptr(residual), out.data_ptr()),
+          "dagl_trunk_conv_forward")
+    return out, pre
+
+
+@_on_device
+def trunk_conv_input_grad(d_out: torch.Tensor, packed_t: torch.Tensor, Cin: int, ksize: int, alpha: float = 1.0, slope=None,
+                          pre=None, skip=None):
+    """alpha * conv_transposed(d_out) [-> PReLU backward from ``pre``] [+ skip] -> (d_in [B,Cin,H,W], slope partials or None)."""
+    B, Cout, H, W = _trunk_geom(d_out, "d_out")
+    _need(packed_t, "packed_t")
+    lib = _lib.load()
+    part = None
+    if slope is not None:
+        _need(slope, "slope")
+        if pre is None or _trunk_geom(pre, "pre") != (B, Cin, H, W):
+            raise DaglError("trunk_conv_input_grad: the PReLU backward needs the pre-activation [B,Cin,H,W]")
+        part = torch.empty(lib.dagl_trunk_input_grad_blocks(B, H, W), device=d_out.device, dtype=torch.float64)
+    if skip is not None and _trunk_geom(skip, "skip") != (B, Cin, H, W):
+        raise DaglError("trunk_conv_input_grad: skip gradient shape mismatch")
+    d_in = torch.empty(B, Cin, H, W, device=d_out.device, dtype=torch.float32)
+    check(lib.dagl_trunk_conv_input_grad(_stream(), B, Cin, Cout, H, W, ksize, d_out.data_ptr(), packed_t.data_ptr(), float(alpha),
+                                         _ptr(slope), _ptr(pre), _ptr(part), _ptr(skip), d_in.data_ptr()), "dagl_trunk_conv_input_grad")
+    return d_in, part
+
+
+@_on_device
+def trunk_conv_weight_grad(x: torch.Tensor, d_out: torch.Tensor, ksize: int, alpha: float = 1.0, want_bias: bool = True,
+                           slope_part=None):
+    """(d weight [Cout,Cin,k,k], d bias [Cout] or None, d slope [1] or None) of a trunk convolution; ``slope_part``: the partials
+    of an earlier ``trunk_conv_input_grad`` to add up into the PReLU slope's gradient."""
+    B, Cin, H, W = _trunk_geom(x, "x")
+    Bo, Cout, Ho, Wo = _trunk_geom(d_out, "d_out")
+    if (Bo, Ho, Wo) != (B, H, W):
+        raise DaglError("trunk_conv_weight_grad: x and d_out do not match")
+    lib = _lib.load()
+    d_w = torch.empty(Cout, Cin, ksize, ksize, device=x.device, dtype=torch.float32)
+    d_b = torch.empty(Cout, device=x.device, dtype=torch.float32) if want_bias else None
+    d_s = None
+    if slope_part is not None:
+        _need(slope_part, "slope_part", torch.float64)
+        d_s = torch.empty(1, device=x.device, dtype=torch.float32)
+    need = lib.dagl_trunk_weight_grad_scratch_bytes(B, Cin, Cout, H, W, ksize)
+    if need == 0:
+        raise DaglError(f"trunk_conv_weight_grad: unsupported layer {Cin}->{Cout} {ksize}x{ksize}")
+    scratch = torch.empty(need // 4, device=x.device, dtype=torch.float32)
+    check(lib.dagl_trunk_conv_weight_grad(_stream(), B, Cin, Cout, H, W, ksize, x.data_ptr(), d_out.data_ptr(), float(alpha),
+                                          d_w.data_ptr(), _ptr(d_b), _ptr(slope_part), slope_part.numel() if slope_part is not None else 0,
+                                          _ptr(d_s), scratch.data_ptr(), need), "dagl_trunk_conv_weight_grad")
+    return d_w, d_b, d_s

@@ -169,7 +169,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 406
+#define DAGL_ABI_VERSION 407
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -533,6 +533,33 @@ int dagl_ce_generic_core_backward(void* stream, int B, int H, int W, int ksize, 
                                   float softmax_scale, int mode, int k, const float* wq_rows, const float* x_rows, const float* b2p,
                                   const float* thr, const float* bias, const float* d_out, float* d_wq, float* d_x, float* d_b2p,
                                   float* d_thr, float* d_bias, void* workspace, size_t workspace_bytes);
+
+/* (ABI 407) The residual trunk's convolutions (csrc/trunk.hip): 2-D convolution, stride 1, padding ksize / 2, ksize 1 or 3,
+ * dilation 1, groups 1, 1 <= Cin, Cout <= 64, fp32 NCHW contiguous at any B, H, W >= 1, on the fp32 matrix cores (exact fp32
+ * products, fp32 accumulation: the stock layer's arithmetic, no range limits).  w is the layer's weight [Cout, Cin, ksize, ksize].
+ * Launches are stream-ordered; nothing is read back.
+ *   pack_weights: w -> the kernels' fragment layout, dagl_trunk_packed_floats(...) floats; transposed = 1 gives the layout of the
+ *     input gradient (taps mirrored, channels swapped).  Callers cache it until the weight changes.
+ *   conv_forward: out = conv(x) (+ bias[o]); with slope (one float): PReLU, pre_out (may be NULL) = the value before it; with
+ *     residual: out = out * res_scale + residual.  bias / slope / pre_out / residual may be NULL.
+ *   conv_input_grad: d_in [B,Cin,H,W] = alpha * conv_transposed(d_out); with slope: the PReLU backward from the saved pre-activation
+ *     pre [B,Cin,H,W] (d_in = pre > 0 ? g : slope g) and slope_part = dagl_trunk_input_grad_blocks(B,H,W) fp64 partial sums of the
+ *     slope gradient; with skip_grad: d_in += skip_grad.
+ *   conv_weight_grad: d_w = alpha * sum_pix x (x) d_out, d_b (may be NULL) = alpha * column sums of d_out, per-block partials in
+ *     scratch (16-byte aligned, dagl_trunk_weight_grad_scratch_bytes) added in a fixed order: the same bits on every call.  With
+ *     d_slope: d_slope[0] = the fixed-order sum of n_slope_part slope partials of an earlier conv_input_grad.                 */
+size_t dagl_trunk_packed_floats(int Cin, int Cout, int ksize, int transposed);
+int dagl_trunk_pack_weights(void* stream, int Cin, int Cout, int ksize, int transposed, const float* w, float* packed);
+int dagl_trunk_conv_forward(void* stream, int B, int Cin, int Cout, int H, int W, int ksize, const float* x, const float* packed,
+                            const float* bias, const float* slope, float* pre_out, float res_scale, const float* residual, float* out);
+int dagl_trunk_input_grad_blocks(int B, int H, int W);
+int dagl_trunk_conv_input_grad(void* stream, int B, int Cin, int Cout, int H, int W, int ksize, const float* d_out,
+                               const float* packed_t, float alpha, const float* slope, const float* pre, double* slope_part,
+                               const float* skip_grad, float* d_in);
+size_t dagl_trunk_weight_grad_scratch_bytes(int B, int Cin, int Cout, int H, int W, int ksize);
+int dagl_trunk_conv_weight_grad(void* stream, int B, int Cin, int Cout, int H, int W, int ksize, const float* x, const float* d_out,
+                                float alpha, float* d_w, float* d_b, const double* slope_part, int n_slope_part, float* d_slope,
+                                void* scratch, size_t scratch_bytes);
 
 #ifdef __cplusplus
 }
