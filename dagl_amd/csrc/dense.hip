@@ -82,13 +82,10 @@ constexpr int DN_CTMAX = 3;
 __host__ __device__ constexpr int dn_ct_start(int w8) { return 3 * w8; }
 constexpr float DN_PS = 32768.0f, DN_VS = 16.0f;      // power-of-two pre-scaling of the split operands (weights are <= 1: 2^15 is the
                                                       // largest power of two fp16 holds)
-#ifndef DAGL_DN_SLACK
-#define DAGL_DN_SLACK 18.5f
-#endif
 // largest tolerated (shift M' - largest logit of a row) of the first pass: a weight is stored to 2^-24 / 2^15 = 2^-39 absolute (hi + lo,
 // the lo part denormal), i.e. to 2^-40 e^slack relative to the row's largest one: 1e-4 at 18.5 for a row that ONE key dominates
 // (rows with many comparable keys average it down)
-constexpr float DN_SHIFT_SLACK = DAGL_DN_SLACK;
+constexpr float DN_SHIFT_SLACK = 18.5f;
 
 __device__ __forceinline__ float dn_logit(float s, float mtq, float bsq, bool& pass) {
     const float m = (s - mtq) + bsq;                  // same expression order as dagl.py:256
@@ -180,20 +177,15 @@ __device__ __forceinline__ DnFrag dn_pv(f32x16 (&acc)[2][DN_CTMAX], unsigned va_
         const unsigned an = t + 1 < DN_CTMAX ? va_kb + vt_off[t + 1] : va_next;
         DnFrag fn;
         fn.h0 = dn_tr16(an); fn.h1 = dn_tr16(an + 128);
-#ifdef DAGL_DN_FNFULL
-        fn.l0 = dn_tr16(an + DN_VPART_B); fn.l1 = dn_tr16(an + DN_VPART_B + 128);
-#endif
         __builtin_amdgcn_sched_barrier(0);
         const dns8 vh = {f.h0[0], f.h0[1], f.h0[2], f.h0[3], f.h1[0], f.h1[1], f.h1[2], f.h1[3]};
         const dns8 vl = {f.l0[0], f.l0[1], f.l0[2], f.l0[3], f.l1[0], f.l1[1], f.l1[2], f.l1[3]};
         const dnh8 v_hi = __builtin_bit_cast(dnh8, vh), v_lo = __builtin_bit_cast(dnh8, vl);
         acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_lo, p_hi[0], acc[0][t], 0, 0, 0);
         acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_lo, p_hi[1], acc[1][t], 0, 0, 0);
-#ifndef DAGL_DN_FNFULL
         __builtin_amdgcn_sched_barrier(0);
         fn.l0 = dn_tr16(an + DN_VPART_B); fn.l1 = dn_tr16(an + DN_VPART_B + 128);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_hi, p_hi[0], acc[0][t], 0, 0, 0);
         acc[1][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_hi, p_hi[1], acc[1][t], 0, 0, 0);
         acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(v_hi, p_lo[0], acc[0][t], 0, 0, 0);
@@ -526,9 +518,6 @@ __global__ __launch_bounds__(DN_THREADS) void dense_attend_kernel(DenseArgs a) {
 #endif
                         weight_store(kg, pbuf, zpv[kg], dt[kg], hq[kg], lq[kg]);
                     }
-#ifdef DAGL_DN_PSLEEP
-                    if (sl >= DAGL_DN_PSLEEP_FROM) __builtin_amdgcn_s_sleep(DAGL_DN_PSLEEP);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 final_scores(s_new);

@@ -33,11 +33,6 @@ constexpr int G16_BK = 32;                             // K step: rows of 64 byt
 constexpr int FCG_O = 196, FCG_OP = 224, FCG_OM = 256; // outputs, padded to the K step / to the M tile
 constexpr int FCG_P = 784, FCG_PP = 896;               // patch length, padded to the N tile (7 x 128)
 constexpr float FCG_XS = 16.0f, FCG_WS = 1024.0f;      // activation / weight pre-scaling (project16.hip)
-#ifdef DAGL_FCG_NO_IMPLICIT                            // (A/B builds: the transposed patch rows as up to round 5)
-constexpr bool FCG_NO_IMPLICIT = true;
-#else
-constexpr bool FCG_NO_IMPLICIT = false;
-#endif
 
 // largest |x| of a tensor -> *word (bits of a non-negative float: integer max = float max, order-independent)
 __global__ __launch_bounds__(256) void fcg_absmax_kernel(size_t n4, const float4* __restrict__ x, unsigned* __restrict__ word) {
@@ -353,11 +348,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 && NS == 2) ? 2 : 1) vo
     auto stage = [&](int buf, int nt, long long k) {        // operand tiles of column tile nt of this block, contraction offset k
         const unsigned dst = lds0 + (unsigned)buf * STAGE;
         const int p0 = wave * PPW;                            // a wave's pieces are consecutive: 1 KiB apart in the LDS
-#if defined(DAGL_G16_M0_PER_PIECE)
-#pragma unroll
-        for (int j = 0; j < PPW; ++j)
-            glds16_asm(reinterpret_cast<const float*>(piece_src(p0 + j, nt, k)), __builtin_amdgcn_readfirstlane(dst + (unsigned)(p0 + j) * 1024));
-#else
         // four requests per M0 value (glds16x4_any_asm): with one M0 value per piece the requests were what a step waited for
 #pragma unroll
         for (int j = 0; j + 4 <= PPW; j += 4)
@@ -371,7 +361,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 && NS == 2) ? 2 : 1) vo
             constexpr int j = PPW - 1;
             glds16_asm(reinterpret_cast<const float*>(piece_src(p0 + j, nt, k)), __builtin_amdgcn_readfirstlane(dst + (unsigned)(p0 + j) * 1024));
         }
-#endif
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -389,7 +378,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 && NS == 2) ? 2 : 1) vo
                                 : g.C + (long long)bz * g.sC;
     const long long ldo = (g.slices > 1) ? g.N : g.ldc;
     // Results: a lane holds four consecutive columns of ONE row per register quad -- stored from the registers a wave instruction
-    // touched 32 rows with 32 bytes each (round 5, -DDAGL_G16_NOSTORE experiment: a third of the d rows product was its 411 MB of
+    // touched 32 rows with 32 bytes each (round 5, a build without the stores: a third of the d rows product was its 411 MB of
     // results leaving that way).  The wave's 64 x 64 tile goes through the LDS instead (the operand ring is dead behind the last
     // step's barrier: two passes of 32 rows, 8.5 KiB per wave) and leaves as whole 256-byte row segments, four rows per instruction.
     constexpr int SPITCH = 68;                                                    // floats per staged row (64 + 4: rows 8 apart share a bank)
@@ -414,11 +403,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN <= 4 && NS == 2) ? 2 : 1) vo
                 const int e = lane + 64 * j;
                 const int row = e >> 4, c4 = e & 15;
                 const int m = mw + row, n = nw + 4 * c4;
-#ifdef DAGL_G16_NOSTORE                       // (timing experiment only: results wrong)
-                if (m < g.M && n < g.N && stg[0] == 12345.678f)
-#else
                 if (m < g.M && n < g.N)                                           // (N is a multiple of 4: whole quads)
-#endif
                     {
                         // results larger than the caches (the top-k modes' score rows beyond 64 neighbours: 537 MB per 2048 queries; d rows of the
                         // projections' backward: 411 MB) leave as streaming stores: they are read back from HBM whatever happens, and as ordinary
@@ -563,16 +548,8 @@ int launch_gemm16s(hipStream_t s, const Gemm16s& g) {
         // its row tile -- one pipeline of 49 steps instead of seven blocks of 7 (each: request latency, 7 steps, 64 KiB of stores)
         const int nt = (g.N + 127) / 128;
         gl.n_loop = (g.slices == 1 && g.K <= 256 && nt > 1 && nt <= 8 && (long long)((g.M + 127) / 128) * nb >= 512) ? nt : 1;
-#ifdef DAGL_G16_NLOOP_256
-        if (gl.n_loop > 1) {                  // the same walk on 256 x 128 tiles / 8 waves / three stages: 2/3 of the operand bytes per product
-            dim3 grid2((nt + gl.n_loop - 1) / gl.n_loop, (g.M + 255) / 256, g.slices * nb);
-            hipLaunchKernelGGL((gemm16s_kernel<4, 2, 3>), grid2, dim3(512), 0, s, gl);
-        } else
-#endif
-        {
         dim3 grid((nt + gl.n_loop - 1) / gl.n_loop, (g.M + 127) / 128, g.slices * nb);
         hipLaunchKernelGGL((gemm16s_kernel<2, 2>), grid, dim3(256), 0, s, gl);
-        }
     }
     DAGL_LAUNCH_CHECK("gemm16s_kernel");
     if (g.slices > 1) {
@@ -688,7 +665,7 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
     DAGL_REQUIRE(((uintptr_t)scratch % 256) == 0, "dagl_fc_grad16: scratch must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * oh * ow;
-    const int im_rps = (d_w && !FCG_NO_IMPLICIT) ? fcg_implicit_rows(B, stride, oy, ox, oh, ow, Hp, Wp) : 0;
+    const int im_rps = d_w ? fcg_implicit_rows(B, stride, oy, ox, oh, ow, Hp, Wp) : 0;
     const FcgPlan p = fcg_plan(n, d_map ? ow : 0, im_rps, ow);
     DAGL_REQUIRE(scratch_bytes >= p.o_end, "dagl_fc_grad16: scratch %zu B, need %zu B", scratch_bytes, p.o_end);
     char* ws = static_cast<char*>(scratch);

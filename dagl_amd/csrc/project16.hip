@@ -16,7 +16,7 @@
 // group's tiles (8 or 6 accumulators): a weight fragment read from the LDS feeds two multiply chains, and a block fetches only its
 // group's rows of a tap's weight slice.  (Round 3: a wave = 32 patches x all 7 tiles; per SIMD and tap 6.5 LDS-DMA pieces and 32
 // fragment reads beside 42 multiplies; now 3.5 and 22.)  The overhang of the grid over one resident round is cut into single-tile
-// blocks of 4 items (project16_body<1>).
+// blocks of 4 items (project16_body).
 //   A (patches): keys -- per item a 2-row ring of the hi / lo map rows its patches touch (38 pixels), by LDS-DMA: each
 //                input pixel is fetched once per kernel ROW, not once per tap; queries (stride-4 grid) -- per tap each lane
 //                DMA-copies the 16 bytes it reads back
@@ -169,11 +169,8 @@ struct Proj16Args {
 
 // Block = 4 waves (two blocks per CU, independent barriers).  All operands arrive by LDS-DMA issued from inline asm and are
 // consumed behind COUNTED s_waitcnt vmcnt(N): the weight slice of tap t+PD is requested while tap t is multiplied.
-#ifndef DAGL_P16_BW
-#define DAGL_P16_BW 4
-#endif
-constexpr int P16_BW = DAGL_P16_BW;                    // waves per block (two blocks per CU: independent barriers)
-constexpr int P16_BLOCKS_PER_CU = (P16_BW > 4) ? 1 : 2;
+constexpr int P16_BW = 4;                              // waves per block (two blocks per CU: independent barriers)
+constexpr int P16_BLOCKS_PER_CU = 2;
 constexpr int P16_RING = 4;                            // weight stages
 constexpr int P16_PD_KEYS = 3;                         // prefetch distance (taps): key blocks
 constexpr int P16_PD_Q = 2;                            // query blocks (their per-tap patch stages leave room for 3 only)
@@ -222,14 +219,16 @@ __device__ __forceinline__ bool p16_tier_is_coarse(const Proj16Args& pa, int hea
     return !(m * B1_FINE_SCALE < RANGE_LIMIT);
 }
 
-template <int NT, bool KEYS, int VAR>
+// Single-tile key blocks (the overhang of the grid, project16_kernel): 4 waves x one 32-patch item x output tile n0 -- the round-3 shape
+// (a wave = 32 patches, a 2-row ring of map rows per wave, 14 KiB weight stages) cut down to one of the 7 tiles.
 __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned char* smem, int n0, int blk, int b) {
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lane = tid & 63;
     const int i = lane & 31, h = lane >> 5;
     const Grid& gr = pa.gr;
-    constexpr int which = KEYS ? 0 : 1;
+    constexpr int which = 0;                           // (keys)
+    constexpr int NT = 1;                              // output tiles per block
     const int head = b / pa.imgs_per_head;
     P16TierReq tier_rq;
     p16_tier_request(pa, head, lane, tier_rq);
@@ -237,17 +236,11 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
     const unsigned short* __restrict__ wp = pa.wp[which] + (size_t)head * P16_PACKED_HALFS + (size_t)n0 * 32 * P16_ROWH;
     const int n_items = pa.n_items[which];
     const int segs_per_row = pa.segs[which];
-    constexpr int PD = KEYS ? P16_PD_KEYS : P16_PD_Q;
-    // the 14th KiB of a tap's slice holds output rows 208..223: padding whose products are never stored (feature rows end at
-    // column 203, the bf16 copies at 207; an output column depends on its own weight row only) -- not fetched
-    constexpr int PIECES = (NT == P16_NT) ? 13 : (NT * 32 * P16_ROWH * 2 + 1023) / 1024;   // 13 (NT=7) / 2 (NT=1)
-    constexpr int PBASE = PIECES / P16_BW;                                      // weight pieces per wave per tap ...
-    const bool extra = wave < (PIECES % P16_BW);                                // ... plus one for the first waves
 
     int item = blk * P16_BW + wave;
     const bool wave_valid = item < n_items;
     if (!wave_valid) item = n_items - 1;
-    const int row_len = KEYS ? gr.W : gr.Lw;
+    const int row_len = gr.W;
     // the item's patches: lin -> n = 32 item + i in row-major order: nA of them in row gy from pixel gx0 on, the rest at the
     // start of row gy + 1 (rows are at least 32 wide in this mode); else 32 patches of row gy from gx0 on
     const bool lin = pa.lin[which] != 0;
@@ -256,12 +249,12 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
         base_row = item * 32;
         gy = base_row / row_len; gx0 = base_row - gy * row_len;
         nA = row_len - gx0 < 32 ? row_len - gx0 : 32;
-        lim = (KEYS ? gr.N : gr.L) - base_row;
+        lim = gr.N - base_row;
     } else {
         gy = item / segs_per_row; gx0 = (item % segs_per_row) * 32;
         nA = 32; base_row = gy * row_len + gx0; lim = row_len - gx0;
     }
-    const int off_i = (i < nA) ? i : i + 6;            // keys: the patch's pixel position in the staged row (segment B behind A's halo)
+    const int off_i = (i < nA) ? i : i + 6;            // the patch's pixel position in the staged row (segment B behind A's halo)
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(smem));
 
     f32x16 hh[NT];
@@ -270,39 +263,9 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
 #pragma unroll
         for (int r = 0; r < 16; ++r) hh[n][r] = 0.f;
 
-    auto issue_w = [&](int t) {                        // weight slice of tap t -> ring stage t % RING
-        if (VAR == 6) return;
-        if (VAR == 11 && (t & 1)) return;
-        const unsigned st = lds0 + (unsigned)(t % P16_RING) * P16_STAGE_B;
-        const unsigned short* wsrc = wp + (size_t)t * P16_SLICE_H;
-#pragma unroll
-        for (int j = 0; j < PBASE; ++j) {
-            const int p = wave + P16_BW * j;
-            glds16_asm(reinterpret_cast<const float*>(wsrc + (size_t)p * 512 + lane * 8),
-                       __builtin_amdgcn_readfirstlane(st + p * 1024));
-        }
-        if (extra) {
-            const int p = wave + P16_BW * PBASE;
-            glds16_asm(reinterpret_cast<const float*>(wsrc + (size_t)p * 512 + lane * 8),
-                       __builtin_amdgcn_readfirstlane(st + p * 1024));
-        }
-    };
-
-    // ---- patch operand plumbing -------------------------------------------------------------------------
-    const unsigned short* ahi = nullptr; const unsigned short* alo = nullptr;   // queries: this lane's patch corner
-    size_t krow0 = 0;                                                            // keys: halfs offset of (row py, pixel gx0)
-    if (KEYS) {
-        krow0 = (size_t)b * gr.Hp * gr.Wp * CH;
-    } else {
-        int qy = gy, gx = gx0 + i;
-        if (lin) { int q = base_row + i; if (q > gr.L - 1) q = gr.L - 1; qy = q / row_len; gx = q - qy * row_len; }
-        else if (gx >= row_len) gx = row_len - 1;
-        const int py = QS * qy - gr.pt + PADPIX, px = QS * gx - gr.pl + PADPIX;
-        const size_t aoff = (((size_t)b * gr.Hp + py) * gr.Wp + px) * CH + 8 * h;
-        ahi = tier.hi + aoff; alo = tier.lo + aoff;
-    }
-    auto issue_row = [&](int r) {                      // keys: kernel row r of the item (44 pixels, hi | lo) -> row buffer r & 1
-        if (VAR == 6) return;                          // positions 0 .. nA+5: map row gy + r from pixel gx0; from nA+6 on: row gy+1+r from pixel 0
+    const size_t krow0 = (size_t)b * gr.Hp * gr.Wp * CH;                 // halfs offset of the image's map
+    auto issue_row = [&](int r) {                      // kernel row r of the item (44 pixels, hi | lo) -> row buffer r & 1
+                                                       // positions 0 .. nA+5: map row gy + r from pixel gx0; from nA+6 on: row gy+1+r from pixel 0
         const unsigned dst = lds0 + P16_OFF_A + wave * (2 * P16_AROW) + (r & 1) * P16_AROW;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                  // pieces: hi px 0-31, hi px 32-43 (24 lanes), lo px 0-31, lo px 32-43
@@ -316,141 +279,56 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
             if ((j & 1) == 0 || lane < 2 * (P16_APX - 32)) glds16_asm(reinterpret_cast<const float*>(src), __builtin_amdgcn_readfirstlane(d));
         }
     };
-    auto issue_q = [&](int t) {                        // queries: the 16 B of tap t this lane will read back
-        const int kh = t / KS, kw = t - kh * KS;
-        const size_t o = ((size_t)kh * gr.Wp + kw) * CH;
-        const unsigned sa = lds0 + P16_OFF_A + (unsigned)(t % P16_QRING) * (P16_BW * 2048) + wave * 2048;
-        glds16_asm(reinterpret_cast<const float*>(ahi + o), __builtin_amdgcn_readfirstlane(sa));
-        glds16_asm(reinterpret_cast<const float*>(alo + o), __builtin_amdgcn_readfirstlane(sa + 1024));
-    };
-    // landing of tap t+1: its weight pieces (and everything issued before them) are complete once at most the DMAs
-    // issued after them are outstanding.  Patch-row pieces issued in between only make the wait stricter.
-    constexpr int PER_Q = KEYS ? 0 : 2;
-#define P16_WAIT(P) do { if (VAR == 4 || VAR == 6 || VAR == 11) break; if (extra) dma_wait_le<(P) * (PBASE + 1 + PER_Q)>(); else dma_wait_le<(P) * (PBASE + PER_Q)>(); } while (0)
 
-    const int swz = (i >> 2) & 3;                                       // slot swizzle of row n*32 + i (n*32 does not change it)
-    const int boff_hi = i * (P16_ROWH * 2) + ((h ^ swz) << 4);          // bytes: B fragment row n*32 + i, hi half h
+    const int swz = (i >> 2) & 3;                                       // slot swizzle of row i
+    const int boff_hi = i * (P16_ROWH * 2) + ((h ^ swz) << 4);          // bytes: B fragment row i, hi half h
     const int boff_lo = i * (P16_ROWH * 2) + (((2 + h) ^ swz) << 4);
-    if (NT == 1 && KEYS) {
-        // single-tile blocks (the split remainder of the grid) have 3 MFMAs per tap: a barrier per tap would leave them
-        // latency-bound, so a ring stage holds the 7 taps of one kernel row (7 x 2 KiB) and there is one barrier per row
-        auto issue_wrow = [&](int kh) {
-            const unsigned st = lds0 + (unsigned)(kh % P16_RING) * P16_STAGE_B;
+    // 3 MFMAs per tap: a barrier per tap would leave these blocks latency-bound, so a ring stage holds the 7 taps of one kernel
+    // row (7 x 2 KiB) and there is one barrier per row
+    auto issue_wrow = [&](int kh) {
+        const unsigned st = lds0 + (unsigned)(kh % P16_RING) * P16_STAGE_B;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int p = wave + P16_BW * j;                      // 14 pieces: tap kw = p >> 1, half (p & 1) of its 2 KiB
-                if (p < 2 * KS)
-                    glds16_asm(reinterpret_cast<const float*>(wp + (size_t)(kh * KS + (p >> 1)) * P16_SLICE_H + (p & 1) * 512 + lane * 8),
-                               __builtin_amdgcn_readfirstlane(st + p * 1024));
-            }
-        };
-        const bool four = wave < 2;                                    // waves 0, 1 carry 4 weight pieces per row, waves 2, 3 carry 3
-        f32x16 c1, c2;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { c1[r] = 0.f; c2[r] = 0.f; }
-        issue_row(0); issue_wrow(0); issue_wrow(1);
-        if (four) dma_wait_le<4>(); else dma_wait_le<3>();             // row 0 and weight row 0 landed
-        __syncthreads();
-        if (p16_tier_is_coarse(pa, head, lane, tier_rq)) {             // (block-uniform) the map lives in the coarse tier: row 0 again
-            tier.hi = pa.map_hi2; tier.lo = pa.map_lo2; tier.unscale = 1.0f / (B1_COARSE_SCALE * P16_W_SCALE);
-            issue_row(0);
-            dma_wait_le<0>();
-            __syncthreads();
+        for (int j = 0; j < 4; ++j) {
+            const int p = wave + P16_BW * j;                      // 14 pieces: tap kw = p >> 1, half (p & 1) of its 2 KiB
+            if (p < 2 * KS)
+                glds16_asm(reinterpret_cast<const float*>(wp + (size_t)(kh * KS + (p >> 1)) * P16_SLICE_H + (p & 1) * 512 + lane * 8),
+                           __builtin_amdgcn_readfirstlane(st + p * 1024));
         }
-        for (int kh = 0; kh < KS; ++kh) {
-            if (kh + 1 < KS) issue_row(kh + 1);
-            if (kh + 2 < KS) issue_wrow(kh + 2);
-            const unsigned char* sa0 = smem + P16_OFF_A + wave * (2 * P16_AROW) + (kh & 1) * P16_AROW + off_i * 32 + 16 * h;
-            const unsigned char* sb = smem + (kh % P16_RING) * P16_STAGE_B;
+    };
+    const bool four = wave < 2;                                    // waves 0, 1 carry 4 weight pieces per row, waves 2, 3 carry 3
+    f32x16 c1, c2;
 #pragma unroll
-            for (int kw = 0; kw < KS; ++kw) {
-                const f16x8 fa_hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa0 + kw * 32));
-                const f16x8 fa_lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa0 + kw * 32 + P16_APART));
-                const f16x8 w_hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + kw * 2048 + boff_hi));
-                const f16x8 w_lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + kw * 2048 + boff_lo));
-                c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_lo, c1, 0, 0, 0);
-                c2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_lo, w_hi, c2, 0, 0, 0);
-                hh[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_hi, hh[0], 0, 0, 0);
-            }
-            // next row's patches and weights must have landed; only the weight row issued above may still be in flight
-            if (kh + 2 < KS) { if (four) dma_wait_le<4>(); else dma_wait_le<3>(); } else dma_wait_le<0>();
-            __syncthreads();
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hh[0][r] += c1[r] + c2[r];
-    } else {
-    if (KEYS) issue_row(0);
-#pragma unroll
-    for (int t = 0; t < PD; ++t) { issue_w(t); if (!KEYS) issue_q(t); }
-    P16_WAIT(PD - 1);
+    for (int r = 0; r < 16; ++r) { c1[r] = 0.f; c2[r] = 0.f; }
+    issue_row(0); issue_wrow(0); issue_wrow(1);
+    if (four) dma_wait_le<4>(); else dma_wait_le<3>();             // row 0 and weight row 0 landed
     __syncthreads();
-    if (p16_tier_is_coarse(pa, head, lane, tier_rq)) {                 // (block-uniform) the map lives in the coarse tier
+    if (p16_tier_is_coarse(pa, head, lane, tier_rq)) {             // (block-uniform) the map lives in the coarse tier: row 0 again
         tier.hi = pa.map_hi2; tier.lo = pa.map_lo2; tier.unscale = 1.0f / (B1_COARSE_SCALE * P16_W_SCALE);
-        if (!KEYS) {
-            int qy = gy, gx = gx0 + i;
-            if (lin) { int q = base_row + i; if (q > gr.L - 1) q = gr.L - 1; qy = q / row_len; gx = q - qy * row_len; }
-            else if (gx >= row_len) gx = row_len - 1;
-            const int py = QS * qy - gr.pt + PADPIX, px = QS * gx - gr.pl + PADPIX;
-            const size_t aoff = (((size_t)b * gr.Hp + py) * gr.Wp + px) * CH + 8 * h;
-            ahi = tier.hi + aoff; alo = tier.lo + aoff;
-#pragma unroll
-            for (int t = 0; t < PD; ++t) issue_q(t);
-        } else {
-            issue_row(0);
-        }
+        issue_row(0);
         dma_wait_le<0>();
         __syncthreads();
     }
-    dbg_stamp(pa.times, blockIdx.x, 1);
-
-    if (VAR == 9) { if (hh[0][0] != 0.f) pa.feat[which][0] = 1.f; return; }
-    auto compute = [&](int step) {
-        const int kh = step / KS, kw = step - kh * KS;
-        const unsigned char* sa;
-        int lo_off;
-        if (KEYS) { sa = smem + P16_OFF_A + wave * (2 * P16_AROW) + (kh & 1) * P16_AROW + (off_i + kw) * 32 + 16 * h; lo_off = P16_APART; }
-        else { sa = smem + P16_OFF_A + (step % P16_QRING) * (P16_BW * 2048) + wave * 2048 + lane * 16; lo_off = 1024; }
-        const f16x8 fa_hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa));
-        const f16x8 fa_lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa + lo_off));
-        const unsigned char* sb = smem + (step % P16_RING) * P16_STAGE_B;
-        // all fragment reads of the tap first (one exposed LDS latency per tap instead of one per tile), then the
-        // MFMAs grouped so that no instruction depends on its predecessor
-        f16x8 w_hi[NT], w_lo[NT];
+    for (int kh = 0; kh < KS; ++kh) {
+        if (kh + 1 < KS) issue_row(kh + 1);
+        if (kh + 2 < KS) issue_wrow(kh + 2);
+        const unsigned char* sa0 = smem + P16_OFF_A + wave * (2 * P16_AROW) + (kh & 1) * P16_AROW + off_i * 32 + 16 * h;
+        const unsigned char* sb = smem + (kh % P16_RING) * P16_STAGE_B;
 #pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            w_hi[n] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + n * 32 * P16_ROWH * 2 + boff_hi));
-            w_lo[n] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + n * 32 * P16_ROWH * 2 + boff_lo));
+        for (int kw = 0; kw < KS; ++kw) {
+            const f16x8 fa_hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa0 + kw * 32));
+            const f16x8 fa_lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa0 + kw * 32 + P16_APART));
+            const f16x8 w_hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + kw * 2048 + boff_hi));
+            const f16x8 w_lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + kw * 2048 + boff_lo));
+            c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_lo, c1, 0, 0, 0);
+            c2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_lo, w_hi, c2, 0, 0, 0);
+            hh[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_hi, hh[0], 0, 0, 0);
         }
-        if (VAR == 5) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) asm volatile("" :: "v"(fa_hi), "v"(fa_lo), "v"(w_hi[n]), "v"(w_lo[n]));
-            return;
-        }
-        // the two cross terms (2^-11 of the main one) go into the same accumulator: small terms first
-#pragma unroll
-        for (int n = 0; n < NT; ++n) hh[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_lo[n], hh[n], 0, 0, 0);
-#pragma unroll
-        for (int n = 0; n < NT; ++n) hh[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_lo, w_hi[n], hh[n], 0, 0, 0);
-#pragma unroll
-        for (int n = 0; n < NT; ++n) hh[n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi, w_hi[n], hh[n], 0, 0, 0);
-    };
-    // steady state: PD-1 younger taps stay in flight across the barrier
-    for (int step = 0; step < ((VAR == 7) ? 1 : (VAR == 8) ? 23 : P16_STEPS - PD); ++step) {
-        if (KEYS && (step % KS) == 0 && step / KS + 1 < KS) issue_row(step / KS + 1);     // one kernel row ahead
-        issue_w(step + PD);
-        if (!KEYS) issue_q(step + PD);
-        compute(step);
-        P16_WAIT(PD - 1);
+        // next row's patches and weights must have landed; only the weight row issued above may still be in flight
+        if (kh + 2 < KS) { if (four) dma_wait_le<4>(); else dma_wait_le<3>(); } else dma_wait_le<0>();
         __syncthreads();
     }
-    // drain: the last PD taps, nothing left to issue
-    if (PD == 3) { compute(P16_STEPS - 3); P16_WAIT(1); __syncthreads(); }
-    compute(P16_STEPS - 2); P16_WAIT(0); __syncthreads();
-    compute(P16_STEPS - 1);
-    __syncthreads();
-    }
-#undef P16_WAIT
-    static_assert(PD == 2 || PD == 3, "the drain sequence above is written for PD = 2 or 3");
+#pragma unroll
+    for (int r = 0; r < 16; ++r) hh[0][r] += c1[r] + c2[r];
 
     dbg_stamp(pa.times, blockIdx.x, 2);
     // ---- epilogue: D[row = patch (r&3)+8(r>>2)+4h][col = output (n0+n)*32 + i] ----------------------------
@@ -458,75 +336,7 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
     uint16_t* hb = pa.feat_h[which] ? pa.feat_h[which] + (size_t)b * pa.rows_alloc_h[which] * DSH : nullptr;
     const float* __restrict__ fbias = pa.bias[which][head];
     const int grid_row_base = base_row;
-    float colsum_r[NT];                                                 // keys: this lane's share of the column sums
-    if (NT == P16_NT && VAR == 0) {
-        // Full blocks: a lane holds 16 rows x 7 columns of its wave's 32 x 224 tile, one dword of a row per store -- 224 store
-        // instructions per wave (fp32 + bf16), each covering two 128-byte (64-byte) row segments; with every CU storing at once
-        // that was 14.6 us of the kernel (store-issue bound: MI355X_MICROARCH.md, epilogue store tail).  The wave's 32 feature
-        // rows are CONTIGUOUS in memory (row stride = row length = 816 bytes; 432 for the bf16 copy), so the tile goes through
-        // the LDS (the weight ring is dead now: 20 KiB per wave, two passes of 16 rows) and leaves as lane-linear 16-byte
-        // stores: 26 + 14 store instructions per wave instead of 224, whole cache lines.
-        float* stg = reinterpret_cast<float*>(smem) + wave * (16 * DS);     // [16 rows][204] floats = 13056 B per wave
-#pragma unroll
-        for (int n = 0; n < NT; ++n) colsum_r[n] = 0.f;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const int col = n * 32 + i;
-                const float bv = (col < D) ? fbias[col] : 0.0f;
-#pragma unroll
-                for (int r8 = 0; r8 < 8; ++r8) {
-                    const int r = 8 * pass + r8;
-                    const int rl = (r8 & 3) + 8 * (r8 >> 2) + 4 * h;              // row inside the pass: 0..15
-                    const int rr = rl + 16 * pass;
-                    float v = hh[n][r] * tier.unscale + bv;
-                    v = v > 0.f ? v : 0.f;
-                    if (col >= D) v = 0.f;
-                    if (col < DS) stg[rl * DS + col] = v;
-                    colsum_r[n] += (wave_valid && rr < lim) ? v : 0.f;
-                }
-            }
-            // (the wave only reads back what it wrote itself: LDS operations of a wave execute in order, no barrier)
-            const int rows_here = wave_valid ? (lim - 16 * pass < 16 ? (lim - 16 * pass < 0 ? 0 : lim - 16 * pass) : 16) : 0;
-            const int n4 = rows_here * (DS / 4);                                  // float4 chunks of the contiguous rows
-            float4* dst = reinterpret_cast<float4*>(fb + (size_t)(grid_row_base + 16 * pass) * DS);
-            const float4* src = reinterpret_cast<const float4*>(stg);
-#pragma unroll
-            for (int j = 0; j < (16 * (DS / 4) + 63) / 64; ++j) {                 // 13
-                const int e = lane + 64 * j;
-                if (e < n4) dst[e] = src[e];
-            }
-            if (hb != nullptr) {
-                // bf16 copy: rows of 216 halfs = 27 chunks of 8 columns; columns 196.. are zero
-                const bool tiled = pa.tiled_h[which] != 0;                       // 26 x (16 rows x 16 B) per pass instead of 16 rows x 27
-                const int n8 = tiled ? 26 * 16 : rows_here * (DSH / 8);
-                uint4* dh = reinterpret_cast<uint4*>(hb + (size_t)(grid_row_base + (tiled ? 0 : 16 * pass)) * DSH);
-#pragma unroll
-                for (int j = 0; j < (16 * (DSH / 8) + 63) / 64; ++j) {            // 7
-                    const int e = lane + 64 * j;
-                    const int row = tiled ? (e & 15) : e / (DSH / 8);
-                    const int c8 = tiled ? (e >> 4) : e - row * (DSH / 8);
-                    if (e < n8 && row < rows_here) {
-                        // columns 8 c8 .. + 7 of the staged row: two 16-byte reads (row stride 816 B = 51 x 16); past column 203: zeros
-                        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
-                        const float4 lo4 = (8 * c8 < DS) ? *reinterpret_cast<const float4*>(stg + row * DS + 8 * c8) : z4;
-                        const float4 hi4 = (8 * c8 + 4 < DS) ? *reinterpret_cast<const float4*>(stg + row * DS + 8 * c8 + 4) : z4;
-                        const float f8[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-                        unsigned short q[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) {
-                            unsigned bits = __float_as_uint(f8[u]);
-                            bits = (bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16;   // fp32 -> bf16, round to nearest even
-                            q[u] = (unsigned short)bits;
-                        }
-                        dh[tiled ? 416 * pass + e : e] = make_uint4(q[0] | ((unsigned)q[1] << 16), q[2] | ((unsigned)q[3] << 16),
-                                                                               q[4] | ((unsigned)q[5] << 16), q[6] | ((unsigned)q[7] << 16));
-                    }
-                }
-            }
-        }
-    } else {
+    float colsum_r[NT];                                                 // this lane's share of the column sums
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         const int col = (n0 + n) * 32 + i;
@@ -539,15 +349,14 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
             float v = hh[n][r] * tier.unscale + bv;
             v = v > 0.f ? v : 0.f;
             if (col >= D) v = 0.f;
-            if (VAR == 1 && v != 12345.678f) continue;
             if (ok && col < DS) fb[(size_t)(grid_row_base + rr) * DS + col] = v;
-            if (VAR != 3 && ok && hb != nullptr && col < DPAD) {
+            if (ok && hb != nullptr && col < DPAD) {
                 unsigned u = __float_as_uint(v);
                 u = (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;            // fp32 -> bf16, round to nearest even
                 if (pa.tiled_h[which]) hb[(size_t)grid_row_base * DSH + (rr >> 4) * 3328 + ((col >> 3) * 16 + (rr & 15)) * 8 + (col & 7)] = (uint16_t)u;
                 else hb[(size_t)(grid_row_base + rr) * DSH + col] = (uint16_t)u;
             }
-            if (VAR == 0 && ok && pa.split_hi[which] != nullptr && col < DSH) {           // split-fp16 copy (see project16_body2): columns 196 .. 215 zero
+            if (ok && pa.split_hi[which] != nullptr && col < DSH) {           // split-fp16 copy (see project16_body2): columns 196 .. 215 zero
                 const float vs = v * DN_FS;
                 if (!(vs < RANGE_LIMIT) && pa.range.word != nullptr) *pa.range.word = pa.range.tag;
                 const _Float16 hv = (_Float16)vs;
@@ -559,18 +368,14 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
         }
         colsum_r[n] = s;
     }
-    }
     float* csum = reinterpret_cast<float*>(smem);                       // [waves][NT*32] (everything else in the LDS is dead now)
-    if (KEYS) {
-        if (NT == P16_NT && VAR == 0) __syncthreads();                  // the staging regions are about to be overwritten
 #pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            float s = colsum_r[n];
-            s += __shfl_xor(s, 32);                                   // the two row halves of the tile
-            if (h == 0) csum[wave * (NT * 32) + n * 32 + i] = s;
-        }
+    for (int n = 0; n < NT; ++n) {
+        float s = colsum_r[n];
+        s += __shfl_xor(s, 32);                                   // the two row halves of the tile
+        if (h == 0) csum[wave * (NT * 32) + n * 32 + i] = s;
     }
-    if (KEYS && pa.colpart != nullptr) {
+    if (pa.colpart != nullptr) {
         // fixed-order block reduction of the key column sums (no atomics: the row mean must be reproducible)
         __syncthreads();
         if (tid < NT * 32) {
@@ -654,15 +459,8 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
             for (int r = 0; r < 16; ++r) hh[it][n][r] = 0.f;
 
     auto issue_w = [&](int t) {                        // the group's rows of tap t's weight slice -> ring stage t % RING
-#if defined(DAGL_P16_HALFW)
-        if (t & 1) return;               // (timing experiment, wrong results: half of the weight LDS-DMA)
-#endif
-#if defined(DAGL_P16_NOW)
-        return;                          // (timing experiment, wrong results: no weight LDS-DMA at all)
-#endif
         const unsigned st = lds0 + (unsigned)(t % P16_RING) * P16_STAGE2_B;
         const unsigned short* wsrc = wp + (size_t)t * P16_SLICE_H;
-#if !defined(DAGL_P16_M0_PER_PIECE)
         // a wave's pieces are ADJACENT, so that two of them go out under one M0 value (glds16x2_asm); same pieces per wave as below
         if (PBASE == 2 && (PIECES % P16_BW) == 0) {
             const int p = 2 * wave;
@@ -676,9 +474,7 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
                 const int p = nx + wave;
                 glds16_asm(reinterpret_cast<const float*>(wsrc + (size_t)p * 512 + lane * 8), __builtin_amdgcn_readfirstlane(st + p * 1024));
             }
-        } else
-#endif
-        {
+        } else {
 #pragma unroll
         for (int j = 0; j < PBASE; ++j) {
             const int p = wave + P16_BW * j;
@@ -708,11 +504,7 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
     auto issue_row = [&](int r) {                      // keys: kernel row r of both items (44 pixels, hi | lo) -> row buffer r & 1
 #pragma unroll
         for (int it = 0; it < PW; ++it) {
-#if defined(DAGL_P16_HALFROWS)
-            if (it > 0) break;           // (timing experiment, wrong results: half of the key-row LDS-DMA -- what a block shared by both tile groups would issue)
-#endif
             const unsigned dst = lds0 + P16_OFF_A2 + (wave * PW + it) * (2 * P16_AROW) + (r & 1) * P16_AROW;
-#if !defined(DAGL_P16_M0_PER_PIECE)
             // pieces: hi px 0-31, hi px 32-43 (24 lanes), lo px 0-31, lo px 32-43 -- the two whole ones and the two partial ones each under ONE
             // M0 value (glds16x2_off_asm; hi and lo of a pixel sit at the same offset of their maps)
 #pragma unroll
@@ -726,19 +518,6 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
                 if (half == 0) glds16x2_off_asm<0, P16_APART>(tier.hi + o, tier.lo + o, __builtin_amdgcn_readfirstlane(dst));
                 else if (lane < 2 * (P16_APX - 32)) glds16x2_off_asm<1024, P16_APART + 1024>(tier.hi + o, tier.lo + o, __builtin_amdgcn_readfirstlane(dst));
             }
-#else
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {              // pieces: hi px 0-31, hi px 32-43 (24 lanes), lo px 0-31, lo px 32-43
-                const int p = (j & 1) * 32 + (lane >> 1);
-                int row = gy[it] + r, px = gx0[it] + p;
-                if (p >= nA[it] + 6) { row += 1; px = p - (nA[it] + 6); }
-                if (px > gr.Wp - 1) px = gr.Wp - 1;                                   // stay inside the map
-                if (row > gr.Hp - 1) row = gr.Hp - 1;
-                const unsigned short* src = ((j < 2) ? tier.hi : tier.lo) + krow0 + ((size_t)row * gr.Wp + px) * CH + 8 * (lane & 1);
-                const unsigned d = dst + (j >> 1) * P16_APART + (j & 1) * 1024;
-                if ((j & 1) == 0 || lane < 2 * (P16_APX - 32)) glds16_asm(reinterpret_cast<const float*>(src), __builtin_amdgcn_readfirstlane(d));
-            }
-#endif
         }
     };
     auto issue_q = [&](int t) {                        // queries: the 16 B of tap t this lane will read back, both items
@@ -814,7 +593,6 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
 #pragma unroll
             for (int it = 0; it < PW; ++it) hh[it][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa_hi[it], w_hi[n], hh[it][n], 0, 0, 0);
     };
-#ifndef DAGL_P16_PIPE
 #if defined(DAGL_ABLATION) && defined(DAGL_P16_PHASES)
     // (experiment) where a wave's loop time goes: shader clocks of (0) the requests, (1) fragment reads + multiplies issued, (2) the counted
     // wait for tap t + 1's pieces, (3) the barrier; wave 0's sums replace the block's four stamps
@@ -848,83 +626,6 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
     compute(P16_STEPS - 2); P16_WAIT2(0); __syncthreads();
     compute(P16_STEPS - 1);
     __syncthreads();
-#else
-    // (experiment, round 6) the fragments of tap t + 1 are read right behind tap t's barrier -- which is what makes them readable -- and
-    // under tap t's second and third multiply groups; tap t + 1 starts its first group from registers.  Two fragment sets, taps in pairs.
-    (void)compute;
-    struct Frag { f16x8 fa_hi[PW], fa_lo[PW], w_hi[NT], w_lo[NT]; };
-    auto load = [&](int step, Frag& f) {
-        const int kh = step / KS, kw = step - kh * KS;
-#pragma unroll
-        for (int it = 0; it < PW; ++it) {
-            const unsigned char* sa;
-            int lo_off;
-            if (KEYS) { sa = smem + P16_OFF_A2 + (wave * PW + it) * (2 * P16_AROW) + (kh & 1) * P16_AROW + (off_i[it] + kw) * 32 + 16 * h; lo_off = P16_APART; }
-            else { sa = smem + P16_OFF_A2 + (step % P16_QRING) * (P16_BW * PW * 2048) + (wave * PW + it) * 2048 + lane * 16; lo_off = 1024; }
-            f.fa_hi[it] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa));
-            f.fa_lo[it] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sa + lo_off));
-        }
-        const unsigned char* sb = smem + (step % P16_RING) * P16_STAGE2_B;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            f.w_lo[n] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + n * 32 * P16_ROWH * 2 + boff_lo));
-            f.w_hi[n] = __builtin_bit_cast(f16x8, *reinterpret_cast<const s16x8*>(sb + n * 32 * P16_ROWH * 2 + boff_hi));
-        }
-    };
-    auto g1 = [&](const Frag& f) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int it = 0; it < PW; ++it) hh[it][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.fa_hi[it], f.w_lo[n], hh[it][n], 0, 0, 0);
-    };
-    auto g23 = [&](const Frag& f) {
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int it = 0; it < PW; ++it) hh[it][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.fa_lo[it], f.w_hi[n], hh[it][n], 0, 0, 0);
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int it = 0; it < PW; ++it) hh[it][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.fa_hi[it], f.w_hi[n], hh[it][n], 0, 0, 0);
-    };
-    // one tap: WAITP = taps whose requests may stay in flight behind it (-1: the last tap, nothing to wait for)
-#define P16_TAP(STEP, CUR, NXT, ISSUE, WAITP)                                                                              \
-    do {                                                                                                                   \
-        if (ISSUE) {                                                                                                       \
-            if (KEYS && ((STEP) % KS) == 0 && (STEP) / KS + 1 < KS) issue_row((STEP) / KS + 1);                            \
-            issue_w((STEP) + PD);                                                                                          \
-            if (!KEYS) issue_q((STEP) + PD);                                                                               \
-        }                                                                                                                  \
-        g1(CUR);                                                                                                           \
-        if ((WAITP) >= 0) {                                                                                                \
-            if ((WAITP) == 2) P16_WAIT2(2); else if ((WAITP) == 1) P16_WAIT2(1); else P16_WAIT2(0);                        \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      /* this wave's reads of the stage about to be refilled */ \
-            __syncthreads();                                                                                               \
-            load((STEP) + 1, NXT);                                                                                         \
-        }                                                                                                                  \
-        g23(CUR);                                                                                                          \
-        if ((WAITP) >= 0) {          /* one fragment read behind every multiply (left alone, hipcc reads a fragment right before its use) */ \
-            _Pragma("unroll") for (int pin_ = 0; pin_ < 2 * PW + 2 * NT; ++pin_) {                                         \
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                         \
-                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                                                         \
-            }                                                                                                              \
-            __builtin_amdgcn_sched_group_barrier(0x008, 2 * NT * PW - (2 * PW + 2 * NT), 0);                               \
-        }                                                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-    } while (0)
-    Frag fA, fB;
-    load(0, fA);
-    static_assert(P16_STEPS == 49 && (PD == 2 || PD == 3), "the tap pairs below are written for 49 taps");
-    for (int step = 0; step < 46; step += 2) {                 // taps 0 .. 45: steady for both prefetch distances
-        P16_TAP(step, fA, fB, true, PD - 1);
-        P16_TAP(step + 1, fB, fA, true, PD - 1);
-    }
-    if (PD == 2) P16_TAP(46, fA, fB, true, 1); else P16_TAP(46, fA, fB, false, 1);
-    P16_TAP(47, fB, fA, false, 0);
-    P16_TAP(48, fA, fB, false, -1);
-    __syncthreads();
-#undef P16_TAP
-#endif
 #undef P16_WAIT2
 #if !defined(DAGL_P16_PHASES)
     dbg_stamp(pa.times, blockIdx.x, 2);
@@ -1055,12 +756,11 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
     }
 }
 
-template <int VAR>
 __global__ __launch_bounds__(64 * P16_BW, P16_BLOCKS_PER_CU) void project16_kernel(Proj16Args pa) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[P16_LDS];
     // 1-D grid.  Full blocks first (project16_body2: a wave owns 64 patches x the 4 or 3 output tiles of its block's tile group); a
     // grid that overhangs the resident-block capacity by a few blocks would cost a whole extra round, so the overhang comes last,
-    // cut into single-tile blocks (project16_body<1>).
+    // cut into single-tile blocks (project16_body).
     const int bid = blockIdx.x;
     if (bid >= pa.n_proj) {                          // (block-uniform) a block of the thr / bias heads: independent of everything this launch computes
         const int t = bid - pa.n_proj;
@@ -1087,21 +787,11 @@ __global__ __launch_bounds__(64 * P16_BW, P16_BLOCKS_PER_CU) void project16_kern
         int vunit, grp;
         if (bid < (pa.n_full & ~15)) {
             const int xcd = bid & 7, q = bid >> 3;
-#ifndef DAGL_P16_BAND_UNITS
             vunit = 8 * (q >> 1) + xcd; grp = (q ^ (q >> 5)) & 1;
-#else
-            // (round 5, measured and not shipped: profiles/r05_ab_project16_band.log) an XCD owns a BAND of consecutive units =
-            // consecutive image rows: a unit of row-major key patches needs 7 map rows, 6 of which its neighbour needs too -- with units
-            // dealt round-robin every map row is fetched by 7 of the 8 L2s.  Fewer fetches, but +1 us: the re-fetches come from the
-            // Infinity Cache and the band puts the 16 query units' blocks on one XCD
-            vunit = xcd * ((pa.n_full & ~15) >> 4) + (q >> 1); grp = (q ^ (q >> 5)) & 1;
-#endif
+            // (an XCD owning a BAND of consecutive units = image rows fetches fewer map rows and is 1 us slower: profiles/r05_ab_project16_band.log)
         } else { vunit = bid >> 1; grp = bid & 1; }
         const int b = vunit / per_units, unit = vunit - b * per_units;
-        if (VAR != 0) {                                   // ablation builds keep the round-3 body for their variants
-            if (unit < pa.units_q) { project16_body<P16_NT, false, VAR>(pa, smem, 0, 2 * unit + grp, b); }
-            else { project16_body<P16_NT, true, VAR>(pa, smem, 0, 2 * (unit - pa.units_q) + grp, b); }
-        } else if (unit < pa.units_q) {
+        if (unit < pa.units_q) {
             if (grp == 0) project16_body2<P16_G0, false>(pa, smem, 0, unit, b);
             else project16_body2<P16_G1, false>(pa, smem, P16_G0, unit, b);
         } else {
@@ -1112,7 +802,7 @@ __global__ __launch_bounds__(64 * P16_BW, P16_BLOCKS_PER_CU) void project16_kern
         const int sb = bid - pa.n_full;
         const int grp = sb / (2 * P16_NT), rest = sb - grp * (2 * P16_NT);
         const int half = rest / P16_NT, tile = rest - half * P16_NT;
-        project16_body<1, true, VAR>(pa, smem, tile, 2 * (pa.units_k - pa.n_split_groups + grp) + half, pa.batch - 1);
+        project16_body(pa, smem, tile, 2 * (pa.units_k - pa.n_split_groups + grp) + half, pa.batch - 1);
     }
 #if !defined(DAGL_P16_PHASES)
     dbg_stamp(pa.times, bid, 3);
@@ -1197,21 +887,10 @@ int launch_project16(hipStream_t s, int B, const Grid& g, int which, const uint1
         n_thr = pa.thr_x * pa.thr_y * TB_GROUPS;
     }
     const dim3 grid(pa.n_proj + n_thr), block(64 * P16_BW);
-#ifdef DAGL_ABLATION      // debug builds only: the variants give wrong results by construction
+#ifdef DAGL_ABLATION
     if (getenv("DAGL_TIMES_FILE")) pa.times = dbg_times_buffer(grid.x);
-    static const int var = getenv("DAGL_P16_VARIANT") ? atoi(getenv("DAGL_P16_VARIANT")) : 0;
-    if (var == 1) hipLaunchKernelGGL(project16_kernel<1>, grid, block, 0, s, pa);
-    else if (var == 3) hipLaunchKernelGGL(project16_kernel<3>, grid, block, 0, s, pa);
-    else if (var == 4) hipLaunchKernelGGL(project16_kernel<4>, grid, block, 0, s, pa);
-    else if (var == 5) hipLaunchKernelGGL(project16_kernel<5>, grid, block, 0, s, pa);
-    else if (var == 6) hipLaunchKernelGGL(project16_kernel<6>, grid, block, 0, s, pa);
-    else if (var == 7) hipLaunchKernelGGL(project16_kernel<7>, grid, block, 0, s, pa);
-    else if (var == 8) hipLaunchKernelGGL(project16_kernel<8>, grid, block, 0, s, pa);
-    else if (var == 9) hipLaunchKernelGGL(project16_kernel<9>, grid, block, 0, s, pa);
-    else if (var == 11) hipLaunchKernelGGL(project16_kernel<11>, grid, block, 0, s, pa);
-    else
 #endif
-    hipLaunchKernelGGL(project16_kernel<0>, grid, block, 0, s, pa);
+    hipLaunchKernelGGL(project16_kernel, grid, block, 0, s, pa);
     DAGL_LAUNCH_CHECK("project16_kernel");
 #ifdef DAGL_ABLATION
     if (pa.times) dbg_times_dump(s, "project16_kernel", pa.times, grid.x);

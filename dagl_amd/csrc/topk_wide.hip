@@ -457,14 +457,10 @@ int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const
     uint16_t* qs_lo = reinterpret_cast<uint16_t*>(p); p += wide_split_bytes(g.L);
     unsigned* amax_words = reinterpret_cast<unsigned*>(p);              // [0] keys, [1] queries: bits of the image's largest feature
     const int rows_q = feat_rows(g.L), rows_x = feat_rows(g.N);
-    // scores on the fp16 matrix cores with split operands (round 5; DAGL_WIDE_FP32_SCORES: the fp32 matrix cores as before): the image's
+    // scores on the fp16 matrix cores with split operands (round 5; on the fp32 matrix cores before that): the image's
     // features as fp16 pairs, 64 x = hi + lo (dense.hip's copies: rows of 216 halfs, columns 196.. zero), three products per score
     // accumulated in fp32 -- >= 21 significant bits, as the projections -- at 0.36 instead of 0.58 ms per 2048 rows
-#ifndef DAGL_WIDE_FP32_SCORES
     const bool split_scores = g.N >= 2048 && range.word != nullptr;      // (scan = "exact" has no range guard: fp32 products there)
-#else
-    const bool split_scores = false;
-#endif
     const int rows_xh = feat_rows_h(g.N) + 256, rows_qh = feat_rows_h(g.L) + 256;
     for (int b = 0; b < B; ++b) {
         if (split_scores) {
