@@ -329,7 +329,14 @@ __global__ __launch_bounds__(TK_THREADS, 1) void trunk_wgrad_kernel(TkWgradArgs 
     for (int t = 0; t < T; ++t) { acc[t] = (f32x4t){0.f, 0.f, 0.f, 0.f}; acc2[t] = acc[t]; }
     float bsum = 0.f;
     const int cols = (W - x0 < a.tw) ? W - x0 : a.tw;
-    const int n_steps = (cols + 3) / 4;
+    // a tile whose width is not a multiple of 4 ends in a partial step: its k lanes past the last real column hold zeros in dy, and
+    // x must be zero there too -- xs holds the tile's last real pixels at those places (tap kx = 0), and inf * 0 is NaN.  The step
+    // is peeled off the loops (their bound is the full steps) and run by the wave and into the chain that had it before: same bits
+    const int n_steps = cols / 4;
+    const int ks_u = __builtin_amdgcn_readfirstlane(ks);          // wave-uniform: the two branches below are scalar
+    const bool part_mine = (cols & 3) && n_steps % a.ksplit == ks_u;
+    const bool part_odd = ((n_steps - ks_u) / a.ksplit) & 1;
+    const bool k_real = q < (cols & 3);
     for (int y = y0; y < y1; ++y) {
         const bool more = y + 1 < y1;
         if (more) { fetch_x(y + HALO + 1); fetch_d(y + 1); }
@@ -362,6 +369,19 @@ __global__ __launch_bounds__(TK_THREADS, 1) void trunk_wgrad_kernel(TkWgradArgs 
 #pragma unroll
                 for (int kx = 0; kx < KS; ++kx)
                     acc[ky * KS + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(xp[ky][p0 + kx], bv, acc[ky * KS + kx], 0, 0, 0);
+        }
+        if (part_mine) {
+            const int p0 = 4 * n_steps;
+            const float bv = dp[p0];
+            bsum += bv;
+#pragma unroll
+            for (int ky = 0; ky < KS; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < KS; ++kx) {
+                    const float av = k_real ? xp[ky][p0 + kx] : 0.f;
+                    if (part_odd) acc2[ky * KS + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc2[ky * KS + kx], 0, 0, 0);
+                    else acc[ky * KS + kx] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[ky * KS + kx], 0, 0, 0);
+                }
         }
         if (more) { store_x(y + HALO + 1); store_d(y + 1); }
         __syncthreads();

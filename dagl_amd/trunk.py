@@ -55,7 +55,10 @@ def _check_call(conv: "Conv2d", x: torch.Tensor):
 
 class Conv2d(nn.Conv2d):
     """``nn.Conv2d`` (stride 1, same padding, 1x1 / 3x3, <= 64 channels) whose forward and backward run on the library.  The
-    packed weight layouts are cached until the parameter's storage or version changes."""
+    packed weight layouts are cached until the parameter's storage or version changes: an optimizer step, an in-place op on the
+    parameter, ``load_state_dict``, ``weight.data = t`` and ``.to(device)`` are all followed.  Writing THROUGH ``weight.data``
+    (``weight.data.mul_(2)``, ``.data.copy_(t)``, ``.data.normal_()``, ``.data.clamp_()``) changes neither, so the layer would go
+    on convolving with the old weights: call ``invalidate_packed()`` (or ``trunk.invalidate_packed(model)``) after such a write."""
 
     def _packed(self, transposed: bool) -> torch.Tensor:
         w = self.weight
@@ -175,4 +178,13 @@ def convert(module: nn.Module) -> nn.Module:
     visit(module, "")
     for m in todo:
         m.__class__ = Conv2d
+    return module
+
+
+def invalidate_packed(module: nn.Module) -> nn.Module:
+    """Drop the cached packed weights of every converted convolution of ``module``: the next call packs them again.  Needed after
+    weights were written through ``.data`` (``Conv2d``); returns ``module``."""
+    for m in module.modules():
+        if isinstance(m, Conv2d):
+            m.invalidate_packed()
     return module

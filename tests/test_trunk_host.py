@@ -124,3 +124,54 @@ def test_host_side_argument_errors():
     assert lib.dagl_trunk_conv_weight_grad(None, 8, 64, 64, 128, 128, 3, 0x1000, 0x1000, 1.0, 0x1000, None, None, 0, None,
                                            0x1000, 16) == -1
     assert b"scratch" in lib.dagl_last_error()
+
+
+def test_edge_case_table_reaches_every_tiling_class():
+    """The case table of tests/test_gpu_trunk_edges.py, seen through the library's host-callable functions alone: if the tiling is
+    retuned, this says which class the table no longer reaches."""
+    from dagl_amd import _lib
+    from dagl_amd.build import build
+    from tests.test_gpu_trunk_edges import K1_PAIRS, LARGE, PAIRS, SHAPES
+    build()
+    lib = _lib.load()
+
+    def nc(c):                                   # 4-channel k-steps of the input side, padded to a power of two
+        n, r = divmod(lib.dagl_trunk_packed_floats(c, 1, 3, 0), 9 * 64)
+        assert r == 0
+        return n
+
+    def groups(c):                               # 16-channel groups of the output side, padded to a power of two
+        n, r = divmod(lib.dagl_trunk_packed_floats(1, c, 3, 0), 9 * 64)
+        assert r == 0
+        return n
+
+    def n_pairs(cin, cout):
+        return groups(cin) * groups(cout)
+
+    def wgrad_blocks(B, cin, cout, H, W):        # partial sums per pair = blocks of the weight gradient along x
+        n, r = divmod(lib.dagl_trunk_weight_grad_scratch_bytes(B, cin, cout, H, W, 3), 4 * (9 * 256 + 16) * n_pairs(cin, cout))
+        assert r == 0
+        return n
+
+    assert len(PAIRS) == 18 and len(SHAPES) == 17 and len(K1_PAIRS) >= 6 and set(K1_PAIRS) <= set(PAIRS)
+    for table in (PAIRS, K1_PAIRS):
+        for side in (0, 1):
+            assert {nc(p[side]) for p in table} == {1, 2, 4, 8, 16}, (table, side)
+        assert {n_pairs(*p) for p in table} == {1, 2, 4, 8, 16}, table
+    for side in (0, 1):
+        chans = [p[side] for p in PAIRS]
+        assert {groups(c) for c in chans} == {1, 2, 4}, side
+        assert any(9 <= c <= 12 for c in chans) and any(33 <= c <= 48 for c in chans), side      # padding adds an empty k-step / group
+    # (n_pairs, ksplit, grid.y): 8 waves split over min(n_pairs, 8) pairs per block
+    assert {(n, 8 // min(n, 8), n // min(n, 8)) for n in (n_pairs(*p) for p in PAIRS)} == \
+        {(1, 8, 1), (2, 4, 1), (4, 2, 1), (8, 1, 1), (16, 1, 2)}
+    fwd = {s: lib.dagl_trunk_input_grad_blocks(*s) for s in SHAPES}
+    assert all(n >= 1 for n in fwd.values())
+    assert any(n > s[0] * s[1] for s, n in fwd.items())            # column tiles
+    assert any(n < s[0] * s[1] for s, n in fwd.items())            # strips of several rows
+    assert any(wgrad_blocks(s[0], 4, 4, s[1], s[2]) > s[0] * s[1] for s in SHAPES)
+    assert any(wgrad_blocks(s[0], 4, 4, s[1], s[2]) < s[0] * s[1] for s in SHAPES)
+    B, cin, cout, H, W = LARGE
+    assert n_pairs(cin, cout) == 1                                  # the three-level k-split tree
+    assert lib.dagl_trunk_input_grad_blocks(B, H, W) == B * -(-H // 64) * -(-W // 128) == 324      # the 64-row cap
+    assert wgrad_blocks(B, cin, cout, H, W) == B * -(-H // 64) * -(-W // 64)
