@@ -180,6 +180,7 @@ class CE(nn.Module):
         self.scan = "screened"
         self._ws = ops.Workspace()
         self._ws_bwd = ops.Workspace()
+        self._ws_graph = ops.Workspace()  # graph() / degrees(): a buffer of their own, so that the forward's packed weights and policy words survive
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -498,6 +499,73 @@ class CE(nn.Module):
         else:
             out = self._forward_infer(b, k_eff)
         return out if in_dtype == torch.float32 else out.to(in_dtype)
+
+    def _graph_csr(self, b: torch.Tensor, what: str, **kw):
+        """Input checks of ``forward``, the prologue convolutions in fp32, ``ops.ce_graph``."""
+        if b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.{what}: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
+        if not b.is_cuda:
+            raise DaglError(f"CE.{what}: input must be on the GPU; dagl_amd has no CPU path")
+        if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
+            raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
+        if self._generic:
+            raise DaglError(f"CE.{what}: the graph export serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
+                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
+                            f"{self.inter_channels}), which is out of its scope")
+        if torch.cuda.is_current_stream_capturing():
+            raise DaglError(f"CE.{what}: not available while the stream is being captured"
+                            + (" (the edge count is read on the host)" if what == "graph" else ""))
+        k_eff = 0
+        if self.select_mode != "adaptive":
+            if int(self.select_k) < 1:
+                raise DaglError(f"CE: select_k={self.select_k} < 1")
+            k_eff = min(int(self.select_k), b.shape[2] * b.shape[3])
+        if b.dtype in (torch.bfloat16, torch.float16):
+            b = b.float()
+        elif b.dtype != torch.float32:
+            raise DaglError(f"CE.{what}: unsupported dtype {b.dtype}")
+        H, W = b.shape[-2:]
+        heads = self.select_mode != "topk"
+        with torch.no_grad():
+            p = self._params_f32()
+            b = b.detach().contiguous()
+            hw = (p["thr_conv.weight"], p["thr_conv.bias"], p["bias_conv.weight"], p["bias_conv.bias"]) if heads else (None,) * 4
+            if self.in_channels == 64:
+                b1p, _, thr, bias = ops.ce_prologue(b, p["g.weight"], p["g.bias"], p["theta.weight"], p["theta.bias"], *hw)
+            else:
+                from . import train_ops as T
+                hw = tuple(_pad_channels4(w) if w is not None and w.dim() == 4 else w for w in hw)
+                b1p, _, thr, bias = T.prologue_forward_any_width(_pad_channels4(b).contiguous(), _pad_channels4(p["g.weight"]), p["g.bias"],
+                                                                 _pad_channels4(p["theta.weight"]), p["theta.bias"], *hw)
+            b1 = b1p[:, 3:3 + H, 3:3 + W, :].permute(0, 3, 1, 2).contiguous()
+            csr = ops.ce_graph(b1, thr, bias, p["fc1.0.weight"], p["fc1.0.bias"], p["fc2.0.weight"], p["fc2.0.bias"],
+                               mode=self.select_mode, k=k_eff, workspace=self._ws_graph, **kw)
+        return csr, k_eff
+
+    def graph(self, b: torch.Tensor, *, scores: bool = False, max_edges=None, rows_per_chunk: int = 0):
+        """The patch graph this block builds for ``b`` as a ``PatchGraph`` (CSR over the B*L query rows): per query the keys with
+        ``mask_b != 0`` and their weights ``A = softmax(softmax_scale S m) mask_b`` -- the non-zeros of ``yi``, dagl.py:256-261, not
+        renormalised --, with ``scores`` also ``S``; every ``select_mode``, any ``in_channels``, half modules on their fp32 copies.
+
+        The export is the reference semantics on the all-fp32 route (the projections and thresholds of ``scan = "exact"``), not a
+        record of the lists a screened ``forward`` used: the two agree except at pairs whose score lies within fp32 rounding of the
+        selection boundary (the adaptive threshold, the k-th best score).  A diagnostic path: one host synchronisation (the edge
+        count), no autograd, the module's state (packed weights, ``_train_dense``, top-k policy, range verdicts) untouched.
+        ``max_edges``: raise ``DaglError`` instead of allocating a larger graph (dense at 256^2: 2.7e8 edges, 3.2 GB);
+        ``rows_per_chunk``: query rows scored at a time (0 = the library's choice); the result does not depend on it."""
+        from .graph import PatchGraph
+        csr, k_eff = self._graph_csr(b, "graph", scores=bool(scores), max_edges=max_edges, rows_per_chunk=int(rows_per_chunk))
+        score = csr["score"]
+        c = self._scale_c()
+        if score is not None and c != 1.0:
+            score = score / c                        # (the query features carry the factor of _scale_c)
+        return PatchGraph(csr["row_off"], csr["key"], csr["weight"], score, b.shape[0], b.shape[2], b.shape[3], self.select_mode, k_eff)
+
+    def degrees(self, b: torch.Tensor) -> torch.Tensor:
+        """[B, L] int64: keys per query of ``graph(b)`` -- its count pass alone, nothing read on the host."""
+        csr, _ = self._graph_csr(b, "degrees", degrees_only=True)
+        off = csr["row_off"]
+        return (off[1:] - off[:-1]).view(b.shape[0], -1)
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """A module built with non-default ``ksize / stride_1 / stride_2 / inter_channels`` (dagl.py:175-176): the whole method through

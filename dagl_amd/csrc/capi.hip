@@ -1743,4 +1743,52 @@ int dagl_ce_generic_core_backward(void* stream, int B, int H, int W, int ksize, 
                                                  wq_rows, x_rows, b2p, thr, bias, d_out, d_wq, d_x, d_b2p, d_thr, d_bias, workspace);
 }
 
+// (ABI 408) the learned patch graph as CSR: csrc/graph.hip
+size_t dagl_ce_graph_workspace_bytes(int B, int H, int W, int mode, int k, int rows_per_chunk) {
+    GraphPlan p;
+    if (graph_plan(B, H, W, mode, k, rows_per_chunk, p)) return 0;
+    return p.o_end;
+}
+
+// the workspace of both phases, checked against the plan before anything reaches the device
+static int graph_check_workspace(const char* who, const GraphPlan& p, const void* ws, size_t ws_bytes) {
+    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", who);
+    if (ws_bytes < p.o_end) {
+        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, p.o_end);
+        return DAGL_ERR_WORKSPACE;
+    }
+    return DAGL_OK;
+}
+
+int dagl_ce_graph_count(void* stream, int B, int H, int W, const float* b1, const float* thr, const float* bias, const float* fc1_w,
+                        const float* fc1_b, const float* fc2_w, const float* fc2_b, int mode, int k, int rows_per_chunk,
+                        int64_t* row_off_out, void* workspace, size_t ws_bytes, dagl_ce_info* info) {
+    GraphPlan p;
+    int rc = graph_plan(B, H, W, mode, k, rows_per_chunk, p);
+    if (rc) return rc;
+    reset_info(info, (int64_t)p.o_end, 8);
+    DAGL_REQUIRE(row_off_out && b1 && fc1_w && fc1_b && fc2_w && fc2_b, "dagl_ce_graph_count: null tensor pointer");
+    if (mode != DAGL_MODE_TOPK) DAGL_REQUIRE(thr && bias, "dagl_ce_graph_count: thr/bias required in adaptive modes");
+    if ((rc = graph_check_workspace("dagl_ce_graph_count", p, workspace, ws_bytes))) return rc;
+    return launch_graph_count((hipStream_t)stream, p, b1, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, row_off_out, workspace);
+}
+
+int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int rows_per_chunk, const int64_t* row_off,
+                       int32_t* key_out, float* weight_out, float* score_out, int64_t total_edges, int64_t capacity_edges,
+                       void* workspace, size_t ws_bytes) {
+    GraphPlan p;
+    int rc = graph_plan(B, H, W, mode, k, rows_per_chunk, p);
+    if (rc) return rc;
+    DAGL_REQUIRE(total_edges >= 0 && total_edges <= (int64_t)B * p.g.L * p.g.N, "dagl_ce_graph_fill: total_edges=%lld is not a count of this graph's edges",
+                 (long long)total_edges);
+    if (capacity_edges < total_edges) {
+        set_error("dagl_ce_graph_fill: capacity %lld edges < the graph's %lld edges", (long long)capacity_edges, (long long)total_edges);
+        return DAGL_ERR_WORKSPACE;
+    }
+    DAGL_REQUIRE(row_off && (total_edges == 0 || (key_out && weight_out)), "dagl_ce_graph_fill: null tensor pointer");
+    if ((rc = graph_check_workspace("dagl_ce_graph_fill", p, workspace, ws_bytes))) return rc;
+    if (total_edges == 0) return DAGL_OK;
+    return launch_graph_fill((hipStream_t)stream, p, row_off, key_out, weight_out, score_out, (long long)capacity_edges, workspace);
+}
+
 }  // extern "C"

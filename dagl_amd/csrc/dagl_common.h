@@ -790,4 +790,16 @@ int launch_dense_train_backward(hipStream_t s, int B, const Grid& g, const float
                                 int mode = DAGL_MODE_ADAPTIVE, int k = 0);
 int launch_colsum_rows(hipStream_t s, int B, int N, const float* rows, double* colsum);              // per-lane list length used for a requested k (4/8/16/32)
 
+// export of the patch graph as CSR (graph.hip): plan = geometry, chunk height and the carve of the workspace both phases share
+struct GraphPlan {
+    Grid g; int B, mode, k;                        // k clamped to the number of keys (0 in the adaptive mode)
+    int rows; long long ldn;                       // query rows per chunk of scores, row stride of the scores (floats)
+    size_t o_b1p, o_wp1, o_wp2, o_x, o_wq, o_colsum, o_mt, o_bias, o_deg, o_sel, o_rowm, o_rowz, o_scores, o_end;
+};
+int graph_plan(int B, int H, int W, int mode, int k, int rows_per_chunk, GraphPlan& p);
+int launch_graph_count(hipStream_t s, const GraphPlan& p, const float* b1, const float* thr, const float* bias, const float* fc1_w,
+                       const float* fc1_b, const float* fc2_w, const float* fc2_b, int64_t* row_off /* [B L + 1] */, void* ws);
+int launch_graph_fill(hipStream_t s, const GraphPlan& p, const int64_t* row_off, int32_t* key, float* weight, float* score /* or null */,
+                      long long capacity, void* ws);
+
 }  // namespace dagl

@@ -341,6 +341,56 @@ def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adapt
 
 
 @_on_device
+def ce_graph(b1, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adaptive", k: int = 0, scores: bool = False,
+             max_edges: "int | None" = None, rows_per_chunk: int = 0, workspace: "Workspace | None" = None,
+             degrees_only: bool = False):
+    """The patch graph of dagl.py:250-261 as CSR (``dagl_ce_graph_count`` / ``_fill``, include/dagl_ce.h): inputs as ``ce_forward``'s
+    without the value map -> dict(row_off [B*L+1] int64, key [E] int32, weight [E] fp32, score [E] fp32 | None).  The edge count is read
+    on the host between the two phases (one synchronisation; not under stream capture); ``max_edges``: raise instead of allocating
+    more; ``degrees_only``: the count phase alone -> row_off."""
+    lib = _lib.load()
+    _check_mode(mode)
+    for n, t in (("b1", b1), ("fc1_w", fc1_w), ("fc1_b", fc1_b), ("fc2_w", fc2_w), ("fc2_b", fc2_b)):
+        _need(t, n)
+    if b1.dim() != 4 or b1.shape[1] != 16:
+        raise DaglError("ce_graph: b1 must be [B,16,H,W]")
+    B, _, H, W = b1.shape
+    if tuple(fc1_w.shape) != (196, 784) or tuple(fc2_w.shape) != (196, 784):
+        raise DaglError("ce_graph: fc weights must be [196,784]")
+    Lh, Lw = query_grid(H, W)
+    BL = B * Lh * Lw
+    heads = mode != "topk"
+    if heads:
+        _need(thr, "thr"); _need(bias, "bias")
+        if thr.numel() != BL or bias.numel() != BL:
+            raise DaglError("ce_graph: thr/bias must hold B*L values")
+    if torch.cuda.is_current_stream_capturing():
+        raise DaglError("ce_graph: not available under stream capture (the edge count is read on the host between the two phases)")
+    need = lib.dagl_ce_graph_workspace_bytes(B, H, W, MODES[mode], int(k), int(rows_per_chunk))
+    if need == 0:
+        check(-1, "dagl_ce_graph_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, b1.device)
+    row_off = torch.empty(BL + 1, device=b1.device, dtype=torch.int64)
+    info = _lib.CeInfo()
+    check(lib.dagl_ce_graph_count(_stream(), B, H, W, b1.data_ptr(), _ptr(thr, heads), _ptr(bias, heads), fc1_w.data_ptr(),
+                                  fc1_b.data_ptr(), fc2_w.data_ptr(), fc2_b.data_ptr(), MODES[mode], int(k), int(rows_per_chunk),
+                                  row_off.data_ptr(), a, nbytes, C.byref(info)), "dagl_ce_graph_count")
+    if degrees_only:
+        return dict(row_off=row_off)
+    total = int(row_off[-1])                          # the one synchronisation
+    if max_edges is not None and total > int(max_edges):
+        raise DaglError(f"ce_graph: the graph holds {total} edges, max_edges={int(max_edges)}")
+    key = torch.empty(total, device=b1.device, dtype=torch.int32)
+    weight = torch.empty(total, device=b1.device, dtype=torch.float32)
+    score = torch.empty(total, device=b1.device, dtype=torch.float32) if scores else None
+    check(lib.dagl_ce_graph_fill(_stream(), B, H, W, MODES[mode], int(k), int(rows_per_chunk), row_off.data_ptr(),
+                                 _ptr(key, total > 0), _ptr(weight, total > 0), _ptr(score, total > 0), total, total, a, nbytes),
+          "dagl_ce_graph_fill")
+    del buf
+    return dict(row_off=row_off, key=key, weight=weight, score=score)
+
+
+@_on_device
 def ce_forward_generic(x, params: dict, ksize: int, stride_1: int, stride_2: int, inter_channels: int, mode: str = "adaptive",
                        k: int = 0, softmax_scale: float = 10.0, workspace: "Workspace | None" = None, want_degree: bool = False):
     """``CE.forward`` for ANY patch geometry (``dagl_ce_generic_forward``, csrc/generic.hip; dagl.py:175-176 makes ksize, stride_1,

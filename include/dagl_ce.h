@@ -133,7 +133,8 @@ typedef struct dagl_ce_info {
                                  FAST_CAP), 2 = fp32 scan, per-lane top-k lists, 3 = bf16 screen + refine,
                                  4 = dense neighbourhoods: streamed dense formulation (no lists),
                                  5 = dense formulation under autograd (dagl_ce_core_dense_forward),
-                                 6 = top-k modes with min(k, N) > DAGL_MAX_TOPK: row-wise dense form (no lists) */
+                                 6 = top-k modes with min(k, N) > DAGL_MAX_TOPK: row-wise dense form (no lists),
+                                 8 = graph export (dagl_ce_graph_count) */
     int32_t range_fallback;   /* 1 = an operand left the range of the split-fp16 kernels (|activation| >= 3750, see
                                  below: weights, dense-regime features, |b1| >= 1.5e7, non-finite input) and the call was re-run on the fp32 path */
     int32_t dense_rerun_blocks; /* path 4 / 5: blocks of 64 queries the streamed dense formulation ran a second time (rows whose
@@ -167,9 +168,9 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
 /* ABI version of THIS header: bumped whenever a struct or a signature declared here changes (round 3: dagl_ce_info is 40
  * bytes, dagl_ce_prologue takes `scratch`, dagl_ce_core_dense_forward takes `flags`, k <= 64; round 4: DAGL_FLAG_SAMPLED_TOPK,
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
- * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap).  A caller compares
+ * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 407
+#define DAGL_ABI_VERSION 408
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -247,6 +248,36 @@ int dagl_ce_forward_debug(void* stream, int B, int H, int W,
                           int mode, int k, float* out,
                           void* workspace, size_t ws_bytes, dagl_ce_info* info,
                           int32_t* deg_out, float* rowsum_out, float* agg_out);
+
+/* ---- (ABI 408) the learned patch graph as CSR: csrc/graph.hip --------------------------------------------------------------------
+ * For every image and query patch i the keys j with mask_b[i,j] != 0 and their weights A[i,j] = softmax(10 S m)[i,j] mask_b[i,j]
+ * -- the non-zeros of `yi`, dagl.py:256-261; not renormalised: the masked keys' e^0 stay in the denominator -- in all three modes
+ * (DAGL_MODE_TOPK: the min(k, N) best scores, ties to the lower key index; DAGL_MODE_ADAPTIVE_TOPK: the k best of the keys that pass
+ * the adaptive test).  No flags in `mode`.  CSR over the B L query rows:
+ *   row_off [B L + 1] int64   row offsets (a dense graph at 256^2 holds 2.7e8 edges)
+ *   key     [E] int32         key patch index 0 .. N-1, row-major over H x W, strictly ascending inside a row
+ *   weight  [E] fp32          A[i,j]
+ *   score   [E] fp32          S[i,j] (optional)
+ * Everything runs on the all-fp32 route (DAGL_FLAG_EXACT_SCAN's projections and thresholds, score rows on the fp32 matrix cores a
+ * chunk of `rows_per_chunk` query rows at a time; 0 = the library's choice, at most 2048): the reference semantics, which agree with
+ * the neighbours a screened forward used except at pairs within fp32 rounding of the selection boundary.  Inputs as dagl_ce_forward's
+ * (any input width) without the value map, which the graph does not depend on.  A diagnostic path: nothing here is tuned for speed.
+ * Two phases around ONE host read:
+ *   dagl_ce_graph_count   queues everything up to the exclusive scan of the degrees into row_off_out (device memory) and returns
+ *                         without synchronising; row_off_out[r + 1] - row_off_out[r] are the exact degrees, row_off_out[B L] the
+ *                         number of edges E -- the caller reads that word (its one synchronisation), allocates E entries and calls
+ *   dagl_ce_graph_fill    with the SAME workspace, untouched in between (it holds the features and each row's selection threshold
+ *                         and softmax statistics), the same B, H, W, mode, k, rows_per_chunk, the offsets and total_edges = the
+ *                         word it read.  capacity_edges < total_edges is DAGL_ERR_WORKSPACE, never a partial write (the kernels
+ *                         check the capacity against the device's own total once more and write nothing beyond it).
+ * The arrays are the same on every call (ordered compaction, fixed-order fp64 sums, no atomics).  info: required_bytes, path 8.      */
+size_t dagl_ce_graph_workspace_bytes(int B, int H, int W, int mode, int k, int rows_per_chunk);
+int dagl_ce_graph_count(void* stream, int B, int H, int W, const float* b1, const float* thr, const float* bias,
+                        const float* fc1_w, const float* fc1_b, const float* fc2_w, const float* fc2_b, int mode, int k,
+                        int rows_per_chunk, int64_t* row_off_out, void* workspace, size_t ws_bytes, dagl_ce_info* info);
+int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int rows_per_chunk, const int64_t* row_off,
+                       int32_t* key_out, float* weight_out, float* score_out /* may be NULL */, int64_t total_edges,
+                       int64_t capacity_edges, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;
