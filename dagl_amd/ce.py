@@ -591,10 +591,9 @@ class CE(nn.Module):
         from . import train_ops as T
         if any(p.dtype != torch.float32 for p in self.parameters()):
             raise DaglError("CE: the differentiable path needs fp32 parameters")
-        from ._lib import load
         B, Cin, H, W = b.shape
         ks, s1, s2, c = int(self.ksize), int(self.stride_1), int(self.stride_2), int(self.inter_channels)
-        pg = load().dagl_ce_generic_border(ks)
+        pg = ops.generic_border(ks)
         t1, l1 = same_pad_amounts(H, ks, s1)[0], same_pad_amounts(W, ks, s1)[0]
         t2, l2 = same_pad_amounts(H, ks, s2)[0], same_pad_amounts(W, ks, s2)[0]
         Lh, Lw, Nh, Nw = -(-H // s1), -(-W // s1), -(-H // s2), -(-W // s2)

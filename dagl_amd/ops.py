@@ -3,6 +3,9 @@
 Every function takes contiguous fp32 CUDA(HIP) tensors, enqueues on torch's current stream and returns
 freshly allocated outputs.  They mirror the stages of the reference method one to one
 (DN_Gray/model/dagl.py:216-274); see include/dagl_ce.h for the exact contracts.
+
+This module is the only caller of the library inside the package: ce.py, graph.py, trunk.py and train_ops.py keep modules,
+autograd and layouts and hand every operand to a wrapper here, which checks it (``_need``) before its pointer is taken.
 """
 from __future__ import annotations
 
@@ -26,37 +29,41 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _tensors_of(args, kwargs):
-    for a in list(args) + list(kwargs.values()):
+_SCALARS = frozenset((int, float, bool, str, type(None)))       # most arguments of a call: passed over before any isinstance
+
+
+def _common_device(values, dev, who: str):
+    """``dev`` or, when it is None, the device of the first GPU tensor among ``values`` (lists, tuples and dicts are looked
+    into); a GPU tensor on another device is refused."""
+    for a in values:
+        if type(a) in _SCALARS:
+            continue
         if isinstance(a, torch.Tensor):
-            yield a
+            if a.is_cuda:
+                if dev is None:
+                    dev = a.device
+                elif a.device != dev:
+                    raise DaglError(f"{who}: tensors on different devices ({dev} and {a.device})")
         elif isinstance(a, dict):
-            yield from (v for v in a.values() if isinstance(v, torch.Tensor))
+            dev = _common_device(a.values(), dev, who)
         elif isinstance(a, (list, tuple)):
-            for e in a:
-                if isinstance(e, torch.Tensor):
-                    yield e
-                elif isinstance(e, dict):
-                    yield from (v for v in e.values() if isinstance(v, torch.Tensor))
+            dev = _common_device(a, dev, who)
+    return dev
 
 
 def _on_device(fn):
     """Run ``fn`` with the device of its tensor arguments as the current device (a module living on cuda:1 must not
-    launch on cuda:0's stream) and refuse tensors spread over several devices."""
+    launch on cuda:0's stream) and refuse tensors spread over several devices.  Every library call passes through here, a
+    few hundred per training step: a plain loop over the arguments, and the device is switched only when it is not current."""
     import functools
 
     @functools.wraps(fn)
     def wrapped(*args, **kwargs):
-        dev = None
-        for t in _tensors_of(args, kwargs):
-            if not t.is_cuda:
-                continue
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise DaglError(f"{fn.__name__}: tensors on different devices ({dev} and {t.device})")
-        if dev is None:
-            return fn(*args, **kwargs)          # the per-argument checks below report the CPU tensor
+        dev = _common_device(args, None, fn.__name__)
+        if kwargs:
+            dev = _common_device(kwargs.values(), dev, fn.__name__)
+        if dev is None or dev.index == torch.cuda.current_device():
+            return fn(*args, **kwargs)          # (no GPU tensor: the per-argument checks below report the CPU tensor)
         with torch.cuda.device(dev):
             return fn(*args, **kwargs)
     return wrapped
@@ -273,6 +280,13 @@ def _aligned(buf: torch.Tensor):
     return a, buf.numel() - (a - base)
 
 
+def _scratch(nbytes: int, device):
+    """(buffer, 256-byte aligned pointer) of ``nbytes`` of throwaway device scratch; as with ``_region`` the caller keeps the
+    buffer referenced until its launch is queued."""
+    buf = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
+    return buf, _aligned(buf)[0]
+
+
 def _region(workspace: "Workspace | None", nbytes: int, device):
     """(buffer, 256-byte aligned pointer, bytes from there) of at least ``nbytes`` in ``workspace`` (a throwaway one when None).
     The caller keeps the buffer referenced until its launch is queued."""
@@ -425,9 +439,13 @@ def ce_forward_generic(x, params: dict, ksize: int, stride_1: int, stride_2: int
     return (out, deg) if want_degree else out
 
 
+def generic_border(ksize: int) -> int:
+    """Border of the zero-bordered NHWC maps of a generic patch geometry (``dagl_ce_generic_border``)."""
+    return _lib.load().dagl_ce_generic_border(int(ksize))
+
+
 def _generic_geom(H, W, ksize, stride_1, stride_2):
-    lib = _lib.load()
-    pg = lib.dagl_ce_generic_border(int(ksize))
+    pg = generic_border(ksize)
     L = (-(-H // int(stride_1))) * (-(-W // int(stride_1)))
     N = (-(-H // int(stride_2))) * (-(-W // int(stride_2)))
     return pg, L, N
@@ -502,8 +520,7 @@ def ce_prologue(x, g_w, g_b, theta_w, theta_b, thr_w=None, thr_b=None, bias_w=No
         # g / theta on the fp16 matrix cores with split operands (conv_pair16_kernel, the inference path's kernel, fp32 map out)
         lib = _lib.load()
         need = lib.dagl_ce_prologue16_scratch_bytes(B, H, W)
-        scratch = torch.empty(need + 256, device=x.device, dtype=torch.uint8)
-        base, _ = _aligned(scratch)
+        scratch, base = _scratch(need, x.device)
         check(lib.dagl_ce_prologue16(_stream(), B, H, W, x.data_ptr(), g_w.data_ptr(), g_b.data_ptr(), theta_w.data_ptr(), theta_b.data_ptr(),
                                      _ptr(thr_w), _ptr(thr_b), _ptr(bias_w), _ptr(bias_b), b1p.data_ptr(), b2p.data_ptr(), _ptr(thr),
                                      _ptr(bias), base, need),
@@ -852,6 +869,175 @@ def ce_core_wide_backward(d_out, wq_rows, x_rows, b2, thr, bias, mode: str, k: i
                                          _ptr(thr, heads), _ptr(bias, heads), d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(),
                                          d_b2.data_ptr(), _ptr(d_thr), _ptr(d_bias), a, nbytes), "dagl_ce_core_wide_backward")
     return d_wq, d_x, d_b2, d_thr, d_bias
+
+
+# ---- stages of the differentiable convolutions and projections (include/dagl_ce.h: train_ops.hip, gemm16s.hip, conv_grad.hip) ------
+# The library checks the patch geometry against the map's extents; what it cannot see -- how much memory stands behind a pointer --
+# is checked here.
+def _map_geom(t: torch.Tensor, name: str, channels: "int | None" = None):
+    _need(t, name)
+    if t.dim() != 4 or channels not in (None, t.shape[3]):
+        raise DaglError(f"{name}: a channels-last map [B,Hp,Wp,{channels or 'C'}] expected, got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+@_on_device
+def unfold_patches(pmap, k: int, stride: int, oy: int, ox: int, oh: int, ow: int) -> torch.Tensor:
+    """rows[(b,py,px), (kh,kw,c)] = pmap[b, oy + py*stride + kh, ox + px*stride + kw, c] -> [B*oh*ow, k*k*C]."""
+    B, Hp, Wp, c = _map_geom(pmap, "pmap")
+    rows = torch.empty(B * oh * ow, k * k * c, device=pmap.device, dtype=torch.float32)
+    check(_lib.load().dagl_unfold_patches(_stream(), B, Hp, Wp, c, k, stride, oy, ox, oh, ow, pmap.data_ptr(), rows.data_ptr()),
+          "dagl_unfold_patches")
+    return rows
+
+
+@_on_device
+def fold_patches(d_rows, map_shape, k: int, stride: int, oy: int, ox: int, oh: int, ow: int) -> torch.Tensor:
+    """The adjoint of ``unfold_patches``: d_rows [B*oh*ow, k*k*C] -> d_map of ``map_shape`` = (B,Hp,Wp,C), every pixel written."""
+    _need(d_rows, "d_rows")
+    B, Hp, Wp, c = map_shape
+    if d_rows.numel() != B * oh * ow * k * k * c:
+        raise DaglError(f"fold_patches: d_rows {tuple(d_rows.shape)} does not hold {B * oh * ow} patches of {k}x{k}x{c}")
+    d_map = torch.empty(B, Hp, Wp, c, device=d_rows.device, dtype=torch.float32)
+    check(_lib.load().dagl_fold_patches(_stream(), B, Hp, Wp, c, k, stride, oy, ox, oh, ow, d_rows.data_ptr(), d_map.data_ptr()),
+          "dagl_fold_patches")
+    return d_map
+
+
+@_on_device
+def copy4(src, sizes, s_strides, dst, d_strides) -> None:
+    """dst[i . d_strides] = src[i . s_strides] for every index i of the 4-D box ``sizes`` (strides in elements from each tensor's
+    first element; the library takes them as they come, so the far corner of the box is checked here)."""
+    for t, strides, name in ((src, s_strides, "src"), (dst, d_strides, "dst")):
+        _need(t, name)
+        if min(sizes) < 1 or min(strides) < 0 or sum((n - 1) * st for n, st in zip(sizes, strides)) >= t.numel():
+            raise DaglError(f"copy4: box {tuple(sizes)} with strides {tuple(strides)} leaves {name} ({t.numel()} elements)")
+    check(_lib.load().dagl_copy4(_stream(), *sizes, src.data_ptr(), *s_strides, dst.data_ptr(), *d_strides), "dagl_copy4")
+
+
+@_on_device
+def relu_backward(y, dz) -> torch.Tensor:
+    """dz * (y > 0)."""
+    _need(y, "y"); _need(dz, "dz")
+    if y.numel() != dz.numel():
+        raise DaglError("relu_backward: y and dz differ in size")
+    out = torch.empty_like(dz)
+    check(_lib.load().dagl_relu_backward(_stream(), dz.numel(), y.data_ptr(), dz.data_ptr(), out.data_ptr()), "dagl_relu_backward")
+    return out
+
+
+@_on_device
+def col_sum(x) -> torch.Tensor:
+    """Column sums of x [rows, cols] -> [cols] (fixed summation order)."""
+    _need(x, "x")
+    rows, cols = x.shape
+    lib = _lib.load()
+    out = torch.empty(cols, device=x.device, dtype=torch.float32)
+    scratch = torch.empty(lib.dagl_col_sum_scratch_bytes(rows, cols), device=x.device, dtype=torch.uint8)
+    check(lib.dagl_col_sum(_stream(), rows, cols, x.data_ptr(), out.data_ptr(), scratch.data_ptr()), "dagl_col_sum")
+    return out
+
+
+@_on_device
+def project_patches16(pmap, weight, bias, H: int, W: int, queries: bool) -> torch.Tensor:
+    """relu(Linear(patch)) of every 7x7x16 patch of the zero-bordered map [B,H+6,W+6,16] on the split-fp16 matrix cores (the forward
+    of the differentiable path; weight [196,784] in (kh,kw,c) order) -> [B*rows, 196], rows = L (``queries``) or H*W."""
+    B, Hp, Wp, _ = _map_geom(pmap, "pmap", 16)
+    _need(weight, "weight"); _need(bias, "bias")
+    if (Hp, Wp) != (H + 6, W + 6) or tuple(weight.shape) != (D, P) or bias.numel() != D:
+        raise DaglError("project_patches16: expected pmap [B,H+6,W+6,16], weight [196,784], bias [196]")
+    lib = _lib.load()
+    Lh, Lw = query_grid(H, W)
+    need = lib.dagl_project_patches16_scratch_bytes(B, H, W, int(queries))
+    scratch, base = _scratch(need, pmap.device)
+    y = torch.empty(B * (Lh * Lw if queries else H * W), D, device=pmap.device, dtype=torch.float32)
+    check(lib.dagl_project_patches16(_stream(), B, H, W, int(queries), pmap.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                     base, need), "dagl_project_patches16")
+    return y
+
+
+def fc_grad16_fold_ok(stride: int, ow: int) -> bool:
+    """Whether ``fc_grad16(fold=True)`` serves the grid (``dagl_fc_grad16_dmap_ok``)."""
+    return bool(_lib.load().dagl_fc_grad16_dmap_ok(stride, ow))
+
+
+@_on_device
+def fc_grad16(pmap, weight, y, dz, geometry, need_w: bool = True, need_b: bool = True, need_map: bool = True, fold: bool = False):
+    """The gradient products of a 7x7x16 -> 196 patch projection on the split-fp16 matrix cores (``dagl_fc_grad16``; ``fold``:
+    ``dagl_fc_grad16_dmap``) -> (d_w [196,784], d_b [196], d_rows [n,784] or, with ``fold``, d_map like ``pmap``), None where not
+    needed.  ``geometry`` = (stride, oy, ox, oh, ow); dz [n,196], n = B*oh*ow; ``y``: the layer's output (ReLU backward) or None."""
+    B, Hp, Wp, _ = _map_geom(pmap, "pmap", 16)
+    _need(weight, "weight"); _need(dz, "dz")
+    if y is not None:
+        _need(y, "y")
+    stride, oy, ox, oh, ow = geometry
+    n = B * oh * ow
+    if tuple(weight.shape) != (D, P) or dz.numel() != n * D or (y is not None and y.numel() != n * D) or (fold and not need_map):
+        raise DaglError(f"fc_grad16: expected weight [196,784], dz / y [{n},196]; fold=True computes the gradient of the map")
+    lib = _lib.load()
+    dev = pmap.device
+    d_w = torch.empty(D, P, device=dev, dtype=torch.float32) if need_w else None
+    d_b = torch.empty(D, device=dev, dtype=torch.float32) if need_b else None
+    name = "dagl_fc_grad16_dmap" if fold else "dagl_fc_grad16"
+    need = getattr(lib, name + "_scratch_bytes")(B, oh, ow)
+    scratch, base = _scratch(need, dev)
+    d_out = (torch.empty_like(pmap) if fold else torch.empty(n, P, device=dev, dtype=torch.float32)) if need_map else None
+    check(getattr(lib, name)(_stream(), B, Hp, Wp, stride, oy, ox, oh, ow, pmap.data_ptr(), weight.data_ptr(), _ptr(y), dz.data_ptr(),
+                             _ptr(d_w), _ptr(d_b), _ptr(d_out), base, need), name)
+    return d_w, d_b, d_out
+
+
+def conv_pair_backward_supported(B: int, H: int, W: int) -> bool:
+    return bool(_lib.load().dagl_conv_pair_backward_supported(B, H, W))
+
+
+@_on_device
+def conv_pair_backward(x, d_b1p, d_b2p, g_w, th_w, need_x: bool = True, need_params: bool = True):
+    """Backward of g (3x3) and theta (1x1), 64 -> 16, on the maps themselves (``dagl_conv_pair_backward``): x [B,64,H,W] and the
+    gradients of the two zero-bordered NHWC maps [B,H+6,W+6,16] -> (d_x, d_g_w, d_g_b, d_th_w, d_th_b), None where not needed."""
+    for n, t in (("x", x), ("d_b1p", d_b1p), ("d_b2p", d_b2p), ("g_w", g_w), ("th_w", th_w)):
+        _need(t, n)
+    B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if tuple(x.shape) != (B, 64, H, W) or tuple(d_b1p.shape) != (B, H + 6, W + 6, 16) or d_b2p.shape != d_b1p.shape \
+            or tuple(g_w.shape) != (16, 64, 3, 3) or th_w.numel() != 16 * 64:
+        raise DaglError("conv_pair_backward: expected x [B,64,H,W], d_b1p / d_b2p [B,H+6,W+6,16], g_w [16,64,3,3], th_w [16,64,1,1]")
+    lib = _lib.load()
+    dev = x.device
+    d_x = torch.empty_like(x) if need_x else None
+    d_gw = d_gb = d_tw = d_tb = scratch = None
+    if need_params:
+        d_gw, d_gb = torch.empty_like(g_w), torch.empty(16, device=dev, dtype=torch.float32)
+        d_tw, d_tb = torch.empty_like(th_w), torch.empty(16, device=dev, dtype=torch.float32)
+        scratch = torch.empty(max(16, lib.dagl_conv_pair_backward_scratch_bytes(B, H, W)), device=dev, dtype=torch.uint8)
+    check(lib.dagl_conv_pair_backward(_stream(), B, H, W, x.data_ptr(), d_b1p.data_ptr(), d_b2p.data_ptr(), g_w.data_ptr(), th_w.data_ptr(),
+                                      _ptr(d_x), _ptr(d_gw), _ptr(d_gb), _ptr(d_tw), _ptr(d_tb), _ptr(scratch)), "dagl_conv_pair_backward")
+    return d_x, d_gw, d_gb, d_tw, d_tb
+
+
+@_on_device
+def prelu_forward(x, weight) -> torch.Tensor:
+    """Single-parameter PReLU, x > 0 ? x : weight * x (a multiple of 4 elements, 16-byte aligned: the kernels move float4s)."""
+    _need(x, "x"); _need(weight, "weight")
+    if weight.numel() != 1:
+        raise DaglError("prelu_forward: one shared slope expected")
+    y = torch.empty_like(x)
+    check(_lib.load().dagl_prelu_forward(_stream(), x.numel(), x.data_ptr(), weight.data_ptr(), y.data_ptr()), "dagl_prelu_forward")
+    return y
+
+
+@_on_device
+def prelu_backward(x, dy, weight):
+    """(dx, d weight) of ``prelu_forward``; d weight by a fixed-order fp64 reduction."""
+    _need(x, "x"); _need(dy, "dy"); _need(weight, "weight")
+    if weight.numel() != 1 or dy.numel() != x.numel():
+        raise DaglError("prelu_backward: one shared slope and a dy of x's size expected")
+    lib = _lib.load()
+    dx = torch.empty_like(x)
+    da = torch.empty_like(weight)
+    scratch = torch.empty(max(8, lib.dagl_prelu_scratch_bytes(x.numel())), device=x.device, dtype=torch.uint8)
+    check(lib.dagl_prelu_backward(_stream(), x.numel(), x.data_ptr(), dy.data_ptr(), weight.data_ptr(), dx.data_ptr(), da.data_ptr(),
+                                  scratch.data_ptr()), "dagl_prelu_backward")
+    return dx, da
 
 
 # ---- the residual trunk's convolutions (include/dagl_ce.h: dagl_trunk_*) -------------------------------------------------------

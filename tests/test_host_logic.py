@@ -1,10 +1,15 @@
 """CPU tests of the host-side mirror: geometry helpers, module surface, state_dict compatibility."""
+import glob
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
 
 from dagl_amd.synth import make_ce_params, make_features, query_grid, same_pad_amounts
 from oracle.ce_oracle import same_pad
+from tests.helpers import REPO
 
 
 @pytest.mark.parametrize("size", list(range(1, 41)) + [63, 64, 72, 255, 256, 1024])
@@ -87,3 +92,55 @@ def test_network_width_other_than_64_fails_like_the_reference():
     assert ces.c1_1.in_channels == 32 and ces.c1_c.weight.shape == (32, 32, 1, 1)
     with pytest.raises(RuntimeError):
         ces.c1_c(torch.zeros(1, 64, 8, 8))          # what cat(four 16-channel heads) hands the mix
+
+
+def test_only_ops_calls_the_library():
+    """Layering of the host code: ``ops.py`` is the one module that turns tensors into C-ABI calls (``_lib.py`` binds the library,
+    ``build.py`` compiles it).  No other module of the package calls an entry point on a library handle or takes the stream itself,
+    and ``train_ops.py`` -- autograd bookkeeping -- neither imports the binding nor selects the device."""
+    for path in sorted(glob.glob(os.path.join(REPO, "dagl_amd", "*.py"))):
+        name = os.path.basename(path)
+        if name in ("ops.py", "_lib.py", "build.py"):
+            continue
+        text = open(path).read()
+        assert not re.search(r"\.dagl_[a-z0-9_]+\(", text), name
+        assert "ops._stream" not in text, name
+    text = open(os.path.join(REPO, "dagl_amd", "train_ops.py")).read()
+    for banned in (r"\bops\._", r"torch\.cuda\.device", r"\bcheck\(", r"import .*\b(check|_lib)\b", r"data_ptr\(\)\s*[-+*/]"):
+        assert not re.search(banned, text), banned
+
+
+def _z(*shape):
+    return torch.zeros(*shape)
+
+
+# the training wrappers of ops.py with minimal-shape arguments: (shape of the first tensor argument, call on it)
+_TRAIN_WRAPPERS = {
+    "unfold_patches": ((1, 7, 7, 16), lambda ops, t: ops.unfold_patches(t, 7, 1, 0, 0, 1, 1)),
+    "fold_patches": ((1, 784), lambda ops, t: ops.fold_patches(t, (1, 7, 7, 16), 7, 1, 0, 0, 1, 1)),
+    "copy4": ((4,), lambda ops, t: ops.copy4(t, (1, 1, 1, 4), (4, 4, 4, 1), _z(4), (4, 4, 4, 1))),
+    "relu_backward": ((4,), lambda ops, t: ops.relu_backward(t, _z(4))),
+    "col_sum": ((2, 4), lambda ops, t: ops.col_sum(t)),
+    "project_patches16": ((1, 7, 7, 16), lambda ops, t: ops.project_patches16(t, _z(196, 784), _z(196), 1, 1, False)),
+    "fc_grad16": ((1, 7, 7, 16), lambda ops, t: ops.fc_grad16(t, _z(196, 784), None, _z(1, 196), (1, 0, 0, 1, 1))),
+    "fc_grad16 fold": ((1, 7, 7, 16), lambda ops, t: ops.fc_grad16(t, _z(196, 784), None, _z(1, 196), (1, 0, 0, 1, 1), fold=True)),
+    "conv_pair_backward": ((1, 64, 4, 4), lambda ops, t: ops.conv_pair_backward(t, _z(1, 10, 10, 16), _z(1, 10, 10, 16),
+                                                                                _z(16, 64, 3, 3), _z(16, 64, 1, 1))),
+    "prelu_forward": ((4,), lambda ops, t: ops.prelu_forward(t, _z(1))),
+    "prelu_backward": ((4,), lambda ops, t: ops.prelu_backward(t, _z(4), _z(1))),
+}
+
+
+@pytest.mark.parametrize("wrapper", sorted(_TRAIN_WRAPPERS))
+def test_training_wrappers_check_their_operands(wrapper):
+    """Every tensor-taking wrapper ``train_ops.py`` calls refuses a CPU tensor and a float64 tensor in its first tensor argument
+    before anything reaches the library (``_need``), so no raw pointer of the wrong kind gets to a kernel.  The float64 tensor
+    lives on the GPU where there is one, so that the dtype check is the one that answers."""
+    from dagl_amd import ops
+    from dagl_amd._lib import DaglError
+    shape, call = _TRAIN_WRAPPERS[wrapper]
+    with pytest.raises(DaglError, match="GPU"):
+        call(ops, torch.zeros(*shape))
+    on_gpu = torch.cuda.is_available()
+    with pytest.raises(DaglError, match="dtype" if on_gpu else "GPU"):
+        call(ops, torch.zeros(*shape, dtype=torch.float64, device="cuda" if on_gpu else "cpu"))

@@ -7,7 +7,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dagl_amd import _lib, ops  # noqa: E402
+from dagl_amd import ops  # noqa: E402
 
 
 def timed(fn, reps=10):
@@ -24,7 +24,6 @@ def timed(fn, reps=10):
 
 def main():
     dev = torch.device("cuda:0")
-    lib = _lib.load()
     B, H, W = 8, 128, 128
     n = B * H * W
     g = torch.Generator(device=dev).manual_seed(0)
@@ -32,20 +31,12 @@ def main():
     pmap[:, 3:3 + H, 3:3 + W] = torch.randn(B, H, W, 16, device=dev, generator=g)
     w = (torch.rand(196, 784, device=dev, generator=g) - 0.5) * 0.07
     dz = torch.randn(n, 196, device=dev, generator=g) * 1e-4
-    need = lib.dagl_fc_grad16_scratch_bytes(B, H, W)
-    scratch = torch.empty(need + 256, device=dev, dtype=torch.uint8)
-    base = (scratch.data_ptr() + 255) // 256 * 256
-    d_w = torch.empty(196, 784, device=dev); d_rows = torch.empty(n, 784, device=dev)
 
-    def fast(both=True, dw=True):
-        _lib.check(lib.dagl_fc_grad16(ops._stream(), B, H + 6, W + 6, 1, 0, 0, H, W, pmap.data_ptr(), w.data_ptr(), None, dz.data_ptr(),
-                                      d_w.data_ptr() if (both or dw) else None, None, d_rows.data_ptr() if (both or not dw) else None,
-                                      base, need), "dagl_fc_grad16")
-
-    rows = torch.empty(n, 784, device=dev)
+    def fast(both=True, dw=True):       # (outputs and scratch come from torch's caching allocator: no device allocation in the loop)
+        ops.fc_grad16(pmap, w, None, dz, (1, 0, 0, H, W), need_w=both or dw, need_b=False, need_map=both or not dw)
 
     def slow():
-        _lib.check(lib.dagl_unfold_patches(ops._stream(), B, H + 6, W + 6, 16, 7, 1, 0, 0, H, W, pmap.data_ptr(), rows.data_ptr()), "unfold")
+        rows = ops.unfold_patches(pmap, 7, 1, 0, 0, H, W)
         ops.gemm_f32(dz, rows, a_k_contiguous=False, b_k_contiguous=False)
         ops.gemm_f32(dz, w, a_k_contiguous=True, b_k_contiguous=False, out=rows)
 
