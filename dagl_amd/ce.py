@@ -105,6 +105,29 @@ def _generic_route(geom, mode, k, scale, ws_f, ws_b):
     return forward, backward
 
 
+class _GraphApply(torch.autograd.Function):
+    """Value map -> block output on a given patch graph (``ops.graph_apply``): ``fold(A_G . V(b2)) / cnt``, dagl.py:263-272 with ``yi``
+    supplied.  Differentiable in the zero-bordered NHWC value map and in the edge weights (``ops.graph_apply_backward``); the graph's
+    structure is a constant."""
+
+    @staticmethod
+    def forward(ctx, b2p, weight, graph, ws_f, ws_b):
+        b2p, weight = b2p.contiguous(), weight.contiguous()
+        ctx.graph, ctx.ws_b = graph, ws_b
+        ctx.save_for_backward(b2p, weight)
+        return ops.graph_apply(b2p, graph.row_off, graph.key, weight, workspace=ws_f)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        b2p, weight = ctx.saved_tensors
+        g = ctx.graph
+        need_map, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_b2p, d_w = ops.graph_apply_backward(d_out.contiguous().float(), b2p, g.row_off, g.key, weight,
+                                              transposed=g.transpose() if need_map else None, need_b2p=need_map, need_weight=need_w,
+                                              workspace=ctx.ws_b)
+        return d_b2p, d_w, None, None, None
+
+
 _CONV_WEIGHTS = ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight")
 
 
@@ -181,6 +204,8 @@ class CE(nn.Module):
         self._ws = ops.Workspace()
         self._ws_bwd = ops.Workspace()
         self._ws_graph = ops.Workspace()  # graph() / degrees(): a buffer of their own, so that the forward's packed weights and policy words survive
+        self._ws_apply = ops.Workspace()      # apply_graph(): its aggregated and partial rows; its backward's rows
+        self._ws_apply_bwd = ops.Workspace()
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -559,13 +584,72 @@ class CE(nn.Module):
         c = self._scale_c()
         if score is not None and c != 1.0:
             score = score / c                        # (the query features carry the factor of _scale_c)
-        return PatchGraph(csr["row_off"], csr["key"], csr["weight"], score, b.shape[0], b.shape[2], b.shape[3], self.select_mode, k_eff)
+        g = PatchGraph(csr["row_off"], csr["key"], csr["weight"], score, b.shape[0], b.shape[2], b.shape[3], self.select_mode, k_eff)
+        g._valid = True                              # (the fill kernels write keys 0 .. N-1 only: ``apply_graph`` need not look again)
+        return g
 
     def degrees(self, b: torch.Tensor) -> torch.Tensor:
         """[B, L] int64: keys per query of ``graph(b)`` -- its count pass alone, nothing read on the host."""
         csr, _ = self._graph_csr(b, "degrees", degrees_only=True)
         off = csr["row_off"]
         return (off[1:] - off[:-1]).view(b.shape[0], -1)
+
+    def apply_graph(self, b: torch.Tensor, graph) -> torch.Tensor:
+        """This block's output for ``b`` on a GIVEN patch graph instead of the one it would select: ``fold(A_G . V(theta(b))) / cnt``,
+        dagl.py:263-272 with ``yi`` = ``graph`` (a ``PatchGraph``: what ``graph(b)`` returned, edited -- ``select`` / ``with_weight`` --,
+        taken from another input or module, or built by hand; keys in any order, repeats add up, any weights).  theta, projection,
+        screen, selection and softmax are skipped: the value map ``theta(b)`` is a 1x1 ``train_ops.patch_linear`` (fp32 matrix cores,
+        any input width), then ``ops.graph_apply`` (csrc/graph_apply.hip).  ``graph.B / H / W`` must be the input's and its arrays on the
+        input's device; ``graph.mode`` / ``k`` are not looked at.  Half / bf16 modules and inputs as in ``forward``.
+
+        ``graph.validate()`` runs first (one host read, once per graph).  After that the call has no host synchronisation and can be
+        captured; an unvalidated graph under capture is refused.  With autograd enabled and ``b``, theta's parameters or
+        ``graph.weight`` requiring grad, the call is differentiable in exactly those (fp32 parameters only); ``g``, the fc layers and
+        the heads are not part of it.  The module's state (packed weights, top-k policy, range verdicts, ``_train_dense``) is untouched."""
+        from . import train_ops as T
+        from .graph import PatchGraph
+        if b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.apply_graph: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
+        if not b.is_cuda:
+            raise DaglError("CE.apply_graph: input must be on the GPU; dagl_amd has no CPU path")
+        if self._generic:
+            raise DaglError(f"CE.apply_graph: applying a graph serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
+                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
+                            f"{self.inter_channels}), which is out of its scope")
+        if not isinstance(graph, PatchGraph):
+            raise DaglError(f"CE.apply_graph: a PatchGraph expected, got {type(graph).__name__}")
+        B, _, H, W = b.shape
+        if (graph.B, graph.H, graph.W) != (B, H, W):
+            raise DaglError(f"CE.apply_graph: the graph was built for B={graph.B} H={graph.H} W={graph.W}, the input is B={B} H={H} W={W}")
+        for name in ("row_off", "key", "weight"):
+            if getattr(graph, name).device != b.device:
+                raise DaglError(f"CE.apply_graph: graph.{name} lives on {getattr(graph, name).device}, the input on {b.device} "
+                                "(PatchGraph.to moves a graph)")
+        in_dtype = b.dtype
+        if in_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise DaglError(f"CE.apply_graph: unsupported dtype {in_dtype}")
+        if not graph._valid:
+            if torch.cuda.is_current_stream_capturing():
+                raise DaglError("CE.apply_graph: the graph has not been validated and the stream is being captured (validate() reads "
+                                "one word on the host): call graph.validate() before the capture")
+            graph.validate()
+        grad = torch.is_grad_enabled() and (b.requires_grad or graph.weight.requires_grad
+                                            or any(p.requires_grad for p in self.theta.parameters()))
+        if grad:
+            if any(p.dtype != torch.float32 for p in self.parameters()):
+                raise DaglError("CE: the differentiable path needs fp32 parameters (the reference's --precision half is a test-time "
+                                "switch, DN_Gray/model/__init__.py:98-99); run half-precision modules under torch.no_grad()")
+            th_w, th_b = self.theta.weight, self.theta.bias
+        else:
+            p = self._params_f32(scaled=False)
+            th_w, th_b = p["theta.weight"], p["theta.bias"]
+        with torch.enable_grad() if grad else torch.no_grad():
+            x = b.float() if in_dtype != torch.float32 else b
+            xp = T.to_padded_nhwc(_pad_channels4(x), H, W)
+            b2 = T.patch_linear(xp, T.conv_weight_rows(_pad_channels4(th_w)), th_b, 1, 1, T.PAD, T.PAD, H, W, allow_fast=False)   # dagl.py:209
+            b2p = T.to_padded_nhwc(b2, H, W, True)
+            out = _GraphApply.apply(b2p, graph.weight, graph, self._ws_apply, self._ws_apply_bwd)
+        return out if in_dtype == torch.float32 else out.to(in_dtype)
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """A module built with non-default ``ksize / stride_1 / stride_2 / inter_channels`` (dagl.py:175-176): the whole method through

@@ -1791,4 +1791,67 @@ int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int r
     return launch_graph_fill((hipStream_t)stream, p, row_off, key_out, weight_out, score_out, (long long)capacity_edges, workspace);
 }
 
+// (ABI 409) a block run on a given patch graph: csrc/graph_apply.hip
+int dagl_graph_apply_segment(void) { return graph_apply_segment(); }
+
+// shape and edge count of both calls; 0 = refused (dagl_last_error says why)
+static int graph_apply_shape_ok(const char* who, int B, int H, int W, int64_t total_edges) {
+    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    DAGL_REQUIRE((int64_t)B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    DAGL_REQUIRE(total_edges >= 0 && total_edges < (1ll << 31), "%s: total_edges=%lld outside [0, 2^31)", who, (long long)total_edges);
+    return DAGL_OK;
+}
+
+static size_t graph_apply_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
+    if (graph_apply_shape_ok(who, B, H, W, total_edges)) return 0;
+    return graph_apply_workspace_bytes(B, make_grid(H, W), total_edges, backward);
+}
+
+size_t dagl_graph_apply_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_apply_bytes("dagl_graph_apply_workspace_bytes", B, H, W, total_edges, false);
+}
+
+size_t dagl_graph_apply_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_apply_bytes("dagl_graph_apply_backward_workspace_bytes", B, H, W, total_edges, true);
+}
+
+static int graph_apply_check_workspace(const char* who, size_t need, const void* ws, size_t ws_bytes) {
+    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", who);
+    if (ws_bytes < need) {
+        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
+        return DAGL_ERR_WORKSPACE;
+    }
+    return DAGL_OK;
+}
+
+int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
+                     int64_t total_edges, float* out, void* workspace, size_t ws_bytes) {
+    int rc = graph_apply_shape_ok("dagl_graph_apply", B, H, W, total_edges);
+    if (rc) return rc;
+    DAGL_REQUIRE(b2p && row_off && out && (total_edges == 0 || (key && weight)), "dagl_graph_apply: null tensor pointer");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_apply: b2p must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = graph_apply_check_workspace("dagl_graph_apply", graph_apply_workspace_bytes(B, g, total_edges, false), workspace, ws_bytes)))
+        return rc;
+    return launch_graph_apply((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, out, workspace);
+}
+
+int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key,
+                              const float* weight, int64_t total_edges, const float* d_out, const int64_t* col_off,
+                              const int32_t* src_row, const int32_t* perm, float* d_b2p, float* d_weight, void* workspace,
+                              size_t ws_bytes) {
+    int rc = graph_apply_shape_ok("dagl_graph_apply_backward", B, H, W, total_edges);
+    if (rc) return rc;
+    DAGL_REQUIRE(b2p && row_off && d_out && (total_edges == 0 || (key && weight)), "dagl_graph_apply_backward: null tensor pointer");
+    DAGL_REQUIRE(d_b2p == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
+                 "dagl_graph_apply_backward: null transposed CSR (col_off, src_row, perm are required with d_b2p)");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0 && ((uintptr_t)d_b2p % 16) == 0, "dagl_graph_apply_backward: maps must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = graph_apply_check_workspace("dagl_graph_apply_backward", graph_apply_workspace_bytes(B, g, total_edges, true), workspace,
+                                          ws_bytes)))
+        return rc;
+    return launch_graph_apply_backward((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, d_out, col_off, src_row, perm,
+                                       d_b2p, d_weight, workspace);
+}
+
 }  // extern "C"

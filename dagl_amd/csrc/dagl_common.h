@@ -802,4 +802,13 @@ int launch_graph_count(hipStream_t s, const GraphPlan& p, const float* b1, const
 int launch_graph_fill(hipStream_t s, const GraphPlan& p, const int64_t* row_off, int32_t* key, float* weight, float* score /* or null */,
                       long long capacity, void* ws);
 
+// a block run on a given patch graph (graph_apply.hip; ABI 409): workspace = whole bytes of the forward / backward call
+int graph_apply_segment();
+size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward);
+int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
+                       const float* weight, int64_t E, float* out, void* workspace);
+int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
+                                const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
+                                const int32_t* perm, float* d_b2p /* or null */, float* d_weight /* or null */, void* workspace);
+
 }  // namespace dagl

@@ -20,7 +20,11 @@ class PatchGraph:
 
     ``row_off`` [B*L+1] int64 row offsets; ``key`` [E] int32 key patch index, ``0 .. N-1`` row-major over ``H x W``, strictly
     ascending inside a row; ``weight`` [E] fp32 ``A[i, j]``; ``score`` [E] fp32 ``S[i, j]`` or None.  ``mode`` / ``k`` say how the
-    keys were selected (``k`` = 0 in mode "adaptive")."""
+    keys were selected (``k`` = 0 in mode "adaptive").
+
+    ``CE.apply_graph`` runs a block on such a graph, and the graph may be edited first (``select``, ``with_weight``) or built by hand:
+    there keys may come in any order and repeat (repeats add up) and weights are any floats; ``validate`` checks the key range,
+    ``transpose`` gives the column-major view the backward walks, ``to`` moves the arrays."""
 
     def __init__(self, row_off: torch.Tensor, key: torch.Tensor, weight: torch.Tensor, score: Optional[torch.Tensor],
                  B: int, H: int, W: int, mode: str = "adaptive", k: int = 0):
@@ -53,6 +57,8 @@ class PatchGraph:
             raise DaglError(f"PatchGraph: row_off ends at {last}, the arrays hold {E} edges")
         self.row_off, self.key, self.weight, self.score = row_off, key, weight, score
         self.B, self.L, self.N, self.H, self.W, self.mode, self.k = B, L, N, H, W, mode, k
+        self._valid = False              # ``validate`` has found every key in [0, N)
+        self._transposed = None          # ``transpose``'s (col_off, src_row, perm)
 
     @property
     def n_edges(self) -> int:
@@ -88,6 +94,83 @@ class PatchGraph:
     def cpu(self) -> "PatchGraph":
         return PatchGraph(self.row_off.cpu(), self.key.cpu(), self.weight.cpu(), self.score.cpu() if self.score is not None else None,
                           self.B, self.H, self.W, self.mode, self.k)
+
+    # ---- editing (``CE.apply_graph`` takes the result): keys may then come in any order and repeat, weights are any floats ----------
+    def _like(self, row_off, key, weight, score) -> "PatchGraph":
+        """A graph of this one's shape over arrays that are already known to be consistent (no host read)."""
+        g = object.__new__(PatchGraph)
+        g.row_off, g.key, g.weight, g.score = row_off, key, weight, score
+        g.B, g.L, g.N, g.H, g.W, g.mode, g.k = self.B, self.L, self.N, self.H, self.W, self.mode, self.k
+        g._valid, g._transposed = self._valid, None
+        return g
+
+    def rows(self) -> torch.Tensor:
+        """[E] int64: the query row ``b * L + i`` of every edge."""
+        n = self.B * self.L
+        return torch.repeat_interleave(torch.arange(n, device=self.row_off.device), self.row_off[1:] - self.row_off[:-1],
+                                       output_size=self.n_edges)
+
+    def to(self, device) -> "PatchGraph":
+        """The same graph with its arrays on ``device`` (what ``validate`` and ``transpose`` have found goes along)."""
+        device = torch.device(device)
+        g = self._like(self.row_off.to(device), self.key.to(device), self.weight.to(device),
+                       self.score.to(device) if self.score is not None else None)
+        if self._transposed is not None:
+            g._transposed = tuple(t.to(device) for t in self._transposed)
+        return g
+
+    def with_weight(self, weight: torch.Tensor) -> "PatchGraph":
+        """The same structure (the offsets and keys are shared, not copied) with ``weight`` [E] fp32 in the place of the weights.  A
+        ``weight`` that requires grad is kept as it is: ``CE.apply_graph`` under autograd returns its gradient."""
+        if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or weight.numel() != self.n_edges:
+            raise DaglError(f"PatchGraph.with_weight: a 1-d tensor of {self.n_edges} weights expected")
+        if weight.dtype != torch.float32:
+            raise DaglError(f"PatchGraph.with_weight: weight has dtype {weight.dtype}, expected {torch.float32}")
+        if weight.device != self.row_off.device:
+            raise DaglError(f"PatchGraph.with_weight: weight lives on {weight.device}, the graph on {self.row_off.device}")
+        g = self._like(self.row_off, self.key, weight, self.score)
+        g._transposed = self._transposed
+        return g
+
+    def select(self, mask: torch.Tensor) -> "PatchGraph":
+        """The edges with ``mask`` [E] bool set, in their order, as a new CSR with recomputed offsets."""
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() != 1 or mask.numel() != self.n_edges:
+            raise DaglError(f"PatchGraph.select: a 1-d bool mask over the {self.n_edges} edges expected")
+        if mask.device != self.row_off.device:
+            raise DaglError(f"PatchGraph.select: mask lives on {mask.device}, the graph on {self.row_off.device}")
+        deg = torch.zeros(self.B * self.L, dtype=torch.int64, device=mask.device).index_add_(0, self.rows(), mask.long())
+        row_off = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
+        return self._like(row_off, self.key[mask], self.weight[mask], self.score[mask] if self.score is not None else None)
+
+    def validate(self) -> "PatchGraph":
+        """Every key must lie in [0, N): raises ``DaglError`` naming the first edge whose key does not.  One reduction and one host read;
+        the verdict is kept (``with_weight`` / ``select`` / ``to`` hand it on: they add no keys)."""
+        if self._valid:
+            return self
+        if self.n_edges:
+            bad = (self.key < 0) | (self.key >= self.N)
+            first = int(torch.where(bad.any(), bad.int().argmax(), bad.new_full((), -1, dtype=torch.int64)))      # the one host read
+            if first >= 0:
+                row = int(torch.searchsorted(self.row_off, torch.tensor(first, device=self.row_off.device), right=True)) - 1
+                raise DaglError(f"PatchGraph.validate: edge {first} (query {row % self.L} of image {row // self.L}) has key "
+                                f"{int(self.key[first])}, outside [0, {self.N})")
+        self._valid = True
+        return self
+
+    def transpose(self):
+        """The transposed CSR ``CE.apply_graph``'s backward walks: (col_off [B*N+1] int64, src_row [E] int32, perm [E] int32) -- the edges
+        in a stable order of their column ``b * N + key``: transposed edge ``t`` is edge ``perm[t]`` of this graph and belongs to query
+        row ``src_row[t]``; column ``c`` owns ``col_off[c] .. col_off[c+1]``.  Needs valid keys (``validate``); kept on the object."""
+        if self._transposed is None:
+            self.validate()
+            if self.n_edges >= 1 << 31:
+                raise DaglError(f"PatchGraph.transpose: {self.n_edges} edges do not fit 32-bit edge ids")
+            rows = self.rows()
+            col = torch.div(rows, self.L, rounding_mode="floor") * self.N + self.key.long()
+            col, perm = torch.sort(col, stable=True)
+            col_off = torch.searchsorted(col, torch.arange(self.B * self.N + 1, device=col.device))
+            self._transposed = (col_off.contiguous(), rows[perm].int().contiguous(), perm.int().contiguous())
+        return self._transposed
 
     def __repr__(self):
         return (f"PatchGraph(B={self.B}, L={self.L}, N={self.N}, edges={self.n_edges}, mode={self.mode!r}, k={self.k}, "

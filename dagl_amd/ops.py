@@ -404,6 +404,76 @@ def ce_graph(b1, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adaptive", 
     return dict(row_off=row_off, key=key, weight=weight, score=score)
 
 
+def graph_apply_segment() -> int:
+    """Edges a block of the graph-apply kernels takes (``dagl_graph_apply_segment``)."""
+    return int(_lib.load().dagl_graph_apply_segment())
+
+
+def _graph_apply_operands(who: str, b2p, row_off, key, weight):
+    """Shapes of a graph-apply call's operands -> (B, H, W, E).  Array CONTENTS stay unread: the kernels bound every index themselves."""
+    _need(b2p, "b2p"); _need(row_off, "row_off", torch.int64); _need(key, "key", torch.int32); _need(weight, "weight")
+    if b2p.dim() != 4 or b2p.shape[3] != 16 or b2p.shape[1] < 7 or b2p.shape[2] < 7:
+        raise DaglError(f"{who}: b2p must be the zero-bordered NHWC value map [B,H+6,W+6,16], got {tuple(b2p.shape)}")
+    B, H, W = b2p.shape[0], b2p.shape[1] - 6, b2p.shape[2] - 6
+    Lh, Lw = query_grid(H, W)
+    E = key.numel()
+    if row_off.dim() != 1 or row_off.numel() != B * Lh * Lw + 1:
+        raise DaglError(f"{who}: row_off holds {row_off.numel()} offsets, expected B*L+1 = {B * Lh * Lw + 1}")
+    if key.dim() != 1 or weight.dim() != 1 or weight.numel() != E:
+        raise DaglError(f"{who}: key and weight must be 1-d with one entry per edge")
+    return B, H, W, E
+
+
+@_on_device
+def graph_apply(b2p, row_off, key, weight, workspace: "Workspace | None" = None) -> torch.Tensor:
+    """A block's output from a given patch graph (``dagl_graph_apply``, csrc/graph_apply.hip): ``fold(A_G . V(b2)) / cnt`` with b2p the
+    zero-bordered NHWC value map [B,H+6,W+6,16] and (row_off [B*L+1] int64, key [E] int32, weight [E] fp32) the CSR of ``A_G`` ->
+    [B,16,H,W].  Nothing is read on the host; keys outside [0, N) contribute nothing."""
+    lib = _lib.load()
+    B, H, W, E = _graph_apply_operands("graph_apply", b2p, row_off, key, weight)
+    need = lib.dagl_graph_apply_workspace_bytes(B, H, W, E)
+    if need == 0:
+        check(-1, "dagl_graph_apply_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, b2p.device)
+    out = torch.empty(B, 16, H, W, device=b2p.device, dtype=torch.float32)
+    check(lib.dagl_graph_apply(_stream(), B, H, W, b2p.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), _ptr(weight, E > 0), E,
+                               out.data_ptr(), a, nbytes), "dagl_graph_apply")
+    del buf
+    return out
+
+
+@_on_device
+def graph_apply_backward(d_out, b2p, row_off, key, weight, transposed=None, need_b2p: bool = True, need_weight: bool = True,
+                         workspace: "Workspace | None" = None):
+    """Gradients of ``graph_apply`` (``dagl_graph_apply_backward``) -> (d_b2p [B,H+6,W+6,16] | None, d_weight [E] | None).
+    ``transposed`` = (col_off [B*N+1] int64, src_row [E] int32, perm [E] int32), the graph's transposed CSR
+    (``PatchGraph.transpose``): required with ``need_b2p``."""
+    lib = _lib.load()
+    B, H, W, E = _graph_apply_operands("graph_apply_backward", b2p, row_off, key, weight)
+    _need(d_out, "d_out")
+    if tuple(d_out.shape) != (B, 16, H, W):
+        raise DaglError(f"graph_apply_backward: d_out is {tuple(d_out.shape)}, expected {(B, 16, H, W)}")
+    col_off = src_row = perm = None
+    if need_b2p:
+        if transposed is None:
+            raise DaglError("graph_apply_backward: d_b2p needs the transposed CSR (col_off, src_row, perm)")
+        col_off, src_row, perm = transposed
+        _need(col_off, "col_off", torch.int64); _need(src_row, "src_row", torch.int32); _need(perm, "perm", torch.int32)
+        if col_off.numel() != B * H * W + 1 or src_row.numel() != E or perm.numel() != E:
+            raise DaglError(f"graph_apply_backward: the transposed CSR must hold B*N+1 = {B * H * W + 1} offsets and {E} edges")
+    need = lib.dagl_graph_apply_backward_workspace_bytes(B, H, W, E)
+    if need == 0:
+        check(-1, "dagl_graph_apply_backward_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, b2p.device)
+    d_b2p = torch.empty_like(b2p) if need_b2p else None
+    d_weight = torch.empty_like(weight) if need_weight else None
+    check(lib.dagl_graph_apply_backward(_stream(), B, H, W, b2p.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), _ptr(weight, E > 0), E,
+                                        d_out.data_ptr(), _ptr(col_off), _ptr(src_row, E > 0), _ptr(perm, E > 0), _ptr(d_b2p),
+                                        _ptr(d_weight, E > 0), a, nbytes), "dagl_graph_apply_backward")
+    del buf
+    return d_b2p, d_weight
+
+
 @_on_device
 def ce_forward_generic(x, params: dict, ksize: int, stride_1: int, stride_2: int, inter_channels: int, mode: str = "adaptive",
                        k: int = 0, softmax_scale: float = 10.0, workspace: "Workspace | None" = None, want_degree: bool = False):

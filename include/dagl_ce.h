@@ -168,9 +168,9 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
 /* ABI version of THIS header: bumped whenever a struct or a signature declared here changes (round 3: dagl_ce_info is 40
  * bytes, dagl_ce_prologue takes `scratch`, dagl_ce_core_dense_forward takes `flags`, k <= 64; round 4: DAGL_FLAG_SAMPLED_TOPK,
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
- * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*).  A caller compares
+ * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 408
+#define DAGL_ABI_VERSION 409
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -278,6 +278,40 @@ int dagl_ce_graph_count(void* stream, int B, int H, int W, const float* b1, cons
 int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int rows_per_chunk, const int64_t* row_off,
                        int32_t* key_out, float* weight_out, float* score_out /* may be NULL */, int64_t total_edges,
                        int64_t capacity_edges, void* workspace, size_t ws_bytes);
+
+/* ---- (ABI 409) a block run on a GIVEN patch graph: csrc/graph_apply.hip ------------------------------------------------------------
+ * The consumer of the export above:  out[b] = fold(A_G[b] . V(b2[b])) / cnt  -- dagl.py:263-272 with `yi` supplied by the caller: A_G[b]
+ * the [L, N] matrix the CSR rows b L .. b L + L - 1 describe, V the 7x7 stride-1 patches of the value map theta(x) (dagl.py:209, 224),
+ * fold and overlap count those of dagl_fold_normalize.  The graph need not come from dagl_ce_graph_fill: keys may be in any order inside
+ * a row and may repeat (repeats add up), weights are arbitrary floats, a row may be empty or longer than N.  A key outside [0, N)
+ * contributes nothing; it is tested before an address is formed, so no array content makes a kernel read outside the map.
+ *   b2p     [B,H+6,W+6,16]  zero-bordered NHWC value map, as dagl_ce_prologue writes it (value rows are read from it on the fly)
+ *   row_off [B L + 1] int64, key [E] int32, weight [E] fp32   (key / weight may be NULL when total_edges = 0);  total_edges < 2^31
+ *   out     [B,16,H,W]
+ * The edge array is cut into segments of dagl_graph_apply_segment() edges, a block each, whatever rows they belong to: the longest
+ * row does not set the launch time and short rows share a block; the partial rows of a row that crosses segments are added in segment
+ * order (no float atomics): two calls on the same arrays return the same bits.  Grids come from total_edges and B L: nothing is read
+ * on the host, the call can be captured.  Workspace: dagl_graph_apply_workspace_bytes = [B L, 784] aggregated rows + one 784-float
+ * partial row per segment (24.5 bytes per edge).
+ *
+ * dagl_graph_apply_backward: gradients of that call.  dAgg = unfold(d_out / cnt);
+ *   d_weight [E]  (may be NULL)  d_weight[e] = <dAgg[row(e)], V[key(e)]>, the patch read from the map; 0 for a key outside [0, N)
+ *   d_b2p [B,H+6,W+6,16] (may be NULL)  the stride-1 adjoint of unfold of the rows d V = A_G^T dAgg, every element written (the
+ *           border too).  d V runs through the same segmented product over the TRANSPOSED CSR, which the caller supplies:
+ *           col_off [B N + 1] int64 offsets over the columns b N + key, src_row [E] int32 the query row b L + i of each transposed edge,
+ *           perm [E] int32 its position in key / weight (a stable sort of b N + key: dagl_amd.PatchGraph.transpose); entries outside
+ *           their range contribute nothing.
+ * Workspace: dagl_graph_apply_backward_workspace_bytes = dAgg [B L, 784] + the d V rows [B N, 784] (205 MB at 256^2: this route
+ * materialises them, which is acceptable for a diagnostic / fine-tuning path) + the partial rows.  Fixed summation order throughout. */
+int    dagl_graph_apply_segment(void);
+size_t dagl_graph_apply_workspace_bytes(int B, int H, int W, int64_t total_edges);
+size_t dagl_graph_apply_backward_workspace_bytes(int B, int H, int W, int64_t total_edges);
+int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key,
+                     const float* weight, int64_t total_edges, float* out, void* workspace, size_t ws_bytes);
+int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key,
+                              const float* weight, int64_t total_edges, const float* d_out, const int64_t* col_off,
+                              const int32_t* src_row, const int32_t* perm, float* d_b2p /* may be NULL */,
+                              float* d_weight /* may be NULL */, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

@@ -1,6 +1,7 @@
 """What ``CE.graph`` costs next to the forward of the same call (a diagnostic path: the number is for users, not a target).
 
     python tools/time_patch_graph.py [H W]          # default 256 256: top-k 8 and the dense adaptive regime
+    python tools/time_patch_graph.py --apply [H W]  # what ``CE.apply_graph`` costs: forward / graph / apply / apply + backward
 """
 import os
 import sys
@@ -21,7 +22,87 @@ def _timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
+def _events(fn, warmup=3, repeats=5, inner=10):
+    """Median and spread (ms per call) of ``repeats`` event-timed windows of ``inner`` calls, after ``warmup`` calls."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(repeats):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(inner):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        times.append(t0.elapsed_time(t1) / inner)
+    times.sort()
+    return times[len(times) // 2], times[0], times[-1]
+
+
+def _long_tailed(g, n_rows=16):
+    """``g`` with every key once (weight 1 / N) in the place of ``n_rows`` of its rows, spread over the row range."""
+    from dagl_amd.graph import PatchGraph
+    dev = g.key.device
+    deg = g.degrees().reshape(-1).clone()
+    picked = torch.linspace(0, deg.numel() - 1, n_rows, device=dev).long()
+    keep = torch.ones(g.n_edges, dtype=torch.bool, device=dev)
+    keep[torch.isin(g.rows(), picked)] = False
+    rows = torch.cat([g.rows()[keep], picked.repeat_interleave(g.N)])
+    key = torch.cat([g.key[keep], torch.arange(g.N, dtype=torch.int32, device=dev).repeat(n_rows)])
+    weight = torch.cat([g.weight[keep], torch.full((n_rows * g.N,), 1.0 / g.N, device=dev)])
+    order = torch.sort(rows, stable=True).indices
+    deg[picked] = g.N
+    row_off = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
+    return PatchGraph(row_off, key[order].contiguous(), weight[order].contiguous(), None, g.B, g.H, g.W, g.mode, g.k)
+
+
+def apply_leg(H, W):
+    """forward / graph / apply_graph(graph) / apply_graph forward + backward of one module and input, and the gather's algorithmic
+    bytes per second: E * (3136 + 8) -- an edge's 784 value floats, its key and its weight -- over the time of ``ops.graph_apply``
+    alone (the value map given: no theta convolution in the window)."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    for name, mode, k, variant, tail in (("top-k 8", "topk", 8, "default", False), ("sparse adaptive (gain 1.65)", "adaptive", 0, "sparse", False),
+                                         ("top-k 8 + 16 rows of degree N", "topk", 8, "default", True)):
+        prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=1.65).items()}
+        ce = CE(in_channels=64)
+        ce.load_state_dict(prm, strict=True)
+        ce.select_mode, ce.select_k = mode, max(k, 1)
+        ce = ce.to(dev).eval()
+        with torch.no_grad():
+            g = ce.graph(x)
+            if tail:
+                g = _long_tailed(g)
+            g.validate()
+            fwd = _events(lambda: ce(x))
+            exp = _events(lambda: ce.graph(x), warmup=1, repeats=3, inner=2)
+            app = _events(lambda: ce.apply_graph(x, g))
+            b2p = ops.ce_prologue(x, *(ce._params_f32()[n] for n in ("g.weight", "g.bias", "theta.weight", "theta.bias")))[1]
+            ws = ops.Workspace()
+            ker = _events(lambda: ops.graph_apply(b2p, g.row_off, g.key, g.weight, workspace=ws))
+        xg = x.clone().requires_grad_(True)
+        gw = g.with_weight(g.weight.clone().requires_grad_(True))
+        g.transpose()
+
+        def both():
+            ce.apply_graph(xg, gw).sum().backward()
+            xg.grad = gw.weight.grad = None
+            ce.zero_grad(set_to_none=True)
+        fb = _events(both, repeats=3, inner=5)
+        gbs = g.n_edges * (3136 + 8) / (ker[0] * 1e-3) / 1e12
+        fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+        print(f"[1,64,{H},{W}] {name}: {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {int(g.degrees().max())}\n"
+              f"    forward {fmt(fwd)}; graph {fmt(exp)}; apply_graph(graph) {fmt(app)}; apply_graph forward + backward {fmt(fb)}\n"
+              f"    ops.graph_apply alone {fmt(ker)}: {gbs:.2f} TB/s of E * (3136 + 8) algorithmic bytes", flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--apply":
+        return apply_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     from dagl_amd.ce import CE
     from dagl_amd.synth import make_ce_params, make_features
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (256, 256)
