@@ -137,11 +137,6 @@ struct Plan {
 };
 
 static bool g_N_small(int H, int W);
-static size_t carve(size_t& off, size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-}
 
 constexpr int SCREEN_MIN_KEYS = 2048;     // below this the fp32 scan is launch-bound anyway
 constexpr int SCREEN_CAPSEG = 16;
@@ -250,81 +245,78 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
     }
 
     const size_t BL = (size_t)B * g.L;
-    size_t off = 0;
+    Carver cv;
     const size_t map_b = (size_t)B * g.Hp * g.Wp * CH * sizeof(float);
-    p.o_b1p = carve(off, map_b);
-    p.o_b2p = carve(off, map_b);
-    p.o_wp1 = carve(off, (size_t)DPAD * P * sizeof(float));
-    p.o_wp2 = carve(off, (size_t)DPAD * P * sizeof(float));
-    p.o_x = carve(off, (size_t)B * feat_rows(g.N) * DS * sizeof(float));
-    p.o_wq = carve(off, (size_t)B * feat_rows(g.L) * DS * sizeof(float));
-    p.o_colsum = carve(off, (size_t)B * DS * sizeof(double));
-    p.o_mt = carve(off, BL * sizeof(float));
-    p.o_cnt = carve(off, BL * sizeof(int32_t));
-    p.o_segcnt = carve(off, BL * p.splits * 2 * sizeof(int32_t));
-    p.o_segoff = carve(off, BL * p.splits * 2 * sizeof(int32_t));
-    p.o_rowoff = carve(off, (BL + 1) * sizeof(int64_t));
-    p.o_deg = carve(off, BL * sizeof(int32_t));
-    p.o_stats = carve(off, STAT_WORDS * sizeof(int64_t));     // (StatWord, dagl_common.h)
+    p.o_b1p = cv.reserve(map_b);
+    p.o_b2p = cv.reserve(map_b);
+    p.o_wp1 = cv.reserve((size_t)DPAD * P * sizeof(float));
+    p.o_wp2 = cv.reserve((size_t)DPAD * P * sizeof(float));
+    p.o_x = cv.reserve((size_t)B * feat_rows(g.N) * DS * sizeof(float));
+    p.o_wq = cv.reserve((size_t)B * feat_rows(g.L) * DS * sizeof(float));
+    p.o_colsum = cv.reserve((size_t)B * DS * sizeof(double));
+    p.o_mt = cv.reserve(BL * sizeof(float));
+    p.o_cnt = cv.reserve(BL * sizeof(int32_t));
+    p.o_segcnt = cv.reserve(BL * p.splits * 2 * sizeof(int32_t));
+    p.o_segoff = cv.reserve(BL * p.splits * 2 * sizeof(int32_t));
+    p.o_rowoff = cv.reserve((BL + 1) * sizeof(int64_t));
+    p.o_deg = cv.reserve(BL * sizeof(int32_t));
+    p.o_stats = cv.reserve(STAT_WORDS * sizeof(int64_t));     // (StatWord, dagl_common.h)
     if (mode == DAGL_MODE_ADAPTIVE) {
-        p.o_lidx = carve(off, BL * DAGL_FAST_CAP * sizeof(int32_t));
-        p.o_lval = carve(off, BL * DAGL_FAST_CAP * sizeof(float));
+        p.o_lidx = cv.reserve(BL * DAGL_FAST_CAP * sizeof(int32_t));
+        p.o_lval = cv.reserve(BL * DAGL_FAST_CAP * sizeof(float));
     } else {
-        p.o_cidx = carve(off, BL * p.splits * 2 * p.kslots * sizeof(int32_t));
-        p.o_cval = carve(off, BL * p.splits * 2 * p.kslots * sizeof(float));
+        p.o_cidx = cv.reserve(BL * p.splits * 2 * p.kslots * sizeof(int32_t));
+        p.o_cval = cv.reserve(BL * p.splits * 2 * p.kslots * sizeof(float));
     }
-    p.o_nbidx = carve(off, BL * p.width * sizeof(int32_t));
-    p.o_nbwgt = carve(off, BL * p.width * sizeof(float));
-    p.o_nbcnt = carve(off, BL * sizeof(int32_t));
-    p.o_agg = carve(off, BL * P * sizeof(float));
-    p.o_thr = carve(off, BL * sizeof(float));
-    p.o_bias = carve(off, BL * sizeof(float));
-    p.o_thrpart = carve(off, 8 * BL * sizeof(float));                       // prologue: partial thr/bias sums of 4 channel groups
+    p.o_nbidx = cv.reserve(BL * p.width * sizeof(int32_t));
+    p.o_nbwgt = cv.reserve(BL * p.width * sizeof(float));
+    p.o_nbcnt = cv.reserve(BL * sizeof(int32_t));
+    p.o_agg = cv.reserve(BL * P * sizeof(float));
+    p.o_thr = cv.reserve(BL * sizeof(float));
+    p.o_bias = cv.reserve(BL * sizeof(float));
+    p.o_thrpart = cv.reserve(8 * BL * sizeof(float));                       // prologue: partial thr/bias sums of 4 channel groups
     if (!exact) {
-        p.o_maphi = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
-        p.o_maplo = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
+        p.o_maphi = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
+        p.o_maplo = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
         // the coarse tier of the key / query map and the conv blocks' |b1| slots (B1Tiers, dagl_common.h): written by conv_pair16_kernel,
         // read by project16_kernel, so that activations beyond the fine tier's |b1| < 3750 are served by the same launches
-        p.o_maphi2 = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
-        p.o_maplo2 = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
-        p.o_b1amax = carve(off, (size_t)conv16_blocks_per_head(g, 1, B) * sizeof(float));
-        p.o_wp1h = carve(off, 4 * P16_PACKED_HALFS * sizeof(uint16_t));          // up to 4 heads (stage entry point)
-        p.o_wp2h = carve(off, 4 * P16_PACKED_HALFS * sizeof(uint16_t));
-        p.o_convw = carve(off, 4 * CONV_W16_BYTES);                                       // packed g / theta weights per head
-        p.o_colpart = carve(off, (size_t)B * project16_key_blocks(g) * 224 * sizeof(float));
+        p.o_maphi2 = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
+        p.o_maplo2 = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t));
+        p.o_b1amax = cv.reserve((size_t)conv16_blocks_per_head(g, 1, B) * sizeof(float));
+        p.o_wp1h = cv.reserve(4 * P16_PACKED_HALFS * sizeof(uint16_t));          // up to 4 heads (stage entry point)
+        p.o_wp2h = cv.reserve(4 * P16_PACKED_HALFS * sizeof(uint16_t));
+        p.o_convw = cv.reserve(4 * CONV_W16_BYTES);                                       // packed g / theta weights per head
+        p.o_colpart = cv.reserve((size_t)B * project16_key_blocks(g) * 224 * sizeof(float));
     }
     if (p.screen) {
-        p.o_xh = carve(off, (size_t)B * feat_rows_h(g.N) * DSH * sizeof(uint16_t));
-        p.o_wqh = carve(off, (size_t)B * feat_rows_h(g.L) * DSH * sizeof(uint16_t));
+        p.o_xh = cv.reserve((size_t)B * feat_rows_h(g.N) * DSH * sizeof(uint16_t));
+        p.o_wqh = cv.reserve((size_t)B * feat_rows_h(g.L) * DSH * sizeof(uint16_t));
         p.s_gkeep = (p.s_splits * 2 * 16 <= 512) ? 16 : 4;       // (screen_theta_kernel takes up to 512 values per query)
-        p.o_gmax = carve(off, BL * p.s_splits * 2 * p.s_gkeep * sizeof(float));
-        p.o_theta = carve(off, BL * sizeof(float));
-        p.o_scand = carve(off, BL * p.s_splits * 2 * p.capseg_alloc * sizeof(int2));     // candidate records (count in slot 0)
+        p.o_gmax = cv.reserve(BL * p.s_splits * 2 * p.s_gkeep * sizeof(float));
+        p.o_theta = cv.reserve(BL * sizeof(float));
+        p.o_scand = cv.reserve(BL * p.s_splits * 2 * p.capseg_alloc * sizeof(int2));     // candidate records (count in slot 0)
         if (mode != DAGL_MODE_ADAPTIVE) {       // top-k modes: a query's shared area behind its segments (ScreenArgs::spill)
-            p.o_spill = carve(off, BL * SCREEN_SPILL * sizeof(int2));
-            p.o_spillcnt = carve(off, BL * sizeof(unsigned));
+            p.o_spill = cv.reserve(BL * SCREEN_SPILL * sizeof(int2));
+            p.o_spillcnt = cv.reserve(BL * sizeof(unsigned));
         }
         if (mode == DAGL_MODE_ADAPTIVE) {
-            p.o_smax = carve(off, BL * sizeof(float));       // dense formulation: the rows' shifts (as scores)
-            p.o_traw = carve(off, BL * sizeof(float));       // ... and their largest sampled screened scores
+            p.o_smax = cv.reserve(BL * sizeof(float));       // dense formulation: the rows' shifts (as scores)
+            p.o_traw = cv.reserve(BL * sizeof(float));       // ... and their largest sampled screened scores
         }
-        p.o_redo = carve(off, (size_t)B * n_qgroups * sizeof(int32_t));
+        p.o_redo = cv.reserve((size_t)B * n_qgroups * sizeof(int32_t));
     }
     if (p.screen && mode == DAGL_MODE_ADAPTIVE && !core) {
         p.ovf_cap = overflow_cap(g.N, B);
-        p.o_ovflist = carve(off, (size_t)p.ovf_cap * sizeof(int32_t));
-        p.o_heavy = carve(off, (size_t)refine_heavy_cap() * sizeof(int32_t));
-        p.o_ovfq = carve(off, (size_t)p.ovf_cap * DS * sizeof(float));
-        p.o_ovfscores = carve(off, (size_t)B * p.ovf_cap * ((g.N + 31) / 32 * 32) * sizeof(float));
-        p.o_ovfpart = carve(off, (size_t)p.ovf_cap * OVF_CHUNKS * OVF_PART_FLOATS * sizeof(float));
+        p.o_ovflist = cv.reserve((size_t)p.ovf_cap * sizeof(int32_t));
+        p.o_heavy = cv.reserve((size_t)refine_heavy_cap() * sizeof(int32_t));
+        p.o_ovfq = cv.reserve((size_t)p.ovf_cap * DS * sizeof(float));
+        p.o_ovfscores = cv.reserve((size_t)B * p.ovf_cap * ((g.N + 31) / 32 * 32) * sizeof(float));
+        p.o_ovfpart = cv.reserve((size_t)p.ovf_cap * OVF_CHUNKS * OVF_PART_FLOATS * sizeof(float));
     }
-    if (p.wide) p.o_wide = carve(off, topk_wide_workspace_bytes(g.N, g.L));
-    p.o_end = off;
+    if (p.wide) p.o_wide = cv.reserve(topk_wide_workspace_bytes(g.N, g.L));
+    p.o_end = cv.bytes();
     return DAGL_OK;
 }
-
-template <class T>
-static T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
 static int check_device() {
     int dev = 0;
@@ -340,10 +332,8 @@ static int check_device() {
 
 // the streamed dense formulation's workspace (dense.hip), carved behind the plan: the end of it, and its offset
 static size_t dense_ws_end(const Plan& p, size_t* o_dense = nullptr) {
-    size_t off = p.o_end;
-    const size_t o = carve(off, dense_workspace_bytes(p.B, p.g));
-    if (o_dense) *o_dense = o;
-    return off;
+    if (o_dense) *o_dense = p.o_end;
+    return p.o_end + dense_workspace_bytes(p.B, p.g);
 }
 
 // every field of a call's info "not known" but the workspace it needs and the path
@@ -415,12 +405,7 @@ static int check_request(const ForwardRequest& r, const Plan& p) {
         DAGL_REQUIRE(m->b1 && m->b2, "dagl_ce_forward: null tensor pointer");
         if (thresholds) DAGL_REQUIRE(m->thr && m->bias, "dagl_ce_forward: thr/bias required in adaptive modes");
     }
-    DAGL_REQUIRE(r.ws != nullptr && ((uintptr_t)r.ws % 256) == 0, "dagl_ce_forward: workspace must be 256-byte aligned");
-    if (r.ws_bytes < p.o_end) {
-        set_error("dagl_ce_forward: workspace %zu B < required %zu B", r.ws_bytes, p.o_end);
-        return DAGL_ERR_WORKSPACE;
-    }
-    return DAGL_OK;
+    return check_workspace("dagl_ce_forward", r.ws, r.ws_bytes, p.o_end);
 }
 
 // One forward call: its plan, the workspace carve resolved to pointers, and what its stages share.  Built once per call.
@@ -564,19 +549,31 @@ static int prologue_fused(Call& c) {
                                                clear_redo_words, c.rt))) return rc;
             if (thr_heads && !c.thr_in_proj && (rc = launch_thr_bias_heads(c.s, heads, imgs, g, c.thr_all, thr_part))) return rc;
         }
-        // default path: the key/query map is only ever consumed as split fp16 (project16), so the prologue
-        // writes the hi / lo maps itself and no fp32 copy exists
-        B1Tiers tiers_hd;
-        const bool first = hd == 0;
-        if ((rc = launch_prologue(c.s, imgs, g, f.x, f.g_w, f.g_b, f.th_w, f.th_b, f.thr_w, f.thr_b, f.bias_w, f.bias_b,
-                                  p.split16 ? nullptr : c.b1p + hd * map_f, c.b2p + hd * map_f,
-                                  (thr_heads && !c.thr_in_proj) ? at<float>(ws, p.o_thr) + (size_t)hd * imgs * g.L : nullptr,
-                                  at<float>(ws, p.o_bias) + (size_t)hd * imgs * g.L,
-                                  p.split16 ? map_hi + hd * map_f : nullptr, p.split16 ? map_lo + hd * map_f : nullptr,
-                                  thr_part + (size_t)hd * 8 * imgs * g.L, c.prepared, /*defer_thr_reduce=*/thr_heads,
-                                  first ? clear_stats : nullptr, first ? clear_stats_words : 0,
-                                  first ? clear_redo : nullptr, first ? clear_redo_words : 0, c.rt, convw, conv_merged,
-                                  p.split16 ? &(tiers_hd = B1Tiers{tiers_all.hi2 + hd * map_f, tiers_all.lo2 + hd * map_f, tiers_all.amax, tiers_all.slots}) : nullptr))) return rc;
+        PrologueLaunch pl;
+        pl.B = imgs; pl.g = g; pl.x = f.x;
+        pl.g_w = f.g_w; pl.g_b = f.g_b; pl.th_w = f.th_w; pl.th_b = f.th_b;
+        pl.thr_w = f.thr_w; pl.thr_b = f.thr_b; pl.bias_w = f.bias_w; pl.bias_b = f.bias_b;
+        pl.b2p = c.b2p + hd * map_f;
+        if (p.split16) {
+            // default path: the key/query map is only ever consumed as split fp16 (project16), so the prologue
+            // writes the hi / lo maps itself and no fp32 copy exists
+            pl.conv = conv_merged ? ConvPath::DoneByCaller : ConvPath::Split16;
+            pl.conv_w16 = convw;
+            pl.b1_hi = map_hi + hd * map_f; pl.b1_lo = map_lo + hd * map_f;
+            pl.tiers = B1Tiers{tiers_all.hi2 + hd * map_f, tiers_all.lo2 + hd * map_f, tiers_all.amax, tiers_all.slots};
+        } else {
+            pl.b1p = c.b1p + hd * map_f;
+        }
+        if (thr_heads && !c.thr_in_proj) pl.thr = at<float>(ws, p.o_thr) + (size_t)hd * imgs * g.L;
+        pl.bias = at<float>(ws, p.o_bias) + (size_t)hd * imgs * g.L;
+        pl.thr_part = thr_part + (size_t)hd * 8 * imgs * g.L;
+        pl.borders_zero = c.prepared; pl.defer_thr_reduce = thr_heads;
+        if (hd == 0) {
+            pl.clear_a = clear_stats; pl.clear_a_words = clear_stats_words;
+            pl.clear_b = clear_redo; pl.clear_b_words = clear_redo_words;
+        }
+        pl.range = c.rt;
+        if ((rc = launch_prologue(c.s, pl))) return rc;
     }
     return DAGL_OK;
 }
@@ -673,22 +670,32 @@ static int stage_project(Call& c) {
         if ((rc = launch_rows_to_feat(c.s, c.B, g.L, c.core->wq_rows, c.Wq, c.Wqh, c.rt))) return rc;
         return c.mode != DAGL_MODE_TOPK ? launch_colsum_rows(c.s, c.B, g.N, c.core->x_rows, c.colsum) : DAGL_OK;
     }
-    if (!p.split16) return launch_project(c.s, c.B, g, 3, c.b1p, c.wp2, c.fc2_b, c.X, c.colsum, c.wp1, c.fc1_b, c.Wq, c.Xh, c.Wqh, c.rt);
-    B1Tiers tiers_fused;               // (the fused entry points: conv_pair16_kernel wrote both tiers; dagl_ce_forward's split_map_kernel only the fine one)
-    if (c.fin) {
-        tiers_fused.hi2 = at<uint16_t>(ws, p.o_maphi2); tiers_fused.lo2 = at<uint16_t>(ws, p.o_maplo2);
-        tiers_fused.amax = at<float>(ws, p.o_b1amax); tiers_fused.slots = conv16_blocks_per_head(g, c.heads, c.B / c.heads);
+    if (!p.split16) {
+        ProjectLaunch pj;
+        pj.B = c.B; pj.g = g; pj.which = 3; pj.map = c.b1p; pj.colsum = c.colsum; pj.range = c.rt;
+        pj.keys.wp = c.wp2; pj.keys.bias = c.fc2_b; pj.keys.feat = c.X; pj.keys.feat_bf16 = c.Xh;
+        pj.queries.wp = c.wp1; pj.queries.bias = c.fc1_b; pj.queries.feat = c.Wq; pj.queries.feat_bf16 = c.Wqh;
+        return launch_project(c.s, pj);
+    }
+    Project16Launch pj;
+    pj.B = c.B; pj.g = g; pj.which = 3; pj.heads = c.heads; pj.range = c.rt;
+    pj.map_hi = at<uint16_t>(ws, p.o_maphi); pj.map_lo = at<uint16_t>(ws, p.o_maplo);
+    if (c.fin) {       // (the fused entry points: conv_pair16_kernel wrote both tiers; dagl_ce_forward's split_map_kernel only the fine one)
+        pj.tiers.hi2 = at<uint16_t>(ws, p.o_maphi2); pj.tiers.lo2 = at<uint16_t>(ws, p.o_maplo2);
+        pj.tiers.amax = at<float>(ws, p.o_b1amax); pj.tiers.slots = conv16_blocks_per_head(g, c.heads, c.B / c.heads);
     }
     const float* b1s[4]; const float* b2s[4];
     for (int hd = 0; hd < 4; ++hd) {
         b1s[hd] = (c.fin && hd < c.heads) ? c.fin[hd].fc1_b : c.fc1_b;
         b2s[hd] = (c.fin && hd < c.heads) ? c.fin[hd].fc2_b : c.fc2_b;
     }
-    return launch_project16(c.s, c.B, g, 3, at<uint16_t>(ws, p.o_maphi), at<uint16_t>(ws, p.o_maplo), at<uint16_t>(ws, p.o_wp2h), b2s, c.X,
-                            (c.mode == DAGL_MODE_TOPK) ? nullptr : c.colsum, at<float>(ws, p.o_colpart), at<uint16_t>(ws, p.o_wp1h), b1s,
-                            c.Wq, c.Xh, c.Wqh, c.heads, c.rt, c.q_tiled, c.split_p,
-                            c.thr_in_proj ? &c.thr_all : nullptr, c.thr_in_proj ? c.B : 0, c.thr_in_proj ? at<float>(ws, p.o_thrpart) : nullptr,
-                            c.fin ? &tiers_fused : nullptr);
+    pj.keys.wp = at<uint16_t>(ws, p.o_wp2h); pj.keys.bias = b2s; pj.keys.feat = c.X; pj.keys.feat_bf16 = c.Xh;
+    pj.queries.wp = at<uint16_t>(ws, p.o_wp1h); pj.queries.bias = b1s; pj.queries.feat = c.Wq; pj.queries.feat_bf16 = c.Wqh;
+    if (c.mode != DAGL_MODE_TOPK) pj.colsum = c.colsum;
+    pj.colpart = at<float>(ws, p.o_colpart);
+    pj.q_tiled = c.q_tiled; pj.split = c.split_p;
+    if (c.thr_in_proj) { pj.thr_hs = &c.thr_all; pj.thr_head_imgs = c.B; pj.thr_part = at<float>(ws, p.o_thrpart); }
+    return launch_project16(c.s, pj);
 }
 
 // ---- stage 2: adaptive thresholds ----------------------------------------------------------------------
@@ -900,12 +907,13 @@ static int scan_adaptive(Call& c) {
         return launch_edge_softmax(c.s, ea);
     }
     // two-pass CSR: exact degrees are known, refill deterministically at per-lane cursors
-    size_t off = p.o_end;
+    Carver cv(ws, p.o_end);
     const size_t e = (size_t)edges;
-    const size_t o_ci = carve(off, e * sizeof(int32_t));
-    const size_t o_cv = carve(off, e * sizeof(float));
-    const size_t o_ni = carve(off, e * sizeof(int32_t));
-    const size_t o_nw = carve(off, e * sizeof(float));
+    int32_t* csr_idx = cv.take<int32_t>(e);
+    float* csr_val = cv.take<float>(e);
+    int32_t* csr_nb_idx = cv.take<int32_t>(e);
+    float* csr_nb_wgt = cv.take<float>(e);
+    const size_t off = cv.bytes();
     if (info) { info->required_bytes = (int64_t)off; info->path = 1; }
     if (c.core) {
         if (info) info->required_bytes = -1;
@@ -920,10 +928,10 @@ static int scan_adaptive(Call& c) {
     }
     int64_t* rowoff = at<int64_t>(ws, p.o_rowoff);
     if ((rc = launch_row_scan(c.s, (int)c.BL, deg, rowoff))) return rc;
-    sa.list_idx = at<int32_t>(ws, o_ci); sa.list_val = at<float>(ws, o_cv); sa.seg_rel = segrel; sa.row_off = rowoff;
+    sa.list_idx = csr_idx; sa.list_val = csr_val; sa.seg_rel = segrel; sa.row_off = rowoff;
     if ((rc = launch_score_select(c.s, sa, 1))) return rc;
     ea.cnt = deg; ea.list_idx = sa.list_idx; ea.list_val = sa.list_val; ea.row_off = rowoff;
-    ea.nb_idx = at<int32_t>(ws, o_ni); ea.nb_wgt = at<float>(ws, o_nw);
+    ea.nb_idx = csr_nb_idx; ea.nb_wgt = csr_nb_wgt;
     if ((rc = launch_edge_softmax(c.s, ea))) return rc;
     c.ag.nb_idx = ea.nb_idx; c.ag.nb_wgt = ea.nb_wgt; c.ag.row_off = rowoff;
     return DAGL_OK;
@@ -1249,11 +1257,7 @@ int dagl_ces_stage_forward(void* stream, int B, int H, int W, const float* x, co
     if (rc) return rc;
     const size_t cat_bytes = align_up((size_t)B * 64 * H * W * sizeof(float), 256);
     if (info) info->required_bytes = (int64_t)(p.o_end + cat_bytes);
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ces_stage_forward: workspace must be 256-byte aligned");
-    if (ws_bytes < p.o_end + cat_bytes) {
-        set_error("dagl_ces_stage_forward: workspace %zu B < required %zu B", ws_bytes, p.o_end + cat_bytes);
-        return DAGL_ERR_WORKSPACE;
-    }
+    if ((rc = check_workspace("dagl_ces_stage_forward", workspace, ws_bytes, p.o_end + cat_bytes))) return rc;
     FusedIn fin[4];
     for (int h = 0; h < 4; ++h) {
         const dagl_ce_weights& w = heads4[h];
@@ -1262,7 +1266,7 @@ int dagl_ces_stage_forward(void* stream, int B, int H, int W, const float* x, co
         DAGL_REQUIRE(w.g_w && w.g_b && w.theta_w && w.theta_b && w.fc1_w && w.fc1_b && w.fc2_w && w.fc2_b,
                      "dagl_ces_stage_forward: head %d has a null weight pointer", h);
     }
-    float* cat = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.o_end);       // [B,64,H,W]
+    float* cat = at<float>(workspace, p.o_end);       // [B,64,H,W]
     // a dense adaptive neighbourhood asks for more workspace than planned: give the block everything up to the concat map
     ForwardRequest r(stream, 4 * B, H, W, mode, k, cat, workspace, p.o_end, info);
     r.fin = fin; r.heads = 4;
@@ -1286,7 +1290,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
     if (mode & DAGL_FLAG_EXACT_SCAN) return DAGL_OK;                      // the fp32 path has no such range (and always waits)
     // ONE read-back (one synchronisation) of the statistics words STAT_FLAGGED .. STAT_NO_REDO_STICKY
     int64_t hw[STAT_WORDS] = {0};
-    int64_t* st = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + p.o_stats);
+    int64_t* st = at<int64_t>(workspace, p.o_stats);
     if ((rc = read_back((hipStream_t)stream, st + STAT_FLAGGED, STAT_NO_REDO_STICKY + 1 - STAT_FLAGGED, hw + STAT_FLAGGED))) return rc;
     const bool topk_screen = (mode & 0xff) != DAGL_MODE_ADAPTIVE && p.screen;
     // sticky: the word keeps the tag of the last call that left the range until it is read here (calls that reuse a
@@ -1322,29 +1326,33 @@ int dagl_ce_core_forward(void* stream, int B, int H, int W, const float* wq_rows
     return ce_forward(r);
 }
 
-static size_t backward_offsets(int B, const Grid& g, int width, size_t o[13], size_t* sort_temp) {
-    size_t off = 0;
+// the list backward's workspace: the one walk that sizes it (null base) and hands its regions to the launch
+struct BwdWs { float* dagg; float* b2p; float* dS; float* dmu; double* colsum; float* dxbar; BwdSortWs sort; size_t bytes; };
+static BwdWs backward_carve(void* ws, int B, const Grid& g, int width) {
+    Carver cv(ws);
     const size_t BL = (size_t)B * g.L, E = BL * width, n_keys = (size_t)B * g.N;
-    o[0] = carve(off, BL * P * sizeof(float));                                  // d agg
-    o[1] = carve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(float));            // b2 padded NHWC
-    o[2] = carve(off, E * sizeof(float));                                       // d S
-    o[3] = carve(off, BL * sizeof(float));                                      // d mu
-    o[4] = carve(off, (size_t)B * DS * sizeof(double) + (size_t)B * D * sizeof(float));   // column sums, d Xbar
-    for (int i = 5; i < 9; ++i) o[i] = carve(off, E * sizeof(uint32_t));        // sort keys / edge ids, in and out
-    o[9] = carve(off, 2 * n_keys * sizeof(uint32_t));                           // run of every key
-    const size_t tb = edge_sort_temp_bytes(E, n_keys);
-    o[10] = carve(off, tb);
-    o[11] = carve(off, edge_rowbuf_floats(E) * sizeof(float));
-    o[12] = carve(off, edge_part_floats(E) * sizeof(float));
-    if (sort_temp) *sort_temp = tb;
-    return off;
+    BwdWs w;
+    w.dagg = cv.take<float>(BL * P);
+    w.b2p = cv.take<float>((size_t)B * g.Hp * g.Wp * CH);                       // b2 padded NHWC
+    w.dS = cv.take<float>(E);
+    w.dmu = cv.take<float>(BL);
+    w.colsum = reinterpret_cast<double*>(cv.take<char>((size_t)B * DS * sizeof(double) + (size_t)B * D * sizeof(float)));
+    w.dxbar = reinterpret_cast<float*>(w.colsum + (size_t)B * DS);              // (d Xbar shares the column sums' region)
+    w.sort.keys_in = cv.take<uint32_t>(E); w.sort.keys_out = cv.take<uint32_t>(E);      // sort keys / edge ids, in and out
+    w.sort.vals_in = cv.take<uint32_t>(E); w.sort.vals_out = cv.take<uint32_t>(E);
+    w.sort.seg = cv.take<uint32_t>(2 * n_keys);                                 // run of every key
+    w.sort.temp_bytes = edge_sort_temp_bytes(E, n_keys);
+    w.sort.temp = cv.take<char>(w.sort.temp_bytes);
+    w.sort.rowbuf = cv.take<float>(edge_rowbuf_floats(E));
+    w.sort.part = cv.take<float>(edge_part_floats(E));
+    w.bytes = cv.bytes();
+    return w;
 }
 
 size_t dagl_ce_core_backward_workspace_bytes(int B, int H, int W, int mode, int k) {
     const int width = dagl_ce_list_width(mode, k);
     if (B < 1 || H < 1 || W < 1 || width < 0) return 0;
-    size_t o[13];
-    return backward_offsets(B, make_grid(H, W), width, o, nullptr);
+    return backward_carve(nullptr, B, make_grid(H, W), width).bytes;
 }
 
 int dagl_ce_core_backward(void* stream, int B, int H, int W, int mode, int k, const float* wq_rows, const float* x_rows,
@@ -1360,38 +1368,34 @@ int dagl_ce_core_backward(void* stream, int B, int H, int W, int mode, int k, co
                  "dagl_ce_core_backward: null tensor pointer");
     if (m != DAGL_MODE_TOPK)
         DAGL_REQUIRE(thr && bias && mu && d_thr && d_bias, "dagl_ce_core_backward: thr/bias/mu and their gradients required in adaptive modes");
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ce_core_backward: workspace must be 256-byte aligned");
+    int rc;
+    if ((rc = check_workspace("dagl_ce_core_backward", workspace, ws_bytes, 0))) return rc;
     const Grid g = make_grid(H, W);
     DAGL_REQUIRE((size_t)B * g.L * width < (1ull << 31) && (size_t)B * g.N < (1ull << 31), "dagl_ce_core_backward: batch too large for 32-bit edge ids");
-    size_t o[13], sort_temp = 0;
-    const size_t need = backward_offsets(B, g, width, o, &sort_temp);
-    if (ws_bytes < need) {
-        set_error("dagl_ce_core_backward: workspace %zu B < required %zu B", ws_bytes, need);
-        return DAGL_ERR_WORKSPACE;
-    }
+    const BwdWs w = backward_carve(workspace, B, g, width);
+    if ((rc = check_workspace("dagl_ce_core_backward", workspace, ws_bytes, w.bytes))) return rc;
     hipStream_t s = (hipStream_t)stream;
     BwdArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.g = g; a.mode = m; a.width = width;
     a.wq_rows = wq_rows; a.x_rows = x_rows; a.thr = thr; a.bs = bias; a.mu = mu;
     a.nb_idx = nb_idx; a.nb_wgt = nb_wgt; a.nb_s = nb_s; a.nb_cnt = nb_cnt; a.dout = d_out;
-    a.dagg = at<float>(workspace, o[0]);
-    float* b2p = at<float>(workspace, o[1]);
-    a.b2p = b2p; a.dS = at<float>(workspace, o[2]); a.dmu = at<float>(workspace, o[3]);
-    double* colsum = at<double>(workspace, o[4]);
-    float* dxbar = reinterpret_cast<float*>(colsum + (size_t)B * DS);
-    a.colsum = colsum;
+    a.dagg = w.dagg; a.b2p = w.b2p; a.dS = w.dS; a.dmu = w.dmu; a.colsum = w.colsum;
     a.dwq_rows = d_wq_rows; a.dx_rows = d_x_rows; a.dthr = d_thr; a.dbias = d_bias;
-    BwdSortWs w;
-    w.keys_in = at<uint32_t>(workspace, o[5]); w.keys_out = at<uint32_t>(workspace, o[6]);
-    w.vals_in = at<uint32_t>(workspace, o[7]); w.vals_out = at<uint32_t>(workspace, o[8]);
-    w.seg = at<uint32_t>(workspace, o[9]); w.temp = at<void>(workspace, o[10]); w.temp_bytes = sort_temp;
-    w.rowbuf = at<float>(workspace, o[11]); w.part = at<float>(workspace, o[12]);
-    int rc;
-    if ((rc = launch_pad_nhwc(s, B, H, W, b2, b2p))) return rc;
+    if ((rc = launch_pad_nhwc(s, B, H, W, b2, w.b2p))) return rc;
     if (m != DAGL_MODE_TOPK)
-        if ((rc = launch_colsum_rows(s, B, g.N, x_rows, colsum))) return rc;
-    return launch_core_backward(s, a, w, dxbar, d_b2);
+        if ((rc = launch_colsum_rows(s, B, g.N, x_rows, w.colsum))) return rc;
+    return launch_core_backward(s, a, w.sort, w.dxbar, d_b2);
+}
+
+// total edges / largest degree of a dense-core call, from the two statistics words behind its workspace (info == NULL: not read)
+static int read_edge_stats(hipStream_t s, const int64_t* stats, dagl_ce_info* info) {
+    if (!info) return DAGL_OK;
+    int64_t hs[STAT_MAX_DEGREE + 1] = {0};
+    const int rc = read_back(s, stats, STAT_MAX_DEGREE + 1, hs);
+    if (rc) return rc;
+    info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
+    return DAGL_OK;
 }
 
 // forward on the inference path's streamed kernel (split-fp16 S and A V in one pass over the keys) when the image has enough
@@ -1416,7 +1420,8 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
                                void* workspace, size_t ws_bytes, dagl_ce_info* info) {
     DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && wq_rows && x_rows && b2 && thr && bias && out && lse && mu &&
                  (flags & ~DAGL_FLAG_EXACT_SCAN) == 0, "dagl_ce_core_dense_forward: bad argument");
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ce_core_dense_forward: workspace must be 256-byte aligned");
+    int rc;
+    if ((rc = check_workspace("dagl_ce_core_dense_forward", workspace, ws_bytes, 0))) return rc;
     const Grid g = make_grid(H, W);
     hipStream_t s = (hipStream_t)stream;
     bool left_range = false;
@@ -1433,18 +1438,15 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
     reset_info(info, (int64_t)dense_train_workspace_bytes(B, g, false), 5);
     // the two statistics words live at the very end of the caller's buffer (past the plan)
     const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
-    if (ws_bytes < need) { set_error("dagl_ce_core_dense_forward: workspace %zu B < required %zu B", ws_bytes, need);
-                           if (info) info->required_bytes = (int64_t)need; return DAGL_ERR_WORKSPACE; }
-    int64_t* stats = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + need - 256);
-    int rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, thr, bias, out, lse, mu, workspace, need - 256,
-                                        info ? stats : nullptr);
-    if (rc) return rc;
-    if (info) {
-        int64_t hs[STAT_MAX_DEGREE + 1] = {0};
-        if ((rc = read_back(s, stats, STAT_MAX_DEGREE + 1, hs))) return rc;
-        info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
-        info->range_fallback = left_range ? 1 : 0;
+    if ((rc = check_workspace("dagl_ce_core_dense_forward", workspace, ws_bytes, need))) {
+        if (info) info->required_bytes = (int64_t)need;
+        return rc;
     }
+    int64_t* stats = at<int64_t>(workspace, need - 256);
+    if ((rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, thr, bias, out, lse, mu, workspace, need - 256,
+                                         info ? stats : nullptr))) return rc;
+    if ((rc = read_edge_stats(s, stats, info))) return rc;
+    if (info) info->range_fallback = left_range ? 1 : 0;
     return DAGL_OK;
 }
 
@@ -1454,7 +1456,8 @@ int dagl_ce_core_dense_backward(void* stream, int B, int H, int W, int flags, co
                                 size_t ws_bytes) {
     DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && wq_rows && x_rows && b2 && thr && bias && lse && mu && d_out && d_wq_rows &&
                  d_x_rows && d_b2 && d_thr && d_bias && (flags & ~DAGL_FLAG_EXACT_SCAN) == 0, "dagl_ce_core_dense_backward: bad argument");
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ce_core_dense_backward: workspace must be 256-byte aligned");
+    const int rc = check_workspace("dagl_ce_core_dense_backward", workspace, ws_bytes, 0);
+    if (rc) return rc;
     return launch_dense_train_backward((hipStream_t)stream, B, make_grid(H, W), wq_rows, x_rows, b2, thr, bias, lse, mu, d_out,
                                        d_wq_rows, d_x_rows, d_b2, d_thr, d_bias, workspace, ws_bytes, (flags & DAGL_FLAG_EXACT_SCAN) != 0);
 }
@@ -1467,24 +1470,19 @@ int dagl_ce_core_wide_forward(void* stream, int B, int H, int W, int mode, int k
     DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && wq_rows && x_rows && b2 && out && k >= 1 &&
                  (mode == DAGL_MODE_TOPK || mode == DAGL_MODE_ADAPTIVE_TOPK), "dagl_ce_core_wide_forward: bad argument");
     DAGL_REQUIRE(mode == DAGL_MODE_TOPK || (thr && bias), "dagl_ce_core_wide_forward: the intersection mode needs thr and bias");
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ce_core_wide_forward: workspace must be 256-byte aligned");
+    int rc;
+    if ((rc = check_workspace("dagl_ce_core_wide_forward", workspace, ws_bytes, 0))) return rc;
     const Grid g = make_grid(H, W);
     if (k > g.N) k = g.N;                                              // top_k = min(num_edge, N)
     const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
     reset_info(info, (int64_t)need, 5);
-    if (ws_bytes < need) { set_error("dagl_ce_core_wide_forward: workspace %zu B < required %zu B", ws_bytes, need); return DAGL_ERR_WORKSPACE; }
+    if ((rc = check_workspace("dagl_ce_core_wide_forward", workspace, ws_bytes, need))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    int64_t* stats = reinterpret_cast<int64_t*>(static_cast<char*>(workspace) + need - 256);
+    int64_t* stats = at<int64_t>(workspace, need - 256);
     const bool heads = mode != DAGL_MODE_TOPK;
-    int rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, heads ? thr : nullptr, heads ? bias : nullptr, out, nullptr, nullptr,
-                                        workspace, need - 256, info ? stats : nullptr, mode, k);
-    if (rc) return rc;
-    if (info) {
-        int64_t hs[STAT_MAX_DEGREE + 1] = {0};
-        if ((rc = read_back(s, stats, STAT_MAX_DEGREE + 1, hs))) return rc;
-        info->total_edges = hs[STAT_EDGES]; info->max_degree = (int32_t)hs[STAT_MAX_DEGREE];
-    }
-    return DAGL_OK;
+    if ((rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, heads ? thr : nullptr, heads ? bias : nullptr, out, nullptr, nullptr,
+                                         workspace, need - 256, info ? stats : nullptr, mode, k))) return rc;
+    return read_edge_stats(s, stats, info);
 }
 
 int dagl_ce_core_wide_backward(void* stream, int B, int H, int W, int mode, int k, const float* wq_rows, const float* x_rows,
@@ -1494,7 +1492,8 @@ int dagl_ce_core_wide_backward(void* stream, int B, int H, int W, int mode, int 
                  (mode == DAGL_MODE_TOPK || mode == DAGL_MODE_ADAPTIVE_TOPK), "dagl_ce_core_wide_backward: bad argument");
     DAGL_REQUIRE(mode == DAGL_MODE_TOPK || (thr && bias && d_thr && d_bias),
                  "dagl_ce_core_wide_backward: the intersection mode needs thr, bias and their gradients");
-    DAGL_REQUIRE(workspace != nullptr && ((uintptr_t)workspace % 256) == 0, "dagl_ce_core_wide_backward: workspace must be 256-byte aligned");
+    const int rc = check_workspace("dagl_ce_core_wide_backward", workspace, ws_bytes, 0);
+    if (rc) return rc;
     const Grid g = make_grid(H, W);
     if (k > g.N) k = g.N;
     const bool heads = mode != DAGL_MODE_TOPK;
@@ -1530,23 +1529,33 @@ int dagl_ce_prologue(void* stream, int B, int H, int W, const float* x, const fl
     if (thr || bias)
         DAGL_REQUIRE(thr && bias && thr_w && thr_b && bias_w && bias_b && scratch,
                      "dagl_ce_prologue: thr/bias heads incomplete (weights, outputs and 8*B*L floats of scratch)");
-    hipStream_t s = (hipStream_t)stream;
-    const Grid g = make_grid(H, W);
-    return launch_prologue(s, B, g, x, g_w, g_b, theta_w, theta_b, thr_w, thr_b, bias_w, bias_b, b1_nhwc, b2_nhwc,
-                           thr, bias, nullptr, nullptr, scratch);
+    PrologueLaunch pl;
+    pl.B = B; pl.g = make_grid(H, W); pl.x = x;
+    pl.g_w = g_w; pl.g_b = g_b; pl.th_w = theta_w; pl.th_b = theta_b;
+    pl.thr_w = thr_w; pl.thr_b = thr_b; pl.bias_w = bias_w; pl.bias_b = bias_b;
+    pl.conv = ConvPath::Fp32;
+    pl.b1p = b1_nhwc; pl.b2p = b2_nhwc; pl.thr = thr; pl.bias = bias; pl.thr_part = scratch;
+    return launch_prologue((hipStream_t)stream, pl);
 }
 
 // (ABI 405) the same four convolutions with g / theta on the fp16 matrix cores (split operands, conv_pair16_kernel: a third of the fp32
 // kernel's time) and the key / query map out in fp32 -- the differentiable path's forward.  The input is split with a power-of-two scale
 // of each block's own (a second run of the strip when its rows leave |16 x| < 60000): no range on x; |w_conv| < 234 as everywhere.
+struct Pro16Ws { unsigned char* convw; float* amax; int slots; float* thr_part; size_t bytes; };
+static Pro16Ws prologue16_carve(void* scratch, int B, const Grid& g) {
+    Carver cv(scratch);
+    Pro16Ws w;
+    w.convw = cv.take<unsigned char>(CONV_W16_BYTES);
+    w.slots = conv16_blocks_per_head(g, 1, B);
+    w.amax = cv.take<float>((size_t)w.slots);
+    w.thr_part = cv.take<float>(8 * (size_t)B * g.L);
+    w.bytes = cv.bytes();
+    return w;
+}
+
 size_t dagl_ce_prologue16_scratch_bytes(int B, int H, int W) {
     if (B < 1 || H < 1 || W < 1) return 0;
-    const Grid g = make_grid(H, W);
-    size_t off = 0;
-    carve(off, CONV_W16_BYTES);
-    carve(off, (size_t)conv16_blocks_per_head(g, 1, B) * sizeof(float));
-    carve(off, 8 * (size_t)B * g.L * sizeof(float));
-    return off;
+    return prologue16_carve(nullptr, B, make_grid(H, W)).bytes;
 }
 
 int dagl_ce_prologue16(void* stream, int B, int H, int W, const float* x, const float* g_w, const float* g_b,
@@ -1561,37 +1570,38 @@ int dagl_ce_prologue16(void* stream, int B, int H, int W, const float* x, const 
                  "dagl_ce_prologue16: scratch %zu B (256-byte aligned), need %zu B", scratch_bytes, dagl_ce_prologue16_scratch_bytes(B, H, W));
     hipStream_t s = (hipStream_t)stream;
     const Grid g = make_grid(H, W);
-    size_t off = 0;
-    unsigned char* convw = at<unsigned char>(scratch, carve(off, CONV_W16_BYTES));
-    B1Tiers tiers;                                   // (slots only: the fp32 map has no tiers; they switch the per-block input scale on)
-    tiers.slots = conv16_blocks_per_head(g, 1, B);
-    tiers.amax = at<float>(scratch, carve(off, (size_t)tiers.slots * sizeof(float)));
-    float* thr_part = at<float>(scratch, carve(off, 8 * (size_t)B * g.L * sizeof(float)));
+    const Pro16Ws w = prologue16_carve(scratch, B, g);
     int rc;
-    if ((rc = launch_pack_conv_weight16(s, g_w, theta_w, convw))) return rc;
-    return launch_prologue(s, B, g, x, g_w, g_b, theta_w, theta_b, thr_w, thr_b, bias_w, bias_b, b1_nhwc, b2_nhwc,
-                           thr, bias, nullptr, nullptr, thr_part, false, false, nullptr, 0, nullptr, 0, RangeTag(), convw, false, &tiers);
+    if ((rc = launch_pack_conv_weight16(s, g_w, theta_w, w.convw))) return rc;
+    PrologueLaunch pl;
+    pl.B = B; pl.g = g; pl.x = x;
+    pl.g_w = g_w; pl.g_b = g_b; pl.th_w = theta_w; pl.th_b = theta_b;
+    pl.thr_w = thr_w; pl.thr_b = thr_b; pl.bias_w = bias_w; pl.bias_b = bias_b;
+    pl.conv = ConvPath::Split16; pl.conv_w16 = w.convw;
+    pl.tiers.amax = w.amax; pl.tiers.slots = w.slots;   // (slots only: the fp32 map has no tiers; they switch the per-block input scale on)
+    pl.b1p = b1_nhwc; pl.b2p = b2_nhwc; pl.thr = thr; pl.bias = bias; pl.thr_part = w.thr_part;
+    return launch_prologue(s, pl);
 }
 
 // ---- the 7x7x16 -> 196 patch Linear (+ReLU) of the differentiable path's FORWARD on the inference kernels: split the map,
 // pack the weight, project (split-fp16 matrix cores, no unfolded rows), copy the feature rows out densely ---------------
-static void pp16_carve(int B, const Grid& g, int n, size_t& o_hi, size_t& o_lo, size_t& o_wp, size_t& o_feat, size_t& o_range,
-                       size_t& total) {
-    size_t off = 0;
-    const size_t map_h = (size_t)B * g.Hp * g.Wp * CH * sizeof(uint16_t);
-    o_hi = carve(off, map_h); o_lo = carve(off, map_h);
-    o_wp = carve(off, P16_PACKED_HALFS * sizeof(uint16_t));
-    o_feat = carve(off, (size_t)B * feat_rows(n) * DS * sizeof(float));
-    o_range = carve(off, 2 * sizeof(int64_t));                        // range word, completion word (RangeTag)
-    total = off;
+struct Pp16Ws { uint16_t *hi, *lo, *wp; float* feat; int64_t* words; size_t bytes; };
+static Pp16Ws pp16_carve(void* scratch, int B, const Grid& g, int n) {
+    Carver cv(scratch);
+    const size_t map_h = (size_t)B * g.Hp * g.Wp * CH;
+    Pp16Ws w;
+    w.hi = cv.take<uint16_t>(map_h); w.lo = cv.take<uint16_t>(map_h);
+    w.wp = cv.take<uint16_t>(P16_PACKED_HALFS);
+    w.feat = cv.take<float>((size_t)B * feat_rows(n) * DS);
+    w.words = cv.take<int64_t>(2);                                    // range word, completion word (RangeTag)
+    w.bytes = cv.bytes();
+    return w;
 }
 
 size_t dagl_project_patches16_scratch_bytes(int B, int H, int W, int queries) {
     if (B < 1 || H < 1 || W < 1) return 0;
     const Grid g = make_grid(H, W);
-    size_t a, b2, c, d, e, total;
-    pp16_carve(B, g, queries ? g.L : g.N, a, b2, c, d, e, total);
-    return total;
+    return pp16_carve(nullptr, B, g, queries ? g.L : g.N).bytes;
 }
 
 int dagl_project_patches16(void* stream, int B, int H, int W, int queries, const float* map_nhwc, const float* w_rows,
@@ -1602,28 +1612,24 @@ int dagl_project_patches16(void* stream, int B, int H, int W, int queries, const
     hipStream_t s = (hipStream_t)stream;
     const Grid g = make_grid(H, W);
     const int n = queries ? g.L : g.N;
-    size_t o_hi, o_lo, o_wp, o_feat, o_range, total;
-    pp16_carve(B, g, n, o_hi, o_lo, o_wp, o_feat, o_range, total);
-    DAGL_REQUIRE(scratch_bytes >= total, "dagl_project_patches16: scratch %zu B, need %zu B", scratch_bytes, total);
-    uint16_t* hi = at<uint16_t>(scratch, o_hi);
-    uint16_t* lo = at<uint16_t>(scratch, o_lo);
-    uint16_t* wp = at<uint16_t>(scratch, o_wp);
-    float* feat = at<float>(scratch, o_feat);
+    const Pp16Ws w = pp16_carve(scratch, B, g, n);
+    DAGL_REQUIRE(scratch_bytes >= w.bytes, "dagl_project_patches16: scratch %zu B, need %zu B", scratch_bytes, w.bytes);
     int rc;
     // range guard (|16 map| , |1024 w| < 65504): the split / pack / projection kernels store this call's tag into the range
     // word when they meet a larger value, and the copy-out below then writes NaN instead of numbers formed from inf halves
     RangeTag rt;
-    int64_t* words = at<int64_t>(scratch, o_range);
-    DAGL_HIP_TRY(hipMemsetAsync(words, 0, 2 * sizeof(int64_t), s));
-    rt.word = reinterpret_cast<int32_t*>(words); rt.done = reinterpret_cast<int32_t*>(words + 1); rt.tag = next_call_tag();
-    if ((rc = launch_split_map(s, (size_t)B * g.Hp * g.Wp * CH, map_nhwc, hi, lo, rt))) return rc;
-    if ((rc = launch_pack_fc_weight16(s, w_rows, wp, /*rows_order=*/true))) return rc;
+    DAGL_HIP_TRY(hipMemsetAsync(w.words, 0, 2 * sizeof(int64_t), s));
+    rt.word = reinterpret_cast<int32_t*>(w.words); rt.done = reinterpret_cast<int32_t*>(w.words + 1); rt.tag = next_call_tag();
+    if ((rc = launch_split_map(s, (size_t)B * g.Hp * g.Wp * CH, map_nhwc, w.hi, w.lo, rt))) return rc;
+    if ((rc = launch_pack_fc_weight16(s, w_rows, w.wp, /*rows_order=*/true))) return rc;
     const float* bias1[1] = {fc_bias};
-    if (queries) rc = launch_project16(s, B, g, 2, hi, lo, nullptr, nullptr, nullptr, nullptr, nullptr, wp, bias1, feat, nullptr, nullptr, 1, rt);
-    else rc = launch_project16(s, B, g, 1, hi, lo, wp, bias1, feat, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, rt);
-    if (rc) return rc;
+    Project16Launch pj;
+    pj.B = B; pj.g = g; pj.which = queries ? 2 : 1; pj.map_hi = w.hi; pj.map_lo = w.lo; pj.range = rt;
+    auto& side = queries ? pj.queries : pj.keys;
+    side.wp = w.wp; side.bias = bias1; side.feat = w.feat;
+    if ((rc = launch_project16(s, pj))) return rc;
     // [B, feat_rows(n), DS] -> [B, n, 196]
-    return launch_feat_rows_out(s, B, n, feat, rows_out, rt);
+    return launch_feat_rows_out(s, B, n, w.feat, rows_out, rt);
 }
 
 int dagl_pad_nhwc(void* stream, int B, int H, int W, const float* src_nchw, float* dst_nhwc) {
@@ -1648,8 +1654,12 @@ int dagl_project_patches(void* stream, int B, int H, int W, int queries, const f
     for (int b = 0; b < B; ++b)
         DAGL_HIP_TRY(hipMemsetAsync(feat + ((size_t)b * ra + rows) * DS, 0, (size_t)(ra - rows) * DS * sizeof(float), s));
     if (colsum) DAGL_HIP_TRY(hipMemsetAsync(colsum, 0, (size_t)B * DS * sizeof(double), s));
-    if (queries) return launch_project(s, B, g, 2, map_nhwc, nullptr, nullptr, nullptr, nullptr, w_packed, fc_bias, feat);
-    return launch_project(s, B, g, 1, map_nhwc, w_packed, fc_bias, feat, colsum, nullptr, nullptr, nullptr);
+    ProjectLaunch pj;
+    pj.B = B; pj.g = g; pj.which = queries ? 2 : 1; pj.map = map_nhwc;
+    auto& side = queries ? pj.queries : pj.keys;
+    side.wp = w_packed; side.bias = fc_bias; side.feat = feat;
+    if (!queries) pj.colsum = colsum;
+    return launch_project(s, pj);
 }
 
 int dagl_query_thresholds(void* stream, int B, int L, int N, const float* wq, const double* colsum,
@@ -1750,16 +1760,6 @@ size_t dagl_ce_graph_workspace_bytes(int B, int H, int W, int mode, int k, int r
     return p.o_end;
 }
 
-// the workspace of both phases, checked against the plan before anything reaches the device
-static int graph_check_workspace(const char* who, const GraphPlan& p, const void* ws, size_t ws_bytes) {
-    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", who);
-    if (ws_bytes < p.o_end) {
-        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, p.o_end);
-        return DAGL_ERR_WORKSPACE;
-    }
-    return DAGL_OK;
-}
-
 int dagl_ce_graph_count(void* stream, int B, int H, int W, const float* b1, const float* thr, const float* bias, const float* fc1_w,
                         const float* fc1_b, const float* fc2_w, const float* fc2_b, int mode, int k, int rows_per_chunk,
                         int64_t* row_off_out, void* workspace, size_t ws_bytes, dagl_ce_info* info) {
@@ -1769,7 +1769,7 @@ int dagl_ce_graph_count(void* stream, int B, int H, int W, const float* b1, cons
     reset_info(info, (int64_t)p.o_end, 8);
     DAGL_REQUIRE(row_off_out && b1 && fc1_w && fc1_b && fc2_w && fc2_b, "dagl_ce_graph_count: null tensor pointer");
     if (mode != DAGL_MODE_TOPK) DAGL_REQUIRE(thr && bias, "dagl_ce_graph_count: thr/bias required in adaptive modes");
-    if ((rc = graph_check_workspace("dagl_ce_graph_count", p, workspace, ws_bytes))) return rc;
+    if ((rc = check_workspace("dagl_ce_graph_count", workspace, ws_bytes, p.o_end))) return rc;
     return launch_graph_count((hipStream_t)stream, p, b1, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, row_off_out, workspace);
 }
 
@@ -1786,7 +1786,7 @@ int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int r
         return DAGL_ERR_WORKSPACE;
     }
     DAGL_REQUIRE(row_off && (total_edges == 0 || (key_out && weight_out)), "dagl_ce_graph_fill: null tensor pointer");
-    if ((rc = graph_check_workspace("dagl_ce_graph_fill", p, workspace, ws_bytes))) return rc;
+    if ((rc = check_workspace("dagl_ce_graph_fill", workspace, ws_bytes, p.o_end))) return rc;
     if (total_edges == 0) return DAGL_OK;
     return launch_graph_fill((hipStream_t)stream, p, row_off, key_out, weight_out, score_out, (long long)capacity_edges, workspace);
 }
@@ -1815,15 +1815,6 @@ size_t dagl_graph_apply_backward_workspace_bytes(int B, int H, int W, int64_t to
     return graph_apply_bytes("dagl_graph_apply_backward_workspace_bytes", B, H, W, total_edges, true);
 }
 
-static int graph_apply_check_workspace(const char* who, size_t need, const void* ws, size_t ws_bytes) {
-    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", who);
-    if (ws_bytes < need) {
-        set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
-        return DAGL_ERR_WORKSPACE;
-    }
-    return DAGL_OK;
-}
-
 int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
                      int64_t total_edges, float* out, void* workspace, size_t ws_bytes) {
     int rc = graph_apply_shape_ok("dagl_graph_apply", B, H, W, total_edges);
@@ -1831,8 +1822,7 @@ int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const 
     DAGL_REQUIRE(b2p && row_off && out && (total_edges == 0 || (key && weight)), "dagl_graph_apply: null tensor pointer");
     DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_apply: b2p must be 16-byte aligned");
     const Grid g = make_grid(H, W);
-    if ((rc = graph_apply_check_workspace("dagl_graph_apply", graph_apply_workspace_bytes(B, g, total_edges, false), workspace, ws_bytes)))
-        return rc;
+    if ((rc = check_workspace("dagl_graph_apply", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, false)))) return rc;
     return launch_graph_apply((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, out, workspace);
 }
 
@@ -1847,9 +1837,7 @@ int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2
                  "dagl_graph_apply_backward: null transposed CSR (col_off, src_row, perm are required with d_b2p)");
     DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0 && ((uintptr_t)d_b2p % 16) == 0, "dagl_graph_apply_backward: maps must be 16-byte aligned");
     const Grid g = make_grid(H, W);
-    if ((rc = graph_apply_check_workspace("dagl_graph_apply_backward", graph_apply_workspace_bytes(B, g, total_edges, true), workspace,
-                                          ws_bytes)))
-        return rc;
+    if ((rc = check_workspace("dagl_graph_apply_backward", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, true)))) return rc;
     return launch_graph_apply_backward((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, d_out, col_off, src_row, perm,
                                        d_b2p, d_weight, workspace);
 }

@@ -317,6 +317,29 @@ inline Grid make_grid(int H, int W) {
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// ---- workspaces -----------------------------------------------------------------------------------------------------------------
+// A device workspace is a run of 256-byte aligned regions.  Every layout is written ONCE, as a walk of a Carver: over the caller's
+// buffer the walk hands out the regions, over a null base the same walk yields the size alone (bytes()).  Plans that keep byte
+// offsets (Plan, GraphPlan, ...) fill them from reserve() and resolve them with at<T>().
+struct Carver {
+    char* base; size_t off;
+    explicit Carver(void* ws = nullptr, size_t start = 0) : base(static_cast<char*>(ws)), off(start) {}
+    size_t reserve(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }   // the region's byte offset
+    template <class T>
+    T* take(size_t count) { const size_t o = reserve(count * sizeof(T)); return base ? reinterpret_cast<T*>(base + o) : nullptr; }
+    size_t bytes() const { return off; }
+};
+template <class T>
+inline T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
+
+// the two checks of an entry point on its workspace argument; need = 0: the alignment alone (the size is checked further on)
+inline int check_workspace(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+    DAGL_REQUIRE(ws != nullptr && ((uintptr_t)ws % 256) == 0, "%s: workspace must be 256-byte aligned", who);
+    if (ws_bytes >= need) return DAGL_OK;
+    set_error("%s: workspace %zu B < required %zu B", who, ws_bytes, need);
+    return DAGL_ERR_WORKSPACE;
+}
+
 // rows allocated for a [rows, DS] feature matrix: whole 32-row tiles plus one guard tile so that the
 // 1-KiB LDS-DMA pieces of the last tile stay in bounds.
 inline int feat_rows(int rows) { return round_up(rows, KT) + KT; }
@@ -363,26 +386,40 @@ int launch_thr_bias_heads(hipStream_t s, int heads, int imgs, const Grid& g, con
 int launch_conv_pair16_heads(hipStream_t s, int heads, int imgs, const Grid& g, const ConvHeadSet& hs, float* b2p,
                              uint16_t* b1_hi, uint16_t* b1_lo, uint32_t* clear_a, int clear_a_words, uint32_t* clear_b,
                              int clear_b_words, RangeTag range);
-int launch_prologue(hipStream_t s, int B, const Grid& g, const float* x, const float* g_w, const float* g_b,
-                    const float* th_w, const float* th_b, const float* thr_w, const float* thr_b,
-                    const float* bias_w, const float* bias_b, float* b1p /* may be null */, float* b2p, float* thr,
-                    float* bias, uint16_t* b1_hi /* optional fp16 split of b1 */, uint16_t* b1_lo,
-                    float* thr_part /* scratch [4][B][L][2] floats when thr != null */,
-                    bool borders_zero = false /* the maps' 3-pixel borders still hold the zeros of an earlier call */,
-                    bool defer_thr_reduce = false /* leave the partial sums in thr_part: launch_query_thresholds finishes them */,
-                    uint32_t* clear_a = nullptr, int clear_a_words = 0, uint32_t* clear_b = nullptr, int clear_b_words = 0
-                    /* two small per-call regions (counters, flags) cleared by the first block of the conv kernel */,
-                    RangeTag range = RangeTag(), const unsigned char* conv_w16 = nullptr /* packed g / theta weights (split-fp16 path) */,
-                    bool skip_conv = false /* the g / theta convolutions of all heads were one launch_conv_pair16_heads */,
-                    const B1Tiers* tiers = nullptr /* split-fp16 path: the coarse tier maps + the blocks' |b1| slots (see B1Tiers) */);
+// the four convolutions of one head (prologue.hip).  `conv` names the kernel of the g / theta pair:
+enum class ConvPath {
+    Fp32,             // conv_pair_kernel: fp32 maps b1p, b2p (and the fp16 pair b1_hi / b1_lo when given)
+    Split16,          // conv_pair16_kernel on the packed weights conv_w16: b2p and b1p and / or the fp16 pair (+ tiers)
+    DoneByCaller      // one launch_conv_pair16_heads (and launch_thr_bias_heads) served all heads of the caller: thr / bias reduce only
+};
+struct PrologueLaunch {
+    int B = 0; Grid g = {}; const float* x = nullptr;
+    const float *g_w = nullptr, *g_b = nullptr, *th_w = nullptr, *th_b = nullptr;
+    const float *thr_w = nullptr, *thr_b = nullptr, *bias_w = nullptr, *bias_b = nullptr;
+    ConvPath conv = ConvPath::Fp32; const unsigned char* conv_w16 = nullptr;     // Split16: packed weights (launch_pack_conv_weight16)
+    float *b1p = nullptr, *b2p = nullptr;           // padded NHWC maps (b1p may be null on the Split16 path)
+    uint16_t *b1_hi = nullptr, *b1_lo = nullptr;    // optional fp16 split of b1
+    B1Tiers tiers;                                  // Split16: the coarse tier maps + the blocks' |b1| slots (see B1Tiers)
+    float *thr = nullptr, *bias = nullptr, *thr_part = nullptr;     // [B,L] per-query heads or null: none; scratch [4][B][L][2] floats with them
+    bool borders_zero = false;                      // the maps' 3-pixel borders still hold the zeros of an earlier call
+    bool defer_thr_reduce = false;                  // leave the partial sums in thr_part: launch_query_thresholds finishes them
+    // two small per-call regions (counters, flags) cleared by the first block of the conv kernel
+    uint32_t *clear_a = nullptr, *clear_b = nullptr; int clear_a_words = 0, clear_b_words = 0; RangeTag range;
+};
+int launch_prologue(hipStream_t s, const PrologueLaunch& a);
 constexpr size_t CONV_W16_BYTES = (18 + 2) * 16 * 128 + 256;   // packed conv weights of one head + range flag
 int launch_pack_conv_weight16(hipStream_t s, const float* g_w, const float* th_w, unsigned char* img);
 int launch_zero_borders16(hipStream_t s, int B, int H, int W, uint16_t* m1, uint16_t* m2);
-int launch_project(hipStream_t s, int B, const Grid& g, int which /* bit0 keys, bit1 queries */, const float* map,
-                   const float* wp_keys, const float* bias_keys, float* feat_keys, double* colsum,
-                   const float* wp_q, const float* bias_q, float* feat_q,
-                   uint16_t* feat_keys_bf16 = nullptr, uint16_t* feat_q_bf16 = nullptr,
-                   RangeTag range = RangeTag() /* set by a non-finite feature: the call's output is NaN-filled, as the reference's is */);
+// one side (keys / queries) of a patch projection: packed weight, bias(es), fp32 feature rows out, optional bf16 copy
+template <class W, class Bias>
+struct ProjSide { const W* wp = nullptr; Bias bias = nullptr; float* feat = nullptr; uint16_t* feat_bf16 = nullptr; };
+struct ProjectLaunch {
+    int B = 0; Grid g = {}; int which = 0;          // bit 0 keys, bit 1 queries
+    const float* map = nullptr; double* colsum = nullptr;
+    ProjSide<float, const float*> keys, queries;
+    RangeTag range;                                 // set by a non-finite feature: the call's output is NaN-filled, as the reference's is
+};
+int launch_project(hipStream_t s, const ProjectLaunch& a);
 // fp16 split-operand projection (project16.hip)
 int launch_split_map(hipStream_t s, size_t n_floats, const float* src, uint16_t* hi, uint16_t* lo, RangeTag range = RangeTag());
 int launch_pack_fc_weight16(hipStream_t s, const float* w, uint16_t* wp, bool rows_order = false /* [196][tap][c] instead of [196][c][tap] */);
@@ -390,15 +427,18 @@ int launch_pack_fc_weight16(hipStream_t s, const float* w, uint16_t* wp, bool ro
 // what the streamed dense formulation (dense.hip) consumes; index 0 = keys, 1 = queries; [B, rows_alloc, 216]
 constexpr float DN_FS = 64.0f;                        // pre-scaling of the split features: 64 x = hi + lo
 struct Split16Out { uint16_t* hi[2]; uint16_t* lo[2]; int rows_alloc[2]; };
-int launch_project16(hipStream_t s, int B, const Grid& g, int which, const uint16_t* map_hi, const uint16_t* map_lo,
-                     const uint16_t* wp_keys, const float* const* bias_keys /*[heads]*/, float* feat_keys, double* colsum,
-                     float* colpart, const uint16_t* wp_q, const float* const* bias_q /*[heads]*/, float* feat_q,
-                     uint16_t* feat_keys_bf16, uint16_t* feat_q_bf16, int heads = 1, RangeTag range = RangeTag(),
-                     int q_tiled = 0 /* bf16 query copy in the screen's fragment order (ScreenArgs::q_tiled) */,
-                     const Split16Out* split = nullptr,
-                     const ThrHeadSet* thr_hs = nullptr /* with thr_part: the thr / bias heads' partial sums (thr_bias4.h) as extra blocks of this launch */,
-                     int thr_head_imgs = 0 /* heads x imgs of those heads */, float* thr_part = nullptr,
-                     const B1Tiers* tiers = nullptr /* the map's coarse tier + the conv blocks' |b1| slots: the kernel picks the tier per head */);
+struct Project16Launch {
+    int B = 0; Grid g = {}; int which = 0;          // bit 0 keys, bit 1 queries
+    const uint16_t *map_hi = nullptr, *map_lo = nullptr;
+    ProjSide<uint16_t, const float* const*> keys, queries;      // bias: [heads]
+    double* colsum = nullptr; float* colpart = nullptr; int heads = 1; RangeTag range;
+    int q_tiled = 0;                                // bf16 query copy in the screen's fragment order (ScreenArgs::q_tiled)
+    const Split16Out* split = nullptr;
+    const ThrHeadSet* thr_hs = nullptr;             // with thr_part: the thr / bias heads' partial sums (thr_bias4.h) as extra blocks of this launch
+    int thr_head_imgs = 0; float* thr_part = nullptr;           // heads x imgs of those heads
+    B1Tiers tiers;                                  // the map's coarse tier + the conv blocks' |b1| slots: the kernel picks the tier per head
+};
+int launch_project16(hipStream_t s, const Project16Launch& a);
 int launch_feat_rows_out(hipStream_t s, int B, int n, const float* feat /* [B, feat_rows(n), DS] */, float* rows_out /* [B, n, 196] */,
                          RangeTag range);            // dense copy of the feature rows; NaN when the call left the fp16 range
 int project16_key_blocks(const Grid& g);     // key blocks of project16: colpart is [B, key blocks, 224] floats

@@ -876,38 +876,29 @@ int dense_splits(int B, const Grid& g) {
     return s;
 }
 
-static size_t dn_feat16_bytes(int B, int rows) { return align_up((size_t)B * feat_rows_h(rows) * DSH * sizeof(uint16_t), 256); }
-// split value maps: whole maps + one staged row of slack (the last piece of a region may start past the map's last pixel)
-static size_t dn_map16_bytes(int B, const Grid& g) { return align_up(((size_t)B * g.Hp * g.Wp * CH + 1024) * sizeof(uint16_t), 256); }
-
-size_t dense_workspace_bytes(int B, const Grid& g) {
-    const size_t rows = (size_t)dense_splits(B, g) * B * g.L;
-    return align_up(rows * P * sizeof(float), 256) + align_up(rows * sizeof(float), 256) +
-           align_up(rows * 3 * sizeof(double), 256) + align_up(rows * sizeof(int32_t), 256) +
-           2 * dn_feat16_bytes(B, g.N) + 2 * dn_feat16_bytes(B, g.L) + 2 * dn_map16_bytes(B, g) +
-           align_up((size_t)B * g.L * sizeof(float), 256) + align_up((size_t)B * ((g.L + 63) / 64) * sizeof(int32_t), 256);
-}
-
-// carve of the dense workspace (shared by launch_dense_attend and dense_split_buffers)
-struct DnCarve { float* part_acc; float* part_m; double* part_z; int32_t* part_deg; uint16_t *xh, *xl, *qh, *ql, *vh, *vl; float* m_exact; int32_t* redo_blk; };
+// carve of the dense workspace: the one walk behind dense_workspace_bytes (null base), launch_dense_attend and dense_split_buffers
+struct DnCarve { float* part_acc; float* part_m; double* part_z; int32_t* part_deg; uint16_t *xh, *xl, *qh, *ql, *vh, *vl; float* m_exact; int32_t* redo_blk; size_t bytes; };
 static DnCarve dn_carve(void* ws, int B, const Grid& g) {
     const size_t rows = (size_t)dense_splits(B, g) * B * g.L;                // carve with the planned (upper) split count
+    const size_t feat_x = (size_t)B * feat_rows_h(g.N) * DSH, feat_q = (size_t)B * feat_rows_h(g.L) * DSH;
+    // split value maps: whole maps + one staged row of slack (the last piece of a region may start past the map's last pixel)
+    const size_t map16 = (size_t)B * g.Hp * g.Wp * CH + 1024;
+    Carver cv(ws);
     DnCarve c;
-    char* p = static_cast<char*>(ws);
-    c.part_acc = reinterpret_cast<float*>(p); p += align_up(rows * P * sizeof(float), 256);
-    c.part_m = reinterpret_cast<float*>(p); p += align_up(rows * sizeof(float), 256);
-    c.part_z = reinterpret_cast<double*>(p); p += align_up(rows * 3 * sizeof(double), 256);
-    c.part_deg = reinterpret_cast<int32_t*>(p); p += align_up(rows * sizeof(int32_t), 256);
-    c.xh = reinterpret_cast<uint16_t*>(p); p += dn_feat16_bytes(B, g.N);
-    c.xl = reinterpret_cast<uint16_t*>(p); p += dn_feat16_bytes(B, g.N);
-    c.qh = reinterpret_cast<uint16_t*>(p); p += dn_feat16_bytes(B, g.L);
-    c.ql = reinterpret_cast<uint16_t*>(p); p += dn_feat16_bytes(B, g.L);
-    c.vh = reinterpret_cast<uint16_t*>(p); p += dn_map16_bytes(B, g);
-    c.vl = reinterpret_cast<uint16_t*>(p); p += dn_map16_bytes(B, g);
-    c.m_exact = reinterpret_cast<float*>(p); p += align_up((size_t)B * g.L * sizeof(float), 256);
-    c.redo_blk = reinterpret_cast<int32_t*>(p);
+    c.part_acc = cv.take<float>(rows * P);
+    c.part_m = cv.take<float>(rows);
+    c.part_z = cv.take<double>(rows * 3);
+    c.part_deg = cv.take<int32_t>(rows);
+    c.xh = cv.take<uint16_t>(feat_x); c.xl = cv.take<uint16_t>(feat_x);
+    c.qh = cv.take<uint16_t>(feat_q); c.ql = cv.take<uint16_t>(feat_q);
+    c.vh = cv.take<uint16_t>(map16); c.vl = cv.take<uint16_t>(map16);
+    c.m_exact = cv.take<float>((size_t)B * g.L);
+    c.redo_blk = cv.take<int32_t>((size_t)B * ((g.L + 63) / 64));
+    c.bytes = cv.bytes();
     return c;
 }
+
+size_t dense_workspace_bytes(int B, const Grid& g) { return dn_carve(nullptr, B, g).bytes; }
 
 Split16Out dense_split_buffers(void* dense_ws, int B, const Grid& g) {
     const DnCarve c = dn_carve(dense_ws, B, g);

@@ -53,25 +53,24 @@ static DtPlan dt_plan(int B, const Grid& g, bool backward) {
         long long bc = (long long)(DT_CHUNK_FLOATS / ((size_t)p.Lc * p.ldn));
         p.Bc = (int)(bc < 1 ? 1 : (bc > B ? B : bc));
     }
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
+    Carver cv;
     const size_t chunk = (size_t)p.Bc * p.Lc * p.ldn * sizeof(float);
-    p.o_sbuf = carve(chunk);
-    p.o_abuf = backward ? carve(chunk) : 0;
-    p.o_vrows = carve((size_t)p.Bc * g.N * P * sizeof(float));
-    p.o_dvrows = backward ? carve((size_t)p.Bc * g.N * P * sizeof(float)) : 0;
-    p.o_dagg = backward ? carve((size_t)B * g.L * P * sizeof(float)) : 0;
-    p.o_agg = backward ? 0 : carve((size_t)B * g.L * P * sizeof(float));
-    p.o_b2p = carve((size_t)B * g.Hp * g.Wp * CH * sizeof(float));
-    p.o_colsum = carve((size_t)B * DS * sizeof(double));
-    p.o_mt = carve((size_t)B * g.L * sizeof(float));
-    p.o_dmu = carve((size_t)B * g.L * sizeof(float));
-    p.o_dxbar = carve((size_t)B * D * sizeof(float));
-    p.o_deg = carve((size_t)B * g.L * sizeof(int32_t));
-    p.o_rowsum = carve((size_t)B * g.L * sizeof(float));
-    p.o_sel = carve((size_t)B * g.L * 2 * sizeof(int32_t));      // wide top-k modes: (sort key of the k-th best score, last key index taken at it)
-    p.o_lse = carve((size_t)B * g.L * 2 * sizeof(float));        // (their entry points keep the softmax statistics and the row means here)
-    p.o_mu = carve((size_t)B * g.L * sizeof(float));
+    p.o_sbuf = cv.reserve(chunk);
+    p.o_abuf = backward ? cv.reserve(chunk) : 0;
+    p.o_vrows = cv.reserve((size_t)p.Bc * g.N * P * sizeof(float));
+    p.o_dvrows = backward ? cv.reserve((size_t)p.Bc * g.N * P * sizeof(float)) : 0;
+    p.o_dagg = backward ? cv.reserve((size_t)B * g.L * P * sizeof(float)) : 0;
+    p.o_agg = backward ? 0 : cv.reserve((size_t)B * g.L * P * sizeof(float));
+    p.o_b2p = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(float));
+    p.o_colsum = cv.reserve((size_t)B * DS * sizeof(double));
+    p.o_mt = cv.reserve((size_t)B * g.L * sizeof(float));
+    p.o_dmu = cv.reserve((size_t)B * g.L * sizeof(float));
+    p.o_dxbar = cv.reserve((size_t)B * D * sizeof(float));
+    p.o_deg = cv.reserve((size_t)B * g.L * sizeof(int32_t));
+    p.o_rowsum = cv.reserve((size_t)B * g.L * sizeof(float));
+    p.o_sel = cv.reserve((size_t)B * g.L * 2 * sizeof(int32_t));      // wide top-k modes: (sort key of the k-th best score, last key index taken at it)
+    p.o_lse = cv.reserve((size_t)B * g.L * 2 * sizeof(float));        // (their entry points keep the softmax statistics and the row means here)
+    p.o_mu = cv.reserve((size_t)B * g.L * sizeof(float));
     p.h16 = backward && p.n_chunks == 1;
     p.Lp = (g.L + 31) / 32 * 32;
     p.kslices = 1;
@@ -87,20 +86,18 @@ static DtPlan dt_plan(int B, const Grid& g, bool backward) {
         p.dgk_h = bc * g.L * DT_PK; p.dgt_h = bc * P * p.ldl; p.vk_h = bc * g.N * DT_PK;
         p.xk_h = bc * g.N * DT_DK; p.xt_h = bc * D * p.ldk; p.wqk_h = bc * g.L * DT_DK; p.wqt_h = bc * D * p.ldl;
         p.dsk_h = bc * p.Lc * p.ldk; p.dst_h = bc * g.N * p.ldl; p.at_h = bc * g.N * p.ldl;
-        p.o_words = carve(256);
-        p.o_dgk = carve(2 * p.dgk_h * 2); p.o_dgt = carve(2 * p.dgt_h * 2); p.o_vk = carve(2 * p.vk_h * 2);
-        p.o_xk = carve(2 * p.xk_h * 2); p.o_xt = carve(2 * p.xt_h * 2); p.o_wqk = carve(2 * p.wqk_h * 2); p.o_wqt = carve(2 * p.wqt_h * 2);
-        p.o_dsk = carve(2 * p.dsk_h * 2); p.o_dst = carve(2 * p.dst_h * 2); p.o_at = carve(2 * p.at_h * 2);
-        p.o_part = carve((size_t)p.kslices * bc * g.L * D * sizeof(float));
+        p.o_words = cv.reserve(256);
+        p.o_dgk = cv.reserve(2 * p.dgk_h * 2); p.o_dgt = cv.reserve(2 * p.dgt_h * 2); p.o_vk = cv.reserve(2 * p.vk_h * 2);
+        p.o_xk = cv.reserve(2 * p.xk_h * 2); p.o_xt = cv.reserve(2 * p.xt_h * 2); p.o_wqk = cv.reserve(2 * p.wqk_h * 2); p.o_wqt = cv.reserve(2 * p.wqt_h * 2);
+        p.o_dsk = cv.reserve(2 * p.dsk_h * 2); p.o_dst = cv.reserve(2 * p.dst_h * 2); p.o_at = cv.reserve(2 * p.at_h * 2);
+        p.o_part = cv.reserve((size_t)p.kslices * bc * g.L * D * sizeof(float));
     }
-    p.o_end = off;
+    p.o_end = cv.bytes();
     return p;
 }
 
 size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward) { return dt_plan(B, g, backward).o_end; }
 
-template <class T>
-static T* dt_at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
 // mu[b,l] = Wq_l . colsum / N (fp64 dot, as query_thresholds_kernel), mt = mu * thr: one wave per query, dense rows
 __global__ __launch_bounds__(256) void dt_thresholds_kernel(int L, int N, const float* __restrict__ wq_rows,
@@ -406,11 +403,11 @@ static Gemm32 dt_gemm(int M, int N, int K, int batch, const float* A, long long 
 static int dt_prepare(hipStream_t s, int B, const Grid& g, const DtPlan& p, void* ws, const float* wq_rows, const float* x_rows,
                       const float* b2, const float* thr, float* mu) {
     int rc;
-    if ((rc = launch_pad_nhwc(s, B, g.H, g.W, b2, dt_at<float>(ws, p.o_b2p)))) return rc;
+    if ((rc = launch_pad_nhwc(s, B, g.H, g.W, b2, at<float>(ws, p.o_b2p)))) return rc;
     if (thr == nullptr) return DAGL_OK;                  // (the fixed-k mode has no threshold heads)
-    if ((rc = launch_colsum_rows(s, B, g.N, x_rows, dt_at<double>(ws, p.o_colsum)))) return rc;
+    if ((rc = launch_colsum_rows(s, B, g.N, x_rows, at<double>(ws, p.o_colsum)))) return rc;
     hipLaunchKernelGGL(dt_thresholds_kernel, dim3((g.L + 3) / 4, B), dim3(256), 0, s, g.L, g.N, wq_rows,
-                       dt_at<double>(ws, p.o_colsum), thr, dt_at<float>(ws, p.o_mt), mu);
+                       at<double>(ws, p.o_colsum), thr, at<float>(ws, p.o_mt), mu);
     DAGL_LAUNCH_CHECK("dt_thresholds_kernel");
     return DAGL_OK;
 }
@@ -419,19 +416,19 @@ int launch_dense_train_forward(hipStream_t s, int B, const Grid& g, const float*
                                const float* thr, const float* bias, float* out, float* lse, float* mu, void* ws, size_t ws_bytes,
                                int64_t* stats_dev, int mode, int k) {
     const DtPlan p = dt_plan(B, g, false);
-    if (lse == nullptr) lse = dt_at<float>(ws, p.o_lse);
-    if (mu == nullptr) mu = dt_at<float>(ws, p.o_mu);
-    int32_t* sel = dt_at<int32_t>(ws, p.o_sel);
+    if (lse == nullptr) lse = at<float>(ws, p.o_lse);
+    if (mu == nullptr) mu = at<float>(ws, p.o_mu);
+    int32_t* sel = at<int32_t>(ws, p.o_sel);
     if (ws_bytes < p.o_end) { set_error("dense forward: workspace %zu B < required %zu B", ws_bytes, p.o_end); return DAGL_ERR_WORKSPACE; }
     int rc;
     if ((rc = dt_prepare(s, B, g, p, ws, wq_rows, x_rows, b2, thr, mu))) return rc;
-    float* sbuf = dt_at<float>(ws, p.o_sbuf);
-    float* vrows = dt_at<float>(ws, p.o_vrows);
-    float* agg = dt_at<float>(ws, p.o_agg);
-    const float* b2p = dt_at<float>(ws, p.o_b2p);
-    const float* mt = dt_at<float>(ws, p.o_mt);
-    int32_t* deg = dt_at<int32_t>(ws, p.o_deg);
-    float* rowsum = dt_at<float>(ws, p.o_rowsum);
+    float* sbuf = at<float>(ws, p.o_sbuf);
+    float* vrows = at<float>(ws, p.o_vrows);
+    float* agg = at<float>(ws, p.o_agg);
+    const float* b2p = at<float>(ws, p.o_b2p);
+    const float* mt = at<float>(ws, p.o_mt);
+    int32_t* deg = at<int32_t>(ws, p.o_deg);
+    float* rowsum = at<float>(ws, p.o_rowsum);
     for (int b0 = 0; b0 < B; b0 += p.Bc) {
         const int nb = (B - b0 < p.Bc) ? B - b0 : p.Bc;
         if ((rc = launch_unfold_values(s, nb, g, b2p + (size_t)b0 * g.Hp * g.Wp * CH, vrows))) return rc;
@@ -582,17 +579,16 @@ static int dt_backward_group16(hipStream_t s, const Grid& g, const DtPlan& p, vo
                                const float* x_rows, const float* thr, const float* bias, const float* lse, const float* mu,
                                float* dwq_rows, float* dx_rows, float* dthr, float* dbias) {
     int rc;
-    unsigned* words = dt_at<unsigned>(ws, p.o_words);          // 0 d agg, 1 values, 2 X, 3 Wq, 4 d S
-    float* sbuf = dt_at<float>(ws, p.o_sbuf);
-    float* abuf = dt_at<float>(ws, p.o_abuf);
-    float* dvrows = dt_at<float>(ws, p.o_dvrows);
-    const float* dagg = dt_at<float>(ws, p.o_dagg) + (size_t)b0 * g.L * P;
-    const float* b2p = dt_at<float>(ws, p.o_b2p) + (size_t)b0 * g.Hp * g.Wp * CH;
-    const float* mt = dt_at<float>(ws, p.o_mt);
-    float* dmu = dt_at<float>(ws, p.o_dmu);
+    unsigned* words = at<unsigned>(ws, p.o_words);          // 0 d agg, 1 values, 2 X, 3 Wq, 4 d S
+    float* sbuf = at<float>(ws, p.o_sbuf);
+    float* abuf = at<float>(ws, p.o_abuf);
+    float* dvrows = at<float>(ws, p.o_dvrows);
+    const float* dagg = at<float>(ws, p.o_dagg) + (size_t)b0 * g.L * P;
+    const float* b2p = at<float>(ws, p.o_b2p) + (size_t)b0 * g.Hp * g.Wp * CH;
+    const float* mt = at<float>(ws, p.o_mt);
+    float* dmu = at<float>(ws, p.o_dmu);
     const float* wq = wq_rows + (size_t)b0 * g.L * D;
     const float* xr = x_rows + (size_t)b0 * g.N * D;
-    auto H = [&](size_t o) { return dt_at<unsigned short>(ws, o); };
     const int L = g.L, N = g.N, Lp = p.Lp;
     const long long ldn = p.ldn, ldl = p.ldl, ldk = p.ldk;
     DAGL_HIP_TRY(hipMemsetAsync(words, 0, 256, s));
@@ -601,40 +597,40 @@ static int dt_backward_group16(hipStream_t s, const Grid& g, const DtPlan& p, vo
     if ((rc = launch_absmax(s, (size_t)nb * N * D, xr, words + 2))) return rc;
     if ((rc = launch_absmax(s, (size_t)nb * L * D, wq, words + 3))) return rc;
     // operand copies that do not depend on the softmax
-    if ((rc = dt_split_rows(s, (size_t)nb * L, P, P, DT_PK, DT_PK, dagg, words + 0, 1.f, H(p.o_dgk), p.dgk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, P, P, (long long)L * P, Lp, ldl, dagg, words + 0, 1.f, H(p.o_dgt), p.dgt_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * L, P, P, DT_PK, DT_PK, dagg, words + 0, 1.f, at<unsigned short>(ws, p.o_dgk), p.dgk_h))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, P, P, (long long)L * P, Lp, ldl, dagg, words + 0, 1.f, at<unsigned short>(ws, p.o_dgt), p.dgt_h))) return rc;
     {
         const size_t total = (size_t)nb * N * 50;
         hipLaunchKernelGGL(dt_unfold_values_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g.H, g.W, total, b2p,
-                           words + 1, H(p.o_vk), H(p.o_vk) + p.vk_h);
+                           words + 1, at<unsigned short>(ws, p.o_vk), at<unsigned short>(ws, p.o_vk) + p.vk_h);
         DAGL_LAUNCH_CHECK("dt_unfold_values_split_kernel");
     }
-    if ((rc = dt_split_rows(s, (size_t)nb * N, D, D, DT_DK, DT_DK, xr, words + 2, 1.f, H(p.o_xk), p.xk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, N, D, D, (long long)N * D, p.nk, ldk, xr, words + 2, 1.f, H(p.o_xt), p.xt_h))) return rc;
-    if ((rc = dt_split_rows(s, (size_t)nb * L, D, D, DT_DK, DT_DK, wq, words + 3, 1.f, H(p.o_wqk), p.wqk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, D, D, (long long)L * D, Lp, ldl, wq, words + 3, 1.f, H(p.o_wqt), p.wqt_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * N, D, D, DT_DK, DT_DK, xr, words + 2, 1.f, at<unsigned short>(ws, p.o_xk), p.xk_h))) return rc;
+    if ((rc = dt_split_transpose(s, nb, N, D, D, (long long)N * D, p.nk, ldk, xr, words + 2, 1.f, at<unsigned short>(ws, p.o_xt), p.xt_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * L, D, D, DT_DK, DT_DK, wq, words + 3, 1.f, at<unsigned short>(ws, p.o_wqk), p.wqk_h))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, D, D, (long long)L * D, Lp, ldl, wq, words + 3, 1.f, at<unsigned short>(ws, p.o_wqt), p.wqt_h))) return rc;
     const long long sS = (long long)p.Lc * ldn;
     // d A = d agg V^T ; S = Wq X^T
-    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_PK, nb, H(p.o_dgk), p.dgk_h, DT_PK, (long long)L * DT_PK, H(p.o_vk), p.vk_h, DT_PK,
+    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_PK, nb, at<unsigned short>(ws, p.o_dgk), p.dgk_h, DT_PK, (long long)L * DT_PK, at<unsigned short>(ws, p.o_vk), p.vk_h, DT_PK,
                                           (long long)N * DT_PK, abuf, ldn, sS, words + 0, words + 1, 1.f)))) return rc;
-    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_DK, nb, H(p.o_wqk), p.wqk_h, DT_DK, (long long)L * DT_DK, H(p.o_xk), p.xk_h, DT_DK,
+    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_DK, nb, at<unsigned short>(ws, p.o_wqk), p.wqk_h, DT_DK, (long long)L * DT_DK, at<unsigned short>(ws, p.o_xk), p.xk_h, DT_DK,
                                           (long long)N * DT_DK, sbuf, ldn, sS, words + 3, words + 2, 1.f)))) return rc;
     if ((rc = launch_dense_softmax_bwd(s, L, nb, N, ldn, L, 0, p.Lc, sbuf, abuf, mt, bias, lse, mu, thr, dthr, dbias, dmu, b0, words + 4))) return rc;
     // d S by rows and transposed, A transposed
-    if ((rc = dt_split_rows(s, (size_t)nb * p.Lc, (int)ldn, ldn, p.nk, ldk, sbuf, words + 4, 1.f, H(p.o_dsk), p.dsk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, sbuf, words + 4, 1.f, H(p.o_dst), p.dst_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, abuf, nullptr, 8192.f, H(p.o_at), p.at_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * p.Lc, (int)ldn, ldn, p.nk, ldk, sbuf, words + 4, 1.f, at<unsigned short>(ws, p.o_dsk), p.dsk_h))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, sbuf, words + 4, 1.f, at<unsigned short>(ws, p.o_dst), p.dst_h))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, abuf, nullptr, 8192.f, at<unsigned short>(ws, p.o_at), p.at_h))) return rc;
     // d Wq = d S X (split over the keys)
     {
-        Gemm16s q = dt_gemm16(L, D, p.nk / p.kslices, nb, H(p.o_dsk), p.dsk_h, ldk, (long long)p.Lc * ldk, H(p.o_xt), p.xt_h, ldk, (long long)D * ldk,
+        Gemm16s q = dt_gemm16(L, D, p.nk / p.kslices, nb, at<unsigned short>(ws, p.o_dsk), p.dsk_h, ldk, (long long)p.Lc * ldk, at<unsigned short>(ws, p.o_xt), p.xt_h, ldk, (long long)D * ldk,
                               dwq_rows + (size_t)b0 * L * D, D, (long long)L * D, words + 4, words + 2, 1.f);
-        q.slices = p.kslices; q.part = dt_at<float>(ws, p.o_part);
+        q.slices = p.kslices; q.part = at<float>(ws, p.o_part);
         if ((rc = launch_gemm16s(s, q))) return rc;
     }
     // d X = d S^T Wq ; d V = A^T d agg
-    if ((rc = launch_gemm16s(s, dt_gemm16(N, D, Lp, nb, H(p.o_dst), p.dst_h, ldl, (long long)N * ldl, H(p.o_wqt), p.wqt_h, ldl,
+    if ((rc = launch_gemm16s(s, dt_gemm16(N, D, Lp, nb, at<unsigned short>(ws, p.o_dst), p.dst_h, ldl, (long long)N * ldl, at<unsigned short>(ws, p.o_wqt), p.wqt_h, ldl,
                                           (long long)D * ldl, dx_rows + (size_t)b0 * N * D, D, (long long)N * D, words + 4, words + 3, 1.f)))) return rc;
-    if ((rc = launch_gemm16s(s, dt_gemm16(N, P, Lp, nb, H(p.o_at), p.at_h, ldl, (long long)N * ldl, H(p.o_dgt), p.dgt_h, ldl,
+    if ((rc = launch_gemm16s(s, dt_gemm16(N, P, Lp, nb, at<unsigned short>(ws, p.o_at), p.at_h, ldl, (long long)N * ldl, at<unsigned short>(ws, p.o_dgt), p.dgt_h, ldl,
                                           (long long)P * ldl, dvrows, P, (long long)N * P, nullptr, words + 0, 1.f / 8192.f)))) return rc;
     return DAGL_OK;
 }
@@ -647,22 +643,22 @@ int launch_dense_train_backward(hipStream_t s, int B, const Grid& g, const float
     // the wide top-k modes re-select from the recomputed scores: the fp32 product of the forward, bit for bit (a split-fp16 S could
     // order two near-equal scores the other way round)
     const bool h16 = p.h16 && !fp32_products && mode == DAGL_MODE_ADAPTIVE;
-    int32_t* sel = dt_at<int32_t>(ws, p.o_sel);
+    int32_t* sel = at<int32_t>(ws, p.o_sel);
     if (ws_bytes < p.o_end) { set_error("dense backward: workspace %zu B < required %zu B", ws_bytes, p.o_end); return DAGL_ERR_WORKSPACE; }
     int rc;
-    float* mu = dt_at<float>(ws, p.o_rowsum);                    // recomputed with the thresholds (same values as the forward's)
+    float* mu = at<float>(ws, p.o_rowsum);                    // recomputed with the thresholds (same values as the forward's)
     if ((rc = dt_prepare(s, B, g, p, ws, wq_rows, x_rows, b2, thr, mu))) return rc;
     (void)mu_saved;
-    float* sbuf = dt_at<float>(ws, p.o_sbuf);
-    float* abuf = dt_at<float>(ws, p.o_abuf);
-    float* vrows = dt_at<float>(ws, p.o_vrows);
-    float* dvrows = dt_at<float>(ws, p.o_dvrows);
-    float* dagg = dt_at<float>(ws, p.o_dagg);
-    const float* b2p = dt_at<float>(ws, p.o_b2p);
-    const float* mt = dt_at<float>(ws, p.o_mt);
-    float* dmu = dt_at<float>(ws, p.o_dmu);
-    float* dxbar = dt_at<float>(ws, p.o_dxbar);
-    const double* colsum = dt_at<double>(ws, p.o_colsum);
+    float* sbuf = at<float>(ws, p.o_sbuf);
+    float* abuf = at<float>(ws, p.o_abuf);
+    float* vrows = at<float>(ws, p.o_vrows);
+    float* dvrows = at<float>(ws, p.o_dvrows);
+    float* dagg = at<float>(ws, p.o_dagg);
+    const float* b2p = at<float>(ws, p.o_b2p);
+    const float* mt = at<float>(ws, p.o_mt);
+    float* dmu = at<float>(ws, p.o_dmu);
+    float* dxbar = at<float>(ws, p.o_dxbar);
+    const double* colsum = at<double>(ws, p.o_colsum);
     if ((rc = launch_unfold_dout(s, B, g, dout, dagg))) return rc;
     for (int b0 = 0; b0 < B; b0 += p.Bc) {
         const int nb = (B - b0 < p.Bc) ? B - b0 : p.Bc;

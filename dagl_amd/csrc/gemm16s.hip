@@ -571,8 +571,6 @@ struct FcgPlan {
     int stat_blocks;
 };
 
-static size_t fcg_carve(size_t& off, size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
-
 // d rows folded inside the product (Gemm16s::fold_part): stride-1 patches whose row tiles of 128 hold whole image rows or one 128-patch
 // segment of a row
 static bool fcg_fold_ok(int stride, int ow) { return stride == 1 && ow >= 16 && ((ow % 128) == 0 || (128 % ow) == 0); }
@@ -609,20 +607,20 @@ static FcgPlan fcg_plan(size_t n, int ow_fold = 0, int im_rps = 0, int im_ow = 0
     if (im_rps > 0) { ks = (size_t)im_rps * im_ow; slices = (int)(n / ks); }      // (whole image rows: n = slices * ks exactly)
     p.slices = slices; p.k_slice = ks; p.n_pad = (size_t)slices * ks;
     if (p.n_pad % 128) p.n_pad = (p.n_pad + 127) / 128 * 128;          // (the transposing producers work in tiles of 128 patches)
-    size_t off = 0;
-    p.o_word = fcg_carve(off, 256);
-    p.o_zk_hi = fcg_carve(off, p.n_pad * FCG_OP * 2); p.o_zk_lo = fcg_carve(off, p.n_pad * FCG_OP * 2);
-    p.o_zt_hi = fcg_carve(off, (size_t)FCG_OM * (p.n_pad + 64) * 2); p.o_zt_lo = fcg_carve(off, (size_t)FCG_OM * (p.n_pad + 64) * 2);
-    p.o_rt_hi = fcg_carve(off, (size_t)FCG_P * p.n_pad * 2); p.o_rt_lo = fcg_carve(off, (size_t)FCG_P * p.n_pad * 2);
-    p.o_wt_hi = fcg_carve(off, (size_t)FCG_PP * FCG_OP * 2); p.o_wt_lo = fcg_carve(off, (size_t)FCG_PP * FCG_OP * 2);
-    p.o_part = fcg_carve(off, (size_t)slices * FCG_O * FCG_P * sizeof(float));
-    p.o_dz = fcg_carve(off, n * FCG_O * sizeof(float));
+    Carver cv;
+    p.o_word = cv.reserve(256);
+    p.o_zk_hi = cv.reserve(p.n_pad * FCG_OP * 2); p.o_zk_lo = cv.reserve(p.n_pad * FCG_OP * 2);
+    p.o_zt_hi = cv.reserve((size_t)FCG_OM * (p.n_pad + 64) * 2); p.o_zt_lo = cv.reserve((size_t)FCG_OM * (p.n_pad + 64) * 2);
+    p.o_rt_hi = cv.reserve((size_t)FCG_P * p.n_pad * 2); p.o_rt_lo = cv.reserve((size_t)FCG_P * p.n_pad * 2);
+    p.o_wt_hi = cv.reserve((size_t)FCG_PP * FCG_OP * 2); p.o_wt_lo = cv.reserve((size_t)FCG_PP * FCG_OP * 2);
+    p.o_part = cv.reserve((size_t)slices * FCG_O * FCG_P * sizeof(float));
+    p.o_dz = cv.reserve(n * FCG_O * sizeof(float));
     p.stat_blocks = (int)((n + FCG_SROWS - 1) / FCG_SROWS);
-    p.o_csum = fcg_carve(off, (size_t)p.stat_blocks * FCG_O * sizeof(double));
-    p.o_fold = off;
+    p.o_csum = cv.reserve((size_t)p.stat_blocks * FCG_O * sizeof(double));
+    p.o_fold = cv.bytes();
     if (p.fold_seg > 0)       // [row tiles][7 kh][rows of a tile][seg + 6][16] partial rows
-        p.o_fold = fcg_carve(off, (p.n_pad / 128) * KS * (size_t)p.fold_rows * (p.fold_seg + KS - 1) * CH * sizeof(float));
-    p.o_end = off;
+        p.o_fold = cv.reserve((p.n_pad / 128) * KS * (size_t)p.fold_rows * (p.fold_seg + KS - 1) * CH * sizeof(float));
+    p.o_end = cv.bytes();
     return p;
 }
 
@@ -668,55 +666,54 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
     const int im_rps = d_w ? fcg_implicit_rows(B, stride, oy, ox, oh, ow, Hp, Wp) : 0;
     const FcgPlan p = fcg_plan(n, d_map ? ow : 0, im_rps, ow);
     DAGL_REQUIRE(scratch_bytes >= p.o_end, "dagl_fc_grad16: scratch %zu B, need %zu B", scratch_bytes, p.o_end);
-    char* ws = static_cast<char*>(scratch);
-    unsigned* word = reinterpret_cast<unsigned*>(ws + p.o_word);
-    auto H = [&](size_t o) { return reinterpret_cast<unsigned short*>(ws + o); };
+    void* ws = scratch;
+    unsigned* word = at<unsigned>(ws, p.o_word);
     DAGL_HIP_TRY(hipMemsetAsync(word, 0, 256, s));
     // one pass over the gradient: ReLU backward (y given), largest magnitude, column sums
-    const float* dz = y ? reinterpret_cast<const float*>(ws + p.o_dz) : dy;
+    const float* dz = y ? at<const float>(ws, p.o_dz) : dy;
     {
-        double* csum = reinterpret_cast<double*>(ws + p.o_csum);
+        double* csum = at<double>(ws, p.o_csum);
         hipLaunchKernelGGL(fcg_relu_stats_kernel, dim3(p.stat_blocks), dim3(256), 0, s, n, reinterpret_cast<const float4*>(y),
-                           reinterpret_cast<const float4*>(dy), reinterpret_cast<float4*>(ws + p.o_dz), csum, word);
+                           reinterpret_cast<const float4*>(dy), at<float4>(ws, p.o_dz), csum, word);
         DAGL_LAUNCH_CHECK("fcg_relu_stats_kernel");
         if (d_b) { const int rc = launch_col_sum_final(s, p.stat_blocks, FCG_O, csum, d_b); if (rc) return rc; }
     }
     const bool merged_split = (d_rows || d_map) && d_w;          // one pass over d Z writes both of its split copies
     if (merged_split) {
         hipLaunchKernelGGL(fcg_split_transpose_kernel, dim3((unsigned)(p.n_pad / 128), FCG_OM / 32), dim3(256), 0, s, n, p.n_pad, p.n_pad + 64, dz,
-                           word, H(p.o_zt_hi), H(p.o_zt_lo), H(p.o_zk_hi), H(p.o_zk_lo));
+                           word, at<unsigned short>(ws, p.o_zt_hi), at<unsigned short>(ws, p.o_zt_lo), at<unsigned short>(ws, p.o_zk_hi), at<unsigned short>(ws, p.o_zk_lo));
         DAGL_LAUNCH_CHECK("fcg_split_transpose_kernel");
     }
     if (d_rows || d_map) {
         const size_t items = p.n_pad * (FCG_OP / 8);
         if (!merged_split) {
         hipLaunchKernelGGL(fcg_split_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, n, p.n_pad, dz, word,
-                           H(p.o_zk_hi), H(p.o_zk_lo));
+                           at<unsigned short>(ws, p.o_zk_hi), at<unsigned short>(ws, p.o_zk_lo));
         DAGL_LAUNCH_CHECK("fcg_split_rows_kernel");
         }
-        hipLaunchKernelGGL(fcg_weight_transpose_kernel, dim3((FCG_PP * FCG_OP + 255) / 256), dim3(256), 0, s, w_rows, H(p.o_wt_hi),
-                           H(p.o_wt_lo), d_map ? 1 : 0);
+        hipLaunchKernelGGL(fcg_weight_transpose_kernel, dim3((FCG_PP * FCG_OP + 255) / 256), dim3(256), 0, s, w_rows, at<unsigned short>(ws, p.o_wt_hi),
+                           at<unsigned short>(ws, p.o_wt_lo), d_map ? 1 : 0);
         DAGL_LAUNCH_CHECK("fcg_weight_transpose_kernel");
         Gemm16s g;
         g.M = (int)n; g.N = d_map ? FCG_PP : FCG_P; g.K = FCG_OP;
-        g.a_hi = H(p.o_zk_hi); g.a_lo = H(p.o_zk_lo); g.lda = FCG_OP; g.a_rows = (int)p.n_pad;
-        g.b_hi = H(p.o_wt_hi); g.b_lo = H(p.o_wt_lo); g.ldb = FCG_OP; g.b_rows = FCG_PP;
-        g.C = d_map ? reinterpret_cast<float*>(ws + p.o_fold) : d_rows;
+        g.a_hi = at<unsigned short>(ws, p.o_zk_hi); g.a_lo = at<unsigned short>(ws, p.o_zk_lo); g.lda = FCG_OP; g.a_rows = (int)p.n_pad;
+        g.b_hi = at<unsigned short>(ws, p.o_wt_hi); g.b_lo = at<unsigned short>(ws, p.o_wt_lo); g.ldb = FCG_OP; g.b_rows = FCG_PP;
+        g.C = d_map ? at<float>(ws, p.o_fold) : d_rows;
         g.ldc = FCG_P; g.part = nullptr; g.slices = 1; g.scale_word = word; g.alpha0 = 1.0f / FCG_WS;
-        if (d_map) { g.fold_part = reinterpret_cast<float*>(ws + p.o_fold); g.fold_seg = p.fold_seg; g.fold_rows = p.fold_rows; }
+        if (d_map) { g.fold_part = at<float>(ws, p.o_fold); g.fold_seg = p.fold_seg; g.fold_rows = p.fold_rows; }
         const int rc = launch_gemm16s(s, g);
         if (rc) return rc;
         if (d_map) {
             const size_t nt = (size_t)Hp * Wp * 4;
             hipLaunchKernelGGL(fcg_fold_kh_kernel, dim3((unsigned)((nt + 255) / 256), B), dim3(256), 0, s, Hp, Wp, oy, ox, oh, ow, p.fold_seg,
-                               p.fold_rows, reinterpret_cast<const float4*>(ws + p.o_fold), reinterpret_cast<float4*>(d_map));
+                               p.fold_rows, at<const float4>(ws, p.o_fold), reinterpret_cast<float4*>(d_map));
             DAGL_LAUNCH_CHECK("fcg_fold_kh_kernel");
         }
     }
     if (d_w) {
         if (!merged_split) {
         hipLaunchKernelGGL(fcg_split_transpose_kernel, dim3((unsigned)(p.n_pad / 128), FCG_OM / 32), dim3(256), 0, s, n, p.n_pad, p.n_pad + 64, dz,
-                           word, H(p.o_zt_hi), H(p.o_zt_lo), (unsigned short*)nullptr, (unsigned short*)nullptr);
+                           word, at<unsigned short>(ws, p.o_zt_hi), at<unsigned short>(ws, p.o_zt_lo), (unsigned short*)nullptr, (unsigned short*)nullptr);
         DAGL_LAUNCH_CHECK("fcg_split_transpose_kernel");
         }
         int logw = 0;
@@ -726,19 +723,19 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
             // (round 6) no transposed patch rows (470 MB at [8, 128, 128]): seven shifted copies of the map's planes (61 MB), which the
             // product addresses by (kw, c, row + kh, px)
             hipLaunchKernelGGL(fcg_shift_planes_kernel, dim3((unsigned)(B * Hp)), dim3(256), (size_t)Wp * 17 * sizeof(float), s, Hp, Wp, ow, plane,
-                               map_nhwc, H(p.o_rt_hi), H(p.o_rt_lo));
+                               map_nhwc, at<unsigned short>(ws, p.o_rt_hi), at<unsigned short>(ws, p.o_rt_lo));
             DAGL_LAUNCH_CHECK("fcg_shift_planes_kernel");
         } else {
         hipLaunchKernelGGL(fcg_unfold_transpose_kernel, dim3((unsigned)(p.n_pad / 128), KS * KS), dim3(256), 0, s, Hp, Wp, stride, oy,
-                           ox, oh, ow, n, p.n_pad, map_nhwc, H(p.o_rt_hi), H(p.o_rt_lo));
+                           ox, oh, ow, n, p.n_pad, map_nhwc, at<unsigned short>(ws, p.o_rt_hi), at<unsigned short>(ws, p.o_rt_lo));
         DAGL_LAUNCH_CHECK("fcg_unfold_transpose_kernel");
         }
         // (rows 784..895 of the last N tile do not exist: its loads are clamped to row 783, their products are never stored)
         Gemm16s g;
         g.M = FCG_O; g.N = FCG_P; g.K = (int)p.k_slice;
-        g.a_hi = H(p.o_zt_hi); g.a_lo = H(p.o_zt_lo); g.lda = (long long)p.n_pad + 64; g.a_rows = FCG_OM;
-        g.b_hi = H(p.o_rt_hi); g.b_lo = H(p.o_rt_lo); g.ldb = (long long)p.n_pad; g.b_rows = FCG_P;
-        g.C = d_w; g.ldc = FCG_P; g.part = reinterpret_cast<float*>(ws + p.o_part); g.slices = p.slices; g.scale_word = word;
+        g.a_hi = at<unsigned short>(ws, p.o_zt_hi); g.a_lo = at<unsigned short>(ws, p.o_zt_lo); g.lda = (long long)p.n_pad + 64; g.a_rows = FCG_OM;
+        g.b_hi = at<unsigned short>(ws, p.o_rt_hi); g.b_lo = at<unsigned short>(ws, p.o_rt_lo); g.ldb = (long long)p.n_pad; g.b_rows = FCG_P;
+        g.C = d_w; g.ldc = FCG_P; g.part = at<float>(ws, p.o_part); g.slices = p.slices; g.scale_word = word;
         g.alpha0 = 1.0f / FCG_XS;
         if (p.im_rps > 0) { g.b_implicit = 1; g.im_logw = logw; g.im_H = oh; g.im_Hp = Hp; g.im_plane = plane; }
         const int rc = launch_gemm16s(s, g);

@@ -71,32 +71,31 @@ struct GenPlan {
 };
 inline GenPlan gen_plan(const GenGeom& g) {
     GenPlan p{};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    Carver cv;
     const size_t B = g.B, HW = (size_t)g.H * g.W, pix = (size_t)g.Hp * g.Wp;
-    p.o_xp = carve(B * pix * g.Cin * 4);
-    p.o_wgt = carve((size_t)2 * g.C * 9 * g.Cin * 4);
-    p.o_bgt = carve((size_t)2 * g.C * 4);
-    p.o_wtb = carve((size_t)2 * g.ks * g.ks * g.Cin * 4);
-    p.o_btb = carve(8);
-    p.o_fc1 = carve((size_t)g.D * g.P * 4);
-    p.o_fc2 = carve((size_t)g.D * g.P * 4);
+    p.o_xp = cv.reserve(B * pix * g.Cin * 4);
+    p.o_wgt = cv.reserve((size_t)2 * g.C * 9 * g.Cin * 4);
+    p.o_bgt = cv.reserve((size_t)2 * g.C * 4);
+    p.o_wtb = cv.reserve((size_t)2 * g.ks * g.ks * g.Cin * 4);
+    p.o_btb = cv.reserve(8);
+    p.o_fc1 = cv.reserve((size_t)g.D * g.P * 4);
+    p.o_fc2 = cv.reserve((size_t)g.D * g.P * 4);
     // one row buffer serves every unfold in turn: 3x3 input patches, thr / bias patches, query / key / value patches
     size_t rows = B * HW * 9 * g.Cin;
     const size_t r_tb = B * g.L * (size_t)g.ks * g.ks * g.Cin, r_q = B * g.L * (size_t)g.P, r_k = B * g.N * (size_t)g.P;
     if (r_tb > rows) rows = r_tb;
     if (r_q > rows) rows = r_q;
     if (r_k > rows) rows = r_k;
-    p.o_rows = carve(rows * 4);
-    p.o_y = carve(B * HW * 2 * g.C * 4);
-    p.o_b1p = carve(B * pix * g.C * 4);
-    p.o_b2p = carve(B * pix * g.C * 4);
-    p.o_tb = carve(B * g.L * 2 * 4);
-    p.o_wq = carve(B * g.L * (size_t)g.D * 4);
-    p.o_x = carve(B * g.N * (size_t)g.D * 4);
-    p.o_s = carve((size_t)g.Lc * (g.ldn + 2 * GEN_LIST_CAP_WORDS) * 4);
-    p.o_agg = carve(B * g.L * (size_t)g.P * 4);
-    p.o_end = off;
+    p.o_rows = cv.reserve(rows * 4);
+    p.o_y = cv.reserve(B * HW * 2 * g.C * 4);
+    p.o_b1p = cv.reserve(B * pix * g.C * 4);
+    p.o_b2p = cv.reserve(B * pix * g.C * 4);
+    p.o_tb = cv.reserve(B * g.L * 2 * 4);
+    p.o_wq = cv.reserve(B * g.L * (size_t)g.D * 4);
+    p.o_x = cv.reserve(B * g.N * (size_t)g.D * 4);
+    p.o_s = cv.reserve((size_t)g.Lc * (g.ldn + 2 * GEN_LIST_CAP_WORDS) * 4);
+    p.o_agg = cv.reserve(B * g.L * (size_t)g.P * 4);
+    p.o_end = cv.bytes();
     return p;
 }
 
@@ -423,19 +422,18 @@ __global__ void gen_rank1_add_kernel(size_t rows, int cols, const float* __restr
 struct GenCorePlan { size_t o_vrows, o_dvrows, o_s, o_a, o_da, o_agg, o_rc, o_ones, o_vec, o_end; };
 inline GenCorePlan gen_core_plan(const GenGeom& g, bool backward) {
     GenCorePlan p{};
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    Carver cv;
     const size_t B = g.B;
-    p.o_vrows = carve(B * g.N * (size_t)g.P * 4);
-    p.o_dvrows = backward ? carve(B * g.N * (size_t)g.P * 4) : 0;
-    p.o_s = carve((size_t)g.Lc * (g.ldn + 2 * GEN_LIST_CAP_WORDS) * 4);
-    p.o_a = backward ? carve((size_t)g.Lc * g.ldn * 4) : 0;
-    p.o_da = backward ? carve((size_t)g.Lc * g.ldn * 4) : 0;
-    p.o_agg = carve(B * g.L * (size_t)g.P * 4);
-    p.o_rc = backward ? carve(B * g.L * 4) : 0;
-    p.o_ones = backward ? carve((size_t)(g.N > g.L ? g.N : g.L) * 4) : 0;
-    p.o_vec = backward ? carve((size_t)g.D * 4 * 2) : 0;
-    p.o_end = off;
+    p.o_vrows = cv.reserve(B * g.N * (size_t)g.P * 4);
+    p.o_dvrows = backward ? cv.reserve(B * g.N * (size_t)g.P * 4) : 0;
+    p.o_s = cv.reserve((size_t)g.Lc * (g.ldn + 2 * GEN_LIST_CAP_WORDS) * 4);
+    p.o_a = backward ? cv.reserve((size_t)g.Lc * g.ldn * 4) : 0;
+    p.o_da = backward ? cv.reserve((size_t)g.Lc * g.ldn * 4) : 0;
+    p.o_agg = cv.reserve(B * g.L * (size_t)g.P * 4);
+    p.o_rc = backward ? cv.reserve(B * g.L * 4) : 0;
+    p.o_ones = backward ? cv.reserve((size_t)(g.N > g.L ? g.N : g.L) * 4) : 0;
+    p.o_vec = backward ? cv.reserve((size_t)g.D * 4 * 2) : 0;
+    p.o_end = cv.bytes();
     return p;
 }
 
@@ -511,52 +509,51 @@ int launch_ce_generic(hipStream_t s, int B, int Cin, int H, int W, int ks, int s
     const GenGeom g = gen_geom(B, Cin, H, W, ks, s1, s2, C);
     const GenPlan p = gen_plan(g);
     char* ws = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     int rc;
     const size_t HW = (size_t)H * W;
     const bool heads = mode != DAGL_MODE_TOPK;
 
     // ---- weights in the unfold's element order ------------------------------------------------------------------------------
     const long long kg = 9ll * Cin;
-    DAGL_HIP_TRY(hipMemsetAsync(F(p.o_wgt), 0, (size_t)2 * C * kg * 4, s));
-    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)C * kg + 255) / 256)), dim3(256), 0, s, C, Cin, 3, g_w, F(p.o_wgt), kg, 0ll);
+    DAGL_HIP_TRY(hipMemsetAsync(at<float>(ws, p.o_wgt), 0, (size_t)2 * C * kg * 4, s));
+    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)C * kg + 255) / 256)), dim3(256), 0, s, C, Cin, 3, g_w, at<float>(ws, p.o_wgt), kg, 0ll);
     hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)C * Cin + 255) / 256)), dim3(256), 0, s, C, Cin, 1, th_w,
-                       F(p.o_wgt) + (size_t)C * kg, kg, 4ll * Cin);                       // theta = the centre tap
-    DAGL_HIP_TRY(hipMemcpyAsync(F(p.o_bgt), g_b, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    DAGL_HIP_TRY(hipMemcpyAsync(F(p.o_bgt) + C, th_b, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)g.D * g.P + 255) / 256)), dim3(256), 0, s, g.D, C, ks, fc1_w, F(p.o_fc1), (long long)g.P, 0ll);
-    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)g.D * g.P + 255) / 256)), dim3(256), 0, s, g.D, C, ks, fc2_w, F(p.o_fc2), (long long)g.P, 0ll);
+                       at<float>(ws, p.o_wgt) + (size_t)C * kg, kg, 4ll * Cin);                       // theta = the centre tap
+    DAGL_HIP_TRY(hipMemcpyAsync(at<float>(ws, p.o_bgt), g_b, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    DAGL_HIP_TRY(hipMemcpyAsync(at<float>(ws, p.o_bgt) + C, th_b, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)g.D * g.P + 255) / 256)), dim3(256), 0, s, g.D, C, ks, fc1_w, at<float>(ws, p.o_fc1), (long long)g.P, 0ll);
+    hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)(((size_t)g.D * g.P + 255) / 256)), dim3(256), 0, s, g.D, C, ks, fc2_w, at<float>(ws, p.o_fc2), (long long)g.P, 0ll);
     const long long ktb = (long long)ks * ks * Cin;
     if (heads) {
-        hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)((ktb + 255) / 256)), dim3(256), 0, s, 1, Cin, ks, thr_w, F(p.o_wtb), ktb, 0ll);
-        hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)((ktb + 255) / 256)), dim3(256), 0, s, 1, Cin, ks, bias_w, F(p.o_wtb) + ktb, ktb, 0ll);
-        DAGL_HIP_TRY(hipMemcpyAsync(F(p.o_btb), thr_b, 4, hipMemcpyDeviceToDevice, s));
-        DAGL_HIP_TRY(hipMemcpyAsync(F(p.o_btb) + 1, bias_b, 4, hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)((ktb + 255) / 256)), dim3(256), 0, s, 1, Cin, ks, thr_w, at<float>(ws, p.o_wtb), ktb, 0ll);
+        hipLaunchKernelGGL(gen_weight_rows_kernel, dim3((unsigned)((ktb + 255) / 256)), dim3(256), 0, s, 1, Cin, ks, bias_w, at<float>(ws, p.o_wtb) + ktb, ktb, 0ll);
+        DAGL_HIP_TRY(hipMemcpyAsync(at<float>(ws, p.o_btb), thr_b, 4, hipMemcpyDeviceToDevice, s));
+        DAGL_HIP_TRY(hipMemcpyAsync(at<float>(ws, p.o_btb) + 1, bias_b, 4, hipMemcpyDeviceToDevice, s));
     }
     DAGL_LAUNCH_CHECK("gen_weight_rows_kernel");
 
     // ---- prologue convolutions, dagl.py:208-215 -----------------------------------------------------------------------------
-    hipLaunchKernelGGL(gen_pad_nhwc_kernel, gen_grid((size_t)g.Hp * g.Wp * (Cin / 4), B), dim3(256), 0, s, Cin, H, W, g.PG, x, F(p.o_xp));
+    hipLaunchKernelGGL(gen_pad_nhwc_kernel, gen_grid((size_t)g.Hp * g.Wp * (Cin / 4), B), dim3(256), 0, s, Cin, H, W, g.PG, x, at<float>(ws, p.o_xp));
     DAGL_LAUNCH_CHECK("gen_pad_nhwc_kernel");
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, Cin, 3, 1, g.PG - 1, g.PG - 1, H, W, F(p.o_xp), F(p.o_rows)))) return rc;
-    if ((rc = launch_gemm32(s, gen_gemm((int)(B * HW), 2 * C, (int)kg, F(p.o_rows), kg, F(p.o_wgt), kg, 1, F(p.o_y), 2 * C, F(p.o_bgt), 0)))) return rc;
-    DAGL_HIP_TRY(hipMemsetAsync(F(p.o_b1p), 0, (size_t)B * g.Hp * g.Wp * C * 4, s));
-    DAGL_HIP_TRY(hipMemsetAsync(F(p.o_b2p), 0, (size_t)B * g.Hp * g.Wp * C * 4, s));
-    hipLaunchKernelGGL(gen_split_maps_kernel, gen_grid(HW * 2 * (C / 4), B), dim3(256), 0, s, C, H, W, g.PG, F(p.o_y), F(p.o_b1p), F(p.o_b2p));
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, Cin, 3, 1, g.PG - 1, g.PG - 1, H, W, at<float>(ws, p.o_xp), at<float>(ws, p.o_rows)))) return rc;
+    if ((rc = launch_gemm32(s, gen_gemm((int)(B * HW), 2 * C, (int)kg, at<float>(ws, p.o_rows), kg, at<float>(ws, p.o_wgt), kg, 1, at<float>(ws, p.o_y), 2 * C, at<float>(ws, p.o_bgt), 0)))) return rc;
+    DAGL_HIP_TRY(hipMemsetAsync(at<float>(ws, p.o_b1p), 0, (size_t)B * g.Hp * g.Wp * C * 4, s));
+    DAGL_HIP_TRY(hipMemsetAsync(at<float>(ws, p.o_b2p), 0, (size_t)B * g.Hp * g.Wp * C * 4, s));
+    hipLaunchKernelGGL(gen_split_maps_kernel, gen_grid(HW * 2 * (C / 4), B), dim3(256), 0, s, C, H, W, g.PG, at<float>(ws, p.o_y), at<float>(ws, p.o_b1p), at<float>(ws, p.o_b2p));
     DAGL_LAUNCH_CHECK("gen_split_maps_kernel");
     if (heads) {
-        if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, Cin, ks, s1, g.PG - g.t1, g.PG - g.l1, g.Lh, g.Lw, F(p.o_xp), F(p.o_rows)))) return rc;
-        if ((rc = launch_gemm32(s, gen_gemm(B * g.L, 2, (int)ktb, F(p.o_rows), ktb, F(p.o_wtb), ktb, 1, F(p.o_tb), 2, F(p.o_btb), 0)))) return rc;
+        if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, Cin, ks, s1, g.PG - g.t1, g.PG - g.l1, g.Lh, g.Lw, at<float>(ws, p.o_xp), at<float>(ws, p.o_rows)))) return rc;
+        if ((rc = launch_gemm32(s, gen_gemm(B * g.L, 2, (int)ktb, at<float>(ws, p.o_rows), ktb, at<float>(ws, p.o_wtb), ktb, 1, at<float>(ws, p.o_tb), 2, at<float>(ws, p.o_btb), 0)))) return rc;
     }
 
     // ---- patch features, dagl.py:216-249 ------------------------------------------------------------------------------------
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s1, g.PG - g.t1, g.PG - g.l1, g.Lh, g.Lw, F(p.o_b1p), F(p.o_rows)))) return rc;
-    if ((rc = launch_gemm32(s, gen_gemm(B * g.L, g.D, g.P, F(p.o_rows), g.P, F(p.o_fc1), g.P, 1, F(p.o_wq), g.D, fc1_b, 1)))) return rc;
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, F(p.o_b1p), F(p.o_rows)))) return rc;
-    if ((rc = launch_gemm32(s, gen_gemm(B * g.N, g.D, g.P, F(p.o_rows), g.P, F(p.o_fc2), g.P, 1, F(p.o_x), g.D, fc2_b, 1)))) return rc;
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, F(p.o_b2p), F(p.o_rows)))) return rc;   // value rows
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s1, g.PG - g.t1, g.PG - g.l1, g.Lh, g.Lw, at<float>(ws, p.o_b1p), at<float>(ws, p.o_rows)))) return rc;
+    if ((rc = launch_gemm32(s, gen_gemm(B * g.L, g.D, g.P, at<float>(ws, p.o_rows), g.P, at<float>(ws, p.o_fc1), g.P, 1, at<float>(ws, p.o_wq), g.D, fc1_b, 1)))) return rc;
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, at<float>(ws, p.o_b1p), at<float>(ws, p.o_rows)))) return rc;
+    if ((rc = launch_gemm32(s, gen_gemm(B * g.N, g.D, g.P, at<float>(ws, p.o_rows), g.P, at<float>(ws, p.o_fc2), g.P, 1, at<float>(ws, p.o_x), g.D, fc2_b, 1)))) return rc;
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, at<float>(ws, p.o_b2p), at<float>(ws, p.o_rows)))) return rc;   // value rows
 
-    return gen_core_forward(s, g, scale, mode, k, F(p.o_wq), F(p.o_x), F(p.o_rows), F(p.o_tb), F(p.o_tb) + 1, 2, F(p.o_s), F(p.o_agg), out, degree);
+    return gen_core_forward(s, g, scale, mode, k, at<float>(ws, p.o_wq), at<float>(ws, p.o_x), at<float>(ws, p.o_rows), at<float>(ws, p.o_tb), at<float>(ws, p.o_tb) + 1, 2, at<float>(ws, p.o_s), at<float>(ws, p.o_agg), out, degree);
 }
 
 size_t ce_generic_core_workspace_bytes(int B, int H, int W, int ks, int s1, int s2, int C, int backward) {
@@ -571,10 +568,9 @@ int launch_ce_generic_core_forward(hipStream_t s, int B, int H, int W, int ks, i
     const GenGeom g = gen_geom(B, 4, H, W, ks, s1, s2, C);
     const GenCorePlan p = gen_core_plan(g, false);
     char* ws = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     int rc;
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, b2p, F(p.o_vrows)))) return rc;
-    return gen_core_forward(s, g, scale, mode, k, wq, x, F(p.o_vrows), thr, bias, 1, F(p.o_s), F(p.o_agg), out, degree);
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, b2p, at<float>(ws, p.o_vrows)))) return rc;
+    return gen_core_forward(s, g, scale, mode, k, wq, x, at<float>(ws, p.o_vrows), thr, bias, 1, at<float>(ws, p.o_s), at<float>(ws, p.o_agg), out, degree);
 }
 
 int launch_fold_patches(hipStream_t s, int B, int Hp, int Wp, int C, int k, int stride, int oy, int ox, int oh, int ow, const float* drows,
@@ -587,66 +583,65 @@ int launch_ce_generic_core_backward(hipStream_t s, int B, int H, int W, int ks, 
     const GenGeom g = gen_geom(B, 4, H, W, ks, s1, s2, C);
     const GenCorePlan p = gen_core_plan(g, true);
     char* ws = reinterpret_cast<char*>(((uintptr_t)workspace + 255) / 256 * 256);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     int rc;
     const bool heads = mode != DAGL_MODE_TOPK;
     const int kk = k < g.N ? k : g.N;
-    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, b2p, F(p.o_vrows)))) return rc;
+    if ((rc = launch_unfold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, b2p, at<float>(ws, p.o_vrows)))) return rc;
     hipLaunchKernelGGL(gen_unfold_out_kernel, gen_grid((size_t)g.L * g.P, B), dim3(256), 0, s, C, H, W, ks, s1, g.fold_pad, g.fold_h, g.fold_w,
-                       d_out, F(p.o_agg));
+                       d_out, at<float>(ws, p.o_agg));
     DAGL_LAUNCH_CHECK("gen_unfold_out_kernel");
     const size_t n_ones = (size_t)(g.N > g.L ? g.N : g.L);
-    hipLaunchKernelGGL(gen_fill_kernel, dim3((unsigned)((n_ones + 255) / 256)), dim3(256), 0, s, n_ones, 1.0f, F(p.o_ones));
+    hipLaunchKernelGGL(gen_fill_kernel, dim3((unsigned)((n_ones + 255) / 256)), dim3(256), 0, s, n_ones, 1.0f, at<float>(ws, p.o_ones));
     DAGL_LAUNCH_CHECK("gen_fill_kernel");
     for (int b = 0; b < B; ++b) {
         const float* Xb = x + (size_t)b * g.N * g.D;
-        const float* Vb = F(p.o_vrows) + (size_t)b * g.N * g.P;
-        float* dVb = F(p.o_dvrows) + (size_t)b * g.N * g.P;
+        const float* Vb = at<float>(ws, p.o_vrows) + (size_t)b * g.N * g.P;
+        float* dVb = at<float>(ws, p.o_dvrows) + (size_t)b * g.N * g.P;
         float* dXb = d_x + (size_t)b * g.N * g.D;
         for (int l0 = 0; l0 < g.L; l0 += g.Lc) {
             const int lc = (g.L - l0 < g.Lc) ? g.L - l0 : g.Lc;
             const float* Wqc = wq + ((size_t)b * g.L + l0) * g.D;
-            const float* dAggc = F(p.o_agg) + ((size_t)b * g.L + l0) * g.P;
+            const float* dAggc = at<float>(ws, p.o_agg) + ((size_t)b * g.L + l0) * g.P;
             const float beta = l0 == 0 ? 0.f : 1.f;
-            if ((rc = launch_gemm32(s, gen_gemm(lc, g.N, g.D, Wqc, g.D, Xb, g.D, 1, F(p.o_s), g.ldn, nullptr, 0)))) return rc;          // S
-#define GEN_ROWS(M_) hipLaunchKernelGGL((gen_row_softmax_kernel<M_>), dim3(lc), dim3(256), 0, s, g.N, g.ldn, g.L, l0, b, kk, scale, F(p.o_s), F(p.o_a), thr, bias, 1, (int32_t*)nullptr)
+            if ((rc = launch_gemm32(s, gen_gemm(lc, g.N, g.D, Wqc, g.D, Xb, g.D, 1, at<float>(ws, p.o_s), g.ldn, nullptr, 0)))) return rc;          // S
+#define GEN_ROWS(M_) hipLaunchKernelGGL((gen_row_softmax_kernel<M_>), dim3(lc), dim3(256), 0, s, g.N, g.ldn, g.L, l0, b, kk, scale, at<float>(ws, p.o_s), at<float>(ws, p.o_a), thr, bias, 1, (int32_t*)nullptr)
             if (mode == DAGL_MODE_ADAPTIVE) GEN_ROWS(0); else if (mode == DAGL_MODE_TOPK) GEN_ROWS(1); else GEN_ROWS(2);                 // A
 #undef GEN_ROWS
             DAGL_LAUNCH_CHECK("gen_row_softmax_kernel");
-            if ((rc = launch_gemm32(s, gen_gemm(lc, g.N, g.P, dAggc, g.P, Vb, g.P, 1, F(p.o_da), g.ldn, nullptr, 0)))) return rc;       // d A = d agg V^T
+            if ((rc = launch_gemm32(s, gen_gemm(lc, g.N, g.P, dAggc, g.P, Vb, g.P, 1, at<float>(ws, p.o_da), g.ldn, nullptr, 0)))) return rc;       // d A = d agg V^T
             {                                                                                                                            // d V (+)= A^T d agg
-                Gemm32 q = gen_gemm(g.N, g.P, lc, F(p.o_a), g.ldn, dAggc, g.P, 0, dVb, g.P, nullptr, 0);
+                Gemm32 q = gen_gemm(g.N, g.P, lc, at<float>(ws, p.o_a), g.ldn, dAggc, g.P, 0, dVb, g.P, nullptr, 0);
                 q.a_kc = 0; q.beta = beta;
                 if ((rc = launch_gemm32(s, q))) return rc;
             }
-            float* rc_q = F(p.o_rc) + (size_t)b * g.L;
-#define GEN_BWD(M_) hipLaunchKernelGGL((gen_row_backward_kernel<M_>), dim3(lc), dim3(256), 0, s, g.N, g.ldn, g.L, l0, b, scale, F(p.o_s), F(p.o_a), F(p.o_da), \
-                                       thr, bias, d_thr, d_bias, F(p.o_rc))
+            float* rc_q = at<float>(ws, p.o_rc) + (size_t)b * g.L;
+#define GEN_BWD(M_) hipLaunchKernelGGL((gen_row_backward_kernel<M_>), dim3(lc), dim3(256), 0, s, g.N, g.ldn, g.L, l0, b, scale, at<float>(ws, p.o_s), at<float>(ws, p.o_a), at<float>(ws, p.o_da), \
+                                       thr, bias, d_thr, d_bias, at<float>(ws, p.o_rc))
             if (heads) GEN_BWD(0); else GEN_BWD(1);                                                                                     // d S
 #undef GEN_BWD
             DAGL_LAUNCH_CHECK("gen_row_backward_kernel");
             (void)rc_q;
-            if ((rc = launch_gemm32(s, gen_gemm(lc, g.D, g.N, F(p.o_da), g.ldn, Xb, g.D, 0, d_wq + ((size_t)b * g.L + l0) * g.D, g.D, nullptr, 0)))) return rc;   // d Wq = d S X
+            if ((rc = launch_gemm32(s, gen_gemm(lc, g.D, g.N, at<float>(ws, p.o_da), g.ldn, Xb, g.D, 0, d_wq + ((size_t)b * g.L + l0) * g.D, g.D, nullptr, 0)))) return rc;   // d Wq = d S X
             {                                                                                                                            // d X (+)= d S^T Wq
-                Gemm32 q = gen_gemm(g.N, g.D, lc, F(p.o_da), g.ldn, Wqc, g.D, 0, dXb, g.D, nullptr, 0);
+                Gemm32 q = gen_gemm(g.N, g.D, lc, at<float>(ws, p.o_da), g.ldn, Wqc, g.D, 0, dXb, g.D, nullptr, 0);
                 q.a_kc = 0; q.beta = beta;
                 if ((rc = launch_gemm32(s, q))) return rc;
             }
         }
         if (heads) {
             // the row-mean term of dagl.py:256: d S_lj += rcoef_l for every key j  =>  d Wq_l += rcoef_l sum_j X_j,  d X_j += sum_l rcoef_l Wq_l
-            float* colsum = F(p.o_vec); float* u = F(p.o_vec) + g.D;
-            if ((rc = launch_gemm32(s, gen_gemm(1, g.D, g.N, F(p.o_ones), g.N, Xb, g.D, 0, colsum, g.D, nullptr, 0)))) return rc;
-            if ((rc = launch_gemm32(s, gen_gemm(1, g.D, g.L, F(p.o_rc) + (size_t)b * g.L, g.L, wq + (size_t)b * g.L * g.D, g.D, 0, u, g.D, nullptr, 0)))) return rc;
+            float* colsum = at<float>(ws, p.o_vec); float* u = at<float>(ws, p.o_vec) + g.D;
+            if ((rc = launch_gemm32(s, gen_gemm(1, g.D, g.N, at<float>(ws, p.o_ones), g.N, Xb, g.D, 0, colsum, g.D, nullptr, 0)))) return rc;
+            if ((rc = launch_gemm32(s, gen_gemm(1, g.D, g.L, at<float>(ws, p.o_rc) + (size_t)b * g.L, g.L, wq + (size_t)b * g.L * g.D, g.D, 0, u, g.D, nullptr, 0)))) return rc;
             hipLaunchKernelGGL(gen_rank1_add_kernel, dim3((unsigned)(((size_t)g.L * g.D + 255) / 256)), dim3(256), 0, s, (size_t)g.L, g.D,
-                               F(p.o_rc) + (size_t)b * g.L, colsum, d_wq + (size_t)b * g.L * g.D);
+                               at<float>(ws, p.o_rc) + (size_t)b * g.L, colsum, d_wq + (size_t)b * g.L * g.D);
             hipLaunchKernelGGL(gen_rank1_add_kernel, dim3((unsigned)(((size_t)g.N * g.D + 255) / 256)), dim3(256), 0, s, (size_t)g.N, g.D,
                                (const float*)nullptr, u, dXb);
             DAGL_LAUNCH_CHECK("gen_rank1_add_kernel");
         }
     }
     // d value map = fold(d value rows)
-    return launch_fold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, F(p.o_dvrows), d_b2p);
+    return launch_fold_patches(s, B, g.Hp, g.Wp, C, ks, s2, g.PG - g.t2, g.PG - g.l2, g.Nh, g.Nw, at<float>(ws, p.o_dvrows), d_b2p);
 }
 
 }  // namespace dagl

@@ -214,12 +214,6 @@ __global__ __launch_bounds__(GR_THREADS) void graph_row_fill_kernel(GraphArgs a)
 }
 
 // ---- plan: chunk height, workspace carve -------------------------------------------------------------------------------------------
-static size_t gcarve(size_t& off, size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-}
-
 int graph_plan(int B, int H, int W, int mode, int k, int rows_per_chunk, GraphPlan& p) {
     p = GraphPlan{};
     DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "dagl_ce_graph: bad shape B=%d H=%d W=%d", B, H, W);
@@ -243,35 +237,32 @@ int graph_plan(int B, int H, int W, int mode, int k, int rows_per_chunk, GraphPl
     }
     p.rows = (int)(c < g.L ? c : g.L);
     const size_t BL = (size_t)B * g.L;
-    size_t off = 0;
-    p.o_b1p = gcarve(off, (size_t)B * g.Hp * g.Wp * CH * sizeof(float));
-    p.o_wp1 = gcarve(off, (size_t)DPAD * P * sizeof(float));
-    p.o_wp2 = gcarve(off, (size_t)DPAD * P * sizeof(float));
-    p.o_x = gcarve(off, (size_t)B * feat_rows(g.N) * DS * sizeof(float));
-    p.o_wq = gcarve(off, (size_t)B * feat_rows(g.L) * DS * sizeof(float));
-    p.o_colsum = gcarve(off, (size_t)B * DS * sizeof(double));
-    p.o_mt = gcarve(off, BL * sizeof(float));
-    p.o_bias = gcarve(off, BL * sizeof(float));
-    p.o_deg = gcarve(off, BL * sizeof(int32_t));
-    p.o_sel = gcarve(off, BL * sizeof(uint2));
-    p.o_rowm = gcarve(off, BL * sizeof(double));
-    p.o_rowz = gcarve(off, BL * sizeof(double));
-    p.o_scores = gcarve(off, (size_t)p.rows * p.ldn * sizeof(float));
-    p.o_end = off;
+    Carver cv;
+    p.o_b1p = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(float));
+    p.o_wp1 = cv.reserve((size_t)DPAD * P * sizeof(float));
+    p.o_wp2 = cv.reserve((size_t)DPAD * P * sizeof(float));
+    p.o_x = cv.reserve((size_t)B * feat_rows(g.N) * DS * sizeof(float));
+    p.o_wq = cv.reserve((size_t)B * feat_rows(g.L) * DS * sizeof(float));
+    p.o_colsum = cv.reserve((size_t)B * DS * sizeof(double));
+    p.o_mt = cv.reserve(BL * sizeof(float));
+    p.o_bias = cv.reserve(BL * sizeof(float));
+    p.o_deg = cv.reserve(BL * sizeof(int32_t));
+    p.o_sel = cv.reserve(BL * sizeof(uint2));
+    p.o_rowm = cv.reserve(BL * sizeof(double));
+    p.o_rowz = cv.reserve(BL * sizeof(double));
+    p.o_scores = cv.reserve((size_t)p.rows * p.ldn * sizeof(float));
+    p.o_end = cv.bytes();
     return DAGL_OK;
 }
-
-template <class T>
-static T* gat(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
 static GraphArgs graph_args(const GraphPlan& p, void* ws) {
     GraphArgs a;
     memset(&a, 0, sizeof(a));
     a.N = p.g.N; a.L = p.g.L; a.mode = p.mode; a.k = p.k;
-    a.scores = gat<float>(ws, p.o_scores); a.ldn = p.ldn;
-    a.mt = gat<float>(ws, p.o_mt); a.bs = gat<float>(ws, p.o_bias);
-    a.deg = gat<int32_t>(ws, p.o_deg); a.sel = gat<uint2>(ws, p.o_sel);
-    a.row_m = gat<double>(ws, p.o_rowm); a.row_z = gat<double>(ws, p.o_rowz);
+    a.scores = at<float>(ws, p.o_scores); a.ldn = p.ldn;
+    a.mt = at<float>(ws, p.o_mt); a.bs = at<float>(ws, p.o_bias);
+    a.deg = at<int32_t>(ws, p.o_deg); a.sel = at<uint2>(ws, p.o_sel);
+    a.row_m = at<double>(ws, p.o_rowm); a.row_z = at<double>(ws, p.o_rowz);
     a.n_rows = (long long)p.B * p.g.L;
     return a;
 }
@@ -282,8 +273,8 @@ template <class K>
 static int graph_chunks(hipStream_t s, const GraphPlan& p, void* ws, GraphArgs a, K kernel, const char* name) {
     const Grid& g = p.g;
     const int rows_q = feat_rows(g.L), rows_x = feat_rows(g.N);
-    const float* wq = gat<float>(ws, p.o_wq);
-    const float* x = gat<float>(ws, p.o_x);
+    const float* wq = at<float>(ws, p.o_wq);
+    const float* x = at<float>(ws, p.o_x);
     for (int b = 0; b < p.B; ++b)
         for (int r0 = 0; r0 < g.L; r0 += p.rows) {
             a.b = b; a.r0 = r0; a.R = (g.L - r0 < p.rows) ? g.L - r0 : p.rows;
@@ -291,7 +282,7 @@ static int graph_chunks(hipStream_t s, const GraphPlan& p, void* ws, GraphArgs a
             gm.M = a.R; gm.N = g.N; gm.K = D; gm.batch = 1;
             gm.A = wq + ((size_t)b * rows_q + r0) * DS; gm.lda = DS; gm.sA = 0; gm.a_kc = 1;
             gm.B = x + (size_t)b * rows_x * DS; gm.ldb = DS; gm.sB = 0; gm.b_kc = 1;
-            gm.C = gat<float>(ws, p.o_scores); gm.ldc = p.ldn; gm.sC = 0;
+            gm.C = at<float>(ws, p.o_scores); gm.ldc = p.ldn; gm.sC = 0;
             gm.alpha = 1.f; gm.beta = 0.f; gm.bias = nullptr; gm.relu = 0; gm.chunk_tiles = 3;
             const int rc = launch_gemm32(s, gm);
             if (rc) return rc;
@@ -305,28 +296,32 @@ int launch_graph_count(hipStream_t s, const GraphPlan& p, const float* b1, const
                        const float* fc1_b, const float* fc2_w, const float* fc2_b, int64_t* row_off, void* ws) {
     const Grid& g = p.g;
     const size_t BL = (size_t)p.B * g.L;
-    float* b1p = gat<float>(ws, p.o_b1p);
-    float* X = gat<float>(ws, p.o_x);
-    float* Wq = gat<float>(ws, p.o_wq);
-    double* colsum = gat<double>(ws, p.o_colsum);
+    float* b1p = at<float>(ws, p.o_b1p);
+    float* X = at<float>(ws, p.o_x);
+    float* Wq = at<float>(ws, p.o_wq);
+    double* colsum = at<double>(ws, p.o_colsum);
     int rc;
     // fp32 map, packed weights, features, row thresholds: the launches of the scan = "exact" forward (capi.hip stage_layout .. stage_thresholds)
     if ((rc = launch_pad_nhwc(s, p.B, g.H, g.W, b1, b1p))) return rc;
-    if ((rc = launch_pack_fc_weight(s, fc1_w, gat<float>(ws, p.o_wp1)))) return rc;
-    if ((rc = launch_pack_fc_weight(s, fc2_w, gat<float>(ws, p.o_wp2)))) return rc;
+    if ((rc = launch_pack_fc_weight(s, fc1_w, at<float>(ws, p.o_wp1)))) return rc;
+    if ((rc = launch_pack_fc_weight(s, fc2_w, at<float>(ws, p.o_wp2)))) return rc;
     ZeroList zl;
     const int rx = feat_rows(g.N), rq = feat_rows(g.L);
     zl.add(X + (size_t)g.N * DS, (size_t)(rx - g.N) * DS * sizeof(float), p.B, (size_t)rx * DS * sizeof(float));
     zl.add(Wq + (size_t)g.L * DS, (size_t)(rq - g.L) * DS * sizeof(float), p.B, (size_t)rq * DS * sizeof(float));
     zl.add(colsum, align_up((size_t)p.B * DS * sizeof(double), 16));
     if ((rc = launch_zero_regions(s, zl))) return rc;
-    if ((rc = launch_project(s, p.B, g, 3, b1p, gat<float>(ws, p.o_wp2), fc2_b, X, colsum, gat<float>(ws, p.o_wp1), fc1_b, Wq))) return rc;
+    ProjectLaunch pj;
+    pj.B = p.B; pj.g = g; pj.which = 3; pj.map = b1p; pj.colsum = colsum;
+    pj.keys.wp = at<float>(ws, p.o_wp2); pj.keys.bias = fc2_b; pj.keys.feat = X;
+    pj.queries.wp = at<float>(ws, p.o_wp1); pj.queries.bias = fc1_b; pj.queries.feat = Wq;
+    if ((rc = launch_project(s, pj))) return rc;
     if (p.mode != DAGL_MODE_TOPK) {
-        if ((rc = launch_query_thresholds(s, p.B, g.L, g.N, Wq, colsum, thr, gat<float>(ws, p.o_mt)))) return rc;
-        DAGL_HIP_TRY(hipMemcpyAsync(gat<float>(ws, p.o_bias), bias, BL * sizeof(float), hipMemcpyDeviceToDevice, s));   // (fill is not handed the inputs again)
+        if ((rc = launch_query_thresholds(s, p.B, g.L, g.N, Wq, colsum, thr, at<float>(ws, p.o_mt)))) return rc;
+        DAGL_HIP_TRY(hipMemcpyAsync(at<float>(ws, p.o_bias), bias, BL * sizeof(float), hipMemcpyDeviceToDevice, s));   // (fill is not handed the inputs again)
     }
     if ((rc = graph_chunks(s, p, ws, graph_args(p, ws), graph_row_count_kernel, "graph_row_count_kernel"))) return rc;
-    return launch_row_scan(s, (int)BL, gat<int32_t>(ws, p.o_deg), row_off);
+    return launch_row_scan(s, (int)BL, at<int32_t>(ws, p.o_deg), row_off);
 }
 
 int launch_graph_fill(hipStream_t s, const GraphPlan& p, const int64_t* row_off, int32_t* key, float* weight, float* score,

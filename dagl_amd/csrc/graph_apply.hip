@@ -211,14 +211,19 @@ int graph_apply_segment() { return GA_SEG; }
 
 static size_t ga_chunks(int64_t E) { return (size_t)((E + GA_SEG - 1) / GA_SEG); }
 
-// forward: agg [B L, 784] + the chunks' partial rows;  backward: dAgg [B L, 784] + d V rows [B N, 784] + partial rows
-size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) {
-    size_t off = 0;
-    off = align_up(off + (size_t)B * g.L * P * sizeof(float), 256);
-    if (backward) off = align_up(off + (size_t)B * g.N * P * sizeof(float), 256);
-    off = align_up(off + (ga_chunks(E) + 1) * P * sizeof(float), 256);
-    return off;
+// forward: agg [B L, 784] + the chunks' partial rows;  backward: dAgg [B L, 784] + d V rows [B N, 784] + partial rows.  The one
+// walk behind the size (null base) and both launches
+struct GaWs { float* agg; float* dv; float* part; size_t bytes; };
+static GaWs ga_carve(void* ws, int B, const Grid& g, int64_t E, bool backward) {
+    Carver cv(ws);
+    GaWs w;
+    w.agg = cv.take<float>((size_t)B * g.L * P);
+    w.dv = backward ? cv.take<float>((size_t)B * g.N * P) : nullptr;
+    w.part = cv.take<float>((ga_chunks(E) + 1) * P);
+    w.bytes = cv.bytes();
+    return w;
 }
+size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) { return ga_carve(nullptr, B, g, E, backward).bytes; }
 
 static GaArgs ga_map_args(int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
                           int64_t E) {
@@ -241,10 +246,9 @@ static int ga_product(hipStream_t s, GaArgs a) {
 
 int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
                        const float* weight, int64_t E, float* out, void* workspace) {
-    char* ws = static_cast<char*>(workspace);
+    const GaWs w = ga_carve(workspace, B, g, E, false);
     GaArgs a = ga_map_args(B, g, b2p, row_off, key, weight, E);
-    a.out = reinterpret_cast<float*>(ws);
-    a.part = reinterpret_cast<float*>(ws + align_up((size_t)B * g.L * P * sizeof(float), 256));
+    a.out = w.agg; a.part = w.part;
     const int rc = ga_product<true>(s, a);
     if (rc) return rc;
     return launch_fold(s, B, g, a.out, out);
@@ -253,12 +257,8 @@ int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, co
 int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
                                 const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
                                 const int32_t* perm, float* d_b2p, float* d_weight, void* workspace) {
-    char* ws = static_cast<char*>(workspace);
-    float* dagg = reinterpret_cast<float*>(ws);
-    size_t off = align_up((size_t)B * g.L * P * sizeof(float), 256);
-    float* dv = reinterpret_cast<float*>(ws + off);
-    off = align_up(off + (size_t)B * g.N * P * sizeof(float), 256);
-    float* part = reinterpret_cast<float*>(ws + off);
+    const GaWs w = ga_carve(workspace, B, g, E, true);
+    float *dagg = w.agg, *dv = w.dv, *part = w.part;
     int rc = launch_unfold_dout(s, B, g, d_out, dagg);
     if (rc) return rc;
     if (d_weight != nullptr && E > 0) {

@@ -212,20 +212,19 @@ __global__ __launch_bounds__(256, 2) void project_kernel(ProjArgs pa) {
 }
 
 // which: bit 0 = keys, bit 1 = queries
-int launch_project(hipStream_t s, int B, const Grid& g, int which, const float* map, const float* wp_keys,
-                   const float* bias_keys, float* feat_keys, double* colsum, const float* wp_q,
-                   const float* bias_q, float* feat_q, uint16_t* feat_keys_bf16, uint16_t* feat_q_bf16, RangeTag range) {
+int launch_project(hipStream_t s, const ProjectLaunch& a) {
+    const int B = a.B, which = a.which; const Grid& g = a.g;
     ProjArgs pa;
-    pa.range = range;
-    pa.feat_h[0] = feat_keys_bf16; pa.feat_h[1] = feat_q_bf16;
+    pa.range = a.range;
+    pa.feat_h[0] = a.keys.feat_bf16; pa.feat_h[1] = a.queries.feat_bf16;
     pa.rows_alloc_h[0] = feat_rows_h(g.N); pa.rows_alloc_h[1] = feat_rows_h(g.L);
-    pa.gr = g; pa.map = map;
-    pa.wp[0] = wp_keys; pa.bias[0] = bias_keys; pa.feat[0] = feat_keys;
-    pa.wp[1] = wp_q; pa.bias[1] = bias_q; pa.feat[1] = feat_q;
+    pa.gr = g; pa.map = a.map;
+    pa.wp[0] = a.keys.wp; pa.bias[0] = a.keys.bias; pa.feat[0] = a.keys.feat;
+    pa.wp[1] = a.queries.wp; pa.bias[1] = a.queries.bias; pa.feat[1] = a.queries.feat;
     pa.rows_alloc[0] = feat_rows(g.N); pa.rows_alloc[1] = feat_rows(g.L);
     pa.segs[0] = (g.W + PJ_ROWS - 1) / PJ_ROWS; pa.segs[1] = (g.Lw + PJ_ROWS - 1) / PJ_ROWS;
     pa.n_items[0] = pa.segs[0] * g.H; pa.n_items[1] = pa.segs[1] * g.Lh;
-    pa.colsum = colsum;
+    pa.colsum = a.colsum;
     const int nbq = (which & 2) ? (pa.n_items[1] + PJ_WAVES - 1) / PJ_WAVES : 0;
     const int nbk = (which & 1) ? (pa.n_items[0] + PJ_WAVES - 1) / PJ_WAVES : 0;
     pa.n_blocks_q = nbq;

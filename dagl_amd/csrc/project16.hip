@@ -834,30 +834,28 @@ static inline bool p16_keys_linear(const Grid& g) { return g.W >= 32; }       //
 static inline int p16_key_items(const Grid& g) { return p16_keys_linear(g) ? (g.N + 31) / 32 : ((g.W + 31) / 32) * g.H; }
 int project16_key_blocks(const Grid& g) { return 2 * ((p16_key_items(g) + P16_UNIT - 1) / P16_UNIT); }   // rows of colpart: two per unit
 
-int launch_project16(hipStream_t s, int B, const Grid& g, int which, const uint16_t* map_hi, const uint16_t* map_lo,
-                     const uint16_t* wp_keys, const float* const* bias_keys, float* feat_keys, double* colsum, float* colpart,
-                     const uint16_t* wp_q, const float* const* bias_q, float* feat_q, uint16_t* feat_keys_bf16,
-                     uint16_t* feat_q_bf16, int heads, RangeTag range, int q_tiled, const Split16Out* split,
-                     const ThrHeadSet* thr_hs, int thr_head_imgs, float* thr_part, const B1Tiers* tiers) {
+int launch_project16(hipStream_t s, const Project16Launch& a) {
+    const int B = a.B, which = a.which, heads = a.heads; const Grid& g = a.g;
+    const Split16Out* split = a.split; double* colsum = a.colsum; float* colpart = a.colpart;
     Proj16Args pa;
-    pa.map_hi2 = tiers ? tiers->hi2 : nullptr; pa.map_lo2 = tiers ? tiers->lo2 : nullptr;
-    pa.b1_amax = (tiers && tiers->hi2) ? tiers->amax : nullptr; pa.amax_slots = tiers ? tiers->slots : 0;
+    pa.map_hi2 = a.tiers.hi2; pa.map_lo2 = a.tiers.lo2;
+    pa.b1_amax = a.tiers.hi2 ? a.tiers.amax : nullptr; pa.amax_slots = a.tiers.slots;
     static_assert(TB4_LDS_BYTES <= P16_LDS, "the thr / bias blocks live in the projection's LDS");
     static_assert(P16_BW == 4, "thr_bias4_block (thr_bias4.h) is written for blocks of exactly 256 threads: tid + 256 j strides, part[4][..]");
     for (int w = 0; w < 2; ++w) {
         pa.split_hi[w] = split ? split->hi[w] : nullptr; pa.split_lo[w] = split ? split->lo[w] : nullptr;
         pa.rows_alloc_s[w] = split ? split->rows_alloc[w] : 0;
     }
-    pa.tiled_h[0] = 0; pa.tiled_h[1] = q_tiled;
-    pa.range = range; pa.heads = heads; pa.times = nullptr;
+    pa.tiled_h[0] = 0; pa.tiled_h[1] = a.q_tiled;
+    pa.range = a.range; pa.heads = heads; pa.times = nullptr;
     pa.imgs_per_head = B / heads;
     for (int h = 0; h < 4; ++h) {
-        pa.bias[0][h] = bias_keys ? bias_keys[h < heads ? h : 0] : nullptr;
-        pa.bias[1][h] = bias_q ? bias_q[h < heads ? h : 0] : nullptr;
+        pa.bias[0][h] = a.keys.bias ? a.keys.bias[h < heads ? h : 0] : nullptr;
+        pa.bias[1][h] = a.queries.bias ? a.queries.bias[h < heads ? h : 0] : nullptr;
     }
-    pa.gr = g; pa.map_hi = map_hi; pa.map_lo = map_lo;
-    pa.wp[0] = wp_keys; pa.feat[0] = feat_keys; pa.feat_h[0] = feat_keys_bf16;
-    pa.wp[1] = wp_q; pa.feat[1] = feat_q; pa.feat_h[1] = feat_q_bf16;
+    pa.gr = g; pa.map_hi = a.map_hi; pa.map_lo = a.map_lo;
+    pa.wp[0] = a.keys.wp; pa.feat[0] = a.keys.feat; pa.feat_h[0] = a.keys.feat_bf16;
+    pa.wp[1] = a.queries.wp; pa.feat[1] = a.queries.feat; pa.feat_h[1] = a.queries.feat_bf16;
     pa.rows_alloc[0] = feat_rows(g.N); pa.rows_alloc[1] = feat_rows(g.L);
     pa.rows_alloc_h[0] = feat_rows_h(g.N); pa.rows_alloc_h[1] = feat_rows_h(g.L);
     pa.segs[0] = (g.W + 31) / 32; pa.segs[1] = (g.Lw + 31) / 32;
@@ -882,8 +880,8 @@ int launch_project16(hipStream_t s, int B, const Grid& g, int which, const uint1
     pa.n_proj = pa.n_full + 2 * P16_NT * groups;
     pa.thr_part = nullptr; pa.thr_x = pa.thr_y = 1; memset(&pa.thr_hs, 0, sizeof(pa.thr_hs));
     int n_thr = 0;
-    if (thr_hs != nullptr && thr_part != nullptr && thr_head_imgs > 0) {
-        pa.thr_hs = *thr_hs; pa.thr_part = thr_part; pa.thr_x = thr_bias4_grid_x(g); pa.thr_y = thr_head_imgs;
+    if (a.thr_hs != nullptr && a.thr_part != nullptr && a.thr_head_imgs > 0) {
+        pa.thr_hs = *a.thr_hs; pa.thr_part = a.thr_part; pa.thr_x = thr_bias4_grid_x(g); pa.thr_y = a.thr_head_imgs;
         n_thr = pa.thr_x * pa.thr_y * TB_GROUPS;
     }
     const dim3 grid(pa.n_proj + n_thr), block(64 * P16_BW);

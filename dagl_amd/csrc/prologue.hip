@@ -600,17 +600,14 @@ int launch_thr_bias_heads(hipStream_t s, int heads, int imgs, const Grid& g, con
     return DAGL_OK;
 }
 
-int launch_prologue(hipStream_t s, int B, const Grid& g, const float* x, const float* g_w, const float* g_b,
-                    const float* th_w, const float* th_b, const float* thr_w, const float* thr_b,
-                    const float* bias_w, const float* bias_b, float* b1p, float* b2p, float* thr, float* bias,
-                    uint16_t* b1_hi, uint16_t* b1_lo, float* thr_part, bool borders_zero, bool defer_thr_reduce, uint32_t* clear_a,
-                    int clear_a_words, uint32_t* clear_b, int clear_b_words, RangeTag range, const unsigned char* conv_w16,
-                    bool skip_conv, const B1Tiers* tiers) {
+int launch_prologue(hipStream_t s, const PrologueLaunch& a) {
+    const int B = a.B; const Grid& g = a.g;
+    float *b1p = a.b1p, *b2p = a.b2p; uint16_t *b1_hi = a.b1_hi, *b1_lo = a.b1_lo;
     int rcz;
-    if (!borders_zero) {
+    if (!a.borders_zero) {
         if ((rcz = launch_zero_borders(s, B, g.H, g.W, b1p ? b1p : b2p, b2p))) return rcz;
         if (b1_hi != nullptr && (rcz = launch_zero_borders16(s, B, g.H, g.W, b1_hi, b1_lo))) return rcz;
-        if (b1_hi != nullptr && tiers != nullptr && tiers->hi2 != nullptr && (rcz = launch_zero_borders16(s, B, g.H, g.W, tiers->hi2, tiers->lo2))) return rcz;
+        if (b1_hi != nullptr && a.tiers.hi2 != nullptr && (rcz = launch_zero_borders16(s, B, g.H, g.W, a.tiers.hi2, a.tiers.lo2))) return rcz;
     }
     const int strips = (g.W + PRO_TW - 1) / PRO_TW;
     // one block per CU over the whole launch (1 block/CU resident: 332 registers), at least 2 rows per block
@@ -620,41 +617,39 @@ int launch_prologue(hipStream_t s, int B, const Grid& g, const float* x, const f
     if (chunks < 1) chunks = 1;
     const int rows_per_block = (g.H + chunks - 1) / chunks;
     chunks = (g.H + rows_per_block - 1) / rows_per_block;
-    if (skip_conv) {
-        // (the caller ran launch_conv_pair16_heads for all its heads)
-    } else if ((b1p == nullptr && b1_hi != nullptr) || (b1p != nullptr && conv_w16 != nullptr)) {
-        // (split-fp16 convolutions; with b1p: the differentiable path's forward -- an fp32 map out, the fp16 pairs optional)
-        if (conv_w16 == nullptr) { set_error("launch_prologue: the split-fp16 convolutions need their packed weights"); return DAGL_ERR_INVALID; }
+    if (a.conv == ConvPath::Split16) {
+        // (with b1p: the differentiable path's forward -- an fp32 map out, the fp16 pairs optional)
+        if (a.conv_w16 == nullptr) { set_error("launch_prologue: the split-fp16 convolutions need their packed weights"); return DAGL_ERR_INVALID; }
         ConvHeadSet hs = {};
-        hs.x[0] = x; hs.w[0] = conv_w16; hs.gb[0] = g_b; hs.tb[0] = th_b; hs.imgs = B;
-        if (tiers != nullptr) hs.tiers = *tiers;
+        hs.x[0] = a.x; hs.w[0] = a.conv_w16; hs.gb[0] = a.g_b; hs.tb[0] = a.th_b; hs.imgs = B;
+        hs.tiers = a.tiers;
         unsigned long long* times = nullptr;
 #ifdef DAGL_ABLATION
         if (getenv("DAGL_TIMES_FILE")) times = dbg_times_buffer((size_t)strips * chunks * B);
 #endif
         hipLaunchKernelGGL(conv_pair16_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, hs,
-                           b2p, b1p, b1_hi, b1_lo, clear_a, clear_a_words, clear_b, clear_b_words, range, times);
+                           b2p, b1p, b1_hi, b1_lo, a.clear_a, a.clear_a_words, a.clear_b, a.clear_b_words, a.range, times);
         DAGL_LAUNCH_CHECK("conv_pair16_kernel");
 #ifdef DAGL_ABLATION
         if (times) dbg_times_dump(s, "conv_pair16_kernel", times, (size_t)strips * chunks * B);
 #endif
-    } else {
-        hipLaunchKernelGGL(conv_pair_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, x, g_w,
-                           g_b, th_w, th_b, b1p, b2p, b1_hi, b1_lo);
+    } else if (a.conv == ConvPath::Fp32) {
+        hipLaunchKernelGGL(conv_pair_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, a.x, a.g_w,
+                           a.g_b, a.th_w, a.th_b, b1p, b2p, b1_hi, b1_lo);
         DAGL_LAUNCH_CHECK("conv_pair_kernel");
     }
-    if (thr != nullptr) {
+    if (a.thr != nullptr) {
         // thr_part: [4][B][L][2] floats of scratch for the channel groups' partial sums
-        if (!skip_conv) {                                          // (else: one launch_thr_bias_heads for all the caller's heads)
+        if (a.conv != ConvPath::DoneByCaller) {                    // (else: one launch_thr_bias_heads for all the caller's heads)
             ThrHeadSet hs = {};
-            hs.x[0] = x; hs.thr_w[0] = thr_w; hs.bias_w[0] = bias_w; hs.imgs = B;
-            const int rct = launch_thr_bias_heads(s, 1, B, g, hs, thr_part);
+            hs.x[0] = a.x; hs.thr_w[0] = a.thr_w; hs.bias_w[0] = a.bias_w; hs.imgs = B;
+            const int rct = launch_thr_bias_heads(s, 1, B, g, hs, a.thr_part);
             if (rct) return rct;
         }
         const size_t n = (size_t)B * g.L;
-        if (!defer_thr_reduce)
-        hipLaunchKernelGGL(thr_bias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, thr_part, thr_b,
-                           bias_b, thr, bias);
+        if (!a.defer_thr_reduce)
+        hipLaunchKernelGGL(thr_bias_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, a.thr_part, a.thr_b,
+                           a.bias_b, a.thr, a.bias);
         DAGL_LAUNCH_CHECK("thr_bias_reduce_kernel");
     }
     return DAGL_OK;

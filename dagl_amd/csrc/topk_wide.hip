@@ -427,15 +427,28 @@ int topk_wide_rows(int N, int L) {
     const long long lr = (L + 127) / 128 * 128;
     return (int)(c < lr ? c : lr);
 }
-// split-fp16 copy of one image's feature rows (hi or lo): [feat_rows_h(rows) + a tile of slack][DSH] halfs
-static size_t wide_split_bytes(int rows) { return align_up(((size_t)feat_rows_h(rows) + 256) * DSH * sizeof(uint16_t), 256); }
-size_t topk_wide_workspace_bytes(int N, int L) {
+// carve of the wide workspace: the one walk behind topk_wide_workspace_bytes (null base) and launch_topk_wide, which takes the
+// batch's regions of WideArgs (scores, part, sel, eq_before) and ldn from it
+struct WideWs { int32_t* served; uint16_t *xs_hi, *xs_lo, *qs_hi, *qs_lo; unsigned* amax_words; size_t bytes; };
+static WideWs wide_carve(void* ws, int N, int L, WideArgs& a) {
     const size_t R = (size_t)topk_wide_rows(N, L);
-    const size_t ldn = (size_t)(N + 31) / 32 * 32;
-    return align_up(R * ldn * sizeof(float), 256) + align_up(R * ROW_CHUNKS * ROW_PART_FLOATS * sizeof(float), 256) +
-           align_up(R * 4 * sizeof(int32_t), 256) + align_up(R * WIDE_RANGES * sizeof(int32_t), 256) + align_up(R * sizeof(int32_t), 256) +
-           2 * wide_split_bytes(N) + 2 * wide_split_bytes(L) + 256;
+    // split-fp16 copy of one image's feature rows (hi or lo): [feat_rows_h(rows) + a tile of slack][DSH] halfs
+    const size_t split_x = ((size_t)feat_rows_h(N) + 256) * DSH, split_q = ((size_t)feat_rows_h(L) + 256) * DSH;
+    Carver cv(ws);
+    WideWs w;
+    a.ldn = (N + 31) / 32 * 32;
+    a.scores = cv.take<float>(R * a.ldn);
+    a.part = cv.take<float>(R * ROW_CHUNKS * ROW_PART_FLOATS);
+    a.sel = cv.take<int32_t>(R * 4);
+    a.eq_before = cv.take<int32_t>(R * WIDE_RANGES);
+    w.served = cv.take<int32_t>(R);
+    w.xs_hi = cv.take<uint16_t>(split_x); w.xs_lo = cv.take<uint16_t>(split_x);
+    w.qs_hi = cv.take<uint16_t>(split_q); w.qs_lo = cv.take<uint16_t>(split_q);
+    w.amax_words = cv.take<unsigned>(2);              // [0] keys, [1] queries: bits of the image's largest feature (a 256-byte block)
+    w.bytes = cv.bytes();
+    return w;
 }
+size_t topk_wide_workspace_bytes(int N, int L) { WideArgs a; return wide_carve(nullptr, N, L, a).bytes; }
 
 int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const float* wq, const float* x, const float* mt,
                      const float* bs, const float* b2p, void* ws, float* agg, int32_t* deg, float* rowsum, RangeTag range) {
@@ -444,18 +457,7 @@ int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const
     a.g = g; a.mode = mode; a.k = k; a.mt = mt; a.bs = bs; a.b2p = b2p; a.agg = agg; a.deg = deg; a.rowsum = rowsum;
     a.wq = wq; a.x = x; a.rows_q = feat_rows(g.L); a.rows_x = feat_rows(g.N);
     const int Rmax = topk_wide_rows(g.N, g.L);
-    a.ldn = (g.N + 31) / 32 * 32;
-    char* p = static_cast<char*>(ws);
-    a.scores = reinterpret_cast<float*>(p); p += align_up((size_t)Rmax * a.ldn * sizeof(float), 256);
-    a.part = reinterpret_cast<float*>(p); p += align_up((size_t)Rmax * ROW_CHUNKS * ROW_PART_FLOATS * sizeof(float), 256);
-    a.sel = reinterpret_cast<int32_t*>(p); p += align_up((size_t)Rmax * 4 * sizeof(int32_t), 256);
-    a.eq_before = reinterpret_cast<int32_t*>(p); p += align_up((size_t)Rmax * WIDE_RANGES * sizeof(int32_t), 256);
-    int32_t* served = reinterpret_cast<int32_t*>(p); p += align_up((size_t)Rmax * sizeof(int32_t), 256);
-    uint16_t* xs_hi = reinterpret_cast<uint16_t*>(p); p += wide_split_bytes(g.N);
-    uint16_t* xs_lo = reinterpret_cast<uint16_t*>(p); p += wide_split_bytes(g.N);
-    uint16_t* qs_hi = reinterpret_cast<uint16_t*>(p); p += wide_split_bytes(g.L);
-    uint16_t* qs_lo = reinterpret_cast<uint16_t*>(p); p += wide_split_bytes(g.L);
-    unsigned* amax_words = reinterpret_cast<unsigned*>(p);              // [0] keys, [1] queries: bits of the image's largest feature
+    const WideWs w = wide_carve(ws, g.N, g.L, a);
     const int rows_q = feat_rows(g.L), rows_x = feat_rows(g.N);
     // scores on the fp16 matrix cores with split operands (round 5; on the fp32 matrix cores before that): the image's
     // features as fp16 pairs, 64 x = hi + lo (dense.hip's copies: rows of 216 halfs, columns 196.. zero), three products per score
@@ -467,12 +469,12 @@ int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const
             // (round 6) the features' split takes its power of two from the image's largest feature -- two small passes (53 + 3 MB at
             // 256^2: ~12 us of a 1.3 ms call) -- instead of the fixed 64: finite features of any size are served (a non-finite one still
             // sets the range word: the scale of an inf / NaN maximum is 1 and the split flags the value)
-            DAGL_HIP_TRY(hipMemsetAsync(amax_words, 0, 2 * sizeof(unsigned), s));
-            int rc = launch_absmax(s, (size_t)g.N * DS, x + (size_t)b * rows_x * DS, amax_words);
+            DAGL_HIP_TRY(hipMemsetAsync(w.amax_words, 0, 2 * sizeof(unsigned), s));
+            int rc = launch_absmax(s, (size_t)g.N * DS, x + (size_t)b * rows_x * DS, w.amax_words);
             if (rc) return rc;
-            if ((rc = launch_absmax(s, (size_t)g.L * DS, wq + (size_t)b * rows_q * DS, amax_words + 1))) return rc;
-            if ((rc = launch_feat_split(s, 1, g.N, rows_x, rows_xh, x + (size_t)b * rows_x * DS, xs_hi, xs_lo, range, amax_words))) return rc;
-            if ((rc = launch_feat_split(s, 1, g.L, rows_q, rows_qh, wq + (size_t)b * rows_q * DS, qs_hi, qs_lo, range, amax_words + 1))) return rc;
+            if ((rc = launch_absmax(s, (size_t)g.L * DS, wq + (size_t)b * rows_q * DS, w.amax_words + 1))) return rc;
+            if ((rc = launch_feat_split(s, 1, g.N, rows_x, rows_xh, x + (size_t)b * rows_x * DS, w.xs_hi, w.xs_lo, range, w.amax_words))) return rc;
+            if ((rc = launch_feat_split(s, 1, g.L, rows_q, rows_qh, wq + (size_t)b * rows_q * DS, w.qs_hi, w.qs_lo, range, w.amax_words + 1))) return rc;
         }
         for (int r0 = 0; r0 < g.L; r0 += Rmax) {
             const int R = (g.L - r0 < Rmax) ? g.L - r0 : Rmax;
@@ -480,9 +482,9 @@ int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const
             if (split_scores) {
                 Gemm16s gs;
                 gs.M = R; gs.N = g.N; gs.K = 224; gs.k_valid = DSH;
-                gs.a_hi = qs_hi + (size_t)r0 * DSH; gs.a_lo = qs_lo + (size_t)r0 * DSH; gs.lda = DSH; gs.a_rows = rows_qh - r0;
-                gs.b_hi = xs_hi; gs.b_lo = xs_lo; gs.ldb = DSH; gs.b_rows = rows_xh;
-                gs.C = a.scores; gs.ldc = a.ldn; gs.part = nullptr; gs.slices = 1; gs.scale_word = amax_words + 1; gs.scale_word_b = amax_words; gs.alpha0 = 1.0f;
+                gs.a_hi = w.qs_hi + (size_t)r0 * DSH; gs.a_lo = w.qs_lo + (size_t)r0 * DSH; gs.lda = DSH; gs.a_rows = rows_qh - r0;
+                gs.b_hi = w.xs_hi; gs.b_lo = w.xs_lo; gs.ldb = DSH; gs.b_rows = rows_xh;
+                gs.C = a.scores; gs.ldc = a.ldn; gs.part = nullptr; gs.slices = 1; gs.scale_word = w.amax_words + 1; gs.scale_word_b = w.amax_words; gs.alpha0 = 1.0f;
                 const int rc = launch_gemm16s(s, gs);
                 if (rc) return rc;
             } else {
@@ -501,7 +503,7 @@ int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const
             // go through the three kernels behind it
             a.served = nullptr;
             if (k <= WL_KMAX) {
-                a.served = served;
+                a.served = w.served;
                 hipLaunchKernelGGL(wide_list_kernel, dim3(R), dim3(WL_THREADS), 0, s, a);
                 DAGL_LAUNCH_CHECK("wide_list_kernel");
             }
