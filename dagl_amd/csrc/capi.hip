@@ -1415,6 +1415,14 @@ size_t dagl_ce_core_dense_workspace_bytes(int B, int H, int W, int backward) {
     return streamed > gemm_form ? streamed : gemm_form;
 }
 
+long long dagl_ce_core_dense_chunk_floats(long long floats) { return dense_train_chunk_floats(floats); }
+
+int dagl_ce_core_dense_plan(int B, int H, int W, int backward, int32_t out[6]) {
+    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && out, "dagl_ce_core_dense_plan: bad argument");
+    dense_train_plan(B, make_grid(H, W), backward != 0, out);
+    return DAGL_OK;
+}
+
 int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, const float* wq_rows, const float* x_rows,
                                const float* b2, const float* thr, const float* bias, float* out, float* lse, float* mu,
                                void* workspace, size_t ws_bytes, dagl_ce_info* info) {

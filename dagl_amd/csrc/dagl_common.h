@@ -803,6 +803,8 @@ int launch_unfold_dout(hipStream_t s, int B, const Grid& g, const float* dout, f
 int launch_dxbar(hipStream_t s, int B, int L, const float* wq_rows, const float* dmu, float* dxbar);
 // dense neighbourhoods under autograd (dense_train.hip): the dense formulation chunked over queries
 size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward);
+long long dense_train_chunk_floats(long long floats);                          // sets the chunk budget (<= 0: the built-in one), returns the previous
+void dense_train_plan(int B, const Grid& g, bool backward, int32_t out[6]);    // Lc, n_chunks, Bc, kslices, nk, h16
 // any patch geometry (generic.hip; ABI 406)
 size_t ce_generic_workspace_bytes(int B, int Cin, int H, int W, int ks, int s1, int s2, int C);
 int ce_generic_check(int B, int Cin, int H, int W, int ks, int s1, int s2, int C, int mode, int k);

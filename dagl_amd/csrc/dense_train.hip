@@ -17,10 +17,13 @@
 // All sums run in a fixed order: bit-reproducible gradients.
 #include "dagl_common.h"
 #include "wide_select.h"
+#include <atomic>
 
 namespace dagl {
 
-constexpr size_t DT_CHUNK_FLOATS = (size_t)128 << 20;      // floats per [chunk, N] matrix (512 MiB)
+constexpr size_t DT_CHUNK_FLOATS = (size_t)128 << 20;      // floats per [chunk, N] matrix (512 MiB): the built-in budget
+// the budget in force (dagl_ce_core_dense_chunk_floats: a testing and tuning hook); dt_plan reads it once per call
+static std::atomic<long long> dt_chunk_floats{(long long)DT_CHUNK_FLOATS};
 
 struct DtPlan {
     int Lc, n_chunks, Bc;            // queries per chunk, chunks per image, images per group
@@ -42,15 +45,16 @@ constexpr int DT_DK = 224;           // feature length 196 rounded up to the K s
 
 static DtPlan dt_plan(int B, const Grid& g, bool backward) {
     DtPlan p;
+    const size_t budget = (size_t)dt_chunk_floats.load(std::memory_order_relaxed);
     p.ldn = (g.N + 31) / 32 * 32;
     // (measured: skewing rows that are a multiple of 2 KiB long by 128 bytes does nothing for the row-per-block softmax kernels)
-    long long lc = (long long)(DT_CHUNK_FLOATS / (size_t)p.ldn) / 128 * 128;
+    long long lc = (long long)(budget / (size_t)p.ldn) / 128 * 128;
     if (lc < 128) lc = 128;
     p.Lc = (int)(lc < g.L ? lc : g.L);
     p.n_chunks = (g.L + p.Lc - 1) / p.Lc;
     p.Bc = 1;
     if (p.n_chunks == 1) {
-        long long bc = (long long)(DT_CHUNK_FLOATS / ((size_t)p.Lc * p.ldn));
+        long long bc = (long long)(budget / ((size_t)p.Lc * p.ldn));
         p.Bc = (int)(bc < 1 ? 1 : (bc > B ? B : bc));
     }
     Carver cv;
@@ -97,6 +101,15 @@ static DtPlan dt_plan(int B, const Grid& g, bool backward) {
 }
 
 size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward) { return dt_plan(B, g, backward).o_end; }
+
+long long dense_train_chunk_floats(long long floats) {
+    return dt_chunk_floats.exchange(floats > 0 ? floats : (long long)DT_CHUNK_FLOATS, std::memory_order_relaxed);
+}
+
+void dense_train_plan(int B, const Grid& g, bool backward, int32_t out[6]) {
+    const DtPlan p = dt_plan(B, g, backward);
+    out[0] = p.Lc; out[1] = p.n_chunks; out[2] = p.Bc; out[3] = p.kslices; out[4] = p.nk; out[5] = p.h16 ? 1 : 0;
+}
 
 
 // mu[b,l] = Wq_l . colsum / N (fp64 dot, as query_thresholds_kernel), mt = mu * thr: one wave per query, dense rows

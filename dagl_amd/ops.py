@@ -9,6 +9,7 @@ autograd and layouts and hand every operand to a wrapper here, which checks it (
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -888,6 +889,31 @@ def ce_core_dense_backward(d_out, wq_rows, x_rows, b2, thr, bias, saved: dict, w
                                           d_out.data_ptr(), d_wq.data_ptr(), d_x.data_ptr(), d_b2.data_ptr(),
                                           d_thr.data_ptr(), d_bias.data_ptr(), a, nbytes), "dagl_ce_core_dense_backward")
     return d_wq, d_x, d_b2, d_thr, d_bias
+
+
+DENSE_PLAN_FIELDS = ("Lc", "n_chunks", "Bc", "kslices", "nk", "h16")
+
+
+def dense_plan(B: int, H: int, W: int, backward: bool = True) -> dict:
+    """The launch plan of the dense / wide core ops at [B,H,W] under the chunk budget in force (``dagl_ce_core_dense_plan``, host
+    only): queries per chunk ``Lc``, chunks per image ``n_chunks``, images per group ``Bc``, split-K factor of d Wq ``kslices``,
+    K extent of the key-major operand copies ``nk``, ``h16`` = 1 where the backward's products may run on the fp16 matrix cores."""
+    out = (C.c_int32 * 6)()
+    check(_lib.load().dagl_ce_core_dense_plan(int(B), int(H), int(W), int(bool(backward)), out), "dagl_ce_core_dense_plan")
+    return dict(zip(DENSE_PLAN_FIELDS, (int(v) for v in out)))
+
+
+@contextlib.contextmanager
+def dense_chunk_budget(floats: int):
+    """Run the body with the dense core's chunk budget set to ``floats`` per [chunk, N] matrix (``dagl_ce_core_dense_chunk_floats``;
+    0 = the built-in 128 Mi) and put the previous value back afterwards, also when the body raises.  A testing and tuning hook: the
+    budget is process-wide, and a workspace sized under one budget is refused under a larger one (``ERR_WORKSPACE``)."""
+    lib = _lib.load()
+    before = lib.dagl_ce_core_dense_chunk_floats(int(floats))
+    try:
+        yield before
+    finally:
+        lib.dagl_ce_core_dense_chunk_floats(before)
 
 
 @_on_device

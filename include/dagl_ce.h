@@ -168,9 +168,10 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
 /* ABI version of THIS header: bumped whenever a struct or a signature declared here changes (round 3: dagl_ce_info is 40
  * bytes, dagl_ce_prologue takes `scratch`, dagl_ce_core_dense_forward takes `flags`, k <= 64; round 4: DAGL_FLAG_SAMPLED_TOPK,
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
- * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*).  A caller compares
+ * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
+ * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 409
+#define DAGL_ABI_VERSION 410
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -393,6 +394,19 @@ int    dagl_ce_core_dense_backward(void* stream, int B, int H, int W, int flags,
                                    const float* d_out,
                                    float* d_wq_rows, float* d_x_rows, float* d_b2, float* d_thr, float* d_bias,
                                    void* workspace, size_t ws_bytes);
+
+/* (ABI 410) A testing and tuning hook: the chunk budget of the four entry points above and below -- how many floats one [chunk, N]
+ * matrix may hold.  From it follow the queries per chunk (a multiple of 128, at least 128), the chunks per image, the images per group
+ * (only when an image is one chunk) and with them the split-K factor of d Wq and whether the backward's products may run on the fp16
+ * matrix cores (one chunk per image only).  dagl_ce_core_dense_chunk_floats sets it process-wide (0 or less restores the built-in 128 Mi floats
+ * = 512 MiB) and returns the value previously in force; it is a relaxed atomic that every call reads once, so a call in flight on another
+ * thread runs wholly under the old or wholly under the new value.  dagl_ce_core_dense_workspace_bytes follows the budget: a workspace
+ * sized under one budget and offered under a larger one is refused with DAGL_ERR_WORKSPACE before anything is launched.
+ * dagl_ce_core_dense_plan reports the launch plan the budget in force gives [B, H, W] (host only, no device access):
+ * out = { queries per chunk, chunks per image, images per group, split-K factor of d Wq, K extent of the key-major operand copies
+ * (N rounded up to 32 x that factor), 1 if the backward's products may run on the fp16 matrix cores else 0 }.                        */
+long long dagl_ce_core_dense_chunk_floats(long long floats);
+int       dagl_ce_core_dense_plan(int B, int H, int W, int backward, int32_t out[6]);
 
 /* The top-k modes with min(k, N) > DAGL_MAX_TOPK under autograd (the fixed-k variant takes any num_edge: top_k = min(num_edge, N),
  * GReccR2b_3mh_1-checkpoint.py:242-250; CA_model-checkpoint.py:134-143 uses 500): no lists -- the dense formulation above with

@@ -30,7 +30,7 @@ def _backward(lib, ws=_WS, ws_bytes=1 << 40, null=(), edges=EDGES):
 
 def test_version_and_segment(lib):
     from dagl_amd import _lib
-    assert lib.dagl_version() == 409 == _lib.ABI_VERSION
+    assert lib.dagl_version() == _lib.ABI_VERSION >= 409
     assert lib.dagl_graph_apply_segment() > 0
 
 
