@@ -1398,6 +1398,20 @@ static int read_edge_stats(hipStream_t s, const int64_t* stats, dagl_ce_info* in
     return DAGL_OK;
 }
 
+// the chunked fp32 GEMM form of a dense-core forward (a.ws / a.ws_bytes: the caller's buffer): the plan's bytes, then the statistics words
+static int dense_train_forward_call(const char* who, hipStream_t s, DenseTrainForward& a, dagl_ce_info* info) {
+    const size_t plan_bytes = dense_train_workspace_bytes(a.B, a.g, false), need = plan_bytes + DENSE_TRAIN_STATS_BYTES;
+    int rc;
+    if ((rc = check_workspace(who, a.ws, a.ws_bytes, need))) {
+        if (info) info->required_bytes = (int64_t)need;
+        return rc;
+    }
+    int64_t* stats = at<int64_t>(a.ws, plan_bytes);
+    a.ws_bytes = plan_bytes; a.stats = info ? stats : nullptr;
+    if ((rc = launch_dense_train_forward(s, a))) return rc;
+    return read_edge_stats(s, stats, info);
+}
+
 // forward on the inference path's streamed kernel (split-fp16 S and A V in one pass over the keys) when the image has enough
 // keys for the screen's machinery it borrows (row-maximum scan); the chunked fp32 GEMM formulation otherwise
 static bool dense_core_streamed(int H, int W) { return (int64_t)H * W >= SCREEN_MIN_KEYS; }
@@ -1431,7 +1445,6 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
     int rc;
     if ((rc = check_workspace("dagl_ce_core_dense_forward", workspace, ws_bytes, 0))) return rc;
     const Grid g = make_grid(H, W);
-    hipStream_t s = (hipStream_t)stream;
     bool left_range = false;
     if (dense_core_streamed(H, W) && !(flags & DAGL_FLAG_EXACT_SCAN)) {
         const CoreIn core{wq_rows, x_rows, b2, thr, bias, nullptr, nullptr, nullptr, nullptr, mu, lse};
@@ -1444,16 +1457,10 @@ int dagl_ce_core_dense_forward(void* stream, int B, int H, int W, int flags, con
         left_range = true;
     }
     reset_info(info, (int64_t)dense_train_workspace_bytes(B, g, false), 5);
-    // the two statistics words live at the very end of the caller's buffer (past the plan)
-    const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
-    if ((rc = check_workspace("dagl_ce_core_dense_forward", workspace, ws_bytes, need))) {
-        if (info) info->required_bytes = (int64_t)need;
-        return rc;
-    }
-    int64_t* stats = at<int64_t>(workspace, need - 256);
-    if ((rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, thr, bias, out, lse, mu, workspace, need - 256,
-                                         info ? stats : nullptr))) return rc;
-    if ((rc = read_edge_stats(s, stats, info))) return rc;
+    DenseTrainForward a;
+    a.B = B; a.g = g; a.wq_rows = wq_rows; a.x_rows = x_rows; a.b2 = b2; a.thr = thr; a.bias = bias;
+    a.out = out; a.lse = lse; a.mu = mu; a.ws = workspace; a.ws_bytes = ws_bytes;
+    if ((rc = dense_train_forward_call("dagl_ce_core_dense_forward", (hipStream_t)stream, a, info))) return rc;
     if (info) info->range_fallback = left_range ? 1 : 0;
     return DAGL_OK;
 }
@@ -1466,8 +1473,11 @@ int dagl_ce_core_dense_backward(void* stream, int B, int H, int W, int flags, co
                  d_x_rows && d_b2 && d_thr && d_bias && (flags & ~DAGL_FLAG_EXACT_SCAN) == 0, "dagl_ce_core_dense_backward: bad argument");
     const int rc = check_workspace("dagl_ce_core_dense_backward", workspace, ws_bytes, 0);
     if (rc) return rc;
-    return launch_dense_train_backward((hipStream_t)stream, B, make_grid(H, W), wq_rows, x_rows, b2, thr, bias, lse, mu, d_out,
-                                       d_wq_rows, d_x_rows, d_b2, d_thr, d_bias, workspace, ws_bytes, (flags & DAGL_FLAG_EXACT_SCAN) != 0);
+    DenseTrainBackward a;
+    a.B = B; a.g = make_grid(H, W); a.wq_rows = wq_rows; a.x_rows = x_rows; a.b2 = b2; a.thr = thr; a.bias = bias;
+    a.lse = lse; a.dout = d_out; a.dwq_rows = d_wq_rows; a.dx_rows = d_x_rows; a.db2 = d_b2; a.dthr = d_thr; a.dbias = d_bias;
+    a.ws = workspace; a.ws_bytes = ws_bytes; a.fp32_products = (flags & DAGL_FLAG_EXACT_SCAN) != 0;
+    return launch_dense_train_backward((hipStream_t)stream, a);
 }
 
 // ---- top-k modes whose neighbourhoods exceed the lists (min(k, N) > DAGL_MAX_TOPK) under autograd: the dense formulation of
@@ -1482,15 +1492,11 @@ int dagl_ce_core_wide_forward(void* stream, int B, int H, int W, int mode, int k
     if ((rc = check_workspace("dagl_ce_core_wide_forward", workspace, ws_bytes, 0))) return rc;
     const Grid g = make_grid(H, W);
     if (k > g.N) k = g.N;                                              // top_k = min(num_edge, N)
-    const size_t need = dense_train_workspace_bytes(B, g, false) + 256;
-    reset_info(info, (int64_t)need, 5);
-    if ((rc = check_workspace("dagl_ce_core_wide_forward", workspace, ws_bytes, need))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    int64_t* stats = at<int64_t>(workspace, need - 256);
-    const bool heads = mode != DAGL_MODE_TOPK;
-    if ((rc = launch_dense_train_forward(s, B, g, wq_rows, x_rows, b2, heads ? thr : nullptr, heads ? bias : nullptr, out, nullptr, nullptr,
-                                         workspace, need - 256, info ? stats : nullptr, mode, k))) return rc;
-    return read_edge_stats(s, stats, info);
+    reset_info(info, (int64_t)(dense_train_workspace_bytes(B, g, false) + DENSE_TRAIN_STATS_BYTES), 5);
+    DenseTrainForward a;
+    a.B = B; a.g = g; a.mode = mode; a.k = k; a.wq_rows = wq_rows; a.x_rows = x_rows; a.b2 = b2; a.thr = thr; a.bias = bias;
+    a.out = out; a.ws = workspace; a.ws_bytes = ws_bytes;
+    return dense_train_forward_call("dagl_ce_core_wide_forward", (hipStream_t)stream, a, info);
 }
 
 int dagl_ce_core_wide_backward(void* stream, int B, int H, int W, int mode, int k, const float* wq_rows, const float* x_rows,
@@ -1504,10 +1510,11 @@ int dagl_ce_core_wide_backward(void* stream, int B, int H, int W, int mode, int 
     if (rc) return rc;
     const Grid g = make_grid(H, W);
     if (k > g.N) k = g.N;
-    const bool heads = mode != DAGL_MODE_TOPK;
-    return launch_dense_train_backward((hipStream_t)stream, B, g, wq_rows, x_rows, b2, heads ? thr : nullptr, heads ? bias : nullptr, nullptr,
-                                       nullptr, d_out, d_wq_rows, d_x_rows, d_b2, heads ? d_thr : nullptr, heads ? d_bias : nullptr,
-                                       workspace, ws_bytes, true, mode, k);
+    DenseTrainBackward a;
+    a.B = B; a.g = g; a.mode = mode; a.k = k; a.wq_rows = wq_rows; a.x_rows = x_rows; a.b2 = b2; a.thr = thr; a.bias = bias;
+    a.dout = d_out; a.dwq_rows = d_wq_rows; a.dx_rows = d_x_rows; a.db2 = d_b2; a.dthr = d_thr; a.dbias = d_bias;
+    a.ws = workspace; a.ws_bytes = ws_bytes; a.fp32_products = true;
+    return launch_dense_train_backward((hipStream_t)stream, a);
 }
 
 size_t dagl_gemm_f32_scratch_floats(int batch, int M, int N, int K) {

@@ -803,6 +803,9 @@ int launch_unfold_dout(hipStream_t s, int B, const Grid& g, const float* dout, f
 int launch_dxbar(hipStream_t s, int B, int L, const float* wq_rows, const float* dmu, float* dxbar);
 // dense neighbourhoods under autograd (dense_train.hip): the dense formulation chunked over queries
 size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward);
+// the forward's entry points keep their two statistics words behind those bytes, in a tail of this size (ops.py adds the same 256 on
+// its side of the ABI)
+constexpr size_t DENSE_TRAIN_STATS_BYTES = 256;
 long long dense_train_chunk_floats(long long floats);                          // sets the chunk budget (<= 0: the built-in one), returns the previous
 void dense_train_plan(int B, const Grid& g, bool backward, int32_t out[6]);    // Lc, n_chunks, Bc, kslices, nk, h16
 // any patch geometry (generic.hip; ABI 406)
@@ -820,16 +823,25 @@ int launch_ce_generic_core_forward(hipStream_t s, int B, int H, int W, int ks, i
 int launch_ce_generic_core_backward(hipStream_t s, int B, int H, int W, int ks, int s1, int s2, int C, float scale, int mode, int k,
                                     const float* wq, const float* x, const float* b2p, const float* thr, const float* bias, const float* d_out,
                                     float* d_wq, float* d_x, float* d_b2p, float* d_thr, float* d_bias, void* workspace);
-int launch_dense_train_forward(hipStream_t s, int B, const Grid& g, const float* wq_rows, const float* x_rows, const float* b2,
-                               const float* thr, const float* bias, float* out, float* lse /*[B,L,2]*/, float* mu /*[B,L]*/,
-                               void* ws, size_t ws_bytes, int64_t* stats_dev /* [2]: edges, max degree */,
-                               int mode = DAGL_MODE_ADAPTIVE, int k = 0 /* the wide top-k modes: DAGL_MODE_TOPK (thr / bias null) / _ADAPTIVE_TOPK;
-                                                                          lse / mu may be null (kept in the workspace) */);
-int launch_dense_train_backward(hipStream_t s, int B, const Grid& g, const float* wq_rows, const float* x_rows, const float* b2,
-                                const float* thr, const float* bias, const float* lse, const float* mu, const float* dout,
-                                float* dwq_rows, float* dx_rows, float* db2, float* dthr, float* dbias, void* ws, size_t ws_bytes,
-                                bool fp32_products = false,      // false: the five products on the fp16 matrix cores, split operands (one-chunk shapes)
-                                int mode = DAGL_MODE_ADAPTIVE, int k = 0);
+// operands of both directions; thr / bias and the backward's d thr / d bias are not looked at in DAGL_MODE_TOPK, which has no threshold heads
+struct DenseTrainArgs {
+    int B = 0; Grid g = {}; int mode = DAGL_MODE_ADAPTIVE, k = 0;      // k: the wide top-k modes DAGL_MODE_TOPK / _ADAPTIVE_TOPK
+    const float *wq_rows = nullptr, *x_rows = nullptr, *b2 = nullptr, *thr = nullptr, *bias = nullptr;
+    void* ws = nullptr; size_t ws_bytes = 0;
+    bool heads() const { return mode != DAGL_MODE_TOPK; }
+};
+struct DenseTrainForward : DenseTrainArgs {
+    float* out = nullptr;
+    float *lse = nullptr /*[B,L,2]*/, *mu = nullptr /*[B,L]*/;          // null: kept in the workspace
+    int64_t* stats = nullptr;                                          // device words [2]: edges, max degree; null: not computed
+};
+struct DenseTrainBackward : DenseTrainArgs {
+    const float *lse = nullptr, *dout = nullptr;
+    float *dwq_rows = nullptr, *dx_rows = nullptr, *db2 = nullptr, *dthr = nullptr, *dbias = nullptr;
+    bool fp32_products = false;      // false: the five products on the fp16 matrix cores, split operands (one-chunk shapes)
+};
+int launch_dense_train_forward(hipStream_t s, const DenseTrainForward& a);
+int launch_dense_train_backward(hipStream_t s, const DenseTrainBackward& a);
 int launch_colsum_rows(hipStream_t s, int B, int N, const float* rows, double* colsum);              // per-lane list length used for a requested k (4/8/16/32)
 
 // export of the patch graph as CSR (graph.hip): plan = geometry, chunk height and the carve of the workspace both phases share

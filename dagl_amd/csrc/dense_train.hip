@@ -28,16 +28,12 @@ static std::atomic<long long> dt_chunk_floats{(long long)DT_CHUNK_FLOATS};
 struct DtPlan {
     int Lc, n_chunks, Bc;            // queries per chunk, chunks per image, images per group
     long long ldn;                   // leading dimension of the [L,N] chunk matrices (N rounded up to 32)
-    size_t o_sbuf, o_abuf, o_vrows, o_dvrows, o_dagg, o_agg, o_b2p, o_colsum, o_mt, o_dmu, o_dxbar, o_deg, o_rowsum, o_sel, o_lse, o_mu, o_end;
-    // split-fp16 backward (one chunk per image group only): hi / lo operand copies, each `..._h` halfs long (lo follows hi)
-    bool h16;
+    bool h16;                        // split-fp16 backward (one chunk per image group only)
     int Lp, kslices;                 // L rounded up to 32; split-K of d Wq
     int nk;                          // N rounded up to 32 kslices: the K extent of the copies whose rows run over the keys
     long long ldl, ldk;              // leading dimensions (halfs) of the copies whose rows run over the queries / the keys: extent + 64 -- a
                                      // power-of-two row stride (L = 1024: 2 KiB, N = 16384: 32 KiB) sends the 16 rows of every LDS-DMA piece
                                      // to the same memory channel (the products ran at a third of the fp32 ones' rate)
-    size_t o_words, o_dgk, o_dgt, o_vk, o_xk, o_xt, o_wqk, o_wqt, o_dsk, o_dst, o_at, o_part;
-    size_t dgk_h, dgt_h, vk_h, xk_h, xt_h, wqk_h, wqt_h, dsk_h, dst_h, at_h;
 };
 
 constexpr int DT_PK = 800;           // value-patch length 784 rounded up to the K step (50 taps of 16)
@@ -57,24 +53,6 @@ static DtPlan dt_plan(int B, const Grid& g, bool backward) {
         long long bc = (long long)(budget / ((size_t)p.Lc * p.ldn));
         p.Bc = (int)(bc < 1 ? 1 : (bc > B ? B : bc));
     }
-    Carver cv;
-    const size_t chunk = (size_t)p.Bc * p.Lc * p.ldn * sizeof(float);
-    p.o_sbuf = cv.reserve(chunk);
-    p.o_abuf = backward ? cv.reserve(chunk) : 0;
-    p.o_vrows = cv.reserve((size_t)p.Bc * g.N * P * sizeof(float));
-    p.o_dvrows = backward ? cv.reserve((size_t)p.Bc * g.N * P * sizeof(float)) : 0;
-    p.o_dagg = backward ? cv.reserve((size_t)B * g.L * P * sizeof(float)) : 0;
-    p.o_agg = backward ? 0 : cv.reserve((size_t)B * g.L * P * sizeof(float));
-    p.o_b2p = cv.reserve((size_t)B * g.Hp * g.Wp * CH * sizeof(float));
-    p.o_colsum = cv.reserve((size_t)B * DS * sizeof(double));
-    p.o_mt = cv.reserve((size_t)B * g.L * sizeof(float));
-    p.o_dmu = cv.reserve((size_t)B * g.L * sizeof(float));
-    p.o_dxbar = cv.reserve((size_t)B * D * sizeof(float));
-    p.o_deg = cv.reserve((size_t)B * g.L * sizeof(int32_t));
-    p.o_rowsum = cv.reserve((size_t)B * g.L * sizeof(float));
-    p.o_sel = cv.reserve((size_t)B * g.L * 2 * sizeof(int32_t));      // wide top-k modes: (sort key of the k-th best score, last key index taken at it)
-    p.o_lse = cv.reserve((size_t)B * g.L * 2 * sizeof(float));        // (their entry points keep the softmax statistics and the row means here)
-    p.o_mu = cv.reserve((size_t)B * g.L * sizeof(float));
     p.h16 = backward && p.n_chunks == 1;
     p.Lp = (g.L + 31) / 32 * 32;
     p.kslices = 1;
@@ -85,22 +63,78 @@ static DtPlan dt_plan(int B, const Grid& g, bool backward) {
     }
     p.nk = (g.N + 32 * p.kslices - 1) / (32 * p.kslices) * (32 * p.kslices);
     p.ldl = p.Lp + 64; p.ldk = p.nk + 64;
-    if (p.h16) {
-        const size_t bc = (size_t)p.Bc;
-        p.dgk_h = bc * g.L * DT_PK; p.dgt_h = bc * P * p.ldl; p.vk_h = bc * g.N * DT_PK;
-        p.xk_h = bc * g.N * DT_DK; p.xt_h = bc * D * p.ldk; p.wqk_h = bc * g.L * DT_DK; p.wqt_h = bc * D * p.ldl;
-        p.dsk_h = bc * p.Lc * p.ldk; p.dst_h = bc * g.N * p.ldl; p.at_h = bc * g.N * p.ldl;
-        p.o_words = cv.reserve(256);
-        p.o_dgk = cv.reserve(2 * p.dgk_h * 2); p.o_dgt = cv.reserve(2 * p.dgt_h * 2); p.o_vk = cv.reserve(2 * p.vk_h * 2);
-        p.o_xk = cv.reserve(2 * p.xk_h * 2); p.o_xt = cv.reserve(2 * p.xt_h * 2); p.o_wqk = cv.reserve(2 * p.wqk_h * 2); p.o_wqt = cv.reserve(2 * p.wqt_h * 2);
-        p.o_dsk = cv.reserve(2 * p.dsk_h * 2); p.o_dst = cv.reserve(2 * p.dst_h * 2); p.o_at = cv.reserve(2 * p.at_h * 2);
-        p.o_part = cv.reserve((size_t)p.kslices * bc * g.L * D * sizeof(float));
-    }
-    p.o_end = cv.bytes();
     return p;
 }
 
-size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward) { return dt_plan(B, g, backward).o_end; }
+// The operands of the products, each described ONCE (dt_carve) for the launch that writes it and the products that read it.
+// fp32: one matrix per image of the group, `stride` floats apart, rows `ld` floats apart; kc: the product's contraction index runs
+// along the rows (Gemm32::a_kc / b_kc), down(): the same matrix contracted over its row index
+template <class T>
+struct MatT {
+    T* p = nullptr; long long ld = 0, stride = 0; int kc = 1;
+    MatT() = default;
+    MatT(T* p_, long long ld_, long long stride_, int kc_ = 1) : p(p_), ld(ld_), stride(stride_), kc(kc_) {}
+    template <class U> MatT(const MatT<U>& o) : p(o.p), ld(o.ld), stride(o.stride), kc(o.kc) {}      // a written matrix, read
+    MatT down() const { return MatT(p, ld, stride, 0); }
+};
+using Mat32 = MatT<const float>;
+using Out32 = MatT<float>;
+// split fp16 (gemm16s.hip), K-contiguous rows of `ld` halfs: s x = hi + lo, lo `lo` halfs behind hi; s from *word (the tensor's largest
+// magnitude, fcg_scale_of) or `fixed` where there is no word
+struct Split16 { unsigned short* hi = nullptr; size_t lo = 0; long long ld = 0, stride = 0; const unsigned* word = nullptr; float fixed = 1.f; };
+
+// the workspace of one call: the one walk that sizes it (null base) and hands its regions to the launches
+struct DtWs {
+    Out32 S, A, V, dV;               // [Bc][Lc][ldn] scores -> weights / d S, d A -> weights (backward); [Bc][N][P] value patches and their gradient
+    float *dagg, *agg, *b2p;         // [B,L,P] d agg (backward) / agg (forward); b2 padded NHWC
+    double* colsum; float *mt, *dmu, *dxbar; int32_t* deg; float* rowsum;
+    int32_t* sel;                    // wide top-k modes: (sort key of the k-th best score, last key index taken at it)
+    float *lse, *mu;                 // (their entry points keep the softmax statistics and the row means here)
+    unsigned* words;                 // h16: the scale words -- 0 d agg, 1 values, 2 X, 3 Wq, 4 d S
+    Split16 dgk, vk, xk, wqk, dsk;   // h16: d agg, V, X, Wq, d S by rows ...
+    Split16 dgt, xt, wqt, dst, at;   // ... and d agg, X, Wq, d S, A transposed (A <= 1: 2^13, no word)
+    float* part;                     // h16: split-K partial sums of d Wq
+    size_t bytes;
+};
+static DtWs dt_carve(void* ws, int B, const Grid& g, const DtPlan& p, bool backward) {
+    Carver cv(ws);
+    DtWs w{};
+    const size_t chunk = (size_t)p.Bc * p.Lc * p.ldn, BL = (size_t)B * g.L;
+    const long long sS = (long long)p.Lc * p.ldn, sV = (long long)g.N * P;
+    w.S = Out32(cv.take<float>(chunk), p.ldn, sS);
+    if (backward) w.A = Out32(cv.take<float>(chunk), p.ldn, sS);
+    w.V = Out32(cv.take<float>((size_t)p.Bc * sV), P, sV);
+    if (backward) w.dV = Out32(cv.take<float>((size_t)p.Bc * sV), P, sV);
+    (backward ? w.dagg : w.agg) = cv.take<float>(BL * P);
+    w.b2p = cv.take<float>((size_t)B * g.Hp * g.Wp * CH);
+    w.colsum = cv.take<double>((size_t)B * DS);
+    w.mt = cv.take<float>(BL);
+    w.dmu = cv.take<float>(BL);
+    w.dxbar = cv.take<float>((size_t)B * D);
+    w.deg = cv.take<int32_t>(BL);
+    w.rowsum = cv.take<float>(BL);
+    w.sel = cv.take<int32_t>(BL * 2);
+    w.lse = cv.take<float>(BL * 2);
+    w.mu = cv.take<float>(BL);
+    if (p.h16) {
+        w.words = cv.take<unsigned>(64);
+        const auto split = [&](int rows, long long ld, int word) {       // [Bc][rows][ld] halfs, hi then lo
+            const size_t halfs = (size_t)p.Bc * rows * ld;
+            Split16 o;
+            o.hi = cv.take<unsigned short>(2 * halfs); o.lo = halfs; o.ld = ld; o.stride = (long long)rows * ld;
+            if (word < 0) o.fixed = 8192.f; else if (w.words) o.word = w.words + word;
+            return o;
+        };
+        w.dgk = split(g.L, DT_PK, 0); w.dgt = split(P, p.ldl, 0); w.vk = split(g.N, DT_PK, 1);
+        w.xk = split(g.N, DT_DK, 2); w.xt = split(D, p.ldk, 2); w.wqk = split(g.L, DT_DK, 3); w.wqt = split(D, p.ldl, 3);
+        w.dsk = split(p.Lc, p.ldk, 4); w.dst = split(g.N, p.ldl, 4); w.at = split(g.N, p.ldl, -1);
+        w.part = cv.take<float>((size_t)p.kslices * p.Bc * g.L * D);
+    }
+    w.bytes = cv.bytes();
+    return w;
+}
+
+size_t dense_train_workspace_bytes(int B, const Grid& g, bool backward) { return dt_carve(nullptr, B, g, dt_plan(B, g, backward), backward).bytes; }
 
 long long dense_train_chunk_floats(long long floats) {
     return dt_chunk_floats.exchange(floats > 0 ? floats : (long long)DT_CHUNK_FLOATS, std::memory_order_relaxed);
@@ -337,26 +371,32 @@ __global__ __launch_bounds__(256) void dense_softmax_bwd_kernel(int N, long long
 // elements, 1 or 2 blocks per CU: 832 us against this kernel's 867 at [8, 1024 x 16384], whatever the variant.  2.1 GB in 0.83 ms;
 // this kernel without its stores: 666 us -- one load in flight per thread and pass; the register form has all of a row's loads in
 // flight but one block per CU, whose load / reduce / store phases do not overlap with anything: ~26 us per row and CU either way.)
-static int launch_dense_softmax_bwd(hipStream_t s, int rows, int nb, int N, long long ldn, int L, int l0, int Lc, float* sbuf, float* abuf,
-                                    const float* mt, const float* bs, const float* lse, const float* mu, const float* thr, float* dthr,
-                                    float* dbias, float* dmu, int b0, unsigned* ds_word, int mode = DAGL_MODE_ADAPTIVE,
-                                    const int32_t* sel = nullptr) {
-#define DT_BWD(M_) hipLaunchKernelGGL(dense_softmax_bwd_kernel<M_>, dim3(rows, nb), dim3(256), 0, s, N, ldn, L, l0, Lc, sbuf, abuf, mt, bs, lse, \
-                                      mu, thr, dthr, dbias, dmu, b0, ds_word, sel)
-    if (mode == DAGL_MODE_TOPK) DT_BWD(1); else if (mode == DAGL_MODE_ADAPTIVE_TOPK) DT_BWD(2); else DT_BWD(0);
-#undef DT_BWD
-    DAGL_LAUNCH_CHECK("dense_softmax_bwd_kernel");
+
+// a chunk of queries of an image group: the coordinates the row-per-block kernels index with (grid = lc rows x nb images)
+struct DtChunk { int b0, nb, l0, lc; int N; long long ldn; int L, Lc; };
+static DtChunk dt_chunk(const Grid& g, const DtPlan& p, int b0, int nb, int l0) {
+    return {b0, nb, l0, (g.L - l0 < p.Lc) ? g.L - l0 : p.Lc, g.N, p.ldn, g.L, p.Lc};
+}
+// the chunk's rows of a [B, L, cols] tensor (one row per query) / its images' rows of a [B, N, cols] one (one row per key)
+template <class T> static MatT<T> dt_query_rows(const DtChunk& c, T* t, int cols) { return {t + ((size_t)c.b0 * c.L + c.l0) * cols, cols, (long long)c.L * cols}; }
+template <class T> static MatT<T> dt_key_rows(const DtChunk& c, T* t, int cols) { return {t + (size_t)c.b0 * c.N * cols, cols, (long long)c.N * cols}; }
+
+// wide top-k modes: the rows' (T, jt) from the chunk's scores
+static int launch_dt_select(hipStream_t s, const DtChunk& c, int mode, int k, const DtWs& w, const float* bs) {
+    const auto kern = mode == DAGL_MODE_ADAPTIVE_TOPK ? dt_select_kernel<true> : dt_select_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(c.lc, c.nb), dim3(256), 0, s, c.N, c.ldn, c.L, c.l0, c.Lc, k, w.S.p, w.mt, bs, w.sel, c.b0);
+    DAGL_LAUNCH_CHECK("dt_select_kernel");
     return DAGL_OK;
 }
 
-// wide top-k modes: the rows' (T, jt) from the chunk's scores
-static int launch_dt_select(hipStream_t s, int rows, int nb, int N, long long ldn, int L, int l0, int Lc, int k, int mode, const float* sbuf,
-                            const float* mt, const float* bs, int32_t* sel, int b0) {
-    if (mode == DAGL_MODE_ADAPTIVE_TOPK)
-        hipLaunchKernelGGL(dt_select_kernel<true>, dim3(rows, nb), dim3(256), 0, s, N, ldn, L, l0, Lc, k, sbuf, mt, bs, sel, b0);
-    else
-        hipLaunchKernelGGL(dt_select_kernel<false>, dim3(rows, nb), dim3(256), 0, s, N, ldn, L, l0, Lc, k, sbuf, mt, bs, sel, b0);
-    DAGL_LAUNCH_CHECK("dt_select_kernel");
+// S, d A -> d S, A over the chunk's rows; ds_word: the split-fp16 products' scale word of d S, or null
+static int launch_dense_softmax_bwd(hipStream_t s, const DtChunk& c, const DenseTrainBackward& a, const DtWs& w, const float* mu,
+                                    unsigned* ds_word) {
+    const auto kern = a.mode == DAGL_MODE_TOPK ? dense_softmax_bwd_kernel<1>
+                    : a.mode == DAGL_MODE_ADAPTIVE_TOPK ? dense_softmax_bwd_kernel<2> : dense_softmax_bwd_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(c.lc, c.nb), dim3(256), 0, s, c.N, c.ldn, c.L, c.l0, c.Lc, w.S.p, w.A.p, w.mt, a.bias, a.lse, mu, a.thr,
+                       a.dthr, a.dbias, w.dmu, c.b0, ds_word, w.sel);
+    DAGL_LAUNCH_CHECK("dense_softmax_bwd_kernel");
     return DAGL_OK;
 }
 
@@ -400,11 +440,10 @@ __global__ __launch_bounds__(256) void dt_fold_dv_kernel(Grid g, int nb, const f
     }
 }
 
-static Gemm32 dt_gemm(int M, int N, int K, int batch, const float* A, long long lda, long long sA, int a_kc, const float* Bm,
-                      long long ldb, long long sB, int b_kc, float* C, long long ldc, long long sC, float beta, bool grad = false) {
+static Gemm32 dt_gemm(int M, int N, int K, int batch, const Mat32& A, const Mat32& Bm, const Out32& C, float beta, bool grad = false) {
     Gemm32 g;
-    g.M = M; g.N = N; g.K = K; g.batch = batch; g.A = A; g.lda = lda; g.sA = sA; g.a_kc = a_kc;
-    g.B = Bm; g.ldb = ldb; g.sB = sB; g.b_kc = b_kc; g.C = C; g.ldc = ldc; g.sC = sC;
+    g.M = M; g.N = N; g.K = K; g.batch = batch; g.A = A.p; g.lda = A.ld; g.sA = A.stride; g.a_kc = A.kc;
+    g.B = Bm.p; g.ldb = Bm.ld; g.sB = Bm.stride; g.b_kc = Bm.kc; g.C = C.p; g.ldc = C.ld; g.sC = C.stride;
     g.alpha = 1.0f; g.beta = beta; g.bias = nullptr; g.relu = 0;
     // S: chains of 48 products; the long forward contraction A V: 128.  Gradient products (1e-3 bar, contractions of at
     // most a few thousand terms per chunk of queries / 16 384 keys) run unchunked: 140 instead of 236 registers, a third
@@ -413,59 +452,48 @@ static Gemm32 dt_gemm(int M, int N, int K, int batch, const float* A, long long 
     return g;
 }
 
-static int dt_prepare(hipStream_t s, int B, const Grid& g, const DtPlan& p, void* ws, const float* wq_rows, const float* x_rows,
-                      const float* b2, const float* thr, float* mu) {
+// padded b2, and with threshold heads the keys' column sums and mt = mu thr
+static int dt_prepare(hipStream_t s, const DenseTrainArgs& a, const DtWs& w, float* mu) {
     int rc;
-    if ((rc = launch_pad_nhwc(s, B, g.H, g.W, b2, at<float>(ws, p.o_b2p)))) return rc;
-    if (thr == nullptr) return DAGL_OK;                  // (the fixed-k mode has no threshold heads)
-    if ((rc = launch_colsum_rows(s, B, g.N, x_rows, at<double>(ws, p.o_colsum)))) return rc;
-    hipLaunchKernelGGL(dt_thresholds_kernel, dim3((g.L + 3) / 4, B), dim3(256), 0, s, g.L, g.N, wq_rows,
-                       at<double>(ws, p.o_colsum), thr, at<float>(ws, p.o_mt), mu);
+    if ((rc = launch_pad_nhwc(s, a.B, a.g.H, a.g.W, a.b2, w.b2p))) return rc;
+    if (a.thr == nullptr) return DAGL_OK;                // (the fixed-k mode has no threshold heads)
+    if ((rc = launch_colsum_rows(s, a.B, a.g.N, a.x_rows, w.colsum))) return rc;
+    hipLaunchKernelGGL(dt_thresholds_kernel, dim3((a.g.L + 3) / 4, a.B), dim3(256), 0, s, a.g.L, a.g.N, a.wq_rows, w.colsum, a.thr, w.mt, mu);
     DAGL_LAUNCH_CHECK("dt_thresholds_kernel");
     return DAGL_OK;
 }
 
-int launch_dense_train_forward(hipStream_t s, int B, const Grid& g, const float* wq_rows, const float* x_rows, const float* b2,
-                               const float* thr, const float* bias, float* out, float* lse, float* mu, void* ws, size_t ws_bytes,
-                               int64_t* stats_dev, int mode, int k) {
+int launch_dense_train_forward(hipStream_t s, const DenseTrainForward& args) {
+    DenseTrainForward a = args;
+    if (!a.heads()) a.thr = a.bias = nullptr;
+    const int B = a.B; const Grid& g = a.g;
     const DtPlan p = dt_plan(B, g, false);
-    if (lse == nullptr) lse = at<float>(ws, p.o_lse);
-    if (mu == nullptr) mu = at<float>(ws, p.o_mu);
-    int32_t* sel = at<int32_t>(ws, p.o_sel);
-    if (ws_bytes < p.o_end) { set_error("dense forward: workspace %zu B < required %zu B", ws_bytes, p.o_end); return DAGL_ERR_WORKSPACE; }
+    const DtWs w = dt_carve(a.ws, B, g, p, false);
+    if (a.ws_bytes < w.bytes) { set_error("dense forward: workspace %zu B < required %zu B", a.ws_bytes, w.bytes); return DAGL_ERR_WORKSPACE; }
+    float* lse = a.lse ? a.lse : w.lse;
+    float* mu = a.mu ? a.mu : w.mu;
     int rc;
-    if ((rc = dt_prepare(s, B, g, p, ws, wq_rows, x_rows, b2, thr, mu))) return rc;
-    float* sbuf = at<float>(ws, p.o_sbuf);
-    float* vrows = at<float>(ws, p.o_vrows);
-    float* agg = at<float>(ws, p.o_agg);
-    const float* b2p = at<float>(ws, p.o_b2p);
-    const float* mt = at<float>(ws, p.o_mt);
-    int32_t* deg = at<int32_t>(ws, p.o_deg);
-    float* rowsum = at<float>(ws, p.o_rowsum);
+    if ((rc = dt_prepare(s, a, w, mu))) return rc;
+    const auto softmax = a.mode == DAGL_MODE_TOPK ? dense_softmax_fwd_kernel<1>
+                       : a.mode == DAGL_MODE_ADAPTIVE_TOPK ? dense_softmax_fwd_kernel<2> : dense_softmax_fwd_kernel<0>;
     for (int b0 = 0; b0 < B; b0 += p.Bc) {
         const int nb = (B - b0 < p.Bc) ? B - b0 : p.Bc;
-        if ((rc = launch_unfold_values(s, nb, g, b2p + (size_t)b0 * g.Hp * g.Wp * CH, vrows))) return rc;
+        if ((rc = launch_unfold_values(s, nb, g, w.b2p + (size_t)b0 * g.Hp * g.Wp * CH, w.V.p))) return rc;
         for (int l0 = 0; l0 < g.L; l0 += p.Lc) {
-            const int lc = (g.L - l0 < p.Lc) ? g.L - l0 : p.Lc;
+            const DtChunk c = dt_chunk(g, p, b0, nb, l0);
             // S = Wq X^T
-            if ((rc = launch_gemm32(s, dt_gemm(lc, g.N, D, nb, wq_rows + ((size_t)b0 * g.L + l0) * D, D, (long long)g.L * D, 1,
-                                               x_rows + (size_t)b0 * g.N * D, D, (long long)g.N * D, 1,
-                                               sbuf, p.ldn, (long long)p.Lc * p.ldn, 0.f)))) return rc;
-            if (mode != DAGL_MODE_ADAPTIVE)
-                if ((rc = launch_dt_select(s, lc, nb, g.N, p.ldn, g.L, l0, p.Lc, k, mode, sbuf, mt, bias, sel, b0))) return rc;
-#define DT_FWD(M_) hipLaunchKernelGGL(dense_softmax_fwd_kernel<M_>, dim3(lc, nb), dim3(256), 0, s, g.N, p.ldn, g.L, l0, p.Lc, sbuf, mt, bias, \
-                                      lse, deg, rowsum, b0, sel)
-            if (mode == DAGL_MODE_TOPK) DT_FWD(1); else if (mode == DAGL_MODE_ADAPTIVE_TOPK) DT_FWD(2); else DT_FWD(0);
-#undef DT_FWD
+            if ((rc = launch_gemm32(s, dt_gemm(c.lc, g.N, D, c.nb, dt_query_rows(c, a.wq_rows, D), dt_key_rows(c, a.x_rows, D), w.S, 0.f)))) return rc;
+            if (a.mode != DAGL_MODE_ADAPTIVE)
+                if ((rc = launch_dt_select(s, c, a.mode, a.k, w, a.bias))) return rc;
+            hipLaunchKernelGGL(softmax, dim3(c.lc, c.nb), dim3(256), 0, s, c.N, c.ldn, c.L, c.l0, c.Lc, w.S.p, w.mt, a.bias, lse, w.deg, w.rowsum,
+                               c.b0, w.sel);
             DAGL_LAUNCH_CHECK("dense_softmax_fwd_kernel");
             // agg = A V
-            if ((rc = launch_gemm32(s, dt_gemm(lc, P, g.N, nb, sbuf, p.ldn, (long long)p.Lc * p.ldn, 1,
-                                               vrows, P, (long long)g.N * P, 0,
-                                               agg + ((size_t)b0 * g.L + l0) * P, P, (long long)g.L * P, 0.f)))) return rc;
+            if ((rc = launch_gemm32(s, dt_gemm(c.lc, P, g.N, c.nb, w.S, w.V.down(), dt_query_rows(c, w.agg, P), 0.f)))) return rc;
         }
     }
-    if ((rc = launch_fold(s, B, g, agg, out))) return rc;
-    if (stats_dev) if ((rc = launch_degree_stats(s, (size_t)B * g.L, deg, stats_dev))) return rc;
+    if ((rc = launch_fold(s, B, g, w.agg, a.out))) return rc;
+    if (a.stats) if ((rc = launch_degree_stats(s, (size_t)B * g.L, w.deg, a.stats))) return rc;
     return DAGL_OK;
 }
 
@@ -557,29 +585,29 @@ __global__ __launch_bounds__(256) void dt_unfold_values_split_kernel(int H, int 
     ol[0] = reinterpret_cast<const uint4*>(vl)[0]; ol[1] = reinterpret_cast<const uint4*>(vl)[1];
 }
 
-static int dt_split_rows(hipStream_t s, size_t R, int C, long long ld, int Cp, long long ldo, const float* src, const unsigned* word,
-                         float fixed, unsigned short* hi, size_t halfs) {
+// the rows of `src` (R of them over the whole group, C columns) -> `o`, Cp >= C columns per row
+static int dt_split_rows(hipStream_t s, size_t R, int C, const Mat32& src, int Cp, const Split16& o) {
     const size_t items = R * (size_t)(Cp / 8);
-    hipLaunchKernelGGL(dt_split_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, R, C, ld, Cp, ldo, src, word, fixed, hi, hi + halfs);
+    hipLaunchKernelGGL(dt_split_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, R, C, src.ld, Cp, o.ld, src.p, o.word, o.fixed,
+                       o.hi, o.hi + o.lo);
     DAGL_LAUNCH_CHECK("dt_split_rows_kernel");
     return DAGL_OK;
 }
 
-static int dt_split_transpose(hipStream_t s, int nb, int R, int C, long long ld, long long ss, int Rp, long long ldo, const float* src,
-                              const unsigned* word, float fixed, unsigned short* hi, size_t halfs) {
-    hipLaunchKernelGGL(dt_split_transpose_kernel, dim3((Rp + 63) / 64, (C + 63) / 64, nb), dim3(256), 0, s, R, C, ld, ss, Rp, ldo,
-                       (long long)C * ldo, src, word, fixed, hi, hi + halfs);
+// `src` [nb][R][C] -> `o` [nb][C][Rp], Rp >= R
+static int dt_split_transpose(hipStream_t s, int nb, int R, int C, const Mat32& src, int Rp, const Split16& o) {
+    hipLaunchKernelGGL(dt_split_transpose_kernel, dim3((Rp + 63) / 64, (C + 63) / 64, nb), dim3(256), 0, s, R, C, src.ld, src.stride, Rp, o.ld,
+                       o.stride, src.p, o.word, o.fixed, o.hi, o.hi + o.lo);
     DAGL_LAUNCH_CHECK("dt_split_transpose_kernel");
     return DAGL_OK;
 }
 
-static Gemm16s dt_gemm16(int M, int N, int K, int nb, const unsigned short* a, size_t a_halfs, long long lda, long long sA,
-                         const unsigned short* b, size_t b_halfs, long long ldb, long long sB, float* C, long long ldc, long long sC,
-                         const unsigned* wa, const unsigned* wb, float alpha0) {
+// slices > 1: K = the contraction length of one slice, the slices' raw sums in `part`
+static Gemm16s dt_gemm16(int M, int N, int K, int nb, const Split16& A, const Split16& Bm, const Out32& C, int slices = 1, float* part = nullptr) {
     Gemm16s g;
-    g.M = M; g.N = N; g.K = K; g.a_hi = a; g.a_lo = a + a_halfs; g.b_hi = b; g.b_lo = b + b_halfs; g.lda = lda; g.ldb = ldb;
-    g.a_rows = M; g.b_rows = N; g.C = C; g.ldc = ldc; g.part = nullptr; g.slices = 1; g.scale_word = wa; g.scale_word_b = wb;
-    g.alpha0 = alpha0; g.batch = nb; g.sA = sA; g.sB = sB; g.sC = sC;
+    g.M = M; g.N = N; g.K = K; g.a_hi = A.hi; g.a_lo = A.hi + A.lo; g.b_hi = Bm.hi; g.b_lo = Bm.hi + Bm.lo; g.lda = A.ld; g.ldb = Bm.ld;
+    g.a_rows = M; g.b_rows = N; g.C = C.p; g.ldc = C.ld; g.part = part; g.slices = slices; g.scale_word = A.word; g.scale_word_b = Bm.word;
+    g.alpha0 = 1.f / (A.fixed * Bm.fixed); g.batch = nb; g.sA = A.stride; g.sB = Bm.stride; g.sC = C.stride;
     return g;
 }
 
@@ -588,139 +616,102 @@ static Gemm16s dt_gemm16(int M, int N, int K, int nb, const unsigned short* a, s
 // step, half of the adaptive-mode training step.  Operand copies: K-contiguous rows for both sides of every product, i.e.
 // d agg, V, Wq, X by rows, and d agg, X, Wq, d S, A transposed; every tensor scaled by a power of two taken from its largest
 // magnitude (A <= 1: 2^13).  The softmax backward between the products stays in fp32 on fp32 S and d A.
-static int dt_backward_group16(hipStream_t s, const Grid& g, const DtPlan& p, void* ws, int b0, int nb, const float* wq_rows,
-                               const float* x_rows, const float* thr, const float* bias, const float* lse, const float* mu,
-                               float* dwq_rows, float* dx_rows, float* dthr, float* dbias) {
+static int dt_backward_group16(hipStream_t s, const DenseTrainBackward& a, const DtPlan& p, const DtWs& w, int b0, int nb, const float* mu) {
     int rc;
-    unsigned* words = at<unsigned>(ws, p.o_words);          // 0 d agg, 1 values, 2 X, 3 Wq, 4 d S
-    float* sbuf = at<float>(ws, p.o_sbuf);
-    float* abuf = at<float>(ws, p.o_abuf);
-    float* dvrows = at<float>(ws, p.o_dvrows);
-    const float* dagg = at<float>(ws, p.o_dagg) + (size_t)b0 * g.L * P;
-    const float* b2p = at<float>(ws, p.o_b2p) + (size_t)b0 * g.Hp * g.Wp * CH;
-    const float* mt = at<float>(ws, p.o_mt);
-    float* dmu = at<float>(ws, p.o_dmu);
-    const float* wq = wq_rows + (size_t)b0 * g.L * D;
-    const float* xr = x_rows + (size_t)b0 * g.N * D;
+    const Grid& g = a.g;
     const int L = g.L, N = g.N, Lp = p.Lp;
-    const long long ldn = p.ldn, ldl = p.ldl, ldk = p.ldk;
-    DAGL_HIP_TRY(hipMemsetAsync(words, 0, 256, s));
-    if ((rc = launch_absmax(s, (size_t)nb * L * P, dagg, words + 0))) return rc;
-    if ((rc = launch_absmax(s, (size_t)nb * g.Hp * g.Wp * CH, b2p, words + 1))) return rc;
-    if ((rc = launch_absmax(s, (size_t)nb * N * D, xr, words + 2))) return rc;
-    if ((rc = launch_absmax(s, (size_t)nb * L * D, wq, words + 3))) return rc;
+    const DtChunk c = dt_chunk(g, p, b0, nb, 0);
+    const Mat32 dagg = dt_query_rows<const float>(c, w.dagg, P), wq = dt_query_rows(c, a.wq_rows, D), x = dt_key_rows(c, a.x_rows, D);
+    const float* b2p = w.b2p + (size_t)b0 * g.Hp * g.Wp * CH;
+    DAGL_HIP_TRY(hipMemsetAsync(w.words, 0, 256, s));
+    if ((rc = launch_absmax(s, (size_t)nb * L * P, dagg.p, w.words + 0))) return rc;
+    if ((rc = launch_absmax(s, (size_t)nb * g.Hp * g.Wp * CH, b2p, w.words + 1))) return rc;
+    if ((rc = launch_absmax(s, (size_t)nb * N * D, x.p, w.words + 2))) return rc;
+    if ((rc = launch_absmax(s, (size_t)nb * L * D, wq.p, w.words + 3))) return rc;
     // operand copies that do not depend on the softmax
-    if ((rc = dt_split_rows(s, (size_t)nb * L, P, P, DT_PK, DT_PK, dagg, words + 0, 1.f, at<unsigned short>(ws, p.o_dgk), p.dgk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, P, P, (long long)L * P, Lp, ldl, dagg, words + 0, 1.f, at<unsigned short>(ws, p.o_dgt), p.dgt_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * L, P, dagg, DT_PK, w.dgk))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, P, dagg, Lp, w.dgt))) return rc;
     {
         const size_t total = (size_t)nb * N * 50;
         hipLaunchKernelGGL(dt_unfold_values_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g.H, g.W, total, b2p,
-                           words + 1, at<unsigned short>(ws, p.o_vk), at<unsigned short>(ws, p.o_vk) + p.vk_h);
+                           w.vk.word, w.vk.hi, w.vk.hi + w.vk.lo);
         DAGL_LAUNCH_CHECK("dt_unfold_values_split_kernel");
     }
-    if ((rc = dt_split_rows(s, (size_t)nb * N, D, D, DT_DK, DT_DK, xr, words + 2, 1.f, at<unsigned short>(ws, p.o_xk), p.xk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, N, D, D, (long long)N * D, p.nk, ldk, xr, words + 2, 1.f, at<unsigned short>(ws, p.o_xt), p.xt_h))) return rc;
-    if ((rc = dt_split_rows(s, (size_t)nb * L, D, D, DT_DK, DT_DK, wq, words + 3, 1.f, at<unsigned short>(ws, p.o_wqk), p.wqk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, D, D, (long long)L * D, Lp, ldl, wq, words + 3, 1.f, at<unsigned short>(ws, p.o_wqt), p.wqt_h))) return rc;
-    const long long sS = (long long)p.Lc * ldn;
+    if ((rc = dt_split_rows(s, (size_t)nb * N, D, x, DT_DK, w.xk))) return rc;
+    if ((rc = dt_split_transpose(s, nb, N, D, x, p.nk, w.xt))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * L, D, wq, DT_DK, w.wqk))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, D, wq, Lp, w.wqt))) return rc;
     // d A = d agg V^T ; S = Wq X^T
-    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_PK, nb, at<unsigned short>(ws, p.o_dgk), p.dgk_h, DT_PK, (long long)L * DT_PK, at<unsigned short>(ws, p.o_vk), p.vk_h, DT_PK,
-                                          (long long)N * DT_PK, abuf, ldn, sS, words + 0, words + 1, 1.f)))) return rc;
-    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_DK, nb, at<unsigned short>(ws, p.o_wqk), p.wqk_h, DT_DK, (long long)L * DT_DK, at<unsigned short>(ws, p.o_xk), p.xk_h, DT_DK,
-                                          (long long)N * DT_DK, sbuf, ldn, sS, words + 3, words + 2, 1.f)))) return rc;
-    if ((rc = launch_dense_softmax_bwd(s, L, nb, N, ldn, L, 0, p.Lc, sbuf, abuf, mt, bias, lse, mu, thr, dthr, dbias, dmu, b0, words + 4))) return rc;
+    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_PK, nb, w.dgk, w.vk, w.A)))) return rc;
+    if ((rc = launch_gemm16s(s, dt_gemm16(L, N, DT_DK, nb, w.wqk, w.xk, w.S)))) return rc;
+    if ((rc = launch_dense_softmax_bwd(s, c, a, w, mu, w.words + 4))) return rc;
     // d S by rows and transposed, A transposed
-    if ((rc = dt_split_rows(s, (size_t)nb * p.Lc, (int)ldn, ldn, p.nk, ldk, sbuf, words + 4, 1.f, at<unsigned short>(ws, p.o_dsk), p.dsk_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, sbuf, words + 4, 1.f, at<unsigned short>(ws, p.o_dst), p.dst_h))) return rc;
-    if ((rc = dt_split_transpose(s, nb, L, N, ldn, sS, Lp, ldl, abuf, nullptr, 8192.f, at<unsigned short>(ws, p.o_at), p.at_h))) return rc;
+    if ((rc = dt_split_rows(s, (size_t)nb * p.Lc, (int)p.ldn, w.S, p.nk, w.dsk))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, N, w.S, Lp, w.dst))) return rc;
+    if ((rc = dt_split_transpose(s, nb, L, N, w.A, Lp, w.at))) return rc;
     // d Wq = d S X (split over the keys)
-    {
-        Gemm16s q = dt_gemm16(L, D, p.nk / p.kslices, nb, at<unsigned short>(ws, p.o_dsk), p.dsk_h, ldk, (long long)p.Lc * ldk, at<unsigned short>(ws, p.o_xt), p.xt_h, ldk, (long long)D * ldk,
-                              dwq_rows + (size_t)b0 * L * D, D, (long long)L * D, words + 4, words + 2, 1.f);
-        q.slices = p.kslices; q.part = at<float>(ws, p.o_part);
-        if ((rc = launch_gemm16s(s, q))) return rc;
-    }
+    if ((rc = launch_gemm16s(s, dt_gemm16(L, D, p.nk / p.kslices, nb, w.dsk, w.xt, dt_query_rows(c, a.dwq_rows, D), p.kslices, w.part)))) return rc;
     // d X = d S^T Wq ; d V = A^T d agg
-    if ((rc = launch_gemm16s(s, dt_gemm16(N, D, Lp, nb, at<unsigned short>(ws, p.o_dst), p.dst_h, ldl, (long long)N * ldl, at<unsigned short>(ws, p.o_wqt), p.wqt_h, ldl,
-                                          (long long)D * ldl, dx_rows + (size_t)b0 * N * D, D, (long long)N * D, words + 4, words + 3, 1.f)))) return rc;
-    if ((rc = launch_gemm16s(s, dt_gemm16(N, P, Lp, nb, at<unsigned short>(ws, p.o_at), p.at_h, ldl, (long long)N * ldl, at<unsigned short>(ws, p.o_dgt), p.dgt_h, ldl,
-                                          (long long)P * ldl, dvrows, P, (long long)N * P, nullptr, words + 0, 1.f / 8192.f)))) return rc;
+    if ((rc = launch_gemm16s(s, dt_gemm16(N, D, Lp, nb, w.dst, w.wqt, dt_key_rows(c, a.dx_rows, D))))) return rc;
+    if ((rc = launch_gemm16s(s, dt_gemm16(N, P, Lp, nb, w.at, w.dgt, w.dV)))) return rc;
     return DAGL_OK;
 }
 
-int launch_dense_train_backward(hipStream_t s, int B, const Grid& g, const float* wq_rows, const float* x_rows, const float* b2,
-                                const float* thr, const float* bias, const float* lse, const float* mu_saved, const float* dout,
-                                float* dwq_rows, float* dx_rows, float* db2, float* dthr, float* dbias, void* ws, size_t ws_bytes,
-                                bool fp32_products, int mode, int k) {
+// ... and with the products in fp32, chunk by chunk: d X and d V add up over the chunks
+static int dt_backward_group32(hipStream_t s, const DenseTrainBackward& a, const DtPlan& p, const DtWs& w, int b0, int nb, const float* mu) {
+    int rc;
+    const Grid& g = a.g;
+    if ((rc = launch_unfold_values(s, nb, g, w.b2p + (size_t)b0 * g.Hp * g.Wp * CH, w.V.p))) return rc;
+    for (int l0 = 0; l0 < g.L; l0 += p.Lc) {
+        const DtChunk c = dt_chunk(g, p, b0, nb, l0);
+        const Mat32 dagg = dt_query_rows<const float>(c, w.dagg, P), wq = dt_query_rows(c, a.wq_rows, D), x = dt_key_rows(c, a.x_rows, D);
+        const float beta = (l0 == 0) ? 0.f : 1.f;
+        // d A = d agg V^T ; S = Wq X^T
+        if ((rc = launch_gemm32(s, dt_gemm(c.lc, g.N, P, nb, dagg, w.V, w.A, 0.f, true)))) return rc;
+        if ((rc = launch_gemm32(s, dt_gemm(c.lc, g.N, D, nb, wq, x, w.S, 0.f)))) return rc;
+        if (a.mode != DAGL_MODE_ADAPTIVE)
+            if ((rc = launch_dt_select(s, c, a.mode, a.k, w, a.bias))) return rc;
+        if ((rc = launch_dense_softmax_bwd(s, c, a, w, mu, nullptr))) return rc;
+        // d Wq = d S X
+        if ((rc = launch_gemm32(s, dt_gemm(c.lc, D, g.N, nb, w.S, x.down(), dt_query_rows(c, a.dwq_rows, D), 0.f, true)))) return rc;
+        // d X (+)= d S^T Wq
+        if ((rc = launch_gemm32(s, dt_gemm(g.N, D, c.lc, nb, w.S.down(), wq.down(), dt_key_rows(c, a.dx_rows, D), beta, true)))) return rc;
+        // d V (+)= A^T d agg
+        if ((rc = launch_gemm32(s, dt_gemm(g.N, P, c.lc, nb, w.A.down(), dagg.down(), w.dV, beta, true)))) return rc;
+    }
+    return DAGL_OK;
+}
+
+int launch_dense_train_backward(hipStream_t s, const DenseTrainBackward& args) {
+    DenseTrainBackward a = args;
+    if (!a.heads()) { a.thr = a.bias = nullptr; a.dthr = a.dbias = nullptr; }
+    const int B = a.B; const Grid& g = a.g;
     const DtPlan p = dt_plan(B, g, true);
+    const DtWs w = dt_carve(a.ws, B, g, p, true);
+    if (a.ws_bytes < w.bytes) { set_error("dense backward: workspace %zu B < required %zu B", a.ws_bytes, w.bytes); return DAGL_ERR_WORKSPACE; }
     // the wide top-k modes re-select from the recomputed scores: the fp32 product of the forward, bit for bit (a split-fp16 S could
     // order two near-equal scores the other way round)
-    const bool h16 = p.h16 && !fp32_products && mode == DAGL_MODE_ADAPTIVE;
-    int32_t* sel = at<int32_t>(ws, p.o_sel);
-    if (ws_bytes < p.o_end) { set_error("dense backward: workspace %zu B < required %zu B", ws_bytes, p.o_end); return DAGL_ERR_WORKSPACE; }
+    const bool h16 = p.h16 && !a.fp32_products && a.mode == DAGL_MODE_ADAPTIVE;
+    float* mu = w.rowsum;                                     // recomputed with the thresholds (same values as the forward's)
     int rc;
-    float* mu = at<float>(ws, p.o_rowsum);                    // recomputed with the thresholds (same values as the forward's)
-    if ((rc = dt_prepare(s, B, g, p, ws, wq_rows, x_rows, b2, thr, mu))) return rc;
-    (void)mu_saved;
-    float* sbuf = at<float>(ws, p.o_sbuf);
-    float* abuf = at<float>(ws, p.o_abuf);
-    float* vrows = at<float>(ws, p.o_vrows);
-    float* dvrows = at<float>(ws, p.o_dvrows);
-    float* dagg = at<float>(ws, p.o_dagg);
-    const float* b2p = at<float>(ws, p.o_b2p);
-    const float* mt = at<float>(ws, p.o_mt);
-    float* dmu = at<float>(ws, p.o_dmu);
-    float* dxbar = at<float>(ws, p.o_dxbar);
-    const double* colsum = at<double>(ws, p.o_colsum);
-    if ((rc = launch_unfold_dout(s, B, g, dout, dagg))) return rc;
+    if ((rc = dt_prepare(s, a, w, mu))) return rc;
+    if ((rc = launch_unfold_dout(s, B, g, a.dout, w.dagg))) return rc;
     for (int b0 = 0; b0 < B; b0 += p.Bc) {
         const int nb = (B - b0 < p.Bc) ? B - b0 : p.Bc;
-        if (h16) {
-            if ((rc = dt_backward_group16(s, g, p, ws, b0, nb, wq_rows, x_rows, thr, bias, lse, mu, dwq_rows, dx_rows, dthr, dbias))) return rc;
-        } else {
-        if ((rc = launch_unfold_values(s, nb, g, b2p + (size_t)b0 * g.Hp * g.Wp * CH, vrows))) return rc;
-        for (int l0 = 0; l0 < g.L; l0 += p.Lc) {
-            const int lc = (g.L - l0 < p.Lc) ? g.L - l0 : p.Lc;
-            const float* wq_c = wq_rows + ((size_t)b0 * g.L + l0) * D;
-            const float* dagg_c = dagg + ((size_t)b0 * g.L + l0) * P;
-            const long long sS = (long long)p.Lc * p.ldn;
-            const float beta = (l0 == 0) ? 0.f : 1.f;
-            // d A = d agg V^T ; S = Wq X^T
-            if ((rc = launch_gemm32(s, dt_gemm(lc, g.N, P, nb, dagg_c, P, (long long)g.L * P, 1, vrows, P, (long long)g.N * P, 1,
-                                               abuf, p.ldn, sS, 0.f, true)))) return rc;
-            if ((rc = launch_gemm32(s, dt_gemm(lc, g.N, D, nb, wq_c, D, (long long)g.L * D, 1,
-                                               x_rows + (size_t)b0 * g.N * D, D, (long long)g.N * D, 1, sbuf, p.ldn, sS, 0.f)))) return rc;
-            if (mode != DAGL_MODE_ADAPTIVE)
-                if ((rc = launch_dt_select(s, lc, nb, g.N, p.ldn, g.L, l0, p.Lc, k, mode, sbuf, mt, bias, sel, b0))) return rc;
-            if ((rc = launch_dense_softmax_bwd(s, lc, nb, g.N, p.ldn, g.L, l0, p.Lc, sbuf, abuf, mt, bias, lse, mu, thr, dthr, dbias, dmu, b0,
-                                               nullptr, mode, sel))) return rc;
-            // d Wq = d S X
-            if ((rc = launch_gemm32(s, dt_gemm(lc, D, g.N, nb, sbuf, p.ldn, sS, 1, x_rows + (size_t)b0 * g.N * D, D, (long long)g.N * D, 0,
-                                               dwq_rows + ((size_t)b0 * g.L + l0) * D, D, (long long)g.L * D, 0.f, true)))) return rc;
-            // d X (+)= d S^T Wq
-            if ((rc = launch_gemm32(s, dt_gemm(g.N, D, lc, nb, sbuf, p.ldn, sS, 0, wq_c, D, (long long)g.L * D, 0,
-                                               dx_rows + (size_t)b0 * g.N * D, D, (long long)g.N * D, beta, true)))) return rc;
-            // d V (+)= A^T d agg
-            if ((rc = launch_gemm32(s, dt_gemm(g.N, P, lc, nb, abuf, p.ldn, sS, 0, dagg_c, P, (long long)g.L * P, 0,
-                                               dvrows, P, (long long)g.N * P, beta, true)))) return rc;
-        }
-        }
-        {
-            const size_t n = (size_t)nb * g.N;
-            hipLaunchKernelGGL(dt_fold_dv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, nb, dvrows,
-                               db2 + (size_t)b0 * CH * g.N);
-            DAGL_LAUNCH_CHECK("dt_fold_dv_kernel");
-        }
+        if ((rc = h16 ? dt_backward_group16(s, a, p, w, b0, nb, mu) : dt_backward_group32(s, a, p, w, b0, nb, mu))) return rc;
+        const size_t n = (size_t)nb * g.N;
+        hipLaunchKernelGGL(dt_fold_dv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, nb, w.dV.p, a.db2 + (size_t)b0 * CH * g.N);
+        DAGL_LAUNCH_CHECK("dt_fold_dv_kernel");
     }
     // dense mean term: d Wq_l += d mu_l Xbar ;  d X_j += (sum_l d mu_l Wq_l) / N   (the fixed-k mode has no threshold)
-    if (mode != DAGL_MODE_TOPK) {
+    if (a.heads()) {
         const size_t nq = (size_t)B * g.L * D, nk = (size_t)B * g.N * D;
-        hipLaunchKernelGGL(dt_rank1_add_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (size_t)B * g.L, g.L, dmu, nullptr,
-                           colsum, DS, 1.0f / (float)g.N, dwq_rows);
+        hipLaunchKernelGGL(dt_rank1_add_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, (size_t)B * g.L, g.L, w.dmu, nullptr,
+                           w.colsum, DS, 1.0f / (float)g.N, a.dwq_rows);
         DAGL_LAUNCH_CHECK("dt_rank1_add_kernel");
-        if ((rc = launch_dxbar(s, B, g.L, wq_rows, dmu, dxbar))) return rc;
-        hipLaunchKernelGGL(dt_rank1_add_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, (size_t)B * g.N, g.N, nullptr, dxbar,
-                           nullptr, D, 1.0f / (float)g.N, dx_rows);
+        if ((rc = launch_dxbar(s, B, g.L, a.wq_rows, w.dmu, w.dxbar))) return rc;
+        hipLaunchKernelGGL(dt_rank1_add_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, (size_t)B * g.N, g.N, nullptr, w.dxbar,
+                           nullptr, D, 1.0f / (float)g.N, a.dx_rows);
         DAGL_LAUNCH_CHECK("dt_rank1_add_kernel");
     }
     return DAGL_OK;
