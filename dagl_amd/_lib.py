@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdagl_ce.so")
 MODE_ADAPTIVE, MODE_TOPK, MODE_ADAPTIVE_TOPK = 0, 1, 2
 MODES = {"adaptive": MODE_ADAPTIVE, "topk": MODE_TOPK, "adaptive_topk": MODE_ADAPTIVE_TOPK}
 MAX_TOPK = 64
-ABI_VERSION = 410          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
+ABI_VERSION = 411          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
 FAST_CAP = 64
 P = 784
 D = 196
@@ -62,6 +62,7 @@ SIGNATURES = {
                              C.POINTER(CeInfo)]),
     "dagl_ce_forward_debug": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz,
                                    C.POINTER(CeInfo), _vp, _vp, _vp]),
+    "dagl_ce_pivot_debug": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "dagl_ce_graph_workspace_bytes": (_sz, [_i] * 6),
     "dagl_ce_graph_count": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _i, _i, _vp, _vp, _sz, C.POINTER(CeInfo)]),
     "dagl_ce_graph_fill": (_i, [_vp] + [_i] * 6 + [_vp] * 4 + [C.c_int64, C.c_int64, _vp, _sz]),

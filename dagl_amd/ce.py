@@ -224,8 +224,9 @@ class CE(nn.Module):
         # all); the device-side verdict NaN-fills a call the in-stream kernels could not serve -- never wrong numbers -- and
         # the sticky word is polled every 16th call, which sends the module back to waiting.
         self.adaptive_sync = "always"
-        # top-k modes: where the candidate threshold comes from.  "sparse" = every 8th key tile (DAGL_FLAG_SAMPLED_TOPK: enough on
-        # maps whose scores are spread evenly, e.g. the synthetic benchmark features); "full" = every second key tile + eight times
+        # top-k modes: where the candidate threshold comes from.  "sparse" = a subset of the keys (DAGL_FLAG_SAMPLED_TOPK): for k <= 16 on
+        # maps of >= 1024 k keys the two keys with the largest feature row sum of every 64 (csrc/pivot.hip: a threshold as good as
+        # "full"'s from N / 32 keys), otherwise every 8th key tile (enough on maps whose scores are spread evenly); "full" = every second key tile + eight times
         # the candidate slots (DAGL_FLAG_TIGHT_TOPK: +25 us at 256^2) -- on natural-image features the sampled threshold lets
         # hundreds of keys per query through, the slots overflow and the call lands on the fp32 redo pass (2.7 ms instead of 0.25);
         # "auto" (default) = the workspace's own policy word, read by the kernels themselves (round 4: no host poll, valid under

@@ -126,13 +126,16 @@ struct Plan {
     int s_gkeep = 4;                                      // group maxima per (query, chunk, half) segment handed to the threshold kernel (ScreenArgs::gkeep)
     int capseg, capseg_alloc;
     int s_sample_tight = 0, capseg_tight = 0;             // top-k modes behind the screen: the tight threshold's pair (DAGL_FLAG_TIGHT_TOPK)
+    bool pivot = false;                                   // the sampled threshold comes from the pivot keys (pivot.hip): regions laid out
+    bool pivot_policy = false;                            // ... also for calls under the workspace's policy word (DAGL_FLAG_SAMPLED_TOPK: p.pivot alone)
+    int pv_steps = 0, pv_steps_per_split = 0;             // 64-row steps of the pivot matrix, per image / per key chunk of the sampling launch
     int width;                      // neighbour-list width of the fixed-width paths
     int ovf_cap;                    // adaptive lists behind the screen: queries that may be redone one by one (overflow.hip)
     bool wide = false;              // top-k modes, k > DAGL_MAX_TOPK: row-wise dense form (topk_wide.hip), no lists
     size_t o_wide = 0;
     // byte offsets into the workspace
     size_t o_b1p, o_b2p, o_wp1, o_wp2, o_x, o_wq, o_xh, o_wqh, o_colsum, o_mt, o_cnt, o_segcnt, o_segoff, o_rowoff,
-        o_deg, o_stats, o_lidx, o_lval, o_cidx, o_cval, o_nbidx, o_nbwgt, o_nbcnt, o_agg, o_gmax, o_theta, o_smax, o_traw, o_scand, o_spill, o_spillcnt,
+        o_deg, o_stats, o_lidx, o_lval, o_cidx, o_cval, o_nbidx, o_nbwgt, o_nbcnt, o_agg, o_gmax, o_rowsum, o_xp, o_pidx, o_theta, o_smax, o_traw, o_scand, o_spill, o_spillcnt,
         o_redo, o_ovflist, o_heavy, o_ovfq, o_ovfscores, o_ovfpart, o_thr, o_bias, o_thrpart, o_maphi, o_maplo, o_maphi2, o_maplo2, o_b1amax, o_wp1h, o_wp2h, o_convw, o_colpart, o_end;
 };
 
@@ -241,6 +244,13 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
         // the tight pair: forced by the flag, or taken by the kernels themselves once the workspace's policy word says so
         p.s_sample_tight = (p.capseg_alloc >= 8 * p.capseg && p.s_sample >= 2) ? 2 : 1;
         p.capseg_tight = p.capseg_alloc;
+        // The sampled threshold from the PIVOT keys (pivot.hip) instead of every s_sample-th key tile: where the sampled stride skips
+        // tiles at all (>= 2: long key streams), k <= 16, and the N / 32 pivots leave the k-th largest of their group maxima room
+        // (>= 32 k keys).  Laid out whatever the call's flags, like the records; the training entry point (features given, no
+        // projection in the call) keeps the tile sampling.
+        p.pivot = !core && p.split16 && p.s_sample >= 2 && k <= 16 && g.N / 32 >= 32 * k;
+        p.pivot_policy = p.s_sample >= 4;      // under the policy word: only where the tile sampling is long (a stride of 2 is a few steps)
+        if (p.pivot) { p.pv_steps = pivot_steps(g.N); p.pv_steps_per_split = (p.pv_steps + p.s_splits - 1) / p.s_splits; }
         if (mode_flags & DAGL_FLAG_TIGHT_TOPK) { p.s_sample = p.s_sample_tight; p.capseg = p.capseg_tight; }
     }
 
@@ -255,7 +265,8 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
     p.o_wq = cv.reserve((size_t)B * feat_rows(g.L) * DS * sizeof(float));
     p.o_colsum = cv.reserve((size_t)B * DS * sizeof(double));
     p.o_mt = cv.reserve(BL * sizeof(float));
-    p.o_cnt = cv.reserve(BL * sizeof(int32_t));
+    p.o_cnt = cv.reserve(BL * sizeof(int32_t));                // LIFETIME: scan_adaptive only.  Top-k modes behind the screen keep the pivot indices
+                                                               // here (o_pidx below): a top-k path that starts using `cnt` must move them
     p.o_segcnt = cv.reserve(BL * p.splits * 2 * sizeof(int32_t));
     p.o_segoff = cv.reserve(BL * p.splits * 2 * sizeof(int32_t));
     p.o_rowoff = cv.reserve((BL + 1) * sizeof(int64_t));
@@ -271,7 +282,10 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
     p.o_nbidx = cv.reserve(BL * p.width * sizeof(int32_t));
     p.o_nbwgt = cv.reserve(BL * p.width * sizeof(float));
     p.o_nbcnt = cv.reserve(BL * sizeof(int32_t));
-    p.o_agg = cv.reserve(BL * P * sizeof(float));
+    p.o_agg = cv.reserve(BL * P * sizeof(float));              // LIFETIME: written from the gather stage on (stage_tail / fold_out / select_wide /
+                                                               // select_dense / overflow rows).  Top-k modes behind the screen keep the pivot row sums and
+                                                               // the pivot matrix here between the projection and the sampling launch (o_rowsum, o_xp
+                                                               // below): anything that writes `agg` BEFORE the sampling launch of a top-k call corrupts them
     p.o_thr = cv.reserve(BL * sizeof(float));
     p.o_bias = cv.reserve(BL * sizeof(float));
     p.o_thrpart = cv.reserve(8 * BL * sizeof(float));                       // prologue: partial thr/bias sums of 4 channel groups
@@ -293,6 +307,17 @@ static int make_plan(int B, int H, int W, int mode_flags, int k, Plan& p, bool c
         p.o_wqh = cv.reserve((size_t)B * feat_rows_h(g.L) * DSH * sizeof(uint16_t));
         p.s_gkeep = (p.s_splits * 2 * 16 <= 512) ? 16 : 4;       // (screen_theta_kernel takes up to 512 values per query)
         p.o_gmax = cv.reserve(BL * p.s_splits * 2 * p.s_gkeep * sizeof(float));
+        if (p.pivot) {
+            // The pivot regions take no workspace of their own.  Row sums and pivot matrix live from the projection to the sampling
+            // launch, the aggregated rows `agg` (196 B per key against their 46) from the gather on -- and only in calls that
+            // materialise them (debug read-out, variable-length lists); the indices sit in `cnt`, which only the adaptive mode's
+            // fp32 scan uses.  Both fit whenever the screen runs (N >= 2048); a layout where they do not keeps the tile sampling.
+            const size_t rs_b = align_up((size_t)B * g.N * PIVOT_SLOTS * sizeof(float), 256);
+            const size_t xp_b = (size_t)B * pivot_rows(g.N) * DSH * sizeof(uint16_t);
+            const size_t px_b = (size_t)B * ((g.N + 63) / 64) * 2 * sizeof(int32_t);
+            p.o_rowsum = p.o_agg; p.o_xp = p.o_agg + rs_b; p.o_pidx = p.o_cnt;
+            if (rs_b + xp_b > BL * P * sizeof(float) || px_b > BL * sizeof(int32_t)) p.pivot = false;
+        }
         p.o_theta = cv.reserve(BL * sizeof(float));
         p.o_scand = cv.reserve(BL * p.s_splits * 2 * p.capseg_alloc * sizeof(int2));     // candidate records (count in slot 0)
         if (mode != DAGL_MODE_ADAPTIVE) {       // top-k modes: a query's shared area behind its segments (ScreenArgs::spill)
@@ -432,6 +457,7 @@ struct Call {
     // the few per-call counters are cleared by the prologue kernel itself -- three launches fewer
     bool prepared;
     bool topk_policy;                                // top-k modes behind the screen: the threshold policy lives in the workspace
+    bool pivot;                                      // a sampled threshold of this call comes from the pivot keys (pivot.hip)
     bool fused_theta;                                // the adaptive screen's threshold comes out of query_thresholds_kernel
     bool no_wait, no_redo;                           // DAGL_FLAG_NO_WAIT / _NO_REDO honoured on this call
     int q_tiled;                                     // the projection writes the bf16 queries in the screen's fragment order
@@ -481,6 +507,10 @@ Call::Call(const ForwardRequest& r_, const Plan& p_) : r(r_), p(p_), g(p_.g) {
     prepared = fin && p.split16 && (flags & DAGL_FLAG_WEIGHTS_PACKED);
     topk_policy = p.screen && mode != DAGL_MODE_ADAPTIVE && !(flags & (DAGL_FLAG_TIGHT_TOPK | DAGL_FLAG_SAMPLED_TOPK)) &&
                   p.capseg_tight > 0 && (p.capseg_tight != p.capseg || p.s_sample_tight != p.s_sample);
+    // Pivot threshold: forced by DAGL_FLAG_SAMPLED_TOPK, or a call under the workspace's policy word on a PREPARED workspace (the word
+    // then has the last say, on the device).  The first call of a shape under the policy keeps the tile sampling: it is that call's
+    // overflow under the UNIFORM sample that decides, as before, whether the workspace moves to the tight threshold for good
+    pivot = p.pivot && !(flags & DAGL_FLAG_TIGHT_TOPK) && ((flags & DAGL_FLAG_SAMPLED_TOPK) || (p.pivot_policy && (!topk_policy || prepared)));
     fused_theta = p.screen && mode == DAGL_MODE_ADAPTIVE;
     no_wait = (flags & DAGL_FLAG_NO_WAIT) && p.ovf_cap > 0 && !dbg && !core && heads == 1;
     no_redo = p.screen && (flags & DAGL_FLAG_NO_REDO) && fin && heads == 1 && !core && !dbg;
@@ -694,6 +724,7 @@ static int stage_project(Call& c) {
     if (c.mode != DAGL_MODE_TOPK) pj.colsum = c.colsum;
     pj.colpart = at<float>(ws, p.o_colpart);
     pj.q_tiled = c.q_tiled; pj.split = c.split_p;
+    if (c.pivot) { pj.rowsum = at<float>(ws, p.o_rowsum); if (c.topk_policy) pj.rowsum_policy = stat32(c.stats, STAT_POLICY); }
     if (c.thr_in_proj) { pj.thr_hs = &c.thr_all; pj.thr_head_imgs = c.B; pj.thr_part = at<float>(ws, p.o_thrpart); }
     return launch_project16(c.s, pj);
 }
@@ -826,6 +857,9 @@ static ScreenArgs screen_args(const Call& c) {
     sc.capseg = p.capseg; sc.cand = at<int2>(ws, p.o_scand);
     if (c.mode != DAGL_MODE_ADAPTIVE) { sc.spill = at<int2>(ws, p.o_spill); sc.spill_cnt = at<unsigned>(ws, p.o_spillcnt); }
     if (c.topk_policy) { sc.policy = stat32(c.stats, STAT_POLICY); sc.sample_tight = p.s_sample_tight; sc.capseg_tight = p.capseg_tight; }
+    if (c.pivot && c.mode != DAGL_MODE_ADAPTIVE) {
+        sc.xp = at<uint16_t>(ws, p.o_xp); sc.rows_xp = pivot_rows(g.N); sc.pv_steps = p.pv_steps; sc.pv_steps_per_split = p.pv_steps_per_split;
+    }
 #ifdef DAGL_ABLATION
     { static const int var = [] { const char* e = getenv("DAGL_SCREEN_VARIANT"); return e ? atoi(e) : 0; }(); sc.variant = var; }
 #endif
@@ -1023,6 +1057,14 @@ static int select_screened(Call& c) {
     int32_t* policy = stat32(c.stats, STAT_POLICY);
     mark(c, 3);
     if (c.mode != DAGL_MODE_ADAPTIVE) {                     // top-k threshold from the sampling pass
+        if (c.pivot) {                                      // ... over the two heaviest keys of every 64 (pivot.hip)
+            PivotArgs pv;
+            memset(&pv, 0, sizeof(pv));
+            pv.B = c.B; pv.N = c.g.N; pv.n_blk = (c.g.N + 63) / 64; pv.steps = p.pv_steps;
+            pv.rowsum = at<float>(ws, p.o_rowsum); pv.xh = c.Xh; pv.rows_xh = sc.rows_xh;
+            pv.xp = at<uint16_t>(ws, p.o_xp); pv.rows_xp = sc.rows_xp; pv.pidx = at<int32_t>(ws, p.o_pidx); pv.policy = sc.policy;
+            if ((rc = launch_pivot_keys(c.s, pv))) return rc;
+        }
         if ((rc = launch_screen(c.s, sc, 0))) return rc;
         if ((rc = launch_screen_theta(c.s, (int)c.BL, p.s_splits * 2 * p.s_gkeep, c.k, sc.gmax, theta, nullptr, sc.spill_cnt))) return rc;
     }
@@ -1157,6 +1199,25 @@ int dagl_ce_forward_debug(void* stream, int B, int H, int W, const float* b1, co
     r.maps = &in;
     r.dbg_deg = deg_out; r.dbg_rowsum = rowsum_out; r.dbg_agg = agg_out;
     return ce_forward(r);
+}
+
+int dagl_ce_pivot_debug(void* stream, int B, int H, int W, int mode, int k, void* workspace, size_t ws_bytes, int32_t* pivot_idx_out,
+                        float* key_rowsum_out) {
+    Plan p;
+    int rc = make_plan(B, H, W, mode, k, p);
+    if (rc) return rc;
+    if (!p.pivot || (mode & DAGL_FLAG_TIGHT_TOPK)) {
+        set_error("dagl_ce_pivot_debug: calls of this shape / mode / k do not take their threshold from pivot keys");
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    DAGL_REQUIRE(pivot_idx_out || key_rowsum_out, "dagl_ce_pivot_debug: null output pointers");
+    if ((rc = check_workspace("dagl_ce_pivot_debug", workspace, ws_bytes, p.o_end))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (pivot_idx_out)
+        DAGL_HIP_TRY(hipMemcpyAsync(pivot_idx_out, at<int32_t>(workspace, p.o_pidx), (size_t)B * ((p.g.N + 63) / 64) * 2 * sizeof(int32_t),
+                                    hipMemcpyDeviceToDevice, s));
+    if (key_rowsum_out && (rc = launch_pivot_rowsum(s, (size_t)B * p.g.N, at<float>(workspace, p.o_rowsum), key_rowsum_out))) return rc;
+    return DAGL_OK;
 }
 
 int dagl_profile_create(int max_calls, dagl_profile** out) {

@@ -437,6 +437,8 @@ struct Project16Launch {
     const ThrHeadSet* thr_hs = nullptr;             // with thr_part: the thr / bias heads' partial sums (thr_bias4.h) as extra blocks of this launch
     int thr_head_imgs = 0; float* thr_part = nullptr;           // heads x imgs of those heads
     B1Tiers tiers;                                  // the map's coarse tier + the conv blocks' |b1| slots: the kernel picks the tier per head
+    float* rowsum = nullptr;                        // [B, N, PIVOT_SLOTS] partial feature row sums of the keys (pivot.hip), or null
+    const int32_t* rowsum_policy = nullptr;         // ... skipped while this workspace policy word is != 0 (tight threshold); null: always written
 };
 int launch_project16(hipStream_t s, const Project16Launch& a);
 int launch_feat_rows_out(hipStream_t s, int B, int n, const float* feat /* [B, feat_rows(n), DS] */, float* rows_out /* [B, n, 196] */,
@@ -577,8 +579,25 @@ struct ScreenArgs {
     int* theta_max;                         // pass 0, top-1 use: [B, L] words (zeroed) that take the query's largest sampled score by an integer
                                             // atomicMax instead of the group maxima going to gmax; pass 1 with seg_max then reads `theta` raw
     int seg_max;                            // pass 1: slot 0 of a segment = {candidates found, largest screened score among them (float bits)}
+    // pass 0, top-k modes: the pivot matrix (pivot.hip) -- with it, and the policy word (if any) on "sampled", the sampling pass streams
+    // EVERY step of xp (pv_steps of them, pv_steps_per_split per key chunk) instead of every sample-th step of xh.  Null: none
+    const uint16_t* xp; int rows_xp, pv_steps, pv_steps_per_split;
 };
 constexpr int SCREEN_SPILL = 256;
+// pivot keys (pivot.hip): the two keys with the largest feature row sum of every 64 consecutive keys, their bf16 rows gathered into xp
+constexpr int PIVOT_SLOTS = 8;          // partial row sums per key (project16_kernel: slot = first output tile of the writing block)
+inline int pivot_steps(int N) { return ((N + 63) / 64 + 31) / 32; }            // 64-row steps of xp: two rows per 64-key block
+inline int pivot_rows(int N) { return pivot_steps(N) * 64 + 64; }              // rows allocated per image (+ a guard step)
+struct PivotArgs {
+    int B, N, n_blk, steps;                 // n_blk = 64-key blocks per image, steps = pivot_steps(N)
+    const float* rowsum;                    // [B, N, PIVOT_SLOTS]
+    const uint16_t* xh; int rows_xh;        // bf16 key features
+    uint16_t* xp; int rows_xp;              // out: [B, rows_xp, DSH]; block v -> rows (v % steps) * 64 + 2 (v / steps) + {0, 1}
+    int32_t* pidx;                          // out: [B, n_blk, 2] key indices in block order (-1: the block has no such key)
+    const int32_t* policy;                  // workspace policy word (ScreenArgs::policy): != 0 -> the launch exits at once; or null
+};
+int launch_pivot_keys(hipStream_t s, const PivotArgs& a);
+int launch_pivot_rowsum(hipStream_t s, size_t n_keys, const float* slots, float* out);
 int launch_screen(hipStream_t s, const ScreenArgs& a, int pass);
 int launch_screen_theta(hipStream_t s, int n_rows, int G, int k, const float* gmax, float* theta, const int32_t* gate = nullptr,
                         unsigned* spill_cnt = nullptr);

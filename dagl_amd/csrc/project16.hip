@@ -161,6 +161,8 @@ struct Proj16Args {
     int units_q, units_k;                                           // 8-item units (two blocks each: tile groups 0-3 / 4-6)
     int n_full, n_split_groups, batch;                              // 1-D grid: full blocks, then 7 single-tile blocks per split group
     float* colpart;                                                 // [B, n_blocks_k, 224] per-block key column sums (or null)
+    float* rowsum;                                                  // [B, N, PIVOT_SLOTS] per-key partial row sums (pivot.hip) or null
+    const int32_t* rowsum_policy;                                   // workspace policy word or null: != 0 (tight threshold) -> no row sums
     RangeTag range; int heads;                                      // range guard: the packed weights' flags feed the call's word
     unsigned long long* times;                                      // ablation builds: block phase stamps (debug.hip) or null
     // the thr / bias heads' blocks (thr_bias4.h) behind the projection's own: n_proj = blocks of the projection, then thr_x x thr_y x TB_GROUPS
@@ -217,6 +219,23 @@ __device__ __forceinline__ bool p16_tier_is_coarse(const Proj16Args& pa, int hea
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
     return !(m * B1_FINE_SCALE < RANGE_LIMIT);
+}
+
+// Row sums of a block's tile(s) for pivot.hip: each lane holds C partial sums (one per accumulator row it owns) over ITS output column;
+// a butterfly over the 32 lanes of a row half that halves the values a lane carries at every exchange leaves lane i with the full
+// sum of value i (C = 32) -- C - 1 exchanges instead of 5 C, the same association for every row (a + b == b + a: both partners
+// of an exchange form the same number).
+template <int C>
+__device__ __forceinline__ void p16_reduce_scatter(float* v, int i) {
+    constexpr int H = C / 2;
+    const bool up = (i & H) != 0;
+#pragma unroll
+    for (int j = 0; j < H; ++j) {
+        const float keep = up ? v[j + H] : v[j];
+        const float send = up ? v[j] : v[j + H];
+        v[j] = keep + __shfl_xor(send, H);
+    }
+    if constexpr (H > 1) p16_reduce_scatter<H>(v, i);
 }
 
 // Single-tile key blocks (the overhang of the grid, project16_kernel): 4 waves x one 32-patch item x output tile n0 -- the round-3 shape
@@ -337,6 +356,8 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
     const float* __restrict__ fbias = pa.bias[which][head];
     const int grid_row_base = base_row;
     float colsum_r[NT];                                                 // this lane's share of the column sums
+    float rs[16];                                                       // ... and of the rows' sums
+    const bool want_rs = pa.rowsum != nullptr && (pa.rowsum_policy == nullptr || *pa.rowsum_policy == 0);     // (block-uniform)
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         const int col = (n0 + n) * 32 + i;
@@ -365,8 +386,16 @@ __device__ __forceinline__ void project16_body(const Proj16Args& pa, unsigned ch
                 pa.split_lo[which][o] = __builtin_bit_cast(unsigned short, (_Float16)(vs - (float)hv));
             }
             s += ok ? v : 0.f;
+            rs[r] = v;                                                  // (NT == 1)
         }
         colsum_r[n] = s;
+    }
+    if (want_rs) {                                                      // this tile's share of the keys' row sums -> slot n0
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rs[r] += __shfl_xor(rs[r], 16);
+        p16_reduce_scatter<16>(rs, i);                                  // lane i: row r = i & 15 of its half
+        const int r = i & 15, rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (i < 16 && wave_valid && rr < lim) pa.rowsum[((size_t)b * gr.N + grid_row_base + rr) * PIVOT_SLOTS + n0] = rs[0];
     }
     float* csum = reinterpret_cast<float*>(smem);                       // [waves][NT*32] (everything else in the LDS is dead now)
 #pragma unroll
@@ -643,6 +672,11 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
     float colsum_r[NT];
 #pragma unroll
     for (int n = 0; n < NT; ++n) colsum_r[n] = 0.f;
+    // keys, calls whose sampling pass reads the pivots only (block-uniform): this lane's column's share of its rows' sums, tiles in order
+    const bool want_rs = KEYS && pa.rowsum != nullptr && (pa.rowsum_policy == nullptr || *pa.rowsum_policy == 0);
+    float rs[PW * 16];
+#pragma unroll
+    for (int j = 0; j < PW * 16; ++j) rs[j] = 0.f;
 #pragma unroll
     for (int it = 0; it < PW; ++it) {
 #pragma unroll
@@ -661,6 +695,7 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
                     if (col >= D) v = 0.f;
                     stg[rl * SEG + n * 32 + i] = v;
                     colsum_r[n] += (item_valid[it] && rr < lim[it]) ? v : 0.f;
+                    if (want_rs) rs[it * 16 + r] += v;
                 }
             }
             // (the wave only reads back what it wrote itself: LDS operations of a wave execute in order, no barrier)
@@ -733,6 +768,15 @@ __device__ __forceinline__ void project16_body2(const Proj16Args& pa, unsigned c
                 if (bad && pa.range.word != nullptr) *pa.range.word = pa.range.tag;
             }
         }
+    }
+    if (want_rs) {
+        // the group's share of the keys' row sums -> slots n0 .. n0 + 3 = {sum, 0, 0, 0} (the single-tile blocks fill a slot per tile)
+        static_assert(PW == 2, "lane i ends up with value i of 32: item i >> 4, accumulator row i & 15");
+        p16_reduce_scatter<PW * 16>(rs, i);
+        const int it = i >> 4, r = i & 15, rr = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const bool ok = it ? (item_valid[1] && rr < lim[1]) : (item_valid[0] && rr < lim[0]);
+        const int key = (it ? base_row[1] : base_row[0]) + rr;
+        if (ok) *reinterpret_cast<float4*>(pa.rowsum + ((size_t)b * gr.N + key) * PIVOT_SLOTS + n0) = make_float4(rs[0], 0.f, 0.f, 0.f);
     }
     if (KEYS && pa.colpart != nullptr) {
         // fixed-order block reduction of the key column sums (no atomics: the row mean must be reproducible); the unit's sums go
@@ -867,6 +911,7 @@ int launch_project16(hipStream_t s, const Project16Launch& a) {
     pa.units_q = uq; pa.units_k = uk;
     pa.n_blocks_q = nbq; pa.n_blocks_k = nbk;
     pa.colpart = (colsum != nullptr) ? colpart : nullptr;
+    pa.rowsum = (which & 1) ? a.rowsum : nullptr; pa.rowsum_policy = a.rowsum_policy;
     // resident capacity: two blocks per CU.  A remainder of at most half a round is cut into single-tile blocks.
     static const int cus = [] {
         int dev = 0, n = 256;

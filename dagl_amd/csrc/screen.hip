@@ -56,7 +56,8 @@ __device__ __forceinline__ void load_query_fragments(const ScreenArgs& a, int b,
     for (int t = 0; t < KB; ++t) qf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(qp + qs * t));
 }
 
-// PASS 0: group maxima over every `sample`-th step (top-k threshold estimation)
+// PASS 0: group maxima over every `sample`-th step, or over every step of the pivot matrix ScreenArgs::xp (top-k threshold
+//         estimation: the k-th largest of disjoint group maxima bounds the k-th best score from below whatever keys are scored)
 // PASS 1: candidate filter over every step: key is a candidate of query q iff S~ >= theta[q]
 //         (theta carries the whole conservative test of either mode; +inf for padding queries).
 // Keys past N are zero rows (S~ = 0): they can only pass a degenerate theta <= 0 and are dropped by refine.
@@ -76,6 +77,9 @@ template <int PASS, int QW, int VAR, int SCR_QUERIES = 256, bool SMAX = false>
 __global__ __launch_bounds__(SCR_QUERIES / QW * 2, (SCR_QUERIES == 256) ? QW : 1) void screen_kernel(ScreenArgs a, int n_qgroups) {
     if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
     if (a.policy != nullptr && *a.policy != 0) { a.capseg = a.capseg_tight; a.sample = a.sample_tight; }   // device-side threshold policy
+    else if (PASS == 0 && a.xp != nullptr) {         // sampled threshold: every step of the pivot matrix instead of every sample-th key tile
+        a.xh = a.xp; a.rows_xh = a.rows_xp; a.n_steps = a.pv_steps; a.steps_per_split = a.pv_steps_per_split; a.sample = 1;
+    }
     constexpr int WAVES = SCR_QUERIES / 32 / QW;
     // key tiles in flight: a tile is requested NBUF-1 steps before it is multiplied.  LDS-DMA lands a tile ~2 us after its
     // request under load, a step's matrix work is 1.45 us: with two buffers (request one step ahead) every step ends waiting
@@ -332,6 +336,9 @@ template <int PASS, int WAVES, int VAR = 0, int QW = 1, bool SMAX = false>
 __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a, int n_qgroups) {
     if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
     if (a.policy != nullptr && *a.policy != 0) { a.capseg = a.capseg_tight; a.sample = a.sample_tight; }   // device-side threshold policy
+    else if (PASS == 0 && a.xp != nullptr) {         // sampled threshold: every step of the pivot matrix instead of every sample-th key tile
+        a.xh = a.xp; a.rows_xh = a.rows_xp; a.n_steps = a.pv_steps; a.steps_per_split = a.pv_steps_per_split; a.sample = 1;
+    }
     // ONE shared object (a second one makes hipcc drain vmcnt(0) in front of every ds_read of the loop)
     __shared__ __attribute__((aligned(16))) unsigned short smem[RING_NBUF * STEP_ELEMS + RING_FLAG_BYTES / 2];
     unsigned* const flags = reinterpret_cast<unsigned*>(smem + RING_NBUF * STEP_ELEMS);     // ready[0..4] at +0, done[0..4] at +32 bytes

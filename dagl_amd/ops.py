@@ -682,6 +682,25 @@ def ce_range_check(shape, mode: str, k: int, workspace: "Workspace", device) -> 
                                      # bit 3: the workspace's top-k threshold policy word says "tight", bit 4: a no-redo call went unserved
 
 
+def ce_pivot_debug(shape, mode: str, k: int, workspace: "Workspace", device, sampled_topk: bool = True):
+    """Test read-out (``dagl_ce_pivot_debug``): what the last top-k call on ``workspace`` (input shape ``shape``) that took its
+    sampled threshold from pivot keys left there -> (pivot_idx [B, ceil(N/64), 2] int32, key_rowsum [B, N] fp32).  Raises
+    ``DaglError`` (code ERR_UNSUPPORTED) for shapes / modes / k whose calls keep the tile sampling."""
+    lib = _lib.load()
+    buf = workspace.peek(device)
+    if buf is None:
+        raise DaglError("ce_pivot_debug: the workspace has served no call on this device")
+    B, _, H, W = shape
+    a, nbytes = _aligned(buf)
+    idx = torch.empty(B, (H * W + 63) // 64, 2, device=device, dtype=torch.int32)
+    rowsum = torch.empty(B, H * W, device=device, dtype=torch.float32)
+    flags = MODES[mode] | (_lib.FLAG_SAMPLED_TOPK if sampled_topk and mode != "adaptive" else 0)
+    with torch.cuda.device(device):
+        check(lib.dagl_ce_pivot_debug(_stream(), B, H, W, flags, int(k), a, nbytes, idx.data_ptr(), rowsum.data_ptr()),
+              "dagl_ce_pivot_debug")
+    return idx, rowsum
+
+
 @_on_device
 def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: int = 0,
                       workspace: "Workspace | None" = None, profile: "StageProfile | None" = None,

@@ -73,8 +73,8 @@ extern "C" {
  * beyond required_bytes / path.  Callers use it once a workspace's calls have been served in-stream before (dagl_amd.CE).   */
 #define DAGL_FLAG_NO_WAIT        0x800
 
-/* OR-ed into `mode` (top-k modes behind the bf16 screen): take the candidate threshold from every SECOND key tile instead of every
- * 8th and give a query's candidate segments eight times the slots (every tile, where a gigabyte of records does not hold that many).  The sampled threshold is as good as the true k-th best on maps
+/* OR-ed into `mode` (top-k modes behind the bf16 screen): take the candidate threshold from every SECOND key tile instead of the
+ * sampled subset (every 8th tile; round 7: the two heaviest keys of every 64, where dagl_ce_pivot_debug applies) and give a query's candidate segments eight times the slots (every tile, where a gigabyte of records does not hold that many).  The sampled threshold is as good as the true k-th best on maps
  * whose scores are spread evenly (the synthetic benchmark features); on natural-image features the k-th best of an eighth of the
  * keys lies 4-25 % below the true one, hundreds to thousands of keys pass it, the slots overflow and most query groups land on
  * the fp32 redo pass (2.6 ms instead of 0.25 at 256^2, tools/time_real_image.py).  Costs half a pass more of the screen's
@@ -169,9 +169,9 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * bytes, dagl_ce_prologue takes `scratch`, dagl_ce_core_dense_forward takes `flags`, k <= 64; round 4: DAGL_FLAG_SAMPLED_TOPK,
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
- * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan).  A caller compares
+ * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; workspace sizes unchanged).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 410
+#define DAGL_ABI_VERSION 411
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -249,6 +249,22 @@ int dagl_ce_forward_debug(void* stream, int B, int H, int W,
                           int mode, int k, float* out,
                           void* workspace, size_t ws_bytes, dagl_ce_info* info,
                           int32_t* deg_out, float* rowsum_out, float* agg_out);
+
+/* (ABI 411) Read-out for tests of the top-k screen's threshold source (csrc/pivot.hip): calls of a top-k mode behind the screen that
+ * use the SAMPLED threshold (the policy word, or DAGL_FLAG_SAMPLED_TOPK) with k <= 16 on maps of N >= 1024 k keys take it from the
+ * two keys with the largest feature row sum of every 64 consecutive keys.  What the LAST such call on `workspace` (same B, H, W,
+ * mode, k) left there, copied to device memory (either pointer may be NULL):
+ *   pivot_idx_out  [B, ceil(N/64), 2] int32  the picked keys of every 64-key block, larger row sum first (-1: the block holds no
+ *                                            second key)
+ *   key_rowsum_out [B, N] fp32               sum over the 196 features of relu(fc2(patch)), as the kernel adds it up
+ * The row sums share their workspace region with the aggregated rows: after a call that materialised those (dagl_ce_forward_debug
+ * with agg_out) only pivot_idx_out is meaningful.  Under the workspace's policy word (neither threshold flag) the pivots are used
+ * only by calls that carry DAGL_FLAG_WEIGHTS_PACKED (a workspace that last served an identical call), and only where the tile
+ * sampling would skip three of four tiles or more (long key streams): every other call under the policy word -- a caller that
+ * never sets that flag included -- keeps the tile sampling, whose overflow on such a call decides the policy.
+ * DAGL_ERR_UNSUPPORTED: calls of this shape / mode / k keep the tile sampling (nothing was written).                              */
+int dagl_ce_pivot_debug(void* stream, int B, int H, int W, int mode, int k, void* workspace, size_t ws_bytes,
+                        int32_t* pivot_idx_out, float* key_rowsum_out);
 
 /* ---- (ABI 408) the learned patch graph as CSR: csrc/graph.hip --------------------------------------------------------------------
  * For every image and query patch i the keys j with mask_b[i,j] != 0 and their weights A[i,j] = softmax(10 S m)[i,j] mask_b[i,j]
