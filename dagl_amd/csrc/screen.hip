@@ -56,37 +56,104 @@ __device__ __forceinline__ void load_query_fragments(const ScreenArgs& a, int b,
     for (int t = 0; t < KB; ++t) qf[t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(qp + qs * t));
 }
 
+constexpr int SCR_WAVES = 8;                     // barrier form: waves (= query tiles) per block
+
+// ---- what screen_kernel (barrier form) and screen_ring_kernel (ring form) share --------------------------------------------
+// As functions: load_query_fragments, screen_policy, screen_finish.  As text, marked in both kernels and to be changed in both: the
+// query set-up and the step's tail (threshold test, candidate extraction) -- as functions they come out of hipcc as other step loops.
+// Three spellings in both kernels are there for hipcc alone (tools/same_device_code.sh shows what a change to one of them does):
+//   - the query set-up sits in a one-trip loop over w (left from the time a wave could have several query tiles): without it the
+//     set-up is simplified earlier and every instance, in release and ablation builds, gets other registers in its step loop;
+//   - the step counter `it` is declared ahead of smx and n_loc: the registers of the loop-carried values follow the declaration
+//     order (release build: without it the filter instances' step loops change);
+//   - the step loop declares its trip count n in its header.  This one serves the ablation build (-DDAGL_ABLATION) only, the
+//     release build's code is the same without it: there it keeps the compare-and-branch at the bottom of the step loop of the
+//     VAR == 0 instances -- the baseline every ablation figure is compared with -- as it was when those figures were taken.
+
+// Second thing in either kernel, after the gate test (as a function returning the flag it changes the ring form's sampling kernel):
+// the call's threshold policy, written into the kernel's own copy of a
+template <int PASS>
+__device__ __forceinline__ void screen_policy(ScreenArgs& a) {
+    if (a.policy != nullptr && *a.policy != 0) { a.capseg = a.capseg_tight; a.sample = a.sample_tight; }   // device-side threshold policy
+    else if (PASS == 0 && a.xp != nullptr) {         // sampled threshold: every step of the pivot matrix instead of every sample-th key tile
+        a.xh = a.xp; a.rows_xh = a.rows_xp; a.n_steps = a.pv_steps; a.steps_per_split = a.pv_steps_per_split; a.sample = 1;
+    }
+}
+
+// After the step loop, in both forms.  Sampling pass: the lane's sixteen group maxima gm[] go to theta_max, or all sixteen / the
+// GKEEP largest of them to gmax; filter pass: the segment's header (candidate count, SMAX: largest screened score).
+template <int PASS, bool SMAX>
+__device__ __forceinline__ void screen_finish(const ScreenArgs& a, float (&gm)[16], bool qvalid, size_t seg, int2* cseg, int n_loc, float smx) {
+    if (PASS == 0) {
+        if (a.theta_max != nullptr) {
+            // top-1 use (the dense formulation's row maxima): the threshold is the query's LARGEST sampled score -- an integer
+            // maximum over the lanes' values (scores are >= 0: their bit patterns order like the values; the word was zeroed by
+            // query_thresholds_kernel), no separate threshold kernel
+            float m = gm[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[r]);
+            if (qvalid && m > 0.f) atomicMax(a.theta_max + (seg >> 1) / a.splits, __float_as_int(m));
+            return;
+        }
+        if (a.gkeep == 16) {
+            // few segments per query (small maps, large batches): ALL sixteen group maxima of the lane go to the threshold kernel --
+            // with four of them per segment a query had 8 * chunks values to take its k-th largest from: fewer than k = 50 on a
+            // batch of 64 leaf tiles (theta = 0, every key a candidate, every query group on the fp32 redo pass: 12 ms a call)
+            if (qvalid) {
+                float4* o = reinterpret_cast<float4*>(a.gmax + seg * 16);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) o[u] = make_float4(gm[4 * u], gm[4 * u + 1], gm[4 * u + 2], gm[4 * u + 3]);
+            }
+            return;
+        }
+        // keep the lane's GKEEP largest group maxima: GKEEP distinct keys, so still a valid pool for the
+        // k-th-largest lower bound, at a quarter of the traffic into the theta kernel
+        float top[GKEEP];
+#pragma unroll
+        for (int u = 0; u < GKEEP; ++u) {
+            float m = gm[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[r]);
+            top[u] = m;
+            bool taken = false;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const bool hit = !taken && (gm[r] == m);
+                gm[r] = hit ? -1.0f : gm[r];
+                taken = taken || hit;
+            }
+        }
+        if (qvalid) *reinterpret_cast<float4*>(a.gmax + seg * GKEEP) = make_float4(top[0], top[1], top[2], top[3]);
+    } else {
+        if (qvalid) cseg[-(a.splits * 2)] = make_int2(n_loc, SMAX ? __float_as_int(smx) : 0);
+    }
+}
+
 // PASS 0: group maxima over every `sample`-th step, or over every step of the pivot matrix ScreenArgs::xp (top-k threshold
 //         estimation: the k-th largest of disjoint group maxima bounds the k-th best score from below whatever keys are scored)
 // PASS 1: candidate filter over every step: key is a candidate of query q iff S~ >= theta[q]
 //         (theta carries the whole conservative test of either mode; +inf for padding queries).
 // Keys past N are zero rows (S~ = 0): they can only pass a degenerate theta <= 0 and are dropped by refine.
 //
-// A block covers SCR_QUERIES queries (256 in every launch: 8 waves, two blocks per CU, two key tiles in flight; 512 / 384:
-// 16 / 12 waves, one block per CU, four tiles -- those block sizes run the ring form below), a wave QW query tiles of 32 (1
-// in every launch; 2 -- half the LDS reads per MFMA at half the occupancy -- measured the same: docs/HISTORY.md, round 3).
-// Neither parameter has a second value left; they stay until the loop is next edited.  Every key fragment is one ds_read_b128 per
-// lane; LDS (256 B/clk for b128 reads, conflict-free by the odd row stride) is ~25 % busy, the matrix pipes 50-54 %:
-// DESIGN.md section 7 lists what was tried to close that gap.
+// A block covers 256 queries: 8 waves with one query tile of 32 each, two blocks per CU (by their LDS and registers; the
+// launch bound asks for one), two key tiles in flight (blocks of 512 / 384 queries run the ring form below).  Every key
+// fragment is one ds_read_b128 per lane; LDS (256 B/clk for b128 reads, conflict-free by the odd row stride) is ~25 % busy,
+// the matrix pipes 50-54 %: DESIGN.md section 7 lists what was tried to close that gap.
 // VAR (ablation builds only, results wrong by construction): 1 no tile DMA, 2 no MFMA, 4 no test, 8 theta = inf, 16 key
 // fragments from registers, 32 no barrier, 64 accumulators carried across steps.
 // SMAX (filter pass only): the segment's header also carries the largest screened score among its candidates (ScreenArgs::seg_max:
 // the dense formulation's row maxima, rowmax_exact_kernel) -- a template parameter so that the top-k / adaptive filters keep their
 // register budget untouched
-template <int PASS, int QW, int VAR, int SCR_QUERIES = 256, bool SMAX = false>
-__global__ __launch_bounds__(SCR_QUERIES / QW * 2, (SCR_QUERIES == 256) ? QW : 1) void screen_kernel(ScreenArgs a, int n_qgroups) {
+template <int PASS, int VAR, bool SMAX = false>
+__global__ __launch_bounds__(SCR_WAVES * 64, 1) void screen_kernel(ScreenArgs a, int n_qgroups) {
     if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
-    if (a.policy != nullptr && *a.policy != 0) { a.capseg = a.capseg_tight; a.sample = a.sample_tight; }   // device-side threshold policy
-    else if (PASS == 0 && a.xp != nullptr) {         // sampled threshold: every step of the pivot matrix instead of every sample-th key tile
-        a.xh = a.xp; a.rows_xh = a.rows_xp; a.n_steps = a.pv_steps; a.steps_per_split = a.pv_steps_per_split; a.sample = 1;
-    }
-    constexpr int WAVES = SCR_QUERIES / 32 / QW;
+    screen_policy<PASS>(a);
+    constexpr int WAVES = SCR_WAVES;
     // key tiles in flight: a tile is requested NBUF-1 steps before it is multiplied.  LDS-DMA lands a tile ~2 us after its
     // request under load, a step's matrix work is 1.45 us: with two buffers (request one step ahead) every step ends waiting
-    // for the next tile.  512-query blocks are alone on their CU and can afford four buffers (108 KiB).
-    constexpr int NBUF = (SCR_QUERIES >= 384) ? 4 : 2;
-    constexpr int PPW = STEP_PIECES / WAVES;                                  // DMA pieces per wave and step (+1 for the first waves)
-    __shared__ __attribute__((aligned(16))) unsigned short sK[NBUF][STEP_ELEMS];     // 54 / 108 KiB
+    // for the next tile, and two blocks per CU leave no room for more.
+    constexpr int NBUF = 2;
+    __shared__ __attribute__((aligned(16))) unsigned short sK[NBUF][STEP_ELEMS];     // 54 KiB
 
     const int tid = threadIdx.x;
     dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 0);
@@ -103,50 +170,42 @@ __global__ __launch_bounds__(SCR_QUERIES / QW * 2, (SCR_QUERIES == 256) ? QW : 1
     if (step1 > a.n_steps) step1 = a.n_steps;
     const int stride = (PASS == 0) ? a.sample : 1;
 
-    // query fragments: QW x 13 x 8 bf16: Wq~[q][16t + 8h .. +7]
-    bf16x8 qf[QW][KB];
-    bool qvalid[QW];
-    size_t qlin[QW];
-    float thq[QW], thlo[QW];          // thlo = predecessor of thq:  S~ >= thq  <=>  S~ > thlo  <=>  sign(thlo - S~) set
-    int n_loc[QW];
-    int2* cseg[QW];
-    size_t seg[QW];
+    // the lane's query (the same set-up as in screen_ring_kernel); query fragments, 13 x 8 bf16: Wq~[q][16t + 8h .. +7]
+    bf16x8 qf[KB];
+    bool qvalid;
+    float thq, thlo;                  // thlo = predecessor of thq:  S~ >= thq  <=>  S~ > thlo  <=>  sign(thlo - S~) set
+    size_t seg;
+    int2* cseg;
+    int cur = 0, it = 0;              // (buffer of this step, step counter: ahead of smx and n_loc, see the note on hipcc)
+    float smx;                        // SMAX: largest screened score among this lane's (= this segment's) candidates
+    int n_loc;
 #pragma unroll
-    for (int w = 0; w < QW; ++w) {
-        const int q = ((qg * WAVES + wave) * QW + w) * QT + i;
-        qvalid[w] = q < a.L;
-        const int qc = qvalid[w] ? q : a.L - 1;
-        qlin[w] = (size_t)b * a.L + qc;
-        load_query_fragments(a, b, q - i, qc, lane, qf[w]);
-        thq[w] = 0.f;
-        if (PASS == 1) thq[w] = (qvalid[w] && !(VAR & 8)) ? a.theta[qlin[w]] : __builtin_inff();
-        if (PASS == 1 && SMAX && qvalid[w]) thq[w] = theta_of_sampled_max(thq[w]);      // (a.theta holds the raw sampled maximum)
-        {
-            const unsigned tb = __float_as_uint(thq[w]);
-            thlo[w] = __uint_as_float(thq[w] > 0.f ? tb - 1u : (thq[w] == 0.f ? 0x80000001u : tb + 1u));
-        }
-        n_loc[w] = 0;
-        seg[w] = (qlin[w] * a.splits + split) * 2 + h;
-        cseg[w] = a.cand + (qlin[w] * a.capseg + 1) * (size_t)(a.splits * 2) + split * 2 + h;   // slot 1 (slot 0 = header); slots are splits * 2 apart
+    for (int w = 0; w < 1; ++w) {     // (one trip, see the note on hipcc)
+        const int q = (qg * WAVES + wave + w) * QT + i;
+        qvalid = q < a.L;
+        const int qc = qvalid ? q : a.L - 1;
+        const size_t qlin = (size_t)b * a.L + qc;
+        load_query_fragments(a, b, q - i, qc, lane, qf);
+        thq = 0.f;
+        if (PASS == 1) thq = (qvalid && !(VAR & 8)) ? a.theta[qlin] : __builtin_inff();
+        if (PASS == 1 && SMAX && qvalid) thq = theta_of_sampled_max(thq);      // (a.theta holds the raw sampled maximum)
+        const unsigned tb = __float_as_uint(thq);
+        thlo = __uint_as_float(thq > 0.f ? tb - 1u : (thq == 0.f ? 0x80000001u : tb + 1u));
+        n_loc = 0;
+        seg = (qlin * a.splits + split) * 2 + h;
+        cseg = a.cand + (qlin * a.capseg + 1) * (size_t)(a.splits * 2) + split * 2 + h;   // slot 1 (slot 0 = header); slots are splits * 2 apart
     }
 #pragma unroll
-    for (int w = 0; w < QW; ++w)
-#pragma unroll
-        for (int t = 0; t < KB; ++t) asm volatile("" : "+v"(qf[w][t]));
+    for (int t = 0; t < KB; ++t) asm volatile("" : "+v"(qf[t]));
 
-    float gm[QW][16];
+    float gm[16];
 #pragma unroll
-    for (int w = 0; w < QW; ++w)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gm[w][r] = -1.0f;
-    float smx[QW];                                    // SMAX: largest screened score among this lane's (= this segment's) candidates
-#pragma unroll
-    for (int w = 0; w < QW; ++w) smx[w] = -1.0f;
+    for (int r = 0; r < 16; ++r) gm[r] = -1.0f;
+    smx = -1.0f;
 
     const unsigned short* xb = a.xh + (size_t)b * a.rows_xh * DSH;
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(&sK[0][0]));
     const int n_it = (step1 > step0) ? (step1 - step0 + stride - 1) / stride : 0;
-    const bool more = wave < (STEP_PIECES % WAVES);                          // this wave carries PPW + 1 pieces per step
     auto request = [&](int it) {                                             // key tile of iteration it -> buffer it % NBUF
         const unsigned dst = lds0 + (unsigned)(it % NBUF) * (STEP_ELEMS * 2);
         const unsigned short* src = xb + (size_t)(step0 + it * stride) * STEP_ELEMS;
@@ -160,152 +219,93 @@ __global__ __launch_bounds__(SCR_QUERIES / QW * 2, (SCR_QUERIES == 256) ? QW : 1
     __syncthreads();
     dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 1);
 
-    int cur = 0;
-    for (int it = 0; it < n_it; ++it) {
+    for (const int n = n_it; it < n; ++it) {                    // (n: see the note on hipcc)
         const int step = step0 + it * stride;
         const bool ahead = it + NBUF - 1 < n_it;
         if (ahead && !(VAR & 1)) request(it + NBUF - 1);                    // into the buffer the previous step has left
-        // two 32-key row tiles x QW query tiles, MFMA chains interleaved so that no instruction waits on its predecessor
-        f32x16 acc[QW][2];
+        // two 32-key row tiles, MFMA chains interleaved so that no instruction waits on its predecessor
+        f32x16 acc[2];
         if (VAR & 64) {                                  // ablation: accumulators carried across the steps, no epilogue
 #pragma unroll
-            for (int w = 0; w < QW; ++w)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { acc[w][0][r] = gm[w][r]; acc[w][1][r] = gm[w][(r + 1) & 15]; }
+            for (int r = 0; r < 16; ++r) { acc[0][r] = gm[r]; acc[1][r] = gm[(r + 1) & 15]; }
         } else {
 #pragma unroll
-        for (int w = 0; w < QW; ++w)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[w][0][r] = 0.f; acc[w][1][r] = 0.f; }
+            for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
         }
         const unsigned short* kp0 = &sK[cur][i * DSH + 8 * h];
         const unsigned short* kp1 = kp0 + 32 * DSH;
 #pragma unroll
         for (int t = 0; t < KB; ++t) {
             bf16x8 k0, k1;
-            if (VAR & 16) { k0 = qf[0][t]; k1 = qf[0][(t + 1) % KB]; }
+            if (VAR & 16) { k0 = qf[t]; k1 = qf[(t + 1) % KB]; }
             else {
                 k0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp0 + 16 * t));
                 k1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp1 + 16 * t));
             }
-            if (VAR & 2) {
-#pragma unroll
-                for (int w = 0; w < QW; ++w) { acc[w][0][t] += (float)k0[0] * (float)qf[w][t][0]; acc[w][1][t] += (float)k1[0] * (float)qf[w][t][1]; }
-                continue;
-            }
-#pragma unroll
-            for (int w = 0; w < QW; ++w) {
-                acc[w][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[w][t], acc[w][0], 0, 0, 0);
-                acc[w][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[w][t], acc[w][1], 0, 0, 0);
-            }
+            if (VAR & 2) { acc[0][t] += (float)k0[0] * (float)qf[t][0]; acc[1][t] += (float)k1[0] * (float)qf[t][1]; continue; }
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[t], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[t], acc[1], 0, 0, 0);
         }
+        if (VAR & 64) {
 #pragma unroll
-        for (int w = 0; w < QW; ++w) {
-            if (VAR & 64) {
+            for (int r = 0; r < 16; ++r) gm[r] = acc[0][r] + acc[1][r];
+        } else if (VAR & 4) {
+            gm[0] += acc[0][0] + acc[1][0];
+        } else if (PASS == 0) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) gm[w][r] = acc[w][0][r] + acc[w][1][r];
-                continue;
+            for (int r = 0; r < 16; ++r) gm[r] = fmaxf(fmaxf(gm[r], acc[0][r]), acc[1][r]);
+        } else {
+            // (this test and extraction: the same text in screen_ring_kernel)
+            // common case (no candidate in the whole wave): 16 v_max3 + one compare + one branch
+            float mxt[2];
+#pragma unroll
+            for (int tl = 0; tl < 2; ++tl) {
+                float m = acc[tl][0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[tl][r]);
+                mxt[tl] = m;
             }
-            if (VAR & 4) { gm[w][0] += acc[w][0][0] + acc[w][1][0]; continue; }
-            if (PASS == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) gm[w][r] = fmaxf(fmaxf(gm[w][r], acc[w][0][r]), acc[w][1][r]);
-            } else {
-                // common case (no candidate in the whole wave): 16 v_max3 + one compare + one branch
-                float mxt[2];
+            if (__any(fmaxf(mxt[0], mxt[1]) >= thq)) {
+                // ~3 of 4 wave-steps hold a candidate somewhere in their 2048 scores, so this path matters: one tile at a
+                // time, two VALU per score (sign of thlo - S~, shifted into the lane's mask by v_alignbit)
+                if (SMAX) smx = fmaxf(smx, fmaxf(mxt[0], mxt[1]));       // (a tile maximum below theta is below every candidate)
 #pragma unroll
                 for (int tl = 0; tl < 2; ++tl) {
-                    float m = acc[w][tl][0];
+                    if (!__any(mxt[tl] >= thq)) continue;
+                    unsigned mask = 0;
 #pragma unroll
-                    for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[w][tl][r]);
-                    mxt[tl] = m;
-                }
-                if (__any(fmaxf(mxt[0], mxt[1]) >= thq[w])) {
-                    // ~3 of 4 wave-steps hold a candidate somewhere in their 2048 scores, so this path matters: one tile at a
-                    // time, two VALU per score (sign of thlo - S~, shifted into the lane's mask by v_alignbit)
-                    if (SMAX) smx[w] = fmaxf(smx[w], fmaxf(mxt[0], mxt[1]));       // (a tile maximum below theta is below every candidate)
-#pragma unroll
-                    for (int tl = 0; tl < 2; ++tl) {
-                        if (!__any(mxt[tl] >= thq[w])) continue;
-                        unsigned mask = 0;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(thlo[w] - acc[w][tl][r]), 31);
-                        const int kbase = step * SK + 4 * h + tl * 32;
-                        // the screened score travels with the key: exact when the lane has one candidate in this tile (it is
-                        // the tile maximum), otherwise the maximum with the sign bit set = "upper bound only"
-                        const float sv = (__popc(mask) == 1) ? mxt[tl] : -mxt[tl];
-                        while (mask) {                                   // score r sits at bit 15 - r: ascending r
-                            const int bit = 31 - __clz((int)mask);
-                            mask &= ~(1u << bit);
-                            const int r = 15 - bit;
-                            const int key = kbase + (r & 3) + 8 * (r >> 2);
-                            if (n_loc[w] < a.capseg - 1) cseg[w][(size_t)n_loc[w] * (a.splits * 2)] = make_int2(key, __float_as_int(sv));
-                            else if (a.spill != nullptr) screen_spill(a, (size_t)b * a.L + (size_t)((qg * (SCR_QUERIES / (QW * QT)) + wave) * QW + w) * QT + i, key, sv);
-                            ++n_loc[w];
-                        }
+                    for (int r = 0; r < 16; ++r)
+                        mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(thlo - acc[tl][r]), 31);
+                    const int kbase = step * SK + 4 * h + tl * 32;
+                    // the screened score travels with the key: exact when the lane has one candidate in this tile (it is
+                    // the tile maximum), otherwise the maximum with the sign bit set = "upper bound only"
+                    const float sv = (__popc(mask) == 1) ? mxt[tl] : -mxt[tl];
+                    while (mask) {                                   // score r sits at bit 15 - r: ascending r
+                        const int bit = 31 - __clz((int)mask);
+                        mask &= ~(1u << bit);
+                        const int r = 15 - bit;
+                        const int key = kbase + (r & 3) + 8 * (r >> 2);
+                        if (n_loc < a.capseg - 1) cseg[(size_t)n_loc * (a.splits * 2)] = make_int2(key, __float_as_int(sv));
+                        else if (a.spill != nullptr) screen_spill(a, (size_t)b * a.L + (size_t)(qg * WAVES + wave) * QT + i, key, sv);
+                        ++n_loc;
                     }
                 }
             }
         }
         // the next tile must have landed; the NBUF-2 tiles requested after it may still be in flight
-        if (ahead && NBUF > 2) { if (more) dma_wait_le<(NBUF - 2) * (PPW + 1)>(); else dma_wait_le<(NBUF - 2) * PPW>(); }
-        else dma_wait_all();
+        dma_wait_all();
         if (!(VAR & 32)) __syncthreads();
         cur = (cur + 1 == NBUF) ? 0 : cur + 1;
     }
     dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 2);
 
+    if (PASS == 1 && (VAR & 64)) {                   // (keeps the ablated loop's accumulators alive)
+        float t = 0.f;
 #pragma unroll
-    for (int w = 0; w < QW; ++w) {
-        if (PASS == 0) {
-            if (a.theta_max != nullptr) {
-                // top-1 use (the dense formulation's row maxima): the threshold is the query's LARGEST sampled score -- an integer
-                // maximum over the lanes' values (scores are >= 0: their bit patterns order like the values; the word was zeroed by
-                // query_thresholds_kernel), no separate threshold kernel
-                float m = gm[w][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[w][r]);
-                if (qvalid[w] && m > 0.f) atomicMax(a.theta_max + (seg[w] >> 1) / a.splits, __float_as_int(m));
-                continue;
-            }
-            if (a.gkeep == 16) {
-                // few segments per query (small maps, large batches): ALL sixteen group maxima of the lane go to the threshold kernel --
-                // with four of them per segment a query had 8 * chunks values to take its k-th largest from: fewer than k = 50 on a
-                // batch of 64 leaf tiles (theta = 0, every key a candidate, every query group on the fp32 redo pass: 12 ms a call)
-                if (qvalid[w]) {
-                    float4* o = reinterpret_cast<float4*>(a.gmax + seg[w] * 16);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) o[u] = make_float4(gm[w][4 * u], gm[w][4 * u + 1], gm[w][4 * u + 2], gm[w][4 * u + 3]);
-                }
-                continue;
-            }
-            // keep the lane's GKEEP largest group maxima: GKEEP distinct keys, so still a valid pool for the
-            // k-th-largest lower bound, at a quarter of the traffic into the theta kernel
-            float top[GKEEP];
-#pragma unroll
-            for (int u = 0; u < GKEEP; ++u) {
-                float m = gm[w][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[w][r]);
-                top[u] = m;
-                bool taken = false;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool hit = !taken && (gm[w][r] == m);
-                    gm[w][r] = hit ? -1.0f : gm[w][r];
-                    taken = taken || hit;
-                }
-            }
-            if (qvalid[w]) *reinterpret_cast<float4*>(a.gmax + seg[w] * GKEEP) = make_float4(top[0], top[1], top[2], top[3]);
-        } else {
-            if (VAR & 64) { float t = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) t += gm[w][r];
-                if (t == 12345.f) n_loc[w] = 1; }
-            if (qvalid[w]) cseg[w][-(a.splits * 2)] = make_int2(n_loc[w], SMAX ? __float_as_int(smx[w]) : 0);
-        }
+        for (int r = 0; r < 16; ++r) t += gm[r];
+        if (t == 12345.f) n_loc = 1;
     }
+    screen_finish<PASS, SMAX>(a, gm, qvalid, seg, cseg, n_loc, smx);
     dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 3);
 }
 
@@ -329,16 +329,13 @@ constexpr int RING_FLAG_BYTES = 64;
 
 // VAR (ablation builds only, results wrong by construction): 1 no tile requests, 2 theta = inf (no extraction), 4 key fragments
 // from registers, 8 no ready / done words, 16 no threshold test at all
-// QW = query tiles of 32 per wave: 1 in every launch (16 waves x 32 queries: four waves per SIMD, 128 registers); 2 = 8 waves x 64
-// queries (two per SIMD, 256 registers, every key fragment read from the LDS feeding two multiplies) was measured and dropped
-// (docs/HISTORY.md, round 3)
-template <int PASS, int WAVES, int VAR = 0, int QW = 1, bool SMAX = false>
+// One query tile of 32 per wave (16 waves x 32 queries: four waves per SIMD, 128 registers; two tiles per wave were measured and
+// dropped: docs/HISTORY.md, round 3).  Shared with screen_kernel: load_query_fragments, screen_policy and screen_finish as
+// functions; the query set-up and the step's tail as text (see the note above screen_policy).
+template <int PASS, int WAVES, int VAR = 0, bool SMAX = false>
 __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a, int n_qgroups) {
     if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
-    if (a.policy != nullptr && *a.policy != 0) { a.capseg = a.capseg_tight; a.sample = a.sample_tight; }   // device-side threshold policy
-    else if (PASS == 0 && a.xp != nullptr) {         // sampled threshold: every step of the pivot matrix instead of every sample-th key tile
-        a.xh = a.xp; a.rows_xh = a.rows_xp; a.n_steps = a.pv_steps; a.steps_per_split = a.pv_steps_per_split; a.sample = 1;
-    }
+    screen_policy<PASS>(a);
     // ONE shared object (a second one makes hipcc drain vmcnt(0) in front of every ds_read of the loop)
     __shared__ __attribute__((aligned(16))) unsigned short smem[RING_NBUF * STEP_ELEMS + RING_FLAG_BYTES / 2];
     unsigned* const flags = reinterpret_cast<unsigned*>(smem + RING_NBUF * STEP_ELEMS);     // ready[0..4] at +0, done[0..4] at +32 bytes
@@ -358,42 +355,40 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
     if (step1 > a.n_steps) step1 = a.n_steps;
     const int stride = (PASS == 0) ? a.sample : 1;
 
-    // query fragments: QW x 13 x 8 bf16: Wq~[q][16t + 8h .. +7]
-    bf16x8 qf[QW][KB];
-    bool qvalid[QW];
-    float thq[QW], thlo[QW];          // thlo = predecessor of thq:  S~ >= thq  <=>  S~ > thlo  <=>  sign(thlo - S~) set
-    int n_loc[QW];
-    int2* cseg[QW];
-    size_t seg[QW];
+    // the lane's query (the same set-up as in screen_kernel); query fragments, 13 x 8 bf16: Wq~[q][16t + 8h .. +7]
+    bf16x8 qf[KB];
+    bool qvalid;
+    float thq, thlo;                  // thlo = predecessor of thq:  S~ >= thq  <=>  S~ > thlo  <=>  sign(thlo - S~) set
+    size_t seg;
+    int2* cseg;
+    // tile this wave has requested and not yet published (wave-uniform), it % RING_NBUF, step counter (ahead of smx and n_loc, see
+    // the note on hipcc)
+    int pend_tile = -1, buf = 0, it = 0;
+    float smx;                        // SMAX: largest screened score among this lane's (= this segment's) candidates
+    int n_loc;
 #pragma unroll
-    for (int w = 0; w < QW; ++w) {
-        const int q = ((qg * WAVES + wave) * QW + w) * QT + i;
-        qvalid[w] = q < a.L;
-        const int qc = qvalid[w] ? q : a.L - 1;
+    for (int w = 0; w < 1; ++w) {     // (one trip, see the note on hipcc)
+        const int q = (qg * WAVES + wave + w) * QT + i;
+        qvalid = q < a.L;
+        const int qc = qvalid ? q : a.L - 1;
         const size_t qlin = (size_t)b * a.L + qc;
-        load_query_fragments(a, b, q - i, qc, lane, qf[w]);
-        thq[w] = 0.f;
-        if (PASS == 1) thq[w] = (qvalid[w] && !(VAR & 2)) ? a.theta[qlin] : __builtin_inff();
-        if (PASS == 1 && SMAX && qvalid[w]) thq[w] = theta_of_sampled_max(thq[w]);      // (a.theta holds the raw sampled maximum)
-        const unsigned tb = __float_as_uint(thq[w]);
-        thlo[w] = __uint_as_float(thq[w] > 0.f ? tb - 1u : (thq[w] == 0.f ? 0x80000001u : tb + 1u));
-        n_loc[w] = 0;
-        seg[w] = (qlin * a.splits + split) * 2 + h;
-        cseg[w] = a.cand + (qlin * a.capseg + 1) * (size_t)(a.splits * 2) + split * 2 + h;   // slot 1 (slot 0 = header); slots are splits * 2 apart
+        load_query_fragments(a, b, q - i, qc, lane, qf);
+        thq = 0.f;
+        if (PASS == 1) thq = (qvalid && !(VAR & 2)) ? a.theta[qlin] : __builtin_inff();
+        if (PASS == 1 && SMAX && qvalid) thq = theta_of_sampled_max(thq);      // (a.theta holds the raw sampled maximum)
+        const unsigned tb = __float_as_uint(thq);
+        thlo = __uint_as_float(thq > 0.f ? tb - 1u : (thq == 0.f ? 0x80000001u : tb + 1u));
+        n_loc = 0;
+        seg = (qlin * a.splits + split) * 2 + h;
+        cseg = a.cand + (qlin * a.capseg + 1) * (size_t)(a.splits * 2) + split * 2 + h;   // slot 1 (slot 0 = header); slots are splits * 2 apart
     }
 #pragma unroll
-    for (int w = 0; w < QW; ++w)
-#pragma unroll
-        for (int t = 0; t < KB; ++t) asm volatile("" : "+v"(qf[w][t]));
+    for (int t = 0; t < KB; ++t) asm volatile("" : "+v"(qf[t]));
 
-    float gm[QW][16];
+    float gm[16];
 #pragma unroll
-    for (int w = 0; w < QW; ++w)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gm[w][r] = -1.0f;
-    float smx[QW];                                    // SMAX: largest screened score among this lane's (= this segment's) candidates
-#pragma unroll
-    for (int w = 0; w < QW; ++w) smx[w] = -1.0f;
+    for (int r = 0; r < 16; ++r) gm[r] = -1.0f;
+    smx = -1.0f;
 
     const unsigned short* xb = a.xh + (size_t)b * a.rows_xh * DSH;
     const unsigned lds0 = __builtin_amdgcn_readfirstlane(lds_addr_of(&smem[0]));
@@ -421,15 +416,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
     __syncthreads();
     if (!(VAR & 64)) dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 1);
 
-    int pend_tile = -1;                              // tile this wave has requested and not yet published (wave-uniform)
-    int buf = 0;                                     // it % RING_NBUF
     // VAR & 64 (ablation): per-wave sums of shader-clock deltas: 0 tile request (+ wait for the slot), 1 reads + multiplies,
     // 2 test + extraction, 3 wait for the tile's ready word, 4 publishing (vmcnt wait)
     unsigned long long ph[5] = {0, 0, 0, 0, 0};
     unsigned long long ph_t = (VAR & 64) ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long clk0 = (VAR & 128) ? __builtin_amdgcn_s_memtime() : 0ull;      // VAR & 128: shader clocks of the loop -> stamp 3
 #define RING_PH(k) do { if (VAR & 64) { const unsigned long long t1_ = __builtin_amdgcn_s_memtime(); ph[k] += t1_ - ph_t; ph_t = t1_; } } while (0)
-    for (int it = 0; it < n_it; ++it) {
+    for (const int n = n_it; it < n; ++it) {                    // (n: see the note on hipcc)
         const int step = step0 + it * stride;
         // --- requester duty: tile it + AHEAD belongs to wave (it + AHEAD) % WAVES ---------------------------------------
         {
@@ -457,41 +450,36 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
             while (lds_flag_load(ready0 + 4 * buf) < (unsigned)(it + 1)) __builtin_amdgcn_s_sleep(1);
         RING_PH(3);
 
-        f32x16 acc[QW][2];
+        f32x16 acc[2];
 #pragma unroll
-        for (int w = 0; w < QW; ++w)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[w][0][r] = 0.f; acc[w][1][r] = 0.f; }
+        for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
         const unsigned short* kp0 = &smem[buf * STEP_ELEMS + i * DSH + 8 * h];
         const unsigned short* kp1 = kp0 + 32 * DSH;
 #pragma unroll
         for (int t = 0; t < KB; ++t) {
             bf16x8 k0, k1;
-            if (VAR & 4) { k0 = qf[0][t]; k1 = qf[0][(t + 1) % KB]; }
+            if (VAR & 4) { k0 = qf[t]; k1 = qf[(t + 1) % KB]; }
             else {
                 k0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp0 + 16 * t));
                 k1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp1 + 16 * t));
             }
-#pragma unroll
-            for (int w = 0; w < QW; ++w) {
-                acc[w][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[w][t], acc[w][0], 0, 0, 0);
-                acc[w][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[w][t], acc[w][1], 0, 0, 0);
-            }
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[t], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[t], acc[1], 0, 0, 0);
         }
         // issue order of the block above: key fragments are read PF taps ahead of their multiplies (left alone, hipcc waits
         // for a fragment two instructions after asking for it: one exposed LDS latency per tap and wave)
         if (!(VAR & 4)) {
-            constexpr int PF = (QW == 2) ? 3 : 2;
+            constexpr int PF = 2;
             __builtin_amdgcn_sched_group_barrier(0x100, 2 * PF, 0);
 #pragma unroll
             for (int t = 0; t < KB; ++t) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2 * QW, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
                 if (t + PF < KB) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
             }
         }
         // every read of the slot has been issued (LDS executes a wave's operations in order): one more wave-step is through
         if (lane == 0 && !(VAR & 8)) lds_flag_add(done0 + 4 * buf, 1u);
-        if (VAR & 64) { asm volatile("s_nop 0" :: "v"(acc[0][0][0]), "v"(acc[0][1][15])); }       // (the multiplies have completed)
+        if (VAR & 64) { asm volatile("s_nop 0" :: "v"(acc[0][0]), "v"(acc[1][15])); }       // (the multiplies have completed)
         RING_PH(1);
         // --- publisher duty: the tile this wave requested a step ago has had ~1.7 steps to land ---------------------------
         if (pend_tile >= 0 && it > pend_tile - RING_AHEAD) {
@@ -501,45 +489,43 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
         }
         RING_PH(4);
         // --- tail: threshold test, candidate extraction ---------------------------------------------------------------------
+        if (VAR & 16) {
+            gm[0] += acc[0][0] + acc[1][0];
+        } else if (PASS == 0) {
 #pragma unroll
-        for (int w = 0; w < QW; ++w) {
-            if (VAR & 16) {
-                gm[w][0] += acc[w][0][0] + acc[w][1][0];
-            } else if (PASS == 0) {
+            for (int r = 0; r < 16; ++r) gm[r] = fmaxf(fmaxf(gm[r], acc[0][r]), acc[1][r]);
+        } else {
+            // (this test and extraction: the same text in screen_kernel)
+            // common case (no candidate in the whole wave): 16 v_max3 + one compare + one branch
+            float mxt[2];
 #pragma unroll
-                for (int r = 0; r < 16; ++r) gm[w][r] = fmaxf(fmaxf(gm[w][r], acc[w][0][r]), acc[w][1][r]);
-            } else {
-                // common case (no candidate in the whole wave): 16 v_max3 + one compare + one branch
-                float mxt[2];
+            for (int tl = 0; tl < 2; ++tl) {
+                float m = acc[tl][0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[tl][r]);
+                mxt[tl] = m;
+            }
+            if (__any(fmaxf(mxt[0], mxt[1]) >= thq)) {
+                if (SMAX) smx = fmaxf(smx, fmaxf(mxt[0], mxt[1]));       // (a tile maximum below theta is below every candidate)
 #pragma unroll
                 for (int tl = 0; tl < 2; ++tl) {
-                    float m = acc[w][tl][0];
+                    if (!__any(mxt[tl] >= thq)) continue;
+                    unsigned mask = 0;
 #pragma unroll
-                    for (int r = 1; r < 16; ++r) m = fmaxf(m, acc[w][tl][r]);
-                    mxt[tl] = m;
-                }
-                if (__any(fmaxf(mxt[0], mxt[1]) >= thq[w])) {
-                    if (SMAX) smx[w] = fmaxf(smx[w], fmaxf(mxt[0], mxt[1]));       // (a tile maximum below theta is below every candidate)
-#pragma unroll
-                    for (int tl = 0; tl < 2; ++tl) {
-                        if (!__any(mxt[tl] >= thq[w])) continue;
-                        unsigned mask = 0;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(thlo[w] - acc[w][tl][r]), 31);
-                        const int kbase = step * SK + 4 * h + tl * 32;
-                        // the screened score travels with the key: exact when the lane has one candidate in this tile (it is
-                        // the tile maximum), otherwise the maximum with the sign bit set = "upper bound only"
-                        const float sv = (__popc(mask) == 1) ? mxt[tl] : -mxt[tl];
-                        while (mask) {                                   // score r sits at bit 15 - r: ascending r
-                            const int bit = 31 - __clz((int)mask);
-                            mask &= ~(1u << bit);
-                            const int r = 15 - bit;
-                            const int key = kbase + (r & 3) + 8 * (r >> 2);
-                            if (n_loc[w] < a.capseg - 1) cseg[w][(size_t)n_loc[w] * (a.splits * 2)] = make_int2(key, __float_as_int(sv));
-                            else if (a.spill != nullptr) screen_spill(a, (size_t)b * a.L + (size_t)((qg * WAVES + wave) * QW + w) * QT + i, key, sv);
-                            ++n_loc[w];
-                        }
+                    for (int r = 0; r < 16; ++r)
+                        mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(thlo - acc[tl][r]), 31);
+                    const int kbase = step * SK + 4 * h + tl * 32;
+                    // the screened score travels with the key: exact when the lane has one candidate in this tile (it is
+                    // the tile maximum), otherwise the maximum with the sign bit set = "upper bound only"
+                    const float sv = (__popc(mask) == 1) ? mxt[tl] : -mxt[tl];
+                    while (mask) {                                   // score r sits at bit 15 - r: ascending r
+                        const int bit = 31 - __clz((int)mask);
+                        mask &= ~(1u << bit);
+                        const int r = 15 - bit;
+                        const int key = kbase + (r & 3) + 8 * (r >> 2);
+                        if (n_loc < a.capseg - 1) cseg[(size_t)n_loc * (a.splits * 2)] = make_int2(key, __float_as_int(sv));
+                        else if (a.spill != nullptr) screen_spill(a, (size_t)b * a.L + (size_t)(qg * WAVES + wave) * QT + i, key, sv);
+                        ++n_loc;
                     }
                 }
             }
@@ -555,53 +541,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
         for (int k = 0; k < 5; ++k) o[k] = ph[k];
     }
 
-#pragma unroll
-    for (int w = 0; w < QW; ++w) {
-        if (PASS == 0) {
-            if (a.theta_max != nullptr) {
-                // top-1 use (the dense formulation's row maxima): the threshold is the query's LARGEST sampled score -- an integer
-                // maximum over the lanes' values (scores are >= 0: their bit patterns order like the values; the word was zeroed by
-                // query_thresholds_kernel), no separate threshold kernel
-                float m = gm[w][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[w][r]);
-                if (qvalid[w] && m > 0.f) atomicMax(a.theta_max + (seg[w] >> 1) / a.splits, __float_as_int(m));
-                continue;
-            }
-            if (a.gkeep == 16) {
-                // few segments per query (small maps, large batches): ALL sixteen group maxima of the lane go to the threshold kernel --
-                // with four of them per segment a query had 8 * chunks values to take its k-th largest from: fewer than k = 50 on a
-                // batch of 64 leaf tiles (theta = 0, every key a candidate, every query group on the fp32 redo pass: 12 ms a call)
-                if (qvalid[w]) {
-                    float4* o = reinterpret_cast<float4*>(a.gmax + seg[w] * 16);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) o[u] = make_float4(gm[w][4 * u], gm[w][4 * u + 1], gm[w][4 * u + 2], gm[w][4 * u + 3]);
-                }
-                continue;
-            }
-            // keep the lane's GKEEP largest group maxima: GKEEP distinct keys, so still a valid pool for the
-            // k-th-largest lower bound, at a quarter of the traffic into the theta kernel
-            float top[GKEEP];
-#pragma unroll
-            for (int u = 0; u < GKEEP; ++u) {
-                float m = gm[w][0];
-#pragma unroll
-                for (int r = 1; r < 16; ++r) m = fmaxf(m, gm[w][r]);
-                top[u] = m;
-                bool taken = false;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool hit = !taken && (gm[w][r] == m);
-                    gm[w][r] = hit ? -1.0f : gm[w][r];
-                    taken = taken || hit;
-                }
-            }
-            if (qvalid[w]) *reinterpret_cast<float4*>(a.gmax + seg[w] * GKEEP) = make_float4(top[0], top[1], top[2], top[3]);
-        } else {
-            if ((VAR & 16) && gm[w][0] == 12345.f) n_loc[w] = 1;      // (keeps the ablated loop's accumulators alive)
-            if (qvalid[w]) cseg[w][-(a.splits * 2)] = make_int2(n_loc[w], SMAX ? __float_as_int(smx[w]) : 0);
-        }
-    }
+    if (PASS == 1 && (VAR & 16) && gm[0] == 12345.f) n_loc = 1;      // (keeps the ablated loop's accumulators alive)
+    screen_finish<PASS, SMAX>(a, gm, qvalid, seg, cseg, n_loc, smx);
     if (!(VAR & 64)) dbg_stamp(a.times, blockIdx.y * gridDim.x + blockIdx.x, 3);
 #ifdef DAGL_ABLATION
     if ((VAR & 128) && a.times != nullptr && tid == 0) a.times[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 3] = clk1 - clk0;
@@ -632,14 +573,14 @@ int launch_screen(hipStream_t s, const ScreenArgs& a, int pass) {
     // blocks that are alone on their CU (512 / 384 queries): the ring form; 256-query blocks (two per CU, small images) keep
     // the barrier form -- two five-deep rings do not fit one CU's LDS
     if (pass == 1 && a.seg_max) {                    // (the dense formulation's top-1 screen: segment headers carry their maxima)
-        if (qblock == 512) hipLaunchKernelGGL((screen_ring_kernel<1, 16, 0, 1, true>), grid, dim3(1024), 0, s, a, n_qgroups);
-        else if (qblock == 384) hipLaunchKernelGGL((screen_ring_kernel<1, 12, 0, 1, true>), grid, dim3(768), 0, s, a, n_qgroups);
-        else hipLaunchKernelGGL((screen_kernel<1, 1, 0, 256, true>), grid, dim3(512), 0, s, a, n_qgroups);
+        if (qblock == 512) hipLaunchKernelGGL((screen_ring_kernel<1, 16, 0, true>), grid, dim3(1024), 0, s, a, n_qgroups);
+        else if (qblock == 384) hipLaunchKernelGGL((screen_ring_kernel<1, 12, 0, true>), grid, dim3(768), 0, s, a, n_qgroups);
+        else hipLaunchKernelGGL((screen_kernel<1, 0, true>), grid, dim3(512), 0, s, a, n_qgroups);
         DAGL_LAUNCH_CHECK("screen_kernel");
         return DAGL_OK;
     }
 #define SCR_RING(P_, W_, V_) hipLaunchKernelGGL((screen_ring_kernel<P_, W_, V_>), grid, dim3(W_ * 64), 0, s, args, n_qgroups)
-#define SCR_BARRIER(P_, V_) hipLaunchKernelGGL((screen_kernel<P_, 1, V_>), grid, dim3(512), 0, s, args, n_qgroups)
+#define SCR_BARRIER(P_, V_) hipLaunchKernelGGL((screen_kernel<P_, V_>), grid, dim3(512), 0, s, args, n_qgroups)
 #ifdef DAGL_ABLATION      // debug builds only: the same kernels with the VAR of DAGL_SCREEN_VARIANT (results wrong by construction) and block timelines
     const size_t n_blk = (size_t)grid.x * grid.y;
     const bool ring_phases = a.variant == 64 && qblock == 512;             // per-wave phase clocks: 16 waves x 5 sums per block

@@ -198,6 +198,26 @@ def test_dense_formulation_equals_csr_lists(B, H, W):
         assert normwise(o_c.cpu().numpy(), ref64) <= TOL_OUT
 
 
+@pytest.mark.parametrize("H,W", [(192, 192), (256, 256)])
+def test_dense_row_maxima_through_the_ring_sampling_kernels(H, W):
+    """The dense formulation's top-1 screen takes its threshold from the sampling kernel's ``theta_max`` epilogue.  The cases of
+    test_dense_formulation_equals_csr_lists run it in 256-query blocks (barrier form); batch 1 at 192 x 192 (L = 2304) and at
+    256 x 256 (L = 4096) are the smallest maps whose plan picks 384- and 512-query blocks (12- and 16-wave ring form).  Same
+    comparison with the exact scan's CSR lists as there.  A degree differs where one (query, key) pair's mask value lies within
+    rounding of zero, so the allowance of that test -- 1e-3 of the queries at its largest map, 16384 keys -- grows with the keys."""
+    from dagl_amd.synth import make_ce_params, make_features
+    params = {n: torch.from_numpy(a) for n, a in make_ce_params(53, variant="default").items()}
+    x = torch.from_numpy(make_features(53, 1, 64, H, W)).to(_dev())
+    (o_d, i_d), (o_c, i_c) = (_run_debug(_module(params, "adaptive", 0, scan), x) for scan in ("screened", "exact"))
+    ndiff = int((i_d["deg"] != i_c["deg"]).sum())
+    err = normwise(o_d.cpu().numpy(), o_c.cpu().numpy())
+    print(f"[dense-ring] {H}x{W}: paths {i_d['path']} / {i_c['path']}, {ndiff} of {i_c['deg'].numel()} degrees differ, out {err:.2e}")
+    assert i_d["path"] == 4 and i_c["path"] == 1
+    assert ndiff <= int(1e-3 * i_c["deg"].numel() * (H * W / 16384)), ndiff       # rounding-level ties at the threshold
+    assert i_d["total_edges"] == int(i_d["deg"].sum()) and i_d["max_degree"] == int(i_d["deg"].max())
+    assert err <= 2e-4, err
+
+
 def test_dense_hint_skips_the_list_attempt_and_recovers():
     """After a call that ended in the dense formulation the module starts there (no screen / refine / read-back first);
     the result is the same, and sparse inputs switch the hint off again at the next statistics read-back."""
