@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libdagl_ce.so")
 MODE_ADAPTIVE, MODE_TOPK, MODE_ADAPTIVE_TOPK = 0, 1, 2
 MODES = {"adaptive": MODE_ADAPTIVE, "topk": MODE_TOPK, "adaptive_topk": MODE_ADAPTIVE_TOPK}
 MAX_TOPK = 64
-ABI_VERSION = 411          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
+ABI_VERSION = 412          # include/dagl_ce.h DAGL_ABI_VERSION this binding was written against
 FAST_CAP = 64
 P = 784
 D = 196
@@ -31,6 +31,7 @@ FLAG_NO_WAIT = 0x800
 FLAG_TIGHT_TOPK = 0x1000
 FLAG_SAMPLED_TOPK = 0x2000
 FLAG_NO_REDO = 0x4000
+GRAPH_ATTEND_EDGES_ONLY = 0x1      # dagl_graph_attend*: a plain softmax over the row's edges
 
 
 class DaglError(RuntimeError):
@@ -71,6 +72,10 @@ SIGNATURES = {
     "dagl_graph_apply_backward_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64]),
     "dagl_graph_apply": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _vp, _vp, _sz]),
     "dagl_graph_apply_backward": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64] + [_vp] * 7 + [_sz]),
+    "dagl_graph_attend_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64]),
+    "dagl_graph_attend_backward_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64]),
+    "dagl_graph_attend": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _vp, C.c_float, _i, _vp, _vp, _vp, _sz]),
+    "dagl_graph_attend_backward": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _vp, C.c_float, _i] + [_vp] * 10 + [_sz]),
     "dagl_ce_list_width": (_i, [_i, _i]),
     "dagl_ce_range_check": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(_i)]),
     "dagl_ce_core_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

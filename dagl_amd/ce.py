@@ -128,6 +128,37 @@ class _GraphApply(torch.autograd.Function):
         return d_b2p, d_w, None, None, None
 
 
+class _GraphAttend(torch.autograd.Function):
+    """Features -> the block's edge weights on a given structure (``ops.graph_attend``): S on the edges, the margin against ``tau`` (None:
+    the fixed-k variant), the reference's softmax restricted to the graph.  Returns (weight, score); differentiable in the two feature
+    matrices and ``tau`` through ``weight`` (``ops.graph_attend_backward``), ``score`` carries no gradient; the structure is a constant."""
+
+    @staticmethod
+    def forward(ctx, wq_rows, x_rows, tau, graph, scale, normalize, ws_f, ws_b):
+        wq_rows, x_rows = wq_rows.contiguous(), x_rows.contiguous()
+        tau_c = tau.contiguous() if tau is not None else None
+        weight, score = ops.graph_attend(wq_rows, x_rows, graph.row_off, graph.key, tau_c, scale=scale, normalize=normalize,
+                                         workspace=ws_f, hw=(graph.H, graph.W))
+        ctx.graph, ctx.call, ctx.ws_b = graph, (scale, normalize), ws_b
+        ctx.tau_shape = tau.shape if tau is not None else None
+        ctx.save_for_backward(wq_rows, x_rows, tau_c, score, weight)
+        ctx.mark_non_differentiable(score)
+        return weight, score
+
+    @staticmethod
+    def backward(ctx, d_weight, _d_score):
+        wq_rows, x_rows, tau, score, weight = ctx.saved_tensors
+        g = ctx.graph
+        need_wq, need_x, need_tau = ctx.needs_input_grad[:3]
+        d_wq, d_x, d_tau = ops.graph_attend_backward(d_weight.contiguous().float(), wq_rows, x_rows, g.row_off, g.key, score, weight, tau,
+                                                     scale=ctx.call[0], normalize=ctx.call[1],
+                                                     transposed=g.transpose() if need_x else None, need_wq=need_wq, need_x=need_x,
+                                                     need_tau=need_tau and tau is not None, workspace=ctx.ws_b, hw=(g.H, g.W))
+        if d_tau is not None:
+            d_tau = d_tau.view(ctx.tau_shape)
+        return d_wq, d_x, d_tau, None, None, None, None, None
+
+
 _CONV_WEIGHTS = ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight")
 
 
@@ -206,6 +237,8 @@ class CE(nn.Module):
         self._ws_graph = ops.Workspace()  # graph() / degrees(): a buffer of their own, so that the forward's packed weights and policy words survive
         self._ws_apply = ops.Workspace()      # apply_graph(): its aggregated and partial rows; its backward's rows
         self._ws_apply_bwd = ops.Workspace()
+        self._ws_attend = ops.Workspace()     # attend_graph() / forward_on_graph(): the row statistics; the backward's sums and partial rows
+        self._ws_attend_bwd = ops.Workspace()
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -595,6 +628,35 @@ class CE(nn.Module):
         off = csr["row_off"]
         return (off[1:] - off[:-1]).view(b.shape[0], -1)
 
+    def _check_given_graph(self, b: torch.Tensor, graph, what: str):
+        """The refusals of a call on a given graph (``apply_graph``, ``attend_graph``, ``forward_on_graph``), raised before any launch;
+        then ``graph.validate()`` (one host read, once per graph; refused under capture)."""
+        from .graph import PatchGraph
+        if b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.{what}: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
+        if not b.is_cuda:
+            raise DaglError(f"CE.{what}: input must be on the GPU; dagl_amd has no CPU path")
+        if self._generic:
+            raise DaglError(f"CE.{what}: applying a graph serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
+                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
+                            f"{self.inter_channels}), which is out of its scope")
+        if not isinstance(graph, PatchGraph):
+            raise DaglError(f"CE.{what}: a PatchGraph expected, got {type(graph).__name__}")
+        B, _, H, W = b.shape
+        if (graph.B, graph.H, graph.W) != (B, H, W):
+            raise DaglError(f"CE.{what}: the graph was built for B={graph.B} H={graph.H} W={graph.W}, the input is B={B} H={H} W={W}")
+        for name in ("row_off", "key", "weight"):
+            if getattr(graph, name).device != b.device:
+                raise DaglError(f"CE.{what}: graph.{name} lives on {getattr(graph, name).device}, the input on {b.device} "
+                                "(PatchGraph.to moves a graph)")
+        if b.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise DaglError(f"CE.{what}: unsupported dtype {b.dtype}")
+        if not graph._valid:
+            if torch.cuda.is_current_stream_capturing():
+                raise DaglError(f"CE.{what}: the graph has not been validated and the stream is being captured (validate() reads "
+                                "one word on the host): call graph.validate() before the capture")
+            graph.validate()
+
     def apply_graph(self, b: torch.Tensor, graph) -> torch.Tensor:
         """This block's output for ``b`` on a GIVEN patch graph instead of the one it would select: ``fold(A_G . V(theta(b))) / cnt``,
         dagl.py:263-272 with ``yi`` = ``graph`` (a ``PatchGraph``: what ``graph(b)`` returned, edited -- ``select`` / ``with_weight`` --,
@@ -608,32 +670,9 @@ class CE(nn.Module):
         ``graph.weight`` requiring grad, the call is differentiable in exactly those (fp32 parameters only); ``g``, the fc layers and
         the heads are not part of it.  The module's state (packed weights, top-k policy, range verdicts, ``_train_dense``) is untouched."""
         from . import train_ops as T
-        from .graph import PatchGraph
-        if b.dim() != 4 or b.shape[1] != self.in_channels:
-            raise DaglError(f"CE.apply_graph: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
-        if not b.is_cuda:
-            raise DaglError("CE.apply_graph: input must be on the GPU; dagl_amd has no CPU path")
-        if self._generic:
-            raise DaglError(f"CE.apply_graph: applying a graph serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
-                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
-                            f"{self.inter_channels}), which is out of its scope")
-        if not isinstance(graph, PatchGraph):
-            raise DaglError(f"CE.apply_graph: a PatchGraph expected, got {type(graph).__name__}")
+        self._check_given_graph(b, graph, "apply_graph")
         B, _, H, W = b.shape
-        if (graph.B, graph.H, graph.W) != (B, H, W):
-            raise DaglError(f"CE.apply_graph: the graph was built for B={graph.B} H={graph.H} W={graph.W}, the input is B={B} H={H} W={W}")
-        for name in ("row_off", "key", "weight"):
-            if getattr(graph, name).device != b.device:
-                raise DaglError(f"CE.apply_graph: graph.{name} lives on {getattr(graph, name).device}, the input on {b.device} "
-                                "(PatchGraph.to moves a graph)")
         in_dtype = b.dtype
-        if in_dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            raise DaglError(f"CE.apply_graph: unsupported dtype {in_dtype}")
-        if not graph._valid:
-            if torch.cuda.is_current_stream_capturing():
-                raise DaglError("CE.apply_graph: the graph has not been validated and the stream is being captured (validate() reads "
-                                "one word on the host): call graph.validate() before the capture")
-            graph.validate()
         grad = torch.is_grad_enabled() and (b.requires_grad or graph.weight.requires_grad
                                             or any(p.requires_grad for p in self.theta.parameters()))
         if grad:
@@ -651,6 +690,82 @@ class CE(nn.Module):
             b2p = T.to_padded_nhwc(b2, H, W, True)
             out = _GraphApply.apply(b2p, graph.weight, graph, self._ws_apply, self._ws_apply_bwd)
         return out if in_dtype == torch.float32 else out.to(in_dtype)
+
+    _FP32_ONLY = ("CE: the differentiable path needs fp32 parameters (the reference's --precision half is a test-time "
+                  "switch, DN_Gray/model/__init__.py:98-99); run half-precision modules under torch.no_grad()")
+
+    def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool):
+        """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route, ``tau`` in plain
+        torch, ``_GraphAttend`` and -- ``apply`` -- ``_GraphApply`` on the same value map.  -> (weight, score, out | None)."""
+        from types import SimpleNamespace
+        from . import train_ops as T
+        self._check_given_graph(b, graph, what)
+        if normalize not in ("reference", "edges"):
+            raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
+        if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
+            raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
+        margin = self.select_mode != "topk" if margin is None else bool(margin)
+        B, _, H, W = b.shape
+        used = [self.g, self.fc1, self.fc2] + ([self.theta] if apply else []) + ([self.thr_conv, self.bias_conv] if margin else [])
+        grad = torch.is_grad_enabled() and (b.requires_grad or any(p.requires_grad for m in used for p in m.parameters()))
+        if grad:
+            if any(p.dtype != torch.float32 for p in self.parameters()):
+                raise DaglError(self._FP32_ONLY)
+            p = {n: t for n, t in self.named_parameters()}
+        else:
+            p = self._params_f32(scaled=False)
+        ks, c = self.ksize, self.inter_channels
+        t, _bo = same_pad_amounts(H, ks, self.stride_1)
+        l, _r = same_pad_amounts(W, ks, self.stride_1)
+        Lh, Lw = -(-H // self.stride_1), -(-W // self.stride_1)
+        with torch.enable_grad() if grad else torch.no_grad():
+            x = b.float() if b.dtype != torch.float32 else b
+            x = _pad_channels4(x.contiguous())
+            convs = [SimpleNamespace(weight=_pad_channels4(p[n + ".weight"]), bias=p[n + ".bias"])
+                     for n in ("g", "theta") + (("thr_conv", "bias_conv") if margin else ())]
+            maps = T.prologue_convs(x, *convs, fast=False)                                      # dagl.py:208-215, fp32
+            b1p, b2p = maps[0], maps[1]
+            wq_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], c, ks), p["fc1.0.bias"], ks, self.stride_1,
+                                     T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=False)   # [B,L,196]
+            x_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], c, ks), p["fc2.0.bias"], ks, self.stride_2,
+                                    0, 0, H, W, relu=True, allow_fast=False)                      # [B,N,196]
+            tau = None
+            if margin:
+                # mean_j S_ij = <wq_i, mean_j x_j>: linear in the key features, autograd carries the heads and the mean (dagl.py:256-258)
+                mean_s = torch.bmm(wq_rows, x_rows.mean(dim=1).unsqueeze(2)).squeeze(2)
+                tau = mean_s * maps[2].reshape(B, -1) - maps[3].reshape(B, -1)
+            weight, score = _GraphAttend.apply(wq_rows, x_rows, tau, graph, float(self.softmax_scale), normalize,
+                                               self._ws_attend, self._ws_attend_bwd)
+            out = _GraphApply.apply(b2p, weight, graph, self._ws_apply, self._ws_apply_bwd) if apply else None
+        return weight, score, out
+
+    def attend_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference"):
+        """This block's own weights for ``b`` on the STRUCTURE of a given ``PatchGraph``: the same offsets and keys with new ``weight`` and
+        ``score`` -- S on the edges, the margin, the reference's softmax restricted to the graph (``ops.graph_attend``,
+        csrc/graph_attend.hip).  The structure may be ``graph(b)`` of another input or frame, of another module, edited or hand-built.
+
+        ``margin``: None = the module's mode ("topk": no margin, ``z = softmax_scale S``; "adaptive" / "adaptive_topk": the adaptive rule
+        ``m = relu(S - mean(S) thr + bias)``, ``z = softmax_scale S m``, edges with ``m = 0`` weigh 0); True / False override it.
+        ``normalize="reference"``: the reference's softmax over all N keys, every key off the graph counting as ``e^0`` -- on the
+        structure ``graph(b)`` exports this returns the export's weights; ``"edges"``: a plain softmax over each row's edges.  A row's
+        degree counts edges: a repeated key is an entry of its own.  ``score`` is the unscaled S.
+
+        Features come from the fp32 route, as in ``graph``: any ``in_channels``, half / bf16 modules on their fp32 copies under
+        ``torch.no_grad()``.  With autograd enabled and ``b`` or a parameter of g, fc1, fc2, thr_conv, bias_conv requiring grad, the
+        returned ``weight`` carries the autograd graph (fp32 parameters only); the structure is a constant.  The refusals are
+        ``apply_graph``'s, raised before any launch; after ``graph.validate()`` there is no host synchronisation.  The module's state
+        (packed weights, top-k policy, range verdicts, ``_train_dense``) is untouched."""
+        weight, score, _ = self._attend_on_graph(b, graph, "attend_graph", margin, normalize, False)
+        g = graph.with_weight(weight)
+        g.score = score
+        return g
+
+    def forward_on_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference") -> torch.Tensor:
+        """The block's output for ``b`` with its weights recomputed on the structure of ``graph``: ``apply_graph(b, attend_graph(b, graph))``
+        from one prologue call -- differentiable in ``b`` and every parameter of g, theta, fc1, fc2 and (with the margin) thr_conv,
+        bias_conv; selection over the L*N pairs is skipped.  Arguments, refusals and state as ``attend_graph``."""
+        out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True)[2]
+        return out if b.dtype == torch.float32 else out.to(b.dtype)
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """A module built with non-default ``ksize / stride_1 / stride_2 / inter_channels`` (dagl.py:175-176): the whole method through

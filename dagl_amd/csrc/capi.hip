@@ -1918,4 +1918,62 @@ int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2
                                        d_b2p, d_weight, workspace);
 }
 
+// (ABI 412) attention on a given patch graph: csrc/graph_attend.hip
+static size_t graph_attend_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
+    if (graph_apply_shape_ok(who, B, H, W, total_edges)) return 0;
+    return graph_attend_workspace_bytes(B, make_grid(H, W), total_edges, backward);
+}
+
+size_t dagl_graph_attend_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_attend_bytes("dagl_graph_attend_workspace_bytes", B, H, W, total_edges, false);
+}
+
+size_t dagl_graph_attend_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_attend_bytes("dagl_graph_attend_backward_workspace_bytes", B, H, W, total_edges, true);
+}
+
+// what both calls ask of their shared arguments
+static int graph_attend_operands_ok(const char* who, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                                    const int32_t* key, int64_t total_edges, float scale, int flags) {
+    const int rc = graph_apply_shape_ok(who, B, H, W, total_edges);
+    if (rc) return rc;
+    DAGL_REQUIRE(wq_rows && x_rows && row_off && (total_edges == 0 || key), "%s: null tensor pointer", who);
+    DAGL_REQUIRE(((uintptr_t)wq_rows % 16) == 0 && ((uintptr_t)x_rows % 16) == 0, "%s: feature rows must be 16-byte aligned", who);
+    DAGL_REQUIRE((flags & ~DAGL_GRAPH_ATTEND_EDGES_ONLY) == 0, "%s: unknown flags 0x%x", who, flags);
+    DAGL_REQUIRE(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
+    return DAGL_OK;
+}
+
+int dagl_graph_attend(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                      const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, float* score, float* weight,
+                      void* workspace, size_t ws_bytes) {
+    int rc = graph_attend_operands_ok("dagl_graph_attend", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
+    if (rc) return rc;
+    DAGL_REQUIRE(total_edges == 0 || (score && weight), "dagl_graph_attend: null tensor pointer");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace("dagl_graph_attend", workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, false)))) return rc;
+    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
+    return launch_graph_attend((hipStream_t)stream, B, g, c, score, weight, workspace);
+}
+
+int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                               const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, const float* score,
+                               const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
+                               const int32_t* perm, float* d_wq_rows, float* d_x_rows, float* d_tau, void* workspace, size_t ws_bytes) {
+    int rc = graph_attend_operands_ok("dagl_graph_attend_backward", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
+    if (rc) return rc;
+    DAGL_REQUIRE(total_edges == 0 || (score && weight && d_weight), "dagl_graph_attend_backward: null tensor pointer");
+    DAGL_REQUIRE(d_x_rows == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
+                 "dagl_graph_attend_backward: null transposed CSR (col_off, src_row, perm are required with d_x_rows)");
+    DAGL_REQUIRE(d_tau == nullptr || tau != nullptr, "dagl_graph_attend_backward: d_tau asked for without tau");
+    DAGL_REQUIRE(((uintptr_t)d_wq_rows % 16) == 0 && ((uintptr_t)d_x_rows % 16) == 0,
+                 "dagl_graph_attend_backward: gradient rows must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace("dagl_graph_attend_backward", workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, true))))
+        return rc;
+    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
+    return launch_graph_attend_backward((hipStream_t)stream, B, g, c, score, weight, d_weight, col_off, src_row, perm, d_wq_rows, d_x_rows,
+                                        d_tau, workspace);
+}
+
 }  // extern "C"

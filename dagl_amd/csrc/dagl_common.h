@@ -884,4 +884,17 @@ int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float
                                 const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
                                 const int32_t* perm, float* d_b2p /* or null */, float* d_weight /* or null */, void* workspace);
 
+// attention on a given patch graph (graph_attend.hip; ABI 412): what the forward and the backward call share
+struct GraphAttendCall {
+    const float* wq_rows; const float* x_rows;             // [B L, 196], [B N, 196]
+    const int64_t* row_off; const int32_t* key; int64_t E;
+    const float* tau;                                      // [B L] or null: no margin
+    float scale; bool edges_only;
+};
+size_t graph_attend_workspace_bytes(int B, const Grid& g, int64_t E, bool backward);
+int launch_graph_attend(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, float* score, float* weight, void* workspace);
+int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* score, const float* weight,
+                                 const float* d_weight, const int64_t* col_off, const int32_t* src_row, const int32_t* perm,
+                                 float* d_wq_rows /* or null */, float* d_x_rows /* or null */, float* d_tau /* or null */, void* workspace);
+
 }  // namespace dagl

@@ -18,13 +18,13 @@
 // A key (or perm entry) outside its range contributes nothing and is tested BEFORE an address is formed; row indices come out of a
 // bounded search: no array content can make a kernel read or write outside its buffers.
 #include "dagl_common.h"
+#include "graph_rows.h"
 
 namespace dagl {
 
 int launch_fold_patches(hipStream_t s, int B, int Hp, int Wp, int C, int k, int stride, int oy, int ox, int oh, int ow, const float* drows,
                         float* dmap);
 
-constexpr int GA_SEG = 128;                   // edges per block: dagl_graph_apply_segment()
 constexpr int GA_BATCH = 8;                   // gathers in flight per thread
 constexpr int GA_C4 = P / 4;                  // 196 float4 per patch row
 
@@ -37,16 +37,6 @@ struct GaArgs {
     float* out;                               // [n_rows, 784]
     float* part;                              // [chunks, 784]
 };
-
-// the row that holds edge p: the largest r in [0, n_rows) with row_off[r] <= p (empty rows share an offset with their successor)
-__device__ __forceinline__ int ga_row_of(const int64_t* __restrict__ row_off, int n_rows, long long p) {
-    int lo = 0, hi = n_rows - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (row_off[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // float4 offset of an edge's source row, -1 = the edge contributes nothing
 template <bool MAP>

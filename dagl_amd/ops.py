@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 
 import torch
@@ -473,6 +474,104 @@ def graph_apply_backward(d_out, b2p, row_off, key, weight, transposed=None, need
                                         _ptr(d_weight, E > 0), a, nbytes), "dagl_graph_apply_backward")
     del buf
     return d_b2p, d_weight
+
+
+_GRAPH_NORMALIZE = {"reference": 0, "edges": _lib.GRAPH_ATTEND_EDGES_ONLY}
+
+
+def _map_of(L: int, N: int):
+    """A map (H, W) with H*W = N keys and a stride-4 query grid of L rows: the graph-attend kernels use L and N alone, so any such map
+    describes the call (``hw`` names the real one)."""
+    for h in range(1, math.isqrt(N) + 1):
+        if N % h == 0:
+            lh, lw = query_grid(h, N // h)
+            if lh * lw == L:
+                return h, N // h
+    raise DaglError(f"graph_attend: no map of {N} keys has a stride-4 query grid of {L} rows")
+
+
+def _graph_attend_operands(who: str, wq_rows, x_rows, row_off, key, tau, normalize, hw):
+    """Shapes of a graph-attend call's operands -> (B, H, W, E, flags): ``_graph_apply_operands``' checks with the feature rows in the place
+    of the value map.  Array CONTENTS stay unread: the kernels bound every index themselves."""
+    _need(wq_rows, "wq_rows"); _need(x_rows, "x_rows"); _need(row_off, "row_off", torch.int64); _need(key, "key", torch.int32)
+    if wq_rows.dim() != 3 or x_rows.dim() != 3 or wq_rows.shape[2] != D or x_rows.shape[2] != D or wq_rows.shape[0] != x_rows.shape[0]:
+        raise DaglError(f"{who}: expected wq_rows [B,L,{D}] and x_rows [B,N,{D}], got {tuple(wq_rows.shape)} and {tuple(x_rows.shape)}")
+    B, L, N = wq_rows.shape[0], wq_rows.shape[1], x_rows.shape[1]
+    H, W = (int(v) for v in hw) if hw is not None else _map_of(L, N)
+    Lh, Lw = query_grid(H, W)
+    if H * W != N or Lh * Lw != L:
+        raise DaglError(f"{who}: a {H}x{W} map has {Lh * Lw} queries and {H * W} keys, the feature rows hold {L} and {N}")
+    if row_off.dim() != 1 or row_off.numel() != B * L + 1:
+        raise DaglError(f"{who}: row_off holds {row_off.numel()} offsets, expected B*L+1 = {B * L + 1}")
+    if key.dim() != 1:
+        raise DaglError(f"{who}: key must be 1-d with one entry per edge")
+    if tau is not None:
+        _need(tau, "tau")
+        if tau.numel() != B * L:
+            raise DaglError(f"{who}: tau holds {tau.numel()} values, expected B*L = {B * L}")
+    if normalize not in _GRAPH_NORMALIZE:
+        raise DaglError(f"{who}: normalize={normalize!r}, expected 'reference' or 'edges'")
+    return B, H, W, key.numel(), _GRAPH_NORMALIZE[normalize]
+
+
+@_on_device
+def graph_attend(wq_rows, x_rows, row_off, key, tau=None, scale: float = 10.0, normalize: str = "reference",
+                 workspace: "Workspace | None" = None, hw=None):
+    """The block's edge weights on a given graph structure (``dagl_graph_attend``, csrc/graph_attend.hip) -> (weight [E], score [E]):
+    wq_rows [B,L,196] / x_rows [B,N,196] the fc1 / fc2 features, (row_off [B*L+1] int64, key [E] int32) the CSR structure.
+    ``score`` = S_e = <wq_rows[r], x_rows[b, key_e]>; with ``tau`` [B*L] the adaptive rule m = relu(S - tau_r), z = scale S m, edges with
+    m = 0 weigh 0; without it z = scale S.  ``normalize="reference"``: the softmax of the reference over all N keys, every key off the
+    graph counting as e^0 (rows with fewer than N edges); ``"edges"``: a plain softmax over the row's edges.  A row's degree counts
+    EDGES: a repeated key is an entry of its own, not merged with its twin.  Keys outside [0, N) score 0 and weigh 0.  Nothing is read
+    on the host; the same arrays give the same bits on every call.  ``hw``: the map (H, W) when the caller knows it."""
+    lib = _lib.load()
+    B, H, W, E, flags = _graph_attend_operands("graph_attend", wq_rows, x_rows, row_off, key, tau, normalize, hw)
+    need = lib.dagl_graph_attend_workspace_bytes(B, H, W, E)
+    if need == 0:
+        check(-1, "dagl_graph_attend_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+    score = torch.empty(E, device=wq_rows.device, dtype=torch.float32)
+    weight = torch.empty_like(score)
+    check(lib.dagl_graph_attend(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
+                                _ptr(tau), float(scale), flags, _ptr(score, E > 0), _ptr(weight, E > 0), a, nbytes), "dagl_graph_attend")
+    del buf
+    return weight, score
+
+
+@_on_device
+def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
+                          normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,
+                          workspace: "Workspace | None" = None, hw=None):
+    """Gradients of ``graph_attend`` (``dagl_graph_attend_backward``) -> (d_wq [B,L,196] | None, d_x [B,N,196] | None, d_tau [B*L] | None)
+    from ``d_weight`` [E]; ``score`` / ``weight`` are the forward's outputs.  ``transposed`` = (col_off, src_row, perm), the graph's
+    transposed CSR (``PatchGraph.transpose``): required with ``need_x``.  ``d_tau`` is None without ``tau``."""
+    lib = _lib.load()
+    B, H, W, E, flags = _graph_attend_operands("graph_attend_backward", wq_rows, x_rows, row_off, key, tau, normalize, hw)
+    for n, t in (("d_weight", d_weight), ("score", score), ("weight", weight)):
+        _need(t, n)
+        if t.dim() != 1 or t.numel() != E:
+            raise DaglError(f"graph_attend_backward: {n} must be 1-d with one entry per edge ({E})")
+    col_off = src_row = perm = None
+    if need_x:
+        if transposed is None:
+            raise DaglError("graph_attend_backward: d_x needs the transposed CSR (col_off, src_row, perm)")
+        col_off, src_row, perm = transposed
+        _need(col_off, "col_off", torch.int64); _need(src_row, "src_row", torch.int32); _need(perm, "perm", torch.int32)
+        if col_off.numel() != B * H * W + 1 or src_row.numel() != E or perm.numel() != E:
+            raise DaglError(f"graph_attend_backward: the transposed CSR must hold B*N+1 = {B * H * W + 1} offsets and {E} edges")
+    need = lib.dagl_graph_attend_backward_workspace_bytes(B, H, W, E)
+    if need == 0:
+        check(-1, "dagl_graph_attend_backward_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+    d_wq = torch.empty_like(wq_rows) if need_wq else None
+    d_x = torch.empty_like(x_rows) if need_x else None
+    d_tau = torch.empty(B * wq_rows.shape[1], device=wq_rows.device, dtype=torch.float32) if need_tau and tau is not None else None
+    check(lib.dagl_graph_attend_backward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
+                                         _ptr(tau), float(scale), flags, _ptr(score, E > 0), _ptr(weight, E > 0), _ptr(d_weight, E > 0),
+                                         _ptr(col_off), _ptr(src_row, E > 0), _ptr(perm, E > 0), _ptr(d_wq), _ptr(d_x), _ptr(d_tau),
+                                         a, nbytes), "dagl_graph_attend_backward")
+    del buf
+    return d_wq, d_x, d_tau
 
 
 @_on_device

@@ -169,9 +169,10 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * bytes, dagl_ce_prologue takes `scratch`, dagl_ce_core_dense_forward takes `flags`, k <= 64; round 4: DAGL_FLAG_SAMPLED_TOPK,
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
- * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; workspace sizes unchanged).  A caller compares
+ * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
+ * workspace sizes unchanged).  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
-#define DAGL_ABI_VERSION 411
+#define DAGL_ABI_VERSION 412
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
 const char* dagl_last_error(void);              /* thread-local, never NULL                         */
 int         dagl_device_check(void);            /* OK iff the current HIP device is gfx950          */
@@ -329,6 +330,41 @@ int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2
                               const float* weight, int64_t total_edges, const float* d_out, const int64_t* col_off,
                               const int32_t* src_row, const int32_t* perm, float* d_b2p /* may be NULL */,
                               float* d_weight /* may be NULL */, void* workspace, size_t ws_bytes);
+
+/* ---- (ABI 412) attention on a GIVEN patch graph: csrc/graph_attend.hip ---------------------------------------------------------------
+ * The third leg next to the export and dagl_graph_apply: the block's own edge weights on a structure the caller supplies -- dagl.py:250-261
+ * restricted to the edges of the CSR -- and their gradients.  Rows r = b L + i, key_e in [0, N) a key of image b = r / L:
+ *   wq_rows [B,L,196], x_rows [B,N,196]  the fc1 / fc2 features (contiguous 784-byte rows, 16-byte aligned)
+ *   S_e = <wq_rows[r], x_rows[b, key_e]>                                       -> score [E]
+ *   tau [B L] given:  m_e = relu(S_e - tau_r), z_e = scale S_e m_e, on_e = (m_e != 0)   (the adaptive rule; tau_r = mean_j(S_rj) thr_r - bias_r)
+ *   tau NULL:         z_e = scale S_e, on_e = 1                                         (the fixed-k variant)
+ *   flags = 0:  M = max(max_e z_e, 0 if deg_r < N),  D = sum_e e^(z_e - M) + max(N - deg_r, 0) e^(-M): every key off the graph counts as
+ *               the reference's e^0;  DAGL_GRAPH_ATTEND_EDGES_ONLY: a plain softmax over the row's edges, M = max_e z_e, D = sum_e e^(z_e - M)
+ *   w_e = on_e e^(z_e - M) / D                                                 -> weight [E]
+ * deg_r counts edges: a repeated key is an entry of its own (it is NOT merged with its twin).  Empty rows produce nothing.  A key outside
+ * [0, N) is tested before an address is formed: it scores 0, weighs 0 and takes part in D with score 0.
+ * Edges are cut into segments of dagl_graph_apply_segment() whatever rows they belong to; maxima are fp32, the sums of the statistics fp64,
+ * every sum has a fixed order and there are no float atomics: the same arrays give the same bits on every call.  Grids come from
+ * total_edges and the row counts: nothing is read on the host, the calls can be captured.  total_edges = 0: key, score, weight may be NULL.
+ *
+ * dagl_graph_attend_backward: with g_e = d_weight[e], c_r = sum_e w_e g_e:
+ *   d S_e = scale (m_e + S_e) w_e (g_e - c_r) on edges with on_e (tau given), scale w_e (g_e - c_r) (tau NULL), else 0
+ *   d_tau [B L]           = -scale sum_on S_e w_e (g_e - c_r)                    (may be NULL; needs tau)
+ *   d_wq_rows [B,L,196]   = sum_{e in r} d S_e x_rows[b, key_e]                  (may be NULL)
+ *   d_x_rows [B,N,196]    = sum_{key_e = j} d S_e wq_rows[r_e]                   (may be NULL; needs the transposed CSR of
+ *                           dagl_graph_apply_backward: col_off [B N + 1], src_row [E], perm [E])
+ * Every element of a requested output is written.  score / weight are the forward's outputs. */
+#define DAGL_GRAPH_ATTEND_EDGES_ONLY 0x1
+size_t dagl_graph_attend_workspace_bytes(int B, int H, int W, int64_t total_edges);
+size_t dagl_graph_attend_backward_workspace_bytes(int B, int H, int W, int64_t total_edges);
+int dagl_graph_attend(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                      const int32_t* key, int64_t total_edges, const float* tau /* NULL: no margin */, float scale,
+                      int flags /* bit 0: edges-only normalisation */, float* score, float* weight, void* workspace, size_t ws_bytes);
+int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                               const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, const float* score,
+                               const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
+                               const int32_t* perm, float* d_wq_rows /* may be NULL */, float* d_x_rows /* may be NULL */,
+                               float* d_tau /* may be NULL */, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

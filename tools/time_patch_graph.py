@@ -2,6 +2,7 @@
 
     python tools/time_patch_graph.py [H W]          # default 256 256: top-k 8 and the dense adaptive regime
     python tools/time_patch_graph.py --apply [H W]  # what ``CE.apply_graph`` costs: forward / graph / apply / apply + backward
+    python tools/time_patch_graph.py --attend [H W] # what ``CE.attend_graph`` / ``forward_on_graph`` cost on the same three graphs
 """
 import os
 import sys
@@ -66,8 +67,7 @@ def apply_leg(H, W):
     from dagl_amd.synth import make_ce_params, make_features
     dev = torch.device("cuda:0")
     x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
-    for name, mode, k, variant, tail in (("top-k 8", "topk", 8, "default", False), ("sparse adaptive (gain 1.65)", "adaptive", 0, "sparse", False),
-                                         ("top-k 8 + 16 rows of degree N", "topk", 8, "default", True)):
+    for name, mode, k, variant, tail in _table_cases():
         prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=1.65).items()}
         ce = CE(in_channels=64)
         ce.load_state_dict(prm, strict=True)
@@ -100,9 +100,84 @@ def apply_leg(H, W):
               f"    ops.graph_apply alone {fmt(ker)}: {gbs:.2f} TB/s of E * (3136 + 8) algorithmic bytes", flush=True)
 
 
+def _table_cases():
+    return (("top-k 8", "topk", 8, "default", False), ("sparse adaptive (gain 1.65)", "adaptive", 0, "sparse", False),
+            ("top-k 8 + 16 rows of degree N", "topk", 8, "default", True))
+
+
+def attend_leg(H, W):
+    """forward / attend_graph / forward_on_graph / forward_on_graph forward + backward on the three graphs of ``apply_leg``, the two ops
+    calls alone (features given), and the module's own training path (``_forward_train`` forward, forward + backward) to compare with."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    for name, mode, k, variant, tail in _table_cases():
+        prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=1.65).items()}
+        ce = CE(in_channels=64)
+        ce.load_state_dict(prm, strict=True)
+        ce.select_mode, ce.select_k = mode, max(k, 1)
+        ce = ce.to(dev).eval()
+        with torch.no_grad():
+            g = ce.graph(x)
+            if tail:
+                g = _long_tailed(g)
+            g.validate()
+            g.transpose()
+            fwd = _events(lambda: ce(x))
+            att = _events(lambda: ce.attend_graph(x, g))
+            fog = _events(lambda: ce.forward_on_graph(x, g))
+            # the two ops calls alone, on the module's own features
+            from dagl_amd import train_ops as T
+            p = ce._params_f32(scaled=False)
+            b1p = ops.ce_prologue(x, p["g.weight"], p["g.bias"], p["theta.weight"], p["theta.bias"])[0]
+            wq = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], 16, 7), p["fc1.0.bias"], 7, 4, T._head_grid(H, W)[0],
+                                T._head_grid(H, W)[1], -(-H // 4), -(-W // 4), relu=True, allow_fast=False).contiguous()
+            xk = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], 16, 7), p["fc2.0.bias"], 7, 1, 0, 0, H, W, relu=True,
+                                allow_fast=False).contiguous()
+            tau = None
+            if mode != "topk":
+                heads = ops.ce_prologue(x, *(p[n] for n in ("g.weight", "g.bias", "theta.weight", "theta.bias", "thr_conv.weight",
+                                                             "thr_conv.bias", "bias_conv.weight", "bias_conv.bias")))
+                tau = (torch.bmm(wq, xk.mean(dim=1).unsqueeze(2)).squeeze(2) * heads[2].reshape(1, -1) - heads[3].reshape(1, -1)).contiguous()
+            ws, wsb = ops.Workspace(), ops.Workspace()
+            call = dict(tau=tau, scale=float(ce.softmax_scale), hw=(H, W))
+            k_f = _events(lambda: ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws, **call))
+            weight, score = ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws, **call)
+            d_w = torch.randn_like(weight)
+            k_b = _events(lambda: ops.graph_attend_backward(d_w, wq, xk, g.row_off, g.key, score, weight, transposed=g.transpose(),
+                                                            workspace=wsb, **call))
+        xg = x.clone().requires_grad_(True)
+
+        def both():
+            ce.forward_on_graph(xg, g).sum().backward()
+            xg.grad = None
+            ce.zero_grad(set_to_none=True)
+        fb = _events(both, repeats=5, inner=5)
+        ce.train()
+        with torch.no_grad():
+            trf = _events(lambda: ce._forward_train(x))
+
+        def train_both():
+            ce._forward_train(xg).sum().backward()
+            xg.grad = None
+            ce.zero_grad(set_to_none=True)
+        trb = _events(train_both, repeats=5, inner=5)
+        ce.eval()
+        print(f"[1,64,{H},{W}] {name}: {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {int(g.degrees().max())}\n"
+              f"    forward {fmt(fwd)}; attend_graph {fmt(att)}; forward_on_graph {fmt(fog)}; forward_on_graph forward + backward {fmt(fb)}\n"
+              f"    ops.graph_attend alone {fmt(k_f)}; ops.graph_attend_backward alone {fmt(k_b)}\n"
+              f"    the module's own training path (_forward_train, its own selection): forward {fmt(trf)}; forward + backward {fmt(trb)}",
+              flush=True)
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--apply":
         return apply_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
+    if len(sys.argv) > 1 and sys.argv[1] == "--attend":
+        return attend_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     from dagl_amd.ce import CE
     from dagl_amd.synth import make_ce_params, make_features
     H, W = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (256, 256)
