@@ -41,10 +41,10 @@ __global__ __launch_bounds__(256) void edge_softmax_fast_kernel(EdgeArgs a) {
     const float mtq = a.mt[ql], bsq = a.bs[ql];
     const bool valid = lane < n;
     const float lg = valid ? edge_logit(s, mtq, bsq, true) : 0.f;
-    double M = wave_max_d(valid ? (double)lg : -1e300);
+    double M = wave_max_f64(valid ? (double)lg : -1e300);
     if (n < a.N) M = fmax(M, 0.0);
     const double e = valid ? exp((double)lg - M) : 0.0;
-    const double sum = wave_sum_d(e) + (double)(a.N - n) * exp(-M);
+    const double sum = wave_sum_f64(e) + (double)(a.N - n) * exp(-M);
     if (valid) {
         a.nb_idx[ql * a.width + lane] = key;
         a.nb_wgt[ql * a.width + lane] = (float)(e / sum);
@@ -63,11 +63,11 @@ __global__ __launch_bounds__(256) void edge_softmax_csr_kernel(EdgeArgs a) {
     const float mtq = a.mt[ql], bsq = a.bs[ql];
     double M = -1e300;
     for (int64_t o = o0 + lane; o < o1; o += 64) M = fmax(M, (double)edge_logit(a.list_val[o], mtq, bsq, true));
-    M = wave_max_d(M);
+    M = wave_max_f64(M);
     if (n < a.N) M = fmax(M, 0.0);
     double sum = 0.0;
     for (int64_t o = o0 + lane; o < o1; o += 64) sum += exp((double)edge_logit(a.list_val[o], mtq, bsq, true) - M);
-    sum = wave_sum_d(sum) + (double)(a.N - n) * exp(-M);
+    sum = wave_sum_f64(sum) + (double)(a.N - n) * exp(-M);
     for (int64_t o = o0 + lane; o < o1; o += 64) {
         a.nb_idx[o] = a.list_idx[o];
         a.nb_wgt[o] = (float)(exp((double)edge_logit(a.list_val[o], mtq, bsq, true) - M) / sum);

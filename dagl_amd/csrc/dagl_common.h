@@ -222,6 +222,26 @@ __device__ __forceinline__ int wave_scan_incl_i32(int v) {
     v += dpp_zero_i<0x143, 0xc>(v);                                   // + rows 0..1 total into rows 2, 3
     return v;
 }
+// Sum / maximum over a block of 256 threads (all of them at the call), the same value in every thread.  Fixed order -- the xor
+// butterfly inside each wave, then (w0 + w1) + (w2 + w3) through sh -- so the same bits on every run.  The order decides the bits of
+// every row statistic of dense_train.hip and generic.hip: the DPP tree of wave_sum_f64 associates differently, and so does
+// graph.hip's graph_block_sum.  sh may be reused by the next call at once (the leading barrier).
+__device__ __forceinline__ double block_sum_f64(double v, double sh[4]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+__device__ __forceinline__ float block_max_f32(float v, float sh[4]) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
 
 #endif
 

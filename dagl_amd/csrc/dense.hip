@@ -52,6 +52,7 @@
 #include <type_traits>
 
 #include "dagl_common.h"
+#include "wide_select.h"
 
 namespace dagl {
 
@@ -87,12 +88,6 @@ constexpr float DN_PS = 32768.0f, DN_VS = 16.0f;      // power-of-two pre-scalin
 // (rows with many comparable keys average it down)
 constexpr float DN_SHIFT_SLACK = 18.5f;
 
-__device__ __forceinline__ float dn_logit(float s, float mtq, float bsq, bool& pass) {
-    const float m = (s - mtq) + bsq;                  // same expression order as dagl.py:256
-    pass = m > 0.f;
-    return pass ? __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE) : 0.f;
-}
-
 // the softmax shift of a row.  First pass: the logit of smax[q] (rowmax_exact_kernel, screen.hip): the row's largest score -- exact
 // (fp64-accumulated from the fp32 features) where the bf16 bounds of the screen lie more than DN_BOUND_OK logit units apart, their
 // upper bound otherwise -- inflated by 6e-6, more than the split-fp16 products of this kernel can differ from the exact score (three
@@ -102,7 +97,7 @@ __device__ __forceinline__ float dn_shift(const DenseArgs& a, size_t ql) {
     if (a.pass == 1) return a.m_exact[ql];
     const float sub = a.smax[ql] * (1.0f + 6e-6f);
     bool ps;
-    return fmaxf(dn_logit(sub, a.mt[ql], a.bs[ql], ps), 0.f);
+    return fmaxf(masked_logit(sub, a.mt[ql], a.bs[ql], ps), 0.f);
 }
 
 __device__ __forceinline__ dns4 dn_tr16(unsigned lds_byte_addr) {
@@ -553,7 +548,7 @@ __global__ __launch_bounds__(DN_THREADS) void dense_attend_kernel(DenseArgs a) {
             const float e0 = __builtin_amdgcn_exp2f(fminf(0.f - m_run, 0.f) * DN_LOG2E + 15.0f);     // 2^15 e^(0 - m_run): a masked key's weight
             const double z_run = zp_run + (double)(8 * n_t - n_inv - deg) * (double)e0;
             bool ps_;
-            const float lt = dn_logit(s_top, mtq, bsq, ps_);
+            const float lt = masked_logit(s_top, mtq, bsq, ps_);
             szz[wave][lane][0] = z_run * inv_ps; szz[wave][lane][1] = zp_run * inv_ps; sdg[wave][lane] = deg;
             slt[wave][lane] = ps_ ? fmaxf(lt, 0.f) : 0.f;
         }

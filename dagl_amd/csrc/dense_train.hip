@@ -166,76 +166,20 @@ __global__ __launch_bounds__(256) void dt_thresholds_kernel(int L, int N, const 
     }
 }
 
-__device__ __forceinline__ double dt_block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-__device__ __forceinline__ float dt_block_max(float v, float* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-
-// MODE 0: the adaptive mask (dagl.py:256-261).  MODE 1: the k best scores of the row, a 0/1 mask: logits 10 S on them
-// (GReccR2b_3mh_1-checkpoint.py:242-250).  MODE 2: both tests, m = relu(S - mean thr + bias) on the k best of the keys that pass.
-// (T, jt) = sort key of the k-th best score and the last key index taken AT that key (ties go to the lower index): dt_select_kernel.
-template <int MODE>
-__device__ __forceinline__ float dt_logit(float s, int j, float mtq, float bsq, unsigned T, int jt, bool& pass, float& m) {
-    if (MODE == 1) {
-        const unsigned key = wide_key(s, false, 0.f, 0.f);
-        pass = key > T || (key == T && j <= jt);
-        m = 1.f;
-        return pass ? __fmul_rn(s, SOFTMAX_SCALE) : 0.f;
-    }
-    m = (s - mtq) + bsq;                               // expression order of dagl.py:256
-    pass = m > 0.f;
-    if (MODE == 2) {
-        const unsigned key = pass ? __float_as_uint(fmaxf(s, 0.f)) + 1u : 0u;
-        pass = key != 0u && (key > T || (key == T && j <= jt));
-    }
-    return pass ? __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE) : 0.f;       // (S m) 10, dagl.py:259-260
-}
-
 // wide top-k modes: one block per query row of the chunk -> sel[ql] = (T, jt)
 template <bool ADAPTIVE>
 __global__ __launch_bounds__(256) void dt_select_kernel(int N, long long ldn, int L, int l0, int Lc, int k, const float* __restrict__ sbuf,
                                                         const float* __restrict__ mt, const float* __restrict__ bs,
                                                         int32_t* __restrict__ sel, int b0) {
     __shared__ WideSelShared shs;
-    __shared__ int sh_cnt[4];
-    __shared__ int sh_jt;
-    const int lr = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ WideTieShared sht;
+    const int lr = blockIdx.x, bi = blockIdx.y, tid = threadIdx.x;
     const size_t ql = (size_t)(b0 + bi) * L + l0 + lr;
     const float* row = sbuf + ((size_t)bi * Lc + lr) * ldn;
     const float mtq = ADAPTIVE ? mt[ql] : 0.f, bsq = ADAPTIVE ? bs[ql] : 0.f;
     unsigned T, need, bin_count;
     wide_radix_select(row, N, k, ADAPTIVE, mtq, bsq, shs, T, need, bin_count);
-    int jt = 0x7fffffff;
-    if (need < bin_count) {                                        // block-uniform: a tie at the k-th place, the `need` lowest key indices win
-        int run = 0;
-        for (int j0 = 0; j0 < N; j0 += 256) {
-            const int j = j0 + tid;
-            const bool eq = j < N && wide_key(row[j], ADAPTIVE, mtq, bsq) == T;
-            const unsigned long long eqb = __ballot(eq);
-            if (lane == 0) sh_cnt[w] = __popcll(eqb);
-            __syncthreads();
-            int before = run;
-            for (int u = 0; u < w; ++u) before += sh_cnt[u];
-            const int rank = before + __popcll(eqb & ((1ull << lane) - 1ull));
-            if (eq && rank == (int)need - 1) sh_jt = j;
-            run += sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
-            __syncthreads();
-            if (run >= (int)need) break;
-        }
-        jt = sh_jt;
-    }
+    const int jt = wide_tie_index(row, N, ADAPTIVE, mtq, bsq, T, need, bin_count, sht);
     if (tid == 0) { sel[2 * ql] = (int32_t)T; sel[2 * ql + 1] = jt; }
 }
 
@@ -258,31 +202,31 @@ __global__ __launch_bounds__(256) void dense_softmax_fwd_kernel(int N, long long
     int cnt = 0;
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(row[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(row[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         cnt += pass ? 1 : 0;
         mx = pass ? fmaxf(mx, l) : mx;
     }
     // (logits of passing keys are positive: S > 0 and m > 0, or zero when S = 0; so max over all keys = max(0, ...) either way)
-    const float M = dt_block_max(mx, shf);
+    const float M = block_max_f32(mx, shf);
     double z = 0.0;
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(row[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(row[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         z += (double)expf(l - M);
     }
-    const double Z = dt_block_sum(z, shd);
+    const double Z = block_sum_f64(z, shd);
     const float invz = (float)(1.0 / Z);
     double rs = 0.0;
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(row[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(row[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         const float a = pass ? expf(l - M) * invz : 0.f;
         row[j] = a;
         rs += (double)a;
     }
     for (int j = N + threadIdx.x; j < ldn; j += 256) row[j] = 0.f;           // pad columns: zero weights
-    const double RS = dt_block_sum(rs, shd);
-    const double C = dt_block_sum((double)cnt, shd);
+    const double RS = block_sum_f64(rs, shd);
+    const double C = block_sum_f64((double)cnt, shd);
     if (threadIdx.x == 0) {
         lse[2 * ql] = M; lse[2 * ql + 1] = (float)Z;
         deg[ql] = (int32_t)C; rowsum[ql] = (float)RS;
@@ -317,33 +261,33 @@ __global__ __launch_bounds__(256) void dense_softmax_bwd_kernel(int N, long long
 #pragma unroll 16
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(srow[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(srow[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         mx = pass ? fmaxf(mx, l) : mx;
     }
-    const float M = dt_block_max(mx, shf);
+    const float M = block_max_f32(mx, shf);
     double zz = 0.0;
 #pragma unroll 16
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(srow[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(srow[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         zz += (double)expf(l - M);
     }
-    const float invz = (float)(1.0 / dt_block_sum(zz, shd));
+    const float invz = (float)(1.0 / block_sum_f64(zz, shd));
     double c = 0.0;
 #pragma unroll 16
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
-        const float l = dt_logit<MODE>(srow[j], j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(srow[j], j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         const float a = pass ? expf(l - M) * invz : 0.f;
         c += (double)a * (double)arow[j];
     }
-    const float cf = (float)dt_block_sum(c, shd);
+    const float cf = (float)block_sum_f64(c, shd);
     double sdm = 0.0;
 #pragma unroll 16
     for (int j = threadIdx.x; j < N; j += 256) {
         bool pass; float m;
         const float s = srow[j];
-        const float l = dt_logit<MODE>(s, j, mtq, bsq, T, jt, pass, m);
+        const float l = row_logit<MODE>(s, j, mtq, bsq, SOFTMAX_SCALE, T, jt, pass, m);
         const float a = pass ? expf(l - M) * invz : 0.f;
         const float dl = a * (arow[j] - cf);           // non-neighbours: A = 0 and their logit is the constant 0
         const float ds = MODE == 1 ? SOFTMAX_SCALE * dl          // the 0/1 mask is a constant: d (10 S) / d S
@@ -354,7 +298,7 @@ __global__ __launch_bounds__(256) void dense_softmax_bwd_kernel(int N, long long
         sdm += (double)(SOFTMAX_SCALE * s * dl);       // d m
     }
     for (int j = N + threadIdx.x; j < ldn; j += 256) { srow[j] = 0.f; arow[j] = 0.f; }
-    const float S = (float)dt_block_sum(sdm, shd);
+    const float S = (float)block_sum_f64(sdm, shd);
     if (ds_word != nullptr) {                          // the split-fp16 products' scale for d S (order-independent integer maximum)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) ds_max = fmaxf(ds_max, __shfl_xor(ds_max, o));

@@ -141,36 +141,6 @@ __global__ __launch_bounds__(256) void gen_split_maps_kernel(int C, int H, int W
     reinterpret_cast<float4*>(m + (((size_t)b * Hp + yy + pg) * Wp + xx + pg) * C)[e < c4n ? e : e - c4n] = v;
 }
 
-__device__ __forceinline__ double gen_block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-__device__ __forceinline__ float gen_block_max(float v, float* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-
-// MODE 0 adaptive (dagl.py:256-261), 1 the k best (0/1 mask), 2 both.  (T, jt, tie): wide_radix_select's k-th sort key, the last
-// key index taken at that key when the k-th place is tied (ties go to the lower index)
-template <int MODE>
-__device__ __forceinline__ float gen_logit(float s, int j, float mtq, float bsq, float scale, unsigned T, int jt, bool& pass) {
-    float m = 1.f;
-    if (MODE != 1) { m = (s - mtq) + bsq; pass = m > 0.f; }          // expression order of dagl.py:256
-    if (MODE != 0) {
-        const unsigned key = wide_key(s, MODE == 2, mtq, bsq);
-        pass = key != 0u && (key > T || (key == T && j <= jt));
-    }
-    return pass ? __fmul_rn(__fmul_rn(s, m), scale) : 0.f;            // (S m) softmax_scale, dagl.py:259-260
-}
-
 // whether key j makes the reference's softmax row NaN: its logit S m softmax_scale is taken over ALL keys (dagl.py:259), so a
 // non-finite score poisons the row even where the mask is 0 (inf x 0, NaN x 0), and so does a mask value relu(m) that is NaN
 // (relu(NaN) != 0 passes the adaptive test, dagl.py:257) or +inf
@@ -195,8 +165,8 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
     __shared__ double shd[4];
     __shared__ float shf[4];
     __shared__ WideSelShared shs;
-    __shared__ int sh_cnt[4];
-    __shared__ int sh_jt;
+    __shared__ WideTieShared sht;
+    __shared__ int sh_cnt[4];                                      // (the LIST compaction's)
     const int lr = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const size_t ql = (size_t)b * L + l0 + lr;
     const float* row = sbuf + (size_t)lr * ldn;
@@ -205,51 +175,34 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
     if (MODE != 1) {
         double sm = 0.0;
         for (int j = tid; j < N; j += 256) sm += (double)row[j];
-        const float mean = (float)(gen_block_sum(sm, shd) / (double)N);           // yi.mean(dim=1), dagl.py:256
+        const float mean = (float)(block_sum_f64(sm, shd) / (double)N);           // yi.mean(dim=1), dagl.py:256
         mtq = __fmul_rn(mean, thr[ql * tstride]); bsq = bias[ql * tstride];
     }
     unsigned T = 0u; int jt = 0x7fffffff;
     if (MODE != 0) {
         unsigned need, bin_count;
         wide_radix_select(row, N, k, MODE == 2, mtq, bsq, shs, T, need, bin_count);
-        if (need < bin_count) {                                    // block-uniform: a tie at the k-th place, the `need` lowest key indices win
-            int run = 0;
-            for (int j0 = 0; j0 < N; j0 += 256) {
-                const int j = j0 + tid;
-                const bool eq = j < N && wide_key(row[j], MODE == 2, mtq, bsq) == T;
-                const unsigned long long eqb = __ballot(eq);
-                if (lane == 0) sh_cnt[w] = __popcll(eqb);
-                __syncthreads();
-                int before = run;
-                for (int u = 0; u < w; ++u) before += sh_cnt[u];
-                const int rank = before + __popcll(eqb & ((1ull << lane) - 1ull));
-                if (eq && rank == (int)need - 1) sh_jt = j;
-                run += sh_cnt[0] + sh_cnt[1] + sh_cnt[2] + sh_cnt[3];
-                __syncthreads();
-                if (run >= (int)need) break;
-            }
-            jt = sh_jt;
-        }
+        jt = wide_tie_index(row, N, MODE == 2, mtq, bsq, T, need, bin_count, sht);
     }
     float mx = -__builtin_inff(); int cnt = 0;                     // the softmax runs over ALL keys: a masked key's logit is 0 (dagl.py:259: yi * mask)
     bool bad = false;
     for (int j = tid; j < N; j += 256) {
-        bool pass;
-        const float l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
+        bool pass; float m;
+        const float l = row_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass, m);
         cnt += pass ? 1 : 0;
         mx = fmaxf(mx, l);
         bad = bad || gen_nonfinite<MODE>(row[j], mtq, bsq);
     }
     const bool row_nan = __syncthreads_or(bad) != 0;
     const float qnan = __int_as_float(0x7fc00000);
-    const float M = gen_block_max(mx, shf);
+    const float M = block_max_f32(mx, shf);
     double z = 0.0;
     for (int j = tid; j < N; j += 256) {
-        bool pass;
-        const float l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
+        bool pass; float m;
+        const float l = row_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass, m);
         z += (double)expf(l - M);
     }
-    const float invz = (float)(1.0 / gen_block_sum(z, shd));
+    const float invz = (float)(1.0 / block_sum_f64(z, shd));
     if (LIST && row_nan) {
         for (int e = tid; e < k; e += 256) { nb_idx[(size_t)lr * k + e] = e; nb_wgt[(size_t)lr * k + e] = qnan; }
     } else if (LIST) {
@@ -260,8 +213,8 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
         int run = 0;
         for (int j0 = 0; j0 < N; j0 += 256) {
             const int j = j0 + tid;
-            bool pass = false; float l = 0.f;
-            if (j < N) l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
+            bool pass = false; float l = 0.f, m;
+            if (j < N) l = row_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass, m);
             const unsigned long long pb = __ballot(pass);
             if (lane == 0) sh_cnt[w] = __popcll(pb);
             __syncthreads();
@@ -276,8 +229,8 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
         for (int e = run + tid; e < k; e += 256) { li[e] = -1; lw[e] = 0.f; }
     } else {
         for (int j = tid; j < N; j += 256) {
-            bool pass;
-            const float l = gen_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass);
+            bool pass; float m;
+            const float l = row_logit<MODE>(row[j], j, mtq, bsq, scale, T, jt, pass, m);
             arow[j] = pass ? expf(l - M) * invz : 0.f;             // softmax * mask_b, dagl.py:260-261
         }
         // (a loop of its own: folded into the select above, the compiler fused "l - M" into an FMA there, and the finite rows' weights
@@ -286,7 +239,7 @@ __global__ __launch_bounds__(256) void gen_row_softmax_kernel(int N, long long l
             for (int j = tid; j < N; j += 256) arow[j] = qnan;
         for (int j = N + tid; j < ldn; j += 256) arow[j] = 0.f;
     }
-    const double Cn = gen_block_sum((double)cnt, shd);
+    const double Cn = block_sum_f64((double)cnt, shd);
     if (tid == 0 && deg != nullptr) deg[ql] = (int32_t)Cn;
 }
 
@@ -375,12 +328,12 @@ __global__ __launch_bounds__(256) void gen_row_backward_kernel(int N, long long 
     if (MODE != 1) {
         double sm = 0.0;
         for (int j = tid; j < N; j += 256) sm += (double)srow[j];
-        mean = (float)(gen_block_sum(sm, shd) / (double)N);
+        mean = (float)(block_sum_f64(sm, shd) / (double)N);
         mtq = __fmul_rn(mean, thr[ql]); bsq = bias[ql];
     }
     double cs = 0.0;
     for (int j = tid; j < N; j += 256) cs += (double)arow[j] * (double)drow[j];
-    const float c = (float)gen_block_sum(cs, shd);
+    const float c = (float)block_sum_f64(cs, shd);
     double ts = 0.0;
     for (int j = tid; j < N; j += 256) {
         const float a = arow[j], sj = srow[j];
@@ -398,7 +351,7 @@ __global__ __launch_bounds__(256) void gen_row_backward_kernel(int N, long long 
     }
     for (int j = N + tid; j < ldn; j += 256) drow[j] = 0.f;
     if (MODE != 1) {
-        const double t = gen_block_sum(ts, shd);
+        const double t = block_sum_f64(ts, shd);
         if (tid == 0) {
             d_bias[ql] = (float)t;
             d_thr[ql] = (float)(-t * (double)mean);

@@ -35,7 +35,8 @@ struct GraphArgs {
     long long capacity;
 };
 
-// logit of a kept key: 10 S m with m = relu(S - mean thr + bias) as the mask saw it (fp32), m = 1 in the fixed-k mode
+// logit of a kept key: 10 S m with m = relu(S - mean thr + bias) as the mask saw it (fp32), m = 1 in the fixed-k mode -- in fp64, unlike the
+// fp32 forms of wide_select.h
 __device__ __forceinline__ double graph_logit(float s, bool adaptive, float mtq, float bsq) {
     const double m = adaptive ? (double)((s - mtq) + bsq) : 1.0;
     return (double)SOFTMAX_SCALE * (double)s * m;
@@ -68,6 +69,7 @@ struct GraphCountShared {
     int ired[2][GR_THREADS / 64];
 };
 
+// (an LDS tree over all the threads: another association, so other bits, than block_sum_f64 / block_max_f32 of dagl_common.h)
 __device__ __forceinline__ double graph_block_sum(double v, double* dred) {      // fixed tree: the same sum on every run
     const int tid = threadIdx.x;
     dred[tid] = v;

@@ -13,14 +13,9 @@
 #include "dagl_common.h"
 #include "aggregate_direct.h"
 #include "row_attend.h"
+#include "wide_select.h"
 
 namespace dagl {
-
-__device__ __forceinline__ float ovf_logit(float s, float mtq, float bsq, bool& pass) {
-    const float m = (s - mtq) + bsq;                                      // dagl.py:256, same expression order
-    pass = m > 0.f;
-    return pass ? __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE) : 0.f;
-}
 
 constexpr int OVF_SMALL = 16;     // up to this many flagged queries the scores come from a VALU kernel, beyond that from ONE matrix
                                   // product [flagged, 196] x [196, N] on the fp32 matrix cores
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(256) void ovf_count_kernel(OvfArgs a) {
         int cnt = 0;
         for (int c0 = j0; c0 < j1; c0 += 64) {
             const int j = c0 + lane; bool pass = false;
-            if (j < j1) (void)ovf_logit(row[j], mtq, bsq, pass);
+            if (j < j1) (void)masked_logit(row[j], mtq, bsq, pass);
             cnt += __popcll(__ballot(pass));
         }
         if (lane == 0) shc[w] = cnt;
@@ -152,7 +147,7 @@ __global__ __launch_bounds__(256) void ovf_attend_kernel(OvfArgs a) {
         int cnt = 0;
         for (int c0 = j0; c0 < j1; c0 += 64) {
             const int j = c0 + lane; bool pass = false;
-            if (j < j1) (void)ovf_logit(row[j], mtq, bsq, pass);
+            if (j < j1) (void)masked_logit(row[j], mtq, bsq, pass);
             cnt += __popcll(__ballot(pass));
         }
         if (lane == 0) shc[w] = cnt;
@@ -166,7 +161,7 @@ __global__ __launch_bounds__(256) void ovf_attend_kernel(OvfArgs a) {
         RowAcc o; row_acc_clear(o);
         if (cnt_blk > 0)                                                         // block-uniform
             row_wave_walk(a.g, vmb, cols, lane, j0, j1, gather,
-                          [&](int j, bool in, float& l) { bool pass = false; if (in) l = ovf_logit(row[j], mtq, bsq, pass); return pass; }, o);
+                          [&](int j, bool in, float& l) { bool pass = false; if (in) l = masked_logit(row[j], mtq, bsq, pass); return pass; }, o);
         row_block_store(sh, cols, o, cnt_blk, a.part + ((size_t)slot * ROW_CHUNKS + chunk) * ROW_PART_FLOATS);
     }
 }

@@ -18,6 +18,7 @@
 // Keys passing these tests are the candidates; a (query, chunk, half) segment that receives more than its
 // slot count raises a flag and that query group is redone by the exact fp32 kernel (select.hip).
 #include "dagl_common.h"
+#include "wide_select.h"
 
 namespace dagl {
 
@@ -692,12 +693,6 @@ int launch_screen_theta(hipStream_t s, int n_rows, int G, int k, const float* gm
 constexpr int RF_MAX_CAND = 1024;
 constexpr int RF_ROUNDS_MAX_K = 16;                 // up to this k the candidate threshold is tightened by k rounds of wave maxima, beyond by a bit-wise search
 
-__device__ __forceinline__ float rf_logit(float s, float mtq, float bsq, bool adaptive) {
-    float m = 1.0f;
-    if (adaptive) m = (s - mtq) + bsq;
-    return __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE);
-}
-
 // (value desc, key asc) ordering used everywhere a "k best" is taken
 __device__ __forceinline__ bool rf_before(float va, int ka, float vb, int kb) {
     return (va > vb) || (va == vb && ka < kb);
@@ -1033,7 +1028,7 @@ __device__ __forceinline__ void refine_query(const RefineArgs& a, const size_t q
     for (int u = 0; u < RU; ++u) {
         const int e = (u == 0) ? pos0 : lane + 64 * u;
         const bool valid = e >= 0 && e < n;
-        lg[u] = valid ? rf_logit(my_s[u], mtq, bsq, adaptive) : 0.f;
+        lg[u] = valid ? edge_logit(my_s[u], mtq, bsq, adaptive) : 0.f;
         if (valid) M = fmax(M, (double)lg[u]);
     }
     M = wave_max_f64(M);
@@ -1118,10 +1113,6 @@ __global__ __launch_bounds__(64 * RF_HEAVY_WAVES) void refine_heavy_kernel(Refin
 //     maximum and dense_combine_kernel flags its block for the second pass: the round-4 mechanism, now the fallback of the fallback.
 // Output: smax[q] = a score whose logit (dense.hip dn_shift) is the row's shift.
 constexpr float DN_BOUND_OK = 12.0f;
-__device__ __forceinline__ float rm_logit(float sc, float mtq, float bsq) {
-    const float m = (sc - mtq) + bsq;                     // dagl.py:256, the expression order of dense.hip dn_logit
-    return m > 0.f ? __fmul_rn(__fmul_rn(sc, m), SOFTMAX_SCALE) : 0.f;
-}
 __global__ __launch_bounds__(256) void rowmax_exact_kernel(RefineArgs a, float* __restrict__ smax) {
     __shared__ int c_idx[4][RF_MAX_CAND];
     __shared__ float c_val[4][RF_MAX_CAND];
@@ -1147,7 +1138,8 @@ __global__ __launch_bounds__(256) void rowmax_exact_kernel(RefineArgs a, float* 
     overflow = __any(overflow) || total > RF_MAX_CAND;
     const float s_hi = sm * (1.0f / (1.0f - DELTA)) * (1.0f + 1e-6f), s_lo = sm * (1.0f / (1.0f + DELTA));
     const float mtq = a.mt[ql], bsq = a.bs[ql];
-    if (overflow || rm_logit(s_hi, mtq, bsq) - rm_logit(s_lo, mtq, bsq) <= DN_BOUND_OK) {      // (wave-uniform)
+    bool ps;                                               // (the bounds of a masked row: both 0)
+    if (overflow || masked_logit(s_hi, mtq, bsq, ps) - masked_logit(s_lo, mtq, bsq, ps) <= DN_BOUND_OK) {      // (wave-uniform)
         if (lane == 0) smax[ql] = s_hi;
         return;
     }

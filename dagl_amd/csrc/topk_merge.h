@@ -1,23 +1,10 @@
-// Shared by aggregate.hip (edge softmax kernels) and select.hip (the fused redo kernel of the top-k modes): the edge logit, fp64
-// wave reductions, and the merge of a query's per-(chunk, half) k-best lists into its exact k best + weights.
+// Shared by aggregate.hip (edge softmax kernels) and select.hip (the fused redo kernel of the top-k modes): the merge of a query's
+// per-(chunk, half) k-best lists into its exact k best + weights.
 #pragma once
 #include "dagl_common.h"
+#include "wide_select.h"
 
 namespace dagl {
-
-// ------------------------------------------------------------------------------------------------------
-// edge softmax
-// ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float edge_logit(float s, float mtq, float bsq, bool adaptive) {
-    // l = (S * m) * 10 in fp32, m = relu((S - mean*thr) + bias) or 1  -- the reference's operation order
-    float m = 1.0f;
-    if (adaptive) m = (s - mtq) + bsq;
-    return __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE);
-}
-
-// (all 64 lanes active at every call site; DPP forms: dagl_common.h)
-__device__ __forceinline__ double wave_max_d(double v) { return wave_max_f64(v); }
-__device__ __forceinline__ double wave_sum_d(double v) { return wave_sum_f64(v); }
 
 // MODE 2/3: merge the per-(chunk, half) k-best candidate lists of a query into its exact k best
 // (value descending, ties -> smaller key index), then weights.  One wave per query; candidates in LDS.
@@ -63,10 +50,10 @@ __device__ __forceinline__ void edge_softmax_topk_unit(const EdgeArgs& a, int ks
     }
     const bool valid = lane < n;
     const float lg = valid ? edge_logit(my_s, mtq, bsq, adaptive) : 0.f;
-    double M = wave_max_d(valid ? (double)lg : -1e300);
+    double M = wave_max_f64(valid ? (double)lg : -1e300);
     if (n < a.N) M = fmax(M, 0.0);
     const double e = valid ? exp((double)lg - M) : 0.0;
-    const double sum = wave_sum_d(e) + (double)(a.N - n) * exp(-M);
+    const double sum = wave_sum_f64(e) + (double)(a.N - n) * exp(-M);
     if (valid) {
         a.nb_idx[ql * a.width + lane] = my_key;
         a.nb_wgt[ql * a.width + lane] = (float)(e / sum);

@@ -17,11 +17,6 @@
 
 namespace dagl {
 
-__device__ __forceinline__ float wide_logit(float s, bool adaptive, float mtq, float bsq) {
-    // top-k: softmax(10 S mask), mask in {0, 1} (GReccR2b_3mh_1-checkpoint.py:248-250); intersection: 10 S m, m = relu(S - mt + bs)
-    return adaptive ? __fmul_rn(__fmul_rn(s, (s - mtq) + bsq), SOFTMAX_SCALE) : __fmul_rn(s, SOFTMAX_SCALE);
-}
-
 constexpr int WIDE_RANGES = ROW_CHUNKS * 4;          // (chunk, wave) key ranges of the attend kernel
 
 // block = one row.  sel[slot] = {threshold key T, keys to take with key == T (0x7fffffff: all of them), -, -};
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(256) void wide_attend_kernel(WideArgs a) {
                           const int rank = eq_seen + __popcll(eqb & ((1ull << lane) - 1ull));
                           eq_seen += __popcll(eqb);
                           const bool pass = in && key != 0u && (key > T || (eq && rank < need));
-                          if (pass) l = wide_logit(s, adaptive, mtq, bsq);
+                          if (pass) l = edge_logit(s, mtq, bsq, adaptive);
                           return pass;
                       }, o);
         if (lane == 0) shc[w] = o.cnt;
@@ -312,7 +307,7 @@ __global__ __launch_bounds__(WL_THREADS) void wide_list_kernel(WideArgs a) {
                 const int j = sh.u.c.ckey[w][i];
                 const int jy = j / a.g.W, jx = j - jy * a.g.W;
                 sh.lst_of[pos] = (jy * a.g.Wp + jx) * (CH / 4);
-                sh.lst_w[pos] = wide_logit(sh.u.c.cscore[w][i], adaptive, mtq, bsq);
+                sh.lst_w[pos] = edge_logit(sh.u.c.cscore[w][i], mtq, bsq, adaptive);
             }
         }
     }
@@ -346,7 +341,7 @@ __global__ __launch_bounds__(WL_THREADS) void wide_list_kernel(WideArgs a) {
                 const float4 v = *reinterpret_cast<const float4*>(xr + c);
                 acc += (double)qrow[c] * (double)v.x + (double)qrow[c + 1] * (double)v.y + (double)qrow[c + 2] * (double)v.z + (double)qrow[c + 3] * (double)v.w;
             }
-            const float lg = wide_logit((float)acc, adaptive, mtq, bsq);
+            const float lg = edge_logit((float)acc, mtq, bsq, adaptive);
             sh.lst_w[e] = lg;
             m2 = fmaxf(m2, lg);
         }

@@ -1,16 +1,55 @@
-// Row-wise selection of the k best scores by radix selection over the scores' bit patterns (shared by the inference form of the wide
-// top-k modes, topk_wide.hip, and their differentiable form, dense_train.hip).  Reference: top_k = min(num_edge, N) best scores of
-// every query, GReccR2b_3mh_1-checkpoint.py:242-250 (CA_model-checkpoint.py:134-143 uses 500).
+// What every route's mask and softmax share: the logit of a key (three forms, below), and the row-wise selection of the k best scores
+// by radix selection over the scores' bit patterns with its rule for a tie at the k-th place (the inference form of the wide top-k
+// modes, topk_wide.hip; their differentiable form, dense_train.hip; the generic-geometry route, generic.hip; the graph export,
+// graph.hip).  Reference: top_k = min(num_edge, N) best scores of every query, GReccR2b_3mh_1-checkpoint.py:242-250
+// (CA_model-checkpoint.py:134-143 uses 500).
 #pragma once
 #include "dagl_common.h"
 
 namespace dagl {
+
+// ------------------------------------------------------------------------------------------------------
+// The logit of a key.  m = (S - mean thr) + bias, pass = m > 0, l = (S m) scale: DN_Gray/model/dagl.py:256-260 in fp32, in the
+// reference's expression order, the products rounded one by one (__fmul_rn: no contraction into an FMA, whatever surrounds the call)
+// -- this is what ties every route to the reference bit for bit.  The fixed-k variant's mask is 0/1, so m = 1 on a kept key:
+// l = S scale (GReccR2b_3mh_1-checkpoint.py:242-250).  mtq = mean thr and bsq = bias of the query.
+// Separate by design: gt_logit (graph_attend.hip) forms scale S m with m = relu(S - tau), a rounding order its backward depends on;
+// graph_logit (graph.hip) forms the products in fp64; dense_attend_kernel (dense.hip) has the same expression packed two keys wide (dnf2) in its
+// fenced block at the register cap.
+// ------------------------------------------------------------------------------------------------------
+// a key that is kept (a list entry): no mask test
+__device__ __forceinline__ float edge_logit(float s, float mtq, float bsq, bool adaptive) {
+    float m = 1.0f;
+    if (adaptive) m = (s - mtq) + bsq;
+    return __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE);
+}
+// the adaptive mask: a masked key's logit is 0 (the softmax runs over ALL keys, dagl.py:259: yi * mask)
+__device__ __forceinline__ float masked_logit(float s, float mtq, float bsq, bool& pass) {
+    const float m = (s - mtq) + bsq;
+    pass = m > 0.f;
+    return pass ? __fmul_rn(__fmul_rn(s, m), SOFTMAX_SCALE) : 0.f;
+}
 
 // sort key of a score: 0 = "not a candidate" (fails the adaptive test of the intersection mode), else bits + 1
 // (scores are >= 0 -- sums of products of post-ReLU features --, so their bit patterns sort like the values)
 __device__ __forceinline__ unsigned wide_key(float s, bool adaptive, float mtq, float bsq) {
     if (adaptive && !(((s - mtq) + bsq) > 0.f)) return 0u;
     return __float_as_uint(fmaxf(s, 0.f)) + 1u;
+}
+// whether key j is one of the k best: (T, jt) = sort key of the k-th best score (wide_radix_select) and the last key index taken
+// AT that key (wide_tie_index: ties go to the lower index)
+__device__ __forceinline__ bool wide_taken(unsigned key, int j, unsigned T, int jt) {
+    return key != 0u && (key > T || (key == T && j <= jt));
+}
+
+// a key of a whole score row.  MODE 0: the adaptive mask.  MODE 1: the k best scores of the row, a 0/1 mask (m = 1).  MODE 2: both
+// tests, m = relu(S - mean thr + bias) on the k best of the keys that pass.  m is what the backward needs (d S = scale (m + S) d l).
+template <int MODE>
+__device__ __forceinline__ float row_logit(float s, int j, float mtq, float bsq, float scale, unsigned T, int jt, bool& pass, float& m) {
+    m = 1.f;
+    if (MODE != 1) { m = (s - mtq) + bsq; pass = m > 0.f; }
+    if (MODE != 0) pass = wide_taken(wide_key(s, MODE == 2, mtq, bsq), j, T, jt);
+    return pass ? __fmul_rn(__fmul_rn(s, m), scale) : 0.f;
 }
 
 struct WideSelShared {
@@ -63,6 +102,31 @@ __device__ __forceinline__ void wide_radix_select(const float* __restrict__ row,
         bin_count = sh.bin_count;
     }
     T = sh.prefix; need = sh.remaining;
+}
+
+// A tie at the k-th place, after wide_radix_select (same block, same row): the `need` lowest key indices of the `bin_count` keys equal
+// to T win.  Returns the last key index taken at T -- 0x7fffffff when all of them are (need >= bin_count).  Block-uniform.
+struct WideTieShared { int cnt[4]; int jt; };
+__device__ __forceinline__ int wide_tie_index(const float* __restrict__ row, int N, bool adaptive, float mtq, float bsq, unsigned T,
+                                              unsigned need, unsigned bin_count, WideTieShared& sh) {
+    if (need >= bin_count) return 0x7fffffff;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int run = 0;
+    for (int j0 = 0; j0 < N; j0 += 256) {
+        const int j = j0 + tid;
+        const bool eq = j < N && wide_key(row[j], adaptive, mtq, bsq) == T;
+        const unsigned long long eqb = __ballot(eq);
+        if (lane == 0) sh.cnt[w] = __popcll(eqb);
+        __syncthreads();
+        int before = run;
+        for (int u = 0; u < w; ++u) before += sh.cnt[u];
+        const int rank = before + __popcll(eqb & ((1ull << lane) - 1ull));
+        if (eq && rank == (int)need - 1) sh.jt = j;
+        run += sh.cnt[0] + sh.cnt[1] + sh.cnt[2] + sh.cnt[3];
+        __syncthreads();
+        if (run >= (int)need) break;
+    }
+    return sh.jt;
 }
 
 }  // namespace dagl

@@ -62,6 +62,10 @@ CASES = {
     # ([1,36,40] has L = 90 < 128 queries: a chunk never holds fewer than 128, so it stays one chunk under any budget)
     "wide_topk90_ties_chunks2": dict(shape=(1, 48, 50), budget=_budget(128, 48, 50), plan=dict(Lc=128, n_chunks=2), mode="topk", k=90,
                                      ties=True),
+    # ... and with the adaptive test in force but passed by every key (thr = 0, bias = 1: m = S + 1 >= 1), so that the tie falls where
+    # the topk case has it: the tie rule is shared by both modes
+    "wide_adaptive_topk90_ties_chunks2": dict(shape=(1, 48, 50), budget=_budget(128, 48, 50), plan=dict(Lc=128, n_chunks=2),
+                                              mode="adaptive_topk", k=90, ties=True),
 }
 _SEEDS = {name: zlib.crc32(name.encode()) for name in CASES}       # (a case added later leaves the others' inputs alone)
 
@@ -129,7 +133,9 @@ def case_inputs(name):
             wq[close] = torch.rand(int(close.sum()), 196, generator=g) * 0.1
         facts["kth_gap"] = _kth_gap(wq, xr, k)
     thr = bias = None
-    if mode != "topk":
+    if mode != "topk" and case.get("ties"):
+        thr, bias = torch.zeros(B, L), torch.ones(B, L)                    # scores are sums of non-negative products: every key passes
+    elif mode != "topk":
         S = torch.einsum("bld,bnd->bln", wq.double(), xr.double())
         T = _midgap_thresholds(S)
         if case.get("degenerate"):
@@ -269,6 +275,7 @@ def test_wide_modes_across_chunks_and_groups_match_fp64(name):
     gap = facts["kth_gap"]
     if case.get("ties"):
         assert bool((gap == 0).all())                      # every row ties at the k-th place: the lower key index decides
+        assert bool((reference(name)["deg"] == case["k"]).all())             # ... and exactly k keys are taken, not all that reach the k-th score
     else:
         assert float(gap.min()) > 1e-5, float(gap.min())   # no row leaves the choice of its k-th key to fp32 rounding
     out, grads, info = run_case(name)

@@ -221,14 +221,16 @@ def test_generic_fixed_k_beyond_the_lists_against_the_fp64_oracle(geom, mode, va
 
 def test_generic_fixed_k_ties_at_the_kth_place():
     """A constant input map: the interior keys' scores are all equal; exactly k keys are taken on either side of the lists' cutoff
-    and far beyond it, not every key that reaches the k-th score."""
+    and far beyond it, not every key that reaches the k-th score.  "adaptive_topk" with heads that let every key pass: the tie rule
+    is shared by both modes."""
     from dagl_amd import ops
-    params = {n: t.to(DEV) for n, t in _params(405, ksize=5).items()}
     x = torch.full((1, 64, 24, 28), 0.25, device=DEV)                           # N = 672
-    for k in (64, 65, 300):
-        out, deg = ops.ce_forward_generic(x, params, 5, 3, 1, 16, mode="topk", k=k, want_degree=True)
-        assert int(deg.min()) == k == int(deg.max()), k
-        assert bool(torch.isfinite(out).all()), k
+    for mode, variant in (("topk", "default"), ("adaptive_topk", "allpass")):
+        params = {n: t.to(DEV) for n, t in _params(405, ksize=5, variant=variant).items()}
+        for k in (64, 65, 300):
+            out, deg = ops.ce_forward_generic(x, params, 5, 3, 1, 16, mode=mode, k=k, want_degree=True)
+            assert int(deg.min()) == k == int(deg.max()), (mode, k)
+            assert bool(torch.isfinite(out).all()), (mode, k)
 
 
 def test_generic_fixed_k_over_two_chunks_of_score_rows():
