@@ -235,7 +235,7 @@ class CE(nn.Module):
         self._ws = ops.Workspace()
         self._ws_bwd = ops.Workspace()
         self._ws_graph = ops.Workspace()  # graph() / degrees(): a buffer of their own, so that the forward's packed weights and policy words survive
-        self._ws_apply = ops.Workspace()      # apply_graph(): its aggregated and partial rows; its backward's rows
+        self._ws_apply = ops.Workspace()      # apply_graph() and the fused forward_on_graph(): aggregated and partial rows; the backward's rows
         self._ws_apply_bwd = ops.Workspace()
         self._ws_attend = ops.Workspace()     # attend_graph() / forward_on_graph(): the row statistics; the backward's sums and partial rows
         self._ws_attend_bwd = ops.Workspace()
@@ -694,14 +694,20 @@ class CE(nn.Module):
     _FP32_ONLY = ("CE: the differentiable path needs fp32 parameters (the reference's --precision half is a test-time "
                   "switch, DN_Gray/model/__init__.py:98-99); run half-precision modules under torch.no_grad()")
 
-    def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool):
-        """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route, ``tau`` in plain
-        torch, ``_GraphAttend`` and -- ``apply`` -- ``_GraphApply`` on the same value map.  -> (weight, score, out | None)."""
+    def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool, features: str = "fp32",
+                         fused=False):
+        """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route or
+        (``features="split16"``) the training path's split-fp16 kernels, ``tau`` in plain torch, then ``_GraphAttend`` and -- ``apply`` --
+        ``_GraphApply`` on the same value map, or (``fused``; None = with ``features="split16"`` whenever no gradient is wanted)
+        ``ops.graph_forward`` in their place.  -> (weight, score, out | None); the fused call returns (None, None, out)."""
         from types import SimpleNamespace
         from . import train_ops as T
         self._check_given_graph(b, graph, what)
         if normalize not in ("reference", "edges"):
             raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
+        if features not in ("fp32", "split16"):
+            raise DaglError(f"CE.{what}: features={features!r}, expected 'fp32' or 'split16'")
+        fast = features == "split16"
         if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
             raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
         margin = self.select_mode != "topk" if margin is None else bool(margin)
@@ -709,11 +715,16 @@ class CE(nn.Module):
         used = [self.g, self.fc1, self.fc2] + ([self.theta] if apply else []) + ([self.thr_conv, self.bias_conv] if margin else [])
         grad = torch.is_grad_enabled() and (b.requires_grad or any(p.requires_grad for m in used for p in m.parameters()))
         if grad:
+            if fused:
+                raise DaglError(f"CE.{what}: fused=True has no backward (a gradient is wanted for the input or a parameter); "
+                                "fused=None or False keeps the two differentiable ops")
             if any(p.dtype != torch.float32 for p in self.parameters()):
                 raise DaglError(self._FP32_ONLY)
             p = {n: t for n, t in self.named_parameters()}
         else:
             p = self._params_f32(scaled=False)
+        # (None: the fused kernel belongs to the opt-in route -- the default call keeps the bits of the two-op composition)
+        fused = apply and not grad and (fast if fused is None else bool(fused))
         ks, c = self.ksize, self.inter_channels
         t, _bo = same_pad_amounts(H, ks, self.stride_1)
         l, _r = same_pad_amounts(W, ks, self.stride_1)
@@ -723,23 +734,35 @@ class CE(nn.Module):
             x = _pad_channels4(x.contiguous())
             convs = [SimpleNamespace(weight=_pad_channels4(p[n + ".weight"]), bias=p[n + ".bias"])
                      for n in ("g", "theta") + (("thr_conv", "bias_conv") if margin else ())]
-            maps = T.prologue_convs(x, *convs, fast=False)                                      # dagl.py:208-215, fp32
+            maps = T.prologue_convs(x, *convs, fast=fast)                                       # dagl.py:208-215
             b1p, b2p = maps[0], maps[1]
             wq_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], c, ks), p["fc1.0.bias"], ks, self.stride_1,
-                                     T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=False)   # [B,L,196]
+                                     T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=fast)    # [B,L,196]
             x_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], c, ks), p["fc2.0.bias"], ks, self.stride_2,
-                                    0, 0, H, W, relu=True, allow_fast=False)                      # [B,N,196]
+                                    0, 0, H, W, relu=True, allow_fast=fast)                       # [B,N,196]
             tau = None
             if margin:
                 # mean_j S_ij = <wq_i, mean_j x_j>: linear in the key features, autograd carries the heads and the mean (dagl.py:256-258)
                 mean_s = torch.bmm(wq_rows, x_rows.mean(dim=1).unsqueeze(2)).squeeze(2)
                 tau = mean_s * maps[2].reshape(B, -1) - maps[3].reshape(B, -1)
+            # the split-fp16 kernels NaN-fill ALL they hand out once an operand leaves their range; the margin would turn such rows
+            # into "no edge passes" and zeros: one element of each feature matrix carries the verdict into every result instead
+            # (t + 0 * wq[0] * x[0], one launch per result)
+            poisoned = (lambda t: torch.addcmul(t, wq_rows.detach().reshape(-1)[:1], x_rows.detach().reshape(-1)[:1], value=0.0)) if fast \
+                else (lambda t: t)
+            if fused:
+                out = ops.graph_forward(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
+                                        tau.contiguous() if tau is not None else None, scale=float(self.softmax_scale),
+                                        normalize=normalize, workspace=self._ws_apply)
+                return None, None, poisoned(out)
             weight, score = _GraphAttend.apply(wq_rows, x_rows, tau, graph, float(self.softmax_scale), normalize,
                                                self._ws_attend, self._ws_attend_bwd)
             out = _GraphApply.apply(b2p, weight, graph, self._ws_apply, self._ws_apply_bwd) if apply else None
+            weight, score = poisoned(weight), poisoned(score)
+            out = poisoned(out) if apply else None
         return weight, score, out
 
-    def attend_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference"):
+    def attend_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference", features: str = "fp32"):
         """This block's own weights for ``b`` on the STRUCTURE of a given ``PatchGraph``: the same offsets and keys with new ``weight`` and
         ``score`` -- S on the edges, the margin, the reference's softmax restricted to the graph (``ops.graph_attend``,
         csrc/graph_attend.hip).  The structure may be ``graph(b)`` of another input or frame, of another module, edited or hand-built.
@@ -750,21 +773,34 @@ class CE(nn.Module):
         structure ``graph(b)`` exports this returns the export's weights; ``"edges"``: a plain softmax over each row's edges.  A row's
         degree counts edges: a repeated key is an entry of its own.  ``score`` is the unscaled S.
 
-        Features come from the fp32 route, as in ``graph``: any ``in_channels``, half / bf16 modules on their fp32 copies under
-        ``torch.no_grad()``.  With autograd enabled and ``b`` or a parameter of g, fc1, fc2, thr_conv, bias_conv requiring grad, the
+        ``features="fp32"``: features come from the fp32 route, as in ``graph``: any ``in_channels``, half / bf16 modules on their fp32
+        copies under ``torch.no_grad()``.  ``features="split16"``: the prologue and the two patch projections run as the training path
+        runs them when ``scan != "exact"`` (the split-fp16 kernels, forward and -- under autograd -- backward; where those do not serve
+        a shape or an input width the calls fall back to fp32 by themselves).  Their range contract is the training path's: an operand
+        outside the split-fp16 range (|b1| < 4094, |w_fc| < 64) NaN-fills the result, numbers are never wrong.  Because this call leaves
+        the module's state alone there is no automatic move to ``scan="exact"`` and no redo: on a NaN result call again with
+        ``features="fp32"``.  With autograd enabled and ``b`` or a parameter of g, fc1, fc2, thr_conv, bias_conv requiring grad, the
         returned ``weight`` carries the autograd graph (fp32 parameters only); the structure is a constant.  The refusals are
         ``apply_graph``'s, raised before any launch; after ``graph.validate()`` there is no host synchronisation.  The module's state
         (packed weights, top-k policy, range verdicts, ``_train_dense``) is untouched."""
-        weight, score, _ = self._attend_on_graph(b, graph, "attend_graph", margin, normalize, False)
+        weight, score, _ = self._attend_on_graph(b, graph, "attend_graph", margin, normalize, False, features)
         g = graph.with_weight(weight)
         g.score = score
         return g
 
-    def forward_on_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference") -> torch.Tensor:
+    def forward_on_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference", features: str = "fp32",
+                         fused=None) -> torch.Tensor:
         """The block's output for ``b`` with its weights recomputed on the structure of ``graph``: ``apply_graph(b, attend_graph(b, graph))``
         from one prologue call -- differentiable in ``b`` and every parameter of g, theta, fc1, fc2 and (with the margin) thr_conv,
-        bias_conv; selection over the L*N pairs is skipped.  Arguments, refusals and state as ``attend_graph``."""
-        out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True)[2]
+        bias_conv; selection over the L*N pairs is skipped.  Arguments (``features`` and its range contract included), refusals and state
+        as ``attend_graph``.
+
+        ``fused``: True = ``ops.graph_forward`` (csrc/graph_forward.hip: scores, softmax and aggregation in one crossing of the edges, no
+        ``weight`` / ``score`` arrays) -- refused before any launch when a gradient is wanted, it has no backward; False = the two
+        differentiable ops; None = the fused kernel whenever no gradient is wanted on the ``features="split16"`` route, the two ops
+        otherwise -- so a call with default arguments returns the bits it always did.  The fused result differs from the two-op one
+        by fp32 roundings only.  ``graph.weight`` / ``graph.score`` are left alone either way."""
+        out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True, features, fused)[2]
         return out if b.dtype == torch.float32 else out.to(b.dtype)
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:

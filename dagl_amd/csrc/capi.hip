@@ -1976,4 +1976,23 @@ int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* w
                                         d_tau, workspace);
 }
 
+// the fused forward on a given patch graph: csrc/graph_forward.hip (no ABI bump: found by symbol)
+size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    if (graph_apply_shape_ok("dagl_graph_forward_workspace_bytes", B, H, W, total_edges)) return 0;
+    return graph_forward_workspace_bytes(B, make_grid(H, W), total_edges);
+}
+
+int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                       const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags,
+                       float* out, void* workspace, size_t ws_bytes) {
+    int rc = graph_attend_operands_ok("dagl_graph_forward", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
+    if (rc) return rc;
+    DAGL_REQUIRE(b2p && out, "dagl_graph_forward: null tensor pointer");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_forward: b2p must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace("dagl_graph_forward", workspace, ws_bytes, graph_forward_workspace_bytes(B, g, total_edges)))) return rc;
+    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
+    return launch_graph_forward((hipStream_t)stream, B, g, c, b2p, out, workspace);
+}
+
 }  // extern "C"

@@ -917,4 +917,8 @@ int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const Grap
                                  const float* d_weight, const int64_t* col_off, const int32_t* src_row, const int32_t* perm,
                                  float* d_wq_rows /* or null */, float* d_x_rows /* or null */, float* d_tau /* or null */, void* workspace);
 
+// both in one crossing of the edges (graph_forward.hip): out = graph_apply(weight = graph_attend(c)), score / weight never stored
+size_t graph_forward_workspace_bytes(int B, const Grid& g, int64_t E);
+int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace);
+
 }  // namespace dagl

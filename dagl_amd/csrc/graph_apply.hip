@@ -25,29 +25,6 @@ namespace dagl {
 int launch_fold_patches(hipStream_t s, int B, int Hp, int Wp, int C, int k, int stride, int oy, int ox, int oh, int ow, const float* drows,
                         float* dmap);
 
-constexpr int GA_BATCH = 8;                   // gathers in flight per thread
-constexpr int GA_C4 = P / 4;                  // 196 float4 per patch row
-
-struct GaArgs {
-    const int64_t* row_off; int n_rows;       // CSR (or transposed CSR) offsets [n_rows + 1]
-    const int32_t* key; const float* weight; const int32_t* perm /* NULL: weight[e] */;
-    long long E;
-    const float* src; int n_src;              // MAP: the padded map, n_src = N;  !MAP: [n_src, 784]
-    int L, W, Wp; long long img4;             // MAP: rows per image, map geometry, float4 per image
-    float* out;                               // [n_rows, 784]
-    float* part;                              // [chunks, 784]
-};
-
-// float4 offset of an edge's source row, -1 = the edge contributes nothing
-template <bool MAP>
-__device__ __forceinline__ long long ga_source(const GaArgs& a, int row, int key) {
-    if ((unsigned)key >= (unsigned)a.n_src) return -1;
-    if (!MAP) return (long long)key * GA_C4;
-    const int b = row / a.L;
-    const int jy = key / a.W, jx = key - jy * a.W;
-    return (long long)b * a.img4 + ((long long)jy * a.Wp + jx) * (CH / 4);
-}
-
 template <bool MAP>
 __global__ __launch_bounds__(256) void graph_apply_segment_kernel(GaArgs a) {
     __shared__ long long sh_of[GA_SEG];

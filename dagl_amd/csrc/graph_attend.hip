@@ -25,33 +25,7 @@
 
 namespace dagl {
 
-constexpr int GT_C4 = D / 4;                  // 49 float4 per feature row
 constexpr int GT_BATCH = 8;                   // gathers in flight per thread of the products
-
-struct GtArgs {
-    const int64_t* row_off; int n_rows;       // CSR offsets [B L + 1]
-    const int32_t* key; long long E;
-    const float* wq; const float* x;          // [B L, 196], [B N, 196]
-    const float* tau;                         // [B L] or NULL (no margin)
-    int L, N; float scale; int edges_only;
-};
-
-// logit of a score; m = the margin (1 without tau): the edge is "on" iff m != 0.  The products are rounded one by one (no contraction
-// into the caller's z - M): every kernel must see the bits the row maximum was taken from, or the heaviest edge of a one-hot row weighs
-// e^(rounding residue) instead of 1 and the backward's g_e - c_r no longer cancels
-__device__ __forceinline__ float gt_logit(const GtArgs& a, int row, float s, float& m) {
-#pragma clang fp contract(off)
-    m = 1.f;
-    if (a.tau != nullptr) {
-        const float d = s - a.tau[row];
-        m = d > 0.f ? d : 0.f;
-    }
-    return a.scale * s * m;
-}
-
-__device__ __forceinline__ float gt_dot4(const float4 p, const float4 q) { return p.x * q.x + p.y * q.y + p.z * q.z + p.w * q.w; }
-
-__device__ __forceinline__ long long gt_clamp(long long v, long long E) { return v < 0 ? 0 : (v > E ? E : v); }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void graph_attend_score_kernel(GtArgs a, float* __restrict__ score, int32_t* __restrict__ row_of,
@@ -71,25 +45,14 @@ __global__ __launch_bounds__(256) void graph_attend_score_kernel(GtArgs a, float
         row_of[p0 + t] = row;
     }
     __syncthreads();
-    // an edge per 16 lanes: lane l reads float4 l, l + 16, l + 32 and (lane 0) 48 of both rows
+    // an edge per 16 lanes (gt_edge_dot)
     const int l = t & 15, grp = t >> 4;
-    const bool tail = l + 48 < GT_C4;
-    const int c3 = tail ? l + 48 : GT_C4 - 1;
     const float4* wq = reinterpret_cast<const float4*>(a.wq);
     const float4* xk = reinterpret_cast<const float4*>(a.x);
     for (int e = grp; e < m; e += 16) {
         const long long of = sh_x[e];
         const int row = sh_row[e];
-        const float4* q = wq + (size_t)row * GT_C4;
-        const float4* k = xk + (of >= 0 ? of : 0);
-        const float4 q0 = q[l], q1 = q[l + 16], q2 = q[l + 32], q3 = q[c3];
-        const float4 k0 = k[l], k1 = k[l + 16], k2 = k[l + 32], k3 = k[c3];
-        float acc = gt_dot4(q0, k0);
-        acc += gt_dot4(q1, k1);
-        acc += gt_dot4(q2, k2);
-        acc += tail ? gt_dot4(q3, k3) : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 16);
+        const float acc = gt_edge_dot(wq + (size_t)row * GT_C4, xk + (of >= 0 ? of : 0), l);
         if (l == 0) {
             const float s = of >= 0 ? acc : 0.f;
             float mg;

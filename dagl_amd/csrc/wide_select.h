@@ -13,7 +13,7 @@ namespace dagl {
 // reference's expression order, the products rounded one by one (__fmul_rn: no contraction into an FMA, whatever surrounds the call)
 // -- this is what ties every route to the reference bit for bit.  The fixed-k variant's mask is 0/1, so m = 1 on a kept key:
 // l = S scale (GReccR2b_3mh_1-checkpoint.py:242-250).  mtq = mean thr and bsq = bias of the query.
-// Separate by design: gt_logit (graph_attend.hip) forms scale S m with m = relu(S - tau), a rounding order its backward depends on;
+// Separate by design: gt_logit (graph_rows.h) forms scale S m with m = relu(S - tau), a rounding order its backward depends on;
 // graph_logit (graph.hip) forms the products in fp64; dense_attend_kernel (dense.hip) has the same expression packed two keys wide (dnf2) in its
 // fenced block at the register cap.
 // ------------------------------------------------------------------------------------------------------

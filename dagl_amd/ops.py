@@ -539,6 +539,32 @@ def graph_attend(wq_rows, x_rows, row_off, key, tau=None, scale: float = 10.0, n
 
 
 @_on_device
+def graph_forward(wq_rows, x_rows, b2p, row_off, key, tau=None, scale: float = 10.0, normalize: str = "reference",
+                  workspace: "Workspace | None" = None) -> torch.Tensor:
+    """``graph_apply(b2p, row_off, key, graph_attend(...)[0])`` in one crossing of the edges (``dagl_graph_forward``,
+    csrc/graph_forward.hip) -> [B,16,H,W]: the operands and the semantics of the two calls, ``score`` and ``weight`` never stored.  The
+    result differs from the two-call one by fp32 roundings (weights are applied as e^(z - max) and scaled per row afterwards); the same
+    arrays give the same bits on every call.  Nothing is read on the host."""
+    lib = _lib.load()
+    _need(b2p, "b2p")
+    if b2p.dim() != 4 or b2p.shape[3] != 16 or b2p.shape[1] < 7 or b2p.shape[2] < 7:
+        raise DaglError(f"graph_forward: b2p must be the zero-bordered NHWC value map [B,H+6,W+6,16], got {tuple(b2p.shape)}")
+    hw = (b2p.shape[1] - 6, b2p.shape[2] - 6)
+    B, H, W, E, flags = _graph_attend_operands("graph_forward", wq_rows, x_rows, row_off, key, tau, normalize, hw)
+    if b2p.shape[0] != B:
+        raise DaglError(f"graph_forward: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    need = lib.dagl_graph_forward_workspace_bytes(B, H, W, E)
+    if need == 0:
+        check(-1, "dagl_graph_forward_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+    out = torch.empty(B, 16, H, W, device=wq_rows.device, dtype=torch.float32)
+    check(lib.dagl_graph_forward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
+                                 _ptr(key, E > 0), E, _ptr(tau), float(scale), flags, out.data_ptr(), a, nbytes), "dagl_graph_forward")
+    del buf
+    return out
+
+
+@_on_device
 def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,
                           workspace: "Workspace | None" = None, hw=None):

@@ -170,7 +170,8 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  A caller compares
+ * workspace sizes unchanged).  dagl_graph_forward* came in without a bump -- no declared signature or struct changed --: a caller that
+ * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
 int         dagl_version(void);                 /* DAGL_ABI_VERSION of the library = 10000*major + 100*minor + patch */
@@ -365,6 +366,26 @@ int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* w
                                const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
                                const int32_t* perm, float* d_wq_rows /* may be NULL */, float* d_x_rows /* may be NULL */,
                                float* d_tau /* may be NULL */, void* workspace, size_t ws_bytes);
+
+/* ---- the forward on a GIVEN patch graph in one crossing of the edges: csrc/graph_forward.hip (ABI 412, detected by symbol) ----------
+ * out = dagl_graph_apply(weight = dagl_graph_attend(...)) without materialising `score` or `weight`: the operands and the semantics are
+ * exactly those written above for the two entries -- S_e, with tau the margin m_e, z_e, on_e; flags = 0 the reference's normalisation
+ * (every key off the graph counts as e^0), DAGL_GRAPH_ATTEND_EDGES_ONLY the edges-only softmax; a repeated key is an entry of its own;
+ * a key outside [0, N) is tested before an address is formed, scores 0, takes part in D and contributes no value row; empty rows give
+ * zero aggregated rows; fold and overlap count are dagl_graph_apply's.
+ *   wq_rows [B,L,196], x_rows [B,N,196] fp32 (16-byte aligned), b2p [B,H+6,W+6,16] the zero-bordered value map (16-byte aligned),
+ *   row_off [B L + 1] int64, key [E] int32 (may be NULL when total_edges = 0: the output is all zeros), tau [B L] or NULL, out [B,16,H,W]
+ * One launch per segment of dagl_graph_apply_segment() edges forms the scores and, per run of edges that share a row, the fp32 maximum,
+ * the fp64 sum of e^(z - max) and the 784-float partial row sum on_e e^(z - max) V[key_e]; a launch per row brings those onto the row's
+ * maximum in segment order, adds the (N - deg) e^(-M) term and divides; the fold follows: three launches for the six of the two calls.
+ * No float atomics, fixed summation order: the same arrays give the same bits on every call (they differ from the two-call result by
+ * fp32 roundings: the weights are applied as e^(z - max) and scaled afterwards).  Grids come from total_edges and B L: nothing is read
+ * on the host, the call can be captured.  Workspace: dagl_graph_forward_workspace_bytes = [B L, 784] aggregated rows + per segment one
+ * 784-float partial row and a (max, sum) slot + a slot per row.  Every argument is checked before the first launch. */
+size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edges);
+int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                       const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau /* NULL: no margin */, float scale,
+                       int flags /* bit 0: edges-only normalisation */, float* out, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

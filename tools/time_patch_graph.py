@@ -106,8 +106,8 @@ def _table_cases():
 
 
 def attend_leg(H, W):
-    """forward / attend_graph / forward_on_graph / forward_on_graph forward + backward on the three graphs of ``apply_leg``, the two ops
-    calls alone (features given), and the module's own training path (``_forward_train`` forward, forward + backward) to compare with."""
+    """forward / attend_graph / forward_on_graph (fp32 features; split-fp16 features with the two ops and fused; fp32 features fused) /
+    forward_on_graph forward + backward on the three graphs of ``apply_leg``, the ops calls alone (features given), and the module's own training path (``_forward_train`` forward, forward + backward) to compare with."""
     from dagl_amd import ops
     from dagl_amd.ce import CE
     from dagl_amd.synth import make_ce_params, make_features
@@ -129,6 +129,9 @@ def attend_leg(H, W):
             fwd = _events(lambda: ce(x))
             att = _events(lambda: ce.attend_graph(x, g))
             fog = _events(lambda: ce.forward_on_graph(x, g))
+            f16 = _events(lambda: ce.forward_on_graph(x, g, features="split16", fused=False))
+            f16f = _events(lambda: ce.forward_on_graph(x, g, features="split16"))
+            f32f = _events(lambda: ce.forward_on_graph(x, g, fused=True))
             # the two ops calls alone, on the module's own features
             from dagl_amd import train_ops as T
             p = ce._params_f32(scaled=False)
@@ -146,6 +149,11 @@ def attend_leg(H, W):
             call = dict(tau=tau, scale=float(ce.softmax_scale), hw=(H, W))
             k_f = _events(lambda: ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws, **call))
             weight, score = ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws, **call)
+            b2p = ops.ce_prologue(x, p["g.weight"], p["g.bias"], p["theta.weight"], p["theta.bias"])[1]
+            wsa, wsf = ops.Workspace(), ops.Workspace()
+            k_a = _events(lambda: ops.graph_apply(b2p, g.row_off, g.key, weight, workspace=wsa))
+            fcall = dict(tau=tau, scale=float(ce.softmax_scale))
+            k_ff = _events(lambda: ops.graph_forward(wq, xk, b2p, g.row_off, g.key, workspace=wsf, **fcall))
             d_w = torch.randn_like(weight)
             k_b = _events(lambda: ops.graph_attend_backward(d_w, wq, xk, g.row_off, g.key, score, weight, transposed=g.transpose(),
                                                             workspace=wsb, **call))
@@ -168,7 +176,9 @@ def attend_leg(H, W):
         ce.eval()
         print(f"[1,64,{H},{W}] {name}: {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {int(g.degrees().max())}\n"
               f"    forward {fmt(fwd)}; attend_graph {fmt(att)}; forward_on_graph {fmt(fog)}; forward_on_graph forward + backward {fmt(fb)}\n"
-              f"    ops.graph_attend alone {fmt(k_f)}; ops.graph_attend_backward alone {fmt(k_b)}\n"
+              f"    forward_on_graph split16, two ops {fmt(f16)}; split16 fused {fmt(f16f)}; fp32 features fused {fmt(f32f)}\n"
+              f"    ops.graph_attend alone {fmt(k_f)}; ops.graph_apply alone {fmt(k_a)}; ops.graph_forward alone {fmt(k_ff)}; "
+              f"ops.graph_attend_backward alone {fmt(k_b)}\n"
               f"    the module's own training path (_forward_train, its own selection): forward {fmt(trf)}; forward + backward {fmt(trb)}",
               flush=True)
 
