@@ -64,6 +64,7 @@ SIGNATURES = {
     "dagl_ce_forward_debug": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz,
                                    C.POINTER(CeInfo), _vp, _vp, _vp]),
     "dagl_ce_pivot_debug": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "dagl_ce_wide_debug": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "dagl_ce_graph_workspace_bytes": (_sz, [_i] * 6),
     "dagl_ce_graph_count": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_i, _i, _i, _vp, _vp, _sz, C.POINTER(CeInfo)]),
     "dagl_ce_graph_fill": (_i, [_vp] + [_i] * 6 + [_vp] * 4 + [C.c_int64, C.c_int64, _vp, _sz]),

@@ -1220,6 +1220,22 @@ int dagl_ce_pivot_debug(void* stream, int B, int H, int W, int mode, int k, void
     return DAGL_OK;
 }
 
+int dagl_ce_wide_debug(void* stream, int B, int H, int W, int mode, int k, void* workspace, size_t ws_bytes, int32_t* served_out) {
+    Plan p;
+    int rc = make_plan(B, H, W, mode, k, p);
+    if (rc) return rc;
+    const int32_t* served = nullptr; int rows = 0;
+    if (!p.wide || topk_wide_served(p.k, p.g.N, p.g.L, nullptr, &served, &rows)) {
+        set_error("dagl_ce_wide_debug: calls of this mode / k run no list kernel (not the wide path, or k > 1024)");
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    DAGL_REQUIRE(served_out, "dagl_ce_wide_debug: null output pointer");
+    if ((rc = check_workspace("dagl_ce_wide_debug", workspace, ws_bytes, p.o_end))) return rc;
+    (void)topk_wide_served(p.k, p.g.N, p.g.L, at<char>(workspace, p.o_wide), &served, &rows);
+    DAGL_HIP_TRY(hipMemcpyAsync(served_out, served, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return DAGL_OK;
+}
+
 int dagl_profile_create(int max_calls, dagl_profile** out) {
     DAGL_REQUIRE(max_calls >= 1 && max_calls <= 4096 && out, "dagl_profile_create: bad argument");
     Profile* p = new Profile();

@@ -694,6 +694,7 @@ struct WideArgs {
                                                                // with logits beyond WL_RESCORE_LOGIT), or null
 };
 size_t topk_wide_workspace_bytes(int N, int L);
+int topk_wide_served(int k, int N, int L, void* ws, const int32_t** served, int* rows);   // the last row batch's `served` words (test read-out)
 int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const float* wq /* [B, rows, DS] */, const float* x,
                      const float* mt, const float* bs, const float* b2p, void* ws, float* agg, int32_t* deg, float* rowsum,
                      RangeTag range = RangeTag());

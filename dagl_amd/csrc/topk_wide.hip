@@ -444,6 +444,15 @@ static WideWs wide_carve(void* ws, int N, int L, WideArgs& a) {
     return w;
 }
 size_t topk_wide_workspace_bytes(int N, int L) { WideArgs a; return wide_carve(nullptr, N, L, a).bytes; }
+// test read-out (dagl_ce_wide_debug): the `served` words of the last row batch of a call with k <= WL_KMAX, from the same carve
+int topk_wide_served(int k, int N, int L, void* ws, const int32_t** served, int* rows) {
+    if (k > WL_KMAX) return DAGL_ERR_UNSUPPORTED;                 // (no list launch: the words are stale)
+    WideArgs a;
+    *served = wide_carve(ws, N, L, a).served;
+    const int Rmax = topk_wide_rows(N, L);
+    *rows = L - (L - 1) / Rmax * Rmax;
+    return DAGL_OK;
+}
 
 int launch_topk_wide(hipStream_t s, int B, const Grid& g, int mode, int k, const float* wq, const float* x, const float* mt,
                      const float* bs, const float* b2p, void* ws, float* agg, int32_t* deg, float* rowsum, RangeTag range) {

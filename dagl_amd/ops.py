@@ -826,6 +826,25 @@ def ce_pivot_debug(shape, mode: str, k: int, workspace: "Workspace", device, sam
     return idx, rowsum
 
 
+def ce_wide_debug(shape, mode: str, k: int, workspace: "Workspace", device, exact_scan: bool = False):
+    """Test read-out (``dagl_ce_wide_debug``): which query rows of the last row batch (L <= 2048: every row of the last image) the
+    last wide top-k call on ``workspace`` (input shape ``shape``, same mode / k / ``exact_scan``) served from the one-block list kernel
+    -> served [rows] int32, 1 = served, 0 = declined and left to the three-kernel form.  Raises ``DaglError`` (code ERR_UNSUPPORTED)
+    for calls that run no list kernel (min(k, N) <= 64 or > 1024, the adaptive mode)."""
+    lib = _lib.load()
+    buf = workspace.peek(device)
+    if buf is None:
+        raise DaglError("ce_wide_debug: the workspace has served no call on this device")
+    B, _, H, W = shape
+    a, nbytes = _aligned(buf)
+    Lh, Lw = query_grid(H, W)
+    served = torch.full((Lh * Lw,), -1, device=device, dtype=torch.int32)       # (a batch holds at most L rows: the tail stays -1)
+    flags = MODES[mode] | (_lib.FLAG_EXACT_SCAN if exact_scan else 0)
+    with torch.cuda.device(device):
+        check(lib.dagl_ce_wide_debug(_stream(), B, H, W, flags, int(k), a, nbytes, served.data_ptr()), "dagl_ce_wide_debug")
+    return served[served >= 0]
+
+
 @_on_device
 def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: int = 0,
                       workspace: "Workspace | None" = None, profile: "StageProfile | None" = None,

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward* came in without a bump -- no declared signature or struct changed --: a caller that
+ * workspace sizes unchanged).  dagl_graph_forward* and dagl_ce_wide_debug came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -267,6 +267,15 @@ int dagl_ce_forward_debug(void* stream, int B, int H, int W,
  * DAGL_ERR_UNSUPPORTED: calls of this shape / mode / k keep the tile sampling (nothing was written).                              */
 int dagl_ce_pivot_debug(void* stream, int B, int H, int W, int mode, int k, void* workspace, size_t ws_bytes,
                         int32_t* pivot_idx_out, float* key_rowsum_out);
+
+/* Read-out for tests of the wide top-k path (csrc/topk_wide.hip; found by symbol, no ABI bump): top-k modes with 64 < min(k, N)
+ * <= 1024 hand every query row to a one-block list kernel, which declines the rows whose sample misleads it (too many candidates for
+ * a wave's segment, or fewer than k in all); declined rows go through the three-kernel form behind it, as every row does when
+ * min(k, N) > 1024.  What the LAST such call on `workspace` (same B, H, W, mode, k) left there for its LAST batch of query rows -- with
+ * L <= 2048 that is every row of the last image --, copied to device memory:
+ *   served_out [min(L, rows per batch)] int32   1 = the list kernel served the row, 0 = it declined it
+ * DAGL_ERR_UNSUPPORTED: calls of this mode / k are not on the wide path, or run no list kernel (nothing was written).           */
+int dagl_ce_wide_debug(void* stream, int B, int H, int W, int mode, int k, void* workspace, size_t ws_bytes, int32_t* served_out);
 
 /* ---- (ABI 408) the learned patch graph as CSR: csrc/graph.hip --------------------------------------------------------------------
  * For every image and query patch i the keys j with mask_b[i,j] != 0 and their weights A[i,j] = softmax(10 S m)[i,j] mask_b[i,j]

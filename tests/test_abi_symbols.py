@@ -23,7 +23,7 @@ def lib_path():
 def test_header_declares_the_path():
     syms = _declared_symbols()
     for must in ("dagl_ce_forward", "dagl_ce_workspace_bytes", "dagl_gather_aggregate", "dagl_last_error",
-                 "dagl_project_patches", "dagl_fold_normalize"):
+                 "dagl_project_patches", "dagl_fold_normalize", "dagl_ce_pivot_debug", "dagl_ce_wide_debug"):
         assert must in syms
 
 
@@ -131,6 +131,24 @@ def test_host_side_forward_rejections(lib_path, entry):
     short = [r for r in rows if r[0][0] == "one byte short"]
     full = [r for r in rows if r[0][0] == "no workspace"]
     assert [r[3][0] for r in short] == [r[3][0] for r in full]       # one byte short of the size it asked for: the same answer
+
+
+def test_wide_debug_rejections(lib_path):
+    """dagl_ce_wide_debug refuses, before anything reaches the device, the calls that run no list kernel -- the adaptive mode, k up to
+    the list width, min(k, N) > 1024 -- and checks its pointer and workspace like the forward entry points."""
+    from dagl_amd import _lib
+    lib = _lib.load()
+    call = lambda mode, k, ws=_WS, ws_bytes=1 << 40, out=_FAKE, H=64, W=64: lib.dagl_ce_wide_debug(None, 1, H, W, mode, k, ws, ws_bytes, out)
+    for mode, k in ((0, 0), (1, 8), (1, 64), (2, 64), (1, 1025), (2, 4096), (1, 1 << 20)):
+        assert call(mode, k) == _lib.ERR_UNSUPPORTED, (mode, k)
+        assert b"dagl_ce_wide_debug" in lib.dagl_last_error()
+    assert call(1, 5000, H=40, W=44) == _lib.ERR_UNSUPPORTED            # min(k, N) = 1760 > 1024
+    assert call(1, 100, out=None) == -1 and b"null" in lib.dagl_last_error()
+    assert call(1, 100, ws=_WS + 8) == -1 and b"aligned" in lib.dagl_last_error()
+    for mode, k in ((1, 100), (2, 1024)):
+        need = lib.dagl_ce_workspace_bytes(1, 64, 64, mode, k)
+        assert need > 0 and call(mode, k, ws_bytes=need - 1) == _lib.ERR_WORKSPACE and b"workspace" in lib.dagl_last_error()
+        assert call(mode, k, ws_bytes=0) == _lib.ERR_WORKSPACE
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
