@@ -239,6 +239,9 @@ class CE(nn.Module):
         self._ws_apply_bwd = ops.Workspace()
         self._ws_attend = ops.Workspace()     # attend_graph() / forward_on_graph(): the row statistics; the backward's sums and partial rows
         self._ws_attend_bwd = ops.Workspace()
+        self._ws_lists = ops.Workspace()      # forward_with_graph(): the list-form core's forward and backward, the degrees of the CSR conversion
+        self._ws_lists_bwd = ops.Workspace()
+        self._ws_lists_csr = ops.Workspace()
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -802,6 +805,124 @@ class CE(nn.Module):
         by fp32 roundings only.  ``graph.weight`` / ``graph.score`` are left alone either way."""
         out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True, features, fused)[2]
         return out if b.dtype == torch.float32 else out.to(b.dtype)
+
+    def forward_with_graph(self, b: torch.Tensor, *, scores: bool = False, features=None):
+        """The block's output for ``b`` AND the patch graph that produced it, from one call -> ``(out, PatchGraph)``: the list-form route
+        of the differentiable forward (prologue, fc1 / fc2, the graph core over each query's neighbour list), whose lists
+        ``ops.graph_from_lists`` (csrc/graph_lists.hip) turns into the CSR of ``graph`` -- the very neighbours this call aggregated,
+        at about the cost of a forward instead of ``graph``'s all-fp32 scan of the L*N pairs.
+
+        ``features``: "split16" = the prologue and the projections on the split-fp16 kernels, the selection behind the bf16 screen (the
+        route of ``scan = "screened"``); "fp32" = all on the fp32 route (``scan = "exact"``), which differs from ``graph`` in summation
+        order only; None = "split16" unless ``self.scan == "exact"``.  The range contract of "split16" is ``attend_graph``'s: an operand
+        outside the split-fp16 range NaN-fills ``out``, ``weight`` and ``score`` (the structure still holds valid keys only), the module's
+        state is left alone, the caller repeats with ``features="fp32"``.
+
+        ``out`` is that route's output; with autograd enabled and ``b`` or a parameter requiring grad (fp32 parameters only) it
+        carries the autograd graph of the module's own differentiable forward -- same kernels, same bits.  The graph's arrays are
+        constants: ``weight = exp(l) / Z`` with the unlisted keys' e^0 in Z, i.e. ``A = softmax(softmax_scale S m) mask_b``; ``scores``:
+        also ``S``; ``mode`` / ``k`` the module's, keys valid (``apply_graph`` need not look again).
+
+        Scope: what the lists serve.  Refused before any launch: a non-default patch geometry, ``min(select_k, N) > 64`` (``graph`` is the
+        export for those), a stream under capture (the edge count is read on the host), and ``graph``'s refusals for dtype, shape and
+        device.  An adaptive mask that keeps more than 64 keys for some query is found by the core and raised as a ``DaglError`` with
+        ``code == ERR_UNSUPPORTED``: there is no silent move to ``graph``'s route, the caller decides.  The module's state (packed
+        weights, top-k policy, range verdicts, ``_train_dense``, ``last_info``) is untouched: the call has workspaces of its own."""
+        from types import SimpleNamespace
+        from . import train_ops as T
+        from .graph import PatchGraph
+        what = "forward_with_graph"
+        if b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.{what}: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
+        if not b.is_cuda:
+            raise DaglError(f"CE.{what}: input must be on the GPU; dagl_amd has no CPU path")
+        if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
+            raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
+        if self._generic:
+            raise DaglError(f"CE.{what}: the graph export serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
+                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
+                            f"{self.inter_channels}), which is out of its scope")
+        if torch.cuda.is_current_stream_capturing():
+            raise DaglError(f"CE.{what}: not available while the stream is being captured (the edge count is read on the host)")
+        B, _, H, W = b.shape
+        k_eff = 0
+        if self.select_mode != "adaptive":
+            if int(self.select_k) < 1:
+                raise DaglError(f"CE: select_k={self.select_k} < 1")
+            k_eff = min(int(self.select_k), H * W)
+            if k_eff > MAX_TOPK:
+                raise DaglError(f"CE.{what}: min(select_k, N) = {k_eff} neighbours per query, the neighbour lists hold {MAX_TOPK}; "
+                                "CE.graph is the export for wider neighbourhoods")
+        if features is None:
+            features = "fp32" if self.scan == "exact" else "split16"
+        if features not in ("fp32", "split16"):
+            raise DaglError(f"CE.{what}: features={features!r}, expected 'fp32' or 'split16'")
+        fast = features == "split16"
+        in_dtype = b.dtype
+        if in_dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise DaglError(f"CE.{what}: unsupported dtype {in_dtype}")
+        grad = torch.is_grad_enabled() and (b.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if grad:
+            if any(p.dtype != torch.float32 for p in self.parameters()):
+                raise DaglError(self._FP32_ONLY)
+            p = {n: t for n, t in self.named_parameters()}
+        else:
+            p = self._params_f32(scaled=False)
+        heads = self.select_mode != "topk"
+        ks, c = self.ksize, self.inter_channels
+        t, _bo = same_pad_amounts(H, ks, self.stride_1)
+        l, _r = same_pad_amounts(W, ks, self.stride_1)
+        Lh, Lw = -(-H // self.stride_1), -(-W // self.stride_1)
+        lists = {}
+        fwd, bwd = _lists_route(self.select_mode, k_eff, not fast, self._ws_lists, self._ws_lists_bwd)
+
+        def fwd_keeping_lists(*operands):
+            out, saved, info = fwd(*operands)
+            lists.update(zip(("nb_idx", "nb_wgt", "nb_s", "nb_cnt"), saved))
+            return out, saved, info
+
+        with torch.enable_grad() if grad else torch.no_grad():
+            # the calls of _forward_train's list-form route, one for one (dagl.py:208-272)
+            x = b.float() if in_dtype != torch.float32 else b
+            x = _pad_channels4(x.contiguous())
+            convs = [SimpleNamespace(weight=_pad_channels4(p[n + ".weight"]), bias=p[n + ".bias"])
+                     for n in ("g", "theta") + (("thr_conv", "bias_conv") if heads else ())]
+            maps = T.prologue_convs(x, *convs, fast=fast)
+            b1p, b2p = maps[0], maps[1]
+            thr, bias = (maps[2], maps[3]) if heads else (None, None)
+            b2 = b2p[:, T.PAD:T.PAD + H, T.PAD:T.PAD + W, :].permute(0, 3, 1, 2)
+            wq_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], c, ks), p["fc1.0.bias"], ks, self.stride_1,
+                                     T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=fast)    # [B,L,196]
+            x_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], c, ks), p["fc2.0.bias"], ks, self.stride_2,
+                                    0, 0, H, W, relu=True, allow_fast=fast)                       # [B,N,196]
+            sc = self._scale_c()
+            if sc != 1.0:                   # softmax_scale != 10: see _scale_c
+                wq_rows = wq_rows * sc
+                if bias is not None:
+                    bias = bias * sc
+            try:
+                out = _GraphCore.apply(wq_rows, x_rows, b2, thr, bias, (fwd_keeping_lists, bwd), {})
+            except DaglError as e:
+                if self.select_mode != "adaptive" or e.code != ERR_UNSUPPORTED:
+                    raise
+                err = DaglError(f"CE.{what}: an adaptive mask keeps more than {FAST_CAP} keys for some query, more than a neighbour "
+                                f"list holds; CE.graph is the export for such neighbourhoods ({e})")
+                err.code = ERR_UNSUPPORTED
+                raise err from None
+            # (as in _attend_on_graph: the split-fp16 kernels NaN-fill the features once an operand leaves their range; one element
+            # of each feature matrix carries that verdict into every result)
+            poisoned = (lambda v: torch.addcmul(v, wq_rows.detach().reshape(-1)[:1], x_rows.detach().reshape(-1)[:1], value=0.0)) if fast \
+                else (lambda v: v)
+            out = poisoned(out)
+            with torch.no_grad():
+                csr = ops.graph_from_lists(lists["nb_idx"], lists["nb_wgt"], lists["nb_s"] if scores else None, lists["nb_cnt"],
+                                           (H, W), workspace=self._ws_lists_csr)
+                weight, score = poisoned(csr["weight"]), csr["score"]
+                if score is not None:
+                    score = poisoned(score / sc if sc != 1.0 else score)     # (the query features carry the factor of _scale_c)
+        g = PatchGraph(csr["row_off"], csr["key"], weight, score, B, H, W, self.select_mode, k_eff)
+        g._valid = True                              # (graph_from_lists drops every key outside [0, N))
+        return (out if in_dtype == torch.float32 else out.to(in_dtype)), g
 
     def _forward_infer_generic(self, b: torch.Tensor, k_eff: int) -> torch.Tensor:
         """A module built with non-default ``ksize / stride_1 / stride_2 / inter_channels`` (dagl.py:175-176): the whole method through

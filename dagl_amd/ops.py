@@ -565,6 +565,47 @@ def graph_forward(wq_rows, x_rows, b2p, row_off, key, tau=None, scale: float = 1
 
 
 @_on_device
+def graph_from_lists(nb_idx, nb_wgt, nb_s, nb_cnt, hw, workspace: "Workspace | None" = None) -> dict:
+    """The CSR patch graph of a list-form core forward's neighbour lists (``dagl_graph_from_lists``, csrc/graph_lists.hip): nb_idx /
+    nb_wgt / nb_s [B,L,width] (``nb_s`` may be None) and nb_cnt [B,L] as ``ce_core_forward`` saves them, ``hw`` the map (H, W) ->
+    dict(row_off [B*L+1] int64, key [E] int32, weight [E] fp32, score [E] fp32 | None), keys ascending inside a row.  Row r owns its
+    first min(max(nb_cnt[r], 0), width) slots; a slot whose key is outside [0, H*W) is dropped; equal keys keep their slot order.  The
+    arrays are allocated at capacity B*L*width and returned as views of their first E entries: E is read on the host (the one
+    synchronisation; not under stream capture)."""
+    lib = _lib.load()
+    _need(nb_idx, "nb_idx", torch.int32); _need(nb_wgt, "nb_wgt"); _need(nb_cnt, "nb_cnt", torch.int32)
+    if nb_s is not None:
+        _need(nb_s, "nb_s")
+    if nb_idx.dim() != 3 or nb_cnt.dim() != 2 or tuple(nb_cnt.shape) != tuple(nb_idx.shape[:2]):
+        raise DaglError(f"graph_from_lists: expected nb_idx [B,L,width] and nb_cnt [B,L], got {tuple(nb_idx.shape)} and {tuple(nb_cnt.shape)}")
+    for n, t in (("nb_wgt", nb_wgt), ("nb_s", nb_s)):
+        if t is not None and t.shape != nb_idx.shape:
+            raise DaglError(f"graph_from_lists: {n} is {tuple(t.shape)}, nb_idx {tuple(nb_idx.shape)}")
+    B, L, width = nb_idx.shape
+    H, W = (int(v) for v in hw)
+    Lh, Lw = query_grid(H, W) if H >= 1 and W >= 1 else (0, 0)
+    if B < 1 or Lh * Lw != L:
+        raise DaglError(f"graph_from_lists: a {H}x{W} map has {Lh * Lw} queries, the lists hold {L} rows of {B} images")
+    if torch.cuda.is_current_stream_capturing():
+        raise DaglError("graph_from_lists: not available under stream capture (the edge count is read on the host)")
+    need = lib.dagl_graph_from_lists_workspace_bytes(B, H, W)
+    if need == 0:
+        check(-1, "dagl_graph_from_lists_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, nb_idx.device)
+    cap = B * L * width
+    row_off = torch.empty(B * L + 1, device=nb_idx.device, dtype=torch.int64)
+    key = torch.empty(cap, device=nb_idx.device, dtype=torch.int32)
+    weight = torch.empty(cap, device=nb_idx.device, dtype=torch.float32)
+    score = torch.empty(cap, device=nb_idx.device, dtype=torch.float32) if nb_s is not None else None
+    check(lib.dagl_graph_from_lists(_stream(), B, H, W, width, nb_idx.data_ptr(), nb_wgt.data_ptr(), _ptr(nb_s), nb_cnt.data_ptr(),
+                                    row_off.data_ptr(), key.data_ptr(), weight.data_ptr(), _ptr(score), cap, a, nbytes),
+          "dagl_graph_from_lists")
+    del buf
+    total = int(row_off[-1])                          # the one synchronisation
+    return dict(row_off=row_off, key=key[:total], weight=weight[:total], score=score[:total] if score is not None else None)
+
+
+@_on_device
 def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,
                           workspace: "Workspace | None" = None, hw=None):

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward* and dagl_ce_wide_debug came in without a bump -- no declared signature or struct changed --: a caller that
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug and dagl_graph_from_lists* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -395,6 +395,27 @@ size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edg
 int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
                        const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau /* NULL: no margin */, float scale,
                        int flags /* bit 0: edges-only normalisation */, float* out, void* workspace, size_t ws_bytes);
+
+/* ---- the patch graph of a differentiable forward, from its own neighbour lists: csrc/graph_lists.hip (ABI 412, detected by symbol) ---
+ * dagl_ce_core_forward leaves each query's neighbours as fixed-width lists in selection order; nb_wgt = exp(l_t) / Z_l with the unlisted
+ * keys' e^0 in Z_l is exactly the export's A = softmax(10 S m) mask.  This call changes the container alone: lists -> the CSR of
+ * dagl_ce_graph_fill.  It is written for ARBITRARY lists, not only for what the selection produces:
+ *   nb_idx [B,L,width] int32, nb_wgt [B,L,width] fp32, nb_s [B,L,width] fp32 or NULL, nb_cnt [B,L] int32;  1 <= width <= 64
+ *   row r = b L + i owns the slots t < min(max(nb_cnt[r], 0), width); a slot whose key is outside [0, H W) is dropped (every key written
+ *   is valid, whatever a range-violating call left in the lists); the survivors are written in ascending key order, equal keys in slot
+ *   order (stable), weight and score following their key.
+ *   row_off_out [B L + 1] int64  exclusive scan of the surviving degrees, row_off_out[B L] = E
+ *   key_out / weight_out / score_out [capacity_edges]  entries [0, E) written, nothing at E and beyond; score_out NULL iff nb_s NULL
+ * capacity_edges < B L width is DAGL_ERR_WORKSPACE (E cannot exceed B L width, so the kernels carry no capacity test of their own);
+ * B L width >= 2^31 is DAGL_ERR_INVALID.  One call queues three launches -- a wavefront per row counts its valid slots (ballot), the
+ * exclusive scan, the same wavefront per row ranks and stores its slots -- with no host read and no atomics: the same lists give the
+ * same bits on every call, and the call can be captured (the CALLER reads row_off_out[B L] to learn E).  Workspace:
+ * dagl_graph_from_lists_workspace_bytes = the [B L] int32 degrees.  Every argument is checked before the first launch. */
+size_t dagl_graph_from_lists_workspace_bytes(int B, int H, int W);
+int dagl_graph_from_lists(void* stream, int B, int H, int W, int width, const int32_t* nb_idx, const float* nb_wgt,
+                          const float* nb_s /* may be NULL */, const int32_t* nb_cnt, int64_t* row_off_out /* [B L + 1] */,
+                          int32_t* key_out, float* weight_out, float* score_out /* NULL iff nb_s is NULL */, int64_t capacity_edges,
+                          void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

@@ -3,6 +3,7 @@
     python tools/time_patch_graph.py [H W]          # default 256 256: top-k 8 and the dense adaptive regime
     python tools/time_patch_graph.py --apply [H W]  # what ``CE.apply_graph`` costs: forward / graph / apply / apply + backward
     python tools/time_patch_graph.py --attend [H W] # what ``CE.attend_graph`` / ``forward_on_graph`` cost on the same three graphs
+    python tools/time_patch_graph.py --lists [H W]  # what ``CE.forward_with_graph`` costs next to forward + graph, same three graphs
 """
 import os
 import sys
@@ -183,7 +184,62 @@ def attend_leg(H, W):
               flush=True)
 
 
+def lists_leg(H, W):
+    """forward / graph / forward_with_graph (split-fp16 and fp32 features) / ops.graph_from_lists alone (the lists given) /
+    forward_with_graph followed by forward_on_graph(features="split16") on its result, on the three graphs of ``apply_leg``.  The
+    call serves what the neighbour lists hold (64 keys per query): a graph beyond that is refused, and the line says so."""
+    from dagl_amd import DaglError, ops
+    from dagl_amd import train_ops as T
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    for name, mode, k, variant, tail in _table_cases():
+        prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=1.65).items()}
+        ce = CE(in_channels=64)
+        ce.load_state_dict(prm, strict=True)
+        ce.select_mode, ce.select_k = mode, max(k, 1)
+        ce = ce.to(dev).eval()
+        with torch.no_grad():
+            g = ce.graph(x)
+            head = f"[1,64,{H},{W}] {name}: {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {int(g.degrees().max())}"
+            if tail:
+                print(f"{head} before the edit\n    refused: rows of degree N are written by hand, no forward produces them and no neighbour "
+                      "list holds them; forward_with_graph on this module returns the top-k 8 graph of the first table", flush=True)
+                continue
+            try:
+                ce.forward_with_graph(x)
+            except DaglError as e:
+                print(f"{head}\n    refused (code {e.code}): {e}", flush=True)
+                continue
+            fwd = _events(lambda: ce(x))
+            exp = _events(lambda: ce.graph(x), warmup=1, repeats=3, inner=2)
+            w16 = _events(lambda: ce.forward_with_graph(x, features="split16"))
+            w32 = _events(lambda: ce.forward_with_graph(x, features="fp32"))
+            chain = _events(lambda: ce.forward_on_graph(x, ce.forward_with_graph(x, features="split16")[1], features="split16"))
+            # the conversion alone, on the lists of a core call on the module's own fp32 features
+            p = ce._params_f32(scaled=False)
+            heads = mode != "topk"
+            maps = ops.ce_prologue(x, *(p[n] for n in ("g.weight", "g.bias", "theta.weight", "theta.bias")
+                                        + (("thr_conv.weight", "thr_conv.bias", "bias_conv.weight", "bias_conv.bias") if heads else ())))
+            wq = T.patch_linear(maps[0], T.fc_weight_rows(p["fc1.0.weight"], 16, 7), p["fc1.0.bias"], 7, 4, T._head_grid(H, W)[0],
+                                T._head_grid(H, W)[1], -(-H // 4), -(-W // 4), relu=True, allow_fast=False).contiguous()
+            xk = T.patch_linear(maps[0], T.fc_weight_rows(p["fc2.0.weight"], 16, 7), p["fc2.0.bias"], 7, 1, 0, 0, H, W, relu=True,
+                                allow_fast=False).contiguous()
+            b2 = maps[1][:, 3:3 + H, 3:3 + W, :].permute(0, 3, 1, 2).contiguous()
+            _, s = ops.ce_core_forward(wq, xk, b2, maps[2] if heads else None, maps[3] if heads else None, mode=mode, k=k, exact_scan=True)
+            ws = ops.Workspace()
+            conv = _events(lambda: ops.graph_from_lists(s["nb_idx"], s["nb_wgt"], None, s["nb_cnt"], (H, W), workspace=ws))
+        both = fwd[0] + exp[0]
+        print(f"{head}\n    forward {fmt(fwd)}; graph {fmt(exp)}; forward + graph {both:.3f} ms\n"
+              f"    forward_with_graph split16 {fmt(w16)} = {w16[0] / both:.2f} of forward + graph; fp32 {fmt(w32)} = {w32[0] / both:.2f}\n"
+              f"    ops.graph_from_lists alone {fmt(conv)}; forward_with_graph + forward_on_graph(split16) on its graph {fmt(chain)}", flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--lists":
+        return lists_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     if len(sys.argv) > 1 and sys.argv[1] == "--apply":
         return apply_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     if len(sys.argv) > 1 and sys.argv[1] == "--attend":
