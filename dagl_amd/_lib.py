@@ -104,6 +104,7 @@ SIGNATURES = {
     "dagl_fc_grad16_dmap_ok": (_i, [_i, _i]),
     "dagl_fc_grad16_dmap_scratch_bytes": (_sz, [_i, _i, _i]),
     "dagl_fc_grad16_dmap": (_i, [_vp] + [_i] * 8 + [_vp] * 8 + [_sz]),
+    "dagl_fc_grad16_plan": (_i, [_i] * 11 + [C.POINTER(C.c_int32)]),
     "dagl_unfold_patches": (_i, [_vp] + [_i] * 10 + [_vp, _vp]),
     "dagl_fold_patches": (_i, [_vp] + [_i] * 10 + [_vp, _vp]),
     "dagl_copy4": (_i, [_vp, _i, _i, _i, _i, _vp] + [C.c_longlong] * 4 + [_vp] + [C.c_longlong] * 4),

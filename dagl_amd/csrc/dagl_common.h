@@ -830,7 +830,9 @@ struct Gemm16s {
     // (round 6) the weight gradient's second operand straight from SHIFTED PLANES of the map instead of the transposed patch rows
     // (fcg_shift_planes_kernel: planes[kw][c][b Hp + y][x] = 16 map[b, y, x + kw, c], x < W = 2^im_logw; 61 MB instead of 470 MB at
     // [8, 128, 128]): row n = (kh, kw, c) of B, contraction index k = patch (b, py, px) -> planes[kw][c][b Hp + py + kh][px].  A slice
-    // (K patches) must be whole image rows of ONE image: the block derives (b, py) of its first patch once, no per-lane division
+    // (K patches) must be whole image rows of ONE image: the block derives (b, py) of its first patch once, no per-lane division.
+    // Only the IMPL instantiation of gemm16s_kernel can read such an operand: launch_gemm16s gives every b_implicit call the 256 x 128
+    // tiles that have one (a single slice included) and refuses, with an error code, a call it could not route there (fold_part)
     int b_implicit = 0, im_logw = 0, im_H = 0, im_Hp = 0; long long im_plane = 0;       // im_plane = B Hp W halfs per (kw, c) plane
     int n_loop = 1;                             // column tiles a block walks one after the other (slices == 1; set by launch_gemm16s): short
                                                 // contractions (d rows of the projections: K = 224 = 7 steps) are one operand pipeline of

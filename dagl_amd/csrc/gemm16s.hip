@@ -174,7 +174,8 @@ __global__ __launch_bounds__(256) void fcg_split_transpose_kernel(size_t n, size
 }
 
 // patches of the zero-bordered map [B,Hp,Wp,16], transposed and split: out[(tap, c)][patch] = 16 map[b, oy + py s + kh, ox + px s + kw, c]
-// (patch = (b, py, px) row-major; rows 784..895 are zeroed by the caller, columns past the last patch written as zero).
+// (patch = (b, py, px) row-major; rows 784..895 of the product's last column tile do not exist -- its loads are clamped to row 783 and
+// their results never stored --, columns past the last patch, up to n_pad, are written as zero).
 // Block = 128 consecutive patches x one tap: 64-byte pixel reads, transposed in LDS, 256-byte runs written.
 __global__ __launch_bounds__(256) void fcg_unfold_transpose_kernel(int Hp, int Wp, int stride, int oy, int ox, int oh, int ow,
                                                                    size_t n, size_t n_pad, const float* __restrict__ map,
@@ -525,11 +526,13 @@ __global__ void gemm16s_reduce_kernel(size_t n4, int slices, const float4* __res
     C[i] = make_float4(s.x * alpha, s.y * alpha, s.z * alpha, s.w * alpha);
 }
 
-int launch_gemm16s(hipStream_t s, const Gemm16s& g) {
-    const int nb = g.batch > 1 ? g.batch : 1;
-    // (k_valid: rows shorter than the contraction -- the pieces past a row's end re-read its LAST eight columns, which the caller keeps zero)
-    DAGL_REQUIRE(g.k_valid == 0 || (g.k_valid >= 8 && g.k_valid % 8 == 0 && g.k_valid < g.K),
-                 "gemm16s: k_valid = %d must be a multiple of 8 in [8, K = %d)", g.k_valid, g.K);
+// What launch_gemm16s chooses its kernel by, and the choice (dagl_fc_grad16_plan reports it through the same function)
+struct Gemm16sShape { int M, N, K, slices, batch; bool fold, implicit; };
+struct Gemm16sTile { int bm; bool impl; int n_loop; };      // tile rows (256: eight waves, three-stage ring; 128), IMPL instantiation, Gemm16s::n_loop
+static Gemm16sShape gemm16s_shape_of(const Gemm16s& g) {
+    return {g.M, g.N, g.K, g.slices, g.batch > 1 ? g.batch : 1, g.fold_part != nullptr, g.b_implicit != 0};
+}
+static Gemm16sTile gemm16s_tile(const Gemm16sShape& g) {
     // tile shape by measurement (tools/time_fc_grad.py, n = 131 072): the weight gradient (one 196-row M tile, long K) is
     // faster on 256 x 128 tiles / 8 waves / one block per CU (0.55 against 0.59 ms with its producers), d rows (K = 224:
     // seven steps per block) on 128 x 128 / 4 waves / two blocks per CU (0.42 against 0.49 ms)
@@ -537,17 +540,34 @@ int launch_gemm16s(hipStream_t s, const Gemm16s& g) {
     // backward's batched products (K >= 512, M >= 1024): 114.5 -> 113.0 ms per adaptive-mode step, 47.6 -> 47.1 top-k; the 128 x 128
     // kernel with three stages (one block per CU instead of two): 123.6.  d rows (K = 224: seven steps per block): 128 x 128.
     const bool small_m = g.M <= 256 && g.slices > 1;
+    // A second operand read from shifted planes (Gemm16s::b_implicit) has ONE kernel that can address it, the IMPL instantiation of these
+    // tiles: such a call goes there whatever its slice count (a one-image map whose only admissible slice is the whole image -- 8 x 32,
+    // 5 x 128, 1 x 256 patches -- has a single slice: on the 128 x 128 kernel it read the planes as [784][n_pad] patch rows)
+    if (!g.fold && (small_m || g.implicit || (g.K >= 512 && g.M >= 1024))) return {256, g.implicit, 1};
+    // short contraction, many column tiles (d rows of the patch projections: K = 224, N = 784): a block walks ALL column tiles of
+    // its row tile -- one pipeline of 49 steps instead of seven blocks of 7 (each: request latency, 7 steps, 64 KiB of stores)
+    const int nt = (g.N + 127) / 128;
+    const bool loop = g.slices == 1 && g.K <= 256 && nt > 1 && nt <= 8 && (long long)((g.M + 127) / 128) * g.batch >= 512;
+    return {128, false, loop ? nt : 1};
+}
+
+int launch_gemm16s(hipStream_t s, const Gemm16s& g) {
+    const int nb = g.batch > 1 ? g.batch : 1;
+    // (k_valid: rows shorter than the contraction -- the pieces past a row's end re-read its LAST eight columns, which the caller keeps zero)
+    DAGL_REQUIRE(g.k_valid == 0 || (g.k_valid >= 8 && g.k_valid % 8 == 0 && g.k_valid < g.K),
+                 "gemm16s: k_valid = %d must be a multiple of 8 in [8, K = %d)", g.k_valid, g.K);
+    const Gemm16sTile tile = gemm16s_tile(gemm16s_shape_of(g));
+    DAGL_REQUIRE(!g.b_implicit || tile.impl, "gemm16s: an operand of shifted planes (b_implicit) cannot run on the %d x 128 kernel chosen for "
+                 "M = %d, K = %d, %d slices%s", tile.bm, g.M, g.K, g.slices, g.fold_part ? ", folded" : "");
     Gemm16s gl = g;
     gl.nt_store = (size_t)nb * (size_t)(g.slices > 1 ? g.slices : 1) * (size_t)g.M * (size_t)g.N * sizeof(float) >= ((size_t)64 << 20);
-    if (!g.fold_part && (small_m || (g.K >= 512 && g.M >= 1024))) {
+    if (tile.bm == 256) {
         dim3 grid((g.N + 127) / 128, (g.M + 255) / 256, g.slices * nb);
-        if (g.b_implicit) hipLaunchKernelGGL((gemm16s_kernel<4, 2, 3, true>), grid, dim3(512), 0, s, gl);
+        if (tile.impl) hipLaunchKernelGGL((gemm16s_kernel<4, 2, 3, true>), grid, dim3(512), 0, s, gl);
         else hipLaunchKernelGGL((gemm16s_kernel<4, 2, 3>), grid, dim3(512), 0, s, gl);
     } else {
-        // short contraction, many column tiles (d rows of the patch projections: K = 224, N = 784): a block walks ALL column tiles of
-        // its row tile -- one pipeline of 49 steps instead of seven blocks of 7 (each: request latency, 7 steps, 64 KiB of stores)
         const int nt = (g.N + 127) / 128;
-        gl.n_loop = (g.slices == 1 && g.K <= 256 && nt > 1 && nt <= 8 && (long long)((g.M + 127) / 128) * nb >= 512) ? nt : 1;
+        gl.n_loop = tile.n_loop;
         dim3 grid((nt + gl.n_loop - 1) / gl.n_loop, (g.M + 127) / 128, g.slices * nb);
         hipLaunchKernelGGL((gemm16s_kernel<2, 2>), grid, dim3(256), 0, s, gl);
     }
@@ -624,6 +644,29 @@ static FcgPlan fcg_plan(size_t n, int ow_fold = 0, int im_rps = 0, int im_ow = 0
     return p;
 }
 
+// One call of dagl_fc_grad16 / dagl_fc_grad16_dmap as planned on the host: the scratch layout and K slices, whether one pass over d Z writes
+// both of its split copies, and the shapes of the two products (fc_grad16_impl adds the pointers; dagl_fc_grad16_plan reports the kernels
+// launch_gemm16s picks for them)
+struct FcgCall {
+    FcgPlan p;
+    bool merged_split;
+    Gemm16sShape rows, weight;         // d rows = d Z W (or its fold), d W = d Z^T rows
+};
+static FcgCall fcg_call(int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow, bool want_w, bool want_rows, bool want_map) {
+    FcgCall c;
+    const size_t n = (size_t)B * oh * ow;
+    const int im_rps = want_w ? fcg_implicit_rows(B, stride, oy, ox, oh, ow, Hp, Wp) : 0;
+    c.p = fcg_plan(n, want_map ? ow : 0, im_rps, ow);
+    c.merged_split = (want_rows || want_map) && want_w;
+    c.rows = {(int)n, want_map ? FCG_PP : FCG_P, FCG_OP, 1, 1, want_map, false};
+    c.weight = {FCG_O, FCG_P, (int)c.p.k_slice, c.p.slices, 1, false, c.p.im_rps > 0};
+    return c;
+}
+static bool fcg_geometry_ok(int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow) {
+    return B >= 1 && Hp >= 1 && Wp >= 1 && stride >= 1 && oy >= 0 && ox >= 0 && oh >= 1 && ow >= 1 &&
+           oy + (oh - 1) * stride + KS <= Hp && ox + (ow - 1) * stride + KS <= Wp;
+}
+
 }  // namespace dagl
 
 using namespace dagl;
@@ -654,8 +697,7 @@ size_t dagl_fc_grad16_dmap_scratch_bytes(int B, int oh, int ow) {
 static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow, const float* map_nhwc,
                           const float* w_rows, const float* y, const float* dy, float* d_w, float* d_b, float* d_rows, float* d_map,
                           void* scratch, size_t scratch_bytes) {
-    DAGL_REQUIRE(B >= 1 && Hp >= 1 && Wp >= 1 && stride >= 1 && oy >= 0 && ox >= 0 && oh >= 1 && ow >= 1 &&
-                 oy + (oh - 1) * stride + KS <= Hp && ox + (ow - 1) * stride + KS <= Wp && dy && scratch && (d_w || d_rows || d_b || d_map),
+    DAGL_REQUIRE(fcg_geometry_ok(B, Hp, Wp, stride, oy, ox, oh, ow) && dy && scratch && (d_w || d_rows || d_b || d_map),
                  "dagl_fc_grad16: bad argument");
     DAGL_REQUIRE((!d_w || map_nhwc) && ((!d_rows && !d_map) || w_rows), "dagl_fc_grad16: d_w needs the map, d_rows / d_map the weight");
     DAGL_REQUIRE(!(d_rows && d_map), "dagl_fc_grad16: d_rows or d_map, not both");
@@ -663,8 +705,8 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
     DAGL_REQUIRE(((uintptr_t)scratch % 256) == 0, "dagl_fc_grad16: scratch must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * oh * ow;
-    const int im_rps = d_w ? fcg_implicit_rows(B, stride, oy, ox, oh, ow, Hp, Wp) : 0;
-    const FcgPlan p = fcg_plan(n, d_map ? ow : 0, im_rps, ow);
+    const FcgCall call = fcg_call(B, Hp, Wp, stride, oy, ox, oh, ow, d_w != nullptr, d_rows != nullptr, d_map != nullptr);
+    const FcgPlan& p = call.p;
     DAGL_REQUIRE(scratch_bytes >= p.o_end, "dagl_fc_grad16: scratch %zu B, need %zu B", scratch_bytes, p.o_end);
     void* ws = scratch;
     unsigned* word = at<unsigned>(ws, p.o_word);
@@ -678,7 +720,7 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
         DAGL_LAUNCH_CHECK("fcg_relu_stats_kernel");
         if (d_b) { const int rc = launch_col_sum_final(s, p.stat_blocks, FCG_O, csum, d_b); if (rc) return rc; }
     }
-    const bool merged_split = (d_rows || d_map) && d_w;          // one pass over d Z writes both of its split copies
+    const bool merged_split = call.merged_split;                 // one pass over d Z writes both of its split copies
     if (merged_split) {
         hipLaunchKernelGGL(fcg_split_transpose_kernel, dim3((unsigned)(p.n_pad / 128), FCG_OM / 32), dim3(256), 0, s, n, p.n_pad, p.n_pad + 64, dz,
                            word, at<unsigned short>(ws, p.o_zt_hi), at<unsigned short>(ws, p.o_zt_lo), at<unsigned short>(ws, p.o_zk_hi), at<unsigned short>(ws, p.o_zk_lo));
@@ -695,11 +737,11 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
                            at<unsigned short>(ws, p.o_wt_lo), d_map ? 1 : 0);
         DAGL_LAUNCH_CHECK("fcg_weight_transpose_kernel");
         Gemm16s g;
-        g.M = (int)n; g.N = d_map ? FCG_PP : FCG_P; g.K = FCG_OP;
+        g.M = call.rows.M; g.N = call.rows.N; g.K = call.rows.K;
         g.a_hi = at<unsigned short>(ws, p.o_zk_hi); g.a_lo = at<unsigned short>(ws, p.o_zk_lo); g.lda = FCG_OP; g.a_rows = (int)p.n_pad;
         g.b_hi = at<unsigned short>(ws, p.o_wt_hi); g.b_lo = at<unsigned short>(ws, p.o_wt_lo); g.ldb = FCG_OP; g.b_rows = FCG_PP;
         g.C = d_map ? at<float>(ws, p.o_fold) : d_rows;
-        g.ldc = FCG_P; g.part = nullptr; g.slices = 1; g.scale_word = word; g.alpha0 = 1.0f / FCG_WS;
+        g.ldc = FCG_P; g.part = nullptr; g.slices = call.rows.slices; g.scale_word = word; g.alpha0 = 1.0f / FCG_WS;
         if (d_map) { g.fold_part = at<float>(ws, p.o_fold); g.fold_seg = p.fold_seg; g.fold_rows = p.fold_rows; }
         const int rc = launch_gemm16s(s, g);
         if (rc) return rc;
@@ -732,15 +774,30 @@ static int fc_grad16_impl(void* stream, int B, int Hp, int Wp, int stride, int o
         }
         // (rows 784..895 of the last N tile do not exist: its loads are clamped to row 783, their products are never stored)
         Gemm16s g;
-        g.M = FCG_O; g.N = FCG_P; g.K = (int)p.k_slice;
+        g.M = call.weight.M; g.N = call.weight.N; g.K = call.weight.K;
         g.a_hi = at<unsigned short>(ws, p.o_zt_hi); g.a_lo = at<unsigned short>(ws, p.o_zt_lo); g.lda = (long long)p.n_pad + 64; g.a_rows = FCG_OM;
         g.b_hi = at<unsigned short>(ws, p.o_rt_hi); g.b_lo = at<unsigned short>(ws, p.o_rt_lo); g.ldb = (long long)p.n_pad; g.b_rows = FCG_P;
-        g.C = d_w; g.ldc = FCG_P; g.part = at<float>(ws, p.o_part); g.slices = p.slices; g.scale_word = word;
+        g.C = d_w; g.ldc = FCG_P; g.part = at<float>(ws, p.o_part); g.slices = call.weight.slices; g.scale_word = word;
         g.alpha0 = 1.0f / FCG_XS;
-        if (p.im_rps > 0) { g.b_implicit = 1; g.im_logw = logw; g.im_H = oh; g.im_Hp = Hp; g.im_plane = plane; }
+        if (call.weight.implicit) { g.b_implicit = 1; g.im_logw = logw; g.im_H = oh; g.im_Hp = Hp; g.im_plane = plane; }
         const int rc = launch_gemm16s(s, g);
         if (rc) return rc;
     }
+    return DAGL_OK;
+}
+
+int dagl_fc_grad16_plan(int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow, int want_w, int want_rows, int want_map,
+                        int32_t out[12]) {
+    DAGL_REQUIRE(fcg_geometry_ok(B, Hp, Wp, stride, oy, ox, oh, ow) && out, "dagl_fc_grad16_plan: bad argument");
+    DAGL_REQUIRE(!(want_rows && want_map), "dagl_fc_grad16_plan: d_rows or d_map, not both");
+    DAGL_REQUIRE(!want_map || fcg_fold_ok(stride, ow), "dagl_fc_grad16_plan: stride %d, %d patches per row: not a geometry the product can fold", stride, ow);
+    const FcgCall c = fcg_call(B, Hp, Wp, stride, oy, ox, oh, ow, want_w != 0, want_rows != 0, want_map != 0);
+    const Gemm16sTile tw = gemm16s_tile(c.weight), tr = gemm16s_tile(c.rows);
+    const bool rows = want_rows || want_map;
+    const int32_t v[12] = {(int32_t)c.p.n, (int32_t)c.p.n_pad, c.p.slices, (int32_t)c.p.k_slice, c.p.im_rps,
+                           want_w ? tw.bm : 0, (want_w && tw.impl) ? 1 : 0, rows ? tr.bm : 0, rows ? tr.n_loop : 0,
+                           c.p.fold_seg, c.p.fold_rows, c.merged_split ? 1 : 0};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
     return DAGL_OK;
 }
 

@@ -1261,6 +1261,25 @@ def fc_grad16_fold_ok(stride: int, ow: int) -> bool:
     return bool(_lib.load().dagl_fc_grad16_dmap_ok(stride, ow))
 
 
+FC_GRAD16_PLAN_FIELDS = ("n", "n_pad", "slices", "k_slice", "im_rps", "w_tile", "w_impl", "rows_tile", "n_loop", "fold_seg", "fold_rows",
+                         "merged_split")
+
+
+def fc_grad16_plan(B: int, Hp: int, Wp: int, geometry, want_w: bool = True, want_rows: bool = False, want_map: bool = False) -> dict:
+    """The launch plan of one ``dagl_fc_grad16`` / ``dagl_fc_grad16_dmap`` call (``dagl_fc_grad16_plan``, host only), by the functions the
+    call itself plans with.  ``geometry`` = (stride, oy, ox, oh, ow); ``want_*``: the outputs asked for (d_rows or d_map, not both).
+    For d W: ``n`` patches, ``n_pad``, K ``slices`` of ``k_slice`` patches, ``im_rps`` image rows per slice where it reads shifted planes
+    of the map (0: transposed patch rows), ``w_tile`` = 256 / 128 tile rows of its kernel (0: no d W), ``w_impl`` = 1 where that kernel
+    is the instantiation that reads shifted planes.  For d rows / d map: ``rows_tile`` (0: neither), ``n_loop`` column tiles per block,
+    ``fold_seg`` patches per folded row segment and ``fold_rows`` segments per 128-patch tile.  ``merged_split`` = 1 where one pass over
+    d z writes both of its split copies."""
+    stride, oy, ox, oh, ow = (int(v) for v in geometry)
+    out = (C.c_int32 * 12)()
+    check(_lib.load().dagl_fc_grad16_plan(int(B), int(Hp), int(Wp), stride, oy, ox, oh, ow, int(bool(want_w)), int(bool(want_rows)),
+                                          int(bool(want_map)), out), "dagl_fc_grad16_plan")
+    return dict(zip(FC_GRAD16_PLAN_FIELDS, (int(v) for v in out)))
+
+
 @_on_device
 def fc_grad16(pmap, weight, y, dz, geometry, need_w: bool = True, need_b: bool = True, need_map: bool = True, fold: bool = False):
     """The gradient products of a 7x7x16 -> 196 patch projection on the split-fp16 matrix cores (``dagl_fc_grad16``; ``fold``:

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug and dagl_graph_from_lists* came in without a bump -- no declared signature or struct changed --: a caller that
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists* and dagl_fc_grad16_plan came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -591,6 +591,17 @@ size_t dagl_fc_grad16_dmap_scratch_bytes(int B, int oh, int ow);
 int dagl_fc_grad16_dmap(void* stream, int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow, const float* map_nhwc,
                         const float* w_rows, const float* y, const float* dy, float* d_w, float* d_b, float* d_map, void* scratch,
                         size_t scratch_bytes);
+/* (detected by symbol) A read-out for tests: the launch plan one call of the two entries above would run, computed on the host by the
+ * functions the call itself plans with (no device access).  want_w / want_rows / want_map: which of d_w, d_rows (dagl_fc_grad16) and
+ * d_map (dagl_fc_grad16_dmap) the call asks for -- at most one of the last two; all three 0 is the bias-only call.
+ * out = { n = B oh ow patches, n_pad (the K extent of the weight gradient's operands), K slices of d_w, patches per slice,
+ *         image rows per slice when d_w reads shifted planes of the map (0: transposed patch rows),
+ *         tile rows of d_w's kernel (256 or 128; 0: no d_w), 1 if that kernel is the instantiation that reads shifted planes,
+ *         tile rows of the d rows product's kernel (0: neither d_rows nor d_map), column tiles one of its blocks walks,
+ *         patches per folded row segment and segments per 128-patch tile (both 0 unless want_map),
+ *         1 if one pass over d z writes both of its split copies }.                                                            */
+int dagl_fc_grad16_plan(int B, int Hp, int Wp, int stride, int oy, int ox, int oh, int ow, int want_w, int want_rows, int want_map,
+                        int32_t out[12]);
 
 /* Backward of the first two convolutions of the block (g 3x3 and theta 1x1, 64 -> 16: dagl.py:208-209 under loss.backward(),
  * DN_Gray/trainer.py:48-57) straight on the maps -- no patch rows (conv_grad.hip): tap-wise products on the fp32 matrix cores,
