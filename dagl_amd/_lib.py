@@ -32,6 +32,8 @@ FLAG_TIGHT_TOPK = 0x1000
 FLAG_SAMPLED_TOPK = 0x2000
 FLAG_NO_REDO = 0x4000
 GRAPH_ATTEND_EDGES_ONLY = 0x1      # dagl_graph_attend*: a plain softmax over the row's edges
+GRAPH_REFRESH_KEEP_ALL = 0x2       # dagl_graph_refresh: keep every candidate (the dilated graph)
+GRAPH_REFRESH_BLOCK_ROWS = 0x4     # dagl_graph_refresh: a block per row also where rows are short (measurements)
 
 
 class DaglError(RuntimeError):
@@ -81,6 +83,10 @@ SIGNATURES = {
     "dagl_graph_forward": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _vp, C.c_float, _i, _vp, _vp, _sz]),
     "dagl_graph_from_lists_workspace_bytes": (_sz, [_i, _i, _i]),
     "dagl_graph_from_lists": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8 + [C.c_int64, _vp, _sz]),
+    "dagl_graph_refresh_max_candidates": (_i, []),
+    "dagl_graph_refresh_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i]),
+    "dagl_graph_refresh": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 4
+                           + [C.c_int64, _vp, _vp, _sz]),
     "dagl_ce_list_width": (_i, [_i, _i]),
     "dagl_ce_range_check": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(_i)]),
     "dagl_ce_core_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

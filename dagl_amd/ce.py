@@ -242,6 +242,7 @@ class CE(nn.Module):
         self._ws_lists = ops.Workspace()      # forward_with_graph(): the list-form core's forward and backward, the degrees of the CSR conversion
         self._ws_lists_bwd = ops.Workspace()
         self._ws_lists_csr = ops.Workspace()
+        self._ws_refresh = ops.Workspace()    # refresh_graph(): the degrees and the staged candidates
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -697,14 +698,46 @@ class CE(nn.Module):
     _FP32_ONLY = ("CE: the differentiable path needs fp32 parameters (the reference's --precision half is a test-time "
                   "switch, DN_Gray/model/__init__.py:98-99); run half-precision modules under torch.no_grad()")
 
+    def _graph_features(self, b: torch.Tensor, margin: bool, fast: bool, grad: bool):
+        """What the calls on a given graph share once their refusals are through (the caller sets the grad mode): one prologue call,
+        fc1 / fc2 on the fp32 route or (``fast``) the training path's split-fp16 kernels, ``tau`` in plain torch
+        -> (wq_rows [B,L,196], x_rows [B,N,196], tau [B,L] | None, b2p, poisoned)."""
+        from types import SimpleNamespace
+        from . import train_ops as T
+        B, _, H, W = b.shape
+        p = {n: t for n, t in self.named_parameters()} if grad else self._params_f32(scaled=False)
+        ks, c = self.ksize, self.inter_channels
+        t, _bo = same_pad_amounts(H, ks, self.stride_1)
+        l, _r = same_pad_amounts(W, ks, self.stride_1)
+        Lh, Lw = -(-H // self.stride_1), -(-W // self.stride_1)
+        x = b.float() if b.dtype != torch.float32 else b
+        x = _pad_channels4(x.contiguous())
+        convs = [SimpleNamespace(weight=_pad_channels4(p[n + ".weight"]), bias=p[n + ".bias"])
+                 for n in ("g", "theta") + (("thr_conv", "bias_conv") if margin else ())]
+        maps = T.prologue_convs(x, *convs, fast=fast)                                       # dagl.py:208-215
+        b1p, b2p = maps[0], maps[1]
+        wq_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], c, ks), p["fc1.0.bias"], ks, self.stride_1,
+                                 T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=fast)    # [B,L,196]
+        x_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], c, ks), p["fc2.0.bias"], ks, self.stride_2,
+                                0, 0, H, W, relu=True, allow_fast=fast)                       # [B,N,196]
+        tau = None
+        if margin:
+            # mean_j S_ij = <wq_i, mean_j x_j>: linear in the key features, autograd carries the heads and the mean (dagl.py:256-258)
+            mean_s = torch.bmm(wq_rows, x_rows.mean(dim=1).unsqueeze(2)).squeeze(2)
+            tau = mean_s * maps[2].reshape(B, -1) - maps[3].reshape(B, -1)
+        # the split-fp16 kernels NaN-fill ALL they hand out once an operand leaves their range; the margin would turn such rows
+        # into "no edge passes" and zeros: one element of each feature matrix carries the verdict into every result instead
+        # (t + 0 * wq[0] * x[0], one launch per result)
+        poisoned = (lambda t: torch.addcmul(t, wq_rows.detach().reshape(-1)[:1], x_rows.detach().reshape(-1)[:1], value=0.0)) if fast \
+            else (lambda t: t)
+        return wq_rows, x_rows, tau, b2p, poisoned
+
     def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool, features: str = "fp32",
                          fused=False):
         """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route or
         (``features="split16"``) the training path's split-fp16 kernels, ``tau`` in plain torch, then ``_GraphAttend`` and -- ``apply`` --
         ``_GraphApply`` on the same value map, or (``fused``; None = with ``features="split16"`` whenever no gradient is wanted)
         ``ops.graph_forward`` in their place.  -> (weight, score, out | None); the fused call returns (None, None, out)."""
-        from types import SimpleNamespace
-        from . import train_ops as T
         self._check_given_graph(b, graph, what)
         if normalize not in ("reference", "edges"):
             raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
@@ -714,7 +747,6 @@ class CE(nn.Module):
         if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
             raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
         margin = self.select_mode != "topk" if margin is None else bool(margin)
-        B, _, H, W = b.shape
         used = [self.g, self.fc1, self.fc2] + ([self.theta] if apply else []) + ([self.thr_conv, self.bias_conv] if margin else [])
         grad = torch.is_grad_enabled() and (b.requires_grad or any(p.requires_grad for m in used for p in m.parameters()))
         if grad:
@@ -723,36 +755,10 @@ class CE(nn.Module):
                                 "fused=None or False keeps the two differentiable ops")
             if any(p.dtype != torch.float32 for p in self.parameters()):
                 raise DaglError(self._FP32_ONLY)
-            p = {n: t for n, t in self.named_parameters()}
-        else:
-            p = self._params_f32(scaled=False)
         # (None: the fused kernel belongs to the opt-in route -- the default call keeps the bits of the two-op composition)
         fused = apply and not grad and (fast if fused is None else bool(fused))
-        ks, c = self.ksize, self.inter_channels
-        t, _bo = same_pad_amounts(H, ks, self.stride_1)
-        l, _r = same_pad_amounts(W, ks, self.stride_1)
-        Lh, Lw = -(-H // self.stride_1), -(-W // self.stride_1)
         with torch.enable_grad() if grad else torch.no_grad():
-            x = b.float() if b.dtype != torch.float32 else b
-            x = _pad_channels4(x.contiguous())
-            convs = [SimpleNamespace(weight=_pad_channels4(p[n + ".weight"]), bias=p[n + ".bias"])
-                     for n in ("g", "theta") + (("thr_conv", "bias_conv") if margin else ())]
-            maps = T.prologue_convs(x, *convs, fast=fast)                                       # dagl.py:208-215
-            b1p, b2p = maps[0], maps[1]
-            wq_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc1.0.weight"], c, ks), p["fc1.0.bias"], ks, self.stride_1,
-                                     T.PAD - t, T.PAD - l, Lh, Lw, relu=True, allow_fast=fast)    # [B,L,196]
-            x_rows = T.patch_linear(b1p, T.fc_weight_rows(p["fc2.0.weight"], c, ks), p["fc2.0.bias"], ks, self.stride_2,
-                                    0, 0, H, W, relu=True, allow_fast=fast)                       # [B,N,196]
-            tau = None
-            if margin:
-                # mean_j S_ij = <wq_i, mean_j x_j>: linear in the key features, autograd carries the heads and the mean (dagl.py:256-258)
-                mean_s = torch.bmm(wq_rows, x_rows.mean(dim=1).unsqueeze(2)).squeeze(2)
-                tau = mean_s * maps[2].reshape(B, -1) - maps[3].reshape(B, -1)
-            # the split-fp16 kernels NaN-fill ALL they hand out once an operand leaves their range; the margin would turn such rows
-            # into "no edge passes" and zeros: one element of each feature matrix carries the verdict into every result instead
-            # (t + 0 * wq[0] * x[0], one launch per result)
-            poisoned = (lambda t: torch.addcmul(t, wq_rows.detach().reshape(-1)[:1], x_rows.detach().reshape(-1)[:1], value=0.0)) if fast \
-                else (lambda t: t)
+            wq_rows, x_rows, tau, b2p, poisoned = self._graph_features(b, margin, fast, grad)
             if fused:
                 out = ops.graph_forward(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
                                         tau.contiguous() if tau is not None else None, scale=float(self.softmax_scale),
@@ -805,6 +811,64 @@ class CE(nn.Module):
         by fp32 roundings only.  ``graph.weight`` / ``graph.score`` are left alone either way."""
         out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True, features, fused)[2]
         return out if b.dtype == torch.float32 else out.to(b.dtype)
+
+    def refresh_graph(self, b: torch.Tensor, graph, *, radius: int = 1, margin=None, normalize: str = "reference",
+                      features: str = "fp32"):
+        """``graph`` moved to the input ``b`` -> a new ``PatchGraph``: every query looks only at the keys in the
+        ``(2 radius + 1)^2`` windows around its neighbours in ``graph`` (clipped at the map border; repeats count once), scores those
+        candidates exactly and applies this module's selection rule to them (``ops.graph_refresh``, csrc/graph_refresh.hip) -- the
+        structure update that costs O(edges) where ``graph`` / ``forward`` scan all L*N pairs.  For a sequence (video frames, bursts,
+        recurrent passes over slowly changing features): ``g = ce.refresh_graph(frame, g)``, then ``forward_on_graph(frame, g)``.
+
+        Selection by the module's mode: "adaptive" = the margin ``S - tau > 0``, no rank cut; "topk" = the ``min(select_k, N)`` best
+        candidates, no margin; "adaptive_topk" = both; a tie at the last place goes to the lower key.  ``margin`` True / False
+        overrides whether ``tau`` is used, ``normalize`` and ``features`` (with its range contract) are ``attend_graph``'s, and so are
+        the features and ``tau`` themselves.  Because the adaptive threshold is linear in the key features, the result is exactly the
+        reference's mask restricted to the candidates; where the candidates contain the true neighbours --
+        ``refresh_graph(x, graph(x))`` -- the result is ``graph(x)``.  ``weight`` is what ``attend_graph`` gives on the new structure,
+        ``score`` the unscaled S; the result carries the module's ``mode`` and ``k`` and valid keys.
+
+        Always under ``torch.no_grad()``: the result is a constant structure with constant weights; gradients are
+        ``forward_on_graph``'s job on the result.  Refused before any launch: ``attend_graph``'s refusals (patch geometry, device,
+        dtype, shape), a stream under capture (the edge count is read on the host), ``select_k < 1`` in the top-k modes, ``radius``
+        outside 0..8, and a graph whose largest degree times ``(2 radius + 1)^2`` exceeds ``ops.graph_refresh_max_candidates()``.  The
+        largest degree is read once per graph (kept on the object, as ``validate``'s verdict).  The module's state (packed weights,
+        top-k policy, range verdicts, ``_train_dense``) is untouched: the call has a workspace of its own."""
+        what = "refresh_graph"
+        if torch.cuda.is_current_stream_capturing():
+            raise DaglError(f"CE.{what}: not available while the stream is being captured (the edge count is read on the host)")
+        self._check_given_graph(b, graph, what)
+        if normalize not in ("reference", "edges"):
+            raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
+        if features not in ("fp32", "split16"):
+            raise DaglError(f"CE.{what}: features={features!r}, expected 'fp32' or 'split16'")
+        if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
+            raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
+        radius = int(radius)
+        if not 0 <= radius <= 8:
+            raise DaglError(f"CE.{what}: radius={radius} outside [0, 8]")
+        B, _, H, W = b.shape
+        k_eff = 0
+        if self.select_mode != "adaptive":
+            if int(self.select_k) < 1:
+                raise DaglError(f"CE: select_k={self.select_k} < 1")
+            k_eff = min(int(self.select_k), H * W)
+        margin = self.select_mode != "topk" if margin is None else bool(margin)
+        longest, cap = graph.max_degree(), ops.graph_refresh_max_candidates()
+        if longest * (2 * radius + 1) ** 2 > cap:
+            err = DaglError(f"CE.{what}: the graph's largest degree {longest} times (2 radius + 1)^2 = {(2 * radius + 1) ** 2} is "
+                            f"{longest * (2 * radius + 1) ** 2} candidates, a row may expand into {cap}")
+            err.code = ERR_UNSUPPORTED
+            raise err
+        with torch.no_grad():
+            wq_rows, x_rows, tau, _b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
+            csr = ops.graph_refresh(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, radius=radius,
+                                    tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
+                                    normalize=normalize, max_row_edges=longest, workspace=self._ws_refresh, hw=(H, W))
+            g = graph._like(csr["row_off"], csr["key"], poisoned(csr["weight"]), poisoned(csr["score"]))     # (no second host read)
+        g.mode, g.k = self.select_mode, k_eff
+        g._valid = True                              # (every candidate is a key of the map)
+        return g
 
     def forward_with_graph(self, b: torch.Tensor, *, scores: bool = False, features=None):
         """The block's output for ``b`` AND the patch graph that produced it, from one call -> ``(out, PatchGraph)``: the list-form route

@@ -1,0 +1,379 @@
+// Refresh of a patch graph on a new input (ABI 412, detected by symbol): the structure update that costs O(edges).  Every query row looks
+// only at the keys in a (2 radius + 1)^2 window around each of its previous neighbours, scores those candidates exactly, applies the
+// module's selection rule to them and leaves a new CSR -- the PatchMatch / NN-descent propagation step on the PatchGraph.  With
+// Wq [B L, 196] / X [B N, 196] the fc1 / fc2 features, per row r (image b = r / L):
+//   candidates   the SET of keys (y + dy) W + (x + dx), (y, x) = (key_e / W, key_e % W) over the row's edges with key_e in [0, N),
+//                |dy|, |dx| <= radius, clipped at the map border (never wrapped); a key outside [0, N) contributes nothing
+//   S_j          <Wq[r], X[b N + j]> by gt_edge_dot (graph_rows.h): the bits dagl_graph_attend computes for the same pair, whatever k,
+//                tau, the flags or the rest of the row are
+//   selection    tau given: j passes iff S_j - tau_r > 0 (gt_logit);  k > 0: the min(k, passing) passing candidates with the largest S,
+//                a tie at the last place to the lower key;  DAGL_GRAPH_REFRESH_KEEP_ALL: every candidate (the dilated graph)
+//   weight       dagl_graph_attend's on the OUTPUT structure: z = scale S m, M = max(max z, 0 if deg < N),
+//                D = sum e^(z - M) + (N - deg) e^(-M) (DAGL_GRAPH_ATTEND_EDGES_ONLY: over the edges alone), w = on e^(z - M) / D
+//
+//   graph_refresh_rows_kernel     a block per row (a wavefront per row where rows are short): expand into the LDS, bitonic sort, drop the
+//                                 repeats, score the distinct candidates (a candidate per 16 lanes, two in flight per group), margin,
+//                                 rank counting, fp32 maximum, fp64 sum in a fixed order, then the kept (key, score, weight) in ascending
+//                                 key order to the front of the row's staging region -- it starts at row_off[r] (2 radius + 1)^2, a place
+//                                 known without a scan -- and the degree
+//   row_scan_kernel               select.hip: int32 degrees -> int64 offsets, row_off_out[B L] = E
+//   graph_refresh_compact_kernel  a wavefront per row copies its staged entries to row_off_out[r]: ordered, no atomics
+//
+// A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
+// atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
+// candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
+// makes a kernel leave its buffers.  Nothing is read on the host; the same arrays give the same bits on every call.
+#include "dagl_common.h"
+#include "graph_rows.h"
+
+namespace dagl {
+
+constexpr int RF_CAP = 2048;                  // candidates (before the repeats are dropped) a row may expand into: dagl_graph_refresh_max_candidates()
+constexpr int RF_WAVE_CAP = 128;              // up to here a row is a wavefront's work (measured: DESIGN.md section 7; launch_graph_refresh)
+constexpr int RF_MAX_RADIUS = 8;
+constexpr int RF_EMPTY = 0x7fffffff;          // sorts behind every key
+constexpr int RF_COPY_ROWS = 4;               // rows (wavefronts) per block of the compaction
+
+struct RfArgs {
+    int W, H, radius, max_row_edges, k, keep_all;
+    int32_t* deg;                             // [B L] kept candidates per row
+    int32_t* st_key; float* st_score; float* st_weight;     // [E (2 radius + 1)^2] staging
+    unsigned long long* status;               // [2]: rows longer than max_row_edges, largest number of distinct candidates of a row
+};
+
+// a float as an unsigned that orders the same way: -0 = +0, NaN below everything (a strict total order with the key as tie-break: a rank
+// cut keeps exactly min(k, passing) entries whatever the scores hold)
+__device__ __forceinline__ unsigned rf_ord(float s) {
+    if (s != s) return 0u;
+    const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// exclusive prefix of v over the block's threads and the total, the same in every thread
+template <int T>
+__device__ __forceinline__ int rf_scan(int v, int* sh, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    __syncthreads();
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int i = 0; i < T / 64; ++i) {
+        base += i < w ? sh[i] : 0;
+        total += sh[i];
+    }
+    return base + inc - v;
+}
+
+// maximum / sum over the block, fixed order: the xor butterfly inside each wave, then the waves one after the other
+template <int T>
+__device__ __forceinline__ float rf_max(float v, float* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float m = sh[0];
+#pragma unroll
+    for (int i = 1; i < T / 64; ++i) m = fmaxf(m, sh[i]);
+    return m;
+}
+template <int T>
+__device__ __forceinline__ double rf_sum(double v, double* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = sh[0];
+#pragma unroll
+    for (int i = 1; i < T / 64; ++i) s += sh[i];
+    return s;
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs f) {
+    __shared__ int s_sort[CAP];               // the expanded candidates, sorted; then the order word of a passing candidate
+    __shared__ int s_key[CAP];                // the distinct candidates, ascending
+    __shared__ float s_sc[CAP];               // their scores
+    __shared__ unsigned char s_flag[CAP];     // bits 0-1: the margin is not 0 (the candidate passes), bit 2: kept
+    __shared__ int sh_i[T / 64];
+    __shared__ float sh_f[T / 64];
+    __shared__ double sh_d[T / 64];
+    const int t = threadIdx.x;
+    const int row = blockIdx.x;
+    const long long lo = gt_clamp(a.row_off[row], a.E), hi = gt_clamp(a.row_off[row + 1], a.E);
+    const long long deg_in = hi - lo;
+    const int wd = 2 * f.radius + 1, w2 = wd * wd;
+    if (deg_in <= 0 || deg_in > f.max_row_edges || deg_in * w2 > CAP) {          // (the same in every thread)
+        if (t == 0) {
+            f.deg[row] = 0;
+            if (deg_in > 0) atomicAdd(f.status, 1ull);
+        }
+        return;
+    }
+    // 1. expand: entry idx = (edge, window offset); what falls off the map or comes from a key off the map sorts to the end
+    const int raw = (int)deg_in * w2;
+    int n_pad = 64;
+    while (n_pad < raw) n_pad <<= 1;                                              // <= CAP: CAP is a power of two >= raw
+    for (int idx = t; idx < n_pad; idx += T) {
+        int c = RF_EMPTY;
+        if (idx < raw) {
+            const int e = idx / w2, o = idx - e * w2;
+            const int key = a.key[lo + e];
+            if ((unsigned)key < (unsigned)a.N) {
+                const int oy = o / wd;
+                const int y = key / f.W + oy - f.radius, x = key % f.W + (o - oy * wd) - f.radius;
+                if ((unsigned)y < (unsigned)f.H && (unsigned)x < (unsigned)f.W) c = y * f.W + x;
+            }
+        }
+        s_sort[idx] = c;
+    }
+    __syncthreads();
+    // 2. bitonic sort, ascending
+    for (int kk = 2; kk <= n_pad; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < n_pad; i += T) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const int u = s_sort[i], v = s_sort[p];
+                    if ((u > v) == ((i & kk) == 0)) { s_sort[i] = v; s_sort[p] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // 3. the distinct candidates, in order: a run of consecutive entries per thread, an exclusive scan of the counts
+    const int per = n_pad / T > 0 ? n_pad / T : 1;
+    const int i0 = min(n_pad, t * per), i1 = min(n_pad, i0 + per);
+    int cnt = 0;
+    for (int i = i0; i < i1; ++i) cnt += s_sort[i] != RF_EMPTY && (i == 0 || s_sort[i] != s_sort[i - 1]);
+    int n;
+    int pos = rf_scan<T>(cnt, sh_i, n);
+    for (int i = i0; i < i1; ++i)
+        if (s_sort[i] != RF_EMPTY && (i == 0 || s_sort[i] != s_sort[i - 1])) s_key[pos++] = s_sort[i];
+    __syncthreads();
+    if (t == 0 && (unsigned long long)n > f.status[1]) atomicMax(f.status + 1, (unsigned long long)n);
+    // 4. scores and margins: a candidate per 16 lanes, two in flight per group
+    {
+        const int l = t & 15, grp = t >> 4, G = T / 16;
+        const float4* q = reinterpret_cast<const float4*>(a.wq) + (size_t)row * GT_C4;
+        const float4* xk = reinterpret_cast<const float4*>(a.x) + (size_t)(row / a.L) * a.N * GT_C4;
+        for (int c0 = grp; c0 < n; c0 += 2 * G) {
+            const int c1 = c0 + G < n ? c0 + G : c0;
+            const float v0 = gt_edge_dot(q, xk + (size_t)s_key[c0] * GT_C4, l);
+            const float v1 = gt_edge_dot(q, xk + (size_t)s_key[c1] * GT_C4, l);
+            if (l == 0) {
+                float mg;
+                gt_logit(a, row, v0, mg);
+                s_sc[c0] = v0;
+                s_flag[c0] = mg != 0.f ? 3 : 0;
+                if (c1 != c0) {
+                    gt_logit(a, row, v1, mg);
+                    s_sc[c1] = v1;
+                    s_flag[c1] = mg != 0.f ? 3 : 0;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // 5. the rank cut among the passing candidates: better = a larger score, or an equal one with a lower key
+    unsigned* s_ord = reinterpret_cast<unsigned*>(s_sort);
+    if (f.keep_all) {
+        for (int c = t; c < n; c += T) s_flag[c] |= 4;
+    } else if (f.k <= 0) {
+        for (int c = t; c < n; c += T) s_flag[c] |= (s_flag[c] & 2) << 1;
+    } else {
+        for (int c = t; c < n; c += T) s_ord[c] = rf_ord(s_sc[c]);
+        __syncthreads();
+        for (int c = t; c < n; c += T) {
+            if (!(s_flag[c] & 2)) continue;
+            const unsigned oc = s_ord[c];
+            int rank = 0;
+            for (int j = 0; j < n; ++j) {                        // (ascending keys: j < c is the lower key)
+                const unsigned oj = s_ord[j];
+                rank += (s_flag[j] & 2) && (oj > oc || (oj == oc && j < c));
+            }
+            if (rank < f.k) s_flag[c] |= 4;
+        }
+    }
+    __syncthreads();
+    // 6. the output row: its degree, the maximum, the sum, the weights
+    cnt = 0;
+    const int pr = (n + T - 1) / T;
+    const int c0 = min(n, t * pr), c1 = min(n, c0 + pr);
+    for (int c = c0; c < c1; ++c) cnt += (s_flag[c] >> 2) & 1;
+    int kept;
+    pos = rf_scan<T>(cnt, sh_i, kept);
+    if (t == 0) f.deg[row] = kept;
+    if (kept == 0) return;                                       // (the same in every thread)
+    const bool off_graph = !a.edges_only && kept < a.N;
+    float mx = -INFINITY;
+    for (int c = c0; c < c1; ++c) {
+        float mg;
+        if (s_flag[c] & 4) mx = fmaxf(mx, gt_logit(a, row, s_sc[c], mg));
+    }
+    mx = rf_max<T>(mx, sh_f);
+    const float M = off_graph ? fmaxf(mx, 0.f) : mx;
+    double sum = 0.0;
+    for (int c = c0; c < c1; ++c) {
+        float mg;
+        if (s_flag[c] & 4) sum += (double)expf(gt_logit(a, row, s_sc[c], mg) - M);
+    }
+    sum = rf_sum<T>(sum, sh_d);
+    if (off_graph) sum += (double)(a.N - kept) * exp(-(double)M);
+    // 7. the kept entries, ascending keys, to the front of the row's staging region (kept <= n <= raw = its size)
+    const long long base = lo * w2;
+    for (int c = c0; c < c1; ++c) {
+        if (!(s_flag[c] & 4)) continue;
+        float mg;
+        const float z = gt_logit(a, row, s_sc[c], mg);
+        f.st_key[base + pos] = s_key[c];
+        f.st_score[base + pos] = s_sc[c];
+        f.st_weight[base + pos] = mg != 0.f ? (float)((double)expf(z - M) / sum) : 0.f;
+        ++pos;
+    }
+}
+
+// a wavefront per row: its staged entries to their place in the output
+__global__ __launch_bounds__(RF_COPY_ROWS * 64) void graph_refresh_compact_kernel(int n_rows, int w2, long long E, const int64_t* __restrict__ row_off,
+                                                                                  const int32_t* __restrict__ deg,
+                                                                                  const int64_t* __restrict__ row_off_out,
+                                                                                  const int32_t* __restrict__ st_key, const float* __restrict__ st_score,
+                                                                                  const float* __restrict__ st_weight, int32_t* __restrict__ key,
+                                                                                  float* __restrict__ weight, float* __restrict__ score,
+                                                                                  long long capacity) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * RF_COPY_ROWS + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const long long src = gt_clamp(row_off[row], E) * w2, dst = row_off_out[row];
+    const int n = deg[row];                                      // <= the row's staging region (graph_refresh_rows_kernel)
+    for (int i = lane; i < n; i += 64) {
+        if (dst + i >= capacity) break;                          // (offsets that overlap: more staged than the caller's bound)
+        key[dst + i] = st_key[src + i];
+        score[dst + i] = st_score[src + i];
+        weight[dst + i] = st_weight[src + i];
+    }
+}
+
+struct RefreshWs { int32_t* deg; int32_t* st_key; float* st_score; float* st_weight; size_t bytes; };
+
+static RefreshWs refresh_carve(void* ws, size_t n_rows, size_t staged) {
+    Carver cv(ws);
+    RefreshWs w;
+    w.deg = cv.take<int32_t>(n_rows);
+    w.st_key = cv.take<int32_t>(staged + 1);
+    w.st_score = cv.take<float>(staged + 1);
+    w.st_weight = cv.take<float>(staged + 1);
+    w.bytes = cv.bytes();
+    return w;
+}
+
+struct RefreshCall {
+    GraphAttendCall c; int max_row_edges, radius, k; bool keep_all, block_rows;
+    int64_t* row_off_out; int32_t* key_out; float* weight_out; float* score_out; int64_t capacity; int64_t* status;
+};
+
+static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const RefreshCall& r, void* workspace) {
+    const int n_rows = B * g.L, wd = 2 * r.radius + 1, w2 = wd * wd;
+    DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
+    if (r.c.E == 0) {
+        DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
+        return DAGL_OK;
+    }
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2);
+    GtArgs a{};
+    a.row_off = r.c.row_off; a.n_rows = n_rows; a.key = r.c.key; a.E = r.c.E;
+    a.wq = r.c.wq_rows; a.x = r.c.x_rows; a.tau = r.c.tau; a.L = g.L; a.N = g.N; a.scale = r.c.scale; a.edges_only = r.c.edges_only ? 1 : 0;
+    RfArgs f{};
+    f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
+    f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
+    f.status = reinterpret_cast<unsigned long long*>(r.status);
+    // short rows (top-k 8 at radius 1: 72 candidates) take a wavefront each, longer ones a block of four
+    if (!r.block_rows && (long long)r.max_row_edges * w2 <= RF_WAVE_CAP) {
+        hipLaunchKernelGGL((graph_refresh_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f);
+    } else {
+        hipLaunchKernelGGL((graph_refresh_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f);
+    }
+    DAGL_LAUNCH_CHECK("graph_refresh_rows_kernel");
+    const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
+    if (rc) return rc;
+    hipLaunchKernelGGL(graph_refresh_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0, s,
+                       n_rows, w2, (long long)r.c.E, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out,
+                       r.weight_out, r.score_out, (long long)r.capacity);
+    DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
+    return DAGL_OK;
+}
+
+static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
+    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+    DAGL_REQUIRE((int64_t)B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    DAGL_REQUIRE(radius >= 0 && radius <= RF_MAX_RADIUS, "%s: radius=%d outside [0, %d]", who, radius, RF_MAX_RADIUS);
+    DAGL_REQUIRE(total_edges >= 0 && total_edges < (1ll << 31), "%s: total_edges=%lld outside [0, 2^31)", who, (long long)total_edges);
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    DAGL_REQUIRE(total_edges * w2 < (1ll << 31), "%s: total_edges (2 radius + 1)^2 = %lld staged candidates, 2^31 or more", who,
+                 (long long)(total_edges * w2));
+    return DAGL_OK;
+}
+
+}  // namespace dagl
+
+using namespace dagl;
+
+extern "C" {
+
+int dagl_graph_refresh_max_candidates(void) { return RF_CAP; }
+
+size_t dagl_graph_refresh_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius) {
+    if (refresh_shape_ok("dagl_graph_refresh_workspace_bytes", B, H, W, total_edges, radius)) return 0;
+    return refresh_carve(nullptr, (size_t)B * make_grid(H, W).L, (size_t)total_edges * (2 * radius + 1) * (2 * radius + 1)).bytes;
+}
+
+int dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                       const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau, int k, float scale,
+                       int flags, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges,
+                       int64_t* status_out, void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_refresh";
+    int rc = refresh_shape_ok(who, B, H, W, total_edges, radius);
+    if (rc) return rc;
+    DAGL_REQUIRE(wq_rows && x_rows && row_off && row_off_out && status_out && (total_edges == 0 || (key && key_out && weight_out && score_out)),
+                 "%s: null tensor pointer", who);
+    DAGL_REQUIRE(((uintptr_t)wq_rows % 16) == 0 && ((uintptr_t)x_rows % 16) == 0, "%s: feature rows must be 16-byte aligned", who);
+    DAGL_REQUIRE((flags & ~(DAGL_GRAPH_ATTEND_EDGES_ONLY | DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)) == 0,
+                 "%s: unknown flags 0x%x", who, flags);
+    DAGL_REQUIRE(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    if ((int64_t)max_row_edges * w2 > RF_CAP) {
+        set_error("%s: max_row_edges (2 radius + 1)^2 = %lld candidates per row, more than the %d a row may expand into", who,
+                  (long long)((int64_t)max_row_edges * w2), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    const Grid g = make_grid(H, W);
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    int64_t may = total_edges * w2;
+    if (!keep_all && k > 0 && (int64_t)B * g.L * k < may) may = (int64_t)B * g.L * k;
+    if (capacity_edges < may) {
+        set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
+        return DAGL_ERR_WORKSPACE;
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)B * g.L, (size_t)(total_edges * w2)).bytes;
+    if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
+    RefreshCall r{};
+    r.c = GraphAttendCall{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
+    r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.row_off_out = row_off_out; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.capacity = capacity_edges;
+    r.status = status_out;
+    return launch_graph_refresh((hipStream_t)stream, B, g, r, workspace);
+}
+
+}  // extern "C"

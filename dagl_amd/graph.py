@@ -59,6 +59,7 @@ class PatchGraph:
         self.B, self.L, self.N, self.H, self.W, self.mode, self.k = B, L, N, H, W, mode, k
         self._valid = False              # ``validate`` has found every key in [0, N)
         self._transposed = None          # ``transpose``'s (col_off, src_row, perm)
+        self._max_degree = None          # ``max_degree``'s value
 
     @property
     def n_edges(self) -> int:
@@ -67,6 +68,13 @@ class PatchGraph:
     def degrees(self) -> torch.Tensor:
         """[B, L] int64: keys per query."""
         return (self.row_off[1:] - self.row_off[:-1]).view(self.B, self.L)
+
+    def max_degree(self) -> int:
+        """The largest number of keys a query holds.  One reduction and one host read; the value is kept (``with_weight`` and ``to`` hand
+        it on -- they keep the offsets --, ``select`` does not)."""
+        if self._max_degree is None:
+            self._max_degree = int((self.row_off[1:] - self.row_off[:-1]).max()) if self.n_edges else 0
+        return self._max_degree
 
     def _row_index(self, b: int, i: int) -> int:
         if not (0 <= b < self.B and 0 <= i < self.L):
@@ -101,7 +109,7 @@ class PatchGraph:
         g = object.__new__(PatchGraph)
         g.row_off, g.key, g.weight, g.score = row_off, key, weight, score
         g.B, g.L, g.N, g.H, g.W, g.mode, g.k = self.B, self.L, self.N, self.H, self.W, self.mode, self.k
-        g._valid, g._transposed = self._valid, None
+        g._valid, g._transposed, g._max_degree = self._valid, None, None
         return g
 
     def rows(self) -> torch.Tensor:
@@ -117,6 +125,7 @@ class PatchGraph:
                        self.score.to(device) if self.score is not None else None)
         if self._transposed is not None:
             g._transposed = tuple(t.to(device) for t in self._transposed)
+        g._max_degree = self._max_degree
         return g
 
     def with_weight(self, weight: torch.Tensor) -> "PatchGraph":
@@ -129,7 +138,7 @@ class PatchGraph:
         if weight.device != self.row_off.device:
             raise DaglError(f"PatchGraph.with_weight: weight lives on {weight.device}, the graph on {self.row_off.device}")
         g = self._like(self.row_off, self.key, weight, self.score)
-        g._transposed = self._transposed
+        g._transposed, g._max_degree = self._transposed, self._max_degree
         return g
 
     def select(self, mask: torch.Tensor) -> "PatchGraph":

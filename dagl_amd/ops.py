@@ -605,6 +605,77 @@ def graph_from_lists(nb_idx, nb_wgt, nb_s, nb_cnt, hw, workspace: "Workspace | N
     return dict(row_off=row_off, key=key[:total], weight=weight[:total], score=score[:total] if score is not None else None)
 
 
+def graph_refresh_max_candidates() -> int:
+    """Candidates (``max_row_edges * (2 radius + 1)^2``) a row of ``graph_refresh`` may expand into: a constant of the library."""
+    return int(_lib.load().dagl_graph_refresh_max_candidates())
+
+
+@_on_device
+def graph_refresh(wq_rows, x_rows, row_off, key, *, radius: int = 1, tau=None, k: int = 0, scale: float = 10.0,
+                  normalize: str = "reference", keep_all: bool = False, max_row_edges=None, workspace: "Workspace | None" = None,
+                  hw=None, block_rows: bool = False) -> dict:
+    """A graph structure moved onto new features (``dagl_graph_refresh``, csrc/graph_refresh.hip) -> dict(row_off [B*L+1] int64, key [E]
+    int32, weight [E] fp32, score [E] fp32), keys strictly ascending inside a row.  Operands as ``graph_attend``.  Per row the candidates
+    are the set of keys in the (2 radius + 1)^2 windows around its edges' keys (clipped at the map border; keys outside [0, N) contribute
+    nothing, repeats count once), scored exactly (``score`` = the bits ``graph_attend`` gives the pair); with ``tau`` [B*L] a candidate
+    passes when S - tau_r > 0; with ``k`` > 0 the min(k, passing) best stay, a tie at the last place going to the lower key;
+    ``keep_all``: every candidate stays (the dilated graph; ``k`` is not looked at, edges with margin 0 weigh 0).  ``weight`` is
+    ``graph_attend``'s on the output structure with the same ``tau``, ``scale``, ``normalize``.
+
+    ``max_row_edges``: the largest degree of the input (None = one host read of it); ``max_row_edges * (2 radius + 1)^2`` must not
+    exceed ``graph_refresh_max_candidates()``.  A row longer than declared is never truncated: the call raises ``DaglError`` with
+    ``code == ERR_UNSUPPORTED`` naming the count.  The arrays are allocated at capacity and returned as views of their first E
+    entries; E and the status words come from one host read (not under stream capture).  ``block_rows``: a block per row also where rows
+    are short (for measurements; the same bits).  ``hw``: the map (H, W) -- the windows need it; it may be left out only where L and N
+    fit one map alone.  The same arrays give the same bits on every call."""
+    lib = _lib.load()
+    if hw is None and isinstance(wq_rows, torch.Tensor) and isinstance(x_rows, torch.Tensor) and wq_rows.dim() == 3 and x_rows.dim() == 3:
+        # (the windows need the map itself: L and N alone leave H x W and W x H apart only when one of them does not fit)
+        L, N = wq_rows.shape[1], x_rows.shape[1]
+        maps = [(h, N // h) for h in range(1, N + 1) if N % h == 0 and math.prod(query_grid(h, N // h)) == L]
+        if len(maps) > 1:
+            raise DaglError(f"graph_refresh: {len(maps)} maps have {N} keys and {L} queries ({maps[0][0]}x{maps[0][1]}, "
+                            f"{maps[1][0]}x{maps[1][1]}, ...): pass hw=(H, W)")
+        hw = maps[0] if maps else None
+    B, H, W, E, flags = _graph_attend_operands("graph_refresh", wq_rows, x_rows, row_off, key, tau, normalize, hw)
+    radius, k = int(radius), int(k)
+    if torch.cuda.is_current_stream_capturing():
+        raise DaglError("graph_refresh: not available under stream capture (the edge count is read on the host)")
+    if max_row_edges is None:
+        max_row_edges = int((row_off[1:] - row_off[:-1]).max()) if E > 0 else 0
+    max_row_edges = int(max_row_edges)
+    if keep_all:
+        flags |= _lib.GRAPH_REFRESH_KEEP_ALL
+    if block_rows:
+        flags |= _lib.GRAPH_REFRESH_BLOCK_ROWS
+    dev = wq_rows.device
+    need = lib.dagl_graph_refresh_workspace_bytes(B, H, W, E, radius)
+    if need == 0:
+        check(-1, "dagl_graph_refresh_workspace_bytes")
+    buf, a, nbytes = _region(workspace, need, dev)
+    L = wq_rows.shape[1]
+    cap = E * (2 * radius + 1) ** 2
+    if k > 0 and not keep_all:
+        cap = min(cap, B * L * k)
+    # (the offsets and the two status words in one array: E and the status come from one host read)
+    head = torch.empty(B * L + 3, device=dev, dtype=torch.int64)
+    key_out = torch.empty(cap, device=dev, dtype=torch.int32)
+    weight = torch.empty(cap, device=dev, dtype=torch.float32)
+    score = torch.empty(cap, device=dev, dtype=torch.float32)
+    status = head[B * L + 1:]
+    check(lib.dagl_graph_refresh(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
+                                 max_row_edges, radius, _ptr(tau), k, float(scale), flags, head.data_ptr(), _ptr(key_out, E > 0),
+                                 _ptr(weight, E > 0), _ptr(score, E > 0), cap, status.data_ptr(), a, nbytes), "dagl_graph_refresh")
+    del buf
+    total, overlong, _most = (int(v) for v in head[B * L:].tolist())          # the one synchronisation
+    if overlong:
+        err = DaglError(f"graph_refresh: {overlong} row(s) hold more than max_row_edges = {max_row_edges} edges; they were left empty, "
+                        "not truncated: state the input's largest degree")
+        err.code = _lib.ERR_UNSUPPORTED
+        raise err
+    return dict(row_off=head[:B * L + 1], key=key_out[:total], weight=weight[:total], score=score[:total])
+
+
 @_on_device
 def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,

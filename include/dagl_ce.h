@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists* and dagl_fc_grad16_plan came in without a bump -- no declared signature or struct changed --: a caller that
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh* and dagl_fc_grad16_plan came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -416,6 +416,44 @@ int dagl_graph_from_lists(void* stream, int B, int H, int W, int width, const in
                           const float* nb_s /* may be NULL */, const int32_t* nb_cnt, int64_t* row_off_out /* [B L + 1] */,
                           int32_t* key_out, float* weight_out, float* score_out /* NULL iff nb_s is NULL */, int64_t capacity_edges,
                           void* workspace, size_t ws_bytes);
+
+/* ---- refresh of a patch graph on a new input: csrc/graph_refresh.hip (ABI 412, detected by symbol) -----------------------------------
+ * The structure update that costs O(edges) instead of the L N scan of dagl_ce_graph_*: every query row looks only at the keys in a
+ * (2 radius + 1)^2 window around each of its previous neighbours, scores them exactly, applies the selection rule to them and a new
+ * CSR comes out -- what dagl_graph_attend / dagl_graph_forward / dagl_graph_apply take.  The input structure follows dagl_graph_attend's
+ * rules: keys in any order, repeats, keys outside [0, N) and empty rows are all allowed.
+ *   candidates of row r = b L + i: the SET of keys (y + dy) W + (x + dx), (y, x) = (key_e / W, key_e % W) over the row's edges with key_e in
+ *     [0, N), |dy|, |dx| <= radius, 0 <= y + dy < H, 0 <= x + dx < W (clipped at the border, not wrapped; a key outside [0, N) contributes
+ *     nothing; repeated and overlapping windows give each key once; radius = 0: the row's distinct valid keys), keys of image b
+ *   score S_j = <wq_rows[r], x_rows[b, j]>, the bits dagl_graph_attend gives the same pair; it depends on nothing else of the call
+ *   selection: tau given -> j passes iff S_j - tau_r > 0 (fp32, formed as dagl_graph_attend forms its margin), tau NULL -> all pass;
+ *     k > 0 -> the min(k, passing) passing candidates with the largest S, a tie at the last place to the lower key; k = 0 -> no rank cut.
+ *     (adaptive: tau, k = 0; topk: NULL, k; adaptive_topk: both.)  DAGL_GRAPH_REFRESH_KEEP_ALL: every candidate is kept -- the output
+ *     structure is the dilated graph, k is not looked at, edges with margin 0 weigh 0.
+ *   row_off_out [B L + 1] int64, row_off_out[B L] = E;  key_out / weight_out / score_out [capacity_edges]: entries [0, E), keys strictly
+ *     ascending inside a row, score = the unscaled S, weight = what dagl_graph_attend defines on the OUTPUT structure with the same tau,
+ *     scale and normalisation bit (flags bit 0 = DAGL_GRAPH_ATTEND_EDGES_ONLY; default: the reference's softmax, every key off the graph
+ *     counting as e^0).  Maxima fp32, sums fp64 in a fixed order, no float atomics: the same arrays give the same bits on every call.
+ *   status_out [2] int64 (device): rows longer than max_row_edges -- such a row comes out EMPTY, it is never truncated --, and the largest
+ *     number of distinct candidates a row had.
+ * Limits: 0 <= radius <= 8; max_row_edges (2 radius + 1)^2 <= dagl_graph_refresh_max_candidates() (a compile-time constant >= 2048: 64-key
+ * lists at radius 2), else DAGL_ERR_UNSUPPORTED; total_edges (2 radius + 1)^2 < 2^31; capacity_edges >= what the call may produce --
+ * total_edges (2 radius + 1)^2, or B L k when k > 0 (without KEEP_ALL) and that is smaller --, else DAGL_ERR_WORKSPACE.  Workspace:
+ * dagl_graph_refresh_workspace_bytes = the [B L] degrees + three staging arrays of total_edges (2 radius + 1)^2 entries (row r stages at
+ * row_off[r] (2 radius + 1)^2: no scan places it).  Three launches: a block per row (a wavefront per row when max_row_edges
+ * (2 radius + 1)^2 <= 128; DAGL_GRAPH_REFRESH_BLOCK_ROWS forces the block form, for measurements), the offsets' scan, an ordered copy.
+ * Every argument is checked before the first launch; nothing is read on the host and the call can be captured: the CALLER reads
+ * row_off_out[B L] and status_out.  total_edges = 0 gives an empty graph (key may then be NULL). */
+#define DAGL_GRAPH_REFRESH_KEEP_ALL   0x2
+#define DAGL_GRAPH_REFRESH_BLOCK_ROWS 0x4
+int    dagl_graph_refresh_max_candidates(void);
+size_t dagl_graph_refresh_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius);
+int    dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                          const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau /* NULL: no margin */,
+                          int k /* 0: no rank cut */, float scale, int flags, int64_t* row_off_out /* [B L + 1] */, int32_t* key_out,
+                          float* weight_out, float* score_out, int64_t capacity_edges,
+                          int64_t* status_out /* [2]: rows longer than max_row_edges, largest candidate count met */, void* workspace,
+                          size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

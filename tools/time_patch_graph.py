@@ -4,6 +4,8 @@
     python tools/time_patch_graph.py --apply [H W]  # what ``CE.apply_graph`` costs: forward / graph / apply / apply + backward
     python tools/time_patch_graph.py --attend [H W] # what ``CE.attend_graph`` / ``forward_on_graph`` cost on the same three graphs
     python tools/time_patch_graph.py --lists [H W]  # what ``CE.forward_with_graph`` costs next to forward + graph, same three graphs
+    python tools/time_patch_graph.py --refresh [H W]  # ``CE.refresh_graph`` + ``forward_on_graph`` on a next frame next to ``forward``:
+                                                      # top-k 8 at 256 256; with a size (1024 1024) adaptive AND top-16
 """
 import os
 import sys
@@ -237,7 +239,60 @@ def lists_leg(H, W):
               f"    ops.graph_from_lists alone {fmt(conv)}; forward_with_graph + forward_on_graph(split16) on its graph {fmt(chain)}", flush=True)
 
 
+def refresh_leg(H, W, big):
+    """A sequence step: the graph of one frame moved to the next (``refresh_graph``, radius 1, split-fp16 features) and used
+    (``forward_on_graph(features="split16")``), next to ``forward`` on the next frame -- top-k 8, or (``big``: a size was given)
+    adaptive AND top-16 on the sparse variant of the benchmark's 1024^2 configuration.  The next frame is the input rolled by one
+    pixel each way.  ``ops.graph_refresh`` alone (features given) at radius 0 / 1 / 2, a wavefront and a block per row, and the recall of
+    the refreshed structure against ``graph`` of the next frame."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    x2 = torch.roll(x, (1, 1), (2, 3))
+    name, mode, k, variant, gain = ("adaptive AND top-16 (sparse, gain 1.7)", "adaptive_topk", 16, "sparse", 1.7) if big else \
+        ("top-k 8", "topk", 8, "default", 1.65)
+    prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=gain).items()}
+    ce = CE(in_channels=64)
+    ce.load_state_dict(prm, strict=True)
+    ce.select_mode, ce.select_k = mode, k
+    ce = ce.to(dev).eval()
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    with torch.no_grad():
+        g = ce.graph(x)
+        g.max_degree()
+        full = ce.graph(x2)
+        fwd = _events(lambda: ce(x2))
+        ref = _events(lambda: ce.refresh_graph(x2, g, radius=1, features="split16"))
+        g2 = ce.refresh_graph(x2, g, radius=1, features="split16")
+        fog = _events(lambda: ce.forward_on_graph(x2, g2, features="split16"))
+        chain = _events(lambda: ce.forward_on_graph(x2, ce.refresh_graph(x2, g, radius=1, features="split16"), features="split16"))
+        wq, xk, tau, _, _ = ce._graph_features(x2, mode != "topk", True, False)
+        wq, xk, tau = wq.contiguous(), xk.contiguous(), (tau.contiguous() if tau is not None else None)
+        ws = ops.Workspace()
+        call = dict(tau=tau, k=k, scale=float(ce.softmax_scale), max_row_edges=g.max_degree(), workspace=ws, hw=(H, W))
+        alone, stats = {}, {}
+        full_keys = full.rows() * full.N + full.key.long()
+        for radius in (0, 1, 2):
+            for block in (False, True):
+                alone[(radius, block)] = _events(lambda: ops.graph_refresh(wq, xk, g.row_off, g.key, radius=radius, block_rows=block, **call))
+            r = ce.refresh_graph(x2, g, radius=radius, features="split16")
+            hit = torch.isin(r.rows() * r.N + r.key.long(), full_keys).sum()
+            dil = ops.graph_refresh(wq, xk, g.row_off, g.key, radius=radius, keep_all=True, **call)
+            stats[radius] = (r.n_edges, int(hit) / max(full.n_edges, 1), dil["key"].numel() / g.L)
+    print(f"[1,64,{H},{W}] {name}: graph(x) {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {g.max_degree()}; graph(x2) {full.n_edges} edges\n"
+          f"    forward(x2) {fmt(fwd)}; refresh_graph(x2, graph(x), radius 1, split16) {fmt(ref)}; forward_on_graph(x2, refreshed, split16) "
+          f"{fmt(fog)}; refresh_graph + forward_on_graph {fmt(chain)} = {chain[0] / fwd[0]:.2f} of forward", flush=True)
+    for radius in (0, 1, 2):
+        edges, recall, cands = stats[radius]
+        print(f"    radius {radius}: {cands:.1f} candidates per row, {edges} edges, recall against graph(x2) {recall:.3f}; ops.graph_refresh alone "
+              f"{fmt(alone[(radius, False)])}, a block per row {fmt(alone[(radius, True)])}", flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--refresh":
+        return refresh_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--lists":
         return lists_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     if len(sys.argv) > 1 and sys.argv[1] == "--apply":
