@@ -137,6 +137,9 @@ SIGNATURES = {
     "dagl_ce_prologue": (_i, [_vp, _i, _i, _i] + [_vp] * 14),
     "dagl_ce_prologue16_scratch_bytes": (_sz, [_i, _i, _i]),
     "dagl_ce_prologue16": (_i, [_vp, _i, _i, _i] + [_vp] * 14 + [_sz]),
+    "dagl_ce_prologue16_plan": (_i, [_i] * 4 + [C.POINTER(C.c_int32)]),
+    "dagl_ce_prologue16_debug_scratch_bytes": (_sz, [_i]),
+    "dagl_ce_prologue16_debug": (_i, [_vp, _i, _i, _i, _i] + [C.POINTER(_vp)] * 5 + [C.c_int32, _vp, _sz] + [_vp] * 9 + [_i]),
     "dagl_pad_nhwc": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dagl_pack_fc_weight": (_i, [_vp, _vp, _vp]),
     "dagl_project_patches": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -575,7 +575,7 @@ static int prologue_fused(Call& c) {
             }
             hs.imgs = imgs;
             hs.tiers = tiers_all;
-            if ((rc = launch_conv_pair16_heads(c.s, heads, imgs, g, hs, c.b2p, map_hi, map_lo, clear_stats, clear_stats_words, clear_redo,
+            if ((rc = launch_conv_pair16_heads(c.s, heads, imgs, g, hs, c.b2p, nullptr, map_hi, map_lo, clear_stats, clear_stats_words, clear_redo,
                                                clear_redo_words, c.rt))) return rc;
             if (thr_heads && !c.thr_in_proj && (rc = launch_thr_bias_heads(c.s, heads, imgs, g, c.thr_all, thr_part))) return rc;
         }
@@ -1673,6 +1673,56 @@ int dagl_ce_prologue16(void* stream, int B, int H, int W, const float* x, const 
     pl.tiers.amax = w.amax; pl.tiers.slots = w.slots;   // (slots only: the fp32 map has no tiers; they switch the per-block input scale on)
     pl.b1p = b1_nhwc; pl.b2p = b2_nhwc; pl.thr = thr; pl.bias = bias; pl.thr_part = w.thr_part;
     return launch_prologue(s, pl);
+}
+
+// (detected by symbol) the launch plan of conv_pair16_kernel, by the function its launcher and the carves of its slots plan with
+int dagl_ce_prologue16_plan(int heads, int imgs, int H, int W, int32_t out[4]) {
+    DAGL_REQUIRE(heads >= 1 && heads <= 4 && imgs >= 1 && H >= 1 && W >= 1 && out, "dagl_ce_prologue16_plan: bad argument");
+    const Conv16Plan p = conv16_plan(make_grid(H, W), heads, imgs);
+    out[0] = p.strips; out[1] = p.chunks; out[2] = p.rows_per_block; out[3] = p.slots;
+    return DAGL_OK;
+}
+
+// (detected by symbol) read-out of the inference flavour of conv_pair16_kernel for tests: the launcher of the fused forward on heads x imgs
+// images, every output in the caller's buffers -- the planes, the |b1| slots, the range word and the words the first block clears
+size_t dagl_ce_prologue16_debug_scratch_bytes(int heads) {
+    return heads >= 1 && heads <= 4 ? (size_t)heads * CONV_W16_BYTES : 0;
+}
+
+int dagl_ce_prologue16_debug(void* stream, int heads, int imgs, int H, int W, const float* const* x, const float* const* g_w,
+                             const float* const* g_b, const float* const* theta_w, const float* const* theta_b, int32_t tag,
+                             void* scratch, size_t scratch_bytes, float* b1_nhwc, float* b2_nhwc, uint16_t* b1_hi, uint16_t* b1_lo,
+                             uint16_t* b1_hi2, uint16_t* b1_lo2, float* amax, int32_t* range_word, uint32_t* clear_a, int n) {
+    DAGL_REQUIRE(heads >= 1 && heads <= 4 && imgs >= 1 && H >= 1 && W >= 1, "dagl_ce_prologue16_debug: bad shape (1..4 heads)");
+    DAGL_REQUIRE(x && g_w && g_b && theta_w && theta_b, "dagl_ce_prologue16_debug: null pointer table");
+    for (int h = 0; h < heads; ++h)
+        DAGL_REQUIRE(x[h] && g_w[h] && g_b[h] && theta_w[h] && theta_b[h], "dagl_ce_prologue16_debug: null input of head %d", h);
+    DAGL_REQUIRE(b2_nhwc && b1_hi && b1_lo && amax && range_word, "dagl_ce_prologue16_debug: null output");
+    DAGL_REQUIRE((b1_hi2 == nullptr) == (b1_lo2 == nullptr), "dagl_ce_prologue16_debug: the coarse tier is both planes or neither");
+    DAGL_REQUIRE(tag != 0, "dagl_ce_prologue16_debug: the tag must not be 0");
+    DAGL_REQUIRE(n >= 0 && (n == 0 || clear_a), "dagl_ce_prologue16_debug: %d words to clear, null clear_a", n);
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+    DAGL_REQUIRE(al16(b1_nhwc) && al16(b2_nhwc) && al16(b1_hi) && al16(b1_lo) && al16(b1_hi2) && al16(b1_lo2),
+                 "dagl_ce_prologue16_debug: maps and planes must be 16-byte aligned");
+    int rc;
+    if ((rc = check_workspace("dagl_ce_prologue16_debug", scratch, scratch_bytes, dagl_ce_prologue16_debug_scratch_bytes(heads)))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const Grid g = make_grid(H, W);
+    const int B = heads * imgs;
+    ConvHeadSet hs = {};
+    for (int h = 0; h < heads; ++h) {
+        unsigned char* convw = static_cast<unsigned char*>(scratch) + (size_t)h * CONV_W16_BYTES;
+        if ((rc = launch_pack_conv_weight16(s, g_w[h], theta_w[h], convw))) return rc;
+        hs.x[h] = x[h]; hs.w[h] = convw; hs.gb[h] = g_b[h]; hs.tb[h] = theta_b[h];
+    }
+    hs.imgs = imgs;
+    hs.tiers.hi2 = b1_hi2; hs.tiers.lo2 = b1_lo2; hs.tiers.amax = amax; hs.tiers.slots = conv16_plan(g, heads, imgs).slots;
+    if ((rc = launch_zero_borders(s, B, H, W, b1_nhwc ? b1_nhwc : b2_nhwc, b2_nhwc))) return rc;
+    if ((rc = launch_zero_borders16(s, B, H, W, b1_hi, b1_lo))) return rc;
+    if (b1_hi2 && (rc = launch_zero_borders16(s, B, H, W, b1_hi2, b1_lo2))) return rc;
+    RangeTag range;
+    range.word = range_word; range.tag = tag;
+    return launch_conv_pair16_heads(s, heads, imgs, g, hs, b2_nhwc, b1_nhwc, b1_hi, b1_lo, clear_a, n, nullptr, 0, range);
 }
 
 // ---- the 7x7x16 -> 196 patch Linear (+ReLU) of the differentiable path's FORWARD on the inference kernels: split the map,

@@ -399,13 +399,15 @@ struct B1Tiers {
     int slots = 0;                                          // 4 x conv blocks per head
 };
 struct ConvHeadSet { const float* x[4]; const unsigned char* w[4]; const float* gb[4]; const float* tb[4]; int imgs; B1Tiers tiers; };
+struct Conv16Plan { int strips, chunks, rows_per_block, slots; };   // grid (strips, chunks, heads * imgs) of the g / theta kernels; slots per head
+Conv16Plan conv16_plan(const Grid& g, int heads, int imgs);         // (prologue.hip: the one place the plan is computed)
 int conv16_blocks_per_head(const Grid& g, int heads, int imgs);     // 4 x (grid of conv_pair16_kernel / heads): the slots of B1Tiers::amax per head
 struct ThrHeadSet { const float* x[4]; const float* thr_w[4]; const float* bias_w[4]; int imgs; };     // thr / bias heads likewise
 int launch_thr_bias_heads(hipStream_t s, int heads, int imgs, const Grid& g, const ThrHeadSet& hs,
                           float* thr_part /* per head [4][imgs][L][2] partial sums */);
 int launch_conv_pair16_heads(hipStream_t s, int heads, int imgs, const Grid& g, const ConvHeadSet& hs, float* b2p,
-                             uint16_t* b1_hi, uint16_t* b1_lo, uint32_t* clear_a, int clear_a_words, uint32_t* clear_b,
-                             int clear_b_words, RangeTag range);
+                             float* b1p /* optional fp32 map */, uint16_t* b1_hi, uint16_t* b1_lo, uint32_t* clear_a, int clear_a_words,
+                             uint32_t* clear_b, int clear_b_words, RangeTag range);
 // the four convolutions of one head (prologue.hip).  `conv` names the kernel of the g / theta pair:
 enum class ConvPath {
     Fp32,             // conv_pair_kernel: fp32 maps b1p, b2p (and the fp16 pair b1_hi / b1_lo when given)

@@ -142,7 +142,8 @@ __global__ __launch_bounds__(256) void conv_pair_kernel(int H, int W, int rows_p
 }
 
 // ---- the same two convolutions on the fp16 matrix cores with split operands (default path) ---------------------------
-// 16 x = hi + lo and 256 w = hi + lo (fp16 pairs, power-of-two pre-scaling keeps the lo parts normal; see project16.hip);
+// 16 x = hi + lo and 256 w = hi + lo (fp16 pairs; the power-of-two pre-scaling keeps the lo parts normal for |x| >~ 8e-3 and |w| >~ 5e-4 -- below, the lo halves are
+// fp16 subnormals, below |x| ~ 4e-6 the hi halves too: an absolute floor of 2^-25 / scale per operand; see project16.hip);
 // a product keeps hi*hi + hi*lo + lo*hi in ONE fp32 accumulator.  v_mfma_f32_16x16x32_f16 with A = weights (M = 16 output
 // channels) and B = pixels (N = 16 consecutive pixels of a row), K = 32 input channels of one tap: 3 x 3 x 2 K-blocks for
 // g, 2 for theta, three MFMAs each: 960 matrix-core cycles per 16 pixels against 5120 of the fp32 kernel above, and no
@@ -453,16 +454,25 @@ __global__ __launch_bounds__(256) void conv_pair16_kernel(int H, int W, int rows
     dbg_stamp(times, blin, 3);
 }
 
-int conv16_blocks_per_head(const Grid& g, int heads, int imgs) {
+// The launch plan of the g / theta pair (both kernels): grid (strips, chunks, heads * imgs), rows_per_block rows per block.  One block per
+// CU over the whole launch (1 block/CU resident: 332 registers), at least 2 rows per block (H = 1: one); no block is empty.  slots: what
+// B1Tiers::amax holds per head, one per wave of every block of that head -- the grid that writes the slots and the carve that sizes them
+// read this one function (dagl_ce_prologue16_plan reports it).
+Conv16Plan conv16_plan(const Grid& g, int heads, int imgs) {
     const int B = heads * imgs;
-    const int strips = (g.W + PRO_TW - 1) / PRO_TW;
-    int chunks = (256 + strips * B - 1) / (strips * B);
+    Conv16Plan p;
+    p.strips = (g.W + PRO_TW - 1) / PRO_TW;
+    constexpr int target = 256;
+    int chunks = (target + p.strips * B - 1) / (p.strips * B);
     if (chunks > (g.H + 1) / 2) chunks = (g.H + 1) / 2;
     if (chunks < 1) chunks = 1;
-    const int rows_per_block = (g.H + chunks - 1) / chunks;
-    chunks = (g.H + rows_per_block - 1) / rows_per_block;
-    return strips * chunks * imgs * 4;                      // (a slot per wave of every block)
+    p.rows_per_block = (g.H + chunks - 1) / chunks;
+    p.chunks = (g.H + p.rows_per_block - 1) / p.rows_per_block;
+    p.slots = p.strips * p.chunks * imgs * 4;
+    return p;
 }
+
+int conv16_blocks_per_head(const Grid& g, int heads, int imgs) { return conv16_plan(g, heads, imgs).slots; }
 
 // thr / bias heads (two 7x7 stride-4 convolutions 64 -> 1 over the SAME-padded input, dagl.py:212-215).
 // One block per (image, query row, 32 queries, 16-channel group): the 7 input rows the queries need are staged in LDS
@@ -564,26 +574,25 @@ __global__ void thr_bias_reduce_kernel(size_t n /* B*L */, const float* __restri
     bias[i] = ((p0.y + p1.y) + (p2.y + p3.y)) + bias_b[0];
 }
 
-int launch_conv_pair16_heads(hipStream_t s, int heads, int imgs, const Grid& g, const ConvHeadSet& hs, float* b2p,
+// the one launch site of conv_pair16_kernel (b1p: the optional fp32 copy of the key / query map; b1_hi / b1_lo may then be null)
+int launch_conv_pair16_heads(hipStream_t s, int heads, int imgs, const Grid& g, const ConvHeadSet& hs, float* b2p, float* b1p,
                              uint16_t* b1_hi, uint16_t* b1_lo, uint32_t* clear_a, int clear_a_words, uint32_t* clear_b,
                              int clear_b_words, RangeTag range) {
     const int B = heads * imgs;
-    const int strips = (g.W + PRO_TW - 1) / PRO_TW;
-    constexpr int target = 256;                       // one block per CU over the whole launch, at least 2 rows per block
-    int chunks = (target + strips * B - 1) / (strips * B);
-    if (chunks > (g.H + 1) / 2) chunks = (g.H + 1) / 2;
-    if (chunks < 1) chunks = 1;
-    const int rows_per_block = (g.H + chunks - 1) / chunks;
-    chunks = (g.H + rows_per_block - 1) / rows_per_block;
+    const Conv16Plan p = conv16_plan(g, heads, imgs);
+    if (hs.tiers.amax != nullptr && hs.tiers.slots != p.slots) {
+        set_error("launch_conv_pair16_heads: %d |b1| slots per head, the grid writes %d", hs.tiers.slots, p.slots);
+        return DAGL_ERR_INVALID;
+    }
     unsigned long long* times = nullptr;
 #ifdef DAGL_ABLATION
-    if (getenv("DAGL_TIMES_FILE")) times = dbg_times_buffer((size_t)strips * chunks * B);
+    if (getenv("DAGL_TIMES_FILE")) times = dbg_times_buffer((size_t)p.strips * p.chunks * B);
 #endif
-    hipLaunchKernelGGL(conv_pair16_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, hs,
-                       b2p, (float*)nullptr, b1_hi, b1_lo, clear_a, clear_a_words, clear_b, clear_b_words, range, times);
+    hipLaunchKernelGGL(conv_pair16_kernel, dim3(p.strips, p.chunks, B), dim3(256), 0, s, g.H, g.W, p.rows_per_block, hs,
+                       b2p, b1p, b1_hi, b1_lo, clear_a, clear_a_words, clear_b, clear_b_words, range, times);
     DAGL_LAUNCH_CHECK("conv_pair16_kernel");
 #ifdef DAGL_ABLATION
-    if (times) dbg_times_dump(s, "conv_pair16_kernel", times, (size_t)strips * chunks * B);
+    if (times) dbg_times_dump(s, "conv_pair16_kernel", times, (size_t)p.strips * p.chunks * B);
 #endif
     return DAGL_OK;
 }
@@ -609,32 +618,17 @@ int launch_prologue(hipStream_t s, const PrologueLaunch& a) {
         if (b1_hi != nullptr && (rcz = launch_zero_borders16(s, B, g.H, g.W, b1_hi, b1_lo))) return rcz;
         if (b1_hi != nullptr && a.tiers.hi2 != nullptr && (rcz = launch_zero_borders16(s, B, g.H, g.W, a.tiers.hi2, a.tiers.lo2))) return rcz;
     }
-    const int strips = (g.W + PRO_TW - 1) / PRO_TW;
-    // one block per CU over the whole launch (1 block/CU resident: 332 registers), at least 2 rows per block
-    constexpr int target = 256;
-    int chunks = (target + strips * B - 1) / (strips * B);
-    if (chunks > (g.H + 1) / 2) chunks = (g.H + 1) / 2;
-    if (chunks < 1) chunks = 1;
-    const int rows_per_block = (g.H + chunks - 1) / chunks;
-    chunks = (g.H + rows_per_block - 1) / rows_per_block;
     if (a.conv == ConvPath::Split16) {
         // (with b1p: the differentiable path's forward -- an fp32 map out, the fp16 pairs optional)
         if (a.conv_w16 == nullptr) { set_error("launch_prologue: the split-fp16 convolutions need their packed weights"); return DAGL_ERR_INVALID; }
         ConvHeadSet hs = {};
         hs.x[0] = a.x; hs.w[0] = a.conv_w16; hs.gb[0] = a.g_b; hs.tb[0] = a.th_b; hs.imgs = B;
         hs.tiers = a.tiers;
-        unsigned long long* times = nullptr;
-#ifdef DAGL_ABLATION
-        if (getenv("DAGL_TIMES_FILE")) times = dbg_times_buffer((size_t)strips * chunks * B);
-#endif
-        hipLaunchKernelGGL(conv_pair16_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, hs,
-                           b2p, b1p, b1_hi, b1_lo, a.clear_a, a.clear_a_words, a.clear_b, a.clear_b_words, a.range, times);
-        DAGL_LAUNCH_CHECK("conv_pair16_kernel");
-#ifdef DAGL_ABLATION
-        if (times) dbg_times_dump(s, "conv_pair16_kernel", times, (size_t)strips * chunks * B);
-#endif
+        if ((rcz = launch_conv_pair16_heads(s, 1, B, g, hs, b2p, b1p, b1_hi, b1_lo, a.clear_a, a.clear_a_words, a.clear_b, a.clear_b_words,
+                                            a.range))) return rcz;
     } else if (a.conv == ConvPath::Fp32) {
-        hipLaunchKernelGGL(conv_pair_kernel, dim3(strips, chunks, B), dim3(256), 0, s, g.H, g.W, rows_per_block, a.x, a.g_w,
+        const Conv16Plan p = conv16_plan(g, 1, B);
+        hipLaunchKernelGGL(conv_pair_kernel, dim3(p.strips, p.chunks, B), dim3(256), 0, s, g.H, g.W, p.rows_per_block, a.x, a.g_w,
                            a.g_b, a.th_w, a.th_b, b1p, b2p, b1_hi, b1_lo);
         DAGL_LAUNCH_CHECK("conv_pair_kernel");
     }

@@ -841,6 +841,54 @@ def ce_prologue(x, g_w, g_b, theta_w, theta_b, thr_w=None, thr_b=None, bias_w=No
     return b1p, b2p, thr, bias
 
 
+def ce_prologue16_plan(heads: int, imgs: int, H: int, W: int) -> dict:
+    """The launch plan of ``conv_pair16_kernel`` on ``heads`` x ``imgs`` images of [H, W] (``dagl_ce_prologue16_plan``, host only), by the
+    function the launcher and the workspace carves plan with: ``strips`` of 64 columns, row ``chunks``, ``rows`` per block and ``slots``
+    of |b1| maxima per head (4 waves x strips x chunks x imgs); the grid is (strips, chunks, heads * imgs)."""
+    out = (C.c_int32 * 4)()
+    check(_lib.load().dagl_ce_prologue16_plan(int(heads), int(imgs), int(H), int(W), out), "dagl_ce_prologue16_plan")
+    return dict(zip(("strips", "chunks", "rows", "slots"), (int(v) for v in out)))
+
+
+@_on_device
+def ce_prologue16_debug(xs, g_w, g_b, theta_w, theta_b, tag: int = 1, range_init: int = 0, n_clear: int = 8, want_b1: bool = True,
+                        coarse: bool = True) -> dict:
+    """The inference flavour of the split-fp16 g / theta kernel with every output read out (``dagl_ce_prologue16_debug``, for tests).
+    ``xs``, ``g_w`` ...: lists of one tensor per head (1..4), ``xs[h]`` [imgs,64,H,W].  Every buffer is poisoned before the call: NaN in
+    the fp32 maps and the slots, 0x7e00 in the planes, 0xff in the scratch and the ``n_clear`` words, ``range_init`` in the range word.
+    -> dict(b1, b2 [heads*imgs,H+6,W+6,16] fp32 (b1 None without ``want_b1``), hi, lo, hi2, lo2 (int16 bits; the coarse pair None without
+    ``coarse``), amax [heads, slots], range (int32 [1]), clear (int32 [n_clear]))."""
+    lib = _lib.load()
+    heads = len(xs)
+    if not (1 <= heads <= 4 and len(g_w) == len(g_b) == len(theta_w) == len(theta_b) == heads):
+        raise DaglError("ce_prologue16_debug: 1..4 heads, one tensor of each kind per head")
+    for h in range(heads):
+        for n, t in (("x", xs[h]), ("g_w", g_w[h]), ("g_b", g_b[h]), ("theta_w", theta_w[h]), ("theta_b", theta_b[h])):
+            _need(t, f"{n}[{h}]")
+        if xs[h].shape != xs[0].shape or xs[h].dim() != 4 or xs[h].shape[1] != 64:
+            raise DaglError("ce_prologue16_debug: every head's input is [imgs,64,H,W]")
+    imgs, _, H, W = xs[0].shape
+    dev = xs[0].device
+    B = heads * imgs
+    slots = ce_prologue16_plan(heads, imgs, H, W)["slots"]
+    fmap = lambda: torch.full((B, H + 6, W + 6, 16), float("nan"), device=dev, dtype=torch.float32)
+    plane = lambda: torch.full((B, H + 6, W + 6, 16), 0x7e00, device=dev, dtype=torch.int16)
+    out = dict(b1=fmap() if want_b1 else None, b2=fmap(), hi=plane(), lo=plane(), hi2=plane() if coarse else None,
+               lo2=plane() if coarse else None, amax=torch.full((heads, slots), float("nan"), device=dev, dtype=torch.float32),
+               range=torch.full((1,), int(range_init), device=dev, dtype=torch.int32),
+               clear=torch.full((max(int(n_clear), 1),), -1, device=dev, dtype=torch.int32)[:int(n_clear)])
+    need = lib.dagl_ce_prologue16_debug_scratch_bytes(heads)
+    scratch, base = _scratch(need, dev)
+    scratch.fill_(0xff)
+    table = lambda ts: (C.c_void_p * heads)(*[t.data_ptr() for t in ts])
+    check(lib.dagl_ce_prologue16_debug(_stream(), heads, imgs, H, W, table(xs), table(g_w), table(g_b), table(theta_w), table(theta_b),
+                                       int(tag), base, need, _ptr(out["b1"]), out["b2"].data_ptr(), out["hi"].data_ptr(),
+                                       out["lo"].data_ptr(), _ptr(out["hi2"]), _ptr(out["lo2"]), out["amax"].data_ptr(),
+                                       out["range"].data_ptr(), out["clear"].data_ptr() if n_clear else None, int(n_clear)),
+          "dagl_ce_prologue16_debug")
+    return out
+
+
 @_on_device
 def ce_forward_fused(x, params: dict, mode: str = "adaptive", k: int = 0, workspace: "Workspace | None" = None,
                      profile: "StageProfile | None" = None, exact_scan: bool = False, weights_packed: bool = False,

@@ -170,7 +170,8 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh* and dagl_fc_grad16_plan came in without a bump -- no declared signature or struct changed --: a caller that
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_fc_grad16_plan,
+ * dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -672,6 +673,27 @@ int dagl_ce_prologue16(void* stream, int B, int H, int W, const float* x,
                        const float* g_w, const float* g_b, const float* theta_w, const float* theta_b,
                        const float* thr_w, const float* thr_b, const float* bias_w, const float* bias_b,
                        float* b1_nhwc, float* b2_nhwc, float* thr, float* bias, void* scratch, size_t scratch_bytes);
+
+/* (detected by symbol) Read-outs for tests of the split-fp16 g / theta kernel (csrc/prologue.hip, conv_pair16_kernel).
+ * dagl_ce_prologue16_plan: the launch plan of one call on heads (1..4) x imgs images of [H, W], computed on the host by the function the
+ * launcher and the workspace carves plan with:  out = { strips of 64 columns, row chunks, rows per block, |b1| slots per head
+ * (= 4 waves x strips x chunks x imgs) }; the grid is (strips, chunks, heads * imgs).
+ * dagl_ce_prologue16_debug: the inference flavour of the kernel, through the fused forward's launcher, with every output in the caller's
+ * buffers.  x, g_w, g_b, theta_w, theta_b: HOST arrays of `heads` device pointers (x[h]: [imgs,64,H,W]); batch index b = h * imgs + image.
+ *   tag         != 0: written to *range_word when the call leaves the split-fp16 range (else the word keeps what the caller put there)
+ *   scratch     256-byte aligned, dagl_ce_prologue16_debug_scratch_bytes(heads) bytes (the heads' packed weights)
+ *   b1_nhwc     [heads*imgs, H+6, W+6, 16] fp32 key / query map, or NULL;  b2_nhwc likewise (required)
+ *   b1_hi/b1_lo [heads*imgs, H+6, W+6, 16] fp16 bits, 16 b1 = hi + lo;  b1_hi2 / b1_lo2: 2^-8 b1 = hi2 + lo2, both or neither
+ *   amax        [heads][slots] floats: largest |b1| of every wave of every block (+inf for a non-finite value), slot
+ *               ((image * chunks + chunk) * strips + strip) * 4 + wave of its head
+ *   clear_a     n 32-bit words the first block zeroes (the fused forward's per-call counters), or NULL with n = 0
+ * The 3-pixel borders of all maps are zeroed by the launchers the forward uses.                                                      */
+int    dagl_ce_prologue16_plan(int heads, int imgs, int H, int W, int32_t out[4]);
+size_t dagl_ce_prologue16_debug_scratch_bytes(int heads);
+int    dagl_ce_prologue16_debug(void* stream, int heads, int imgs, int H, int W, const float* const* x, const float* const* g_w,
+                                const float* const* g_b, const float* const* theta_w, const float* const* theta_b, int32_t tag,
+                                void* scratch, size_t scratch_bytes, float* b1_nhwc, float* b2_nhwc, uint16_t* b1_hi, uint16_t* b1_lo,
+                                uint16_t* b1_hi2, uint16_t* b1_lo2, float* amax, int32_t* range_word, uint32_t* clear_a, int n);
 
 /* NCHW [B,16,H,W] -> zero-bordered NHWC [B,H+6,W+6,16]  (patch unfold without materialising
  * patches: replaces same_padding/extract_image_patches, dagl.py:123-169, for all three uses).    */
