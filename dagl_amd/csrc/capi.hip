@@ -1933,132 +1933,7 @@ int dagl_ce_graph_fill(void* stream, int B, int H, int W, int mode, int k, int r
     return launch_graph_fill((hipStream_t)stream, p, row_off, key_out, weight_out, score_out, (long long)capacity_edges, workspace);
 }
 
-// (ABI 409) a block run on a given patch graph: csrc/graph_apply.hip
-int dagl_graph_apply_segment(void) { return graph_apply_segment(); }
-
-// shape and edge count of both calls; 0 = refused (dagl_last_error says why)
-static int graph_apply_shape_ok(const char* who, int B, int H, int W, int64_t total_edges) {
-    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    DAGL_REQUIRE((int64_t)B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
-    DAGL_REQUIRE(total_edges >= 0 && total_edges < (1ll << 31), "%s: total_edges=%lld outside [0, 2^31)", who, (long long)total_edges);
-    return DAGL_OK;
-}
-
-static size_t graph_apply_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
-    if (graph_apply_shape_ok(who, B, H, W, total_edges)) return 0;
-    return graph_apply_workspace_bytes(B, make_grid(H, W), total_edges, backward);
-}
-
-size_t dagl_graph_apply_workspace_bytes(int B, int H, int W, int64_t total_edges) {
-    return graph_apply_bytes("dagl_graph_apply_workspace_bytes", B, H, W, total_edges, false);
-}
-
-size_t dagl_graph_apply_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
-    return graph_apply_bytes("dagl_graph_apply_backward_workspace_bytes", B, H, W, total_edges, true);
-}
-
-int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
-                     int64_t total_edges, float* out, void* workspace, size_t ws_bytes) {
-    int rc = graph_apply_shape_ok("dagl_graph_apply", B, H, W, total_edges);
-    if (rc) return rc;
-    DAGL_REQUIRE(b2p && row_off && out && (total_edges == 0 || (key && weight)), "dagl_graph_apply: null tensor pointer");
-    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_apply: b2p must be 16-byte aligned");
-    const Grid g = make_grid(H, W);
-    if ((rc = check_workspace("dagl_graph_apply", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, false)))) return rc;
-    return launch_graph_apply((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, out, workspace);
-}
-
-int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key,
-                              const float* weight, int64_t total_edges, const float* d_out, const int64_t* col_off,
-                              const int32_t* src_row, const int32_t* perm, float* d_b2p, float* d_weight, void* workspace,
-                              size_t ws_bytes) {
-    int rc = graph_apply_shape_ok("dagl_graph_apply_backward", B, H, W, total_edges);
-    if (rc) return rc;
-    DAGL_REQUIRE(b2p && row_off && d_out && (total_edges == 0 || (key && weight)), "dagl_graph_apply_backward: null tensor pointer");
-    DAGL_REQUIRE(d_b2p == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
-                 "dagl_graph_apply_backward: null transposed CSR (col_off, src_row, perm are required with d_b2p)");
-    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0 && ((uintptr_t)d_b2p % 16) == 0, "dagl_graph_apply_backward: maps must be 16-byte aligned");
-    const Grid g = make_grid(H, W);
-    if ((rc = check_workspace("dagl_graph_apply_backward", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, true)))) return rc;
-    return launch_graph_apply_backward((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, d_out, col_off, src_row, perm,
-                                       d_b2p, d_weight, workspace);
-}
-
-// (ABI 412) attention on a given patch graph: csrc/graph_attend.hip
-static size_t graph_attend_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
-    if (graph_apply_shape_ok(who, B, H, W, total_edges)) return 0;
-    return graph_attend_workspace_bytes(B, make_grid(H, W), total_edges, backward);
-}
-
-size_t dagl_graph_attend_workspace_bytes(int B, int H, int W, int64_t total_edges) {
-    return graph_attend_bytes("dagl_graph_attend_workspace_bytes", B, H, W, total_edges, false);
-}
-
-size_t dagl_graph_attend_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
-    return graph_attend_bytes("dagl_graph_attend_backward_workspace_bytes", B, H, W, total_edges, true);
-}
-
-// what both calls ask of their shared arguments
-static int graph_attend_operands_ok(const char* who, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
-                                    const int32_t* key, int64_t total_edges, float scale, int flags) {
-    const int rc = graph_apply_shape_ok(who, B, H, W, total_edges);
-    if (rc) return rc;
-    DAGL_REQUIRE(wq_rows && x_rows && row_off && (total_edges == 0 || key), "%s: null tensor pointer", who);
-    DAGL_REQUIRE(((uintptr_t)wq_rows % 16) == 0 && ((uintptr_t)x_rows % 16) == 0, "%s: feature rows must be 16-byte aligned", who);
-    DAGL_REQUIRE((flags & ~DAGL_GRAPH_ATTEND_EDGES_ONLY) == 0, "%s: unknown flags 0x%x", who, flags);
-    DAGL_REQUIRE(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
-    return DAGL_OK;
-}
-
-int dagl_graph_attend(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
-                      const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, float* score, float* weight,
-                      void* workspace, size_t ws_bytes) {
-    int rc = graph_attend_operands_ok("dagl_graph_attend", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
-    if (rc) return rc;
-    DAGL_REQUIRE(total_edges == 0 || (score && weight), "dagl_graph_attend: null tensor pointer");
-    const Grid g = make_grid(H, W);
-    if ((rc = check_workspace("dagl_graph_attend", workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, false)))) return rc;
-    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
-    return launch_graph_attend((hipStream_t)stream, B, g, c, score, weight, workspace);
-}
-
-int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
-                               const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, const float* score,
-                               const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
-                               const int32_t* perm, float* d_wq_rows, float* d_x_rows, float* d_tau, void* workspace, size_t ws_bytes) {
-    int rc = graph_attend_operands_ok("dagl_graph_attend_backward", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
-    if (rc) return rc;
-    DAGL_REQUIRE(total_edges == 0 || (score && weight && d_weight), "dagl_graph_attend_backward: null tensor pointer");
-    DAGL_REQUIRE(d_x_rows == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
-                 "dagl_graph_attend_backward: null transposed CSR (col_off, src_row, perm are required with d_x_rows)");
-    DAGL_REQUIRE(d_tau == nullptr || tau != nullptr, "dagl_graph_attend_backward: d_tau asked for without tau");
-    DAGL_REQUIRE(((uintptr_t)d_wq_rows % 16) == 0 && ((uintptr_t)d_x_rows % 16) == 0,
-                 "dagl_graph_attend_backward: gradient rows must be 16-byte aligned");
-    const Grid g = make_grid(H, W);
-    if ((rc = check_workspace("dagl_graph_attend_backward", workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, true))))
-        return rc;
-    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
-    return launch_graph_attend_backward((hipStream_t)stream, B, g, c, score, weight, d_weight, col_off, src_row, perm, d_wq_rows, d_x_rows,
-                                        d_tau, workspace);
-}
-
-// the fused forward on a given patch graph: csrc/graph_forward.hip (no ABI bump: found by symbol)
-size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
-    if (graph_apply_shape_ok("dagl_graph_forward_workspace_bytes", B, H, W, total_edges)) return 0;
-    return graph_forward_workspace_bytes(B, make_grid(H, W), total_edges);
-}
-
-int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
-                       const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags,
-                       float* out, void* workspace, size_t ws_bytes) {
-    int rc = graph_attend_operands_ok("dagl_graph_forward", B, H, W, wq_rows, x_rows, row_off, key, total_edges, scale, flags);
-    if (rc) return rc;
-    DAGL_REQUIRE(b2p && out, "dagl_graph_forward: null tensor pointer");
-    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_forward: b2p must be 16-byte aligned");
-    const Grid g = make_grid(H, W);
-    if ((rc = check_workspace("dagl_graph_forward", workspace, ws_bytes, graph_forward_workspace_bytes(B, g, total_edges)))) return rc;
-    const GraphAttendCall c{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
-    return launch_graph_forward((hipStream_t)stream, B, g, c, b2p, out, workspace);
-}
+// the routes on a GIVEN patch graph (dagl_graph_apply*, _attend*, _forward*, _refresh*, _from_lists*) have their entries beside their
+// kernels: csrc/graph_apply.hip, graph_attend.hip, graph_forward.hip, graph_refresh.hip, graph_lists.hip
 
 }  // extern "C"

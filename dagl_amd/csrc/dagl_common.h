@@ -900,30 +900,4 @@ int launch_graph_count(hipStream_t s, const GraphPlan& p, const float* b1, const
 int launch_graph_fill(hipStream_t s, const GraphPlan& p, const int64_t* row_off, int32_t* key, float* weight, float* score /* or null */,
                       long long capacity, void* ws);
 
-// a block run on a given patch graph (graph_apply.hip; ABI 409): workspace = whole bytes of the forward / backward call
-int graph_apply_segment();
-size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward);
-int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
-                       const float* weight, int64_t E, float* out, void* workspace);
-int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
-                                const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
-                                const int32_t* perm, float* d_b2p /* or null */, float* d_weight /* or null */, void* workspace);
-
-// attention on a given patch graph (graph_attend.hip; ABI 412): what the forward and the backward call share
-struct GraphAttendCall {
-    const float* wq_rows; const float* x_rows;             // [B L, 196], [B N, 196]
-    const int64_t* row_off; const int32_t* key; int64_t E;
-    const float* tau;                                      // [B L] or null: no margin
-    float scale; bool edges_only;
-};
-size_t graph_attend_workspace_bytes(int B, const Grid& g, int64_t E, bool backward);
-int launch_graph_attend(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, float* score, float* weight, void* workspace);
-int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* score, const float* weight,
-                                 const float* d_weight, const int64_t* col_off, const int32_t* src_row, const int32_t* perm,
-                                 float* d_wq_rows /* or null */, float* d_x_rows /* or null */, float* d_tau /* or null */, void* workspace);
-
-// both in one crossing of the edges (graph_forward.hip): out = graph_apply(weight = graph_attend(c)), score / weight never stored
-size_t graph_forward_workspace_bytes(int B, const Grid& g, int64_t E);
-int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace);
-
 }  // namespace dagl

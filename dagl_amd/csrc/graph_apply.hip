@@ -31,8 +31,7 @@ __global__ __launch_bounds__(256) void graph_apply_segment_kernel(GaArgs a) {
     __shared__ float sh_w[GA_SEG];
     __shared__ int sh_row[GA_SEG];
     const int t = threadIdx.x;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     if (t < m) {
         const long long p = p0 + t;
         const int row = ga_row_of(a.row_off, a.n_rows, p);
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(256) void graph_apply_combine_kernel(const int64_t*
     __shared__ float4 sh[4][GA_C4];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     long long lo = row_off[blockIdx.x], hi = row_off[blockIdx.x + 1];
-    lo = lo < 0 ? 0 : (lo > E ? E : lo);
+    lo = lo < 0 ? 0 : (lo > E ? E : lo);                       // (gt_clamp, written out: called from graph_rows.h this kernel's device code changes)
     hi = hi < 0 ? 0 : (hi > E ? E : hi);
     float4* o = reinterpret_cast<float4*>(out + (size_t)blockIdx.x * P);
     if (hi <= lo) {
@@ -131,8 +130,7 @@ __global__ __launch_bounds__(256) void graph_apply_dweight_kernel(GaArgs a, cons
     __shared__ long long sh_of[GA_SEG];
     __shared__ int sh_row[GA_SEG];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     if (t < m) {
         const int row = ga_row_of(a.row_off, a.n_rows, p0 + t);
         sh_of[t] = ga_source<true>(a, row, a.key[p0 + t]);
@@ -174,10 +172,6 @@ __global__ __launch_bounds__(256) void graph_apply_dweight_kernel(GaArgs a, cons
     }
 }
 
-int graph_apply_segment() { return GA_SEG; }
-
-static size_t ga_chunks(int64_t E) { return (size_t)((E + GA_SEG - 1) / GA_SEG); }
-
 // forward: agg [B L, 784] + the chunks' partial rows;  backward: dAgg [B L, 784] + d V rows [B N, 784] + partial rows.  The one
 // walk behind the size (null base) and both launches
 struct GaWs { float* agg; float* dv; float* part; size_t bytes; };
@@ -190,15 +184,7 @@ static GaWs ga_carve(void* ws, int B, const Grid& g, int64_t E, bool backward) {
     w.bytes = cv.bytes();
     return w;
 }
-size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) { return ga_carve(nullptr, B, g, E, backward).bytes; }
-
-static GaArgs ga_map_args(int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
-                          int64_t E) {
-    GaArgs a{};
-    a.row_off = row_off; a.n_rows = B * g.L; a.key = key; a.weight = weight; a.perm = nullptr; a.E = E;
-    a.src = b2p; a.n_src = g.N; a.L = g.L; a.W = g.W; a.Wp = g.Wp; a.img4 = (long long)g.Hp * g.Wp * (CH / 4);
-    return a;
-}
+static size_t graph_apply_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) { return ga_carve(nullptr, B, g, E, backward).bytes; }
 
 template <bool MAP>
 static int ga_product(hipStream_t s, GaArgs a) {
@@ -211,8 +197,8 @@ static int ga_product(hipStream_t s, GaArgs a) {
     return DAGL_OK;
 }
 
-int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
-                       const float* weight, int64_t E, float* out, void* workspace) {
+static int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
+                              const float* weight, int64_t E, float* out, void* workspace) {
     const GaWs w = ga_carve(workspace, B, g, E, false);
     GaArgs a = ga_map_args(B, g, b2p, row_off, key, weight, E);
     a.out = w.agg; a.part = w.part;
@@ -221,9 +207,9 @@ int launch_graph_apply(hipStream_t s, int B, const Grid& g, const float* b2p, co
     return launch_fold(s, B, g, a.out, out);
 }
 
-int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
-                                const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
-                                const int32_t* perm, float* d_b2p, float* d_weight, void* workspace) {
+static int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float* b2p, const int64_t* row_off, const int32_t* key,
+                                       const float* weight, int64_t E, const float* d_out, const int64_t* col_off, const int32_t* src_row,
+                                       const int32_t* perm, float* d_b2p /* or null */, float* d_weight /* or null */, void* workspace) {
     const GaWs w = ga_carve(workspace, B, g, E, true);
     float *dagg = w.agg, *dv = w.dv, *part = w.part;
     int rc = launch_unfold_dout(s, B, g, d_out, dagg);
@@ -246,4 +232,53 @@ int launch_graph_apply_backward(hipStream_t s, int B, const Grid& g, const float
     return DAGL_OK;
 }
 
+static size_t graph_apply_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
+    if (graph_shape_ok(who, B, H, W, total_edges)) return 0;
+    return graph_apply_workspace_bytes(B, make_grid(H, W), total_edges, backward);
+}
+
 }  // namespace dagl
+
+using namespace dagl;
+
+extern "C" {
+
+// (ABI 409) a block run on a given patch graph; workspace = whole bytes of the forward / backward call
+int dagl_graph_apply_segment(void) { return GA_SEG; }
+
+size_t dagl_graph_apply_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_apply_bytes("dagl_graph_apply_workspace_bytes", B, H, W, total_edges, false);
+}
+
+size_t dagl_graph_apply_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_apply_bytes("dagl_graph_apply_backward_workspace_bytes", B, H, W, total_edges, true);
+}
+
+int dagl_graph_apply(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key, const float* weight,
+                     int64_t total_edges, float* out, void* workspace, size_t ws_bytes) {
+    int rc = graph_shape_ok("dagl_graph_apply", B, H, W, total_edges);
+    if (rc) return rc;
+    DAGL_REQUIRE(b2p && row_off && out && (total_edges == 0 || (key && weight)), "dagl_graph_apply: null tensor pointer");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_apply: b2p must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace("dagl_graph_apply", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, false)))) return rc;
+    return launch_graph_apply((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, out, workspace);
+}
+
+int dagl_graph_apply_backward(void* stream, int B, int H, int W, const float* b2p, const int64_t* row_off, const int32_t* key,
+                              const float* weight, int64_t total_edges, const float* d_out, const int64_t* col_off,
+                              const int32_t* src_row, const int32_t* perm, float* d_b2p, float* d_weight, void* workspace,
+                              size_t ws_bytes) {
+    int rc = graph_shape_ok("dagl_graph_apply_backward", B, H, W, total_edges);
+    if (rc) return rc;
+    DAGL_REQUIRE(b2p && row_off && d_out && (total_edges == 0 || (key && weight)), "dagl_graph_apply_backward: null tensor pointer");
+    DAGL_REQUIRE(d_b2p == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
+                 "dagl_graph_apply_backward: null transposed CSR (col_off, src_row, perm are required with d_b2p)");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0 && ((uintptr_t)d_b2p % 16) == 0, "dagl_graph_apply_backward: maps must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace("dagl_graph_apply_backward", workspace, ws_bytes, graph_apply_workspace_bytes(B, g, total_edges, true)))) return rc;
+    return launch_graph_apply_backward((hipStream_t)stream, B, g, b2p, row_off, key, weight, total_edges, d_out, col_off, src_row, perm,
+                                       d_b2p, d_weight, workspace);
+}
+
+}  // extern "C"

@@ -25,8 +25,6 @@
 
 namespace dagl {
 
-constexpr int GT_BATCH = 8;                   // gathers in flight per thread of the products
-
 // ---- forward ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void graph_attend_score_kernel(GtArgs a, float* __restrict__ score, int32_t* __restrict__ row_of,
                                                                   float* __restrict__ row_max, double* __restrict__ row_sum,
@@ -35,13 +33,12 @@ __global__ __launch_bounds__(256) void graph_attend_score_kernel(GtArgs a, float
     __shared__ int sh_row[GA_SEG];
     __shared__ float sh_z[GA_SEG];
     const int t = threadIdx.x;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     if (t < m) {
         const int row = ga_row_of(a.row_off, a.n_rows, p0 + t);
         const int key = a.key[p0 + t];
         sh_row[t] = row;
-        sh_x[t] = (unsigned)key < (unsigned)a.N ? ((long long)(row / a.L) * a.N + key) * GT_C4 : -1;
+        sh_x[t] = gt_feature_row(a.L, a.N, row, key);
         row_of[p0 + t] = row;
     }
     __syncthreads();
@@ -61,21 +58,11 @@ __global__ __launch_bounds__(256) void graph_attend_score_kernel(GtArgs a, float
         }
     }
     __syncthreads();
-    // one (max, sum) per run of equal row, by the thread of the run's first edge, in edge order
-    if (t < m && (t == 0 || sh_row[t - 1] != sh_row[t])) {
-        const int row = sh_row[t];
-        int end = t + 1;
-        while (end < m && sh_row[end] == row) ++end;
-        float mx = sh_z[t];
-        for (int j = t + 1; j < end; ++j) mx = fmaxf(mx, sh_z[j]);
-        double sum = 0.0;
-        for (int j = t; j < end; ++j) sum += (double)expf(sh_z[j] - mx);
-        if (a.row_off[row] < p0) { chunk_max[blockIdx.x] = mx; chunk_sum[blockIdx.x] = sum; }
-        else { row_max[row] = mx; row_sum[row] = sum; }
-    }
+    gt_run_stats<false>(a, p0, m, sh_row, sh_z, nullptr, GfStats{row_max, row_sum, chunk_max, chunk_sum});
 }
 
 // per non-empty row: (M, D) over its start and the chunks it crosses, in chunk order, written over the row's slots
+// (graph_forward_combine_kernel forms the same (M, D) but fuses the sum into its loop over the partial rows: the two stay apart)
 __global__ __launch_bounds__(256) void graph_attend_rows_kernel(GtArgs a, float* __restrict__ row_max, double* __restrict__ row_sum,
                                                                  const float* __restrict__ chunk_max, const double* __restrict__ chunk_sum) {
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -115,8 +102,7 @@ __global__ __launch_bounds__(GA_SEG) void graph_attend_bwd_partial_kernel(GtArgs
     __shared__ double sh_p[3][GA_SEG];
     __shared__ int sh_row[GA_SEG];
     const int t = threadIdx.x;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     if (t < m) {
         const int row = ga_row_of(a.row_off, a.n_rows, p0 + t);
         const float s = score[p0 + t];
@@ -188,14 +174,13 @@ __global__ __launch_bounds__(64) void graph_attend_product_kernel(GtProduct a) {
     __shared__ float sh_w[GA_SEG];
     __shared__ int sh_row[GA_SEG];
     const int t = threadIdx.x;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     for (int i = t; i < m; i += 64) {
         const long long p = p0 + i;
         const int row = ga_row_of(a.row_off, a.n_rows, p);
         const int key = a.key[p];
         long long of = -1;
-        if (a.L > 0) { if ((unsigned)key < (unsigned)a.N) of = ((long long)(row / a.L) * a.N + key) * GT_C4; }
+        if (a.L > 0) of = gt_feature_row(a.L, a.N, row, key);
         else if ((unsigned)key < (unsigned)a.n_key) of = (long long)key * GT_C4;
         long long wi = p;
         if (a.perm != nullptr) {
@@ -213,23 +198,7 @@ __global__ __launch_bounds__(64) void graph_attend_product_kernel(GtProduct a) {
         const int cur = sh_row[e];
         int end = e + 1;
         while (end < m && sh_row[end] == cur) ++end;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int j = e; j < end; j += GT_BATCH) {
-            float w[GT_BATCH]; float4 v[GT_BATCH]; bool live[GT_BATCH];
-#pragma unroll
-            for (int u = 0; u < GT_BATCH; ++u) {
-                const int i = min(j + u, end - 1);
-                const long long of = sh_of[i];
-                live[u] = j + u < end && of >= 0;
-                v[u] = src[of >= 0 ? of : 0];
-                w[u] = sh_w[i];
-            }
-#pragma unroll
-            for (int u = 0; u < GT_BATCH; ++u) {
-                acc.x = live[u] ? fmaf(w[u], v[u].x, acc.x) : acc.x; acc.y = live[u] ? fmaf(w[u], v[u].y, acc.y) : acc.y;
-                acc.z = live[u] ? fmaf(w[u], v[u].z, acc.z) : acc.z; acc.w = live[u] ? fmaf(w[u], v[u].w, acc.w) : acc.w;
-            }
-        }
+        const float4 acc = ga_gather_run(src, sh_of, sh_w, e, end);
         // a run that came in from an earlier chunk (only the first can) leaves this chunk's partial row, any other starts its row
         const bool head = a.row_off[cur] < p0;
         float4* dst = reinterpret_cast<float4*>(head ? a.part + (size_t)blockIdx.x * D : a.out + (size_t)cur * D);
@@ -263,22 +232,16 @@ __global__ __launch_bounds__(64) void graph_attend_combine_kernel(const int64_t*
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-static size_t gt_chunks(int64_t E) { return (size_t)((E + GA_SEG - 1) / GA_SEG); }
-
 // forward: the row of every edge, a (max, sum) slot per row and per chunk;  backward: the rows, d S, three sums per row and per chunk,
 // the products' partial rows.  The one walk behind the sizes (null base) and both launches
-struct GtWs { int32_t* row_of; float* row_max; double* row_sum; float* chunk_max; double* chunk_sum;
-              float* dscore; double* row_part; double* chunk_part; float* part; size_t bytes; };
+struct GtWs { int32_t* row_of; GfStats st; float* dscore; double* row_part; double* chunk_part; float* part; size_t bytes; };
 static GtWs gt_carve(void* ws, int B, const Grid& g, int64_t E, bool backward) {
     Carver cv(ws);
     GtWs w{};
-    const size_t rows = (size_t)B * g.L, chunks = gt_chunks(E) + 1;
+    const size_t rows = (size_t)B * g.L, chunks = ga_chunks(E) + 1;
     w.row_of = cv.take<int32_t>((size_t)E + 1);
     if (!backward) {
-        w.row_max = cv.take<float>(rows);
-        w.row_sum = cv.take<double>(rows);
-        w.chunk_max = cv.take<float>(chunks);
-        w.chunk_sum = cv.take<double>(chunks);
+        w.st = carve_stats(cv, rows, chunks);
     } else {
         w.dscore = cv.take<float>((size_t)E + 1);
         w.row_part = cv.take<double>(rows * 3);
@@ -288,34 +251,27 @@ static GtWs gt_carve(void* ws, int B, const Grid& g, int64_t E, bool backward) {
     w.bytes = cv.bytes();
     return w;
 }
-size_t graph_attend_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) { return gt_carve(nullptr, B, g, E, backward).bytes; }
+static size_t graph_attend_workspace_bytes(int B, const Grid& g, int64_t E, bool backward) { return gt_carve(nullptr, B, g, E, backward).bytes; }
 
-static GtArgs gt_args(int B, const Grid& g, const GraphAttendCall& c) {
-    GtArgs a{};
-    a.row_off = c.row_off; a.n_rows = B * g.L; a.key = c.key; a.E = c.E;
-    a.wq = c.wq_rows; a.x = c.x_rows; a.tau = c.tau; a.L = g.L; a.N = g.N; a.scale = c.scale; a.edges_only = c.edges_only ? 1 : 0;
-    return a;
-}
-
-int launch_graph_attend(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, float* score, float* weight, void* workspace) {
+static int launch_graph_attend(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, float* score, float* weight, void* workspace) {
     if (c.E == 0) return DAGL_OK;
     const GtWs w = gt_carve(workspace, B, g, c.E, false);
     const GtArgs a = gt_args(B, g, c);
-    hipLaunchKernelGGL(graph_attend_score_kernel, dim3((unsigned)gt_chunks(c.E)), dim3(256), 0, s, a, score, w.row_of, w.row_max, w.row_sum,
-                       w.chunk_max, w.chunk_sum);
+    hipLaunchKernelGGL(graph_attend_score_kernel, dim3((unsigned)ga_chunks(c.E)), dim3(256), 0, s, a, score, w.row_of, w.st.row_max, w.st.row_sum,
+                       w.st.chunk_max, w.st.chunk_sum);
     DAGL_LAUNCH_CHECK("graph_attend_score_kernel");
-    hipLaunchKernelGGL(graph_attend_rows_kernel, dim3((unsigned)((a.n_rows + 255) / 256)), dim3(256), 0, s, a, w.row_max, w.row_sum,
-                       w.chunk_max, w.chunk_sum);
+    hipLaunchKernelGGL(graph_attend_rows_kernel, dim3((unsigned)((a.n_rows + 255) / 256)), dim3(256), 0, s, a, w.st.row_max, w.st.row_sum,
+                       w.st.chunk_max, w.st.chunk_sum);
     DAGL_LAUNCH_CHECK("graph_attend_rows_kernel");
-    hipLaunchKernelGGL(graph_attend_weight_kernel, dim3((unsigned)((c.E + 255) / 256)), dim3(256), 0, s, a, score, w.row_of, w.row_max,
-                       w.row_sum, weight);
+    hipLaunchKernelGGL(graph_attend_weight_kernel, dim3((unsigned)((c.E + 255) / 256)), dim3(256), 0, s, a, score, w.row_of, w.st.row_max,
+                       w.st.row_sum, weight);
     DAGL_LAUNCH_CHECK("graph_attend_weight_kernel");
     return DAGL_OK;
 }
 
 static int gt_product(hipStream_t s, const GtProduct& p) {
     if (p.E > 0) {
-        hipLaunchKernelGGL(graph_attend_product_kernel, dim3((unsigned)gt_chunks(p.E)), dim3(64), 0, s, p);
+        hipLaunchKernelGGL(graph_attend_product_kernel, dim3((unsigned)ga_chunks(p.E)), dim3(64), 0, s, p);
         DAGL_LAUNCH_CHECK("graph_attend_product_kernel");
     }
     hipLaunchKernelGGL(graph_attend_combine_kernel, dim3((unsigned)p.n_rows), dim3(64), 0, s, p.row_off, p.E, p.part, p.out);
@@ -323,13 +279,14 @@ static int gt_product(hipStream_t s, const GtProduct& p) {
     return DAGL_OK;
 }
 
-int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* score, const float* weight,
-                                 const float* d_weight, const int64_t* col_off, const int32_t* src_row, const int32_t* perm,
-                                 float* d_wq_rows, float* d_x_rows, float* d_tau, void* workspace) {
+static int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* score,
+                                        const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
+                                        const int32_t* perm, float* d_wq_rows /* or null */, float* d_x_rows /* or null */,
+                                        float* d_tau /* or null */, void* workspace) {
     const GtWs w = gt_carve(workspace, B, g, c.E, true);
     const GtArgs a = gt_args(B, g, c);
     if (c.E > 0) {
-        hipLaunchKernelGGL(graph_attend_bwd_partial_kernel, dim3((unsigned)gt_chunks(c.E)), dim3(GA_SEG), 0, s, a, score, weight, d_weight,
+        hipLaunchKernelGGL(graph_attend_bwd_partial_kernel, dim3((unsigned)ga_chunks(c.E)), dim3(GA_SEG), 0, s, a, score, weight, d_weight,
                            w.row_of, w.row_part, w.chunk_part);
         DAGL_LAUNCH_CHECK("graph_attend_bwd_partial_kernel");
     }
@@ -361,4 +318,57 @@ int launch_graph_attend_backward(hipStream_t s, int B, const Grid& g, const Grap
     return DAGL_OK;
 }
 
+static size_t graph_attend_bytes(const char* who, int B, int H, int W, int64_t total_edges, bool backward) {
+    if (graph_shape_ok(who, B, H, W, total_edges)) return 0;
+    return graph_attend_workspace_bytes(B, make_grid(H, W), total_edges, backward);
+}
+
 }  // namespace dagl
+
+using namespace dagl;
+
+extern "C" {
+
+// (ABI 412) attention on a given patch graph
+size_t dagl_graph_attend_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_attend_bytes("dagl_graph_attend_workspace_bytes", B, H, W, total_edges, false);
+}
+
+size_t dagl_graph_attend_backward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    return graph_attend_bytes("dagl_graph_attend_backward_workspace_bytes", B, H, W, total_edges, true);
+}
+
+int dagl_graph_attend(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                      const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, float* score, float* weight,
+                      void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_attend";
+    int rc = graph_shape_ok(who, B, H, W, total_edges);
+    if (rc || (rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags))) return rc;
+    DAGL_REQUIRE(total_edges == 0 || (score && weight), "dagl_graph_attend: null tensor pointer");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace(who, workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, false)))) return rc;
+    const GraphAttendCall c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
+    return launch_graph_attend((hipStream_t)stream, B, g, c, score, weight, workspace);
+}
+
+int dagl_graph_attend_backward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                               const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags, const float* score,
+                               const float* weight, const float* d_weight, const int64_t* col_off, const int32_t* src_row,
+                               const int32_t* perm, float* d_wq_rows, float* d_x_rows, float* d_tau, void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_attend_backward";
+    int rc = graph_shape_ok(who, B, H, W, total_edges);
+    if (rc || (rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags))) return rc;
+    DAGL_REQUIRE(total_edges == 0 || (score && weight && d_weight), "dagl_graph_attend_backward: null tensor pointer");
+    DAGL_REQUIRE(d_x_rows == nullptr || (col_off && (total_edges == 0 || (src_row && perm))),
+                 "dagl_graph_attend_backward: null transposed CSR (col_off, src_row, perm are required with d_x_rows)");
+    DAGL_REQUIRE(d_tau == nullptr || tau != nullptr, "dagl_graph_attend_backward: d_tau asked for without tau");
+    DAGL_REQUIRE(((uintptr_t)d_wq_rows % 16) == 0 && ((uintptr_t)d_x_rows % 16) == 0,
+                 "dagl_graph_attend_backward: gradient rows must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace(who, workspace, ws_bytes, graph_attend_workspace_bytes(B, g, total_edges, true)))) return rc;
+    const GraphAttendCall c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
+    return launch_graph_attend_backward((hipStream_t)stream, B, g, c, score, weight, d_weight, col_off, src_row, perm, d_wq_rows, d_x_rows,
+                                        d_tau, workspace);
+}
+
+}  // extern "C"

@@ -24,8 +24,6 @@
 
 namespace dagl {
 
-struct GfStats { float* row_max; double* row_sum; float* chunk_max; double* chunk_sum; };
-
 __global__ __launch_bounds__(256) void graph_forward_segment_kernel(GtArgs a, GaArgs v, GfStats st) {
     __shared__ long long sh_x[GA_SEG];        // float4 offset of the key's feature row, -1 = key out of range
     __shared__ long long sh_of[GA_SEG];       // float4 offset of the key's patch in the map, -1 = the edge carries no value row
@@ -33,13 +31,12 @@ __global__ __launch_bounds__(256) void graph_forward_segment_kernel(GtArgs a, Ga
     __shared__ float sh_z[GA_SEG];
     __shared__ float sh_w[GA_SEG];            // e^(z - the run's maximum)
     const int t = threadIdx.x;
-    const long long p0 = (long long)blockIdx.x * GA_SEG;
-    const int m = (int)((a.E - p0 < GA_SEG) ? a.E - p0 : GA_SEG);
+    const auto [p0, m] = ga_segment(a.E);
     if (t < m) {
         const int row = ga_row_of(a.row_off, a.n_rows, p0 + t);
         const int key = a.key[p0 + t];
         sh_row[t] = row;
-        sh_x[t] = (unsigned)key < (unsigned)a.N ? ((long long)(row / a.L) * a.N + key) * GT_C4 : -1;
+        sh_x[t] = gt_feature_row(a.L, a.N, row, key);
         sh_of[t] = ga_source<true>(v, row, key);
     }
     __syncthreads();
@@ -57,22 +54,7 @@ __global__ __launch_bounds__(256) void graph_forward_segment_kernel(GtArgs a, Ga
         }
     }
     __syncthreads();
-    // one (max, sum) per run of equal row, by the thread of the run's first edge, in edge order
-    if (t < m && (t == 0 || sh_row[t - 1] != sh_row[t])) {
-        const int row = sh_row[t];
-        int end = t + 1;
-        while (end < m && sh_row[end] == row) ++end;
-        float mx = sh_z[t];
-        for (int j = t + 1; j < end; ++j) mx = fmaxf(mx, sh_z[j]);
-        double sum = 0.0;
-        for (int j = t; j < end; ++j) {
-            const float p = expf(sh_z[j] - mx);
-            sum += (double)p;
-            sh_w[j] = p;
-        }
-        if (a.row_off[row] < p0) { st.chunk_max[blockIdx.x] = mx; st.chunk_sum[blockIdx.x] = sum; }
-        else { st.row_max[row] = mx; st.row_sum[row] = sum; }
-    }
+    gt_run_stats<true>(a, p0, m, sh_row, sh_z, sh_w, st);
     __syncthreads();
     const int r = t < GA_C4 ? t : GA_C4 - 1;                   // (threads 196..255 stage and score edges, then idle along)
     const float4* src = reinterpret_cast<const float4*>(v.src) + (r / 28) * v.Wp * (CH / 4) + r % 28;
@@ -146,29 +128,22 @@ struct GfWs { float* agg; float* part; GfStats st; size_t bytes; };
 static GfWs gf_carve(void* ws, int B, const Grid& g, int64_t E) {
     Carver cv(ws);
     GfWs w{};
-    const size_t rows = (size_t)B * g.L, chunks = (size_t)((E + GA_SEG - 1) / GA_SEG) + 1;
+    const size_t rows = (size_t)B * g.L, chunks = ga_chunks(E) + 1;
     w.agg = cv.take<float>(rows * P);
     w.part = cv.take<float>(chunks * P);
-    w.st.row_max = cv.take<float>(rows);
-    w.st.row_sum = cv.take<double>(rows);
-    w.st.chunk_max = cv.take<float>(chunks);
-    w.st.chunk_sum = cv.take<double>(chunks);
+    w.st = carve_stats(cv, rows, chunks);
     w.bytes = cv.bytes();
     return w;
 }
-size_t graph_forward_workspace_bytes(int B, const Grid& g, int64_t E) { return gf_carve(nullptr, B, g, E).bytes; }
+static size_t graph_forward_workspace_bytes(int B, const Grid& g, int64_t E) { return gf_carve(nullptr, B, g, E).bytes; }
 
-int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace) {
+static int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace) {
     const GfWs w = gf_carve(workspace, B, g, c.E);
-    GtArgs a{};
-    a.row_off = c.row_off; a.n_rows = B * g.L; a.key = c.key; a.E = c.E;
-    a.wq = c.wq_rows; a.x = c.x_rows; a.tau = c.tau; a.L = g.L; a.N = g.N; a.scale = c.scale; a.edges_only = c.edges_only ? 1 : 0;
-    GaArgs v{};
-    v.row_off = c.row_off; v.n_rows = a.n_rows; v.key = c.key; v.weight = nullptr; v.perm = nullptr; v.E = c.E;
-    v.src = b2p; v.n_src = g.N; v.L = g.L; v.W = g.W; v.Wp = g.Wp; v.img4 = (long long)g.Hp * g.Wp * (CH / 4);
+    const GtArgs a = gt_args(B, g, c);
+    GaArgs v = ga_map_args(B, g, b2p, c.row_off, c.key, nullptr, c.E);
     v.out = w.agg; v.part = w.part;
     if (c.E > 0) {
-        hipLaunchKernelGGL(graph_forward_segment_kernel, dim3((unsigned)((c.E + GA_SEG - 1) / GA_SEG)), dim3(256), 0, s, a, v, w.st);
+        hipLaunchKernelGGL(graph_forward_segment_kernel, dim3((unsigned)ga_chunks(c.E)), dim3(256), 0, s, a, v, w.st);
         DAGL_LAUNCH_CHECK("graph_forward_segment_kernel");
     }
     hipLaunchKernelGGL(graph_forward_combine_kernel, dim3((unsigned)a.n_rows), dim3(256), 0, s, a, w.st, w.part, w.agg);
@@ -177,3 +152,29 @@ int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendC
 }
 
 }  // namespace dagl
+
+using namespace dagl;
+
+extern "C" {
+
+// the fused forward on a given patch graph (no ABI bump: found by symbol)
+size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    if (graph_shape_ok("dagl_graph_forward_workspace_bytes", B, H, W, total_edges)) return 0;
+    return graph_forward_workspace_bytes(B, make_grid(H, W), total_edges);
+}
+
+int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                       const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags,
+                       float* out, void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_forward";
+    int rc = graph_shape_ok(who, B, H, W, total_edges);
+    if (rc || (rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags))) return rc;
+    DAGL_REQUIRE(b2p && out, "dagl_graph_forward: null tensor pointer");
+    DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "dagl_graph_forward: b2p must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace(who, workspace, ws_bytes, graph_forward_workspace_bytes(B, g, total_edges)))) return rc;
+    const GraphAttendCall c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
+    return launch_graph_forward((hipStream_t)stream, B, g, c, b2p, out, workspace);
+}
+
+}  // extern "C"

@@ -11,6 +11,7 @@
 // of the result is valid whatever the lists hold.  E <= B L width <= capacity (checked on the host): no capacity test on the device.
 // No atomics, no host read: the same lists give the same bits on every call, and the three launches can be captured.
 #include "dagl_common.h"
+#include "graph_rows.h"
 
 namespace dagl {
 
@@ -71,12 +72,6 @@ static int launch_graph_from_lists(hipStream_t s, int n_rows, int width, int N, 
     return DAGL_OK;
 }
 
-static int lists_shape_ok(const char* who, int B, int H, int W) {
-    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    DAGL_REQUIRE((int64_t)B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
-    return DAGL_OK;
-}
-
 }  // namespace dagl
 
 using namespace dagl;
@@ -85,14 +80,14 @@ extern "C" {
 
 // the patch graph from a forward's neighbour lists (no ABI bump: found by symbol)
 size_t dagl_graph_from_lists_workspace_bytes(int B, int H, int W) {
-    if (lists_shape_ok("dagl_graph_from_lists_workspace_bytes", B, H, W)) return 0;
+    if (graph_dims_ok("dagl_graph_from_lists_workspace_bytes", B, H, W)) return 0;
     return lists_carve(nullptr, (size_t)B * make_grid(H, W).L).bytes;
 }
 
 int dagl_graph_from_lists(void* stream, int B, int H, int W, int width, const int32_t* nb_idx, const float* nb_wgt, const float* nb_s,
                           const int32_t* nb_cnt, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out,
                           int64_t capacity_edges, void* workspace, size_t ws_bytes) {
-    int rc = lists_shape_ok("dagl_graph_from_lists", B, H, W);
+    int rc = graph_dims_ok("dagl_graph_from_lists", B, H, W);
     if (rc) return rc;
     DAGL_REQUIRE(width >= 1 && width <= DAGL_MAX_TOPK, "dagl_graph_from_lists: width=%d outside [1, %d]", width, DAGL_MAX_TOPK);
     const Grid g = make_grid(H, W);

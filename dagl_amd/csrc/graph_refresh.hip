@@ -42,13 +42,15 @@ struct RfArgs {
 };
 
 // a float as an unsigned that orders the same way: -0 = +0, NaN below everything (a strict total order with the key as tie-break: a rank
-// cut keeps exactly min(k, passing) entries whatever the scores hold)
+// cut keeps exactly min(k, passing) entries whatever the scores hold).  (Not in graph_rows.h: no other graph route ranks.)
 __device__ __forceinline__ unsigned rf_ord(float s) {
     if (s != s) return 0u;
     const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// rf_scan / rf_max / rf_sum stay here, not on dagl_common.h's block reductions: they are templated on the block size (a wavefront or four
+// per row) and add the waves' partials one after the other where block_sum_f64 adds (w0 + w1) + (w2 + w3) -- other bits.
 // exclusive prefix of v over the block's threads and the total, the same in every thread
 template <int T>
 __device__ __forceinline__ int rf_scan(int v, int* sh, int& total) {
@@ -289,9 +291,7 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
         return DAGL_OK;
     }
     const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2);
-    GtArgs a{};
-    a.row_off = r.c.row_off; a.n_rows = n_rows; a.key = r.c.key; a.E = r.c.E;
-    a.wq = r.c.wq_rows; a.x = r.c.x_rows; a.tau = r.c.tau; a.L = g.L; a.N = g.N; a.scale = r.c.scale; a.edges_only = r.c.edges_only ? 1 : 0;
+    const GtArgs a = gt_args(B, g, r.c);
     RfArgs f{};
     f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
     f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
@@ -313,10 +313,10 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
 }
 
 static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
-    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
-    DAGL_REQUIRE((int64_t)B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
     DAGL_REQUIRE(radius >= 0 && radius <= RF_MAX_RADIUS, "%s: radius=%d outside [0, %d]", who, radius, RF_MAX_RADIUS);
-    DAGL_REQUIRE(total_edges >= 0 && total_edges < (1ll << 31), "%s: total_edges=%lld outside [0, 2^31)", who, (long long)total_edges);
+    if ((rc = graph_edges_ok(who, total_edges))) return rc;
     const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
     DAGL_REQUIRE(total_edges * w2 < (1ll << 31), "%s: total_edges (2 radius + 1)^2 = %lld staged candidates, 2^31 or more", who,
                  (long long)(total_edges * w2));
@@ -343,12 +343,10 @@ int dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_rows, 
     const char* who = "dagl_graph_refresh";
     int rc = refresh_shape_ok(who, B, H, W, total_edges, radius);
     if (rc) return rc;
-    DAGL_REQUIRE(wq_rows && x_rows && row_off && row_off_out && status_out && (total_edges == 0 || (key && key_out && weight_out && score_out)),
-                 "%s: null tensor pointer", who);
-    DAGL_REQUIRE(((uintptr_t)wq_rows % 16) == 0 && ((uintptr_t)x_rows % 16) == 0, "%s: feature rows must be 16-byte aligned", who);
-    DAGL_REQUIRE((flags & ~(DAGL_GRAPH_ATTEND_EDGES_ONLY | DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)) == 0,
-                 "%s: unknown flags 0x%x", who, flags);
-    DAGL_REQUIRE(scale > 0.f && scale < INFINITY, "%s: scale=%g must be positive and finite", who, (double)scale);
+    const bool outputs = row_off_out && status_out && (total_edges == 0 || (key_out && weight_out && score_out));
+    if ((rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags, outputs,
+                                DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
+        return rc;
     DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
     DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
     const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
@@ -368,7 +366,7 @@ int dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_rows, 
     const size_t need = refresh_carve(nullptr, (size_t)B * g.L, (size_t)(total_edges * w2)).bytes;
     if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
     RefreshCall r{};
-    r.c = GraphAttendCall{wq_rows, x_rows, row_off, key, total_edges, tau, scale, (flags & DAGL_GRAPH_ATTEND_EDGES_ONLY) != 0};
+    r.c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
     r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
     r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
     r.row_off_out = row_off_out; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.capacity = capacity_edges;

@@ -296,6 +296,15 @@ def _region(workspace: "Workspace | None", nbytes: int, device):
     return (buf,) + _aligned(buf)
 
 
+def _sized_region(workspace: "Workspace | None", device, entry: str, *args):
+    """``_region`` of the bytes the library's ``entry`` (a ``*_workspace_bytes`` symbol) asks for ``args``.  0 bytes is its refusal of
+    the shape: raised with the library's message."""
+    need = getattr(_lib.load(), entry)(*args)
+    if need == 0:
+        check(-1, entry)
+    return _region(workspace, need, device)
+
+
 @_on_device
 def ce_forward(b1, b2, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adaptive", k: int = 0,
                workspace: "Workspace | None" = None, return_info: bool = False, debug: bool = False,
@@ -382,10 +391,7 @@ def ce_graph(b1, thr, bias, fc1_w, fc1_b, fc2_w, fc2_b, mode: str = "adaptive", 
             raise DaglError("ce_graph: thr/bias must hold B*L values")
     if torch.cuda.is_current_stream_capturing():
         raise DaglError("ce_graph: not available under stream capture (the edge count is read on the host between the two phases)")
-    need = lib.dagl_ce_graph_workspace_bytes(B, H, W, MODES[mode], int(k), int(rows_per_chunk))
-    if need == 0:
-        check(-1, "dagl_ce_graph_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, b1.device)
+    buf, a, nbytes = _sized_region(workspace, b1.device, "dagl_ce_graph_workspace_bytes", B, H, W, MODES[mode], int(k), int(rows_per_chunk))
     row_off = torch.empty(BL + 1, device=b1.device, dtype=torch.int64)
     info = _lib.CeInfo()
     check(lib.dagl_ce_graph_count(_stream(), B, H, W, b1.data_ptr(), _ptr(thr, heads), _ptr(bias, heads), fc1_w.data_ptr(),
@@ -411,12 +417,28 @@ def graph_apply_segment() -> int:
     return int(_lib.load().dagl_graph_apply_segment())
 
 
+def _value_map(who: str, b2p):
+    """Shape of a graph call's value map -> (B, H, W)."""
+    if b2p.dim() != 4 or b2p.shape[3] != 16 or b2p.shape[1] < 7 or b2p.shape[2] < 7:
+        raise DaglError(f"{who}: b2p must be the zero-bordered NHWC value map [B,H+6,W+6,16], got {tuple(b2p.shape)}")
+    return b2p.shape[0], b2p.shape[1] - 6, b2p.shape[2] - 6
+
+
+def _transposed_csr(who: str, what: str, transposed, n_cols: int, E: int):
+    """The transposed CSR a gradient ``what`` needs -> (col_off [n_cols + 1], src_row [E], perm [E])."""
+    if transposed is None:
+        raise DaglError(f"{who}: {what} needs the transposed CSR (col_off, src_row, perm)")
+    col_off, src_row, perm = transposed
+    _need(col_off, "col_off", torch.int64); _need(src_row, "src_row", torch.int32); _need(perm, "perm", torch.int32)
+    if col_off.numel() != n_cols + 1 or src_row.numel() != E or perm.numel() != E:
+        raise DaglError(f"{who}: the transposed CSR must hold B*N+1 = {n_cols + 1} offsets and {E} edges")
+    return col_off, src_row, perm
+
+
 def _graph_apply_operands(who: str, b2p, row_off, key, weight):
     """Shapes of a graph-apply call's operands -> (B, H, W, E).  Array CONTENTS stay unread: the kernels bound every index themselves."""
     _need(b2p, "b2p"); _need(row_off, "row_off", torch.int64); _need(key, "key", torch.int32); _need(weight, "weight")
-    if b2p.dim() != 4 or b2p.shape[3] != 16 or b2p.shape[1] < 7 or b2p.shape[2] < 7:
-        raise DaglError(f"{who}: b2p must be the zero-bordered NHWC value map [B,H+6,W+6,16], got {tuple(b2p.shape)}")
-    B, H, W = b2p.shape[0], b2p.shape[1] - 6, b2p.shape[2] - 6
+    B, H, W = _value_map(who, b2p)
     Lh, Lw = query_grid(H, W)
     E = key.numel()
     if row_off.dim() != 1 or row_off.numel() != B * Lh * Lw + 1:
@@ -433,10 +455,7 @@ def graph_apply(b2p, row_off, key, weight, workspace: "Workspace | None" = None)
     [B,16,H,W].  Nothing is read on the host; keys outside [0, N) contribute nothing."""
     lib = _lib.load()
     B, H, W, E = _graph_apply_operands("graph_apply", b2p, row_off, key, weight)
-    need = lib.dagl_graph_apply_workspace_bytes(B, H, W, E)
-    if need == 0:
-        check(-1, "dagl_graph_apply_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, b2p.device)
+    buf, a, nbytes = _sized_region(workspace, b2p.device, "dagl_graph_apply_workspace_bytes", B, H, W, E)
     out = torch.empty(B, 16, H, W, device=b2p.device, dtype=torch.float32)
     check(lib.dagl_graph_apply(_stream(), B, H, W, b2p.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), _ptr(weight, E > 0), E,
                                out.data_ptr(), a, nbytes), "dagl_graph_apply")
@@ -457,16 +476,8 @@ def graph_apply_backward(d_out, b2p, row_off, key, weight, transposed=None, need
         raise DaglError(f"graph_apply_backward: d_out is {tuple(d_out.shape)}, expected {(B, 16, H, W)}")
     col_off = src_row = perm = None
     if need_b2p:
-        if transposed is None:
-            raise DaglError("graph_apply_backward: d_b2p needs the transposed CSR (col_off, src_row, perm)")
-        col_off, src_row, perm = transposed
-        _need(col_off, "col_off", torch.int64); _need(src_row, "src_row", torch.int32); _need(perm, "perm", torch.int32)
-        if col_off.numel() != B * H * W + 1 or src_row.numel() != E or perm.numel() != E:
-            raise DaglError(f"graph_apply_backward: the transposed CSR must hold B*N+1 = {B * H * W + 1} offsets and {E} edges")
-    need = lib.dagl_graph_apply_backward_workspace_bytes(B, H, W, E)
-    if need == 0:
-        check(-1, "dagl_graph_apply_backward_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, b2p.device)
+        col_off, src_row, perm = _transposed_csr("graph_apply_backward", "d_b2p", transposed, B * H * W, E)
+    buf, a, nbytes = _sized_region(workspace, b2p.device, "dagl_graph_apply_backward_workspace_bytes", B, H, W, E)
     d_b2p = torch.empty_like(b2p) if need_b2p else None
     d_weight = torch.empty_like(weight) if need_weight else None
     check(lib.dagl_graph_apply_backward(_stream(), B, H, W, b2p.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), _ptr(weight, E > 0), E,
@@ -479,15 +490,18 @@ def graph_apply_backward(d_out, b2p, row_off, key, weight, transposed=None, need
 _GRAPH_NORMALIZE = {"reference": 0, "edges": _lib.GRAPH_ATTEND_EDGES_ONLY}
 
 
+def _maps_of(L: int, N: int):
+    """The maps (H, W) with H*W = N keys and a stride-4 query grid of L rows, by ascending H."""
+    return ((h, N // h) for h in range(1, N + 1) if N % h == 0 and math.prod(query_grid(h, N // h)) == L)
+
+
 def _map_of(L: int, N: int):
-    """A map (H, W) with H*W = N keys and a stride-4 query grid of L rows: the graph-attend kernels use L and N alone, so any such map
-    describes the call (``hw`` names the real one)."""
-    for h in range(1, math.isqrt(N) + 1):
-        if N % h == 0:
-            lh, lw = query_grid(h, N // h)
-            if lh * lw == L:
-                return h, N // h
-    raise DaglError(f"graph_attend: no map of {N} keys has a stride-4 query grid of {L} rows")
+    """The first of ``_maps_of``: the graph-attend kernels use L and N alone, so any such map describes the call (``hw`` names the real
+    one)."""
+    hw = next(_maps_of(L, N), None)
+    if hw is None:
+        raise DaglError(f"graph_attend: no map of {N} keys has a stride-4 query grid of {L} rows")
+    return hw
 
 
 def _graph_attend_operands(who: str, wq_rows, x_rows, row_off, key, tau, normalize, hw):
@@ -526,10 +540,7 @@ def graph_attend(wq_rows, x_rows, row_off, key, tau=None, scale: float = 10.0, n
     on the host; the same arrays give the same bits on every call.  ``hw``: the map (H, W) when the caller knows it."""
     lib = _lib.load()
     B, H, W, E, flags = _graph_attend_operands("graph_attend", wq_rows, x_rows, row_off, key, tau, normalize, hw)
-    need = lib.dagl_graph_attend_workspace_bytes(B, H, W, E)
-    if need == 0:
-        check(-1, "dagl_graph_attend_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+    buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_attend_workspace_bytes", B, H, W, E)
     score = torch.empty(E, device=wq_rows.device, dtype=torch.float32)
     weight = torch.empty_like(score)
     check(lib.dagl_graph_attend(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
@@ -547,16 +558,11 @@ def graph_forward(wq_rows, x_rows, b2p, row_off, key, tau=None, scale: float = 1
     arrays give the same bits on every call.  Nothing is read on the host."""
     lib = _lib.load()
     _need(b2p, "b2p")
-    if b2p.dim() != 4 or b2p.shape[3] != 16 or b2p.shape[1] < 7 or b2p.shape[2] < 7:
-        raise DaglError(f"graph_forward: b2p must be the zero-bordered NHWC value map [B,H+6,W+6,16], got {tuple(b2p.shape)}")
-    hw = (b2p.shape[1] - 6, b2p.shape[2] - 6)
+    hw = _value_map("graph_forward", b2p)[1:]
     B, H, W, E, flags = _graph_attend_operands("graph_forward", wq_rows, x_rows, row_off, key, tau, normalize, hw)
     if b2p.shape[0] != B:
         raise DaglError(f"graph_forward: b2p holds {b2p.shape[0]} images, the feature rows {B}")
-    need = lib.dagl_graph_forward_workspace_bytes(B, H, W, E)
-    if need == 0:
-        check(-1, "dagl_graph_forward_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+    buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_forward_workspace_bytes", B, H, W, E)
     out = torch.empty(B, 16, H, W, device=wq_rows.device, dtype=torch.float32)
     check(lib.dagl_graph_forward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
                                  _ptr(key, E > 0), E, _ptr(tau), float(scale), flags, out.data_ptr(), a, nbytes), "dagl_graph_forward")
@@ -588,10 +594,7 @@ def graph_from_lists(nb_idx, nb_wgt, nb_s, nb_cnt, hw, workspace: "Workspace | N
         raise DaglError(f"graph_from_lists: a {H}x{W} map has {Lh * Lw} queries, the lists hold {L} rows of {B} images")
     if torch.cuda.is_current_stream_capturing():
         raise DaglError("graph_from_lists: not available under stream capture (the edge count is read on the host)")
-    need = lib.dagl_graph_from_lists_workspace_bytes(B, H, W)
-    if need == 0:
-        check(-1, "dagl_graph_from_lists_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, nb_idx.device)
+    buf, a, nbytes = _sized_region(workspace, nb_idx.device, "dagl_graph_from_lists_workspace_bytes", B, H, W)
     cap = B * L * width
     row_off = torch.empty(B * L + 1, device=nb_idx.device, dtype=torch.int64)
     key = torch.empty(cap, device=nb_idx.device, dtype=torch.int32)
@@ -632,7 +635,7 @@ def graph_refresh(wq_rows, x_rows, row_off, key, *, radius: int = 1, tau=None, k
     if hw is None and isinstance(wq_rows, torch.Tensor) and isinstance(x_rows, torch.Tensor) and wq_rows.dim() == 3 and x_rows.dim() == 3:
         # (the windows need the map itself: L and N alone leave H x W and W x H apart only when one of them does not fit)
         L, N = wq_rows.shape[1], x_rows.shape[1]
-        maps = [(h, N // h) for h in range(1, N + 1) if N % h == 0 and math.prod(query_grid(h, N // h)) == L]
+        maps = list(_maps_of(L, N))
         if len(maps) > 1:
             raise DaglError(f"graph_refresh: {len(maps)} maps have {N} keys and {L} queries ({maps[0][0]}x{maps[0][1]}, "
                             f"{maps[1][0]}x{maps[1][1]}, ...): pass hw=(H, W)")
@@ -649,10 +652,7 @@ def graph_refresh(wq_rows, x_rows, row_off, key, *, radius: int = 1, tau=None, k
     if block_rows:
         flags |= _lib.GRAPH_REFRESH_BLOCK_ROWS
     dev = wq_rows.device
-    need = lib.dagl_graph_refresh_workspace_bytes(B, H, W, E, radius)
-    if need == 0:
-        check(-1, "dagl_graph_refresh_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, dev)
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_refresh_workspace_bytes", B, H, W, E, radius)
     L = wq_rows.shape[1]
     cap = E * (2 * radius + 1) ** 2
     if k > 0 and not keep_all:
@@ -691,16 +691,8 @@ def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight
             raise DaglError(f"graph_attend_backward: {n} must be 1-d with one entry per edge ({E})")
     col_off = src_row = perm = None
     if need_x:
-        if transposed is None:
-            raise DaglError("graph_attend_backward: d_x needs the transposed CSR (col_off, src_row, perm)")
-        col_off, src_row, perm = transposed
-        _need(col_off, "col_off", torch.int64); _need(src_row, "src_row", torch.int32); _need(perm, "perm", torch.int32)
-        if col_off.numel() != B * H * W + 1 or src_row.numel() != E or perm.numel() != E:
-            raise DaglError(f"graph_attend_backward: the transposed CSR must hold B*N+1 = {B * H * W + 1} offsets and {E} edges")
-    need = lib.dagl_graph_attend_backward_workspace_bytes(B, H, W, E)
-    if need == 0:
-        check(-1, "dagl_graph_attend_backward_workspace_bytes")
-    buf, a, nbytes = _region(workspace, need, wq_rows.device)
+        col_off, src_row, perm = _transposed_csr("graph_attend_backward", "d_x", transposed, B * H * W, E)
+    buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_attend_backward_workspace_bytes", B, H, W, E)
     d_wq = torch.empty_like(wq_rows) if need_wq else None
     d_x = torch.empty_like(x_rows) if need_x else None
     d_tau = torch.empty(B * wq_rows.shape[1], device=wq_rows.device, dtype=torch.float32) if need_tau and tau is not None else None
@@ -1034,12 +1026,9 @@ def ces_stage_forward(x, head_params, mix_w, mix_b, mode: str = "adaptive", k: i
                 raise DaglError(f"ces_stage_forward: head {h} {name} is {tuple(t.shape)}, expected {want[name]}")
             setattr(arr[h], field, t.data_ptr())
     lib = _lib.load()
-    need = lib.dagl_ces_stage_workspace_bytes(B, H, W, MODES[mode], int(k))
-    if need == 0:
-        check(-1, "dagl_ces_stage_workspace_bytes")
     out = torch.empty(B, 64, H, W, device=x.device, dtype=torch.float32)
     info = _lib.CeInfo()
-    buf, a, nbytes = _region(workspace, need, x.device)
+    buf, a, nbytes = _sized_region(workspace, x.device, "dagl_ces_stage_workspace_bytes", B, H, W, MODES[mode], int(k))
     flags = MODES[mode] | (_lib.FLAG_WEIGHTS_PACKED if weights_packed else 0) | _topk_flags(mode, False, tight_topk, sampled_topk)
     rc = lib.dagl_ces_stage_forward(_stream(), B, H, W, x.data_ptr(), arr, mix_w.data_ptr(), mix_b.data_ptr(), flags, int(k),
                                     out.data_ptr(), a, nbytes, C.byref(info), profile._h if profile is not None else None)
@@ -1074,9 +1063,6 @@ def ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode: str = "adaptive", k: i
     mode_flags = MODES[mode] | (_lib.FLAG_EXACT_SCAN if exact_scan else 0)
     width = lib.dagl_ce_list_width(mode_flags, int(k))
     check(min(width, 0), "dagl_ce_list_width")
-    need = lib.dagl_ce_workspace_bytes(B, H, W, mode_flags, int(k))
-    if need == 0:
-        check(-1, "dagl_ce_workspace_bytes")
     dev = b2.device
     out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32)
     saved = dict(nb_idx=torch.zeros(B, L, width, device=dev, dtype=torch.int32),
@@ -1085,7 +1071,7 @@ def ce_core_forward(wq_rows, x_rows, b2, thr, bias, mode: str = "adaptive", k: i
                  nb_cnt=torch.zeros(B, L, device=dev, dtype=torch.int32),
                  mu=torch.zeros(B, L, device=dev, dtype=torch.float32) if adaptive else None)
     info = _lib.CeInfo()
-    buf, a, nbytes = _region(workspace, need, dev)
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_ce_workspace_bytes", B, H, W, mode_flags, int(k))
     rc = lib.dagl_ce_core_forward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2.data_ptr(),
                                   _ptr(thr, adaptive), _ptr(bias, adaptive), mode_flags, int(k), out.data_ptr(),
                                   saved["nb_idx"].data_ptr(), saved["nb_wgt"].data_ptr(), saved["nb_s"].data_ptr(),
@@ -1106,16 +1092,13 @@ def ce_core_backward(d_out, wq_rows, x_rows, b2, thr, bias, saved: dict, mode: s
     adaptive = mode != "topk"
     if mode != "adaptive":
         k = min(int(k), H * W)
-    need = lib.dagl_ce_core_backward_workspace_bytes(B, H, W, MODES[mode], int(k))
-    if need == 0:
-        check(-1, "dagl_ce_core_backward_workspace_bytes")
     dev = b2.device
     d_wq = torch.empty_like(wq_rows)
     d_x = torch.empty_like(x_rows)
     d_b2 = torch.empty_like(b2)
     d_thr = torch.empty(B, wq_rows.shape[1], device=dev, dtype=torch.float32) if adaptive else None
     d_bias = torch.empty_like(d_thr) if adaptive else None
-    buf, a, nbytes = _region(workspace, need, dev)
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_ce_core_backward_workspace_bytes", B, H, W, MODES[mode], int(k))
     rc = lib.dagl_ce_core_backward(_stream(), B, H, W, MODES[mode], int(k), wq_rows.data_ptr(), x_rows.data_ptr(),
                                    b2.data_ptr(), _ptr(thr, adaptive), _ptr(bias, adaptive),
                                    saved["nb_idx"].data_ptr(), saved["nb_wgt"].data_ptr(), saved["nb_s"].data_ptr(),

@@ -1,41 +1,22 @@
 """``CE.forward_with_graph``: a block's output and the patch graph that produced it from one call -- the list-form route of the
 differentiable forward, its neighbour lists turned into CSR by ``ops.graph_from_lists`` (csrc/graph_lists.hip).
 
-The graph is held to the export's own checks (``check_structure`` / ``check_edges`` / ``check_values`` of test_gpu_patch_graph.py: the
+The graph is held to the export's own checks (``check_structure`` / ``check_edges`` / ``check_values`` of graph_reference.py: the
 band TAU = 2e-5, the caps on its share, the 3 e_32 + 1e-6 bound, all unchanged) on the fp32 route, the output to the bits of the
 module's own differentiable forward and, under the project's gap rule, to the inference forward; the graph must reproduce the output
 through ``apply_graph`` and ``forward_on_graph``.  The cases are those whose fp64 oracle degrees fit the lists (<= 64 keys per query)."""
 import pytest
 import torch
 
+from tests.graph_reference import (COMBOS, S0, S1, TOPK8, _cid, _gap, _mod, _module, _oracle, _refused, ambiguity, check_edges,
+                                  check_structure, check_values, membership)
 from tests.helpers import normwise
-from tests.test_gpu_graph_apply import _gap, _refused
-from tests.test_gpu_patch_graph import (_inputs, _module, _oracle, _seed, ambiguity, check_edges, check_structure, check_values,
-                                        membership)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-S0, S1, S2 = (2, 24, 20), (1, 33, 70), (1, 64, 64)
-TOPK8, TOPK64, ATOPK16 = ("default", 2.0, "topk", 8), ("default", 2.0, "topk", 64), ("sparse", 1.2, "adaptive_topk", 16)
-# (shape, (variant, sparse_gain, mode, k), seed)
-COMBOS = [(s, c, _seed(s, c)) for c in (TOPK8, TOPK64, ATOPK16) for s in (S0, S1, S2)] + [
-    (S0, ("sparse", 1.65, "adaptive", 0), 12),        # oracle: max degree 59, 21 empty rows of 60
-    (S1, ("sparse", 2.0, "adaptive", 0), 11),         # max degree 31, 143 empty rows of 162
-    (S2, ("sparse", 2.0, "adaptive", 0), 11),         # max degree 10
-    (S0, ("nonepass", 2.0, "adaptive", 0), 11)]       # the empty graph
 GRAD_COMBOS = [COMBOS[0], COMBOS[9]]                  # (2,24,20): top-k 8 and the adaptive case
 FEATURES = ("split16", "fp32")
 SCAN_OF = {"split16": "screened", "fp32": "exact"}
-
-
-def _cid(combo):
-    shape, case, seed = combo
-    return "x".join(map(str, shape)) + "-" + "-".join(map(str, case)) + f"-s{seed}"
-
-
-def _mod(combo, **kw):
-    shape, (variant, gain, mode, k), seed = combo
-    return _module(seed, shape, variant, gain, mode, k, **kw)
 
 
 def _arrays(g):

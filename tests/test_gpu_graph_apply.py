@@ -2,8 +2,8 @@
 a given patch graph, ``out = fold(A_G . V(theta(x))) / cnt``.
 
 The reference everywhere is torch on the CPU in fp64: the dense ``A_G`` built with ``index_put_(accumulate=True)`` (repeated keys add
-up), times ``oracle.ce_oracle.patch_rows(b2, 7, 1)``, folded as ``_fold`` of test_gpu_patch_graph.py does.  Kernel-level bound (the
-project's pattern, test_gpu_patch_graph.py ``check_values``): ``e_lib <= 3 e_32 + 1e-6``, both normwise against fp64, ``e_32`` the same
+up), times ``oracle.ce_oracle.patch_rows(b2, 7, 1)``, folded as ``_fold`` of graph_reference.py does.  Kernel-level bound (the
+project's pattern, graph_reference.py ``check_values``): ``e_lib <= 3 e_32 + 1e-6``, both normwise against fp64, ``e_32`` the same
 formula evaluated by torch on the CPU in fp32."""
 import functools
 
@@ -11,62 +11,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.graph_reference import (CASES, SHAPES, _crafted, _dense_apply, _gap, _geom, _id, _inputs, _module, _oracle, _padded, _refused,
+                                  _seed)
 from tests.helpers import normwise
-from tests.test_gpu_patch_graph import CASES, SHAPES, _fold, _id, _inputs, _module, _oracle, _same_forward_after, _seed
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def _seg():
-    from dagl_amd import ops
-    return ops.graph_apply_segment()
-
-
-def _geom(shape):
-    B, H, W = shape
-    return B, H, W, (-(-H // 4)) * (-(-W // 4)), H * W
-
-
-@functools.lru_cache(maxsize=None)
-def _crafted(shape, seed=5):
-    """(row_off, key, weight, b2) on the CPU: rows of degree 0, 1, SEG-1, SEG, SEG+1, 2 SEG+3, N (every key once), N+5 (more edges than
-    keys), a row of 3 SEG+1 edges as the LAST row of image 0 -- followed, in a batch of two, by an empty first row of image 1 -- and 8
-    everywhere else; keys drawn with replacement (unsorted, repeating), the four corners of the map in one row, signed weights."""
-    B, H, W, L, N = _geom(shape)
-    seg = _seg()
-    gen = torch.Generator().manual_seed(seed)
-    deg = [8] * (B * L)
-    for r, d in enumerate((0, 1, seg - 1, seg, seg + 1, 2 * seg + 3, N, N + 5)):
-        deg[r] = d
-    deg[L - 1] = 3 * seg + 1
-    if B > 1:
-        deg[L] = 0
-    keys = []
-    for r, d in enumerate(deg):
-        k = torch.randperm(N, generator=gen) if r == 6 else torch.randint(0, N, (d,), generator=gen)
-        if r == 8:
-            k[:4] = torch.tensor([0, W - 1, (H - 1) * W, N - 1])
-        keys.append(k)
-    key = torch.cat(keys).int()
-    row_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(deg, dtype=torch.int64).cumsum(0)])
-    weight = torch.randn(key.numel(), generator=gen)
-    b2 = torch.randn(B, 16, H, W, generator=gen)
-    return row_off, key, weight, b2
-
-
-def _dense_apply(row_off, key, weight, b2, shape):
-    """fold(A_G . V(b2)) / cnt in the dtype of ``b2`` (differentiable in ``weight`` and ``b2``)."""
-    from oracle.ce_oracle import overlap_count, patch_rows
-    B, H, W, L, N = _geom(shape)
-    rows = torch.repeat_interleave(torch.arange(B * L), row_off[1:] - row_off[:-1])
-    a = torch.zeros(B * L, N, dtype=b2.dtype).index_put((rows, key.long()), weight.to(b2.dtype), accumulate=True)
-    agg = torch.bmm(a.view(B, L, N), patch_rows(b2, 7, 1))
-    return _fold(agg, overlap_count(H, W, b2.dtype), H, W)
-
-
-def _padded(b2):
-    return F.pad(b2.permute(0, 2, 3, 1), (0, 0, 3, 3, 3, 3)).contiguous()
 
 
 @functools.lru_cache(maxsize=None)
@@ -112,20 +62,6 @@ def test_empty_graph(shape):
                                           transposed=(torch.zeros(B * N + 1, dtype=torch.int64, device=DEV),
                                                       torch.empty(0, dtype=torch.int32, device=DEV), torch.empty(0, dtype=torch.int32, device=DEV)))
     assert d_w.numel() == 0 and d_b2p.shape == b2p.shape and bool((d_b2p == 0).all())
-
-
-def _gap(st, mode, k, H, W):
-    """The k-th / (k+1)-th relative gap rule of ``test_graph_reproduces_the_block`` (restated)."""
-    if mode == "adaptive" or k >= H * W:
-        return 1.0
-    S = st["S"]
-    if mode == "adaptive_topk":
-        passing = F.relu(S - S.mean(dim=2, keepdim=True) * st["thr"].unsqueeze(2) + st["bias"].unsqueeze(2)) != 0
-        S = torch.where(passing, S, torch.full_like(S, -1.0))
-    top = S.topk(k + 1, dim=2).values
-    ok = top[..., k] > 0
-    rel = (top[..., k - 1] - top[..., k]) / top[..., k - 1].clamp(min=1e-30)
-    return float(torch.where(ok, rel, torch.ones_like(rel)).min())
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[5], CASES[7], CASES[9]], ids=_id)
@@ -275,19 +211,6 @@ def test_other_widths_and_precisions(kind):
     bound = 3.0 * e_32 + 1e-6 + (2.0 ** -11 if half else 0.0)
     print(f"[graph_apply] {kind}: e_lib {e_lib:.2e}, e_ref32 {e_32:.2e}, bound {bound:.2e}")
     assert e_lib <= bound
-
-
-def _state(ce):
-    return {n: t.clone() for n, t in ce.state_dict().items()}, ce._pack_key, ce._pack_epoch
-
-
-def _refused(ce, x, call, word):
-    before = _state(ce)
-    msg = _same_forward_after(ce, x, call)
-    after = _state(ce)
-    assert word in msg, msg
-    assert all(torch.equal(before[0][n], after[0][n]) for n in before[0])
-    return msg
 
 
 def test_refusals_leave_the_module_alone():

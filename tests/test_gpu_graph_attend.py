@@ -11,92 +11,26 @@ import functools
 
 import pytest
 import torch
-import torch.nn.functional as F
 
+from tests.graph_reference import (CASES, SCALE, SHAPES, _GRAD_NAMES, _band, _check, _crafted, _dense_a, _dense_on_structure,
+                                  _edge_reference, _gap, _geom, _id, _inputs, _level_features, _module, _on_edges, _oracle, _refused,
+                                  _rows_of, _seed)
 from tests.helpers import normwise
-from tests.test_gpu_graph_apply import _crafted, _gap, _geom, _refused
-from tests.test_gpu_patch_graph import CASES, SHAPES, _fold, _id, _inputs, _module, _oracle, _seed, ambiguity
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-SCALE = 10.0
 VARIANTS = [(True, "reference"), (False, "reference"), (True, "edges"), (False, "edges")]          # (with tau, normalize)
-_LEVELS = torch.tensor([0.5, 0.75, 1.0, 1.25, 1.5], dtype=torch.float64)
 
 
 def _vid(v):
     return ("tau" if v[0] else "notau") + "-" + v[1]
 
 
-def _rows_of(row_off):
-    return torch.repeat_interleave(torch.arange(row_off.numel() - 1), row_off[1:] - row_off[:-1])
-
-
-def _edge_scores(wq, x, rows, key, L, N):
-    """S_e out of the dense product [B L, N]."""
-    B = wq.shape[0]
-    S = torch.bmm(wq, x.transpose(1, 2)).reshape(B * L, N)
-    return S[rows, key.long()]
-
-
 @functools.lru_cache(maxsize=None)
 def _features(shape, seed=7):
-    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU for the crafted graph of ``shape``: non-negative random rows -- the keys at
-    five levels 0.5 .. 1.5 of a common random direction plus a tenth of noise, so that a row's scores come in separated bands --, each
-    query row scaled so that its largest score is 1.6; tau_r midway between the two adjacent sorted (distinct) scores of the row with the
-    widest gap in the middle half of the sorted list (a single score: half of it)."""
+    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU for the crafted graph of ``shape`` (``_level_features``)."""
     row_off, key, _, _ = _crafted(shape)
-    B, H, W, L, N = _geom(shape)
-    gen = torch.Generator().manual_seed(seed)
-    base = torch.rand(196, generator=gen, dtype=torch.float64)
-    level = _LEVELS[torch.randint(0, 5, (B, N), generator=gen)]
-    x = level.unsqueeze(2) * (base + 0.1 * torch.rand(B, N, 196, generator=gen, dtype=torch.float64))
-    wq = torch.rand(B, L, 196, generator=gen, dtype=torch.float64)
-    rows = _rows_of(row_off)
-    smax = torch.zeros(B * L, dtype=torch.float64).scatter_reduce(0, rows, _edge_scores(wq, x, rows, key, L, N), "amax")
-    wq = wq * torch.where(smax > 0, 1.6 / smax.clamp(min=1e-30), torch.ones_like(smax)).view(B, L, 1)
-    wq, x = wq.float(), x.float()
-    S = _edge_scores(wq.double(), x.double(), rows, key, L, N)
-    tau = torch.zeros(B * L, dtype=torch.float64)
-    for r in range(B * L):
-        s = torch.unique(S[int(row_off[r]):int(row_off[r + 1])])          # sorted
-        if s.numel() == 1:
-            tau[r] = s[0] / 2
-        elif s.numel() >= 2:
-            gaps = s[1:] - s[:-1]
-            lo = gaps.numel() // 4
-            hi = max(lo + 1, (3 * gaps.numel() + 3) // 4)
-            j = lo + int(gaps[lo:hi].argmax())
-            tau[r] = (s[j] + s[j + 1]) / 2
-    return wq, x, tau.float()
-
-
-def _edge_reference(wq, x, row_off, key, tau, normalize, shape, scale=SCALE):
-    """(weight [E], score [E], logits [E]) in the dtype of ``wq``, differentiable in wq, x, tau."""
-    B, H, W, L, N = _geom(shape)
-    deg = row_off[1:] - row_off[:-1]
-    rows = _rows_of(row_off)
-    S = _edge_scores(wq, x, rows, key, L, N)
-    if tau is not None:
-        m = F.relu(S - tau.reshape(-1)[rows])
-        z, on = S * m * scale, m != 0
-    else:
-        z, on = S * scale, torch.ones_like(S, dtype=torch.bool)
-    pos = torch.arange(key.numel()) - row_off[rows]
-    Z = torch.full((B * L, max(int(deg.max()), 1)), float("-inf"), dtype=wq.dtype).index_put((rows, pos), z)
-    off = (N - deg).clamp(min=0) if normalize == "reference" else torch.zeros_like(deg)
-    M = Z.detach().max(dim=1).values
-    M = torch.where(off > 0, M.clamp(min=0.0), M)
-    M = torch.where(deg > 0, M, torch.zeros_like(M))
-    D = torch.exp(Z - M.unsqueeze(1)).sum(dim=1) + off.to(wq.dtype) * torch.exp(-M)
-    return on.to(wq.dtype) * torch.exp(z - M[rows]) / D[rows], S, z
-
-
-def _check(what, lib, ref64, ref32, slack=1e-6):
-    e_lib = normwise(lib.detach().double().cpu().numpy(), ref64.detach().numpy())
-    e_32 = normwise(ref32.detach().double().numpy(), ref64.detach().numpy())
-    print(f"[graph_attend] {what}: e_lib {e_lib:.2e}, e_ref32 {e_32:.2e}, ratio {e_lib / max(e_32, 1e-30):.2f}")
-    assert e_lib <= 3.0 * e_32 + slack, (what, e_lib, e_32)
+    return _level_features(row_off, key, shape, seed)
 
 
 @functools.lru_cache(maxsize=None)
@@ -229,19 +163,9 @@ def test_edges_normalisation_sums_to_one():
         assert float(err) <= 1e-5 and bool((sums[deg == 0] == 0).all())
 
 
-def _band(st64, g, mode, k):
-    """[E] bool: the edges of ``g`` (on the CPU) inside the threshold band of test_gpu_patch_graph.ambiguity."""
-    thr_amb, _ = ambiguity(st64, mode, k)
-    return thr_amb.view(-1, g.N)[g.rows(), g.key.long()]
-
-
-def _on_edges(st, name, g):
-    return st[name].reshape(-1, g.N)[g.rows(), g.key.long()]
-
-
 def _check_against_export(what, got, g, st64, st32, mode, k, over_pairs=False):
     """``attend_graph``'s arrays against the export's on the export's own structure: scores on every edge, weights outside the band.
-    The band may hold at most 5e-4 of the edges (``over_pairs``: of all B L N pairs, the count test_gpu_patch_graph.check_edges caps)."""
+    The band may hold at most 5e-4 of the edges (``over_pairs``: of all B L N pairs, the count graph_reference.check_edges caps)."""
     band = _band(st64, g, mode, k)
     share = float(band.sum()) / max(g.B * g.L * g.N if over_pairs else g.n_edges, 1)
     print(f"[graph_attend] {what}: {int(band.sum())} of {g.n_edges} edges in the threshold band")
@@ -288,30 +212,6 @@ def test_round_trip(shape, case):
         err = normwise(out.double().cpu().numpy(), ref.double().cpu().numpy())
         print(f"[graph_attend] seed {seed} {shape} {case} scan={scan}: forward_on_graph(graph) vs forward {err:.2e} (bound {bound:.0e})")
         assert err <= bound, (scan, err)
-
-
-def _dense_on_structure(x, prm, member, margin, shape, scale=SCALE):
-    """The block's output with its weights recomputed on a structure given as a [B, L, N] 0/1 mask: dagl.py:208-272 with the mask in the
-    place of the selection, in the dtype of ``x`` (differentiable in ``x`` and ``prm``)."""
-    from oracle.ce_oracle import overlap_count, patch_rows, same_pad
-    B, H, W, L, N = _geom(shape)
-    b1 = F.conv2d(x, prm["g.weight"], prm["g.bias"], padding=1)
-    b2 = F.conv2d(x, prm["theta.weight"], prm["theta.bias"])
-    wq = F.relu(F.linear(patch_rows(b1, 7, 4), prm["fc1.0.weight"], prm["fc1.0.bias"]))
-    xk = F.relu(F.linear(patch_rows(b1, 7, 1), prm["fc2.0.weight"], prm["fc2.0.bias"]))
-    S = torch.bmm(wq, xk.transpose(1, 2))
-    m = member.to(x.dtype)
-    if margin:
-        xq, _ = same_pad(x, 7, 4)
-        thr = F.conv2d(xq, prm["thr_conv.weight"], prm["thr_conv.bias"], stride=4).reshape(B, -1)
-        bias = F.conv2d(xq, prm["bias_conv.weight"], prm["bias_conv.bias"], stride=4).reshape(B, -1)
-        m = F.relu(S - (S.mean(dim=2) * thr - bias).unsqueeze(2)) * m
-    A = F.softmax(S * m * scale, dim=2) * (m != 0).to(x.dtype)
-    return _fold(torch.bmm(A, patch_rows(b2, 7, 1)), overlap_count(H, W, x.dtype), H, W)
-
-
-_GRAD_NAMES = ("g.weight", "g.bias", "theta.weight", "theta.bias", "fc1.0.weight", "fc1.0.bias", "fc2.0.weight", "fc2.0.bias",
-               "thr_conv.weight", "thr_conv.bias", "bias_conv.weight", "bias_conv.bias")
 
 
 @pytest.mark.parametrize("case", [CASES[1], CASES[5], CASES[9]], ids=_id)
@@ -384,7 +284,6 @@ def test_margin_and_normalize_arguments():
 def _oracles_of(kind):
     """(st64, st32) of test 6's module: the half module sees half-rounded input and weights, the oracle gets the same values."""
     from oracle.ce_oracle import ce_forward_oracle
-    from tests.test_gpu_patch_graph import _dense_a
     shape, (variant, gain, mode, k) = SHAPES[0], ("sparse", 1.2, "adaptive", 0)
     cin, half = (32, False) if kind == "in_channels_32" else (64, True)
     x0, prm = _inputs(12, shape, variant, gain, cin)

@@ -12,17 +12,14 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.graph_reference import (CASES, KSHAPES, SHAPES, _GRAD_NAMES, _band, _dense_apply, _dense_on_structure, _edge_scores, _gap,
+                                  _geom, _graph, _id, _inputs, _level_features, _module, _on_edges, _oracle, _padded, _refused, _rows_of,
+                                  _seg)
 from tests.helpers import normwise
-from tests.test_gpu_graph_apply import _dense_apply, _gap, _geom, _padded, _refused, _seg
-from tests.test_gpu_graph_attend import _GRAD_NAMES, _LEVELS, _band, _dense_on_structure, _edge_scores, _on_edges, _rows_of
-from tests.test_gpu_patch_graph import CASES, SHAPES, _id, _inputs, _module, _oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 SCALE = 10.0
-KSHAPES = [(1, 8, 8),        # L = 4, N = 64: the long row holds more edges than there are keys
-           (2, 20, 36),      # L = 45, N = 720, two images: empty rows on both sides of the image boundary
-           (1, 45, 45)]      # odd sizes, L = 144, N = 2025
 VARIANTS = [(True, "reference"), (False, "reference"), (True, "edges"), (False, "edges")]          # (with tau, normalize)
 MSHAPES = [(1, 48, 48), (2, 20, 36)]
 MCASES = [CASES[5], CASES[1]]                                                                       # top-k 8, adaptive
@@ -31,39 +28,6 @@ SEED = 11
 
 def _vid(v):
     return ("tau" if v[0] else "notau") + "-" + v[1]
-
-
-@functools.lru_cache(maxsize=None)
-def _graph(shape, seed=5):
-    """(row_off, key, b2) on the CPU.  Per image: an empty first row, a row of 3 SEG + 1 edges (it crosses at least three segments; at
-    8x8 it is also the row with more edges than keys), short rows of 1 .. 5 edges that share a segment, a row of N + 5 edges (every key
-    once and five repeats) where the image has rows to spare, 8 edges elsewhere, an empty last row -- so the first and the last row of
-    the array are empty and, in a batch of two, two empty rows meet at the image boundary.  Keys are drawn with replacement: unsorted,
-    repeating.  (An 8x8 map has four query rows: empty, long, one short row that shares the long row's last segment, empty.)"""
-    B, H, W, L, N = _geom(shape)
-    seg = _seg()
-    gen = torch.Generator().manual_seed(seed)
-    deg = []
-    for b in range(B):
-        d = [8] * L
-        d[0] = d[L - 1] = 0
-        d[1] = 3 * seg + 1
-        for r, n in zip(range(2, L - 1), (3, 1, 5, 2, 3, 4)):
-            d[r] = n
-        if L > 12:
-            d[9] = N + 5
-        deg += d
-    keys = []
-    for r, d in enumerate(deg):
-        if d == N + 5:
-            k = torch.cat([torch.randperm(N, generator=gen), torch.randint(0, N, (5,), generator=gen)])
-        else:
-            k = torch.randint(0, N, (d,), generator=gen)
-        keys.append(k)
-    key = torch.cat(keys).int()
-    row_off = torch.cat([torch.zeros(1, dtype=torch.int64), torch.tensor(deg, dtype=torch.int64).cumsum(0)])
-    b2 = torch.randn(B, 16, H, W, generator=gen)
-    return row_off, key, b2
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,33 +44,9 @@ def _bad_key(shape):
 
 @functools.lru_cache(maxsize=None)
 def _features(shape, seed=7):
-    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU, built as test_gpu_graph_attend._features builds them: keys at five levels of
-    a common direction, every query row scaled so that its largest score on the graph is 1.6, tau_r midway in the widest gap of the
-    middle half of the row's sorted distinct scores."""
+    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU for the graph of ``shape`` (``_level_features``)."""
     row_off, key, _ = _graph(shape)
-    B, H, W, L, N = _geom(shape)
-    gen = torch.Generator().manual_seed(seed)
-    base = torch.rand(196, generator=gen, dtype=torch.float64)
-    level = _LEVELS[torch.randint(0, 5, (B, N), generator=gen)]
-    x = level.unsqueeze(2) * (base + 0.1 * torch.rand(B, N, 196, generator=gen, dtype=torch.float64))
-    wq = torch.rand(B, L, 196, generator=gen, dtype=torch.float64)
-    rows = _rows_of(row_off)
-    smax = torch.zeros(B * L, dtype=torch.float64).scatter_reduce(0, rows, _edge_scores(wq, x, rows, key, L, N), "amax")
-    wq = wq * torch.where(smax > 0, 1.6 / smax.clamp(min=1e-30), torch.ones_like(smax)).view(B, L, 1)
-    wq, x = wq.float(), x.float()
-    S = _edge_scores(wq.double(), x.double(), rows, key, L, N)
-    tau = torch.zeros(B * L, dtype=torch.float64)
-    for r in range(B * L):
-        s = torch.unique(S[int(row_off[r]):int(row_off[r + 1])])
-        if s.numel() == 1:
-            tau[r] = s[0] / 2
-        elif s.numel() >= 2:
-            gaps = s[1:] - s[:-1]
-            lo = gaps.numel() // 4
-            hi = max(lo + 1, (3 * gaps.numel() + 3) // 4)
-            j = lo + int(gaps[lo:hi].argmax())
-            tau[r] = (s[j] + s[j + 1]) / 2
-    return wq, x, tau.float()
+    return _level_features(row_off, key, shape, seed)
 
 
 def _forward_reference(wq, x, b2, row_off, key, tau, normalize, shape, scale=SCALE):

@@ -10,9 +10,8 @@ import functools
 import pytest
 import torch
 
+from tests.graph_reference import _LEVELS, _check, _edge_reference, _geom, _rows_of
 from tests.graph_refresh_reference import candidate_mask, csr_of, mask_of, select_mask
-from tests.test_gpu_graph_apply import _geom
-from tests.test_gpu_graph_attend import _LEVELS, _check, _edge_reference, _rows_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -54,7 +53,7 @@ def _crafted(shape, seed=5):
 
 @functools.lru_cache(maxsize=None)
 def _features(shape, seed=7):
-    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU, banded as test_gpu_graph_attend._features builds them: keys at five levels of
+    """(wq [B,L,196], x [B,N,196], tau [B*L]) fp32 on the CPU, banded as graph_reference._level_features builds them: keys at five levels of
     a common random direction plus a tenth of noise, every third key row a BITWISE copy of its left neighbour (exact ties among the
     candidates of a window), each query row scaled so that its largest candidate score (radius 2) is 1.6; tau_r midway in the widest gap
     of the middle half of the row's sorted distinct candidate scores; row R_FAIL: above every score."""

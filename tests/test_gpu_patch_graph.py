@@ -8,163 +8,16 @@ relative and its score lies within tau relative of them.  tau = 2e-5: all produc
 product over 196 terms is within 196 * 2^-24 = 1.2e-5 relative in any order; the row mean gets the rest.  Outside both bands the
 membership must be the oracle's; inside a pair may go either way -- but at most 5e-4 of all pairs and 10 % of the rows may be
 ambiguous at all, so that the band cannot hide a failure."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.graph_reference import (CASES, SHAPES, _dense_a, _fold, _id, _inputs, _module, _oracle, _same_forward_after, _seed, ambiguity,
+                                  check_edges, check_structure, check_values, membership)
 from tests.helpers import normwise
 
 pytestmark = pytest.mark.gpu
-
-TAU = 2e-5
-SHAPES = [(2, 24, 20),      # N = 480, not a multiple of 256; L = 30; offsets cross an image boundary
-          (1, 33, 70),      # odd sizes
-          (2, 45, 45),      # unscreened size; degrees past 256 and 1024
-          (1, 64, 64)]      # screened size; N = 4096, several block strides per row
-# (variant, sparse_gain, mode, k)
-CASES = [("default", 2.0, "adaptive", 0), ("sparse", 1.65, "adaptive", 0), ("sparse", 1.2, "adaptive", 0),
-         ("allpass", 2.0, "adaptive", 0), ("nonepass", 2.0, "adaptive", 0),
-         ("default", 2.0, "topk", 8), ("default", 2.0, "topk", 64), ("default", 2.0, "topk", 100), ("default", 2.0, "topk", 5000),
-         ("sparse", 1.2, "adaptive_topk", 16), ("sparse", 1.2, "adaptive_topk", 100)]
-SEEDS = (11, 12, 13)
-
-
-def _seed(shape, case):
-    return SEEDS[(SHAPES.index(shape) + CASES.index(case)) % 3]
-
-
-def _id(v):
-    return "x".join(str(e) for e in v) if isinstance(v, tuple) else str(v)
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(seed, shape, variant, gain, in_channels=64):
-    from dagl_amd.synth import make_ce_params, make_features
-    B, H, W = shape
-    prm = {n: torch.from_numpy(a) for n, a in make_ce_params(seed, in_channels=in_channels, variant=variant, sparse_gain=gain).items()}
-    return torch.from_numpy(make_features(seed, B, in_channels, H, W)), prm
-
-
-def _dense_a(st, mode, scale=10.0):
-    """A = softmax(scale S m) mask_b of ``_graph_core`` from an oracle's stages, in their precision: [B, L, N]."""
-    S, mb = st["S"], st["mask_b"]
-    if mode == "topk":
-        m = mb
-    else:
-        m = F.relu(S - S.mean(dim=2, keepdim=True) * st["thr"].unsqueeze(2) + st["bias"].unsqueeze(2)) * mb
-    return F.softmax(S * m * scale, dim=2) * mb
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle(seed, shape, variant, gain, mode, k, dtype=torch.float64, in_channels=64, scale=10.0):
-    """The oracle's stages + A, computed once per case and shared (read-only) by the tests."""
-    from oracle.ce_oracle import ce_forward_oracle
-    x, prm = _inputs(seed, shape, variant, gain, in_channels)
-    torch.set_num_threads(16)
-    with torch.no_grad():
-        out, st = ce_forward_oracle(x, prm, mode=mode, k=k if mode != "adaptive" else None, dtype=dtype, stages=True,
-                                    softmax_scale=scale)
-        st = {n: st[n] for n in ("S", "thr", "bias", "mask_b", "b2", "cnt")}
-        st["A"] = _dense_a(st, mode, scale)
-    return st
-
-
-def _module(seed, shape, variant, gain, mode, k, in_channels=64, half=False, scale=10):
-    from dagl_amd.ce import CE
-    x, prm = _inputs(seed, shape, variant, gain, in_channels)
-    ce = CE(in_channels=in_channels, softmax_scale=scale)
-    ce.load_state_dict(prm, strict=True)
-    ce.select_mode = mode
-    if mode != "adaptive":
-        ce.select_k = k
-    ce = ce.to("cuda:0").eval()
-    x = x.to("cuda:0")
-    if half:
-        ce, x = ce.half(), x.half()
-    return ce, x
-
-
-def ambiguity(st, mode, k):
-    """(threshold-ambiguous, rank-ambiguous) [B, L, N] bool from the fp64 oracle's stages."""
-    S = st["S"]
-    N = S.shape[2]
-    thr_amb = torch.zeros_like(S, dtype=torch.bool)
-    if mode != "topk":
-        mt = S.mean(dim=2, keepdim=True) * st["thr"].unsqueeze(2)
-        bs = st["bias"].unsqueeze(2).expand_as(S)
-        thr_amb = (S - mt + bs).abs() < TAU * (S.abs() + mt.abs() + bs.abs())
-    rank_amb = torch.zeros_like(S, dtype=torch.bool)
-    if mode != "adaptive" and k < N:
-        rankable = torch.ones_like(S, dtype=torch.bool)
-        if mode == "adaptive_topk":
-            rankable = F.relu(S - mt + bs) != 0
-        top = torch.where(rankable, S, torch.full_like(S, -1.0)).topk(k + 1, dim=2).values
-        sk, sk1 = top[..., k - 1:k], top[..., k:k + 1]                 # (-1: the row has fewer rankable keys -- nothing to rank)
-        close = (sk1 >= 0) & ((sk - sk1) < TAU * sk)
-        rank_amb = close & (S >= sk1 * (1 - TAU)) & (S <= sk * (1 + TAU)) & (rankable | thr_amb)
-    return thr_amb, rank_amb
-
-
-def membership(g):
-    """[B, L, N] bool from a PatchGraph (on the CPU)."""
-    deg = g.degrees().reshape(-1)
-    rows = torch.repeat_interleave(torch.arange(g.B * g.L), deg)
-    m = torch.zeros(g.B * g.L, g.N, dtype=torch.bool)
-    m[rows, g.key.long()] = True
-    return m.view(g.B, g.L, g.N), rows
-
-
-def check_structure(g, mode, k, variant):
-    off, key = g.row_off, g.key.long()
-    assert off.dtype == torch.int64 and g.key.dtype == torch.int32 and g.weight.dtype == torch.float32
-    assert off.numel() == g.B * g.L + 1 and int(off[0]) == 0 and bool((off[1:] >= off[:-1]).all()) and int(off[-1]) == key.numel()
-    assert key.numel() == 0 or (int(key.min()) >= 0 and int(key.max()) < g.N)
-    rows = torch.repeat_interleave(torch.arange(g.B * g.L), g.degrees().reshape(-1))
-    same_row = rows[1:] == rows[:-1]
-    assert bool((key[1:] > key[:-1])[same_row].all()), "keys must ascend strictly inside a row"
-    if mode == "topk":
-        assert bool((g.degrees() == min(k, g.N)).all())
-    if variant == "nonepass":
-        assert key.numel() == 0
-    if (variant == "allpass" and mode == "adaptive") or (mode == "topk" and k >= g.N):
-        assert bool((g.degrees() == g.N).all()) and torch.equal(key, torch.arange(g.N).repeat(g.B * g.L))
-
-
-def check_edges(g, st, mode, k):
-    """Membership against the oracle outside the band; returns (lib membership, rows of its edges, rows holding a rank-ambiguous pair)."""
-    mem, rows = membership(g)
-    thr_amb, rank_amb = ambiguity(st, mode, k)
-    amb = thr_amb | rank_amb
-    want = st["mask_b"] != 0
-    wrong = (mem != want) & ~amb
-    share, rank_rows = float(amb.double().mean()), rank_amb.any(dim=2)
-    print(f"[graph] edges {g.n_edges}, degree mean {float(g.degrees().double().mean()):.1f} max {int(g.degrees().max())}; ambiguous pairs "
-          f"{int(amb.sum())} ({share:.1e} of all), of them on the other side {int(((mem != want) & amb).sum())}; rows with a rank-ambiguous "
-          f"pair {int(rank_rows.sum())} of {rank_rows.numel()}; wrong outside the band {int(wrong.sum())}")
-    assert share <= 5e-4, "the band must not hide a failure: too many ambiguous pairs"
-    assert float(rank_rows.double().mean()) <= 0.10, "the band must not hide a failure: too many rows with a rank-ambiguous pair"
-    assert int(wrong.sum()) == 0
-    return mem, rows, rank_rows
-
-
-def check_values(g, mem, rows, rank_rows, st64, st32, mode, what):
-    """Weights and scores over the edges both sides have, against the reference in its own precision (the bound of test_gpu_trunk)."""
-    keep_row = ~rank_rows if mode != "adaptive" else torch.ones_like(rank_rows)
-    want = st64["mask_b"] != 0
-    common_lib = want.view(-1, g.N)[rows, g.key.long()] & keep_row.view(-1)[rows]            # per lib edge
-    common_32 = (st32["mask_b"] != 0) & want & keep_row.unsqueeze(2)
-    if int(common_lib.sum()) == 0 or int(common_32.sum()) == 0:          # (an empty graph: check_edges has compared the sets)
-        print(f"[graph] {what}: no common edges to compare values on")
-        return
-    for name, lib, ref in (("weight", g.weight, "A"), ("score", g.score, "S")):
-        r64 = st64[ref].view(-1, g.N)
-        e_lib = normwise(lib[common_lib].numpy(), r64[rows, g.key.long()][common_lib].numpy())
-        e_32 = normwise(st32[ref][common_32].numpy(), st64[ref][common_32].numpy())
-        print(f"[graph] {what} {name}: e_lib {e_lib:.2e}, e_ref32 {e_32:.2e}, ratio {e_lib / max(e_32, 1e-30):.2f}")
-        assert e_lib <= 3.0 * e_32 + 1e-6, (what, name, e_lib, e_32)
 
 
 @pytest.mark.parametrize("case", CASES, ids=_id)
@@ -245,12 +98,6 @@ def test_chunk_height_does_not_change_the_graph(shape, case):
             assert torch.equal(getattr(g, name), getattr(ref, name)), (rpc, name)
 
 
-def _fold(agg, cnt, H, W):
-    """[B, L, 784] aggregated rows (c, kh, kw) -> [B, 16, H, W], dagl.py:265-272."""
-    z = F.fold(agg.transpose(1, 2), (H, W), (7, 7), padding=3, stride=4)
-    return z / cnt
-
-
 @pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[5], CASES[7], CASES[9]], ids=_id)
 @pytest.mark.parametrize("shape", SHAPES, ids=_id)
 def test_graph_reproduces_the_block(shape, case):
@@ -320,17 +167,6 @@ def test_exact_ties_go_to_the_lower_key():
         tied += int(band.numel() > k)
     print(f"[graph] ties: {checked} of {g.L} rows compared key by key, {tied} of them with more than k keys tied at the k-th place")
     assert tied > 0, "the case must hold rows with an exact tie at the k-th place"
-
-
-def _same_forward_after(ce, x, refused):
-    from dagl_amd import DaglError
-    with torch.no_grad():
-        before = ce(x).clone()
-    with pytest.raises(DaglError) as err:
-        refused()
-    with torch.no_grad():
-        assert torch.equal(ce(x), before)
-    return str(err.value)
 
 
 def test_refusals_leave_the_module_alone():

@@ -2,7 +2,7 @@
 module's own selection rule on them (``ops.graph_refresh``, csrc/graph_refresh.hip).
 
 Fixed point: ``refresh_graph(x, graph(x))`` is ``graph(x)``, so the export's own checks apply unchanged (``check_structure`` /
-``check_edges`` / ``check_values`` of test_gpu_patch_graph.py: the band TAU = 2e-5, its caps, the bound 3 e_32 + 1e-6).  Another frame:
+``check_edges`` / ``check_values`` of graph_reference.py: the band TAU = 2e-5, its caps, the bound 3 e_32 + 1e-6).  Another frame:
 the expected graph is the fp64 oracle's S, thr, bias of the new frame with the selection rule of tests/graph_refresh_reference.py on the
 candidate sets of the old graph; membership must match outside the oracle's two bands, the rank band taken among the candidates."""
 import functools
@@ -11,13 +11,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.graph_reference import (ATOPK16, COMBOS, S0, S2, TAU, TOPK8, _band, _cid, _dense_a, _gap, _inputs, _mod, _module, _oracle,
+                                  _refused, check_edges, check_structure, check_values, membership)
 from tests.graph_refresh_reference import candidate_mask, select_mask
 from tests.helpers import normwise
-from tests.test_gpu_forward_with_graph import ATOPK16, COMBOS, S0, S2, TOPK8, _cid, _mod
-from tests.test_gpu_graph_apply import _gap, _refused
-from tests.test_gpu_graph_attend import _band
-from tests.test_gpu_patch_graph import (TAU, _dense_a, _inputs, _module, _oracle, check_edges, check_structure, check_values,
-                                        membership)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -119,7 +116,7 @@ def restricted(st, cand, mode, k):
 
 
 def ambiguity_on(st, mode, k, cand):
-    """``ambiguity`` of test_gpu_patch_graph.py with ``rankable`` additionally restricted to the candidates; both bands are reported on
+    """``ambiguity`` of graph_reference.py with ``rankable`` additionally restricted to the candidates; both bands are reported on
     the candidates only."""
     S = st["S"]
     N = S.shape[2]
