@@ -87,6 +87,9 @@ SIGNATURES = {
     "dagl_graph_refresh_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i]),
     "dagl_graph_refresh": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 4
                            + [C.c_int64, _vp, _vp, _sz]),
+    "dagl_graph_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),
+    "dagl_graph_step": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 5
+                        + [C.c_int64, _vp, _vp, _sz]),
     "dagl_ce_list_width": (_i, [_i, _i]),
     "dagl_ce_range_check": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(_i)]),
     "dagl_ce_core_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

@@ -243,6 +243,7 @@ class CE(nn.Module):
         self._ws_lists_bwd = ops.Workspace()
         self._ws_lists_csr = ops.Workspace()
         self._ws_refresh = ops.Workspace()    # refresh_graph(): the degrees and the staged candidates
+        self._ws_step = ops.Workspace()       # step_graph(): the aggregated rows and, with the graph, the refresh's regions
         self._pack_key = None
         self._pack_epoch = 0           # bumped by invalidate_packed()
         self._f32_cache = {}              # fp32 copies of half-precision parameters (model.half(), DN_Gray/model/__init__.py:98-99)
@@ -834,8 +835,21 @@ class CE(nn.Module):
         outside 0..8, and a graph whose largest degree times ``(2 radius + 1)^2`` exceeds ``ops.graph_refresh_max_candidates()``.  The
         largest degree is read once per graph (kept on the object, as ``validate``'s verdict).  The module's state (packed weights,
         top-k policy, range verdicts, ``_train_dense``) is untouched: the call has a workspace of its own."""
-        what = "refresh_graph"
-        if torch.cuda.is_current_stream_capturing():
+        radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "refresh_graph", radius, margin, normalize, features)
+        B, _, H, W = b.shape
+        with torch.no_grad():
+            wq_rows, x_rows, tau, _b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
+            csr = ops.graph_refresh(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, radius=radius,
+                                    tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
+                                    normalize=normalize, max_row_edges=longest, workspace=self._ws_refresh, hw=(H, W))
+            return self._refreshed(graph, csr, poisoned, k_eff)
+
+    def _refresh_arguments(self, b: torch.Tensor, graph, what: str, radius, margin, normalize: str, features: str, host_read: bool = True):
+        """The refusals ``refresh_graph`` and ``step_graph`` share, raised before any launch -> (radius, k_eff, margin, largest degree).
+        ``host_read`` False (the step without its graph): the call itself reads nothing on the host, so a stream under capture is
+        served when what the checks read has been read before -- the graph validated, its largest degree known."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if capturing and host_read:
             raise DaglError(f"CE.{what}: not available while the stream is being captured (the edge count is read on the host)")
         self._check_given_graph(b, graph, what)
         if normalize not in ("reference", "edges"):
@@ -854,21 +868,60 @@ class CE(nn.Module):
                 raise DaglError(f"CE: select_k={self.select_k} < 1")
             k_eff = min(int(self.select_k), H * W)
         margin = self.select_mode != "topk" if margin is None else bool(margin)
+        if capturing and graph._max_degree is None:
+            raise DaglError(f"CE.{what}: the graph's largest degree is not known and the stream is being captured (max_degree() reads "
+                            "one word on the host): call graph.max_degree() before the capture")
         longest, cap = graph.max_degree(), ops.graph_refresh_max_candidates()
         if longest * (2 * radius + 1) ** 2 > cap:
             err = DaglError(f"CE.{what}: the graph's largest degree {longest} times (2 radius + 1)^2 = {(2 * radius + 1) ** 2} is "
                             f"{longest * (2 * radius + 1) ** 2} candidates, a row may expand into {cap}")
             err.code = ERR_UNSUPPORTED
             raise err
-        with torch.no_grad():
-            wq_rows, x_rows, tau, _b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
-            csr = ops.graph_refresh(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, radius=radius,
-                                    tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
-                                    normalize=normalize, max_row_edges=longest, workspace=self._ws_refresh, hw=(H, W))
-            g = graph._like(csr["row_off"], csr["key"], poisoned(csr["weight"]), poisoned(csr["score"]))     # (no second host read)
+        return radius, k_eff, margin, longest
+
+    def _refreshed(self, graph, csr: dict, poisoned, k_eff: int):
+        """The ``PatchGraph`` of a refresh's arrays: this module's ``mode`` and ``k``, valid keys, no second host read."""
+        g = graph._like(csr["row_off"], csr["key"], poisoned(csr["weight"]), poisoned(csr["score"]))
         g.mode, g.k = self.select_mode, k_eff
         g._valid = True                              # (every candidate is a key of the map)
         return g
+
+    def step_graph(self, b: torch.Tensor, graph, *, radius: int = 1, margin=None, normalize: str = "reference", features: str = "fp32",
+                   want_graph: bool = True):
+        """A sequence step in one call -> ``(out, PatchGraph | None)``: ``graph`` moved to the input ``b`` exactly as
+        ``refresh_graph(b, graph, radius=..., margin=..., normalize=..., features=...)`` moves it (the same bits in every array, the same
+        ``mode``, ``k`` and valid keys), and the block's output for ``b`` on that result, ``fold(A . V(theta(b))) / cnt`` with the new
+        graph's fp32 weights -- from ONE prologue and projection pass and one scoring of the candidates (``ops.graph_step``,
+        csrc/graph_refresh.hip), where ``refresh_graph`` followed by ``forward_on_graph`` computes the features twice and scores the
+        kept edges a second time.  For a sequence: ``out, g = ce.step_graph(frame, g)``.
+
+        ``out`` [B,16,H,W] has the input's dtype; each element of an aggregated row is one fp32 fmaf chain over the row's kept keys in
+        ascending order, so ``out`` carries the same bits with ``want_graph`` True or False and on every repeat; it differs from
+        ``forward_on_graph`` on the returned graph by the order of fp32 sums alone.  A query whose row comes out empty contributes zeros.
+
+        ``want_graph=False`` returns ``(out, None)``: the structure of a key frame is kept and only the output is wanted on each
+        following frame.  That form reads nothing on the host and can be captured into a HIP graph once the graph has been validated and
+        its largest degree read (``graph.validate()``, ``graph.max_degree()``; ``CE.graph`` validates its result); otherwise it is refused
+        under capture before any launch.  ``want_graph=True`` makes the one host read ``refresh_graph`` makes and is refused under capture.
+
+        Always under ``torch.no_grad()``, ``out.requires_grad`` is False: gradients are ``forward_on_graph``'s job on the returned graph.
+        Arguments, selection, the ``features="split16"`` range contract (both results NaN-filled, never wrong numbers) and refusals are
+        ``refresh_graph``'s, all raised before any launch.  The module's state (packed weights, top-k policy, range verdicts,
+        ``_train_dense``) is untouched: the call has a workspace of its own."""
+        want_graph = bool(want_graph)
+        radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "step_graph", radius, margin, normalize, features,
+                                                                 host_read=want_graph)
+        B, _, H, W = b.shape
+        with torch.no_grad():
+            wq_rows, x_rows, tau, b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
+            out, csr, _status = ops.graph_step(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
+                                               radius=radius, tau=tau.contiguous() if tau is not None else None, k=k_eff,
+                                               scale=float(self.softmax_scale), normalize=normalize, max_row_edges=longest,
+                                               want_graph=want_graph, workspace=self._ws_step, hw=(H, W))
+            out = poisoned(out)
+            if b.dtype != torch.float32:
+                out = out.to(b.dtype)
+            return out, (self._refreshed(graph, csr, poisoned, k_eff) if want_graph else None)
 
     def forward_with_graph(self, b: torch.Tensor, *, scores: bool = False, features=None):
         """The block's output for ``b`` AND the patch graph that produced it, from one call -> ``(out, PatchGraph)``: the list-form route

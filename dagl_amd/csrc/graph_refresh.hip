@@ -19,6 +19,12 @@
 //   row_scan_kernel               select.hip: int32 degrees -> int64 offsets, row_off_out[B L] = E
 //   graph_refresh_compact_kernel  a wavefront per row copies its staged entries to row_off_out[r]: ordered, no atomics
 //
+// The route's second entry, dagl_graph_step, is the refresh AND the block's output on its result: graph_step_rows_kernel is the same row
+// body (rf_row) with an epilogue -- the kept entries' weights and the offsets of their value patches stay in the LDS in ascending key
+// order, and the row's sum_c weight_c V[key_c] goes to agg [B L, 784] (ga_gather_run: one fmaf chain per element, the same bits from a
+// wavefront and a block); every exit of the body writes a row of zeros first, the workspace is never cleared.  launch_fold follows.
+// Without graph outputs the degree, the staging, the scan and the copy are left out: nothing then depends on a count the host reads.
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -100,15 +106,28 @@ __device__ __forceinline__ double rf_sum(double v, double* sh) {
     return s;
 }
 
-template <int T, int CAP>
-__global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs f) {
-    __shared__ int s_sort[CAP];               // the expanded candidates, sorted; then the order word of a passing candidate
-    __shared__ int s_key[CAP];                // the distinct candidates, ascending
-    __shared__ float s_sc[CAP];               // their scores
+// a row of zeros to agg [B L, 784]: what every exit of the aggregating flavour leaves before it returns (the workspace is not cleared)
+template <int T>
+__device__ __forceinline__ void rf_zero_row(float* agg, int row) {
+    float4* o = reinterpret_cast<float4*>(agg + (size_t)row * P);
+    for (int c = threadIdx.x; c < GA_C4; c += T) o[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// the row body of both kernels below.  AGG (dagl_graph_step): the row's weighted sum of value patches goes to v.out [B L, 784] as well,
+// and the graph outputs may be absent (f.st_key null: no degree, no staging writes)
+template <int T, int CAP, bool AGG>
+__device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v) {
+    __shared__ long long s_of[CAP];           // two int arrays (below); AGG: at the end the float4 offset of each kept entry's value patch
+                                              // in the map, compacted -- no array of its own: at 2048 candidates 16 KiB more LDS halve the
+                                              // blocks per CU, and the row body lives on them
+    __shared__ float s_sc[CAP];               // the scores of the distinct candidates; AGG: at the end the kept entries' weights, compacted
     __shared__ unsigned char s_flag[CAP];     // bits 0-1: the margin is not 0 (the candidate passes), bit 2: kept
     __shared__ int sh_i[T / 64];
     __shared__ float sh_f[T / 64];
     __shared__ double sh_d[T / 64];
+    int* const s_sort = reinterpret_cast<int*>(s_of);     // the expanded candidates, sorted; then the order word of a passing candidate
+    int* const s_key = s_sort + CAP;                      // the distinct candidates, ascending
+    const bool graph_out = !AGG || f.st_key != nullptr;
     const int t = threadIdx.x;
     const int row = blockIdx.x;
     const long long lo = gt_clamp(a.row_off[row], a.E), hi = gt_clamp(a.row_off[row + 1], a.E);
@@ -116,9 +135,10 @@ __global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs 
     const int wd = 2 * f.radius + 1, w2 = wd * wd;
     if (deg_in <= 0 || deg_in > f.max_row_edges || deg_in * w2 > CAP) {          // (the same in every thread)
         if (t == 0) {
-            f.deg[row] = 0;
+            if (graph_out) f.deg[row] = 0;
             if (deg_in > 0) atomicAdd(f.status, 1ull);
         }
+        if (AGG) rf_zero_row<T>(v.out, row);
         return;
     }
     // 1. expand: entry idx = (edge, window offset); what falls off the map or comes from a key off the map sorts to the end
@@ -214,8 +234,11 @@ __global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs 
     for (int c = c0; c < c1; ++c) cnt += (s_flag[c] >> 2) & 1;
     int kept;
     pos = rf_scan<T>(cnt, sh_i, kept);
-    if (t == 0) f.deg[row] = kept;
-    if (kept == 0) return;                                       // (the same in every thread)
+    if (t == 0 && graph_out) f.deg[row] = kept;
+    if (kept == 0) {                                             // (the same in every thread)
+        if (AGG) rf_zero_row<T>(v.out, row);
+        return;
+    }
     const bool off_graph = !a.edges_only && kept < a.N;
     float mx = -INFINITY;
     for (int c = c0; c < c1; ++c) {
@@ -233,15 +256,62 @@ __global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs 
     if (off_graph) sum += (double)(a.N - kept) * exp(-(double)M);
     // 7. the kept entries, ascending keys, to the front of the row's staging region (kept <= n <= raw = its size)
     const long long base = lo * w2;
-    for (int c = c0; c < c1; ++c) {
+    //    AGG: a thread also keeps the weight and the patch offset of its kept entries (at most PER = CAP / T >= pr of them) in registers
+    constexpr int PER = CAP / T;
+    float my_w[AGG ? PER : 1];
+    long long my_of[AGG ? PER : 1];
+    const int pos0 = pos;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = c0 + i;
+        if (c >= c1) break;
         if (!(s_flag[c] & 4)) continue;
         float mg;
         const float z = gt_logit(a, row, s_sc[c], mg);
-        f.st_key[base + pos] = s_key[c];
-        f.st_score[base + pos] = s_sc[c];
-        f.st_weight[base + pos] = mg != 0.f ? (float)((double)expf(z - M) / sum) : 0.f;
+        const float wgt = mg != 0.f ? (float)((double)expf(z - M) / sum) : 0.f;
+        if (graph_out) {
+            f.st_key[base + pos] = s_key[c];
+            f.st_score[base + pos] = s_sc[c];
+            f.st_weight[base + pos] = wgt;
+        }
+        if (AGG) {
+            my_w[i] = wgt;
+            my_of[i] = ga_source<true>(v, row, s_key[c]);        // (a candidate is a key of the map: never -1)
+        }
         ++pos;
     }
+    if (!AGG) return;
+    // 8. the kept entries' weights and patch offsets to the LDS in compacted (ascending-key) order, over the scores and the two int
+    //    arrays -- every thread has read its own entries of those above: a barrier, the stores (pos0 .. < kept <= n <= CAP), a barrier
+    __syncthreads();
+    pos = pos0;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int c = c0 + i;
+        if (c < c1 && (s_flag[c] & 4)) {
+            s_sc[pos] = my_w[i];
+            s_of[pos] = my_of[i];
+            ++pos;
+        }
+    }
+    __syncthreads();
+    // 9. agg[row] = sum_c weight_c V[key_c] over the kept entries in ascending key order: a float4 column of the 784-float row at a time,
+    //    one fmaf chain per element (ga_gather_run), so a wavefront (columns lane, lane + 64, ...) and a block (a column per thread of
+    //    0..195) give the same bits
+    const float4* src = reinterpret_cast<const float4*>(v.src);
+    float4* o = reinterpret_cast<float4*>(v.out + (size_t)row * P);
+    for (int c = t; c < GA_C4; c += T) o[c] = ga_gather_run(src + (c / 28) * v.Wp * (CH / 4) + c % 28, s_of, s_sc, 0, kept);
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs f) {
+    rf_row<T, CAP, false>(a, f, GaArgs{});
+}
+
+// dagl_graph_step's: the refresh's row and its aggregated output row from the same kept entries
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v) {
+    rf_row<T, CAP, true>(a, f, v);
 }
 
 // a wavefront per row: its staged entries to their place in the output
@@ -265,51 +335,73 @@ __global__ __launch_bounds__(RF_COPY_ROWS * 64) void graph_refresh_compact_kerne
     }
 }
 
-struct RefreshWs { int32_t* deg; int32_t* st_key; float* st_score; float* st_weight; size_t bytes; };
+struct RefreshWs { float* agg; int32_t* deg; int32_t* st_key; float* st_score; float* st_weight; size_t bytes; };
 
-static RefreshWs refresh_carve(void* ws, size_t n_rows, size_t staged) {
+// agg: the step's [B L, 784] aggregated rows; graph: the degrees and the staging region (the step without graph outputs has neither)
+static RefreshWs refresh_carve(void* ws, size_t n_rows, size_t staged, bool agg = false, bool graph = true) {
     Carver cv(ws);
-    RefreshWs w;
-    w.deg = cv.take<int32_t>(n_rows);
-    w.st_key = cv.take<int32_t>(staged + 1);
-    w.st_score = cv.take<float>(staged + 1);
-    w.st_weight = cv.take<float>(staged + 1);
+    RefreshWs w{};
+    if (agg) w.agg = cv.take<float>(n_rows * P);
+    if (graph) {
+        w.deg = cv.take<int32_t>(n_rows);
+        w.st_key = cv.take<int32_t>(staged + 1);
+        w.st_score = cv.take<float>(staged + 1);
+        w.st_weight = cv.take<float>(staged + 1);
+    }
     w.bytes = cv.bytes();
     return w;
 }
 
+// b2p / out: the step's value map and output, both null for the refresh;  row_off_out null (the step alone): no graph comes out
 struct RefreshCall {
     GraphAttendCall c; int max_row_edges, radius, k; bool keep_all, block_rows;
     int64_t* row_off_out; int32_t* key_out; float* weight_out; float* score_out; int64_t capacity; int64_t* status;
+    const float* b2p; float* out;
 };
 
 static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const RefreshCall& r, void* workspace) {
     const int n_rows = B * g.L, wd = 2 * r.radius + 1, w2 = wd * wd;
+    const bool agg = r.out != nullptr, graph = r.row_off_out != nullptr;
     DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
     if (r.c.E == 0) {
-        DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
+        if (graph) DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
+        if (agg) DAGL_HIP_TRY(hipMemsetAsync(r.out, 0, (size_t)B * CH * g.N * sizeof(float), s));      // fold(0) / cnt
         return DAGL_OK;
     }
-    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2);
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2, agg, graph);
     const GtArgs a = gt_args(B, g, r.c);
     RfArgs f{};
     f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
     f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
     f.status = reinterpret_cast<unsigned long long*>(r.status);
     // short rows (top-k 8 at radius 1: 72 candidates) take a wavefront each, longer ones a block of four
-    if (!r.block_rows && (long long)r.max_row_edges * w2 <= RF_WAVE_CAP) {
-        hipLaunchKernelGGL((graph_refresh_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f);
+    const bool wave = !r.block_rows && (long long)r.max_row_edges * w2 <= RF_WAVE_CAP;
+    if (agg) {
+        GaArgs v = ga_map_args(B, g, r.b2p, nullptr, nullptr, nullptr, 0);
+        v.out = w.agg;
+        if (wave) {
+            hipLaunchKernelGGL((graph_step_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, v);
+        } else {
+            hipLaunchKernelGGL((graph_step_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, v);
+        }
+        DAGL_LAUNCH_CHECK("graph_step_rows_kernel");
     } else {
-        hipLaunchKernelGGL((graph_refresh_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f);
+        if (wave) {
+            hipLaunchKernelGGL((graph_refresh_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f);
+        } else {
+            hipLaunchKernelGGL((graph_refresh_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f);
+        }
+        DAGL_LAUNCH_CHECK("graph_refresh_rows_kernel");
     }
-    DAGL_LAUNCH_CHECK("graph_refresh_rows_kernel");
-    const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
-    if (rc) return rc;
-    hipLaunchKernelGGL(graph_refresh_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0, s,
-                       n_rows, w2, (long long)r.c.E, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out,
-                       r.weight_out, r.score_out, (long long)r.capacity);
-    DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
-    return DAGL_OK;
+    if (graph) {
+        const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
+        if (rc) return rc;
+        hipLaunchKernelGGL(graph_refresh_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0,
+                           s, n_rows, w2, (long long)r.c.E, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out,
+                           r.weight_out, r.score_out, (long long)r.capacity);
+        DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
+    }
+    return agg ? launch_fold(s, B, g, w.agg, r.out) : DAGL_OK;
 }
 
 static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
@@ -321,6 +413,51 @@ static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_
     DAGL_REQUIRE(total_edges * w2 < (1ll << 31), "%s: total_edges (2 radius + 1)^2 = %lld staged candidates, 2^31 or more", who,
                  (long long)(total_edges * w2));
     return DAGL_OK;
+}
+
+// the checks and the call of both entries.  b2p / out null: the refresh.  Else the step, where the four graph outputs may all be null
+// (the output alone: capacity_edges is not looked at)
+static int graph_refresh_entry(const char* who, void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                               const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                               const float* tau, int k, float scale, int flags, float* out, int64_t* row_off_out, int32_t* key_out,
+                               float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
+                               size_t ws_bytes, bool step) {
+    int rc = refresh_shape_ok(who, B, H, W, total_edges, radius);
+    if (rc) return rc;
+    const bool graph = !step || row_off_out || key_out || weight_out || score_out;
+    const bool outputs = status_out && (!graph || (row_off_out && (total_edges == 0 || (key_out && weight_out && score_out))));
+    if ((rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags, outputs,
+                                DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
+        return rc;
+    if (step) {
+        DAGL_REQUIRE(b2p && out, "%s: null tensor pointer", who);
+        DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+    }
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    if ((int64_t)max_row_edges * w2 > RF_CAP) {
+        set_error("%s: max_row_edges (2 radius + 1)^2 = %lld candidates per row, more than the %d a row may expand into", who,
+                  (long long)((int64_t)max_row_edges * w2), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    const Grid g = make_grid(H, W);
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    int64_t may = total_edges * w2;
+    if (!keep_all && k > 0 && (int64_t)B * g.L * k < may) may = (int64_t)B * g.L * k;
+    if (graph && capacity_edges < may) {
+        set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
+        return DAGL_ERR_WORKSPACE;
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)B * g.L, (size_t)(total_edges * w2), step, graph).bytes;
+    if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
+    RefreshCall r{};
+    r.c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
+    r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.row_off_out = graph ? row_off_out : nullptr; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out;
+    r.capacity = capacity_edges; r.status = status_out; r.b2p = b2p; r.out = out;
+    return launch_graph_refresh((hipStream_t)stream, B, g, r, workspace);
 }
 
 }  // namespace dagl
@@ -340,38 +477,25 @@ int dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_rows, 
                        const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau, int k, float scale,
                        int flags, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges,
                        int64_t* status_out, void* workspace, size_t ws_bytes) {
-    const char* who = "dagl_graph_refresh";
-    int rc = refresh_shape_ok(who, B, H, W, total_edges, radius);
-    if (rc) return rc;
-    const bool outputs = row_off_out && status_out && (total_edges == 0 || (key_out && weight_out && score_out));
-    if ((rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags, outputs,
-                                DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
-        return rc;
-    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
-    DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
-    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
-    if ((int64_t)max_row_edges * w2 > RF_CAP) {
-        set_error("%s: max_row_edges (2 radius + 1)^2 = %lld candidates per row, more than the %d a row may expand into", who,
-                  (long long)((int64_t)max_row_edges * w2), RF_CAP);
-        return DAGL_ERR_UNSUPPORTED;
-    }
-    const Grid g = make_grid(H, W);
-    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
-    int64_t may = total_edges * w2;
-    if (!keep_all && k > 0 && (int64_t)B * g.L * k < may) may = (int64_t)B * g.L * k;
-    if (capacity_edges < may) {
-        set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
-        return DAGL_ERR_WORKSPACE;
-    }
-    const size_t need = refresh_carve(nullptr, (size_t)B * g.L, (size_t)(total_edges * w2)).bytes;
-    if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
-    RefreshCall r{};
-    r.c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
-    r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
-    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
-    r.row_off_out = row_off_out; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.capacity = capacity_edges;
-    r.status = status_out;
-    return launch_graph_refresh((hipStream_t)stream, B, g, r, workspace);
+    return graph_refresh_entry("dagl_graph_refresh", stream, B, H, W, wq_rows, x_rows, nullptr, row_off, key, total_edges, max_row_edges,
+                               radius, tau, k, scale, flags, nullptr, row_off_out, key_out, weight_out, score_out, capacity_edges,
+                               status_out, workspace, ws_bytes, false);
+}
+
+// the refresh and the block's output on its result in one call (no ABI bump: found by symbol)
+size_t dagl_graph_step_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int want_graph) {
+    if (refresh_shape_ok("dagl_graph_step_workspace_bytes", B, H, W, total_edges, radius)) return 0;
+    return refresh_carve(nullptr, (size_t)B * make_grid(H, W).L, (size_t)total_edges * (2 * radius + 1) * (2 * radius + 1), true,
+                         want_graph != 0).bytes;
+}
+
+int dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p, const int64_t* row_off,
+                    const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau, int k, float scale, int flags,
+                    float* out, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges,
+                    int64_t* status_out, void* workspace, size_t ws_bytes) {
+    return graph_refresh_entry("dagl_graph_step", stream, B, H, W, wq_rows, x_rows, b2p, row_off, key, total_edges, max_row_edges, radius,
+                               tau, k, scale, flags, out, row_off_out, key_out, weight_out, score_out, capacity_edges, status_out,
+                               workspace, ws_bytes, true);
 }
 
 }  // extern "C"

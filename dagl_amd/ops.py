@@ -632,48 +632,120 @@ def graph_refresh(wq_rows, x_rows, row_off, key, *, radius: int = 1, tau=None, k
     are short (for measurements; the same bits).  ``hw``: the map (H, W) -- the windows need it; it may be left out only where L and N
     fit one map alone.  The same arrays give the same bits on every call."""
     lib = _lib.load()
+    B, H, W, E, flags, radius, k = _graph_refresh_operands("graph_refresh", wq_rows, x_rows, row_off, key, radius, tau, k, normalize,
+                                                           keep_all, block_rows, hw)
+    max_row_edges = _graph_refresh_longest("graph_refresh", row_off, E, max_row_edges)
+    dev = wq_rows.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_refresh_workspace_bytes", B, H, W, E, radius)
+    head, key_out, weight, score, cap = _graph_refresh_arrays(dev, B * wq_rows.shape[1], E, radius, k, keep_all)
+    check(lib.dagl_graph_refresh(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
+                                 max_row_edges, radius, _ptr(tau), k, float(scale), flags, head.data_ptr(), _ptr(key_out, E > 0),
+                                 _ptr(weight, E > 0), _ptr(score, E > 0), cap, head[-2:].data_ptr(), a, nbytes), "dagl_graph_refresh")
+    del buf
+    return _graph_refresh_result("graph_refresh", head, key_out, weight, score, max_row_edges)
+
+
+def _graph_refresh_operands(who: str, wq_rows, x_rows, row_off, key, radius, tau, k, normalize, keep_all, block_rows, hw):
+    """What ``graph_refresh`` and ``graph_step`` ask of their operands -> (B, H, W, E, flags, radius, k)."""
     if hw is None and isinstance(wq_rows, torch.Tensor) and isinstance(x_rows, torch.Tensor) and wq_rows.dim() == 3 and x_rows.dim() == 3:
         # (the windows need the map itself: L and N alone leave H x W and W x H apart only when one of them does not fit)
         L, N = wq_rows.shape[1], x_rows.shape[1]
         maps = list(_maps_of(L, N))
         if len(maps) > 1:
-            raise DaglError(f"graph_refresh: {len(maps)} maps have {N} keys and {L} queries ({maps[0][0]}x{maps[0][1]}, "
+            raise DaglError(f"{who}: {len(maps)} maps have {N} keys and {L} queries ({maps[0][0]}x{maps[0][1]}, "
                             f"{maps[1][0]}x{maps[1][1]}, ...): pass hw=(H, W)")
         hw = maps[0] if maps else None
-    B, H, W, E, flags = _graph_attend_operands("graph_refresh", wq_rows, x_rows, row_off, key, tau, normalize, hw)
-    radius, k = int(radius), int(k)
-    if torch.cuda.is_current_stream_capturing():
-        raise DaglError("graph_refresh: not available under stream capture (the edge count is read on the host)")
-    if max_row_edges is None:
-        max_row_edges = int((row_off[1:] - row_off[:-1]).max()) if E > 0 else 0
-    max_row_edges = int(max_row_edges)
+    B, H, W, E, flags = _graph_attend_operands(who, wq_rows, x_rows, row_off, key, tau, normalize, hw)
     if keep_all:
         flags |= _lib.GRAPH_REFRESH_KEEP_ALL
     if block_rows:
         flags |= _lib.GRAPH_REFRESH_BLOCK_ROWS
-    dev = wq_rows.device
-    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_refresh_workspace_bytes", B, H, W, E, radius)
-    L = wq_rows.shape[1]
+    return B, H, W, E, flags, int(radius), int(k)
+
+
+def _graph_refresh_longest(who: str, row_off, E: int, max_row_edges) -> int:
+    """The refusal under capture of a call that reads the edge count, then ``max_row_edges`` (None = one host read of it)."""
+    if torch.cuda.is_current_stream_capturing():
+        raise DaglError(f"{who}: not available under stream capture (the edge count is read on the host)")
+    if max_row_edges is None:
+        max_row_edges = int((row_off[1:] - row_off[:-1]).max()) if E > 0 else 0
+    return int(max_row_edges)
+
+
+def _graph_refresh_arrays(dev, n_rows: int, E: int, radius: int, k: int, keep_all: bool):
+    """The output arrays at capacity -> (head [n_rows + 3] int64, key, weight, score, capacity): the offsets and the two status words
+    share ``head``, so E and the status come from one host read."""
     cap = E * (2 * radius + 1) ** 2
     if k > 0 and not keep_all:
-        cap = min(cap, B * L * k)
-    # (the offsets and the two status words in one array: E and the status come from one host read)
-    head = torch.empty(B * L + 3, device=dev, dtype=torch.int64)
+        cap = min(cap, n_rows * k)
+    head = torch.empty(n_rows + 3, device=dev, dtype=torch.int64)
     key_out = torch.empty(cap, device=dev, dtype=torch.int32)
     weight = torch.empty(cap, device=dev, dtype=torch.float32)
     score = torch.empty(cap, device=dev, dtype=torch.float32)
-    status = head[B * L + 1:]
-    check(lib.dagl_graph_refresh(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
-                                 max_row_edges, radius, _ptr(tau), k, float(scale), flags, head.data_ptr(), _ptr(key_out, E > 0),
-                                 _ptr(weight, E > 0), _ptr(score, E > 0), cap, status.data_ptr(), a, nbytes), "dagl_graph_refresh")
-    del buf
-    total, overlong, _most = (int(v) for v in head[B * L:].tolist())          # the one synchronisation
+    return head, key_out, weight, score, cap
+
+
+def _graph_refresh_result(who: str, head, key_out, weight, score, max_row_edges: int) -> dict:
+    """The one host read (E and the status words), the overlong-row refusal, the arrays as views of their first E entries."""
+    total, overlong, _most = (int(v) for v in head[-3:].tolist())          # the one synchronisation
     if overlong:
-        err = DaglError(f"graph_refresh: {overlong} row(s) hold more than max_row_edges = {max_row_edges} edges; they were left empty, "
+        err = DaglError(f"{who}: {overlong} row(s) hold more than max_row_edges = {max_row_edges} edges; they were left empty, "
                         "not truncated: state the input's largest degree")
         err.code = _lib.ERR_UNSUPPORTED
         raise err
-    return dict(row_off=head[:B * L + 1], key=key_out[:total], weight=weight[:total], score=score[:total])
+    return dict(row_off=head[:-2], key=key_out[:total], weight=weight[:total], score=score[:total])
+
+
+@_on_device
+def graph_step(wq_rows, x_rows, b2p, row_off, key, *, radius: int = 1, tau=None, k: int = 0, scale: float = 10.0,
+               normalize: str = "reference", keep_all: bool = False, max_row_edges=None, want_graph: bool = True,
+               workspace: "Workspace | None" = None, hw=None, block_rows: bool = False):
+    """``graph_refresh`` and the block's output on its result in one call (``dagl_graph_step``, csrc/graph_refresh.hip) ->
+    (out [B,16,H,W], dict | None, status): the operands and arguments of ``graph_refresh`` plus ``b2p``, the zero-bordered NHWC value map
+    [B,H+6,W+6,16] (it names the map: ``hw`` is not needed).  The dict holds, bit for bit, what ``graph_refresh`` returns for the same
+    arguments; ``out = fold(agg) / cnt`` with ``agg[r] = sum_c weight_c V[key_c]`` over the kept entries of row r in ascending key order,
+    one fp32 fmaf chain per element -- the same bits with ``want_graph`` True or False, a wavefront or a block per row (``block_rows``),
+    on every call.  A row with nothing kept gives zeros.  ``status``: the device int64[2] tensor (rows longer than ``max_row_edges``, the
+    largest number of distinct candidates a row had).
+
+    ``want_graph=True``: one host read (E and the status words; not under stream capture); a row longer than declared raises
+    ``DaglError`` with ``code == ERR_UNSUPPORTED`` as in ``graph_refresh``.  ``want_graph=False``: the output alone -- nothing is read
+    on the host and the call can be captured, so ``max_row_edges`` must be given; a row longer than declared contributes zeros and is
+    counted in ``status[0]``, which is left for the caller to read; it is never truncated."""
+    lib = _lib.load()
+    who = "graph_step"
+    _need(b2p, "b2p")
+    map_hw = _value_map(who, b2p)[1:]
+    if hw is not None and tuple(int(v) for v in hw) != tuple(map_hw):
+        raise DaglError(f"{who}: hw={tuple(hw)} but b2p is the value map of a {map_hw[0]}x{map_hw[1]} image")
+    B, H, W, E, flags, radius, k = _graph_refresh_operands(who, wq_rows, x_rows, row_off, key, radius, tau, k, normalize, keep_all,
+                                                           block_rows, map_hw)
+    if b2p.shape[0] != B:
+        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    if want_graph:
+        max_row_edges = _graph_refresh_longest(who, row_off, E, max_row_edges)
+    elif max_row_edges is None:
+        raise DaglError(f"{who}: want_graph=False needs max_row_edges, the input's largest degree"
+                        + (" (reading it on the host is not available under stream capture)"
+                           if torch.cuda.is_current_stream_capturing() else " (the call itself reads nothing on the host)"))
+    max_row_edges = int(max_row_edges)
+    dev = wq_rows.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_step_workspace_bytes", B, H, W, E, radius, 1 if want_graph else 0)
+    out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32)
+    if want_graph:
+        head, key_out, weight, score, cap = _graph_refresh_arrays(dev, B * wq_rows.shape[1], E, radius, k, keep_all)
+        status = head[-2:]
+    else:
+        head = key_out = weight = score = None
+        cap, status = 0, torch.empty(2, device=dev, dtype=torch.int64)
+    check(lib.dagl_graph_step(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
+                              _ptr(key, E > 0), E, max_row_edges, radius, _ptr(tau), k, float(scale), flags, out.data_ptr(), _ptr(head),
+                              _ptr(key_out, E > 0), _ptr(weight, E > 0), _ptr(score, E > 0), cap, status.data_ptr(), a, nbytes),
+          "dagl_graph_step")
+    del buf
+    if not want_graph:
+        return out, None, status
+    return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
 
 
 @_on_device

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_fc_grad16_plan,
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_fc_grad16_plan,
  * dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
@@ -455,6 +455,30 @@ int    dagl_graph_refresh(void* stream, int B, int H, int W, const float* wq_row
                           float* weight_out, float* score_out, int64_t capacity_edges,
                           int64_t* status_out /* [2]: rows longer than max_row_edges, largest candidate count met */, void* workspace,
                           size_t ws_bytes);
+
+/* ---- a sequence step: the refresh and the block's output on its result in one call: csrc/graph_refresh.hip (detected by symbol) -------
+ * dagl_graph_refresh's operands, limits, flags and outputs, plus the zero-bordered value map b2p [B,H+6,W+6,16] (16-byte aligned, as
+ * dagl_graph_forward takes it) and out [B,16,H,W].  The graph outputs are, bit for bit, what dagl_graph_refresh writes for the same
+ * arguments.  With weight' / key' the kept entries of row r of that result and V the 7x7 patches of the value map,
+ *   agg[r] = sum_c weight'_c V[key'_c],   out = fold(agg) / cnt   (fold and overlap count are dagl_graph_apply's)
+ * each element of agg[r] one fp32 fmaf chain over the kept entries in ascending key order, whichever form of the row kernel runs (a
+ * wavefront or a block per row): no float atomics, the same arrays give the same bits on every call, with or without the graph outputs.
+ * A row with nothing kept -- an empty input row, every candidate failing tau, only keys outside [0, N), a row longer than max_row_edges --
+ * is a row of ZEROS of agg; a row longer than max_row_edges is counted in status_out[0] and never truncated.  total_edges = 0: out is
+ * all zeros.
+ *   row_off_out, key_out, weight_out, score_out ALL NULL: the output alone -- no degrees, no staging, no scan, no copy; capacity_edges is
+ *     not looked at; the two status words are still written.  Some of them NULL (but for key_out / weight_out / score_out at
+ *     total_edges = 0) is DAGL_ERR_INVALID.
+ *   status_out [2] int64 (device), as dagl_graph_refresh.
+ * Workspace: dagl_graph_step_workspace_bytes = the [B L, 784] aggregated rows + (want_graph) dagl_graph_refresh's regions.  Launches: the
+ * row kernel with its aggregation epilogue, (graph outputs) the offsets' scan and the ordered copy, the fold.  Every argument is checked
+ * before the first launch; nothing is read on the host and the call can be captured: the CALLER reads row_off_out[B L] and status_out. */
+size_t dagl_graph_step_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int want_graph);
+int    dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                       const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                       const float* tau /* NULL: no margin */, int k /* 0: no rank cut */, float scale, int flags, float* out,
+                       int64_t* row_off_out /* [B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
+                       int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

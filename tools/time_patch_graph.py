@@ -6,6 +6,8 @@
     python tools/time_patch_graph.py --lists [H W]  # what ``CE.forward_with_graph`` costs next to forward + graph, same three graphs
     python tools/time_patch_graph.py --refresh [H W]  # ``CE.refresh_graph`` + ``forward_on_graph`` on a next frame next to ``forward``:
                                                       # top-k 8 at 256 256; with a size (1024 1024) adaptive AND top-16
+    python tools/time_patch_graph.py --step [H W]     # ``CE.step_graph`` (with and without the graph) next to that two-call sequence and
+                                                      # to ``forward``, the same two cases
 """
 import os
 import sys
@@ -290,7 +292,59 @@ def refresh_leg(H, W, big):
               f"{fmt(alone[(radius, False)])}, a block per row {fmt(alone[(radius, True)])}", flush=True)
 
 
+def step_leg(H, W, big):
+    """A sequence step in one call (``step_graph``, radius 1, split-fp16 features, with and without the graph) next to the two-call
+    sequence ``refresh_graph`` + ``forward_on_graph`` and to ``forward`` on the next frame, in one process: the cases and the protocol
+    of ``refresh_leg``.  ``ops.graph_step`` alone (features given), a wavefront and a block per row, next to ``ops.graph_refresh`` +
+    ``ops.graph_forward`` on the same features."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    x2 = torch.roll(x, (1, 1), (2, 3))
+    name, mode, k, variant, gain = ("adaptive AND top-16 (sparse, gain 1.7)", "adaptive_topk", 16, "sparse", 1.7) if big else \
+        ("top-k 8", "topk", 8, "default", 1.65)
+    prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=gain).items()}
+    ce = CE(in_channels=64)
+    ce.load_state_dict(prm, strict=True)
+    ce.select_mode, ce.select_k = mode, k
+    ce = ce.to(dev).eval()
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    f16 = dict(radius=1, features="split16")
+    with torch.no_grad():
+        g = ce.graph(x)
+        g.max_degree()
+        fwd = _events(lambda: ce(x2))
+        chain = _events(lambda: ce.forward_on_graph(x2, ce.refresh_graph(x2, g, **f16), features="split16"))
+        both = _events(lambda: ce.step_graph(x2, g, **f16))
+        alone = _events(lambda: ce.step_graph(x2, g, want_graph=False, **f16))
+        out, g2 = ce.step_graph(x2, g, **f16)
+        two = ce.forward_on_graph(x2, g2, features="split16")
+        gap = float((out - two).abs().max() / two.abs().max())
+        wq, xk, tau, b2p, _ = ce._graph_features(x2, mode != "topk", True, False)
+        wq, xk, b2p, tau = wq.contiguous(), xk.contiguous(), b2p.contiguous(), (tau.contiguous() if tau is not None else None)
+        feats = _events(lambda: ce._graph_features(x2, mode != "topk", True, False))
+        ws, wsr, wsf = ops.Workspace(), ops.Workspace(), ops.Workspace()
+        call = dict(radius=1, tau=tau, k=k, scale=float(ce.softmax_scale), max_row_edges=g.max_degree())
+        k_step = {(w, blk): _events(lambda: ops.graph_step(wq, xk, b2p, g.row_off, g.key, want_graph=w, block_rows=blk, workspace=ws, **call))
+                  for w in (True, False) for blk in (False, True)}
+        k_ref = _events(lambda: ops.graph_refresh(wq, xk, g.row_off, g.key, workspace=wsr, hw=(H, W), **call))
+        k_fwd = _events(lambda: ops.graph_forward(wq, xk, b2p, g2.row_off, g2.key, tau=tau, scale=float(ce.softmax_scale), workspace=wsf))
+    print(f"[1,64,{H},{W}] {name}: graph(x) {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {g.max_degree()}; stepped to x2 "
+          f"{g2.n_edges} edges\n"
+          f"    forward(x2) {fmt(fwd)}; refresh_graph + forward_on_graph (radius 1, split16) {fmt(chain)}\n"
+          f"    step_graph {fmt(both)} = {both[0] / chain[0]:.2f} of the two calls, {both[0] / fwd[0]:.2f} of forward; "
+          f"step_graph(want_graph=False) {fmt(alone)} = {alone[0] / chain[0]:.2f} of the two calls, {alone[0] / fwd[0]:.2f} of forward\n"
+          f"    step_graph out against forward_on_graph on its graph: {gap:.1e} normwise; the features alone (_graph_features) {fmt(feats)}\n"
+          f"    ops.graph_step alone {fmt(k_step[(True, False)])}, a block per row {fmt(k_step[(True, True)])}; without the graph "
+          f"{fmt(k_step[(False, False)])}, a block per row {fmt(k_step[(False, True)])}; ops.graph_refresh alone {fmt(k_ref)}; "
+          f"ops.graph_forward alone on the result {fmt(k_fwd)}", flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--step":
+        return step_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--refresh":
         return refresh_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--lists":
