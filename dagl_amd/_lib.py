@@ -125,6 +125,7 @@ SIGNATURES = {
     "dagl_conv_pair_backward_supported": (_i, [_i, _i, _i]),
     "dagl_conv_pair_backward_scratch_bytes": (_sz, [_i, _i, _i]),
     "dagl_conv_pair_backward": (_i, [_vp, _i, _i, _i] + [_vp] * 11),
+    "dagl_conv_pair_backward_plan": (_i, [_i] * 3 + [C.POINTER(C.c_int32)]),
     "dagl_col_sum": (_i, [_vp, _sz, _i, _vp, _vp, _vp]),
     "dagl_profile_create": (_i, [_i, C.POINTER(_vp)]),
     "dagl_profile_destroy": (_i, [_vp]),

@@ -392,6 +392,15 @@ size_t dagl_conv_pair_backward_scratch_bytes(int B, int H, int W) {
     return n_part * (4 * CG_PART + 32) * sizeof(float);
 }
 
+// (detected by symbol) the strips of the two launches, by the function the launcher and the scratch size plan with
+int dagl_conv_pair_backward_plan(int B, int H, int W, int32_t out[4]) {
+    DAGL_REQUIRE(dagl_conv_pair_backward_supported(B, H, W) && out,
+                 "dagl_conv_pair_backward_plan: bad argument (W a multiple of 4 and <= 256, out required)");
+    const int rw = cg_rows_per_block(B, H, 4), rx = cg_rows_per_block(B, H, 1);
+    out[0] = rw; out[1] = (H + rw - 1) / rw; out[2] = rx; out[3] = (H + rx - 1) / rx;
+    return DAGL_OK;
+}
+
 int dagl_conv_pair_backward(void* stream, int B, int H, int W, const float* x, const float* d_b1p, const float* d_b2p,
                             const float* g_w, const float* th_w, float* d_x, float* d_g_w, float* d_g_b, float* d_th_w,
                             float* d_th_b, void* scratch) {

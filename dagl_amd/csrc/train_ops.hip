@@ -224,12 +224,17 @@ size_t dagl_col_sum_scratch_bytes(size_t rows, int cols) {
 }
 
 int dagl_col_sum(void* stream, size_t rows, int cols, const float* src, float* out, void* scratch) {
-    DAGL_REQUIRE(cols >= 1 && cols <= 256 && src && out && scratch, "dagl_col_sum: bad argument (1 <= cols <= 256, scratch required)");
+    DAGL_REQUIRE(cols >= 1 && cols <= 256 && out && (rows == 0 || (src && scratch)),
+                 "dagl_col_sum: bad argument (1 <= cols <= 256, scratch required)");
+    if (rows == 0) {                               // no partials: dagl_col_sum_scratch_bytes(0, cols) is 0 and the scratch is not touched
+        DAGL_HIP_TRY(hipMemsetAsync(out, 0, (size_t)cols * sizeof(float), (hipStream_t)stream));
+        return DAGL_OK;
+    }
     const int n_part = (int)((rows + CS_ROWS - 1) / CS_ROWS);
-    hipLaunchKernelGGL(col_sum_partial_kernel, dim3(n_part > 0 ? n_part : 1), dim3(256), 0, (hipStream_t)stream, rows, cols, src,
+    hipLaunchKernelGGL(col_sum_partial_kernel, dim3(n_part), dim3(256), 0, (hipStream_t)stream, rows, cols, src,
                        static_cast<double*>(scratch));
     DAGL_LAUNCH_CHECK("col_sum_partial_kernel");
-    hipLaunchKernelGGL(col_sum_final_kernel, dim3((cols + 3) / 4), dim3(256), 0, (hipStream_t)stream, n_part > 0 ? n_part : 1, cols,
+    hipLaunchKernelGGL(col_sum_final_kernel, dim3((cols + 3) / 4), dim3(256), 0, (hipStream_t)stream, n_part, cols,
                        static_cast<const double*>(scratch), out);
     DAGL_LAUNCH_CHECK("col_sum_final_kernel");
     return DAGL_OK;

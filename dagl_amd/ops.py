@@ -1484,6 +1484,15 @@ def conv_pair_backward_supported(B: int, H: int, W: int) -> bool:
     return bool(_lib.load().dagl_conv_pair_backward_supported(B, H, W))
 
 
+def conv_pair_backward_plan(B: int, H: int, W: int) -> dict:
+    """The strips of one ``dagl_conv_pair_backward`` call (``dagl_conv_pair_backward_plan``, host only), by the function the launcher
+    and the scratch size plan with: ``rows_w`` rows per block and ``strips_w`` strips per image of the parameter gradients' launch,
+    ``rows_x`` / ``strips_x`` of the input gradient's."""
+    out = (C.c_int32 * 4)()
+    check(_lib.load().dagl_conv_pair_backward_plan(int(B), int(H), int(W), out), "dagl_conv_pair_backward_plan")
+    return dict(zip(("rows_w", "strips_w", "rows_x", "strips_x"), (int(v) for v in out)))
+
+
 @_on_device
 def conv_pair_backward(x, d_b1p, d_b2p, g_w, th_w, need_x: bool = True, need_params: bool = True):
     """Backward of g (3x3) and theta (1x1), 64 -> 16, on the maps themselves (``dagl_conv_pair_backward``): x [B,64,H,W] and the

@@ -171,7 +171,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
  * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_fc_grad16_plan,
- * dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
+ * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -679,6 +679,11 @@ size_t dagl_conv_pair_backward_scratch_bytes(int B, int H, int W);
 int    dagl_conv_pair_backward(void* stream, int B, int H, int W, const float* x, const float* d_b1p, const float* d_b2p,
                                const float* g_w, const float* th_w, float* d_x, float* d_g_w, float* d_g_b, float* d_th_w,
                                float* d_th_b, void* scratch);
+/* (detected by symbol) A read-out for tests: the strips of the two launches of one call, computed on the host by the function the
+ * launcher and dagl_conv_pair_backward_scratch_bytes plan with (no device access):
+ * out = { rows per block and strips per image of the parameter gradients' launch, the same two of the input gradient's launch };
+ * the scratch holds B * strips partial sums of (4 * 2560 + 32) floats.  -1 for a shape that is not supported or a NULL out.   */
+int    dagl_conv_pair_backward_plan(int B, int H, int W, int32_t out[4]);
 
 /* The four prologue convolutions alone (dagl.py:208-215): b1/b2 as zero-bordered NHWC maps
  * [B,H+6,W+6,16], thr/bias [B,L] (both NULL = skip the two 7x7 heads).  `scratch` = 8*B*L floats of

@@ -345,3 +345,70 @@ def test_prologue16_matches_the_fp32_prologue_forward_and_backward():
         for a, c in zip(res[True], res[False]):
             assert torch.isfinite(a).all()
             assert normwise(a.numpy(), c.numpy()) <= 2e-6, normwise(a.numpy(), c.numpy())
+
+
+# ---- rounding quality of the fp32 training kernels, per element -------------------------------------------------------------------
+# The unit is u = sum |a||b| of an output element in fp64, the bound (2 r32 + 1) 2^-22 u: r32 is the largest per-element error of
+# torch's fp32 CPU result of the same operation in units of 2^-22 u -- a reference, not the code under test --, doubled for another
+# summation order, plus 1 for the epilogue.  (The paths themselves are checked bit for bit on integers in test_gpu_gemm32_paths.py and
+# test_gpu_conv_pair_backward_plans.py.)
+U22 = 2.0 ** -22
+
+
+def _worst_ratio(got, ref, u, r32):
+    return float(((got.double() - ref).abs() / ((2.0 * r32 + 1.0) * U22 * u)).max())
+
+
+def test_gemm_f32_rounds_like_an_fp32_product_per_element():
+    """(300, 130, 8200) on randn operands, split into 8 K slices and as one chain, with chunked accumulation (7 tiles) on and off.
+    Measured: r32 = 0.58 (torch.matmul, fp32, CPU); worst |err| / bound on the MI355X: split 0.126, split + chunks 0.032,
+    one chain 0.438, one chain + chunks 0.044."""
+    from dagl_amd import ops
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(8200)
+    M, N, K = 300, 130, 8200
+    A = torch.randn(M, K, generator=g); Bm = torch.randn(K, N, generator=g)
+    ref = A.double() @ Bm.double()
+    u = A.double().abs() @ Bm.double().abs()
+    r32 = float((((A @ Bm).double() - ref).abs() / (U22 * u)).max())
+    print(f"[train32] gemm ({M},{N},{K}) r32 {r32:.4f} (torch fp32 CPU, units of 2^-22 u)")
+    assert 0.0 < r32 < 8.0                                              # a sane fp32 reference
+    Ad, Bd = A.to(dev), Bm.to(dev)
+    for split in (True, False):
+        for chunk in (0, 7):
+            got = ops.gemm_f32(Ad, Bd, True, False, chunk_tiles=chunk, split_k=split).cpu()
+            worst = _worst_ratio(got, ref, u, r32)
+            print(f"[train32] gemm ({M},{N},{K}) split_k={split} chunk_tiles={chunk}: worst |err| / bound {worst:.4f}")
+            assert worst <= 1.0, (split, chunk, worst)
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 37, 64), (3, 100, 4)])
+def test_conv_pair_backward_rounds_like_fp32_autograd_per_element(B, H, W):
+    """All five gradients on randn operands against fp64 autograd, per element, in units of the same autograd on the magnitudes.
+    Measured: r32 = 0.99 / 0.93 (fp32 autograd of the two conv2d calls, CPU, largest of the five outputs) at [2,64,37,64] / [3,64,100,4];
+    worst |err| / bound on the MI355X: d_x 0.260 / 0.214, d_g_w 0.015 / 0.041, d_g_b 0.004 / 0.012, d_th_w 0.012 / 0.031,
+    d_th_b 0.006 / 0.014."""
+    from dagl_amd import ops
+    from tests.test_conv_pair_backward_plan_host import NAMES, autograd64
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(H * 131 + W)
+    x = torch.randn(B, 64, H, W, generator=g)
+    gw = torch.randn(16, 64, 3, 3, generator=g) * 0.1
+    tw = torch.randn(16, 64, 1, 1, generator=g) * 0.2
+    d1 = torch.randn(B, H, W, 16, generator=g); d2 = torch.randn(B, H, W, 16, generator=g)
+    ops5 = (x, gw, tw, d1, d2)
+    ref = autograd64(*(t.double() for t in ops5))
+    u = autograd64(*(t.double().abs() for t in ops5))
+    cpu32 = autograd64(*ops5)                                           # (the same function in fp32: torch's own kernels)
+    r32 = max(float(((c.double() - r).abs() / (U22 * uu)).max()) for c, r, uu in zip(cpu32, ref, u))
+    print(f"[train32] conv_pair_backward [{B},64,{H},{W}] r32 {r32:.4f} (torch fp32 CPU autograd, units of 2^-22 u)")
+    assert 0.0 < r32 < 8.0
+    def padded(d):
+        p = torch.full((B, H + 6, W + 6, 16), 1e30)
+        p[:, 3:3 + H, 3:3 + W] = d
+        return p.to(dev)
+    got = ops.conv_pair_backward(x.to(dev), padded(d1), padded(d2), gw.to(dev), tw.to(dev))
+    for name, t, r, uu in zip(NAMES, got, ref, u):
+        worst = _worst_ratio(t.cpu().reshape(r.shape), r, uu, r32)
+        print(f"[train32] conv_pair_backward [{B},64,{H},{W}] {name}: worst |err| / bound {worst:.4f}")
+        assert worst <= 1.0, (name, worst)
