@@ -90,6 +90,11 @@ SIGNATURES = {
     "dagl_graph_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),
     "dagl_graph_step": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 5
                         + [C.c_int64, _vp, _vp, _sz]),
+    "dagl_ces_stage_fold_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
+    "dagl_ces_stage_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
+    "dagl_graph_stage_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),
+    "dagl_graph_stage_step": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 3 + [_vp, _vp, C.c_int64, _i, _i, C.POINTER(_vp), _i, C.c_float, _i]
+                              + [_vp] * 8 + [C.c_int64, _vp, _vp, _sz]),
     "dagl_ce_list_width": (_i, [_i, _i]),
     "dagl_ce_range_check": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(_i)]),
     "dagl_ce_core_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

@@ -429,4 +429,117 @@ int launch_stage_mix(hipStream_t s, int B, int HW, const float* cat, const float
     return DAGL_OK;
 }
 
+// ------------------------------------------------------------------------------------------------------
+// fold + stage mix in one pass: out = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x from the four heads' aggregated rows
+// ------------------------------------------------------------------------------------------------------
+// agg [4, B, L, 784] head-major, element order (kh, kw, c).  stage_mix_kernel's wave (64 outputs x MIX_TILES tiles of 16 pixels, the
+// weights in registers, fp32 MFMA 16x16x4, pixels along the lanes of the result), but the B operand is folded on the fly: lane (i, g)
+// forms, for its pixel and each head, channels 4g .. 4g+3 of fold(agg_h) / cnt -- the <= 2 x 2 covering windows added in fold_kernel's
+// order, then the division: fold_kernel's bits -- from one float4 per (window, head); the four lane groups of a pixel read the whole
+// 64-byte run.  The [B,64,H,W] concat map never goes to memory.  The product's inner index is permuted to fit that read: MFMA step T
+// (head T / 4) carries concat channel 16 (T / 4) + 4 g + T % 4 in lane group g, the weight fragment follows.  No LDS, no atomics.
+constexpr long long FOLD_MIX_SMALL_WAVES = 2048;          // 4-tile waves below which a tile per wave runs: two per SIMD of the device
+__device__ __forceinline__ int fold_mix_channel(int T, int g) { return 16 * (T >> 2) + 4 * g + (T & 3); }
+
+template <int TILES>
+__global__ __launch_bounds__(256) void stage_fold_mix_kernel(Grid gr, int B, int blocks_per_img, const float* __restrict__ agg,
+                                                             const float* __restrict__ x, const float* __restrict__ mix_w,
+                                                             const float* __restrict__ mix_b, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, g = lane >> 4;
+    const int b = blockIdx.x / blocks_per_img;
+    const int HW = gr.N;
+    const int pw = ((blockIdx.x - b * blocks_per_img) * 4 + wave) * (16 * TILES);
+    if (pw >= HW) return;
+    float w[4][16];                                            // A fragment (n, T): w[o = n*16 + i][c = fold_mix_channel(T, g)]
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int T = 0; T < 16; ++T) w[n][T] = mix_w[(n * 16 + i) * 64 + fold_mix_channel(T, g)];
+    float bo[4][4];
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bo[n][r] = mix_b[n * 16 + 4 * g + r];
+    const size_t head_stride = (size_t)B * gr.L * P;
+    // a tile at a time (not unrolled): its 16 float4 reads in flight, then its 64 MFMAs -- all four tiles' reads at once cost 342 registers
+    // and the second wave per SIMD
+#pragma unroll 1
+    for (int t = 0; t < TILES; ++t) {
+        float av[16];
+        int px = pw + 16 * t + i; if (px >= HW) px = HW - 1;
+        const int y = px / gr.W, xx = px - y * gr.W;
+        // rows r with 4r-3 <= y <= 4r+3: one or two (fold_kernel)
+        int r0 = (y - 3 + QS - 1) / QS; if (y - 3 < 0) r0 = 0;
+        int r1 = (y + 3) / QS; if (r1 > gr.Lh - 1) r1 = gr.Lh - 1;
+        int c0 = (xx - 3 + QS - 1) / QS; if (xx - 3 < 0) c0 = 0;
+        int c1 = (xx + 3) / QS; if (c1 > gr.Lw - 1) c1 = gr.Lw - 1;
+        const float cnt = (float)((r1 - r0 + 1) * (c1 - c0 + 1));
+        // the four window slots in fold_kernel's order (r0, c0), (r0, c1), (r1, c0), (r1, c1); a slot that repeats its predecessor's row
+        // or column is off (its read stays on a covering window)
+        size_t of[4]; bool on[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int r = (s >> 1) ? r1 : r0, c = (s & 1) ? c1 : c0;
+            on[s] = (!(s >> 1) || r1 > r0) && (!(s & 1) || c1 > c0);
+            const int kh = y - (QS * r - 3), kw = xx - (QS * c - 3);
+            of[s] = ((size_t)b * gr.L + (size_t)r * gr.Lw + c) * P + (kh * KS + kw) * CH + 4 * g;
+        }
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const float* ah = agg + (size_t)h * head_stride;
+            float4 v[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) v[s] = *reinterpret_cast<const float4*>(ah + of[s]);
+            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                acc.x = on[s] ? acc.x + v[s].x : acc.x; acc.y = on[s] ? acc.y + v[s].y : acc.y;
+                acc.z = on[s] ? acc.z + v[s].z : acc.z; acc.w = on[s] ? acc.w + v[s].w : acc.w;
+            }
+            av[4 * h + 0] = acc.x / cnt; av[4 * h + 1] = acc.y / cnt;
+            av[4 * h + 2] = acc.z / cnt; av[4 * h + 3] = acc.w / cnt;
+        }
+        f32x4 acc[4];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int T = 0; T < 16; ++T)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[n][T], av[T], acc[n], 0, 0, 0);
+        // D[row = output n*16 + 4g + r][col = pixel]
+        const int pp = pw + 16 * t + i;
+#pragma unroll
+        for (int n = 0; n < 4; ++n) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int o = n * 16 + 4 * g + r;
+                if (pp < HW) {
+                    const size_t idx = ((size_t)b * 64 + o) * HW + pp;
+                    out[idx] = (acc[n][r] + bo[n][r]) + x[idx];
+                }
+            }
+        }
+    }
+}
+
+int launch_stage_fold_mix(hipStream_t s, int B, const Grid& g, const float* agg, const float* x, const float* mix_w, const float* mix_b,
+                          float* out) {
+    // MIX_TILES tiles per wave amortise the weight fragment where the map is large; a small map (256^2: one such wave per SIMD, four
+    // dependent rounds of reads each) runs a tile per wave and four times the waves instead -- measured, DESIGN.md section 7.  The
+    // arithmetic of a pixel is the same: the same bits from both.
+    const long long waves4 = (long long)B * ((g.N + 64 * MIX_TILES - 1) / (64 * MIX_TILES)) * 4;
+    if (waves4 >= FOLD_MIX_SMALL_WAVES) {
+        const int per_img = (g.N + 64 * MIX_TILES - 1) / (64 * MIX_TILES);
+        hipLaunchKernelGGL(stage_fold_mix_kernel<MIX_TILES>, dim3((unsigned)per_img * (unsigned)B), dim3(256), 0, s, g, B, per_img, agg, x, mix_w,
+                           mix_b, out);
+    } else {
+        const int per_img = (g.N + 63) / 64;
+        hipLaunchKernelGGL(stage_fold_mix_kernel<1>, dim3((unsigned)per_img * (unsigned)B), dim3(256), 0, s, g, B, per_img, agg, x, mix_w, mix_b,
+                           out);
+    }
+    DAGL_LAUNCH_CHECK("stage_fold_mix_kernel");
+    return DAGL_OK;
+}
+
 }  // namespace dagl

@@ -502,6 +502,9 @@ int launch_gather_fixed(hipStream_t s, int L, int k, int P_, const int32_t* idx,
 int launch_fold(hipStream_t s, int B, const Grid& g, const float* agg, float* out, int heads = 1, RangeTag range = RangeTag());
 int launch_stage_mix(hipStream_t s, int B, int HW, const float* cat, const float* x, const float* mix_w,
                      const float* mix_b, float* out);
+// the two above in one launch from the four heads' aggregated rows agg [4, B, L, 784] (head-major): the concat map is never stored
+int launch_stage_fold_mix(hipStream_t s, int B, const Grid& g, const float* agg, const float* x, const float* mix_w, const float* mix_b,
+                          float* out);
 int launch_scores_dense(hipStream_t s, int B, int L, int N, const float* wq, const float* x, float* sc);
 
 // selection

@@ -25,6 +25,10 @@
 // wavefront and a block); every exit of the body writes a row of zeros first, the workspace is never cleared.  launch_fold follows.
 // Without graph outputs the degree, the staging, the scan and the copy are left out: nothing then depends on a count the host reads.
 //
+// The third entry, dagl_graph_stage_step, is that step for the four heads of a CES stage: one CSR over the 4 B L head-major rows,
+// graph_step_rows_kernel launched once per head on its slice (launch_graph_stage_step), one scan, one copy, and
+// launch_stage_fold_mix (aggregate.hip) in the place of the fold: out = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x.
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -359,6 +363,23 @@ struct RefreshCall {
     const float* b2p; float* out;
 };
 
+// short rows (top-k 8 at radius 1: 72 candidates) take a wavefront each, longer ones a block of four
+static bool rf_wave_rows(const RefreshCall& r) {
+    const long long wd = 2 * r.radius + 1;
+    return !r.block_rows && (long long)r.max_row_edges * wd * wd <= RF_WAVE_CAP;
+}
+
+// the step's row kernel over n_rows rows: a block per row of a.row_off, in either form
+static int launch_step_rows(hipStream_t s, int n_rows, bool wave, const GtArgs& a, const RfArgs& f, const GaArgs& v) {
+    if (wave) {
+        hipLaunchKernelGGL((graph_step_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, v);
+    } else {
+        hipLaunchKernelGGL((graph_step_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, v);
+    }
+    DAGL_LAUNCH_CHECK("graph_step_rows_kernel");
+    return DAGL_OK;
+}
+
 static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const RefreshCall& r, void* workspace) {
     const int n_rows = B * g.L, wd = 2 * r.radius + 1, w2 = wd * wd;
     const bool agg = r.out != nullptr, graph = r.row_off_out != nullptr;
@@ -374,17 +395,12 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
     f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
     f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
     f.status = reinterpret_cast<unsigned long long*>(r.status);
-    // short rows (top-k 8 at radius 1: 72 candidates) take a wavefront each, longer ones a block of four
-    const bool wave = !r.block_rows && (long long)r.max_row_edges * w2 <= RF_WAVE_CAP;
+    const bool wave = rf_wave_rows(r);
     if (agg) {
         GaArgs v = ga_map_args(B, g, r.b2p, nullptr, nullptr, nullptr, 0);
         v.out = w.agg;
-        if (wave) {
-            hipLaunchKernelGGL((graph_step_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, v);
-        } else {
-            hipLaunchKernelGGL((graph_step_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, v);
-        }
-        DAGL_LAUNCH_CHECK("graph_step_rows_kernel");
+        const int rc = launch_step_rows(s, n_rows, wave, a, f, v);
+        if (rc) return rc;
     } else {
         if (wave) {
             hipLaunchKernelGGL((graph_refresh_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f);
@@ -402,6 +418,50 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
         DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
     }
     return agg ? launch_fold(s, B, g, w.agg, r.out) : DAGL_OK;
+}
+
+// The step of a whole CES stage: r.c.row_off / key are ONE CSR over the 4 B L head-major rows, head h has features, value map and tau
+// of its own.  The row kernel runs once per head on that head's slice of the offsets, degrees and aggregated rows -- a row addresses the
+// keys and its staging region by the absolute row_off[r], so nothing is rebased and no feature is copied --, the status words add up
+// over the launches; then one scan and one ordered copy over all the rows, and the fold + mix + residual of the four heads' rows.
+struct StageStepCall { const float* const* wq4; const float* const* x4; const float* const* b2p4; const float* const* tau4;
+                       const float* x; const float* mix_w; const float* mix_b; };
+
+static int launch_graph_stage_step(hipStream_t s, int B, const Grid& g, const RefreshCall& r, const StageStepCall& st, void* workspace) {
+    const int head_rows = B * g.L, n_rows = 4 * head_rows, wd = 2 * r.radius + 1, w2 = wd * wd;
+    const bool graph = r.row_off_out != nullptr;
+    DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2, true, graph);
+    if (r.c.E == 0) {
+        if (graph) DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
+        DAGL_HIP_TRY(hipMemsetAsync(w.agg, 0, (size_t)n_rows * P * sizeof(float), s));                  // fold(0) / cnt: out = mix_b + x
+        return launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out);
+    }
+    RfArgs f{};
+    f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
+    f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
+    f.status = reinterpret_cast<unsigned long long*>(r.status);
+    const bool wave = rf_wave_rows(r);
+    for (int h = 0; h < 4; ++h) {
+        GraphAttendCall c = r.c;
+        c.wq_rows = st.wq4[h]; c.x_rows = st.x4[h]; c.tau = st.tau4 ? st.tau4[h] : nullptr;
+        c.row_off = r.c.row_off + (size_t)h * head_rows;
+        const GtArgs a = gt_args(B, g, c);                       // (E stays the whole array's: the clamp of an offset)
+        f.deg = graph ? w.deg + (size_t)h * head_rows : nullptr;
+        GaArgs v = ga_map_args(B, g, st.b2p4[h], nullptr, nullptr, nullptr, 0);
+        v.out = w.agg + (size_t)h * head_rows * P;
+        const int rc = launch_step_rows(s, head_rows, wave, a, f, v);
+        if (rc) return rc;
+    }
+    if (graph) {
+        const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
+        if (rc) return rc;
+        hipLaunchKernelGGL(graph_refresh_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0,
+                           s, n_rows, w2, (long long)r.c.E, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out,
+                           r.weight_out, r.score_out, (long long)r.capacity);
+        DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
+    }
+    return launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out);
 }
 
 static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
@@ -460,6 +520,19 @@ static int graph_refresh_entry(const char* who, void* stream, int B, int H, int 
     return launch_graph_refresh((hipStream_t)stream, B, g, r, workspace);
 }
 
+// a stage holds four heads of B images: its rows are those of 4 B images
+static int stage_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    DAGL_REQUIRE((int64_t)4 * B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    return refresh_shape_ok(who, 4 * B, H, W, total_edges, radius);
+}
+
+static int stage_mix_operands_ok(const char* who, const float* x, const float* mix_w, const float* mix_b, const float* out) {
+    DAGL_REQUIRE(x && mix_w && mix_b && out, "%s: null tensor pointer", who);
+    return DAGL_OK;
+}
+
 }  // namespace dagl
 
 using namespace dagl;
@@ -496,6 +569,88 @@ int dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, con
     return graph_refresh_entry("dagl_graph_step", stream, B, H, W, wq_rows, x_rows, b2p, row_off, key, total_edges, max_row_edges, radius,
                                tau, k, scale, flags, out, row_off_out, key_out, weight_out, score_out, capacity_edges, status_out,
                                workspace, ws_bytes, true);
+}
+
+// the fold + 1x1 mix + residual of a CES stage from its four heads' aggregated rows, on its own (no ABI bump: found by symbol)
+int dagl_ces_stage_fold_mix(void* stream, int B, int H, int W, const float* agg, const float* x, const float* mix_w, const float* mix_b,
+                            float* out) {
+    const char* who = "dagl_ces_stage_fold_mix";
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    DAGL_REQUIRE((int64_t)4 * B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    DAGL_REQUIRE(agg != nullptr, "%s: null tensor pointer", who);
+    if ((rc = stage_mix_operands_ok(who, x, mix_w, mix_b, out))) return rc;
+    DAGL_REQUIRE(((uintptr_t)agg % 16) == 0, "%s: agg must be 16-byte aligned", who);
+    return launch_stage_fold_mix((hipStream_t)stream, B, make_grid(H, W), agg, x, mix_w, mix_b, out);
+}
+
+// the launch dagl_ces_stage_fold_mix saves, on its own: the mix + residual of a STORED concat map (stage_mix_kernel, what
+// dagl_ces_stage_forward ends with) -- with dagl_fold_normalize on [4 B] rows in front, the two-launch form to measure against
+int dagl_ces_stage_mix(void* stream, int B, int H, int W, const float* cat, const float* x, const float* mix_w, const float* mix_b,
+                       float* out) {
+    const char* who = "dagl_ces_stage_mix";
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    DAGL_REQUIRE(B <= 65535, "%s: B=%d beyond the 65535 images of one launch", who, B);
+    DAGL_REQUIRE(cat != nullptr, "%s: null tensor pointer", who);
+    if ((rc = stage_mix_operands_ok(who, x, mix_w, mix_b, out))) return rc;
+    return launch_stage_mix((hipStream_t)stream, B, H * W, cat, x, mix_w, mix_b, out);
+}
+
+// the step of a whole CES stage: four heads' rows in one CSR, one scan, one copy, the fused fold + mix (no ABI bump: found by symbol)
+size_t dagl_graph_stage_step_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int want_graph) {
+    if (stage_shape_ok("dagl_graph_stage_step_workspace_bytes", B, H, W, total_edges, radius)) return 0;
+    return refresh_carve(nullptr, (size_t)4 * B * make_grid(H, W).L, (size_t)total_edges * (2 * radius + 1) * (2 * radius + 1), true,
+                         want_graph != 0).bytes;
+}
+
+int dagl_graph_stage_step(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                          const float* const* b2p4, const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges,
+                          int radius, const float* const* tau4, int k, float scale, int flags, const float* x, const float* mix_w,
+                          const float* mix_b, float* out, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out,
+                          int64_t capacity_edges, int64_t* status_out, void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_stage_step";
+    int rc = stage_shape_ok(who, B, H, W, total_edges, radius);
+    if (rc) return rc;
+    DAGL_REQUIRE(wq_rows4 && x_rows4 && b2p4, "%s: null pointer table", who);
+    const bool graph = row_off_out || key_out || weight_out || score_out;
+    const bool outputs = status_out && (!graph || (row_off_out && (total_edges == 0 || (key_out && weight_out && score_out))));
+    int with_tau = 0;
+    for (int h = 0; h < 4; ++h) {
+        if ((rc = graph_operands_ok(who, wq_rows4[h], x_rows4[h], row_off, key, total_edges, scale, flags, outputs && b2p4[h],
+                                    DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
+            return rc;
+        DAGL_REQUIRE(((uintptr_t)b2p4[h] % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+        with_tau += tau4 && tau4[h];
+    }
+    DAGL_REQUIRE(with_tau == 0 || with_tau == 4, "%s: tau given for %d of the four heads (all or none)", who, with_tau);
+    if ((rc = stage_mix_operands_ok(who, x, mix_w, mix_b, out))) return rc;
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    if ((int64_t)max_row_edges * w2 > RF_CAP) {
+        set_error("%s: max_row_edges (2 radius + 1)^2 = %lld candidates per row, more than the %d a row may expand into", who,
+                  (long long)((int64_t)max_row_edges * w2), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    const Grid g = make_grid(H, W);
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    int64_t may = total_edges * w2;
+    if (!keep_all && k > 0 && (int64_t)4 * B * g.L * k < may) may = (int64_t)4 * B * g.L * k;
+    if (graph && capacity_edges < may) {
+        set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
+        return DAGL_ERR_WORKSPACE;
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)4 * B * g.L, (size_t)(total_edges * w2), true, graph).bytes;
+    if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
+    RefreshCall r{};
+    r.c = graph_attend_call(nullptr, nullptr, row_off, key, total_edges, nullptr, scale, flags);
+    r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.row_off_out = graph ? row_off_out : nullptr; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out;
+    r.capacity = capacity_edges; r.status = status_out; r.out = out;
+    const StageStepCall st{wq_rows4, x_rows4, b2p4, with_tau ? tau4 : nullptr, x, mix_w, mix_b};
+    return launch_graph_stage_step((hipStream_t)stream, B, g, r, st, workspace);
 }
 
 }  // extern "C"

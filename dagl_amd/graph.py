@@ -128,6 +128,53 @@ class PatchGraph:
         g._max_degree = self._max_degree
         return g
 
+    @staticmethod
+    def cat(graphs) -> "PatchGraph":
+        """The graphs of ``graphs`` one after the other along the image axis (``B`` adds up, offsets rebased): what a ``CES`` stage keeps
+        of its four heads -- head-major, row ``(h * B + b) * L + i`` = query ``i`` of image ``b`` under head ``h``.  They must share H, W,
+        the device and whether ``score`` is present; ``mode`` / ``k`` come from the first; the result is valid when every input is, its
+        largest degree is known when every input's is.  No host read."""
+        graphs = list(graphs)
+        if not graphs or not all(isinstance(g, PatchGraph) for g in graphs):
+            raise DaglError("PatchGraph.cat: a non-empty sequence of PatchGraphs expected")
+        first = graphs[0]
+        for g in graphs[1:]:
+            if (g.H, g.W) != (first.H, first.W):
+                raise DaglError(f"PatchGraph.cat: maps of {first.H}x{first.W} and {g.H}x{g.W}")
+            if g.row_off.device != first.row_off.device:
+                raise DaglError(f"PatchGraph.cat: graphs on {first.row_off.device} and {g.row_off.device}")
+            if (g.score is None) != (first.score is None):
+                raise DaglError("PatchGraph.cat: score must be present in every graph or in none")
+        parts, base = [first.row_off], first.row_off[-1:]
+        for g in graphs[1:]:
+            parts.append(g.row_off[1:] + base)
+            base = base + g.row_off[-1:]
+        out = first._like(torch.cat(parts), torch.cat([g.key for g in graphs]), torch.cat([g.weight for g in graphs]),
+                          torch.cat([g.score for g in graphs]) if first.score is not None else None)
+        out.B = sum(g.B for g in graphs)
+        out._valid = all(g._valid for g in graphs)
+        if all(g._max_degree is not None for g in graphs):
+            out._max_degree = max(g._max_degree for g in graphs)
+        return out
+
+    def images(self, lo: int, hi: int) -> "PatchGraph":
+        """The sub-graph of images ``lo .. hi - 1``: ``key`` / ``weight`` / ``score`` are views, the offsets are rebased on the device.
+        Sizing the views takes the two bounding offsets: ONE host read of two words when the arrays live on the device (none on the CPU,
+        and none for ``images(0, B)``).  Validity is handed on; the largest degree is not (it may be smaller)."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= self.B:
+            raise DaglError(f"PatchGraph.images: [{lo}, {hi}) is not a non-empty range of the {self.B} images")
+        r0, r1 = lo * self.L, hi * self.L
+        if (lo, hi) == (0, self.B):
+            e0, e1 = 0, self.n_edges
+        else:
+            e0, e1 = (int(v) for v in self.row_off[[r0, r1]].tolist())          # the one host read
+        off = self.row_off[r0:r1 + 1]
+        g = self._like(off - off[:1] if lo else off, self.key[e0:e1], self.weight[e0:e1],
+                       self.score[e0:e1] if self.score is not None else None)
+        g.B = hi - lo
+        return g
+
     def with_weight(self, weight: torch.Tensor) -> "PatchGraph":
         """The same structure (the offsets and keys are shared, not copied) with ``weight`` [E] fp32 in the place of the weights.  A
         ``weight`` that requires grad is kept as it is: ``CE.apply_graph`` under autograd returns its gradient."""

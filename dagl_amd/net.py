@@ -56,6 +56,7 @@ class CES(nn.Module):
         self.last_info = None
         from . import ops
         self._ws = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # one per stage: packed weights persist
+        self._ws_step = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # step_graphs' own: _ws keeps its packed weights
         self._pack_key = {1: None, 2: None, 3: None}
         self._skip_fused = {1: 0, 2: 0, 3: 0}     # calls for which a stage stays on the per-head path after it met dense masks
         self._fused_calls = {1: 0, 2: 0, 3: 0}    # fused calls since the stage's range word was last looked at
@@ -134,6 +135,158 @@ class CES(nn.Module):
         out = self.RBS2(out)
         return self._stage(3, out)
 
+    # ---- sequences: the key frame selects (forward_with_graphs), every following frame moves the graphs at O(edges) (step_graphs) ------
+    def _stage_modules(self, s):
+        return [getattr(self, f"c{s}_{h}") for h in (1, 2, 3, 4)], getattr(self, f"c{s}_c")
+
+    def _between_stages(self, s, out):
+        return self.RBS1(out) if s == 1 else self.RBS2(out) if s == 2 else out
+
+    def forward_with_graphs(self, x):
+        """The key frame of a sequence -> ``(out, SequenceState)``: ``forward``'s structure with every head run by
+        ``CE.forward_with_graph`` (its output and the patch graph that produced it), the stage's own mix and residual, ``RBS1`` /
+        ``RBS2`` between the stages.  The state holds the twelve graphs, one ``PatchGraph`` over ``4 B`` images per stage.  Scope,
+        autograd and refusals are ``CE.forward_with_graph``'s, passed through unchanged; the fused stage launch set of ``forward`` is not
+        used, so ``out`` differs from ``forward``'s by that route's roundings."""
+        from ._lib import DaglError
+        from .sequence import SequenceState
+        graphs, out = [], x
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            for hd in heads:
+                if not isinstance(hd, CE):
+                    raise DaglError(f"CES.forward_with_graphs: head {type(hd).__name__} of stage {s} is not a CE: it exports no graph")
+            pairs = [hd.forward_with_graph(out) for hd in heads]
+            graphs.extend(g for _, g in pairs)
+            out = self._between_stages(s, mix(torch.cat([o for o, _ in pairs], dim=1)) + out)
+        return out, SequenceState.from_heads(graphs)
+
+    def _stage_step_fusable(self, s, x) -> bool:
+        """Whether ``ops.graph_stage_step`` serves stage ``s`` on the input ``x``: four plain ``CE`` heads of the default patch geometry
+        that share the selection rule, the scale and hence the margin, a 64-channel fp32 mix, an fp32 input on the GPU."""
+        heads, mix = self._stage_modules(s)
+        return self.fuse_stage and all(type(hd) is CE and not hd._generic and hd.in_channels == 64 for hd in heads) \
+            and len({(hd.select_mode, int(hd.select_k), float(hd.softmax_scale)) for hd in heads}) == 1 \
+            and x.is_cuda and x.dtype == torch.float32 and mix.weight.dtype == torch.float32
+
+    @torch.no_grad()
+    def step_graphs(self, x, state, *, radius: int = 1, features: str = "fp32", want_graphs: bool = True, fused=None):
+        """A sequence step of the whole module -> ``(out, SequenceState | None)``: per stage the stage's graphs are moved to the stage's
+        input exactly as each head's ``CE.refresh_graph`` moves its own, and the stage's output is ``mix(cat(step outputs)) + input`` with
+        each head's step output ``CE.step_graph``'s; ``RBS1`` / ``RBS2`` run between the stages as in ``forward``.  For a sequence:
+        ``out, state = ces.forward_with_graphs(frame0)``, then ``out, state = ces.step_graphs(frame, state)``.
+
+        ``fused=False``: head by head -- ``CE.step_graph`` four times, ``torch.cat``, the mix convolution: the definition of the result.
+        ``fused=True``: the heads' features from ``CE._graph_features`` (either ``features`` route), then ONE ``ops.graph_stage_step`` per
+        stage: the four heads' rows in one CSR, one scan, one copy, fold + mix + residual in one launch.  The graphs are the head-by-head
+        ones bit for bit; ``out`` differs by the fp32 roundings of the mix product alone.  ``fused=None``: fused for every stage whose
+        four heads are plain ``CE`` modules sharing ``select_mode``, ``select_k``, ``softmax_scale`` (hence the margin) and the default
+        patch geometry, on an fp32 GPU input; head by head otherwise.  ``fused=True`` on a stage that does not qualify is refused.
+
+        ``want_graphs=False`` keeps the key frame's structure and returns ``(out, None)``: nothing is read on the host, and the call can be
+        captured once the state's graphs are validated and their largest degrees known (``validate()`` / ``max_degree()`` on
+        ``state.stages``; head by head: on every ``state.head(s, h)``).  ``want_graphs=True`` makes one host read per stage (per head when
+        head by head) and is refused under capture.  With ``features="split16"`` a head whose operands leave the split-fp16 range
+        NaN-fills ``out`` and that head's rows of the new graph, never wrong numbers.
+
+        Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
+        the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
+        does not fit the input -- is raised before any launch of the call."""
+        from ._lib import DaglError
+        from .sequence import SequenceState
+        what = "CES.step_graphs"
+        if not isinstance(state, SequenceState):
+            raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise DaglError(f"{what}: expected [B,C,H,W]")
+        want_graphs = bool(want_graphs)
+        B = x.shape[0]
+        if (state.stages[0].B, state.stages[0].H, state.stages[0].W) != (4 * B, x.shape[2], x.shape[3]):
+            g0 = state.stages[0]
+            raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={B} H={x.shape[2]} W={x.shape[3]}")
+        plan = self._plan_step(x, state, radius, features, want_graphs, fused)
+        out, new = x, []
+        for s in (1, 2, 3):
+            out, g = self._step_stage(s, out, state, plan[s], features, want_graphs)
+            new.append(g)
+            out = self._between_stages(s, out)
+        return out, (SequenceState(new) if want_graphs else None)
+
+    def _plan_step(self, x, state, radius, features, want_graphs, fused):
+        """Every refusal of ``step_graphs`` that depends on a stage, raised before the first launch -- every stage sees an input of x's
+        shape, dtype and device -- -> {stage: (fused?, what ``CE._refresh_arguments`` returns for its heads)}."""
+        from ._lib import DaglError
+        what = "CES.step_graphs"
+        B = x.shape[0]
+        capturing = torch.cuda.is_current_stream_capturing()
+        plan = {}
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            ok = self._stage_step_fusable(s, x)
+            if fused and not ok:
+                raise DaglError(f"{what}: fused=True, but stage {s} does not qualify (four plain CE heads sharing select_mode, select_k, "
+                                "softmax_scale and the default patch geometry, an fp32 input on the GPU)")
+            use = ok if fused is None else bool(fused)
+            for h, hd in enumerate(heads):
+                if not isinstance(hd, CE):
+                    raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it steps no graph")
+                if use:
+                    stage = state.stages[s - 1]
+                    if not capturing and x.is_cuda and stage.row_off.device == x.device:
+                        stage.validate()
+                        stage.max_degree()
+                    g = stage._like(stage.row_off, stage.key, stage.weight, stage.score)      # the stage's arrays under a head's shape
+                    g.B, g._max_degree = B, stage._max_degree
+                else:
+                    if capturing and not state.has_head(s - 1, h):
+                        raise DaglError(f"{what}: head by head under capture needs state.head({s - 1}, {h}) taken before the capture "
+                                        "(it reads two offsets on the host)")
+                    g = state.head(s - 1, h)
+                args = hd._refresh_arguments(x, g, "step_graph", radius, None, "reference", features, host_read=want_graphs)
+            plan[s] = (use, args)
+        return plan
+
+    def _step_stage(self, s, x, state, plan, features, want_graphs):
+        """Stage ``s`` of ``step_graphs`` on its input ``x`` -> (the stage's output, its new graph | None).  ``plan``: (fused?, what
+        ``CE._refresh_arguments`` returned for its heads) -- the refusals are through."""
+        from .graph import PatchGraph
+        heads, mix = self._stage_modules(s)
+        use, (radius, k_eff, margin, longest) = plan
+        if use:
+            return self._stage_step_fused(s, x, state.stages[s - 1], radius, k_eff, margin, longest, features, want_graphs)
+        pairs = [hd.step_graph(x, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs)
+                 for h, hd in enumerate(heads)]
+        return mix(torch.cat([o for o, _ in pairs], dim=1)) + x, (PatchGraph.cat([g for _, g in pairs]) if want_graphs else None)
+
+    def _stage_step_fused(self, s, x, stage, radius, k_eff, margin, longest, features, want_graphs):
+        """One ``ops.graph_stage_step`` on the four heads' features -> (out, the stage's new graph | None)."""
+        from . import ops
+        heads, mix = self._stage_modules(s)
+        fast = features == "split16"
+        x = x.contiguous()
+        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        out, csr, _status = ops.graph_stage_step([f[0].contiguous() for f in feats], [f[1].contiguous() for f in feats],
+                                                 [f[3].contiguous() for f in feats], stage.row_off, stage.key, x,
+                                                 mix.weight.detach().contiguous(), mix.bias.detach().contiguous(), radius=radius,
+                                                 tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff,
+                                                 scale=float(heads[0].softmax_scale), max_row_edges=longest, want_graph=want_graphs,
+                                                 workspace=self._ws_step[s])
+        if fast:
+            for f in feats:
+                out = f[4](out)                     # a head that left the split-fp16 range NaN-fills the stage's output
+        if not want_graphs:
+            return out, None
+        weight, score = csr["weight"], csr["score"]
+        if fast:
+            # ... and its own rows of the graph: 0 or NaN per head, spread over the edges by the heads' first offsets (no host read)
+            verdict = torch.cat([f[4](weight.new_zeros(1)) for f in feats])
+            n = stage.B // 4 * stage.L
+            head_of = torch.bucketize(torch.arange(weight.numel(), device=weight.device), csr["row_off"][n:4 * n:n].contiguous(), right=True)
+            weight, score = weight + verdict[head_of], score + verdict[head_of]
+        g = stage._like(csr["row_off"], csr["key"], weight, score)
+        g.mode, g.k, g._valid = heads[0].select_mode, k_eff, True               # (every candidate is a key of the map)
+        return out, g
+
 
 class _MeanShift(nn.Conv2d):
     """Registered by the reference (``add_mean``, dagl.py:41) but never applied; kept for state_dict compatibility."""
@@ -163,6 +316,27 @@ class RR(nn.Module):
 
     def forward(self, x):
         return x + self.tail(self.body(self.head(x)))
+
+    def _forward_around_ces(self, x, ces_call):
+        """``forward`` with the trunk's modules run in order and ``ces_call`` in the place of the ``CES``'s forward -> (out, its state)."""
+        out, state = self.head(x), None
+        for m in self.body:
+            if isinstance(m, CES):
+                out, state = ces_call(m, out)
+            else:
+                out = m(out)
+        return x + self.tail(out), state
+
+    def forward_with_graphs(self, x):
+        """The key frame of a sequence -> ``(out, SequenceState)``: ``forward`` with ``CES.forward_with_graphs`` where the ``CES`` sits."""
+        return self._forward_around_ces(x, lambda ces, t: ces.forward_with_graphs(t))
+
+    @torch.no_grad()
+    def step_graphs(self, x, state, **kw):
+        """A sequence step of the network -> ``(out, SequenceState | None)``: ``forward`` with ``CES.step_graphs(., state, **kw)`` where the
+        ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused`` as there); always under ``torch.no_grad()``.  The ``CES``'s
+        refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
+        return self._forward_around_ces(x, lambda ces, t: ces.step_graphs(t, state, **kw))
 
     def load_state_dict(self, state_dict, strict=True):
         """The reference network's own loader rule (``dagl.py:56-73``), which is NOT torch's: checkpoint entries are

@@ -748,6 +748,114 @@ def graph_step(wq_rows, x_rows, b2p, row_off, key, *, radius: int = 1, tau=None,
     return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
 
 
+def _stage_mix_operands(who: str, x, mix_w, mix_b):
+    """x [B,64,H,W], the stage's 1x1 mix weights [64,64] or [64,64,1,1] and bias [64] -> (B, H, W)."""
+    _need(x, "x"); _need(mix_w, "mix_w"); _need(mix_b, "mix_b")
+    if x.dim() != 4 or x.shape[1] != 64:
+        raise DaglError(f"{who}: expected x [B,64,H,W], got {tuple(x.shape)}")
+    if tuple(mix_w.shape) not in ((64, 64), (64, 64, 1, 1)) or tuple(mix_b.shape) != (64,):
+        raise DaglError(f"{who}: expected mix_w [64,64] and mix_b [64], got {tuple(mix_w.shape)} and {tuple(mix_b.shape)}")
+    return x.shape[0], x.shape[2], x.shape[3]
+
+
+@_on_device
+def ces_stage_fold_mix(agg, x, mix_w, mix_b) -> torch.Tensor:
+    """The end of a ``CES`` stage from its four heads' aggregated rows in one launch (``dagl_ces_stage_fold_mix``, csrc/aggregate.hip):
+    ``conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x`` -> [B,64,H,W].  agg [4,B,L,784] head-major, element order (kh, kw, c); x
+    [B,64,H,W]; mix_w [64,64] (or [64,64,1,1]), mix_b [64].  The 64 concat values of a pixel are ``fold_normalize``'s bits and never go
+    to memory; the product runs on the fp32 matrix cores.  The same arrays give the same bits on every call."""
+    who = "ces_stage_fold_mix"
+    B, H, W = _stage_mix_operands(who, x, mix_w, mix_b)
+    _need(agg, "agg")
+    Lh, Lw = query_grid(H, W)
+    if tuple(agg.shape) != (4, B, Lh * Lw, P):
+        raise DaglError(f"{who}: expected agg [4,{B},{Lh * Lw},{P}] for x {tuple(x.shape)}, got {tuple(agg.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.load().dagl_ces_stage_fold_mix(_stream(), B, H, W, agg.data_ptr(), x.data_ptr(), mix_w.data_ptr(), mix_b.data_ptr(),
+                                              out.data_ptr()), "dagl_ces_stage_fold_mix")
+    return out
+
+
+@_on_device
+def ces_stage_mix(cat, x, mix_w, mix_b) -> torch.Tensor:
+    """``conv1x1(cat) + mix_b + x`` on a stored concat map cat [B,64,H,W] (``dagl_ces_stage_mix``: the last launch of
+    ``ces_stage_forward``, on its own) -- with ``fold_normalize`` in front, the two launches ``ces_stage_fold_mix`` replaces; for
+    measurements."""
+    B, H, W = _stage_mix_operands("ces_stage_mix", x, mix_w, mix_b)
+    _need(cat, "cat")
+    if cat.shape != x.shape:
+        raise DaglError(f"ces_stage_mix: cat is {tuple(cat.shape)}, x {tuple(x.shape)}")
+    out = torch.empty_like(x)
+    check(_lib.load().dagl_ces_stage_mix(_stream(), B, H, W, cat.data_ptr(), x.data_ptr(), mix_w.data_ptr(), mix_b.data_ptr(),
+                                         out.data_ptr()), "dagl_ces_stage_mix")
+    return out
+
+
+@_on_device
+def graph_stage_step(wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, *, radius: int = 1, tau4=None, k: int = 0,
+                     scale: float = 10.0, normalize: str = "reference", keep_all: bool = False, max_row_edges=None,
+                     want_graph: bool = True, workspace: "Workspace | None" = None, block_rows: bool = False):
+    """``graph_step`` for the four heads of a ``CES`` stage and the stage's mix on the result, in one call (``dagl_graph_stage_step``,
+    csrc/graph_refresh.hip) -> (out [B,64,H,W], dict | None, status).  wq_rows4 / x_rows4 / b2p4 / tau4: sequences of four tensors, entry
+    h what ``graph_step`` takes for head h (``tau4`` None: no margin); (row_off [4*B*L+1], key [E]) ONE CSR over the head-major rows,
+    row ``(h * B + b) * L + i`` = query ``i`` of image ``b`` under head ``h``; x [B,64,H,W] the stage's input, mix_w / mix_b its 1x1 mix.
+    The features stay where they are: the row kernel runs once per head on its slice of the offsets.
+
+    The dict holds ONE CSR over the 4*B*L rows: rows ``h*B*L .. (h+1)*B*L`` are, bit for bit, what ``graph_step`` returns for head h's
+    operands and its slice of the input graph (offsets continuing from head to head); ``out`` is ``ces_stage_fold_mix`` of the heads'
+    aggregated rows, each ``graph_step``'s bits -- the same with ``want_graph`` True or False and on every call.  An empty graph gives
+    ``mix_b + x``.  ``status``: device int64[2] (rows longer than ``max_row_edges`` summed over the heads, the largest candidate count).
+
+    Host reads, ``max_row_edges``, the overlong-row refusal and capture: as ``graph_step`` -- one host read with ``want_graph=True``; none
+    with ``want_graph=False``, which needs ``max_row_edges``."""
+    lib = _lib.load()
+    who = "graph_stage_step"
+    for name, seq in (("wq_rows4", wq_rows4), ("x_rows4", x_rows4), ("b2p4", b2p4)) + ((("tau4", tau4),) if tau4 is not None else ()):
+        if not isinstance(seq, (list, tuple)) or len(seq) != 4:
+            raise DaglError(f"{who}: {name} must be a sequence of four tensors, one per head")
+    B, H, W = _stage_mix_operands(who, x, mix_w, mix_b)
+    _need(row_off, "row_off", torch.int64)
+    L = math.prod(query_grid(H, W))
+    if row_off.dim() != 1 or row_off.numel() != 4 * B * L + 1:
+        raise DaglError(f"{who}: row_off holds {row_off.numel()} offsets, expected 4*B*L+1 = {4 * B * L + 1}")
+    head_off = row_off[:B * L + 1]              # (a head's view: the shape checks of graph_step, head by head)
+    for h in range(4):
+        _need(b2p4[h], "b2p4[%d]" % h)
+        map_hw = _value_map(who, b2p4[h])[1:]
+        if tuple(map_hw) != (H, W) or b2p4[h].shape[0] != B:
+            raise DaglError(f"{who}: b2p4[{h}] is the value map of {b2p4[h].shape[0]} {map_hw[0]}x{map_hw[1]} images, x holds {B} of {H}x{W}")
+        Bh, _, _, E, flags, radius, k = _graph_refresh_operands(who, wq_rows4[h], x_rows4[h], head_off, key, radius,
+                                                                tau4[h] if tau4 is not None else None, k, normalize, keep_all,
+                                                                block_rows, (H, W))
+        if Bh != B:
+            raise DaglError(f"{who}: head {h}'s feature rows hold {Bh} images, x {B}")
+    if want_graph:
+        max_row_edges = _graph_refresh_longest(who, row_off, E, max_row_edges)
+    elif max_row_edges is None:
+        raise DaglError(f"{who}: want_graph=False needs max_row_edges, the input's largest degree"
+                        + (" (reading it on the host is not available under stream capture)"
+                           if torch.cuda.is_current_stream_capturing() else " (the call itself reads nothing on the host)"))
+    max_row_edges = int(max_row_edges)
+    dev = x.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_stage_step_workspace_bytes", B, H, W, E, radius, 1 if want_graph else 0)
+    out = torch.empty_like(x)
+    if want_graph:
+        head, key_out, weight, score, cap = _graph_refresh_arrays(dev, 4 * B * L, E, radius, k, keep_all)
+        status = head[-2:]
+    else:
+        head = key_out = weight = score = None
+        cap, status = 0, torch.empty(2, device=dev, dtype=torch.int64)
+    table = lambda seq: (C.c_void_p * 4)(*[t.data_ptr() for t in seq])
+    check(lib.dagl_graph_stage_step(_stream(), B, H, W, table(wq_rows4), table(x_rows4), table(b2p4), row_off.data_ptr(), _ptr(key, E > 0),
+                                    E, max_row_edges, radius, table(tau4) if tau4 is not None else None, k, float(scale), flags,
+                                    x.data_ptr(), mix_w.data_ptr(), mix_b.data_ptr(), out.data_ptr(), _ptr(head), _ptr(key_out, E > 0),
+                                    _ptr(weight, E > 0), _ptr(score, E > 0), cap, status.data_ptr(), a, nbytes), "dagl_graph_stage_step")
+    del buf
+    if not want_graph:
+        return out, None, status
+    return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
+
+
 @_on_device
 def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,

@@ -1,0 +1,64 @@
+"""``SequenceState`` -- the patch graphs a ``CES`` carries from frame to frame: one ``PatchGraph`` per stage over the stage's four heads.
+
+``CES.forward_with_graphs`` / ``RR.forward_with_graphs`` return one for the key frame, ``step_graphs`` takes it and returns the next.  Plain
+bookkeeping over ``PatchGraph`` (graph.py): it works on CPU tensors.
+"""
+from __future__ import annotations
+
+from ._lib import DaglError
+from .graph import PatchGraph
+
+STAGES, HEADS = 3, 4
+
+
+class SequenceState:
+    """``stages[s]`` (s = 0, 1, 2): the graphs of stage ``s + 1``'s four heads as ONE ``PatchGraph`` over ``4 * B`` images, head-major --
+    row ``(h * B + b) * L + i`` is query ``i`` of image ``b`` under head ``h`` (``PatchGraph.cat`` of the heads' graphs)."""
+
+    def __init__(self, stages):
+        stages = list(stages)
+        if len(stages) != STAGES or not all(isinstance(g, PatchGraph) for g in stages):
+            raise DaglError(f"SequenceState: {STAGES} PatchGraphs expected, one per stage")
+        for g in stages:
+            if g.B % HEADS:
+                raise DaglError(f"SequenceState: a stage graph over {g.B} images does not hold {HEADS} heads of a batch")
+            if (g.B, g.H, g.W) != (stages[0].B, stages[0].H, stages[0].W):
+                raise DaglError("SequenceState: the stage graphs must share B, H and W")
+        self.stages = stages
+        self._heads = {}                 # (s, h) -> the head's sub-graph: ``images`` reads two offsets on the host, once per state
+
+    @property
+    def B(self) -> int:
+        """Images per head."""
+        return self.stages[0].B // HEADS
+
+    @classmethod
+    def from_heads(cls, graphs) -> "SequenceState":
+        """From the 12 graphs of the heads in module order: c1_1 .. c1_4, c2_1 .. c2_4, c3_1 .. c3_4."""
+        graphs = list(graphs)
+        if len(graphs) != STAGES * HEADS:
+            raise DaglError(f"SequenceState.from_heads: {STAGES * HEADS} graphs expected, got {len(graphs)}")
+        if not all(isinstance(g, PatchGraph) for g in graphs) or len({g.B for g in graphs}) != 1:
+            raise DaglError("SequenceState.from_heads: PatchGraphs that share B expected")
+        state = cls(PatchGraph.cat(graphs[s * HEADS:(s + 1) * HEADS]) for s in range(STAGES))
+        state._heads = {(s, h): graphs[s * HEADS + h] for s in range(STAGES) for h in range(HEADS)}
+        return state
+
+    def head(self, s: int, h: int) -> PatchGraph:
+        """The graph of head ``h`` (0..3) of stage ``s`` (0..2): ``stages[s].images(h * B, (h + 1) * B)``, kept on the object."""
+        s, h = int(s), int(h)
+        if not (0 <= s < STAGES and 0 <= h < HEADS):
+            raise IndexError(f"SequenceState.head: ({s}, {h}) outside [0, {STAGES}) x [0, {HEADS})")
+        if (s, h) not in self._heads:
+            self._heads[(s, h)] = self.stages[s].images(h * self.B, (h + 1) * self.B)
+        return self._heads[(s, h)]
+
+    def has_head(self, s: int, h: int) -> bool:
+        """Whether ``head(s, h)`` is at hand without a host read."""
+        return (int(s), int(h)) in self._heads
+
+    def to(self, device) -> "SequenceState":
+        return SequenceState(g.to(device) for g in self.stages)
+
+    def __repr__(self):
+        return f"SequenceState({', '.join(repr(g) for g in self.stages)})"

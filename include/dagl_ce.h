@@ -170,7 +170,8 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_fc_grad16_plan,
+ * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*,
+ * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
  * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
@@ -479,6 +480,46 @@ int    dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, 
                        const float* tau /* NULL: no margin */, int k /* 0: no rank cut */, float scale, int flags, float* out,
                        int64_t* row_off_out /* [B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
                        int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
+
+/* ---- the sequence step of a whole CES stage: csrc/graph_refresh.hip, csrc/aggregate.hip (detected by symbol) ---------------------------
+ * dagl_ces_stage_fold_mix: the end of a stage from its four heads' aggregated rows, in one launch:
+ *     out = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x
+ *   agg [4, B, L, 784] head-major (head h, image b, query i at ((h B + b) L + i) 784), element order (kh, kw, c), 16-byte aligned;
+ *   x, out [B,64,H,W];  mix_w [64,64] (output, concat channel: the stage's 1x1 convolution),  mix_b [64].
+ *   Per pixel the <= 2 x 2 covering windows of each head are added in the order of dagl_fold_normalize and divided by the window count
+ *   (the 64 concat values are dagl_fold_normalize's bits; the [B,64,H,W] concat map is never stored), then the 64 x 64 product on the
+ *   fp32 matrix cores, the bias, the residual.  No float atomics: the same arrays give the same bits on every call.
+ * dagl_graph_stage_step: dagl_graph_step for the four heads of a stage that share the input, and that end on its result.
+ *   wq_rows4, x_rows4, b2p4, tau4: HOST tables of four device pointers, entry h = head h's wq_rows [B L, 196], x_rows [B N, 196],
+ *     b2p [B,H+6,W+6,16] and tau [B L] as dagl_graph_step takes them for B images; tau4 NULL or four NULL entries: no margin; some entries
+ *     NULL is DAGL_ERR_INVALID.  No feature is copied or stacked.
+ *   row_off [4 B L + 1], key [total_edges]: ONE CSR over the head-major rows, row (h B + b) L + i = query i of image b under head h.
+ *   max_row_edges, radius, k, scale, flags: as dagl_graph_step, the same for the four heads.
+ *   out [B,64,H,W] = dagl_ces_stage_fold_mix of the four heads' aggregated rows, each row dagl_graph_step's bits for its head.
+ *   row_off_out [4 B L + 1], key_out / weight_out / score_out [capacity_edges], or ALL NULL (the output alone): rows h B L .. (h + 1) B L
+ *     hold, bit for bit, what dagl_graph_step writes for head h's operands and its slice of the input graph, the offsets continuing
+ *     from head to head (row_off_out[r] - row_off_out[h B L] are that call's offsets).  capacity_edges >= total_edges (2 radius + 1)^2,
+ *     or 4 B L k when k > 0 (without KEEP_ALL) and that is smaller.
+ *   status_out [2] int64 (device): the rows longer than max_row_edges summed over the heads (each comes out empty, never truncated), the
+ *     largest number of distinct candidates over all rows.
+ * Limits, refusals and error codes are dagl_graph_step's with 4 B in the place of B.  total_edges = 0: out = mix_b + x.  Workspace:
+ * dagl_graph_stage_step_workspace_bytes = the [4 B L, 784] aggregated rows + (want_graph) dagl_graph_refresh's regions over 4 B L rows.
+ * Launches: the row kernel once per head on its slice of the offsets (a row stages at the absolute row_off[r] (2 radius + 1)^2), (graph
+ * outputs) one scan and one ordered copy over all rows, the fold + mix.  Every argument is checked before the first launch; nothing is
+ * read on the host and the call can be captured: the CALLER reads row_off_out[4 B L] and status_out. */
+int    dagl_ces_stage_fold_mix(void* stream, int B, int H, int W, const float* agg, const float* x, const float* mix_w,
+                               const float* mix_b, float* out);
+/* The launch it saves, on its own (for measurements): out = conv1x1(cat) + mix_b + x on a STORED concat map cat [B,64,H,W] -- the end of
+ * dagl_ces_stage_forward; dagl_fold_normalize on the [4 B] heads' rows writes such a map when B = 1.  B <= 65535. */
+int    dagl_ces_stage_mix(void* stream, int B, int H, int W, const float* cat, const float* x, const float* mix_w, const float* mix_b,
+                          float* out);
+size_t dagl_graph_stage_step_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int want_graph);
+int    dagl_graph_stage_step(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                             const float* const* b2p4, const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges,
+                             int radius, const float* const* tau4 /* NULL: no margin */, int k /* 0: no rank cut */, float scale, int flags,
+                             const float* x, const float* mix_w, const float* mix_b, float* out,
+                             int64_t* row_off_out /* [4 B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
+                             int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;
