@@ -149,6 +149,10 @@ SIGNATURES = {
     "dagl_ce_prologue16_plan": (_i, [_i] * 4 + [C.POINTER(C.c_int32)]),
     "dagl_ce_prologue16_debug_scratch_bytes": (_sz, [_i]),
     "dagl_ce_prologue16_debug": (_i, [_vp, _i, _i, _i, _i] + [C.POINTER(_vp)] * 5 + [C.c_int32, _vp, _sz] + [_vp] * 9 + [_i]),
+    "dagl_project16_plan": (_i, [_i] * 5 + [C.POINTER(C.c_int32)]),
+    "dagl_ce_project16_debug_scratch_bytes": (_sz, [_i]),
+    "dagl_ce_project16_debug": (_i, [_vp] + [_i] * 5 + [_vp] * 5 + [_i] + [C.POINTER(_vp)] * 4 + [C.c_int32, _vp, _vp, _sz] + [_vp] * 4 + [_i]
+                                + [_vp] * 8 + [C.POINTER(_vp)] * 3 + [_vp]),
     "dagl_pad_nhwc": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "dagl_pack_fc_weight": (_i, [_vp, _vp, _vp]),
     "dagl_project_patches": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1725,6 +1725,93 @@ int dagl_ce_prologue16_debug(void* stream, int heads, int imgs, int H, int W, co
     return launch_conv_pair16_heads(s, heads, imgs, g, hs, b2_nhwc, b1_nhwc, b1_hi, b1_lo, clear_a, n, nullptr, 0, range);
 }
 
+// (detected by symbol) the launch plan of project16_kernel on B images of [H, W], by the function its launcher plans with
+int dagl_project16_plan(int B, int H, int W, int which, int cus, int32_t out[12]) {
+    DAGL_REQUIRE(B >= 1 && H >= 1 && W >= 1 && which >= 1 && which <= 3 && out, "dagl_project16_plan: bad argument");
+    const Project16Plan p = project16_plan(make_grid(H, W), B, which, cus);
+    out[0] = p.n_items[0]; out[1] = p.n_items[1]; out[2] = p.lin[0]; out[3] = p.units_q; out[4] = p.units_k;
+    out[5] = p.n_full; out[6] = p.n_full & ~15; out[7] = p.n_split_groups; out[8] = p.n_proj; out[9] = p.cap;
+    out[10] = p.segs[0]; out[11] = p.segs[1];
+    return DAGL_OK;
+}
+
+// (detected by symbol) read-out of the inference launch of project16_kernel for tests: the launcher of the fused forward on heads x imgs
+// images of fp16 planes, every output -- feature rows, bf16 and split copies, column and row sums, the thr / bias partials -- in the
+// caller's buffers, none of them touched outside the kernel's own stores
+size_t dagl_ce_project16_debug_scratch_bytes(int heads) {
+    return heads >= 1 && heads <= 4 ? (size_t)heads * 2 * P16_PACKED_HALFS * sizeof(uint16_t) : 0;
+}
+
+int dagl_ce_project16_debug(void* stream, int heads, int imgs, int H, int W, int which, const uint16_t* map_hi, const uint16_t* map_lo,
+                            const uint16_t* map_hi2, const uint16_t* map_lo2, const float* amax, int slots, const float* const* fc1_w,
+                            const float* const* fc1_b, const float* const* fc2_w, const float* const* fc2_b, int32_t tag,
+                            int32_t* range_word, void* scratch, size_t scratch_bytes, float* x_feat, float* wq_feat, uint16_t* x_bf16,
+                            uint16_t* wq_bf16, int q_tiled, uint16_t* x_hi, uint16_t* x_lo, uint16_t* wq_hi, uint16_t* wq_lo,
+                            double* colsum, float* colpart, float* rowsum, const int32_t* rowsum_policy, const float* const* thr_x,
+                            const float* const* thr_w, const float* const* bias_w, float* thr_part) {
+    DAGL_REQUIRE(heads >= 1 && heads <= 4 && imgs >= 1 && H >= 1 && W >= 1 && which >= 1 && which <= 3,
+                 "dagl_ce_project16_debug: bad shape (1..4 heads, which 1..3)");
+    const bool keys = (which & 1) != 0, queries = (which & 2) != 0;
+    if (keys) DAGL_REQUIRE(fc2_w && fc2_b, "dagl_ce_project16_debug: null pointer table");
+    if (queries) DAGL_REQUIRE(fc1_w && fc1_b, "dagl_ce_project16_debug: null pointer table");
+    const bool thr = thr_x || thr_w || bias_w || thr_part;
+    if (thr) DAGL_REQUIRE(thr_x && thr_w && bias_w && thr_part, "dagl_ce_project16_debug: the thr / bias ride-along is x, both weights and the partials, or none");
+    for (int h = 0; h < heads; ++h) {
+        DAGL_REQUIRE((!keys || (fc2_w[h] && fc2_b[h])) && (!queries || (fc1_w[h] && fc1_b[h])) && (!thr || (thr_x[h] && thr_w[h] && bias_w[h])),
+                     "dagl_ce_project16_debug: null input of head %d", h);
+    }
+    DAGL_REQUIRE(map_hi && map_lo, "dagl_ce_project16_debug: null plane");
+    DAGL_REQUIRE(range_word && (!keys || x_feat) && (!queries || wq_feat), "dagl_ce_project16_debug: null output");
+    DAGL_REQUIRE((keys || !(x_feat || x_bf16 || x_hi || x_lo || colsum || colpart || rowsum)) && (queries || !(wq_feat || wq_bf16 || wq_hi || wq_lo)),
+                 "dagl_ce_project16_debug: an output of a side `which` leaves out");
+    DAGL_REQUIRE((map_hi2 == nullptr) == (map_lo2 == nullptr), "dagl_ce_project16_debug: the coarse tier is both planes or neither");
+    DAGL_REQUIRE((amax != nullptr) == (map_hi2 != nullptr), "dagl_ce_project16_debug: the slots come with the coarse tier and only with it");
+    if (amax) DAGL_REQUIRE(slots >= 4 && slots % 4 == 0, "dagl_ce_project16_debug: %d slots per head (a multiple of 4, at least 4)", slots);
+    DAGL_REQUIRE((x_hi == nullptr) == (x_lo == nullptr) && (wq_hi == nullptr) == (wq_lo == nullptr),
+                 "dagl_ce_project16_debug: a split copy is both halves or neither");
+    DAGL_REQUIRE((colsum == nullptr) == (colpart == nullptr), "dagl_ce_project16_debug: colsum and colpart come together");
+    DAGL_REQUIRE(rowsum || !rowsum_policy, "dagl_ce_project16_debug: a policy word without rowsum");
+    DAGL_REQUIRE(tag != 0, "dagl_ce_project16_debug: the tag must not be 0");
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+    DAGL_REQUIRE(al16(map_hi) && al16(map_lo) && al16(map_hi2) && al16(map_lo2) && al16(amax) && al16(x_feat) && al16(wq_feat) && al16(x_bf16) &&
+                 al16(wq_bf16) && al16(x_hi) && al16(x_lo) && al16(wq_hi) && al16(wq_lo) && al16(colsum) && al16(colpart) && al16(rowsum),
+                 "dagl_ce_project16_debug: planes, slots, feature rows, copies and sums must be 16-byte aligned");
+    const Grid g = make_grid(H, W);
+    ThrHeadSet ths = {};
+    if (thr) {
+        for (int h = 0; h < heads; ++h) { ths.x[h] = thr_x[h]; ths.thr_w[h] = thr_w[h]; ths.bias_w[h] = bias_w[h]; }
+        ths.imgs = imgs;
+        DAGL_REQUIRE(thr_bias4_ok(g, ths, heads), "dagl_ce_project16_debug: the thr / bias ride-along needs W %% 4 == 0 and 16-byte aligned x");
+    }
+    int rc;
+    if ((rc = check_workspace("dagl_ce_project16_debug", scratch, scratch_bytes, dagl_ce_project16_debug_scratch_bytes(heads)))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    uint16_t* wp2 = static_cast<uint16_t*>(scratch);                       // [heads] fc2 (keys), then [heads] fc1 (queries)
+    uint16_t* wp1 = wp2 + (size_t)heads * P16_PACKED_HALFS;
+    for (int h = 0; h < heads; ++h) {
+        if (keys && (rc = launch_pack_fc_weight16(s, fc2_w[h], wp2 + (size_t)h * P16_PACKED_HALFS))) return rc;
+        if (queries && (rc = launch_pack_fc_weight16(s, fc1_w[h], wp1 + (size_t)h * P16_PACKED_HALFS))) return rc;
+    }
+    const float* b1s[4]; const float* b2s[4];
+    for (int h = 0; h < 4; ++h) { b1s[h] = queries ? fc1_b[h < heads ? h : 0] : nullptr; b2s[h] = keys ? fc2_b[h < heads ? h : 0] : nullptr; }
+    Project16Launch pj;
+    pj.B = heads * imgs; pj.g = g; pj.which = which; pj.heads = heads;
+    pj.range.word = range_word; pj.range.tag = tag;
+    pj.map_hi = map_hi; pj.map_lo = map_lo;
+    pj.tiers.hi2 = const_cast<uint16_t*>(map_hi2); pj.tiers.lo2 = const_cast<uint16_t*>(map_lo2);
+    pj.tiers.amax = const_cast<float*>(amax); pj.tiers.slots = slots;
+    if (keys) { pj.keys.wp = wp2; pj.keys.bias = b2s; pj.keys.feat = x_feat; pj.keys.feat_bf16 = x_bf16; }
+    if (queries) { pj.queries.wp = wp1; pj.queries.bias = b1s; pj.queries.feat = wq_feat; pj.queries.feat_bf16 = wq_bf16; }
+    pj.colsum = colsum; pj.colpart = colpart; pj.q_tiled = q_tiled ? 1 : 0;
+    Split16Out so;
+    so.hi[0] = x_hi; so.lo[0] = x_lo; so.hi[1] = wq_hi; so.lo[1] = wq_lo;
+    so.rows_alloc[0] = feat_rows_h(g.N); so.rows_alloc[1] = feat_rows_h(g.L);
+    if (x_hi || wq_hi) pj.split = &so;
+    pj.rowsum = rowsum; pj.rowsum_policy = rowsum_policy;
+    if (thr) { pj.thr_hs = &ths; pj.thr_head_imgs = heads * imgs; pj.thr_part = thr_part; }
+    return launch_project16(s, pj);
+}
+
 // ---- the 7x7x16 -> 196 patch Linear (+ReLU) of the differentiable path's FORWARD on the inference kernels: split the map,
 // pack the weight, project (split-fp16 matrix cores, no unfolded rows), copy the feature rows out densely ---------------
 struct Pp16Ws { uint16_t *hi, *lo, *wp; float* feat; int64_t* words; size_t bytes; };

@@ -463,6 +463,14 @@ struct Project16Launch {
     const int32_t* rowsum_policy = nullptr;         // ... skipped while this workspace policy word is != 0 (tight threshold); null: always written
 };
 int launch_project16(hipStream_t s, const Project16Launch& a);
+// the launch plan of project16_kernel; index 0 = keys, 1 = queries (project16.hip: the one place the plan is computed)
+struct Project16Plan {
+    int n_items[2], segs[2], lin[2];                // 32-patch items per image / per grid row; items in row-major order across row ends
+    int units_q, units_k;                           // 8-item units per image (two blocks each), 0 for a side `which` leaves out
+    int cap;                                        // resident blocks: two per CU
+    int n_split_groups, n_full, n_proj;             // key units of the last image cut into single-tile blocks; two-group blocks; all blocks
+};
+Project16Plan project16_plan(const Grid& g, int B, int which, int cus /* <= 0: the current device's, 256 without one */);
 int launch_feat_rows_out(hipStream_t s, int B, int n, const float* feat /* [B, feat_rows(n), DS] */, float* rows_out /* [B, n, 196] */,
                          RangeTag range);            // dense copy of the feature rows; NaN when the call left the fp16 range
 int project16_key_blocks(const Grid& g);     // key blocks of project16: colpart is [B, key blocks, 224] floats

@@ -878,6 +878,31 @@ static inline bool p16_keys_linear(const Grid& g) { return g.W >= 32; }       //
 static inline int p16_key_items(const Grid& g) { return p16_keys_linear(g) ? (g.N + 31) / 32 : ((g.W + 31) / 32) * g.H; }
 int project16_key_blocks(const Grid& g) { return 2 * ((p16_key_items(g) + P16_UNIT - 1) / P16_UNIT); }   // rows of colpart: two per unit
 
+// The launch plan of project16_kernel: the one place it is computed (launch_project16 below; dagl_project16_plan reports it).
+// Index 0 = keys, 1 = queries.  cus <= 0: the current device's CU count, 256 without one.
+Project16Plan project16_plan(const Grid& g, int B, int which, int cus) {
+    static const int dev_cus = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    if (cus <= 0) cus = dev_cus;
+    Project16Plan p;
+    p.segs[0] = (g.W + 31) / 32; p.segs[1] = (g.Lw + 31) / 32;
+    p.lin[0] = p16_keys_linear(g) ? 1 : 0; p.lin[1] = 1;             // (queries gather per lane: any row length)
+    p.n_items[0] = p16_key_items(g); p.n_items[1] = (g.L + 31) / 32;
+    p.units_q = (which & 2) ? (p.n_items[1] + P16_UNIT - 1) / P16_UNIT : 0;
+    p.units_k = (which & 1) ? (p.n_items[0] + P16_UNIT - 1) / P16_UNIT : 0;
+    // resident capacity: two blocks per CU.  A remainder of at most half a round is cut into single-tile blocks.
+    p.cap = P16_BLOCKS_PER_CU * cus;
+    const int total = 2 * B * (p.units_q + p.units_k), rem = total % p.cap;
+    int groups = (rem > 0 && rem <= p.cap / 2) ? (rem + 1) / 2 : 0;      // units whose two blocks overhang the last full round
+    if (groups > p.units_k) groups = p.units_k;
+    p.n_split_groups = groups; p.n_full = total - 2 * groups;
+    p.n_proj = p.n_full + 2 * P16_NT * groups;
+    return p;
+}
+
 int launch_project16(hipStream_t s, const Project16Launch& a) {
     const int B = a.B, which = a.which, heads = a.heads; const Grid& g = a.g;
     const Split16Out* split = a.split; double* colsum = a.colsum; float* colpart = a.colpart;
@@ -902,27 +927,16 @@ int launch_project16(hipStream_t s, const Project16Launch& a) {
     pa.wp[1] = a.queries.wp; pa.feat[1] = a.queries.feat; pa.feat_h[1] = a.queries.feat_bf16;
     pa.rows_alloc[0] = feat_rows(g.N); pa.rows_alloc[1] = feat_rows(g.L);
     pa.rows_alloc_h[0] = feat_rows_h(g.N); pa.rows_alloc_h[1] = feat_rows_h(g.L);
-    pa.segs[0] = (g.W + 31) / 32; pa.segs[1] = (g.Lw + 31) / 32;
-    pa.lin[0] = p16_keys_linear(g) ? 1 : 0; pa.lin[1] = 1;           // (queries gather per lane: any row length)
-    pa.n_items[0] = p16_key_items(g); pa.n_items[1] = (g.L + 31) / 32;
-    const int uq = (which & 2) ? (pa.n_items[1] + P16_UNIT - 1) / P16_UNIT : 0;
-    const int uk = (which & 1) ? (pa.n_items[0] + P16_UNIT - 1) / P16_UNIT : 0;
+    const Project16Plan pl = project16_plan(g, B, which, 0);
+    for (int w = 0; w < 2; ++w) { pa.segs[w] = pl.segs[w]; pa.lin[w] = pl.lin[w]; pa.n_items[w] = pl.n_items[w]; }
+    const int uq = pl.units_q, uk = pl.units_k;
     const int nbq = 2 * uq, nbk = 2 * uk;
     pa.units_q = uq; pa.units_k = uk;
     pa.n_blocks_q = nbq; pa.n_blocks_k = nbk;
     pa.colpart = (colsum != nullptr) ? colpart : nullptr;
     pa.rowsum = (which & 1) ? a.rowsum : nullptr; pa.rowsum_policy = a.rowsum_policy;
-    // resident capacity: two blocks per CU.  A remainder of at most half a round is cut into single-tile blocks.
-    static const int cus = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    const int cap = P16_BLOCKS_PER_CU * cus, total = 2 * B * (uq + uk), rem = total % cap;
-    int groups = (rem > 0 && rem <= cap / 2) ? (rem + 1) / 2 : 0;        // units whose two blocks overhang the last full round
-    if (groups > uk) groups = uk;
-    pa.n_split_groups = groups; pa.n_full = total - 2 * groups; pa.batch = B;
-    pa.n_proj = pa.n_full + 2 * P16_NT * groups;
+    pa.n_split_groups = pl.n_split_groups; pa.n_full = pl.n_full; pa.batch = B;
+    pa.n_proj = pl.n_proj;
     pa.thr_part = nullptr; pa.thr_x = pa.thr_y = 1; memset(&pa.thr_hs, 0, sizeof(pa.thr_hs));
     int n_thr = 0;
     if (a.thr_hs != nullptr && a.thr_part != nullptr && a.thr_head_imgs > 0) {

@@ -1061,6 +1061,88 @@ def ce_prologue16_debug(xs, g_w, g_b, theta_w, theta_b, tag: int = 1, range_init
     return out
 
 
+PROJECT16_PLAN_FIELDS = ("key_items", "query_items", "lin", "units_q", "units_k", "n_full", "n_xcd", "n_split_groups", "n_proj", "cap",
+                         "segs_k", "segs_q")
+PROJECT16_FILL16 = 0x5A5A       # what ce_project16_debug leaves in the 16-bit halves the kernel does not store
+
+
+def project16_plan(B: int, H: int, W: int, which: int = 3, cus: int = 0) -> dict:
+    """The launch plan of ``project16_kernel`` on ``B`` images of [H, W] (``dagl_project16_plan``, host only), by the function the
+    launcher plans with; ``which``: 1 keys, 2 queries, 3 both; ``cus`` <= 0: the current device's compute units (256 without one)."""
+    out = (C.c_int32 * 12)()
+    check(_lib.load().dagl_project16_plan(int(B), int(H), int(W), int(which), int(cus), out), "dagl_project16_plan")
+    return dict(zip(PROJECT16_PLAN_FIELDS, (int(v) for v in out)))
+
+
+@_on_device
+def ce_project16_debug(map_hi, map_lo, H: int, W: int, heads: int = 1, which: int = 3, fc1_w=None, fc1_b=None, fc2_w=None, fc2_b=None,
+                       map_hi2=None, map_lo2=None, amax=None, bf16: bool = False, q_tiled: bool = False, split: bool = False,
+                       colsum: bool = False, rowsum: bool = False, policy=None, thr=None, tag: int = 1, range_init: int = 0,
+                       scratch=None) -> dict:
+    """The inference launch of the split-fp16 patch projection with every output read out (``dagl_ce_project16_debug``, for tests).
+    ``map_hi`` / ``map_lo`` (and the optional coarse pair with ``amax`` [heads, slots]): int16 bits [heads*imgs, H+6, W+6, 16]; ``fc1_*``
+    (queries) / ``fc2_*`` (keys): lists of one tensor per head, weights [196,784] in Linear order.  Switches: ``bf16`` copies (the query
+    copy in fragment order with ``q_tiled``), ``split`` copies, ``colsum`` (with colpart), ``rowsum`` (``policy``: None = no policy word,
+    else its value), ``thr`` = (xs, thr_w, bias_w) lists per head for the ride-along blocks.  Every buffer is poisoned before the call:
+    NaN in the floats, ``PROJECT16_FILL16`` in the 16-bit copies, ``range_init`` in the range word.  ``scratch``: a uint8 buffer to reuse.
+    -> dict of device tensors (None where not asked for): x, wq [B, rows, 204]; x_bf16, wq_bf16, x_hi, x_lo, wq_hi, wq_lo [B, rows_h, 216]
+    int16 bits; colsum [B,204] fp64, colpart [B, 2 units_k, 224]; rowsum [B,N,8]; thr_part [heads,4,imgs,L,2]; range int32 [1]."""
+    lib = _lib.load()
+    _need(map_hi, "map_hi", torch.int16); _need(map_lo, "map_lo", torch.int16)
+    B = map_hi.shape[0]
+    if tuple(map_hi.shape) != (B, H + 6, W + 6, 16) or map_lo.shape != map_hi.shape or B % heads:
+        raise DaglError("ce_project16_debug: planes are [heads*imgs, H+6, W+6, 16]")
+    imgs, dev = B // heads, map_hi.device
+    keys, queries = bool(which & 1), bool(which & 2)
+    for side, w, b, on in (("fc2", fc2_w, fc2_b, keys), ("fc1", fc1_w, fc1_b, queries)):
+        if on:
+            if w is None or b is None or len(w) != heads or len(b) != heads:
+                raise DaglError(f"ce_project16_debug: {side}: one weight and one bias per head")
+            for h in range(heads):
+                _need(w[h], f"{side}_w[{h}]"); _need(b[h], f"{side}_b[{h}]")
+    for t, n in ((map_hi2, "map_hi2"), (map_lo2, "map_lo2")):
+        if t is not None:
+            _need(t, n, torch.int16)
+    if amax is not None:
+        _need(amax, "amax")
+    N, (Lh, Lw) = H * W, query_grid(H, W)
+    L = Lh * Lw
+    rows = lambda n: lib.dagl_feat_rows(n)
+    rows_h = lambda n: -(-n // 64) * 64 + 64
+    nan = lambda *s, dtype=torch.float32: torch.full(s, float("nan"), device=dev, dtype=dtype)
+    half = lambda n, on: torch.full((B, rows_h(n), 216), PROJECT16_FILL16, device=dev, dtype=torch.int16) if on else None
+    units_k = project16_plan(B, H, W, which)["units_k"]
+    out = dict(x=nan(B, rows(N), DS) if keys else None, wq=nan(B, rows(L), DS) if queries else None,
+               x_bf16=half(N, bf16 and keys), wq_bf16=half(L, bf16 and queries),
+               x_hi=half(N, split and keys), x_lo=half(N, split and keys), wq_hi=half(L, split and queries), wq_lo=half(L, split and queries),
+               colsum=nan(B, DS, dtype=torch.float64) if colsum else None, colpart=nan(B, 2 * units_k, 224) if colsum else None,
+               rowsum=nan(B, N, 8) if rowsum else None, thr_part=None,
+               range=torch.full((1,), int(range_init), device=dev, dtype=torch.int32))
+    policy_word = torch.full((1,), int(policy), device=dev, dtype=torch.int32) if policy is not None else None
+    table = lambda ts: (C.c_void_p * heads)(*[t.data_ptr() for t in ts]) if ts is not None else None
+    thr_tables = (None, None, None)
+    if thr is not None:
+        for ts in thr:
+            for h in range(heads):
+                _need(ts[h], "thr operand")
+        out["thr_part"] = nan(heads, 4, imgs, L, 2)
+        thr_tables = tuple(table(ts) for ts in thr)
+    need = lib.dagl_ce_project16_debug_scratch_bytes(heads)
+    if scratch is None:
+        scratch = torch.full((need + 256,), 0xFF, device=dev, dtype=torch.uint8)
+    base = scratch.data_ptr() + (-scratch.data_ptr()) % 256
+    check(lib.dagl_ce_project16_debug(_stream(), heads, imgs, H, W, int(which), map_hi.data_ptr(), map_lo.data_ptr(), _ptr(map_hi2),
+                                      _ptr(map_lo2), _ptr(amax), int(amax.shape[-1]) if amax is not None else 0,
+                                      table(fc1_w if queries else None), table(fc1_b if queries else None),
+                                      table(fc2_w if keys else None), table(fc2_b if keys else None), int(tag), out["range"].data_ptr(),
+                                      base, scratch.numel() - (base - scratch.data_ptr()), _ptr(out["x"]), _ptr(out["wq"]),
+                                      _ptr(out["x_bf16"]), _ptr(out["wq_bf16"]), int(q_tiled), _ptr(out["x_hi"]), _ptr(out["x_lo"]),
+                                      _ptr(out["wq_hi"]), _ptr(out["wq_lo"]), _ptr(out["colsum"]), _ptr(out["colpart"]),
+                                      _ptr(out["rowsum"]), _ptr(policy_word), *thr_tables, _ptr(out["thr_part"])),
+          "dagl_ce_project16_debug")
+    return out
+
+
 @_on_device
 def ce_forward_fused(x, params: dict, mode: str = "adaptive", k: int = 0, workspace: "Workspace | None" = None,
                      profile: "StageProfile | None" = None, exact_scan: bool = False, weights_packed: bool = False,

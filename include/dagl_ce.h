@@ -172,7 +172,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
  * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*,
  * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
- * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan and dagl_ce_prologue16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
+ * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan, dagl_ce_prologue16_debug*, dagl_project16_plan and dagl_ce_project16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
 #define DAGL_ABI_VERSION 412
@@ -764,6 +764,38 @@ int    dagl_ce_prologue16_debug(void* stream, int heads, int imgs, int H, int W,
                                 const float* const* g_b, const float* const* theta_w, const float* const* theta_b, int32_t tag,
                                 void* scratch, size_t scratch_bytes, float* b1_nhwc, float* b2_nhwc, uint16_t* b1_hi, uint16_t* b1_lo,
                                 uint16_t* b1_hi2, uint16_t* b1_lo2, float* amax, int32_t* range_word, uint32_t* clear_a, int n);
+
+/* (detected by symbol) Read-outs for tests of the split-fp16 patch projection (csrc/project16.hip, project16_kernel).
+ * dagl_project16_plan: the launch plan of one call on B images of [H, W], which = 1 keys, 2 queries, 3 both, for a device of `cus` compute
+ * units (<= 0: the current device's, 256 without one), computed on the host by the function the launcher plans with:
+ *   out = { key items (32 patches each), query items, keys in row-major order across row ends (W >= 32), query units per image (8 items
+ *   each), key units per image, two-group blocks n_full, the ids among them mapped by XCD (n_full & ~15), key units of the last image cut
+ *   into 14 single-tile blocks each, projection blocks n_full + 14 groups, resident blocks 2 cus, key items per row, query items per row }
+ * dagl_ce_project16_debug: the inference launch of the kernel (the fused forward's launcher) on heads (1..4) x imgs images, with every
+ * output in the caller's buffers; nothing is cleared or padded in here, so what the kernel does not store keeps the caller's bytes.
+ * B = heads * imgs, batch index b = h * imgs + image; N = H W keys, L queries; rows = dagl_feat_rows(n), rows_h = round_up(n, 64) + 64.
+ *   map_hi/map_lo [B, H+6, W+6, 16] fp16 bits, 16 a = hi + lo;  map_hi2 / map_lo2: 2^-8 a = hi2 + lo2, both or neither, and with them
+ *               amax [heads][slots] (slots a multiple of 4, >= 4): a head whose largest slot s has 16 s < 60000 reads the fine pair
+ *   fc1_w/fc1_b queries, fc2_w/fc2_b keys: HOST arrays of `heads` device pointers, weights [196][16][49] (Linear order), biases [196];
+ *               only the sides of `which` are read, the outputs of the other side must be NULL
+ *   tag         != 0: written to *range_word when the call leaves the split-fp16 range (else the word keeps what the caller put there)
+ *   scratch     256-byte aligned, dagl_ce_project16_debug_scratch_bytes(heads) bytes (the heads' packed weights)
+ *   x_feat      [B, rows(N), 204] fp32 key features, wq_feat [B, rows(L), 204] query features
+ *   x_bf16/wq_bf16  optional [B, rows_h, 216] bf16 copies; q_tiled != 0: the query copy in the screen's fragment order
+ *   x_hi/x_lo, wq_hi/wq_lo  optional split copies [B, rows_h, 216] fp16 bits, 64 v = hi + lo (a pair is both or neither)
+ *   colsum      optional [B, 204] doubles with colpart [B, 2 key units, 224] floats (keys)
+ *   rowsum      optional [B, N, 8] floats (keys), not written while *rowsum_policy != 0 (the word may be NULL: always written)
+ *   thr_x/thr_w/bias_w + thr_part  optional ride-along blocks of the thr / bias heads: HOST arrays of `heads` device pointers
+ *               (x[h]: [imgs,64,H,W], 16-byte aligned, W % 4 == 0; weights [64][7][7]) and the partials [heads][4][imgs][L][2]   */
+int    dagl_project16_plan(int B, int H, int W, int which, int cus, int32_t out[12]);
+size_t dagl_ce_project16_debug_scratch_bytes(int heads);
+int    dagl_ce_project16_debug(void* stream, int heads, int imgs, int H, int W, int which, const uint16_t* map_hi, const uint16_t* map_lo,
+                               const uint16_t* map_hi2, const uint16_t* map_lo2, const float* amax, int slots, const float* const* fc1_w,
+                               const float* const* fc1_b, const float* const* fc2_w, const float* const* fc2_b, int32_t tag,
+                               int32_t* range_word, void* scratch, size_t scratch_bytes, float* x_feat, float* wq_feat, uint16_t* x_bf16,
+                               uint16_t* wq_bf16, int q_tiled, uint16_t* x_hi, uint16_t* x_lo, uint16_t* wq_hi, uint16_t* wq_lo,
+                               double* colsum, float* colpart, float* rowsum, const int32_t* rowsum_policy, const float* const* thr_x,
+                               const float* const* thr_w, const float* const* bias_w, float* thr_part);
 
 /* NCHW [B,16,H,W] -> zero-bordered NHWC [B,H+6,W+6,16]  (patch unfold without materialising
  * patches: replaces same_padding/extract_image_patches, dagl.py:123-169, for all three uses).    */

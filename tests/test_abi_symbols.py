@@ -24,7 +24,8 @@ def test_header_declares_the_path():
     syms = _declared_symbols()
     for must in ("dagl_ce_forward", "dagl_ce_workspace_bytes", "dagl_gather_aggregate", "dagl_last_error",
                  "dagl_project_patches", "dagl_fold_normalize", "dagl_ce_pivot_debug", "dagl_ce_wide_debug",
-                 "dagl_ce_prologue16_plan", "dagl_ce_prologue16_debug", "dagl_conv_pair_backward_plan"):
+                 "dagl_ce_prologue16_plan", "dagl_ce_prologue16_debug", "dagl_conv_pair_backward_plan",
+                 "dagl_project16_plan", "dagl_ce_project16_debug", "dagl_ce_project16_debug_scratch_bytes"):
         assert must in syms
 
 
