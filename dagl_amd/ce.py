@@ -159,6 +159,38 @@ class _GraphAttend(torch.autograd.Function):
         return d_wq, d_x, d_tau, None, None, None, None, None
 
 
+class _GraphForward(torch.autograd.Function):
+    """Features and value map -> block output on a given structure in one crossing of the edges (``ops.graph_forward_train``): the
+    composition of ``_GraphAttend`` and ``_GraphApply`` with ``ops.graph_forward``'s bits.  Differentiable in the two feature matrices,
+    ``tau`` and the value map (``ops.graph_forward_backward``); saved between forward and backward: the operands and (M, D) per row --
+    no per-edge tensor; the structure is a constant."""
+
+    @staticmethod
+    def forward(ctx, wq_rows, x_rows, tau, b2p, graph, scale, normalize, ws_f, ws_b):
+        wq_rows, x_rows, b2p = wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous()
+        tau_c = tau.contiguous() if tau is not None else None
+        out, row_max, row_sum = ops.graph_forward_train(wq_rows, x_rows, b2p, graph.row_off, graph.key, tau_c, scale=scale,
+                                                        normalize=normalize, workspace=ws_f)
+        ctx.graph, ctx.call, ctx.ws_b = graph, (scale, normalize), ws_b
+        ctx.tau_shape = tau.shape if tau is not None else None
+        ctx.save_for_backward(wq_rows, x_rows, tau_c, b2p, row_max, row_sum)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        wq_rows, x_rows, tau, b2p, row_max, row_sum = ctx.saved_tensors
+        g = ctx.graph
+        need_wq, need_x, need_tau, need_map = ctx.needs_input_grad[:4]
+        d_wq, d_x, d_tau, d_b2p = ops.graph_forward_backward(d_out.contiguous().float(), wq_rows, x_rows, b2p, g.row_off, g.key, row_max,
+                                                             row_sum, tau, scale=ctx.call[0], normalize=ctx.call[1],
+                                                             transposed=g.transpose() if need_x or need_map else None, need_wq=need_wq,
+                                                             need_x=need_x, need_tau=need_tau and tau is not None, need_b2p=need_map,
+                                                             workspace=ctx.ws_b)
+        if d_tau is not None:
+            d_tau = d_tau.view(ctx.tau_shape)
+        return d_wq, d_x, d_tau, d_b2p, None, None, None, None, None
+
+
 _CONV_WEIGHTS = ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight")
 
 
@@ -239,6 +271,7 @@ class CE(nn.Module):
         self._ws_apply_bwd = ops.Workspace()
         self._ws_attend = ops.Workspace()     # attend_graph() / forward_on_graph(): the row statistics; the backward's sums and partial rows
         self._ws_attend_bwd = ops.Workspace()
+        self._ws_forward_bwd = ops.Workspace()    # forward_on_graph(backward="fused"): dAgg, d V rows, three floats per edge, the rows' sums
         self._ws_lists = ops.Workspace()      # forward_with_graph(): the list-form core's forward and backward, the degrees of the CSR conversion
         self._ws_lists_bwd = ops.Workspace()
         self._ws_lists_csr = ops.Workspace()
@@ -733,33 +766,50 @@ class CE(nn.Module):
             else (lambda t: t)
         return wq_rows, x_rows, tau, b2p, poisoned
 
-    def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool, features: str = "fp32",
-                         fused=False):
-        """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route or
-        (``features="split16"``) the training path's split-fp16 kernels, ``tau`` in plain torch, then ``_GraphAttend`` and -- ``apply`` --
-        ``_GraphApply`` on the same value map, or (``fused``; None = with ``features="split16"`` whenever no gradient is wanted)
-        ``ops.graph_forward`` in their place.  -> (weight, score, out | None); the fused call returns (None, None, out)."""
+    def _attend_arguments(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool, features: str, fused, backward: str):
+        """The refusals of ``attend_graph`` / ``forward_on_graph``, raised before any launch -> (margin, split-fp16 features?, gradient
+        wanted?, ``ops.graph_forward``?, ``_GraphForward``?)."""
         self._check_given_graph(b, graph, what)
         if normalize not in ("reference", "edges"):
             raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
         if features not in ("fp32", "split16"):
             raise DaglError(f"CE.{what}: features={features!r}, expected 'fp32' or 'split16'")
+        if backward not in ("two_ops", "fused"):
+            raise DaglError(f"CE.{what}: backward={backward!r}, expected 'two_ops' or 'fused'")
         fast = features == "split16"
         if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
             raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
         margin = self.select_mode != "topk" if margin is None else bool(margin)
         used = [self.g, self.fc1, self.fc2] + ([self.theta] if apply else []) + ([self.thr_conv, self.bias_conv] if margin else [])
         grad = torch.is_grad_enabled() and (b.requires_grad or any(p.requires_grad for m in used for p in m.parameters()))
+        fused_train = grad and apply and backward == "fused"
         if grad:
-            if fused:
+            if fused_train and fused is not None and not fused:
+                raise DaglError(f"CE.{what}: fused=False contradicts backward='fused' (the fused backward belongs to the fused forward); "
+                                "leave fused at None or pass backward='two_ops'")
+            if fused and not fused_train:
                 raise DaglError(f"CE.{what}: fused=True has no backward (a gradient is wanted for the input or a parameter); "
                                 "fused=None or False keeps the two differentiable ops")
             if any(p.dtype != torch.float32 for p in self.parameters()):
                 raise DaglError(self._FP32_ONLY)
         # (None: the fused kernel belongs to the opt-in route -- the default call keeps the bits of the two-op composition)
         fused = apply and not grad and (fast if fused is None else bool(fused))
+        return margin, fast, grad, fused, fused_train
+
+    def _attend_on_graph(self, b: torch.Tensor, graph, what: str, margin, normalize: str, apply: bool, features: str = "fp32",
+                         fused=False, backward: str = "two_ops"):
+        """``attend_graph`` (``apply`` False) and ``forward_on_graph``: one prologue call, fc1 / fc2 on the fp32 route or
+        (``features="split16"``) the training path's split-fp16 kernels, ``tau`` in plain torch, then ``_GraphAttend`` and -- ``apply`` --
+        ``_GraphApply`` on the same value map, or (``fused``; None = with ``features="split16"`` whenever no gradient is wanted)
+        ``ops.graph_forward`` in their place, or (``backward="fused"`` with a gradient wanted) ``_GraphForward``.
+        -> (weight, score, out | None); the fused calls return (None, None, out)."""
+        margin, fast, grad, fused, fused_train = self._attend_arguments(b, graph, what, margin, normalize, apply, features, fused, backward)
         with torch.enable_grad() if grad else torch.no_grad():
             wq_rows, x_rows, tau, b2p, poisoned = self._graph_features(b, margin, fast, grad)
+            if fused_train:
+                out = _GraphForward.apply(wq_rows, x_rows, tau, b2p, graph, float(self.softmax_scale), normalize, self._ws_apply,
+                                          self._ws_forward_bwd)
+                return None, None, poisoned(out)
             if fused:
                 out = ops.graph_forward(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
                                         tau.contiguous() if tau is not None else None, scale=float(self.softmax_scale),
@@ -799,7 +849,7 @@ class CE(nn.Module):
         return g
 
     def forward_on_graph(self, b: torch.Tensor, graph, *, margin=None, normalize: str = "reference", features: str = "fp32",
-                         fused=None) -> torch.Tensor:
+                         fused=None, backward: str = "two_ops") -> torch.Tensor:
         """The block's output for ``b`` with its weights recomputed on the structure of ``graph``: ``apply_graph(b, attend_graph(b, graph))``
         from one prologue call -- differentiable in ``b`` and every parameter of g, theta, fc1, fc2 and (with the margin) thr_conv,
         bias_conv; selection over the L*N pairs is skipped.  Arguments (``features`` and its range contract included), refusals and state
@@ -809,8 +859,17 @@ class CE(nn.Module):
         ``weight`` / ``score`` arrays) -- refused before any launch when a gradient is wanted, it has no backward; False = the two
         differentiable ops; None = the fused kernel whenever no gradient is wanted on the ``features="split16"`` route, the two ops
         otherwise -- so a call with default arguments returns the bits it always did.  The fused result differs from the two-op one
-        by fp32 roundings only.  ``graph.weight`` / ``graph.score`` are left alone either way."""
-        out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True, features, fused)[2]
+        by fp32 roundings only.  ``graph.weight`` / ``graph.score`` are left alone either way.
+
+        ``backward`` ("two_ops" or "fused"; anything else is refused before any launch) chooses the differentiable route when a gradient
+        is wanted and is only validated otherwise.  "two_ops": the two ops and their backwards, autograd keeps ``score`` and ``weight``
+        (two fp32 arrays per edge); ``fused=True`` stays refused.  "fused": ``ops.graph_forward_train`` -- the output carries the bits of
+        the no-grad ``fused=True`` call on the same features -- and ``ops.graph_forward_backward``, which recomputes scores and weights in
+        one crossing of the edges; autograd keeps twelve bytes per row (the row's maximum and sum) instead.  It serves either
+        ``features`` route with its range contract, is differentiable in the same tensors as "two_ops", and takes ``fused=None`` or
+        True; ``fused=False`` contradicts it and is refused.  For a sequence: ``g = ce.refresh_graph(frame, g)`` (no gradients), then
+        ``ce.forward_on_graph(frame, g, backward="fused")`` under autograd."""
+        out = self._attend_on_graph(b, graph, "forward_on_graph", margin, normalize, True, features, fused, backward)[2]
         return out if b.dtype == torch.float32 else out.to(b.dtype)
 
     def refresh_graph(self, b: torch.Tensor, graph, *, radius: int = 1, margin=None, normalize: str = "reference",

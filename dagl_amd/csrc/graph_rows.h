@@ -9,7 +9,10 @@
 // graph_apply_combine_kernel its two clamps (gt_clamp).  Everything else calls the helpers below.
 // Left written out on purpose: rf_max / rf_sum / rf_scan of graph_refresh.hip (templated on the block size, and they add the waves'
 // partials one after the other where block_sum_f64 adds (w0 + w1) + (w2 + w3): other bits); rf_ord (a total order for the rank cut,
-// no other route ranks); graph_attend_rows_kernel next to graph_forward_combine_kernel (the second fuses the sum into its scaling loop).
+// no other route ranks); graph_attend_rows_kernel next to graph_forward_combine_kernel (the second fuses the sum into its scaling loop);
+// graph_forward.hip's training kernels next to their models -- graph_forward_row_stats_kernel (the combine kernel's (M, D) into arrays
+// of their own), graph_forward_bwd_rows_kernel (graph_attend_bwd_rows_kernel), graph_forward_bwd_combine_kernel
+// (graph_attend_combine_kernel at either width): a __global__ lives in one translation unit, and graph_attend.hip's are pinned.
 #pragma once
 #include <cstdint>
 #include "dagl_common.h"

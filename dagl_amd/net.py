@@ -212,6 +212,41 @@ class CES(nn.Module):
             out = self._between_stages(s, out)
         return out, (SequenceState(new) if want_graphs else None)
 
+    def forward_on_graphs(self, x, state, *, features: str = "fp32", backward: str = "two_ops"):
+        """The module's output for ``x`` on the FROZEN graphs of ``state`` -> ``out``: ``forward``'s wiring with every head run as
+        ``hd.forward_on_graph(stage input, state.head(s, h), features=..., backward=...)`` -- its weights recomputed on the head's
+        structure, no selection --, the stage's own mix and residual, ``RBS1`` / ``RBS2`` between the stages.  Not under
+        ``torch.no_grad()``: differentiable in ``x`` and every parameter it uses (``CE.forward_on_graph`` names the heads'), the
+        structures are constants.  For fine-tuning on a sequence: ``_, state = ces.step_graphs(frame, state)`` moves the graphs without
+        gradients, ``ces.forward_on_graphs(frame, state, backward="fused")`` trains on the result.
+
+        Head by head; a stage-fused training launch does not exist.  Refused before the first launch: a ``state`` that is no
+        ``SequenceState`` or was built for another ``B``, ``H`` or ``W``, a head that is not a ``CE``, and every head's own refusals
+        (``CE.forward_on_graph``'s; those that depend on whether a gradient is wanted are looked at with ``x`` as every stage's input and
+        once more when the head runs).  The modules' state is untouched."""
+        from ._lib import DaglError
+        from .sequence import SequenceState
+        what = "CES.forward_on_graphs"
+        if not isinstance(state, SequenceState):
+            raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise DaglError(f"{what}: expected [B,C,H,W]")
+        g0 = state.stages[0]
+        if (g0.B, g0.H, g0.W) != (4 * x.shape[0], x.shape[2], x.shape[3]):
+            raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={x.shape[0]} H={x.shape[2]} "
+                            f"W={x.shape[3]}")
+        for s in (1, 2, 3):
+            for h, hd in enumerate(self._stage_modules(s)[0]):
+                if not isinstance(hd, CE):
+                    raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it runs on no graph")
+                hd._attend_arguments(x, state.head(s - 1, h), "forward_on_graph", None, "reference", True, features, None, backward)
+        out = x
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            outs = [hd.forward_on_graph(out, state.head(s - 1, h), features=features, backward=backward) for h, hd in enumerate(heads)]
+            out = self._between_stages(s, mix(torch.cat(outs, dim=1)) + out)
+        return out
+
     def _plan_step(self, x, state, radius, features, want_graphs, fused):
         """Every refusal of ``step_graphs`` that depends on a stage, raised before the first launch -- every stage sees an input of x's
         shape, dtype and device -- -> {stage: (fused?, what ``CE._refresh_arguments`` returns for its heads)}."""
@@ -337,6 +372,13 @@ class RR(nn.Module):
         ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused`` as there); always under ``torch.no_grad()``.  The ``CES``'s
         refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
         return self._forward_around_ces(x, lambda ces, t: ces.step_graphs(t, state, **kw))
+
+    def forward_on_graphs(self, x, state, **kw):
+        """The network's output for ``x`` on the frozen graphs of ``state`` -> ``out``: ``forward`` with
+        ``CES.forward_on_graphs(., state, **kw)`` where the ``CES`` sits (``features``, ``backward`` as there).  Not under
+        ``torch.no_grad()``: with autograd enabled the result trains the trunk and the heads on constant structures.  The ``CES``'s
+        refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
+        return self._forward_around_ces(x, lambda ces, t: (ces.forward_on_graphs(t, state, **kw), None))[0]
 
     def load_state_dict(self, state_dict, strict=True):
         """The reference network's own loader rule (``dagl.py:56-73``), which is NOT torch's: checkpoint entries are

@@ -557,17 +557,77 @@ def graph_forward(wq_rows, x_rows, b2p, row_off, key, tau=None, scale: float = 1
     result differs from the two-call one by fp32 roundings (weights are applied as e^(z - max) and scaled per row afterwards); the same
     arrays give the same bits on every call.  Nothing is read on the host."""
     lib = _lib.load()
-    _need(b2p, "b2p")
-    hw = _value_map("graph_forward", b2p)[1:]
-    B, H, W, E, flags = _graph_attend_operands("graph_forward", wq_rows, x_rows, row_off, key, tau, normalize, hw)
-    if b2p.shape[0] != B:
-        raise DaglError(f"graph_forward: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    B, H, W, E, flags = _graph_forward_operands("graph_forward", wq_rows, x_rows, b2p, row_off, key, tau, normalize)
     buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_forward_workspace_bytes", B, H, W, E)
     out = torch.empty(B, 16, H, W, device=wq_rows.device, dtype=torch.float32)
     check(lib.dagl_graph_forward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
                                  _ptr(key, E > 0), E, _ptr(tau), float(scale), flags, out.data_ptr(), a, nbytes), "dagl_graph_forward")
     del buf
     return out
+
+
+def _graph_forward_operands(who: str, wq_rows, x_rows, b2p, row_off, key, tau, normalize):
+    """Shapes of a fused graph call's operands -> (B, H, W, E, flags): ``_graph_attend_operands`` on the map of ``b2p``."""
+    _need(b2p, "b2p")
+    hw = _value_map(who, b2p)[1:]
+    B, H, W, E, flags = _graph_attend_operands(who, wq_rows, x_rows, row_off, key, tau, normalize, hw)
+    if b2p.shape[0] != B:
+        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    return B, H, W, E, flags
+
+
+@_on_device
+def graph_forward_train(wq_rows, x_rows, b2p, row_off, key, tau=None, scale: float = 10.0, normalize: str = "reference",
+                        workspace: "Workspace | None" = None):
+    """``graph_forward`` for training (``dagl_graph_forward_train``) -> (out [B,16,H,W], row_max [B*L] fp32, row_sum [B*L] fp64): ``out``
+    carries ``graph_forward``'s bits, ``row_max`` / ``row_sum`` are the (M, D) each row was normalised with -- twelve bytes per row, all
+    ``graph_forward_backward`` needs next to the operands.  An empty row's slots hold 0 and 1."""
+    lib = _lib.load()
+    B, H, W, E, flags = _graph_forward_operands("graph_forward_train", wq_rows, x_rows, b2p, row_off, key, tau, normalize)
+    buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_forward_workspace_bytes", B, H, W, E)
+    out = torch.empty(B, 16, H, W, device=wq_rows.device, dtype=torch.float32)
+    row_max = torch.empty(B * wq_rows.shape[1], device=wq_rows.device, dtype=torch.float32)
+    row_sum = torch.empty(B * wq_rows.shape[1], device=wq_rows.device, dtype=torch.float64)
+    check(lib.dagl_graph_forward_train(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
+                                       _ptr(key, E > 0), E, _ptr(tau), float(scale), flags, out.data_ptr(), row_max.data_ptr(),
+                                       row_sum.data_ptr(), a, nbytes), "dagl_graph_forward_train")
+    del buf
+    return out, row_max, row_sum
+
+
+@_on_device
+def graph_forward_backward(d_out, wq_rows, x_rows, b2p, row_off, key, row_max, row_sum, tau=None, scale: float = 10.0,
+                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,
+                           need_b2p: bool = True, workspace: "Workspace | None" = None):
+    """Gradients of ``graph_forward_train`` (``dagl_graph_forward_backward``) -> (d_wq [B,L,196] | None, d_x [B,N,196] | None,
+    d_tau [B*L] | None, d_b2p [B,H+6,W+6,16] | None) from ``d_out`` [B,16,H,W]; ``row_max`` / ``row_sum`` are the forward's.  One crossing
+    of the edges recomputes scores and weights and forms ``<dAgg, V>`` per edge: what ``graph_apply_backward`` followed by
+    ``graph_attend_backward`` computes from stored ``score`` / ``weight`` arrays.  ``transposed`` = (col_off, src_row, perm), the graph's
+    transposed CSR (``PatchGraph.transpose``): required with ``need_x`` or ``need_b2p``.  ``d_tau`` is None without ``tau``.  Any subset
+    of the outputs carries the bits of the full call."""
+    lib = _lib.load()
+    who = "graph_forward_backward"
+    B, H, W, E, flags = _graph_forward_operands(who, wq_rows, x_rows, b2p, row_off, key, tau, normalize)
+    n_rows = B * wq_rows.shape[1]
+    _need(d_out, "d_out"); _need(row_max, "row_max"); _need(row_sum, "row_sum", torch.float64)
+    if tuple(d_out.shape) != (B, 16, H, W):
+        raise DaglError(f"{who}: d_out is {tuple(d_out.shape)}, expected {(B, 16, H, W)}")
+    if row_max.numel() != n_rows or row_sum.numel() != n_rows:
+        raise DaglError(f"{who}: row_max and row_sum must hold B*L = {n_rows} values")
+    col_off = src_row = perm = None
+    if need_x or need_b2p:
+        col_off, src_row, perm = _transposed_csr(who, "d_x" if need_x else "d_b2p", transposed, B * H * W, E)
+    buf, a, nbytes = _sized_region(workspace, wq_rows.device, "dagl_graph_forward_backward_workspace_bytes", B, H, W, E)
+    d_wq = torch.empty_like(wq_rows) if need_wq else None
+    d_x = torch.empty_like(x_rows) if need_x else None
+    d_tau = torch.empty(n_rows, device=wq_rows.device, dtype=torch.float32) if need_tau and tau is not None else None
+    d_b2p = torch.empty_like(b2p) if need_b2p else None
+    check(lib.dagl_graph_forward_backward(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
+                                          _ptr(key, E > 0), E, _ptr(tau), float(scale), flags, row_max.data_ptr(), row_sum.data_ptr(),
+                                          d_out.data_ptr(), _ptr(col_off), _ptr(src_row, E > 0), _ptr(perm, E > 0), _ptr(d_wq), _ptr(d_x),
+                                          _ptr(d_tau), _ptr(d_b2p), a, nbytes), "dagl_graph_forward_backward")
+    del buf
+    return d_wq, d_x, d_tau, d_b2p
 
 
 @_on_device

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward*, dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*,
+ * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*,
  * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
  * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan, dagl_ce_prologue16_debug*, dagl_project16_plan and dagl_ce_project16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
@@ -397,6 +397,42 @@ size_t dagl_graph_forward_workspace_bytes(int B, int H, int W, int64_t total_edg
 int dagl_graph_forward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
                        const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau /* NULL: no margin */, float scale,
                        int flags /* bit 0: edges-only normalisation */, float* out, void* workspace, size_t ws_bytes);
+
+/* ---- training on a GIVEN patch graph in one crossing of the edges: csrc/graph_forward.hip (ABI 412, detected by symbol) --------------
+ * dagl_graph_forward_train: dagl_graph_forward -- the same operands, checks, launches and workspace (dagl_graph_forward_workspace_bytes),
+ * `out` bit for bit -- plus one launch that leaves the row statistics the forward normalised with:
+ *   row_max_out [B L] fp32 = M_r, row_sum_out [B L] fp64 = D_r (the (N - deg) e^(-M) term included); an empty row gets 0 and 1, which
+ *   nothing reads.  These twelve bytes per row are all a caller keeps for the backward: no per-edge array.
+ * dagl_graph_forward_backward: the gradients of that forward from d_out [B,16,H,W], the forward's operands and (row_max, row_sum).  With
+ * dAgg = unfold(d_out / cnt) as dagl_graph_apply_backward forms it and w_e = on_e e^(z_e - M_r) / D_r recomputed from the saved statistics:
+ *   g_e = <dAgg[r], V[key_e]> (0 on an edge without a value row),  c_r = sum_e w_e g_e
+ *   d S_e = scale (m_e + S_e) w_e (g_e - c_r) on edges with on_e (tau given), scale w_e (g_e - c_r) (tau NULL), else 0
+ *   d_tau [B L]           = -scale sum_on S_e w_e (g_e - c_r)                    (may be NULL; needs tau)
+ *   d_wq_rows [B,L,196]   = sum_{e in r} d S_e x_rows[b, key_e]                  (may be NULL)
+ *   d_x_rows [B,N,196]    = sum_{key_e = j} d S_e wq_rows[r_e]                   (may be NULL; needs the transposed CSR)
+ *   d_b2p [B,H+6,W+6,16]  = the fold of d V[j] = sum_{key_e = j} w_e dAgg[r_e]   (may be NULL; needs the transposed CSR)
+ * col_off [B N + 1] / src_row [E] / perm [E]: the transposed CSR of dagl_graph_apply_backward.  Every element of a requested output is
+ * written, and any subset of the outputs carries the bits of the full call.  One launch per segment of dagl_graph_apply_segment() edges
+ * recomputes S_e (the forward's own arithmetic: the heaviest edge of a one-hot row weighs exactly 1), w_e and g_e and leaves the fp64
+ * partial sums of c_r and d tau_r; a launch per row finishes them; the three products are segment + combine launches over the CSR and
+ * its transpose, d S_e formed where a segment is staged; d V rows are folded as dagl_graph_apply_backward folds them.  Maxima fp32,
+ * sums of statistics fp64 in edge and segment order, no float atomics: the same arrays give the same bits on every call.  A key,
+ * src_row or perm entry outside its range is tested before an address is formed and contributes nothing (the key still counted in D).
+ * Grids come from total_edges and the row counts: nothing is read on the host.  Workspace: dagl_graph_forward_backward_workspace_bytes =
+ * dAgg [B L, 784] + d V rows [B N, 784] + a partial row per segment + three floats per edge (S, w, g: scratch of this call) + three
+ * fp64 sums per row and per segment.  Every argument is checked before the first launch: null pointers, 16-byte alignment of the
+ * feature rows, the maps and the gradient rows, d_tau without tau, d_x_rows / d_b2p without the transposed CSR, the workspace size. */
+int dagl_graph_forward_train(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                             const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau /* NULL: no margin */,
+                             float scale, int flags /* bit 0: edges-only normalisation */, float* out, float* row_max_out,
+                             double* row_sum_out, void* workspace, size_t ws_bytes);
+size_t dagl_graph_forward_backward_workspace_bytes(int B, int H, int W, int64_t total_edges);
+int dagl_graph_forward_backward(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                                const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau, float scale, int flags,
+                                const float* row_max, const double* row_sum, const float* d_out, const int64_t* col_off,
+                                const int32_t* src_row, const int32_t* perm, float* d_wq_rows /* may be NULL */,
+                                float* d_x_rows /* may be NULL */, float* d_tau /* may be NULL */, float* d_b2p /* may be NULL */,
+                                void* workspace, size_t ws_bytes);
 
 /* ---- the patch graph of a differentiable forward, from its own neighbour lists: csrc/graph_lists.hip (ABI 412, detected by symbol) ---
  * dagl_ce_core_forward leaves each query's neighbours as fixed-width lists in selection order; nb_wgt = exp(l_t) / Z_l with the unlisted

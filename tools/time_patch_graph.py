@@ -8,6 +8,8 @@
                                                       # top-k 8 at 256 256; with a size (1024 1024) adaptive AND top-16
     python tools/time_patch_graph.py --step [H W]     # ``CE.step_graph`` (with and without the graph) next to that two-call sequence and
                                                       # to ``forward``, the same two cases
+    python tools/time_patch_graph.py --train-graph [H W]  # training on a frozen graph: the fused forward / backward next to the two
+                                                          # ops and their backwards, ops alone and through ``forward_on_graph``
 """
 import os
 import sys
@@ -342,7 +344,83 @@ def step_leg(H, W, big):
           f"ops.graph_forward alone on the result {fmt(k_fwd)}", flush=True)
 
 
+def train_graph_leg(H, W):
+    """Training on a frozen graph, the three graphs of ``apply_leg``, one process, the protocol of ``attend_leg``.  The ops alone (the
+    module's own fp32 features given): ``graph_attend`` + ``graph_apply`` next to ``graph_forward_train``, ``graph_apply_backward`` +
+    ``graph_attend_backward`` next to ``graph_forward_backward``.  The module: ``forward_on_graph`` forward + backward with
+    ``backward="two_ops"`` and ``"fused"`` on both feature routes, and the module's own ``_forward_train`` forward + backward for
+    orientation.  The yardstick of every fused figure is the two-op figure of the same run."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    for name, mode, k, variant, tail in _table_cases():
+        prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=1.65).items()}
+        ce = CE(in_channels=64)
+        ce.load_state_dict(prm, strict=True)
+        ce.select_mode, ce.select_k = mode, max(k, 1)
+        ce = ce.to(dev).eval()
+        with torch.no_grad():
+            g = ce.graph(x)
+            if tail:
+                g = _long_tailed(g)
+            g.validate()
+            tr = g.transpose()
+            wq, xk, tau, b2p, _ = ce._graph_features(x, mode != "topk", False, False)
+            wq, xk, b2p, tau = wq.contiguous(), xk.contiguous(), b2p.contiguous(), (tau.contiguous() if tau is not None else None)
+            call = dict(tau=tau, scale=float(ce.softmax_scale))
+            ws = [ops.Workspace() for _ in range(6)]
+            weight, score = ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws[0], hw=(H, W), **call)
+            _, row_max, row_sum = ops.graph_forward_train(wq, xk, b2p, g.row_off, g.key, workspace=ws[2], **call)
+            d_out = torch.randn(1, 16, H, W, device=dev)
+
+            def two_forward():
+                w, _ = ops.graph_attend(wq, xk, g.row_off, g.key, workspace=ws[0], hw=(H, W), **call)
+                return ops.graph_apply(b2p, g.row_off, g.key, w, workspace=ws[1])
+
+            def two_backward():
+                _, d_w = ops.graph_apply_backward(d_out, b2p, g.row_off, g.key, weight, transposed=tr, workspace=ws[3])
+                return ops.graph_attend_backward(d_w, wq, xk, g.row_off, g.key, score, weight, transposed=tr, workspace=ws[4], hw=(H, W), **call)
+            k_f2 = _events(two_forward)
+            k_f1 = _events(lambda: ops.graph_forward_train(wq, xk, b2p, g.row_off, g.key, workspace=ws[2], **call))
+            k_b2 = _events(two_backward)
+            k_b1 = _events(lambda: ops.graph_forward_backward(d_out, wq, xk, b2p, g.row_off, g.key, row_max, row_sum, transposed=tr,
+                                                              workspace=ws[5], **call))
+        xg = x.clone().requires_grad_(True)
+        module = {}
+        for features in ("fp32", "split16"):
+            for backward in ("two_ops", "fused"):
+                def both():
+                    ce.forward_on_graph(xg, g, features=features, backward=backward).sum().backward()
+                    xg.grad = None
+                    ce.zero_grad(set_to_none=True)
+                module[(features, backward)] = _events(both, repeats=5, inner=10)
+        ce.train()
+
+        def train_both():
+            ce._forward_train(xg).sum().backward()
+            xg.grad = None
+            ce.zero_grad(set_to_none=True)
+        trb = _events(train_both, repeats=5, inner=10)
+        ce.eval()
+        rows = g.B * g.L
+        print(f"[1,64,{H},{W}] {name}: {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {int(g.degrees().max())}\n"
+              f"    ops forward: graph_attend + graph_apply {fmt(k_f2)}; graph_forward_train {fmt(k_f1)}\n"
+              f"    ops backward: graph_apply_backward + graph_attend_backward {fmt(k_b2)}; graph_forward_backward {fmt(k_b1)}\n"
+              f"    forward_on_graph forward + backward, fp32 features: two_ops {fmt(module[('fp32', 'two_ops')])}; fused "
+              f"{fmt(module[('fp32', 'fused')])}\n"
+              f"    forward_on_graph forward + backward, split16 features: two_ops {fmt(module[('split16', 'two_ops')])}; fused "
+              f"{fmt(module[('split16', 'fused')])}\n"
+              f"    the module's own training path (_forward_train, its own selection) forward + backward {fmt(trb)}\n"
+              f"    kept by autograd between forward and backward: two_ops score + weight = {8 * g.n_edges} B; fused row_max + row_sum = "
+              f"{12 * rows} B", flush=True)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--train-graph":
+        return train_graph_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     if len(sys.argv) > 1 and sys.argv[1] == "--step":
         return step_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--refresh":
