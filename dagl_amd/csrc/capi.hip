@@ -1057,15 +1057,20 @@ static int select_screened(Call& c) {
     int32_t* policy = stat32(c.stats, STAT_POLICY);
     mark(c, 3);
     if (c.mode != DAGL_MODE_ADAPTIVE) {                     // top-k threshold from the sampling pass
+        bool fused = false;
         if (c.pivot) {                                      // ... over the two heaviest keys of every 64 (pivot.hip)
             PivotArgs pv;
             memset(&pv, 0, sizeof(pv));
             pv.B = c.B; pv.N = c.g.N; pv.n_blk = (c.g.N + 63) / 64; pv.steps = p.pv_steps;
             pv.rowsum = at<float>(ws, p.o_rowsum); pv.xh = c.Xh; pv.rows_xh = sc.rows_xh;
             pv.xp = at<uint16_t>(ws, p.o_xp); pv.rows_xp = sc.rows_xp; pv.pidx = at<int32_t>(ws, p.o_pidx); pv.policy = sc.policy;
-            if ((rc = launch_pivot_keys(c.s, pv))) return rc;
+            // one launch picks, fetches and scores them (pivot_sample_kernel); DAGL_PIVOT_SAMPLE=0 keeps the two launches with the
+            // pivot matrix between them: the same results, for comparing the two
+            static const bool one_launch = [] { const char* e = getenv("DAGL_PIVOT_SAMPLE"); return !(e && atoi(e) == 0); }();
+            fused = one_launch && pivot_sample_serves(sc);
+            if ((rc = fused ? launch_pivot_sample(c.s, sc, pv) : launch_pivot_keys(c.s, pv))) return rc;
         }
-        if ((rc = launch_screen(c.s, sc, 0))) return rc;
+        if (!fused && (rc = launch_screen(c.s, sc, 0))) return rc;
         if ((rc = launch_screen_theta(c.s, (int)c.BL, p.s_splits * 2 * p.s_gkeep, c.k, sc.gmax, theta, nullptr, sc.spill_cnt))) return rc;
     }
     if (c.mode != DAGL_MODE_TOPK && !c.fused_theta)         // adaptive threshold; the intersection mode takes the larger

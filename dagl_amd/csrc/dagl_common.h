@@ -632,6 +632,10 @@ struct PivotArgs {
 int launch_pivot_keys(hipStream_t s, const PivotArgs& a);
 int launch_pivot_rowsum(hipStream_t s, size_t n_keys, const float* slots, float* out);
 int launch_screen(hipStream_t s, const ScreenArgs& a, int pass);
+// screen.hip: pivot_keys_kernel + launch_screen(.., 0) as ONE launch (xp is neither written nor read), for the calls it serves:
+// sampling from the pivots with one step per block (and, under a policy word, blocks of >= 384 queries)
+bool pivot_sample_serves(const ScreenArgs& a);
+int launch_pivot_sample(hipStream_t s, const ScreenArgs& a, const PivotArgs& pv);
 int launch_screen_theta(hipStream_t s, int n_rows, int G, int k, const float* gmax, float* theta, const int32_t* gate = nullptr,
                         unsigned* spill_cnt = nullptr);
 // top-k modes, cold workspace: after the first refine -- more than a fiftieth of the query GROUPS are flagged (overflowed candidate slots) under

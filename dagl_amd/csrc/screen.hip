@@ -18,6 +18,7 @@
 // Keys passing these tests are the candidates; a (query, chunk, half) segment that receives more than its
 // slot count raises a flag and that query group is redone by the exact fp32 kernel (select.hip).
 #include "dagl_common.h"
+#include "pivot_pick.h"
 #include "wide_select.h"
 
 namespace dagl {
@@ -333,12 +334,12 @@ constexpr int RING_FLAG_BYTES = 64;
 // One query tile of 32 per wave (16 waves x 32 queries: four waves per SIMD, 128 registers; two tiles per wave were measured and
 // dropped: docs/HISTORY.md, round 3).  Shared with screen_kernel: load_query_fragments, screen_policy and screen_finish as
 // functions; the query set-up and the step's tail as text (see the note above screen_policy).
+// The block as a function of the kernel's own copy of a (policy applied) and its ONE shared object, RING_SMEM_ELEMS long (a second
+// one makes hipcc drain vmcnt(0) in front of every ds_read of the loop): screen_ring_kernel is this and nothing else, and
+// pivot_sample_kernel runs it on a workspace that is on the tight threshold.
+constexpr int RING_SMEM_ELEMS = RING_NBUF * STEP_ELEMS + RING_FLAG_BYTES / 2;
 template <int PASS, int WAVES, int VAR = 0, bool SMAX = false>
-__global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a, int n_qgroups) {
-    if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
-    screen_policy<PASS>(a);
-    // ONE shared object (a second one makes hipcc drain vmcnt(0) in front of every ds_read of the loop)
-    __shared__ __attribute__((aligned(16))) unsigned short smem[RING_NBUF * STEP_ELEMS + RING_FLAG_BYTES / 2];
+__device__ __forceinline__ void screen_ring_block(const ScreenArgs a, int n_qgroups, unsigned short* smem) {
     unsigned* const flags = reinterpret_cast<unsigned*>(smem + RING_NBUF * STEP_ELEMS);     // ready[0..4] at +0, done[0..4] at +32 bytes
 
     const int tid = threadIdx.x;
@@ -548,6 +549,145 @@ __global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a
 #ifdef DAGL_ABLATION
     if ((VAR & 128) && a.times != nullptr && tid == 0) a.times[(size_t)(blockIdx.y * gridDim.x + blockIdx.x) * 4 + 3] = clk1 - clk0;
 #endif
+}
+
+template <int PASS, int WAVES, int VAR = 0, bool SMAX = false>
+__global__ __launch_bounds__(WAVES * 64, 1) void screen_ring_kernel(ScreenArgs a, int n_qgroups) {
+    if (a.gate != nullptr && *a.gate == 0) return;                 // (a re-run launch of a cold workspace that is not needed)
+    screen_policy<PASS>(a);
+    __shared__ __attribute__((aligned(16))) unsigned short smem[RING_SMEM_ELEMS];
+    screen_ring_block<PASS, WAVES, VAR, SMAX>(a, n_qgroups, smem);
+}
+
+// ---- sampling pass over the pivot keys, one step per block: pick, fetch and score in one launch -----------------------------
+// The sampling pass of a call that takes its threshold from the pivot keys (pivot.hip), where every block has ONE 64-row step of
+// the pivot matrix (pv_steps_per_split == 1: the benchmark's 256 x 256 and smaller maps).  There the ring has nothing to overlap,
+// and the pivot matrix is written by one launch only to be read back by the next.  Here the block of (query group, step s, image)
+// forms step s itself: the 32 key blocks v = s + steps * j behind it (pivot.hip's placement) are picked by its waves -- lane = key, row sums
+// requested together with the query fragments --, the 64 picked rows go from Xh straight into one LDS tile in the layout a
+// streamed step has (a missing pivot: a zero row), and the 13 x 2 multiplies, the group maxima and screen_finish are those of the
+// streaming kernels: gmax comes out bit for bit.  Two block barriers, no flag words, no word shared between blocks.  The blocks of
+// query group 0 also write pidx (dagl_ce_pivot_debug, CE.graph()).
+// A workspace whose policy word says "tight" takes the tile sampling as before: nobody reads the pivots, and the block runs
+// screen_ring_block (WAVES >= 12; the host does not send 8-wave blocks here under a policy word, see launch_pivot_sample).
+constexpr int PS_PICK_ELEMS = 2 * SK;              // the step's 64 picked keys (int) behind the tile
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64, 1) void pivot_sample_kernel(ScreenArgs a, int n_qgroups, PivotArgs pv) {
+    constexpr bool RING = WAVES >= 12;
+    constexpr int T = WAVES * 64;
+    __shared__ __attribute__((aligned(16))) unsigned short smem[RING ? RING_SMEM_ELEMS : STEP_ELEMS + PS_PICK_ELEMS];
+    static_assert(STEP_ELEMS + PS_PICK_ELEMS <= RING_SMEM_ELEMS, "tile + picks fit the ring's object");
+    if (a.policy != nullptr && *a.policy != 0) {     // the workspace is on the tight threshold: nobody reads the pivots
+        if constexpr (RING) { screen_policy<0>(a); screen_ring_block<0, WAVES>(a, n_qgroups, smem); }
+        return;
+    }
+    int* const picks = reinterpret_cast<int*>(smem + STEP_ELEMS);
+
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int i = lane & 31, h = lane >> 5;
+    const int b = blockIdx.y;
+    const int logical = xcd_remap2(blockIdx.x, gridDim.x);
+    const int split = logical / n_qgroups;           // = the block's pivot step
+    const int qg = logical % n_qgroups;
+    const bool has_step = split < pv.steps;          // (more key chunks than pivot steps: the chunks behind them sample nothing)
+
+    // the row sums of this wave's key blocks j = wave, wave + WAVES, .. < 32 of the step ...
+    constexpr int NJ = (32 + WAVES - 1) / WAVES;
+    float rs[NJ]; bool rv[NJ];
+#pragma unroll
+    for (int u = 0; u < NJ; ++u) {
+        const int j = wave + u * WAVES;
+        rs[u] = -__builtin_inff(); rv[u] = false;
+        if (has_step && j < 32) rs[u] = pivot_key_sum(pv, b, split + pv.steps * j, lane, rv[u]);
+    }
+    // ... and the lane's query (the same set-up as in the streaming kernels) in the same round trip
+    bf16x8 qf[KB];
+    const int q = (qg * WAVES + wave) * QT + i;
+    const bool qvalid = q < a.L;
+    const int qc = qvalid ? q : a.L - 1;
+    const size_t qlin = (size_t)b * a.L + qc;
+    load_query_fragments(a, b, q - i, qc, lane, qf);
+    const size_t seg = (qlin * a.splits + split) * 2 + h;
+
+    float gm[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) gm[r] = -1.0f;
+
+    if (has_step) {                                  // (block-uniform)
+#pragma unroll
+        for (int u = 0; u < NJ; ++u) {
+            const int j = wave + u * WAVES;
+            if (j < 32) {                            // (wave-uniform)
+                const int v = split + pv.steps * j;
+                int k0, k1;
+                pivot_pick2(rs[u], rv[u], v, lane, k0, k1);
+                if (lane < 2) {
+                    const int pk = lane ? k1 : k0;
+                    picks[2 * j + lane] = pk;        // rows 2 j, 2 j + 1 of the step
+                    if (qg == 0 && v < pv.n_blk) pv.pidx[((size_t)b * pv.n_blk + v) * 2 + lane] = pk;
+                }
+            }
+        }
+        __syncthreads();                             // every pick is in the LDS before any wave reads one
+        // the 64 rows x 27 16-byte columns: chunk c -> row c / 27, column c % 27, LDS byte 16 c (rows of DSH elements, as streamed)
+        constexpr int CHUNKS = SK * (DSH / 8);
+        constexpr int NC = (CHUNKS + T - 1) / T;
+        const unsigned short* xb = a.xh + (size_t)b * a.rows_xh * DSH;
+        uint4 row[NC];
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            const int c = tid + u * T;
+            row[u] = make_uint4(0u, 0u, 0u, 0u);
+            if (c < CHUNKS) {
+                const int pk = picks[c / (DSH / 8)];
+                if (pk >= 0) row[u] = reinterpret_cast<const uint4*>(xb + (size_t)pk * DSH)[c % (DSH / 8)];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < NC; ++u) {
+            const int c = tid + u * T;
+            if (c < CHUNKS) reinterpret_cast<uint4*>(smem)[c] = row[u];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < KB; ++t) asm volatile("" : "+v"(qf[t]));
+        // two 32-key row tiles, as in the streaming kernels' step
+        f32x16 acc[2];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
+        const unsigned short* kp0 = &smem[i * DSH + 8 * h];
+        const unsigned short* kp1 = kp0 + 32 * DSH;
+#pragma unroll
+        for (int t = 0; t < KB; ++t) {
+            const bf16x8 k0 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp0 + 16 * t));
+            const bf16x8 k1 = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(kp1 + 16 * t));
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k0, qf[t], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(k1, qf[t], acc[1], 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) gm[r] = fmaxf(fmaxf(gm[r], acc[0][r]), acc[1][r]);
+    }
+    screen_finish<0, false>(a, gm, qvalid, seg, nullptr, 0, -1.0f);
+}
+
+// (8-wave blocks have no tile-sampling form in this kernel: under a policy word they keep pivot_keys_kernel + launch_screen)
+bool pivot_sample_serves(const ScreenArgs& a) {
+    const int qblock = (a.qblock == 512 || a.qblock == 384) ? a.qblock : 256;
+    return a.xp != nullptr && a.pv_steps_per_split == 1 && (a.policy == nullptr || qblock != 256);
+}
+
+int launch_pivot_sample(hipStream_t s, const ScreenArgs& a, const PivotArgs& pv) {
+    if (!pivot_sample_serves(a) || a.gate != nullptr) { set_error("pivot_sample: not a call of this launch"); return DAGL_ERR_INVALID; }
+    const int qblock = (a.qblock == 512 || a.qblock == 384) ? a.qblock : 256;
+    const int n_qgroups = (a.L + qblock - 1) / qblock;
+    dim3 grid(n_qgroups * a.splits, a.B);
+    if (qblock == 512) hipLaunchKernelGGL((pivot_sample_kernel<16>), grid, dim3(1024), 0, s, a, n_qgroups, pv);
+    else if (qblock == 384) hipLaunchKernelGGL((pivot_sample_kernel<12>), grid, dim3(768), 0, s, a, n_qgroups, pv);
+    else hipLaunchKernelGGL((pivot_sample_kernel<8>), grid, dim3(512), 0, s, a, n_qgroups, pv);
+    DAGL_LAUNCH_CHECK("pivot_sample_kernel");
+    return DAGL_OK;
 }
 
 // theta of the adaptive modes: S~ >= theta  <=  (S~ (1+DELTA) - mean*thr) + bias > 0, with slack for the fp32
