@@ -93,6 +93,11 @@ SIGNATURES = {
     "dagl_graph_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),
     "dagl_graph_step": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 5
                         + [C.c_int64, _vp, _vp, _sz]),
+    "dagl_graph_search_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64] + [_i] * 6),
+    "dagl_graph_search": (_i, [_vp, _i, _i, _i] + [_vp] * 4 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 4
+                          + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
+    "dagl_graph_search_step": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 5
+                               + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
     "dagl_ces_stage_fold_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
     "dagl_ces_stage_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
     "dagl_graph_stage_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),

@@ -873,7 +873,7 @@ class CE(nn.Module):
         return out if b.dtype == torch.float32 else out.to(b.dtype)
 
     def refresh_graph(self, b: torch.Tensor, graph, *, radius: int = 1, margin=None, normalize: str = "reference",
-                      features: str = "fp32"):
+                      features: str = "fp32", propagate: bool = False, explore: int = 0, seed: int = 0):
         """``graph`` moved to the input ``b`` -> a new ``PatchGraph``: every query looks only at the keys in the
         ``(2 radius + 1)^2`` windows around its neighbours in ``graph`` (clipped at the map border; repeats count once), scores those
         candidates exactly and applies this module's selection rule to them (``ops.graph_refresh``, csrc/graph_refresh.hip) -- the
@@ -888,25 +888,43 @@ class CE(nn.Module):
         ``refresh_graph(x, graph(x))`` -- the result is ``graph(x)``.  ``weight`` is what ``attend_graph`` gives on the new structure,
         ``score`` the unscaled S; the result carries the module's ``mode`` and ``k`` and valid keys.
 
+        ``propagate`` / ``explore`` / ``seed`` (keyword-only, off by default: the call is then exactly the one above) add the two
+        candidate sources of ``ops.graph_search``: the neighbours of the four queries adjacent in the stride-4 query grid, shifted by
+        the query offset, and ``explore`` (0 .. 256) random keys per query from a stateless hash of (row, ``seed``).  With them a
+        graph can improve from call to call and find neighbours again that moved farther than ``radius`` -- selection on the
+        candidates stays exact, so the result is still the reference's mask restricted to the candidate set.  Further refusals, before
+        any launch: ``explore`` outside 0..256, and ``ops.graph_search_row_bound(largest degree, radius, propagate, explore)`` above
+        ``ops.graph_refresh_max_candidates()`` (``code == ERR_UNSUPPORTED``).
+
         Always under ``torch.no_grad()``: the result is a constant structure with constant weights; gradients are
         ``forward_on_graph``'s job on the result.  Refused before any launch: ``attend_graph``'s refusals (patch geometry, device,
         dtype, shape), a stream under capture (the edge count is read on the host), ``select_k < 1`` in the top-k modes, ``radius``
         outside 0..8, and a graph whose largest degree times ``(2 radius + 1)^2`` exceeds ``ops.graph_refresh_max_candidates()``.  The
         largest degree is read once per graph (kept on the object, as ``validate``'s verdict).  The module's state (packed weights,
         top-k policy, range verdicts, ``_train_dense``) is untouched: the call has a workspace of its own."""
-        radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "refresh_graph", radius, margin, normalize, features)
+        radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "refresh_graph", radius, margin, normalize, features,
+                                                                 propagate=propagate, explore=explore, seed=seed)
         B, _, H, W = b.shape
+        search = bool(propagate) or explore != 0
         with torch.no_grad():
             wq_rows, x_rows, tau, _b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
-            csr = ops.graph_refresh(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, radius=radius,
-                                    tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
-                                    normalize=normalize, max_row_edges=longest, workspace=self._ws_refresh, hw=(H, W))
+            kw = dict(radius=radius, tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
+                      normalize=normalize, max_row_edges=longest, hw=(H, W))
+            if search:
+                csr = ops.graph_search(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, workspace=self._ws_refresh,
+                                       propagate=bool(propagate), explore=explore, seed=seed, **kw)
+            else:
+                csr = ops.graph_refresh(wq_rows.contiguous(), x_rows.contiguous(), graph.row_off, graph.key, workspace=self._ws_refresh,
+                                        **kw)
             return self._refreshed(graph, csr, poisoned, k_eff)
 
-    def _refresh_arguments(self, b: torch.Tensor, graph, what: str, radius, margin, normalize: str, features: str, host_read: bool = True):
+    def _refresh_arguments(self, b: torch.Tensor, graph, what: str, radius, margin, normalize: str, features: str, host_read: bool = True,
+                           propagate=False, explore=0, seed=0):
         """The refusals ``refresh_graph`` and ``step_graph`` share, raised before any launch -> (radius, k_eff, margin, largest degree).
         ``host_read`` False (the step without its graph): the call itself reads nothing on the host, so a stream under capture is
-        served when what the checks read has been read before -- the graph validated, its largest degree known."""
+        served when what the checks read has been read before -- the graph validated, its largest degree known.
+        ``propagate`` / ``explore`` / ``seed``: the search keywords, with their own refusals."""
+        ops._graph_search_operands(f"CE.{what}", propagate, explore, seed)
         capturing = torch.cuda.is_current_stream_capturing()
         if capturing and host_read:
             raise DaglError(f"CE.{what}: not available while the stream is being captured (the edge count is read on the host)")
@@ -936,6 +954,12 @@ class CE(nn.Module):
                             f"{longest * (2 * radius + 1) ** 2} candidates, a row may expand into {cap}")
             err.code = ERR_UNSUPPORTED
             raise err
+        if (propagate or explore) and ops.graph_search_row_bound(longest, radius, propagate, explore) > cap:
+            err = DaglError(f"CE.{what}: with propagate={bool(propagate)} and explore={explore} a row of the graph (largest degree "
+                            f"{longest}, radius {radius}) may expand into (1 + 4 propagate) {longest} (2 radius + 1)^2 + explore = "
+                            f"{ops.graph_search_row_bound(longest, radius, propagate, explore)} candidates, more than {cap}")
+            err.code = ERR_UNSUPPORTED
+            raise err
         return radius, k_eff, margin, longest
 
     def _refreshed(self, graph, csr: dict, poisoned, k_eff: int):
@@ -946,7 +970,7 @@ class CE(nn.Module):
         return g
 
     def step_graph(self, b: torch.Tensor, graph, *, radius: int = 1, margin=None, normalize: str = "reference", features: str = "fp32",
-                   want_graph: bool = True):
+                   want_graph: bool = True, propagate: bool = False, explore: int = 0, seed: int = 0):
         """A sequence step in one call -> ``(out, PatchGraph | None)``: ``graph`` moved to the input ``b`` exactly as
         ``refresh_graph(b, graph, radius=..., margin=..., normalize=..., features=...)`` moves it (the same bits in every array, the same
         ``mode``, ``k`` and valid keys), and the block's output for ``b`` on that result, ``fold(A . V(theta(b))) / cnt`` with the new
@@ -963,24 +987,84 @@ class CE(nn.Module):
         its largest degree read (``graph.validate()``, ``graph.max_degree()``; ``CE.graph`` validates its result); otherwise it is refused
         under capture before any launch.  ``want_graph=True`` makes the one host read ``refresh_graph`` makes and is refused under capture.
 
+        ``propagate`` / ``explore`` / ``seed`` are ``refresh_graph``'s search keywords (``ops.graph_search_step``); off by default, the
+        call is then exactly the one above.  ``seed`` is a launch argument: a captured ``want_graph=False`` call replays the seed it
+        was captured with, every replay explores the same keys.
+
         Always under ``torch.no_grad()``, ``out.requires_grad`` is False: gradients are ``forward_on_graph``'s job on the returned graph.
         Arguments, selection, the ``features="split16"`` range contract (both results NaN-filled, never wrong numbers) and refusals are
         ``refresh_graph``'s, all raised before any launch.  The module's state (packed weights, top-k policy, range verdicts,
         ``_train_dense``) is untouched: the call has a workspace of its own."""
         want_graph = bool(want_graph)
         radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "step_graph", radius, margin, normalize, features,
-                                                                 host_read=want_graph)
+                                                                 host_read=want_graph, propagate=propagate, explore=explore, seed=seed)
         B, _, H, W = b.shape
+        search = bool(propagate) or explore != 0
         with torch.no_grad():
             wq_rows, x_rows, tau, b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
-            out, csr, _status = ops.graph_step(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
-                                               radius=radius, tau=tau.contiguous() if tau is not None else None, k=k_eff,
-                                               scale=float(self.softmax_scale), normalize=normalize, max_row_edges=longest,
-                                               want_graph=want_graph, workspace=self._ws_step, hw=(H, W))
+            kw = dict(radius=radius, tau=tau.contiguous() if tau is not None else None, k=k_eff, scale=float(self.softmax_scale),
+                      normalize=normalize, max_row_edges=longest, want_graph=want_graph, hw=(H, W))
+            if search:
+                out, csr, _status = ops.graph_search_step(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off,
+                                                          graph.key, workspace=self._ws_step, propagate=bool(propagate),
+                                                          explore=explore, seed=seed, **kw)
+            else:
+                out, csr, _status = ops.graph_step(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous(), graph.row_off, graph.key,
+                                                   workspace=self._ws_step, **kw)
             out = poisoned(out)
             if b.dtype != torch.float32:
                 out = out.to(b.dtype)
             return out, (self._refreshed(graph, csr, poisoned, k_eff) if want_graph else None)
+
+    def build_graph(self, b: torch.Tensor, *, iters: int = 4, radius: int = 1, explore: int = 8, seed: int = 0, features: str = "fp32",
+                    normalize: str = "reference"):
+        """A ``PatchGraph`` for ``b`` WITHOUT any scan of the L*N pairs: the search step iterated from a trivial start.  The initial
+        graph holds one edge per query, the key at the query patch's own position (the patch origin of ``synth.query_grid`` + 3, clamped
+        to the map); then ``iters`` times ``refresh_graph(b, g, radius=radius, propagate=True, explore=explore, seed=seed + i,
+        features=features, normalize=normalize)``, i = 0 .. iters - 1, on features computed once -- the last result is returned, bit for
+        bit what those public calls give, with the module's ``mode`` and ``k`` and valid keys.  Every iteration keeps the previous
+        keys among its candidates and selects exactly, so in the top-k modes a row's kept scores never get worse from one iteration
+        to the next; how close the result comes to ``graph(b)`` depends on the input (``tools/time_patch_graph.py --search`` prints the
+        recall per iteration).
+
+        Every ``select_mode``; the refusals are ``refresh_graph``'s, looked at again before every iteration: an adaptive mask that
+        grows until ``ops.graph_search_row_bound`` passes ``ops.graph_refresh_max_candidates()`` raises ``DaglError`` with
+        ``code == ERR_UNSUPPORTED`` -- a row is never truncated.  ``iters`` >= 1.  One host read per iteration; always under
+        ``torch.no_grad()``; the module's state is untouched."""
+        from .graph import PatchGraph
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise DaglError(f"CE.build_graph: iters={iters!r}, an int >= 1 expected")
+        ops._graph_search_operands("CE.build_graph", True, explore, seed)
+        if not isinstance(b, torch.Tensor) or b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.build_graph: expected [B,{self.in_channels},H,W], got {tuple(getattr(b, 'shape', ()))}")
+        if not b.is_cuda:
+            raise DaglError("CE.build_graph: input must be on the GPU; dagl_amd has no CPU path")
+        if torch.cuda.is_current_stream_capturing():
+            raise DaglError("CE.build_graph: not available while the stream is being captured (the edge count is read on the host)")
+        B, _, H, W = b.shape
+        Lh, Lw = ops.query_grid(H, W)
+        pt, _bo = same_pad_amounts(H, self.ksize, self.stride_1)
+        pl, _r = same_pad_amounts(W, self.ksize, self.stride_1)
+        with torch.no_grad():
+            dev = b.device
+            qy = (torch.arange(Lh, device=dev) * 4 - pt + 3).clamp_(0, H - 1)
+            qx = (torch.arange(Lw, device=dev) * 4 - pl + 3).clamp_(0, W - 1)
+            key = (qy.view(-1, 1) * W + qx.view(1, -1)).reshape(-1).repeat(B).to(torch.int32)
+            g = PatchGraph(torch.arange(B * Lh * Lw + 1, device=dev, dtype=torch.int64), key, torch.zeros(key.numel(), device=dev),
+                           None, B, H, W, self.select_mode if self.select_mode in ("adaptive", "topk", "adaptive_topk") else "adaptive", 0)
+            g._valid, g._max_degree = True, 1
+            feats = None
+            for i in range(iters):
+                r, k_eff, margin, longest = self._refresh_arguments(b, g, "build_graph", radius, None, normalize, features,
+                                                                    propagate=True, explore=explore, seed=seed + i)
+                if feats is None:
+                    wq_rows, x_rows, tau, _b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
+                    feats = (wq_rows.contiguous(), x_rows.contiguous(), tau.contiguous() if tau is not None else None)
+                csr = ops.graph_search(feats[0], feats[1], g.row_off, g.key, radius=r, tau=feats[2], k=k_eff,
+                                       scale=float(self.softmax_scale), normalize=normalize, max_row_edges=longest,
+                                       workspace=self._ws_refresh, hw=(H, W), propagate=True, explore=explore, seed=seed + i)
+                g = self._refreshed(g, csr, poisoned, k_eff)
+            return g
 
     def forward_with_graph(self, b: torch.Tensor, *, scores: bool = False, features=None):
         """The block's output for ``b`` AND the patch graph that produced it, from one call -> ``(out, PatchGraph)``: the list-form route

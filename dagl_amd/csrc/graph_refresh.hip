@@ -29,6 +29,18 @@
 // graph_step_rows_kernel launched once per head on its slice (launch_graph_stage_step), one scan, one copy, and
 // launch_stage_fold_mix (aggregate.hip) in the place of the fold: out = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x.
 //
+// The search entries, dagl_graph_search / dagl_graph_search_step, are the first two with the other two candidate sources of that
+// algorithm (rf_row's SEARCH flavour, kernels of their own: the instantiations above keep their arguments and their device code):
+//   propagate    the windows around (y - 4 dqy, x - 4 dqx) for every edge (y, x) of the query at (qy + dqy, qx + dqx), (dqy, dqx) in
+//                {(0, -1), (0, 1), (-1, 0), (1, 0)}, inside the Lh x Lw query grid of the same image -- never across a grid-row end or an
+//                image boundary --, clipped cell by cell; the adjacent rows come from the INPUT graph (Jacobi: no scheduling dependence)
+//   explore = m  m keys ((uint64) h_t N) >> 32, h_t = lowbias32(lowbias32(row ^ seed) + t): a counter hash, no state, no window
+// so a graph can improve from step to step, recover from drift and be built from a trivial start without an L N scan.  Everything
+// after the expansion is the same code, a pair's score has the same bits.  A row runs when it has any raw candidate; it comes out
+// empty when its own or an adjacent row's degree exceeds max_row_edges (counted once).  A row can keep more than deg (2 radius + 1)^2
+// entries now, so the flavour stages at r k under a rank cut and else at the prefix sum of the rows' bounds (rs_region_start: from
+// row_off alone, no scan), and graph_search_compact_kernel copies from there.  Both sources off: the plain launches.
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -43,6 +55,7 @@ constexpr int RF_WAVE_CAP = 128;              // up to here a row is a wavefront
 constexpr int RF_MAX_RADIUS = 8;
 constexpr int RF_EMPTY = 0x7fffffff;          // sorts behind every key
 constexpr int RF_COPY_ROWS = 4;               // rows (wavefronts) per block of the compaction
+constexpr int RS_MAX_EXPLORE = 256;           // random keys a row of the SEARCH flavour may ask for
 
 struct RfArgs {
     int W, H, radius, max_row_edges, k, keep_all;
@@ -50,6 +63,44 @@ struct RfArgs {
     int32_t* st_key; float* st_score; float* st_weight;     // [E (2 radius + 1)^2] staging
     unsigned long long* status;               // [2]: rows longer than max_row_edges, largest number of distinct candidates of a row
 };
+
+// what the SEARCH flavour of the row body adds (dagl_graph_search*): a struct of its own, so that the kernels above it keep their arguments
+struct RsArgs {
+    int propagate, explore;                   // the adjacent queries' edges as candidate sources (0 / 1); random keys per row (0 .. 256)
+    unsigned seed;
+    int Lw;                                   // queries per grid row (a.L / Lw grid rows per image)
+    int k_region;                             // > 0: row r stages at r k_region (it keeps at most k);  0: at rs_region_start's prefix sum
+    long long staged;                         // entries of each staging array
+};
+
+// lowbias32: the counter hash of the random candidates
+__device__ __forceinline__ unsigned rs_hash(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+// the offset of row r (r clamped to [0, n_rows]), clamped to [0, E]
+__device__ __forceinline__ long long rs_off(const int64_t* __restrict__ row_off, int n_rows, long long E, long long r) {
+    return gt_clamp(row_off[r < 0 ? 0 : (r > n_rows ? n_rows : r)], E);
+}
+
+// where row r of the SEARCH flavour stages, from row_off alone (no scan, no host read).  k_region = 0: the prefix sum over the rows
+// before r of the bound  w2 (deg_r + the degrees of rows r - 1, r + 1, r - Lw, r + Lw) + explore  -- rows r + s that lie outside
+// [0, n_rows) count 0, rows that are no grid neighbour (a grid-row end, an image boundary) are counted though never read: the sum of
+// the regions is <= (5 E w2 + explore n_rows), what the entry allocates.  (With offsets that do not ascend the result is not a
+// partition; rf_row tests its region against `staged` before it writes.)
+__device__ __forceinline__ long long rs_region_start(const int64_t* __restrict__ row_off, int n_rows, long long E, int w2, const RsArgs& sr,
+                                                     int row) {
+    if (sr.k_region > 0) return (long long)row * sr.k_region;
+    long long v = rs_off(row_off, n_rows, E, row);
+    if (sr.propagate) {
+        v += rs_off(row_off, n_rows, E, (long long)row - 1) - rs_off(row_off, n_rows, E, -1);
+        v += rs_off(row_off, n_rows, E, (long long)row + 1) - rs_off(row_off, n_rows, E, 1);
+        v += rs_off(row_off, n_rows, E, (long long)row - sr.Lw) - rs_off(row_off, n_rows, E, -sr.Lw);
+        v += rs_off(row_off, n_rows, E, (long long)row + sr.Lw) - rs_off(row_off, n_rows, E, sr.Lw);
+    }
+    return v * w2 + (long long)sr.explore * row;
+}
 
 // a float as an unsigned that orders the same way: -0 = +0, NaN below everything (a strict total order with the key as tie-break: a rank
 // cut keeps exactly min(k, passing) entries whatever the scores hold).  (Not in graph_rows.h: no other graph route ranks.)
@@ -117,10 +168,16 @@ __device__ __forceinline__ void rf_zero_row(float* agg, int row) {
     for (int c = threadIdx.x; c < GA_C4; c += T) o[c] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-// the row body of both kernels below.  AGG (dagl_graph_step): the row's weighted sum of value patches goes to v.out [B L, 784] as well,
-// and the graph outputs may be absent (f.st_key null: no degree, no staging writes)
-template <int T, int CAP, bool AGG>
-__device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v) {
+// the row body of the kernels below.  AGG (dagl_graph_step): the row's weighted sum of value patches goes to v.out [B L, 784] as well,
+// and the graph outputs may be absent (f.st_key null: no degree, no staging writes).  SEARCH (dagl_graph_search*): step 1 takes the
+// row's candidates from up to three sources -- (a) the windows around its own edges, as without SEARCH; (b) sr.propagate: the windows
+// around (y - 4 dqy, x - 4 dqx) for every edge (y, x) of the query at (qy + dqy, qx + dqx), (dqy, dqx) in {(0, -1), (0, 1), (-1, 0),
+// (1, 0)}, where that query lies in the Lh x Lw grid of the same image (the adjacent rows are read from the INPUT graph: Jacobi, no
+// dependence on scheduling; the centre may lie off the map, the window is clipped cell by cell); (c) sr.explore keys
+// (lowbias32(lowbias32(row ^ seed) + t) N) >> 32 of the row's image, no window -- and the row stages at rs_region_start; every step
+// after the expansion is the same code
+template <int T, int CAP, bool AGG, bool SEARCH = false>
+__device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v, const RsArgs& sr = RsArgs{}) {
     __shared__ long long s_of[CAP];           // two int arrays (below); AGG: at the end the float4 offset of each kept entry's value patch
                                               // in the map, compacted -- no array of its own: at 2048 candidates 16 KiB more LDS halve the
                                               // blocks per CU, and the row body lives on them
@@ -137,7 +194,52 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     const long long lo = gt_clamp(a.row_off[row], a.E), hi = gt_clamp(a.row_off[row + 1], a.E);
     const long long deg_in = hi - lo;
     const int wd = 2 * f.radius + 1, w2 = wd * wd;
-    if (deg_in <= 0 || deg_in > f.max_row_edges || deg_in * w2 > CAP) {          // (the same in every thread)
+    // SEARCH: the sources' first edges and the running sums of their degrees (0 the row itself, 1-4 the adjacent queries; a source that
+    // does not exist holds no edge), the raw candidate count and the row's staging region
+    long long src_lo[5] = {lo, 0, 0, 0, 0}, stage_at = 0;
+    int src_end[5] = {0, 0, 0, 0, 0}, raw_n = 0;
+    if (SEARCH) {
+        const int q = row % a.L, qy = q / sr.Lw, qx = q - qy * sr.Lw, Lh = a.L / sr.Lw;
+        long long dg[5] = {deg_in > 0 ? deg_in : 0, 0, 0, 0, 0};
+        if (sr.propagate) {
+#pragma unroll
+            for (int s = 1; s < 5; ++s) {
+                const int dqy = s == 3 ? -1 : (s == 4 ? 1 : 0), dqx = s == 1 ? -1 : (s == 2 ? 1 : 0);
+                if ((unsigned)(qy + dqy) < (unsigned)Lh && (unsigned)(qx + dqx) < (unsigned)sr.Lw) {
+                    const int r2 = row + dqy * sr.Lw + dqx;                      // (the same image: in [0, n_rows))
+                    src_lo[s] = gt_clamp(a.row_off[r2], a.E);
+                    const long long d = gt_clamp(a.row_off[r2 + 1], a.E) - src_lo[s];
+                    dg[s] = d > 0 ? d : 0;
+                }
+            }
+        }
+        bool overlong = false;
+        long long sum = 0;
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            overlong |= dg[s] > f.max_row_edges;
+            sum += dg[s];
+        }
+        const long long raw_ll = overlong ? 0 : sum * w2 + sr.explore;           // (<= 5 max_row_edges w2 + 256: no overflow)
+        stage_at = graph_out ? rs_region_start(a.row_off, a.n_rows, a.E, w2, sr, row) : 0;
+        const long long region = sr.k_region > 0 ? sr.k_region : raw_ll;
+        const bool room = !graph_out || (stage_at >= 0 && stage_at + region <= sr.staged);
+        if (overlong || raw_ll <= 0 || raw_ll > CAP || !room) {                  // (the same in every thread)
+            if (t == 0) {
+                if (graph_out) f.deg[row] = 0;
+                if (overlong || raw_ll > CAP) atomicAdd(f.status, 1ull);
+            }
+            if (AGG) rf_zero_row<T>(v.out, row);
+            return;
+        }
+        raw_n = (int)raw_ll;
+        int run = 0;
+#pragma unroll
+        for (int s = 0; s < 5; ++s) {
+            run += (int)dg[s];
+            src_end[s] = run;
+        }
+    } else if (deg_in <= 0 || deg_in > f.max_row_edges || deg_in * w2 > CAP) {   // (the same in every thread)
         if (t == 0) {
             if (graph_out) f.deg[row] = 0;
             if (deg_in > 0) atomicAdd(f.status, 1ull);
@@ -146,21 +248,52 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
         return;
     }
     // 1. expand: entry idx = (edge, window offset); what falls off the map or comes from a key off the map sorts to the end
-    const int raw = (int)deg_in * w2;
+    const int raw = SEARCH ? raw_n : (int)deg_in * w2;
     int n_pad = 64;
     while (n_pad < raw) n_pad <<= 1;                                              // <= CAP: CAP is a power of two >= raw
-    for (int idx = t; idx < n_pad; idx += T) {
-        int c = RF_EMPTY;
-        if (idx < raw) {
-            const int e = idx / w2, o = idx - e * w2;
-            const int key = a.key[lo + e];
-            if ((unsigned)key < (unsigned)a.N) {
-                const int oy = o / wd;
-                const int y = key / f.W + oy - f.radius, x = key % f.W + (o - oy * wd) - f.radius;
-                if ((unsigned)y < (unsigned)f.H && (unsigned)x < (unsigned)f.W) c = y * f.W + x;
+    if (SEARCH) {
+        const int windowed = src_end[4] * w2;                                     // entries (edge of a source, window offset); then the random keys
+        const unsigned h0 = rs_hash((unsigned)row ^ sr.seed);
+        for (int idx = t; idx < n_pad; idx += T) {
+            int c = RF_EMPTY;
+            if (idx < windowed) {
+                const int e = idx / w2, o = idx - e * w2;
+                long long at = src_lo[0] + e;
+                int sy = 0, sx = 0;                                               // the shift of the source's keys: 4 (dqy, dqx)
+#pragma unroll
+                for (int s = 1; s < 5; ++s) {
+                    if (e >= src_end[s - 1]) {
+                        at = src_lo[s] + (e - src_end[s - 1]);
+                        sy = s == 3 ? -QS : (s == 4 ? QS : 0);
+                        sx = s == 1 ? -QS : (s == 2 ? QS : 0);
+                    }
+                }
+                const int key = a.key[at];
+                if ((unsigned)key < (unsigned)a.N) {
+                    const int oy = o / wd;
+                    const int y = key / f.W - sy + oy - f.radius, x = key % f.W - sx + (o - oy * wd) - f.radius;
+                    if ((unsigned)y < (unsigned)f.H && (unsigned)x < (unsigned)f.W) c = y * f.W + x;
+                }
+            } else if (idx < raw) {
+                const unsigned h = rs_hash(h0 + (unsigned)(idx - windowed));
+                c = (int)(((unsigned long long)h * (unsigned long long)(unsigned)a.N) >> 32);      // < N
             }
+            s_sort[idx] = c;
         }
-        s_sort[idx] = c;
+    } else {
+        for (int idx = t; idx < n_pad; idx += T) {
+            int c = RF_EMPTY;
+            if (idx < raw) {
+                const int e = idx / w2, o = idx - e * w2;
+                const int key = a.key[lo + e];
+                if ((unsigned)key < (unsigned)a.N) {
+                    const int oy = o / wd;
+                    const int y = key / f.W + oy - f.radius, x = key % f.W + (o - oy * wd) - f.radius;
+                    if ((unsigned)y < (unsigned)f.H && (unsigned)x < (unsigned)f.W) c = y * f.W + x;
+                }
+            }
+            s_sort[idx] = c;
+        }
     }
     __syncthreads();
     // 2. bitonic sort, ascending
@@ -258,8 +391,9 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     }
     sum = rf_sum<T>(sum, sh_d);
     if (off_graph) sum += (double)(a.N - kept) * exp(-(double)M);
-    // 7. the kept entries, ascending keys, to the front of the row's staging region (kept <= n <= raw = its size)
-    const long long base = lo * w2;
+    // 7. the kept entries, ascending keys, to the front of the row's staging region (kept <= n <= raw = its size; SEARCH with a rank
+    //    cut: kept <= k = its size)
+    const long long base = SEARCH ? stage_at : lo * w2;
     //    AGG: a thread also keeps the weight and the patch offset of its kept entries (at most PER = CAP / T >= pr of them) in registers
     constexpr int PER = CAP / T;
     float my_w[AGG ? PER : 1];
@@ -318,6 +452,42 @@ __global__ __launch_bounds__(T) void graph_step_rows_kernel(GtArgs a, RfArgs f, 
     rf_row<T, CAP, true>(a, f, v);
 }
 
+// dagl_graph_search's and dagl_graph_search_step's: the same two bodies with the SEARCH candidate sources (kernels of their own: the
+// four above keep their arguments and their device code)
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_search_rows_kernel(GtArgs a, RfArgs f, RsArgs sr) {
+    rf_row<T, CAP, false, true>(a, f, GaArgs{}, sr);
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_search_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr) {
+    rf_row<T, CAP, true, true>(a, f, v, sr);
+}
+
+// graph_refresh_compact_kernel (below) for the SEARCH flavour: a row's staged entries start at rs_region_start.  deg[row] > 0 only where
+// rf_row found the whole region inside the staging arrays
+__global__ __launch_bounds__(RF_COPY_ROWS * 64) void graph_search_compact_kernel(int n_rows, int w2, long long E, RsArgs sr,
+                                                                                 const int64_t* __restrict__ row_off,
+                                                                                 const int32_t* __restrict__ deg,
+                                                                                 const int64_t* __restrict__ row_off_out,
+                                                                                 const int32_t* __restrict__ st_key, const float* __restrict__ st_score,
+                                                                                 const float* __restrict__ st_weight, int32_t* __restrict__ key,
+                                                                                 float* __restrict__ weight, float* __restrict__ score,
+                                                                                 long long capacity) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * RF_COPY_ROWS + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const long long src = rs_region_start(row_off, n_rows, E, w2, sr, row), dst = row_off_out[row];
+    const int n = deg[row];
+    if (n <= 0 || src < 0 || src + n > sr.staged) return;
+    for (int i = lane; i < n; i += 64) {
+        if (dst + i >= capacity) break;                          // (offsets that overlap: more staged than the caller's bound)
+        key[dst + i] = st_key[src + i];
+        score[dst + i] = st_score[src + i];
+        weight[dst + i] = st_weight[src + i];
+    }
+}
+
 // a wavefront per row: its staged entries to their place in the output
 __global__ __launch_bounds__(RF_COPY_ROWS * 64) void graph_refresh_compact_kernel(int n_rows, int w2, long long E, const int64_t* __restrict__ row_off,
                                                                                   const int32_t* __restrict__ deg,
@@ -357,16 +527,52 @@ static RefreshWs refresh_carve(void* ws, size_t n_rows, size_t staged, bool agg 
 }
 
 // b2p / out: the step's value map and output, both null for the refresh;  row_off_out null (the step alone): no graph comes out
+// search: the SEARCH flavour (dagl_graph_search*: propagate or explore set) with its candidate sources and its staging layout
 struct RefreshCall {
     GraphAttendCall c; int max_row_edges, radius, k; bool keep_all, block_rows;
     int64_t* row_off_out; int32_t* key_out; float* weight_out; float* score_out; int64_t capacity; int64_t* status;
     const float* b2p; float* out;
+    bool search; int propagate, explore; uint32_t seed;
 };
+
+// the candidates a row may expand into, before the repeats are dropped: its own edges' windows; SEARCH: the four adjacent rows' too, and
+// the random keys
+static long long rf_row_bound(int max_row_edges, int radius, int propagate, int explore) {
+    const long long wd = 2 * radius + 1;
+    return (long long)(1 + 4 * propagate) * max_row_edges * wd * wd + explore;
+}
+
+// the entries of each staging array and the most edges a call may produce.  Without SEARCH: E w2.  SEARCH: a region of k per row
+// under a rank cut, else rs_region_start's prefix sums
+static int64_t rf_staged(int64_t n_rows, int64_t E, int radius, int propagate, int explore, int k_region) {
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    if (!propagate && !explore) return E * w2;
+    return k_region > 0 ? n_rows * k_region : (1 + 4 * propagate) * E * w2 + explore * n_rows;
+}
 
 // short rows (top-k 8 at radius 1: 72 candidates) take a wavefront each, longer ones a block of four
 static bool rf_wave_rows(const RefreshCall& r) {
-    const long long wd = 2 * r.radius + 1;
-    return !r.block_rows && (long long)r.max_row_edges * wd * wd <= RF_WAVE_CAP;
+    return !r.block_rows && rf_row_bound(r.max_row_edges, r.radius, r.search ? r.propagate : 0, r.search ? r.explore : 0) <= RF_WAVE_CAP;
+}
+
+// the SEARCH flavour's row kernel, with or without the aggregation epilogue (v null), in either form
+static int launch_search_rows(hipStream_t s, int n_rows, bool wave, const GtArgs& a, const RfArgs& f, const GaArgs* v, const RsArgs& sr) {
+    if (v) {
+        if (wave) {
+            hipLaunchKernelGGL((graph_search_step_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, *v, sr);
+        } else {
+            hipLaunchKernelGGL((graph_search_step_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, *v, sr);
+        }
+        DAGL_LAUNCH_CHECK("graph_search_step_rows_kernel");
+    } else {
+        if (wave) {
+            hipLaunchKernelGGL((graph_search_rows_kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, sr);
+        } else {
+            hipLaunchKernelGGL((graph_search_rows_kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, sr);
+        }
+        DAGL_LAUNCH_CHECK("graph_search_rows_kernel");
+    }
+    return DAGL_OK;
 }
 
 // the step's row kernel over n_rows rows: a block per row of a.row_off, in either form
@@ -384,19 +590,28 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
     const int n_rows = B * g.L, wd = 2 * r.radius + 1, w2 = wd * wd;
     const bool agg = r.out != nullptr, graph = r.row_off_out != nullptr;
     DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
-    if (r.c.E == 0) {
+    if (r.c.E == 0 && !(r.search && r.explore > 0)) {            // (random keys populate an empty graph)
         if (graph) DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
         if (agg) DAGL_HIP_TRY(hipMemsetAsync(r.out, 0, (size_t)B * CH * g.N * sizeof(float), s));      // fold(0) / cnt
         return DAGL_OK;
     }
-    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)r.c.E * w2, agg, graph);
+    const int k_region = r.keep_all ? 0 : r.k;
+    const int64_t staged = rf_staged(n_rows, r.c.E, r.radius, r.search ? r.propagate : 0, r.search ? r.explore : 0, k_region);
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)staged, agg, graph);
     const GtArgs a = gt_args(B, g, r.c);
     RfArgs f{};
     f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
     f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
     f.status = reinterpret_cast<unsigned long long*>(r.status);
     const bool wave = rf_wave_rows(r);
-    if (agg) {
+    RsArgs sr{};
+    sr.propagate = r.propagate; sr.explore = r.explore; sr.seed = r.seed; sr.Lw = g.Lw; sr.k_region = k_region; sr.staged = staged;
+    if (r.search) {
+        GaArgs v = ga_map_args(B, g, r.b2p, nullptr, nullptr, nullptr, 0);
+        v.out = w.agg;
+        const int rc = launch_search_rows(s, n_rows, wave, a, f, agg ? &v : nullptr, sr);
+        if (rc) return rc;
+    } else if (agg) {
         GaArgs v = ga_map_args(B, g, r.b2p, nullptr, nullptr, nullptr, 0);
         v.out = w.agg;
         const int rc = launch_step_rows(s, n_rows, wave, a, f, v);
@@ -412,10 +627,18 @@ static int launch_graph_refresh(hipStream_t s, int B, const Grid& g, const Refre
     if (graph) {
         const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
         if (rc) return rc;
-        hipLaunchKernelGGL(graph_refresh_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0,
-                           s, n_rows, w2, (long long)r.c.E, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out,
-                           r.weight_out, r.score_out, (long long)r.capacity);
-        DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
+        const dim3 copy_grid((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS));
+        if (r.search) {
+            hipLaunchKernelGGL(graph_search_compact_kernel, copy_grid, dim3(RF_COPY_ROWS * 64), 0, s, n_rows, w2, (long long)r.c.E, sr,
+                               r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out, r.weight_out, r.score_out,
+                               (long long)r.capacity);
+            DAGL_LAUNCH_CHECK("graph_search_compact_kernel");
+        } else {
+            hipLaunchKernelGGL(graph_refresh_compact_kernel, copy_grid, dim3(RF_COPY_ROWS * 64), 0, s, n_rows, w2, (long long)r.c.E,
+                               r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight, r.key_out, r.weight_out, r.score_out,
+                               (long long)r.capacity);
+            DAGL_LAUNCH_CHECK("graph_refresh_compact_kernel");
+        }
     }
     return agg ? launch_fold(s, B, g, w.agg, r.out) : DAGL_OK;
 }
@@ -475,17 +698,26 @@ static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_
     return DAGL_OK;
 }
 
-// the checks and the call of both entries.  b2p / out null: the refresh.  Else the step, where the four graph outputs may all be null
+// what the SEARCH entries add to the refusals (both 0: the plain refresh)
+static int search_args_ok(const char* who, int propagate, int explore) {
+    DAGL_REQUIRE(propagate == 0 || propagate == 1, "%s: propagate=%d, expected 0 or 1", who, propagate);
+    DAGL_REQUIRE(explore >= 0 && explore <= RS_MAX_EXPLORE, "%s: explore=%d outside [0, %d]", who, explore, RS_MAX_EXPLORE);
+    return DAGL_OK;
+}
+
+// the checks and the call of the refresh, step and search entries.  b2p / out null: the refresh.  Else the step, where the four graph outputs may all be null
 // (the output alone: capacity_edges is not looked at)
 static int graph_refresh_entry(const char* who, void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
                                const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
                                const float* tau, int k, float scale, int flags, float* out, int64_t* row_off_out, int32_t* key_out,
                                float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
-                               size_t ws_bytes, bool step) {
+                               size_t ws_bytes, bool step, int propagate = 0, int explore = 0, uint32_t seed = 0) {
     int rc = refresh_shape_ok(who, B, H, W, total_edges, radius);
     if (rc) return rc;
+    if ((rc = search_args_ok(who, propagate, explore))) return rc;
+    const bool search = propagate || explore;
     const bool graph = !step || row_off_out || key_out || weight_out || score_out;
-    const bool outputs = status_out && (!graph || (row_off_out && (total_edges == 0 || (key_out && weight_out && score_out))));
+    const bool outputs = status_out && (!graph || (row_off_out && ((total_edges == 0 && !explore) || (key_out && weight_out && score_out))));
     if ((rc = graph_operands_ok(who, wq_rows, x_rows, row_off, key, total_edges, scale, flags, outputs,
                                 DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
         return rc;
@@ -501,15 +733,24 @@ static int graph_refresh_entry(const char* who, void* stream, int B, int H, int 
                   (long long)((int64_t)max_row_edges * w2), RF_CAP);
         return DAGL_ERR_UNSUPPORTED;
     }
+    if (search && rf_row_bound(max_row_edges, radius, propagate, explore) > RF_CAP) {
+        set_error("%s: (1 + 4 propagate) max_row_edges (2 radius + 1)^2 + explore = %lld candidates per row, more than the %d a row may "
+                  "expand into", who, rf_row_bound(max_row_edges, radius, propagate, explore), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
     const Grid g = make_grid(H, W);
     const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
-    int64_t may = total_edges * w2;
+    // what the call may produce: the raw bound, or B L k under a rank cut where that is smaller; SEARCH without a rank cut: the
+    // staging bound (the same number)
+    int64_t may = rf_staged((int64_t)B * g.L, total_edges, radius, propagate, explore, 0);
     if (!keep_all && k > 0 && (int64_t)B * g.L * k < may) may = (int64_t)B * g.L * k;
     if (graph && capacity_edges < may) {
         set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
         return DAGL_ERR_WORKSPACE;
     }
-    const size_t need = refresh_carve(nullptr, (size_t)B * g.L, (size_t)(total_edges * w2), step, graph).bytes;
+    const size_t need = refresh_carve(nullptr, (size_t)B * g.L,
+                                      (size_t)rf_staged((int64_t)B * g.L, total_edges, radius, propagate, explore, keep_all ? 0 : k), step,
+                                      graph).bytes;
     if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
     RefreshCall r{};
     r.c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
@@ -517,6 +758,7 @@ static int graph_refresh_entry(const char* who, void* stream, int B, int H, int 
     r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
     r.row_off_out = graph ? row_off_out : nullptr; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out;
     r.capacity = capacity_edges; r.status = status_out; r.b2p = b2p; r.out = out;
+    r.search = search; r.propagate = propagate; r.explore = explore; r.seed = seed;
     return launch_graph_refresh((hipStream_t)stream, B, g, r, workspace);
 }
 
@@ -569,6 +811,37 @@ int dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, con
     return graph_refresh_entry("dagl_graph_step", stream, B, H, W, wq_rows, x_rows, b2p, row_off, key, total_edges, max_row_edges, radius,
                                tau, k, scale, flags, out, row_off_out, key_out, weight_out, score_out, capacity_edges, status_out,
                                workspace, ws_bytes, true);
+}
+
+// the search step on a patch graph: the refresh / the step with the adjacent queries' edges and random keys as further candidate
+// sources (no ABI bump: found by symbol).  propagate = explore = 0: the plain entries' launches, workspace and bits
+size_t dagl_graph_search_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int propagate, int explore, int k,
+                                         int want_graph, int aggregate) {
+    const char* who = "dagl_graph_search_workspace_bytes";
+    if (refresh_shape_ok(who, B, H, W, total_edges, radius) || search_args_ok(who, propagate, explore)) return 0;
+    if (k < 0) { set_error("%s: k=%d < 0", who, k); return 0; }
+    const int64_t n_rows = (int64_t)B * make_grid(H, W).L;
+    return refresh_carve(nullptr, (size_t)n_rows, (size_t)rf_staged(n_rows, total_edges, radius, propagate, explore, k), aggregate != 0,
+                         want_graph != 0 || aggregate == 0).bytes;
+}
+
+int dagl_graph_search(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                      const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau, int k, float scale,
+                      int flags, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges,
+                      int64_t* status_out, void* workspace, size_t ws_bytes, int propagate, int explore, uint32_t seed) {
+    return graph_refresh_entry("dagl_graph_search", stream, B, H, W, wq_rows, x_rows, nullptr, row_off, key, total_edges, max_row_edges,
+                               radius, tau, k, scale, flags, nullptr, row_off_out, key_out, weight_out, score_out, capacity_edges,
+                               status_out, workspace, ws_bytes, false, propagate, explore, seed);
+}
+
+int dagl_graph_search_step(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                           const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                           const float* tau, int k, float scale, int flags, float* out, int64_t* row_off_out, int32_t* key_out,
+                           float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
+                           size_t ws_bytes, int propagate, int explore, uint32_t seed) {
+    return graph_refresh_entry("dagl_graph_search_step", stream, B, H, W, wq_rows, x_rows, b2p, row_off, key, total_edges, max_row_edges,
+                               radius, tau, k, scale, flags, out, row_off_out, key_out, weight_out, score_out, capacity_edges, status_out,
+                               workspace, ws_bytes, true, propagate, explore, seed);
 }
 
 // the fold + 1x1 mix + residual of a CES stage from its four heads' aggregated rows, on its own (no ABI bump: found by symbol)

@@ -170,7 +170,8 @@ class CES(nn.Module):
             and x.is_cuda and x.dtype == torch.float32 and mix.weight.dtype == torch.float32
 
     @torch.no_grad()
-    def step_graphs(self, x, state, *, radius: int = 1, features: str = "fp32", want_graphs: bool = True, fused=None):
+    def step_graphs(self, x, state, *, radius: int = 1, features: str = "fp32", want_graphs: bool = True, fused=None,
+                    propagate: bool = False, explore: int = 0, seed: int = 0):
         """A sequence step of the whole module -> ``(out, SequenceState | None)``: per stage the stage's graphs are moved to the stage's
         input exactly as each head's ``CE.refresh_graph`` moves its own, and the stage's output is ``mix(cat(step outputs)) + input`` with
         each head's step output ``CE.step_graph``'s; ``RBS1`` / ``RBS2`` run between the stages as in ``forward``.  For a sequence:
@@ -189,12 +190,24 @@ class CES(nn.Module):
         head by head) and is refused under capture.  With ``features="split16"`` a head whose operands leave the split-fp16 range
         NaN-fills ``out`` and that head's rows of the new graph, never wrong numbers.
 
+        ``propagate`` / ``explore`` / ``seed``: ``CE.step_graph``'s search keywords, handed to every head (off by default: the call is
+        then exactly the one above).  The stage-fused launch has no search flavour: with any of them set ``fused=None`` runs head by
+        head and ``fused=True`` is refused, before any launch.
+
         Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
         the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
         does not fit the input -- is raised before any launch of the call."""
         from ._lib import DaglError
+        from . import ops
         from .sequence import SequenceState
         what = "CES.step_graphs"
+        search = dict(propagate=propagate, explore=explore, seed=seed)
+        ops._graph_search_operands(what, propagate, explore, seed)
+        if bool(propagate) or explore != 0:
+            if fused:
+                raise DaglError(f"{what}: fused=True with propagate / explore set: the stage-fused step (ops.graph_stage_step) has no "
+                                "search flavour; leave fused at None (head by head) or pass fused=False")
+            fused = False
         if not isinstance(state, SequenceState):
             raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
@@ -204,10 +217,10 @@ class CES(nn.Module):
         if (state.stages[0].B, state.stages[0].H, state.stages[0].W) != (4 * B, x.shape[2], x.shape[3]):
             g0 = state.stages[0]
             raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={B} H={x.shape[2]} W={x.shape[3]}")
-        plan = self._plan_step(x, state, radius, features, want_graphs, fused)
+        plan = self._plan_step(x, state, radius, features, want_graphs, fused, search)
         out, new = x, []
         for s in (1, 2, 3):
-            out, g = self._step_stage(s, out, state, plan[s], features, want_graphs)
+            out, g = self._step_stage(s, out, state, plan[s], features, want_graphs, search)
             new.append(g)
             out = self._between_stages(s, out)
         return out, (SequenceState(new) if want_graphs else None)
@@ -247,7 +260,7 @@ class CES(nn.Module):
             out = self._between_stages(s, mix(torch.cat(outs, dim=1)) + out)
         return out
 
-    def _plan_step(self, x, state, radius, features, want_graphs, fused):
+    def _plan_step(self, x, state, radius, features, want_graphs, fused, search=None):
         """Every refusal of ``step_graphs`` that depends on a stage, raised before the first launch -- every stage sees an input of x's
         shape, dtype and device -- -> {stage: (fused?, what ``CE._refresh_arguments`` returns for its heads)}."""
         from ._lib import DaglError
@@ -277,11 +290,11 @@ class CES(nn.Module):
                         raise DaglError(f"{what}: head by head under capture needs state.head({s - 1}, {h}) taken before the capture "
                                         "(it reads two offsets on the host)")
                     g = state.head(s - 1, h)
-                args = hd._refresh_arguments(x, g, "step_graph", radius, None, "reference", features, host_read=want_graphs)
+                args = hd._refresh_arguments(x, g, "step_graph", radius, None, "reference", features, host_read=want_graphs, **(search or {}))
             plan[s] = (use, args)
         return plan
 
-    def _step_stage(self, s, x, state, plan, features, want_graphs):
+    def _step_stage(self, s, x, state, plan, features, want_graphs, search=None):
         """Stage ``s`` of ``step_graphs`` on its input ``x`` -> (the stage's output, its new graph | None).  ``plan``: (fused?, what
         ``CE._refresh_arguments`` returned for its heads) -- the refusals are through."""
         from .graph import PatchGraph
@@ -289,7 +302,7 @@ class CES(nn.Module):
         use, (radius, k_eff, margin, longest) = plan
         if use:
             return self._stage_step_fused(s, x, state.stages[s - 1], radius, k_eff, margin, longest, features, want_graphs)
-        pairs = [hd.step_graph(x, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs)
+        pairs = [hd.step_graph(x, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs, **(search or {}))
                  for h, hd in enumerate(heads)]
         return mix(torch.cat([o for o, _ in pairs], dim=1)) + x, (PatchGraph.cat([g for _, g in pairs]) if want_graphs else None)
 
@@ -369,7 +382,7 @@ class RR(nn.Module):
     @torch.no_grad()
     def step_graphs(self, x, state, **kw):
         """A sequence step of the network -> ``(out, SequenceState | None)``: ``forward`` with ``CES.step_graphs(., state, **kw)`` where the
-        ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused`` as there); always under ``torch.no_grad()``.  The ``CES``'s
+        ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused``, ``propagate``, ``explore``, ``seed`` as there); always under ``torch.no_grad()``.  The ``CES``'s
         refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
         return self._forward_around_ces(x, lambda ces, t: ces.step_graphs(t, state, **kw))
 

@@ -745,11 +745,13 @@ def _graph_refresh_arrays(dev, n_rows: int, E: int, radius: int, k: int, keep_al
     return head, key_out, weight, score, cap
 
 
-def _graph_refresh_result(who: str, head, key_out, weight, score, max_row_edges: int) -> dict:
-    """The one host read (E and the status words), the overlong-row refusal, the arrays as views of their first E entries."""
+def _graph_refresh_result(who: str, head, key_out, weight, score, max_row_edges: int, adjacent: bool = False) -> dict:
+    """The one host read (E and the status words), the overlong-row refusal, the arrays as views of their first E entries.
+    ``adjacent`` (a search call with ``propagate``): a row next to an overlong one is left empty and counted too."""
     total, overlong, _most = (int(v) for v in head[-3:].tolist())          # the one synchronisation
     if overlong:
-        err = DaglError(f"{who}: {overlong} row(s) hold more than max_row_edges = {max_row_edges} edges; they were left empty, "
+        err = DaglError(f"{who}: {overlong} row(s) hold{' or lie next to a row that holds' if adjacent else ''} more than "
+                        f"max_row_edges = {max_row_edges} edges; they were left empty, "
                         "not truncated: state the input's largest degree")
         err.code = _lib.ERR_UNSUPPORTED
         raise err
@@ -806,6 +808,125 @@ def graph_step(wq_rows, x_rows, b2p, row_off, key, *, radius: int = 1, tau=None,
     if not want_graph:
         return out, None, status
     return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
+
+
+GRAPH_SEARCH_MAX_EXPLORE = 256      # random keys a row of ``graph_search`` may ask for (the library's limit)
+
+
+def graph_search_row_bound(max_row_edges: int, radius: int, propagate, explore: int) -> int:
+    """Candidates a row of ``graph_search`` may expand into, ``(1 + 4 propagate) max_row_edges (2 radius + 1)^2 + explore``: it must
+    not exceed ``graph_refresh_max_candidates()``."""
+    return (1 + 4 * int(bool(propagate))) * int(max_row_edges) * (2 * int(radius) + 1) ** 2 + int(explore)
+
+
+def _graph_search_operands(who: str, propagate, explore, seed):
+    """What the search calls ask of their three arguments, before any pointer is taken -> (propagate 0 / 1, explore, seed as uint32)."""
+    if isinstance(propagate, torch.Tensor) or propagate not in (0, 1, False, True):
+        raise DaglError(f"{who}: propagate={propagate!r}, expected False or True")
+    if isinstance(explore, bool) or not isinstance(explore, int) or not 0 <= explore <= GRAPH_SEARCH_MAX_EXPLORE:
+        raise DaglError(f"{who}: explore={explore!r} outside [0, {GRAPH_SEARCH_MAX_EXPLORE}]")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise DaglError(f"{who}: seed={seed!r}, an int expected")
+    return int(bool(propagate)), explore, seed & 0xFFFFFFFF
+
+
+def _graph_search_arrays(dev, n_rows: int, E: int, radius: int, k: int, keep_all: bool, propagate: int, explore: int):
+    """``_graph_refresh_arrays`` at the capacity a search call may produce: ``(1 + 4 propagate) E (2 radius + 1)^2 + explore n_rows``, or
+    ``n_rows k`` under a rank cut where that is smaller.  Both flags off: the plain refresh's arrays."""
+    if not propagate and not explore:
+        return _graph_refresh_arrays(dev, n_rows, E, radius, k, keep_all)
+    cap = (1 + 4 * propagate) * E * (2 * radius + 1) ** 2 + explore * n_rows
+    if k > 0 and not keep_all:
+        cap = min(cap, n_rows * k)
+    head = torch.empty(n_rows + 3, device=dev, dtype=torch.int64)
+    key_out = torch.empty(cap, device=dev, dtype=torch.int32)
+    weight = torch.empty(cap, device=dev, dtype=torch.float32)
+    score = torch.empty(cap, device=dev, dtype=torch.float32)
+    return head, key_out, weight, score, cap
+
+
+@_on_device
+def graph_search(wq_rows, x_rows, row_off, key, *, radius: int = 1, tau=None, k: int = 0, scale: float = 10.0,
+                 normalize: str = "reference", keep_all: bool = False, max_row_edges=None, workspace: "Workspace | None" = None,
+                 hw=None, block_rows: bool = False, propagate=False, explore: int = 0, seed: int = 0) -> dict:
+    """``graph_refresh`` with two more candidate sources (``dagl_graph_search``, csrc/graph_refresh.hip) -> the same dict.  Per row the
+    candidates are the set union of (a) ``graph_refresh``'s windows around the row's own edges; (b) ``propagate``: for each of the four
+    queries adjacent to the row's in the stride-4 query grid of the same image (never across a grid-row end or an image boundary)
+    the windows around its edges' keys shifted by the query offset, ``(y - 4 dqy, x - 4 dqx)``, clipped cell by cell -- the adjacent
+    rows are read from the input graph, so the result does not depend on scheduling; (c) ``explore`` (0 .. 256) keys of the row's
+    image from a stateless counter hash of (row, ``seed``, t), no window around them.  Everything after the expansion is
+    ``graph_refresh``: a pair's score has the same bits, and with both sources off the call returns ``graph_refresh``'s arrays bit for
+    bit.  A row with no edge of its own can be populated by (b) and (c) -- with ``explore`` > 0 also an empty input graph.
+
+    ``max_row_edges`` as in ``graph_refresh``; ``graph_search_row_bound(max_row_edges, radius, propagate, explore)`` must not exceed
+    ``graph_refresh_max_candidates()``.  A row whose own or (``propagate``) adjacent row is longer than declared comes out empty, never
+    truncated, and the call raises ``DaglError`` with ``code == ERR_UNSUPPORTED`` naming the count.  One host read; not under stream
+    capture.  The same arrays and seed give the same bits on every call."""
+    lib = _lib.load()
+    who = "graph_search"
+    propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
+    B, H, W, E, flags, radius, k = _graph_refresh_operands(who, wq_rows, x_rows, row_off, key, radius, tau, k, normalize, keep_all,
+                                                           block_rows, hw)
+    max_row_edges = _graph_refresh_longest(who, row_off, E, max_row_edges)
+    dev = wq_rows.device
+    n_rows = B * wq_rows.shape[1]
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_search_workspace_bytes", B, H, W, E, radius, propagate, explore,
+                                   0 if keep_all else k, 1, 0)
+    head, key_out, weight, score, cap = _graph_search_arrays(dev, n_rows, E, radius, k, keep_all, propagate, explore)
+    check(lib.dagl_graph_search(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), row_off.data_ptr(), _ptr(key, E > 0), E,
+                                max_row_edges, radius, _ptr(tau), k, float(scale), flags, head.data_ptr(), _ptr(key_out, cap > 0),
+                                _ptr(weight, cap > 0), _ptr(score, cap > 0), cap, head[-2:].data_ptr(), a, nbytes, propagate, explore,
+                                seed), "dagl_graph_search")
+    del buf
+    return _graph_refresh_result(who, head, key_out, weight, score, max_row_edges, adjacent=bool(propagate))
+
+
+@_on_device
+def graph_search_step(wq_rows, x_rows, b2p, row_off, key, *, radius: int = 1, tau=None, k: int = 0, scale: float = 10.0,
+                      normalize: str = "reference", keep_all: bool = False, max_row_edges=None, want_graph: bool = True,
+                      workspace: "Workspace | None" = None, hw=None, block_rows: bool = False, propagate=False, explore: int = 0,
+                      seed: int = 0):
+    """``graph_step`` with ``graph_search``'s candidate sources (``dagl_graph_search_step``, csrc/graph_refresh.hip) ->
+    (out [B,16,H,W], dict | None, status): the dict holds, bit for bit, what ``graph_search`` returns for the same arguments, ``out``
+    is ``graph_step``'s aggregation of the kept entries -- the same bits with ``want_graph`` True or False.  Host reads, capture,
+    ``max_row_edges`` and the overlong-row rule as in ``graph_step``; ``seed`` is a launch argument: a captured call replays the seed
+    it was captured with."""
+    lib = _lib.load()
+    who = "graph_search_step"
+    propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
+    _need(b2p, "b2p")
+    map_hw = _value_map(who, b2p)[1:]
+    if hw is not None and tuple(int(v) for v in hw) != tuple(map_hw):
+        raise DaglError(f"{who}: hw={tuple(hw)} but b2p is the value map of a {map_hw[0]}x{map_hw[1]} image")
+    B, H, W, E, flags, radius, k = _graph_refresh_operands(who, wq_rows, x_rows, row_off, key, radius, tau, k, normalize, keep_all,
+                                                           block_rows, map_hw)
+    if b2p.shape[0] != B:
+        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    if want_graph:
+        max_row_edges = _graph_refresh_longest(who, row_off, E, max_row_edges)
+    elif max_row_edges is None:
+        raise DaglError(f"{who}: want_graph=False needs max_row_edges, the input's largest degree"
+                        + (" (reading it on the host is not available under stream capture)"
+                           if torch.cuda.is_current_stream_capturing() else " (the call itself reads nothing on the host)"))
+    max_row_edges = int(max_row_edges)
+    dev = wq_rows.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_search_workspace_bytes", B, H, W, E, radius, propagate, explore,
+                                   0 if keep_all else k, 1 if want_graph else 0, 1)
+    out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32)
+    if want_graph:
+        head, key_out, weight, score, cap = _graph_search_arrays(dev, B * wq_rows.shape[1], E, radius, k, keep_all, propagate, explore)
+        status = head[-2:]
+    else:
+        head = key_out = weight = score = None
+        cap, status = 0, torch.empty(2, device=dev, dtype=torch.int64)
+    check(lib.dagl_graph_search_step(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), b2p.data_ptr(), row_off.data_ptr(),
+                                     _ptr(key, E > 0), E, max_row_edges, radius, _ptr(tau), k, float(scale), flags, out.data_ptr(),
+                                     _ptr(head), _ptr(key_out, cap > 0), _ptr(weight, cap > 0), _ptr(score, cap > 0), cap,
+                                     status.data_ptr(), a, nbytes, propagate, explore, seed), "dagl_graph_search_step")
+    del buf
+    if not want_graph:
+        return out, None, status
+    return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges, adjacent=bool(propagate)), status
 
 
 def _stage_mix_operands(who: str, x, mix_w, mix_b):

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*,
+ * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*, dagl_graph_search*,
  * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
  * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan, dagl_ce_prologue16_debug*, dagl_project16_plan and dagl_ce_project16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
@@ -516,6 +516,41 @@ int    dagl_graph_step(void* stream, int B, int H, int W, const float* wq_rows, 
                        const float* tau /* NULL: no margin */, int k /* 0: no rank cut */, float scale, int flags, float* out,
                        int64_t* row_off_out /* [B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
                        int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
+
+/* ---- the search step on a patch graph: csrc/graph_refresh.hip (detected by symbol) ----------------------------------------------------
+ * dagl_graph_search / dagl_graph_search_step: dagl_graph_refresh / dagl_graph_step with two more candidate sources, so that a graph can
+ * improve from call to call, recover neighbours that moved farther than radius, and be built from any start without an L N scan.  The
+ * arguments of the plain entry, then propagate, explore, seed.  With Lh x Lw = ceil(H / 4) x ceil(W / 4) the query grid, wd = 2 radius + 1
+ * and row r = b L + qy Lw + qx, the candidates of r are the SET union of
+ *   (a) own:        as dagl_graph_refresh -- the wd^2 window, clipped at the map border, around every edge of r with key in [0, N);
+ *   (b) propagate:  for (dqy, dqx) in {(0,-1), (0,+1), (-1,0), (+1,0)} with (qy + dqy, qx + dqx) inside the query grid of the SAME image
+ *                   (never across a grid-row end or an image boundary) and every edge of that row with key (y, x) in [0, N): the wd^2
+ *                   window around (y - 4 dqy, x - 4 dqx), clipped cell by cell (the centre may lie off the map).  The adjacent rows are
+ *                   read from the INPUT graph (Jacobi): the result does not depend on scheduling;
+ *   (c) explore=m:  m keys of image b, key_t = ((uint64) h_t N) >> 32, h_t = lowbias32(lowbias32((uint32) r ^ seed) + t), t = 0 .. m - 1,
+ *                   lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (uint32).  No window.
+ * Scores, selection, weights, the aggregation and the output layout are the plain entries': a pair's score has the same bits.  A row is
+ * processed when it has any raw candidate, also with no edge of its own.  It comes out EMPTY, never truncated, when its own degree or an
+ * adjacent row's (propagate) exceeds max_row_edges -- counted once in status_out[0].  status_out[1]: the largest distinct count.
+ * Limits, beyond the plain entries': propagate 0 or 1 and 0 <= explore <= 256, else DAGL_ERR_INVALID;
+ * (1 + 4 propagate) max_row_edges wd^2 + explore <= dagl_graph_refresh_max_candidates(), else DAGL_ERR_UNSUPPORTED; capacity_edges >=
+ * (1 + 4 propagate) total_edges wd^2 + explore B L, or B L k when k > 0 (without KEEP_ALL) and that is smaller, else DAGL_ERR_WORKSPACE.
+ * With explore > 0 an input of total_edges = 0 is populated (key may be NULL, the outputs may not).  Workspace:
+ * dagl_graph_search_workspace_bytes (k: 0 with KEEP_ALL; aggregate: the step; want_graph: the step's graph outputs) -- the staging
+ * arrays hold B L k entries under a rank cut (row r at r k), else the bound above (row r at the prefix sum of its rows' bounds, formed
+ * from row_off in the kernel: no scan, no host read).  A wavefront per row when the row bound is <= 128.  propagate = explore = 0: the
+ * plain entry's launches, workspace and bits.  Nothing is read on the host; the same arrays and seed give the same bits on every call. */
+size_t dagl_graph_search_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int propagate, int explore, int k,
+                                         int want_graph, int aggregate);
+int    dagl_graph_search(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const int64_t* row_off,
+                         const int32_t* key, int64_t total_edges, int max_row_edges, int radius, const float* tau, int k, float scale,
+                         int flags, int64_t* row_off_out, int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges,
+                         int64_t* status_out, void* workspace, size_t ws_bytes, int propagate, int explore, uint32_t seed);
+int    dagl_graph_search_step(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                              const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                              const float* tau, int k, float scale, int flags, float* out, int64_t* row_off_out, int32_t* key_out,
+                              float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
+                              size_t ws_bytes, int propagate, int explore, uint32_t seed);
 
 /* ---- the sequence step of a whole CES stage: csrc/graph_refresh.hip, csrc/aggregate.hip (detected by symbol) ---------------------------
  * dagl_ces_stage_fold_mix: the end of a stage from its four heads' aggregated rows, in one launch:

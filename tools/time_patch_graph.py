@@ -10,6 +10,9 @@
                                                       # to ``forward``, the same two cases
     python tools/time_patch_graph.py --train-graph [H W]  # training on a frozen graph: the fused forward / backward next to the two
                                                           # ops and their backwards, ops alone and through ``forward_on_graph``
+    python tools/time_patch_graph.py --search [H W]   # the search step: ``refresh_graph`` alone, + propagate, + explore 8, both, on a
+                                                      # shifted frame -- time and recall against ``graph``; ``build_graph`` per
+                                                      # iteration next to the forward that selects; the two cases of --refresh
 """
 import os
 import sys
@@ -344,6 +347,61 @@ def step_leg(H, W, big):
           f"ops.graph_forward alone on the result {fmt(k_fwd)}", flush=True)
 
 
+def _recall(r, full):
+    """Edges of ``full`` that ``r`` holds, over the edges of ``full`` (as ``refresh_leg`` counts it)."""
+    hit = torch.isin(r.rows() * r.N + r.key.long(), full.rows() * full.N + full.key.long()).sum()
+    return int(hit) / max(full.n_edges, 1)
+
+
+def search_leg(H, W, big):
+    """The search step (``refresh_graph`` with ``propagate`` / ``explore``, radius 1, split-fp16 features) on the cases of
+    ``refresh_leg``.  The next frame is the input rolled by 1 pixel each way (inside the radius) and by 3 (outside it: the plain
+    refresh cannot follow); per frame the plain refresh, + propagate, + explore 8 and both: time of the call, edges, recall against
+    ``graph`` of that frame; a second and third search step on the same frame (the graph improves from step to step).  Then
+    ``build_graph`` (no L N scan, explore 8) per number of iterations: time and recall against ``graph(x)``, next to ``forward`` and
+    ``graph`` on the same input."""
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    name, mode, k, variant, gain = ("adaptive AND top-16 (sparse, gain 1.7)", "adaptive_topk", 16, "sparse", 1.7) if big else \
+        ("top-k 8", "topk", 8, "default", 1.65)
+    prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=gain).items()}
+    ce = CE(in_channels=64)
+    ce.load_state_dict(prm, strict=True)
+    ce.select_mode, ce.select_k = mode, k
+    ce = ce.to(dev).eval()
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    f16 = dict(radius=1, features="split16")
+    cases = (("refresh alone", dict()), ("+ propagate", dict(propagate=True)), ("+ explore 8", dict(explore=8, seed=1)),
+             ("+ propagate + explore 8", dict(propagate=True, explore=8, seed=1)))
+    with torch.no_grad():
+        g = ce.graph(x)
+        g.max_degree()
+        fwd = _events(lambda: ce(x))
+        exp = _events(lambda: ce.graph(x), warmup=1, repeats=3, inner=2)
+        print(f"[1,64,{H},{W}] {name}: graph(x) {g.n_edges} edges, degree mean {g.n_edges / g.L:.1f} max {g.max_degree()}; forward(x) "
+              f"{fmt(fwd)}; graph(x) {fmt(exp)}", flush=True)
+        for shift in (1, 3):
+            x2 = torch.roll(x, (shift, shift), (2, 3))
+            full = ce.graph(x2)
+            print(f"    next frame rolled by {shift}: graph(x2) {full.n_edges} edges", flush=True)
+            for what, kw in cases:
+                t = _events(lambda: ce.refresh_graph(x2, g, **f16, **kw))
+                r = ce.refresh_graph(x2, g, **f16, **kw)
+                line = f"        {what}: {fmt(t)}, {r.n_edges} edges, recall {_recall(r, full):.3f}"
+                if kw:
+                    for i in (2, 3):            # further steps on the same frame, a new seed each
+                        r = ce.refresh_graph(x2, r, **f16, **dict(kw, seed=i) if "explore" in kw else kw)
+                        line += f"; after step {i}: {_recall(r, full):.3f}"
+                print(line, flush=True)
+        for iters in (1, 2, 4, 8):
+            t = _events(lambda: ce.build_graph(x, iters=iters, features="split16"), warmup=1, repeats=3, inner=3)
+            b = ce.build_graph(x, iters=iters, features="split16")
+            print(f"    build_graph(x, iters={iters}, explore 8): {fmt(t)} = {t[0] / fwd[0]:.2f} of forward, {t[0] / exp[0]:.2f} of graph; "
+                  f"{b.n_edges} edges, recall against graph(x) {_recall(b, g):.3f}", flush=True)
+
+
 def train_graph_leg(H, W):
     """Training on a frozen graph, the three graphs of ``apply_leg``, one process, the protocol of ``attend_leg``.  The ops alone (the
     module's own fp32 features given): ``graph_attend`` + ``graph_apply`` next to ``graph_forward_train``, ``graph_apply_backward`` +
@@ -421,6 +479,8 @@ def train_graph_leg(H, W):
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--train-graph":
         return train_graph_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
+    if len(sys.argv) > 1 and sys.argv[1] == "--search":
+        return search_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--step":
         return step_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--refresh":
