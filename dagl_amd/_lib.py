@@ -34,6 +34,7 @@ FLAG_NO_REDO = 0x4000
 GRAPH_ATTEND_EDGES_ONLY = 0x1      # dagl_graph_attend*: a plain softmax over the row's edges
 GRAPH_REFRESH_KEEP_ALL = 0x2       # dagl_graph_refresh: keep every candidate (the dilated graph)
 GRAPH_REFRESH_BLOCK_ROWS = 0x4     # dagl_graph_refresh: a block per row also where rows are short (measurements)
+GRAPH_STAGE_SEARCH_HEAD_LAUNCHES = 0x8   # dagl_graph_stage_search*: the row kernel once per head, not once (measurements)
 
 
 class DaglError(RuntimeError):
@@ -103,6 +104,12 @@ SIGNATURES = {
     "dagl_graph_stage_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),
     "dagl_graph_stage_step": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 3 + [_vp, _vp, C.c_int64, _i, _i, C.POINTER(_vp), _i, C.c_float, _i]
                               + [_vp] * 8 + [C.c_int64, _vp, _vp, _sz]),
+    "dagl_graph_stage_search_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64] + [_i] * 6),
+    "dagl_graph_stage_search": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 2 + [_vp, _vp, C.c_int64, _i, _i, C.POINTER(_vp), _i, C.c_float, _i]
+                                + [_vp] * 4 + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
+    "dagl_graph_stage_search_step": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 3 + [_vp, _vp, C.c_int64, _i, _i, C.POINTER(_vp), _i, C.c_float,
+                                                                                     _i] + [_vp] * 8
+                                     + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
     "dagl_ce_list_width": (_i, [_i, _i]),
     "dagl_ce_range_check": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _sz, C.POINTER(_i)]),
     "dagl_ce_core_forward": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

@@ -1031,7 +1031,6 @@ class CE(nn.Module):
         grows until ``ops.graph_search_row_bound`` passes ``ops.graph_refresh_max_candidates()`` raises ``DaglError`` with
         ``code == ERR_UNSUPPORTED`` -- a row is never truncated.  ``iters`` >= 1.  One host read per iteration; always under
         ``torch.no_grad()``; the module's state is untouched."""
-        from .graph import PatchGraph
         if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
             raise DaglError(f"CE.build_graph: iters={iters!r}, an int >= 1 expected")
         ops._graph_search_operands("CE.build_graph", True, explore, seed)
@@ -1042,17 +1041,8 @@ class CE(nn.Module):
         if torch.cuda.is_current_stream_capturing():
             raise DaglError("CE.build_graph: not available while the stream is being captured (the edge count is read on the host)")
         B, _, H, W = b.shape
-        Lh, Lw = ops.query_grid(H, W)
-        pt, _bo = same_pad_amounts(H, self.ksize, self.stride_1)
-        pl, _r = same_pad_amounts(W, self.ksize, self.stride_1)
         with torch.no_grad():
-            dev = b.device
-            qy = (torch.arange(Lh, device=dev) * 4 - pt + 3).clamp_(0, H - 1)
-            qx = (torch.arange(Lw, device=dev) * 4 - pl + 3).clamp_(0, W - 1)
-            key = (qy.view(-1, 1) * W + qx.view(1, -1)).reshape(-1).repeat(B).to(torch.int32)
-            g = PatchGraph(torch.arange(B * Lh * Lw + 1, device=dev, dtype=torch.int64), key, torch.zeros(key.numel(), device=dev),
-                           None, B, H, W, self.select_mode if self.select_mode in ("adaptive", "topk", "adaptive_topk") else "adaptive", 0)
-            g._valid, g._max_degree = True, 1
+            g = self._build_start(B, H, W, b.device)
             feats = None
             for i in range(iters):
                 r, k_eff, margin, longest = self._refresh_arguments(b, g, "build_graph", radius, None, normalize, features,
@@ -1065,6 +1055,12 @@ class CE(nn.Module):
                                        workspace=self._ws_refresh, hw=(H, W), propagate=True, explore=explore, seed=seed + i)
                 g = self._refreshed(g, csr, poisoned, k_eff)
             return g
+
+    def _build_start(self, B: int, H: int, W: int, device):
+        """``build_graph``'s start (``graph.trivial_graph`` at this module's patch geometry and mode; ``SequenceState.start`` holds
+        twelve of them)."""
+        from .graph import trivial_graph
+        return trivial_graph(B, H, W, device, self.select_mode, self.ksize, self.stride_1)
 
     def forward_with_graph(self, b: torch.Tensor, *, scores: bool = False, features=None):
         """The block's output for ``b`` AND the patch graph that produced it, from one call -> ``(out, PatchGraph)``: the list-form route

@@ -41,6 +41,12 @@
 // entries now, so the flavour stages at r k under a rank cut and else at the prefix sum of the rows' bounds (rs_region_start: from
 // row_off alone, no scan), and graph_search_compact_kernel copies from there.  Both sources off: the plain launches.
 //
+// The stage search entries, dagl_graph_stage_search / dagl_graph_stage_search_step, are the search entries for the four heads of a CES
+// stage on the stage step's operands: graph_stage_search_rows_kernel runs rf_row's SEARCH flavour over all 4 B L rows in ONE launch (the
+// heads' operands by value in its arguments, head = row / (B L)), the staging laid out over the whole CSR, then one scan, one
+// graph_search_compact_kernel and launch_stage_fold_mix.  The random keys are hashed from the head-local row: the four heads explore
+// the same keys, as four calls with one seed do.
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -175,9 +181,12 @@ __device__ __forceinline__ void rf_zero_row(float* agg, int row) {
 // (1, 0)}, where that query lies in the Lh x Lw grid of the same image (the adjacent rows are read from the INPUT graph: Jacobi, no
 // dependence on scheduling; the centre may lie off the map, the window is clipped cell by cell); (c) sr.explore keys
 // (lowbias32(lowbias32(row ^ seed) + t) N) >> 32 of the row's image, no window -- and the row stages at rs_region_start; every step
-// after the expansion is the same code
+// after the expansion is the same code.  `row` is the row of the CSR (row_off, deg, the staging region, v.out); `lrow` the row of the
+// head's own operands (a.wq, a.x, a.tau, the value map, the hash of the random keys): the same row but in the stage kernel below, where
+// the CSR holds four heads' rows and lrow = row - h B L
 template <int T, int CAP, bool AGG, bool SEARCH = false>
-__device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v, const RsArgs& sr = RsArgs{}) {
+__device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v, const int row, const int lrow,
+                                       const RsArgs& sr = RsArgs{}) {
     __shared__ long long s_of[CAP];           // two int arrays (below); AGG: at the end the float4 offset of each kept entry's value patch
                                               // in the map, compacted -- no array of its own: at 2048 candidates 16 KiB more LDS halve the
                                               // blocks per CU, and the row body lives on them
@@ -190,7 +199,6 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     int* const s_key = s_sort + CAP;                      // the distinct candidates, ascending
     const bool graph_out = !AGG || f.st_key != nullptr;
     const int t = threadIdx.x;
-    const int row = blockIdx.x;
     const long long lo = gt_clamp(a.row_off[row], a.E), hi = gt_clamp(a.row_off[row + 1], a.E);
     const long long deg_in = hi - lo;
     const int wd = 2 * f.radius + 1, w2 = wd * wd;
@@ -253,7 +261,7 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     while (n_pad < raw) n_pad <<= 1;                                              // <= CAP: CAP is a power of two >= raw
     if (SEARCH) {
         const int windowed = src_end[4] * w2;                                     // entries (edge of a source, window offset); then the random keys
-        const unsigned h0 = rs_hash((unsigned)row ^ sr.seed);
+        const unsigned h0 = rs_hash((unsigned)lrow ^ sr.seed);
         for (int idx = t; idx < n_pad; idx += T) {
             int c = RF_EMPTY;
             if (idx < windowed) {
@@ -323,19 +331,19 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     // 4. scores and margins: a candidate per 16 lanes, two in flight per group
     {
         const int l = t & 15, grp = t >> 4, G = T / 16;
-        const float4* q = reinterpret_cast<const float4*>(a.wq) + (size_t)row * GT_C4;
-        const float4* xk = reinterpret_cast<const float4*>(a.x) + (size_t)(row / a.L) * a.N * GT_C4;
+        const float4* q = reinterpret_cast<const float4*>(a.wq) + (size_t)lrow * GT_C4;
+        const float4* xk = reinterpret_cast<const float4*>(a.x) + (size_t)(lrow / a.L) * a.N * GT_C4;
         for (int c0 = grp; c0 < n; c0 += 2 * G) {
             const int c1 = c0 + G < n ? c0 + G : c0;
             const float v0 = gt_edge_dot(q, xk + (size_t)s_key[c0] * GT_C4, l);
             const float v1 = gt_edge_dot(q, xk + (size_t)s_key[c1] * GT_C4, l);
             if (l == 0) {
                 float mg;
-                gt_logit(a, row, v0, mg);
+                gt_logit(a, lrow, v0, mg);
                 s_sc[c0] = v0;
                 s_flag[c0] = mg != 0.f ? 3 : 0;
                 if (c1 != c0) {
-                    gt_logit(a, row, v1, mg);
+                    gt_logit(a, lrow, v1, mg);
                     s_sc[c1] = v1;
                     s_flag[c1] = mg != 0.f ? 3 : 0;
                 }
@@ -380,14 +388,14 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     float mx = -INFINITY;
     for (int c = c0; c < c1; ++c) {
         float mg;
-        if (s_flag[c] & 4) mx = fmaxf(mx, gt_logit(a, row, s_sc[c], mg));
+        if (s_flag[c] & 4) mx = fmaxf(mx, gt_logit(a, lrow, s_sc[c], mg));
     }
     mx = rf_max<T>(mx, sh_f);
     const float M = off_graph ? fmaxf(mx, 0.f) : mx;
     double sum = 0.0;
     for (int c = c0; c < c1; ++c) {
         float mg;
-        if (s_flag[c] & 4) sum += (double)expf(gt_logit(a, row, s_sc[c], mg) - M);
+        if (s_flag[c] & 4) sum += (double)expf(gt_logit(a, lrow, s_sc[c], mg) - M);
     }
     sum = rf_sum<T>(sum, sh_d);
     if (off_graph) sum += (double)(a.N - kept) * exp(-(double)M);
@@ -405,7 +413,7 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
         if (c >= c1) break;
         if (!(s_flag[c] & 4)) continue;
         float mg;
-        const float z = gt_logit(a, row, s_sc[c], mg);
+        const float z = gt_logit(a, lrow, s_sc[c], mg);
         const float wgt = mg != 0.f ? (float)((double)expf(z - M) / sum) : 0.f;
         if (graph_out) {
             f.st_key[base + pos] = s_key[c];
@@ -414,7 +422,7 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
         }
         if (AGG) {
             my_w[i] = wgt;
-            my_of[i] = ga_source<true>(v, row, s_key[c]);        // (a candidate is a key of the map: never -1)
+            my_of[i] = ga_source<true>(v, lrow, s_key[c]);        // (a candidate is a key of the map: never -1)
         }
         ++pos;
     }
@@ -443,25 +451,45 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
 
 template <int T, int CAP>
 __global__ __launch_bounds__(T) void graph_refresh_rows_kernel(GtArgs a, RfArgs f) {
-    rf_row<T, CAP, false>(a, f, GaArgs{});
+    rf_row<T, CAP, false>(a, f, GaArgs{}, blockIdx.x, blockIdx.x);
 }
 
 // dagl_graph_step's: the refresh's row and its aggregated output row from the same kept entries
 template <int T, int CAP>
 __global__ __launch_bounds__(T) void graph_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v) {
-    rf_row<T, CAP, true>(a, f, v);
+    rf_row<T, CAP, true>(a, f, v, blockIdx.x, blockIdx.x);
 }
 
 // dagl_graph_search's and dagl_graph_search_step's: the same two bodies with the SEARCH candidate sources (kernels of their own: the
 // four above keep their arguments and their device code)
 template <int T, int CAP>
 __global__ __launch_bounds__(T) void graph_search_rows_kernel(GtArgs a, RfArgs f, RsArgs sr) {
-    rf_row<T, CAP, false, true>(a, f, GaArgs{}, sr);
+    rf_row<T, CAP, false, true>(a, f, GaArgs{}, blockIdx.x, blockIdx.x, sr);
 }
 
 template <int T, int CAP>
 __global__ __launch_bounds__(T) void graph_search_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr) {
-    rf_row<T, CAP, true, true>(a, f, v, sr);
+    rf_row<T, CAP, true, true>(a, f, v, blockIdx.x, blockIdx.x, sr);
+}
+
+// dagl_graph_stage_search's and dagl_graph_stage_search_step's: the SEARCH flavour over the 4 B L head-major rows of a CES stage's CSR in
+// ONE launch.  The four heads' own operands come by value in the arguments; row r belongs to head h = r / (B L) and is row r - h B L of
+// that head's features, margins, value map and hash, while the offsets, the adjacent rows, the degree, the staging region (the prefix
+// sum over the WHOLE CSR: a.n_rows = 4 B L) and the aggregated row are those of r.  row0: the first row of the launch (0 but where the
+// heads are launched one by one, for measurements)
+struct RsHeads { const float* wq[4]; const float* x[4]; const float* tau[4]; const float* b2p[4]; };
+
+template <int T, int CAP, bool AGG>
+__global__ __launch_bounds__(T) void graph_stage_search_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr, RsHeads hd, int head_rows,
+                                                                    int row0) {
+    const int row = row0 + (int)blockIdx.x;                      // < 4 head_rows (the launch)
+    const int h = row / head_rows;
+    // (selects, not an index: the table stays in scalar registers)
+    a.wq = h == 0 ? hd.wq[0] : (h == 1 ? hd.wq[1] : (h == 2 ? hd.wq[2] : hd.wq[3]));
+    a.x = h == 0 ? hd.x[0] : (h == 1 ? hd.x[1] : (h == 2 ? hd.x[2] : hd.x[3]));
+    a.tau = h == 0 ? hd.tau[0] : (h == 1 ? hd.tau[1] : (h == 2 ? hd.tau[2] : hd.tau[3]));
+    if (AGG) v.src = h == 0 ? hd.b2p[0] : (h == 1 ? hd.b2p[1] : (h == 2 ? hd.b2p[2] : hd.b2p[3]));
+    rf_row<T, CAP, AGG, true>(a, f, v, row, row - h * head_rows, sr);
 }
 
 // graph_refresh_compact_kernel (below) for the SEARCH flavour: a row's staged entries start at rs_region_start.  deg[row] > 0 only where
@@ -687,6 +715,79 @@ static int launch_graph_stage_step(hipStream_t s, int B, const Grid& g, const Re
     return launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out);
 }
 
+// the entries of each staging array of the stage search: 4 B L k under a rank cut, else rs_region_start's prefix sums over the whole CSR
+// (also with both sources off: the flavour's own layout)
+static int64_t rs_stage_staged(int64_t n_rows, int64_t E, int radius, int propagate, int explore, int k_region) {
+    const int64_t w2 = (int64_t)(2 * radius + 1) * (2 * radius + 1);
+    return k_region > 0 ? n_rows * k_region : (1 + 4 * propagate) * E * w2 + explore * n_rows;
+}
+
+template <bool AGG>
+static void launch_stage_search_rows(hipStream_t s, int rows, bool wave, const GtArgs& a, const RfArgs& f, const GaArgs& v, const RsArgs& sr,
+                                     const RsHeads& hd, int head_rows, int row0) {
+    if (wave) {
+        hipLaunchKernelGGL((graph_stage_search_rows_kernel<64, RF_WAVE_CAP, AGG>), dim3((unsigned)rows), dim3(64), 0, s, a, f, v, sr, hd,
+                           head_rows, row0);
+    } else {
+        hipLaunchKernelGGL((graph_stage_search_rows_kernel<256, RF_CAP, AGG>), dim3((unsigned)rows), dim3(256), 0, s, a, f, v, sr, hd,
+                           head_rows, row0);
+    }
+}
+
+// The search step of a whole CES stage (dagl_graph_stage_search*): the CSR, the operand tables and the end of launch_graph_stage_step,
+// but ONE row launch over the 4 B L rows (graph_stage_search_rows_kernel), and the staging laid out over the whole CSR: without a rank
+// cut a head's rows may need up to 5 E_h w2 entries, which no slice of an E w2 array holds.  st.b2p4 / r.out null: the graph alone.
+// head_launches: the same kernel once per head on its rows (for measurements: the same bits)
+static int launch_graph_stage_search(hipStream_t s, int B, const Grid& g, const RefreshCall& r, const StageStepCall& st, void* workspace,
+                                     bool head_launches) {
+    const int head_rows = B * g.L, n_rows = 4 * head_rows, wd = 2 * r.radius + 1, w2 = wd * wd;
+    const bool agg = r.out != nullptr, graph = r.row_off_out != nullptr;
+    DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
+    const int k_region = r.keep_all ? 0 : r.k;
+    const int64_t staged = rs_stage_staged(n_rows, r.c.E, r.radius, r.propagate, r.explore, k_region);
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, (size_t)staged, agg, graph);
+    if (r.c.E == 0 && r.explore == 0) {                          // (random keys populate an empty graph)
+        if (graph) DAGL_HIP_TRY(hipMemsetAsync(r.row_off_out, 0, ((size_t)n_rows + 1) * sizeof(int64_t), s));
+        if (!agg) return DAGL_OK;
+        DAGL_HIP_TRY(hipMemsetAsync(w.agg, 0, (size_t)n_rows * P * sizeof(float), s));                  // fold(0) / cnt: out = mix_b + x
+        return launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out);
+    }
+    GraphAttendCall c = r.c;
+    c.wq_rows = st.wq4[0]; c.x_rows = st.x4[0];                  // (the kernel takes every head's from the table)
+    const GtArgs a = gt_args(4 * B, g, c);                       // n_rows = 4 B L: the rows rs_region_start sums over
+    RfArgs f{};
+    f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.max_row_edges; f.k = k_region; f.keep_all = r.keep_all ? 1 : 0;
+    f.deg = w.deg; f.st_key = w.st_key; f.st_score = w.st_score; f.st_weight = w.st_weight;
+    f.status = reinterpret_cast<unsigned long long*>(r.status);
+    RsArgs sr{};
+    sr.propagate = r.propagate; sr.explore = r.explore; sr.seed = r.seed; sr.Lw = g.Lw; sr.k_region = k_region; sr.staged = staged;
+    RsHeads hd{};
+    for (int h = 0; h < 4; ++h) {
+        hd.wq[h] = st.wq4[h]; hd.x[h] = st.x4[h]; hd.tau[h] = st.tau4 ? st.tau4[h] : nullptr; hd.b2p[h] = agg ? st.b2p4[h] : nullptr;
+    }
+    GaArgs v{};
+    if (agg) {
+        v = ga_map_args(B, g, st.b2p4[0], nullptr, nullptr, nullptr, 0);
+        v.out = w.agg;
+    }
+    const bool wave = rf_wave_rows(r);
+    for (int row0 = 0; row0 < n_rows; row0 += head_launches ? head_rows : n_rows) {
+        const int rows = head_launches ? head_rows : n_rows;
+        if (agg) launch_stage_search_rows<true>(s, rows, wave, a, f, v, sr, hd, head_rows, row0);
+        else launch_stage_search_rows<false>(s, rows, wave, a, f, v, sr, hd, head_rows, row0);
+        DAGL_LAUNCH_CHECK("graph_stage_search_rows_kernel");
+    }
+    if (graph) {
+        const int rc = launch_row_scan(s, n_rows, w.deg, r.row_off_out);
+        if (rc) return rc;
+        hipLaunchKernelGGL(graph_search_compact_kernel, dim3((unsigned)((n_rows + RF_COPY_ROWS - 1) / RF_COPY_ROWS)), dim3(RF_COPY_ROWS * 64), 0,
+                           s, n_rows, w2, (long long)r.c.E, sr, r.c.row_off, w.deg, r.row_off_out, w.st_key, w.st_score, w.st_weight,
+                           r.key_out, r.weight_out, r.score_out, (long long)r.capacity);
+        DAGL_LAUNCH_CHECK("graph_search_compact_kernel");
+    }
+    return agg ? launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out) : DAGL_OK;
+}
+
 static int refresh_shape_ok(const char* who, int B, int H, int W, int64_t total_edges, int radius) {
     int rc = graph_dims_ok(who, B, H, W);
     if (rc) return rc;
@@ -773,6 +874,61 @@ static int stage_shape_ok(const char* who, int B, int H, int W, int64_t total_ed
 static int stage_mix_operands_ok(const char* who, const float* x, const float* mix_w, const float* mix_b, const float* out) {
     DAGL_REQUIRE(x && mix_w && mix_b && out, "%s: null tensor pointer", who);
     return DAGL_OK;
+}
+
+// the checks and the call of the stage search entries.  step: b2p4, x, mix_w, mix_b and out are given, and the four graph outputs may all
+// be null (the output alone: capacity_edges is not looked at)
+static int graph_stage_search_entry(const char* who, void* stream, int B, int H, int W, const float* const* wq_rows4,
+                                    const float* const* x_rows4, const float* const* b2p4, const int64_t* row_off, const int32_t* key,
+                                    int64_t total_edges, int max_row_edges, int radius, const float* const* tau4, int k, float scale,
+                                    int flags, const float* x, const float* mix_w, const float* mix_b, float* out, int64_t* row_off_out,
+                                    int32_t* key_out, float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out,
+                                    void* workspace, size_t ws_bytes, bool step, int propagate, int explore, uint32_t seed) {
+    int rc = stage_shape_ok(who, B, H, W, total_edges, radius);
+    if (rc) return rc;
+    if ((rc = search_args_ok(who, propagate, explore))) return rc;
+    DAGL_REQUIRE(wq_rows4 && x_rows4 && (!step || b2p4), "%s: null pointer table", who);
+    const bool graph = !step || row_off_out || key_out || weight_out || score_out;
+    const bool outputs = status_out && (!graph || (row_off_out && ((total_edges == 0 && !explore) || (key_out && weight_out && score_out))));
+    int with_tau = 0;
+    for (int h = 0; h < 4; ++h) {
+        if ((rc = graph_operands_ok(who, wq_rows4[h], x_rows4[h], row_off, key, total_edges, scale, flags, outputs && (!step || b2p4[h]),
+                                    DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS | DAGL_GRAPH_STAGE_SEARCH_HEAD_LAUNCHES)))
+            return rc;
+        if (step) DAGL_REQUIRE(((uintptr_t)b2p4[h] % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+        with_tau += tau4 && tau4[h];
+    }
+    DAGL_REQUIRE(with_tau == 0 || with_tau == 4, "%s: tau given for %d of the four heads (all or none)", who, with_tau);
+    if (step && (rc = stage_mix_operands_ok(who, x, mix_w, mix_b, out))) return rc;
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    DAGL_REQUIRE(max_row_edges >= 0, "%s: max_row_edges=%d < 0", who, max_row_edges);
+    if (rf_row_bound(max_row_edges, radius, propagate, explore) > RF_CAP) {
+        set_error("%s: (1 + 4 propagate) max_row_edges (2 radius + 1)^2 + explore = %lld candidates per row, more than the %d a row may "
+                  "expand into", who, rf_row_bound(max_row_edges, radius, propagate, explore), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    const Grid g = make_grid(H, W);
+    const int64_t n_rows = (int64_t)4 * B * g.L;
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    int64_t may = rf_staged(n_rows, total_edges, radius, propagate, explore, 0);
+    if (!keep_all && k > 0 && n_rows * k < may) may = n_rows * k;
+    if (graph && capacity_edges < may) {
+        set_error("%s: capacity %lld edges < the %lld this call may produce", who, (long long)capacity_edges, (long long)may);
+        return DAGL_ERR_WORKSPACE;
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)n_rows,
+                                      (size_t)rs_stage_staged(n_rows, total_edges, radius, propagate, explore, keep_all ? 0 : k), step,
+                                      graph).bytes;
+    if ((rc = check_workspace(who, workspace, ws_bytes, need))) return rc;
+    RefreshCall r{};
+    r.c = graph_attend_call(nullptr, nullptr, row_off, key, total_edges, nullptr, scale, flags);
+    r.max_row_edges = max_row_edges; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.row_off_out = graph ? row_off_out : nullptr; r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out;
+    r.capacity = capacity_edges; r.status = status_out; r.out = step ? out : nullptr;
+    r.search = true; r.propagate = propagate; r.explore = explore; r.seed = seed;
+    const StageStepCall st{wq_rows4, x_rows4, step ? b2p4 : nullptr, with_tau ? tau4 : nullptr, x, mix_w, mix_b};
+    return launch_graph_stage_search((hipStream_t)stream, B, g, r, st, workspace, (flags & DAGL_GRAPH_STAGE_SEARCH_HEAD_LAUNCHES) != 0);
 }
 
 }  // namespace dagl
@@ -924,6 +1080,38 @@ int dagl_graph_stage_step(void* stream, int B, int H, int W, const float* const*
     r.capacity = capacity_edges; r.status = status_out; r.out = out;
     const StageStepCall st{wq_rows4, x_rows4, b2p4, with_tau ? tau4 : nullptr, x, mix_w, mix_b};
     return launch_graph_stage_step((hipStream_t)stream, B, g, r, st, workspace);
+}
+
+// the search step of a whole CES stage: the four heads' rows in one row launch (no ABI bump: found by symbol)
+size_t dagl_graph_stage_search_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int propagate, int explore, int k,
+                                               int want_graph, int aggregate) {
+    const char* who = "dagl_graph_stage_search_workspace_bytes";
+    if (stage_shape_ok(who, B, H, W, total_edges, radius) || search_args_ok(who, propagate, explore)) return 0;
+    if (k < 0) { set_error("%s: k=%d < 0", who, k); return 0; }
+    const int64_t n_rows = (int64_t)4 * B * make_grid(H, W).L;
+    return refresh_carve(nullptr, (size_t)n_rows, (size_t)rs_stage_staged(n_rows, total_edges, radius, propagate, explore, k),
+                         aggregate != 0, want_graph != 0 || aggregate == 0).bytes;
+}
+
+int dagl_graph_stage_search(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                            const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                            const float* const* tau4, int k, float scale, int flags, int64_t* row_off_out, int32_t* key_out,
+                            float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
+                            size_t ws_bytes, int propagate, int explore, uint32_t seed) {
+    return graph_stage_search_entry("dagl_graph_stage_search", stream, B, H, W, wq_rows4, x_rows4, nullptr, row_off, key, total_edges,
+                                    max_row_edges, radius, tau4, k, scale, flags, nullptr, nullptr, nullptr, nullptr, row_off_out, key_out,
+                                    weight_out, score_out, capacity_edges, status_out, workspace, ws_bytes, false, propagate, explore, seed);
+}
+
+int dagl_graph_stage_search_step(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                                 const float* const* b2p4, const int64_t* row_off, const int32_t* key, int64_t total_edges,
+                                 int max_row_edges, int radius, const float* const* tau4, int k, float scale, int flags, const float* x,
+                                 const float* mix_w, const float* mix_b, float* out, int64_t* row_off_out, int32_t* key_out,
+                                 float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
+                                 size_t ws_bytes, int propagate, int explore, uint32_t seed) {
+    return graph_stage_search_entry("dagl_graph_stage_search_step", stream, B, H, W, wq_rows4, x_rows4, b2p4, row_off, key, total_edges,
+                                    max_row_edges, radius, tau4, k, scale, flags, x, mix_w, mix_b, out, row_off_out, key_out, weight_out,
+                                    score_out, capacity_edges, status_out, workspace, ws_bytes, true, propagate, explore, seed);
 }
 
 }  // extern "C"

@@ -15,6 +15,26 @@ from ._lib import MODES, DaglError
 DENSE_LIMIT = 1 << 26          # largest [L, N] ``to_dense`` builds (256 MiB of fp32)
 
 
+def trivial_graph(B: int, H: int, W: int, device, mode: str = "adaptive", ksize: int = 7, stride: int = 4) -> "PatchGraph":
+    """The start of a graph search (``CE.build_graph``, ``SequenceState.start``): one edge per query, the key at the query patch's own
+    position (the patch origin of ``synth.query_grid`` + 3, clamped to the map), weight 0, no score; valid, largest degree 1.  Works
+    on the CPU."""
+    from .synth import same_pad_amounts
+    B, H, W = int(B), int(H), int(W)
+    if B < 1 or H < 1 or W < 1:
+        raise DaglError(f"trivial_graph: bad shape B={B} H={H} W={W}")
+    Lh, Lw = -(-H // stride), -(-W // stride)
+    pt, _bo = same_pad_amounts(H, ksize, stride)
+    pl, _r = same_pad_amounts(W, ksize, stride)
+    qy = (torch.arange(Lh, device=device) * 4 - pt + 3).clamp_(0, H - 1)
+    qx = (torch.arange(Lw, device=device) * 4 - pl + 3).clamp_(0, W - 1)
+    key = (qy.view(-1, 1) * W + qx.view(1, -1)).reshape(-1).repeat(B).to(torch.int32)
+    g = PatchGraph(torch.arange(B * Lh * Lw + 1, device=device, dtype=torch.int64), key, torch.zeros(key.numel(), device=device),
+                   None, B, H, W, mode if mode in MODES else "adaptive", 0)
+    g._valid, g._max_degree = True, 1
+    return g
+
+
 class PatchGraph:
     """CSR over the ``B * L`` query rows (row ``b * L + i`` = query patch ``i`` of image ``b``):
 

@@ -191,8 +191,8 @@ class CES(nn.Module):
         NaN-fills ``out`` and that head's rows of the new graph, never wrong numbers.
 
         ``propagate`` / ``explore`` / ``seed``: ``CE.step_graph``'s search keywords, handed to every head (off by default: the call is
-        then exactly the one above).  The stage-fused launch has no search flavour: with any of them set ``fused=None`` runs head by
-        head and ``fused=True`` is refused, before any launch.
+        then exactly the one above).  The stage-fused launch of THIS method has no search flavour (``search_graphs`` is the
+        stage-fused search step): with any of them set ``fused=None`` runs head by head and ``fused=True`` is refused, before any launch.
 
         Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
         the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
@@ -260,11 +260,10 @@ class CES(nn.Module):
             out = self._between_stages(s, mix(torch.cat(outs, dim=1)) + out)
         return out
 
-    def _plan_step(self, x, state, radius, features, want_graphs, fused, search=None):
-        """Every refusal of ``step_graphs`` that depends on a stage, raised before the first launch -- every stage sees an input of x's
-        shape, dtype and device -- -> {stage: (fused?, what ``CE._refresh_arguments`` returns for its heads)}."""
+    def _plan_step(self, x, state, radius, features, want_graphs, fused, search=None, what="CES.step_graphs"):
+        """Every refusal of ``step_graphs`` / ``search_graphs`` that depends on a stage, raised before the first launch -- every stage
+        sees an input of x's shape, dtype and device -- -> {stage: (fused?, what ``CE._refresh_arguments`` returns for its heads)}."""
         from ._lib import DaglError
-        what = "CES.step_graphs"
         B = x.shape[0]
         capturing = torch.cuda.is_current_stream_capturing()
         plan = {}
@@ -322,8 +321,11 @@ class CES(nn.Module):
         if fast:
             for f in feats:
                 out = f[4](out)                     # a head that left the split-fp16 range NaN-fills the stage's output
-        if not want_graphs:
-            return out, None
+        return out, (self._stage_graph(stage, csr, feats, fast, heads[0].select_mode, k_eff) if want_graphs else None)
+
+    @staticmethod
+    def _stage_graph(stage, csr, feats, fast, mode, k_eff):
+        """The stage's new ``PatchGraph`` from a stage-fused call's CSR over the four heads' rows."""
         weight, score = csr["weight"], csr["score"]
         if fast:
             # ... and its own rows of the graph: 0 or NaN per head, spread over the edges by the heads' first offsets (no host read)
@@ -332,8 +334,124 @@ class CES(nn.Module):
             head_of = torch.bucketize(torch.arange(weight.numel(), device=weight.device), csr["row_off"][n:4 * n:n].contiguous(), right=True)
             weight, score = weight + verdict[head_of], score + verdict[head_of]
         g = stage._like(csr["row_off"], csr["key"], weight, score)
-        g.mode, g.k, g._valid = heads[0].select_mode, k_eff, True               # (every candidate is a key of the map)
-        return out, g
+        g.mode, g.k, g._valid = mode, k_eff, True                               # (every candidate is a key of the map)
+        return g
+
+    # ---- the search step of the whole module: step_graphs with propagation and random candidates, stage-fused -------------------------
+    @torch.no_grad()
+    def search_graphs(self, x, state, *, iters: int = 1, radius: int = 1, propagate: bool = True, explore: int = 8, seed: int = 0,
+                      features: str = "fp32", want_graphs: bool = True, fused=None):
+        """The search step of the whole module -> ``(out, SequenceState | None)``: ``step_graphs`` with ``CE.step_graph``'s search
+        keywords, where the stage-fused form exists.  Per stage, on the stage's input ``x_s``: the four heads' features are computed
+        once; then ``iters - 1`` graph-only search iterations with seeds ``seed + i``; then one search step with seed
+        ``seed + iters - 1``, which also gives the stage's output.  ``RBS1`` / ``RBS2`` run between the stages as in ``forward``.
+
+        ``fused=False`` is the definition: per head ``refresh_graph(x_s, g, radius=, propagate=, explore=, seed=seed + i, features=)``
+        ``iters - 1`` times, then ``step_graph(..., seed=seed + iters - 1)``; the stage's output is ``mix(cat(outputs)) + x_s``.
+        ``fused=True``: ``ops.graph_stage_search`` / ``ops.graph_stage_search_step`` -- ONE row launch over the four heads' rows per
+        iteration, one scan, one copy, fold + mix + residual in one launch.  The graphs are the head-by-head ones bit for bit; ``out``
+        differs by the fp32 roundings of the mix product alone.  ``fused=None``: fused for every stage that qualifies as in
+        ``step_graphs``, head by head otherwise; ``fused=True`` on a stage that does not qualify is refused.
+
+        ``want_graphs=False`` requires ``iters == 1``: it keeps the structure, returns ``(out, None)`` and can be captured under the
+        conditions ``step_graphs`` states (``seed`` is a launch argument: a replay explores the same keys).  The split-fp16 range
+        contract is ``step_graphs``'s.  Every refusal comes before the first launch: ``iters`` that is no int >= 1, every head's
+        ``CE._refresh_arguments``, a state that does not fit the input, and ``ops.graph_search_row_bound`` above
+        ``ops.graph_refresh_max_candidates()`` (``code == ERR_UNSUPPORTED``) -- that bound is looked at again before every iteration, on
+        the graph the previous one left.  Always under ``torch.no_grad()``; the modules' state is untouched; each stage has one workspace
+        (``step_graphs``'s)."""
+        from ._lib import DaglError
+        from . import ops
+        from .sequence import SequenceState
+        what = "CES.search_graphs"
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise DaglError(f"{what}: iters={iters!r}, an int >= 1 expected")
+        want_graphs = bool(want_graphs)
+        if not want_graphs and iters != 1:
+            raise DaglError(f"{what}: want_graphs=False keeps the structure: iters={iters} iterations would be thrown away (iters=1 only)")
+        ops._graph_search_operands(what, propagate, explore, seed)
+        search = dict(propagate=bool(propagate), explore=explore, seed=seed)
+        if not isinstance(state, SequenceState):
+            raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise DaglError(f"{what}: expected [B,C,H,W]")
+        B = x.shape[0]
+        g0 = state.stages[0]
+        if (g0.B, g0.H, g0.W) != (4 * B, x.shape[2], x.shape[3]):
+            raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={B} H={x.shape[2]} W={x.shape[3]}")
+        plan = self._plan_step(x, state, radius, features, want_graphs, fused, search, what=what)
+        out, new = x, []
+        for s in (1, 2, 3):
+            out, g = self._search_stage(s, out, state, plan[s], iters, features, want_graphs, search)
+            new.append(g)
+            out = self._between_stages(s, out)
+        return out, (SequenceState(new) if want_graphs else None)
+
+    def _search_stage(self, s, x, state, plan, iters, features, want_graphs, search):
+        """Stage ``s`` of ``search_graphs`` on its input ``x`` -> (the stage's output, its new graph | None)."""
+        from ._lib import ERR_UNSUPPORTED, DaglError
+        from . import ops
+        from .graph import PatchGraph
+        heads, mix = self._stage_modules(s)
+        use, (radius, k_eff, margin, longest) = plan
+        seed = search["seed"]
+        kw = dict(radius=radius, features=features, propagate=search["propagate"], explore=search["explore"])
+        if not use:
+            pairs = []
+            for h, hd in enumerate(heads):
+                g = state.head(s - 1, h)
+                for i in range(iters - 1):
+                    g = hd.refresh_graph(x, g, seed=seed + i, **kw)
+                pairs.append(hd.step_graph(x, g, seed=seed + iters - 1, want_graph=want_graphs, **kw))
+            return mix(torch.cat([o for o, _ in pairs], dim=1)) + x, (PatchGraph.cat([g for _, g in pairs]) if want_graphs else None)
+        fast = features == "split16"
+        x = x.contiguous()
+        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        wq4, x4, b2p4 = ([f[i].contiguous() for f in feats] for i in (0, 1, 3))
+        common = dict(radius=radius, tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff,
+                      scale=float(heads[0].softmax_scale), workspace=self._ws_step[s], propagate=search["propagate"],
+                      explore=search["explore"])
+        stage = state.stages[s - 1]
+        g, cap = stage, ops.graph_refresh_max_candidates()
+        for i in range(iters):
+            if i:
+                longest = g.max_degree()                   # (one word read on the host: iters > 1 returns graphs, never captured)
+                bound = ops.graph_search_row_bound(longest, radius, search["propagate"], search["explore"])
+                if bound > cap:
+                    err = DaglError(f"CES.search_graphs: after {i} iteration(s) a row of stage {s} holds {longest} edges: with "
+                                    f"propagate={search['propagate']}, explore={search['explore']} and radius {radius} it may expand "
+                                    f"into {bound} candidates, more than {cap}")
+                    err.code = ERR_UNSUPPORTED
+                    raise err
+            if i < iters - 1:
+                csr = ops.graph_stage_search(wq4, x4, g.row_off, g.key, (x.shape[2], x.shape[3]), max_row_edges=longest,
+                                             seed=seed + i, **common)
+                g = stage._like(csr["row_off"], csr["key"], csr["weight"], csr["score"])
+        out, csr, _status = ops.graph_stage_search_step(wq4, x4, b2p4, g.row_off, g.key, x, mix.weight.detach().contiguous(),
+                                                        mix.bias.detach().contiguous(), max_row_edges=longest, want_graph=want_graphs,
+                                                        seed=seed + iters - 1, **common)
+        if fast:
+            for f in feats:
+                out = f[4](out)                     # a head that left the split-fp16 range NaN-fills the stage's output
+        return out, (self._stage_graph(stage, csr, feats, fast, heads[0].select_mode, k_eff) if want_graphs else None)
+
+    @torch.no_grad()
+    def build_graphs(self, x, *, iters: int = 4, radius: int = 1, explore: int = 8, seed: int = 0, features: str = "fp32", fused=None):
+        """A key frame of the whole module WITHOUT any scan of the L*N pairs -> ``(out, SequenceState)``: ``search_graphs`` from
+        ``SequenceState.start`` with ``propagate=True``.  Head ``h`` of stage ``s`` comes out as
+        ``hd.build_graph(x_s, iters=, radius=, explore=, seed=, features=)`` on the stage's input, bit for bit; ``out`` is the module's
+        output on those graphs.  How close they come to ``forward_with_graphs``' depends on the input (``CE.build_graph``)."""
+        from ._lib import DaglError
+        from .sequence import SequenceState
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise DaglError("CES.build_graphs: expected [B,C,H,W]")
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise DaglError(f"CES.build_graphs: iters={iters!r}, an int >= 1 expected")
+        mode = self._stage_modules(1)[0][0]
+        mode = mode.select_mode if isinstance(mode, CE) else "adaptive"
+        start = SequenceState.start(x.shape[0], x.shape[2], x.shape[3], x.device, mode)
+        return self.search_graphs(x, start, iters=iters, radius=radius, propagate=True, explore=explore, seed=seed, features=features,
+                                  want_graphs=True, fused=fused)
 
 
 class _MeanShift(nn.Conv2d):
@@ -385,6 +503,19 @@ class RR(nn.Module):
         ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused``, ``propagate``, ``explore``, ``seed`` as there); always under ``torch.no_grad()``.  The ``CES``'s
         refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
         return self._forward_around_ces(x, lambda ces, t: ces.step_graphs(t, state, **kw))
+
+    @torch.no_grad()
+    def search_graphs(self, x, state, **kw):
+        """The search step of the network -> ``(out, SequenceState | None)``: ``forward`` with ``CES.search_graphs(., state, **kw)`` where
+        the ``CES`` sits (``iters``, ``radius``, ``propagate``, ``explore``, ``seed``, ``features``, ``want_graphs``, ``fused`` as there);
+        always under ``torch.no_grad()``.  The ``CES``'s refusals are raised when it is reached."""
+        return self._forward_around_ces(x, lambda ces, t: ces.search_graphs(t, state, **kw))
+
+    @torch.no_grad()
+    def build_graphs(self, x, **kw):
+        """A key frame of the network without any L*N scan -> ``(out, SequenceState)``: ``forward`` with ``CES.build_graphs(., **kw)``
+        where the ``CES`` sits (``iters``, ``radius``, ``explore``, ``seed``, ``features``, ``fused`` as there)."""
+        return self._forward_around_ces(x, lambda ces, t: ces.build_graphs(t, **kw))
 
     def forward_on_graphs(self, x, state, **kw):
         """The network's output for ``x`` on the frozen graphs of ``state`` -> ``out``: ``forward`` with

@@ -1037,6 +1037,116 @@ def graph_stage_step(wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, *, 
     return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
 
 
+def _graph_stage_search(who: str, entry: str, wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, radius, tau4, k, scale, normalize,
+                        keep_all, max_row_edges, want_graph, workspace, block_rows, propagate, explore, seed, head_launches):
+    """The body of ``graph_stage_search`` (``b2p4`` None: x names the shape alone) and ``graph_stage_search_step``."""
+    lib = _lib.load()
+    step = b2p4 is not None
+    propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
+    tables = (("wq_rows4", wq_rows4), ("x_rows4", x_rows4)) + ((("b2p4", b2p4),) if step else ()) \
+        + ((("tau4", tau4),) if tau4 is not None else ())
+    for name, seq in tables:
+        if not isinstance(seq, (list, tuple)) or len(seq) != 4:
+            raise DaglError(f"{who}: {name} must be a sequence of four tensors, one per head")
+    if step:
+        B, H, W = _stage_mix_operands(who, x, mix_w, mix_b)
+    else:
+        B, H, W = (int(v) for v in x)
+    _need(row_off, "row_off", torch.int64)
+    L = math.prod(query_grid(H, W))
+    if row_off.dim() != 1 or row_off.numel() != 4 * B * L + 1:
+        raise DaglError(f"{who}: row_off holds {row_off.numel()} offsets, expected 4*B*L+1 = {4 * B * L + 1}")
+    head_off = row_off[:B * L + 1]              # (a head's view: the shape checks of graph_search, head by head)
+    for h in range(4):
+        if step:
+            _need(b2p4[h], "b2p4[%d]" % h)
+            map_hw = _value_map(who, b2p4[h])[1:]
+            if tuple(map_hw) != (H, W) or b2p4[h].shape[0] != B:
+                raise DaglError(f"{who}: b2p4[{h}] is the value map of {b2p4[h].shape[0]} {map_hw[0]}x{map_hw[1]} images, "
+                                f"x holds {B} of {H}x{W}")
+        Bh, _, _, E, flags, radius, k = _graph_refresh_operands(who, wq_rows4[h], x_rows4[h], head_off, key, radius,
+                                                                tau4[h] if tau4 is not None else None, k, normalize, keep_all,
+                                                                block_rows, (H, W))
+        if Bh != B:
+            raise DaglError(f"{who}: head {h}'s feature rows hold {Bh} images, expected {B}")
+    if head_launches:
+        flags |= _lib.GRAPH_STAGE_SEARCH_HEAD_LAUNCHES
+    if want_graph:
+        max_row_edges = _graph_refresh_longest(who, row_off, E, max_row_edges)
+    elif max_row_edges is None:
+        raise DaglError(f"{who}: want_graph=False needs max_row_edges, the input's largest degree"
+                        + (" (reading it on the host is not available under stream capture)"
+                           if torch.cuda.is_current_stream_capturing() else " (the call itself reads nothing on the host)"))
+    max_row_edges = int(max_row_edges)
+    dev = wq_rows4[0].device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_stage_search_workspace_bytes", B, H, W, E, radius, propagate, explore,
+                                   0 if keep_all else k, 1 if want_graph else 0, 1 if step else 0)
+    if want_graph:
+        head, key_out, weight, score, cap = _graph_search_arrays(dev, 4 * B * L, E, radius, k, keep_all, propagate, explore)
+        status = head[-2:]
+    else:
+        head = key_out = weight = score = None
+        cap, status = 0, torch.empty(2, device=dev, dtype=torch.int64)
+    table = lambda seq: (C.c_void_p * 4)(*[t.data_ptr() for t in seq])
+    front = (_stream(), B, H, W, table(wq_rows4), table(x_rows4)) + ((table(b2p4),) if step else ())
+    graph = (row_off.data_ptr(), _ptr(key, E > 0), E, max_row_edges, radius, table(tau4) if tau4 is not None else None, k, float(scale),
+             flags)
+    back = (_ptr(head), _ptr(key_out, cap > 0), _ptr(weight, cap > 0), _ptr(score, cap > 0), cap, status.data_ptr(), a, nbytes, propagate,
+            explore, seed)
+    out = None
+    if step:
+        out = torch.empty_like(x)
+        check(lib.dagl_graph_stage_search_step(*front, *graph, x.data_ptr(), mix_w.data_ptr(), mix_b.data_ptr(), out.data_ptr(), *back), entry)
+    else:
+        check(lib.dagl_graph_stage_search(*front, *graph, *back), entry)
+    del buf
+    if not want_graph:
+        return out, None, status
+    return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges, adjacent=bool(propagate)), status
+
+
+@_on_device
+def graph_stage_search(wq_rows4, x_rows4, row_off, key, hw, *, radius: int = 1, tau4=None, k: int = 0, scale: float = 10.0,
+                       normalize: str = "reference", keep_all: bool = False, max_row_edges=None, workspace: "Workspace | None" = None,
+                       block_rows: bool = False, propagate=False, explore: int = 0, seed: int = 0, head_launches: bool = False) -> dict:
+    """``graph_search`` for the four heads of a ``CES`` stage in one row launch (``dagl_graph_stage_search``, csrc/graph_refresh.hip) ->
+    dict: ONE CSR over the 4*B*L head-major rows.  wq_rows4 / x_rows4 / tau4, (row_off, key) as ``graph_stage_step``; ``hw`` the map
+    (H, W).  Rows ``h*B*L .. (h+1)*B*L`` are, bit for bit, what ``graph_search`` returns for head h's operands, its slice of the input
+    graph and the same ``propagate``, ``explore``, ``seed`` (offsets continuing from head to head): the random keys are hashed from the
+    head-local row, so the four heads explore the same keys, and propagation never crosses an image, so never a head.  One host read;
+    not under stream capture; the overlong-row refusal of ``graph_search``.  ``head_launches``: the row kernel once per head (for
+    measurements; the same bits)."""
+    wq0 = wq_rows4[0] if isinstance(wq_rows4, (list, tuple)) and len(wq_rows4) == 4 else None
+    if not isinstance(wq0, torch.Tensor) or wq0.dim() != 3:
+        raise DaglError("graph_stage_search: wq_rows4 must be a sequence of four [B,L,196] tensors, one per head")
+    H, W = (int(v) for v in hw)
+    return _graph_stage_search("graph_stage_search", "dagl_graph_stage_search", wq_rows4, x_rows4, None, row_off, key,
+                               (wq0.shape[0], H, W), None, None, radius, tau4, k, scale, normalize, keep_all, max_row_edges, True, workspace,
+                               block_rows, propagate, explore, seed, head_launches)[1]
+
+
+@_on_device
+def graph_stage_search_step(wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, *, radius: int = 1, tau4=None, k: int = 0,
+                            scale: float = 10.0, normalize: str = "reference", keep_all: bool = False, max_row_edges=None,
+                            want_graph: bool = True, workspace: "Workspace | None" = None, block_rows: bool = False, propagate=False,
+                            explore: int = 0, seed: int = 0, head_launches: bool = False):
+    """``graph_search_step`` for the four heads of a ``CES`` stage and the stage's mix on the result (``dagl_graph_stage_search_step``,
+    csrc/graph_refresh.hip) -> (out [B,64,H,W], dict | None, status): the arguments of ``graph_stage_step`` plus ``propagate``,
+    ``explore`` and ``seed``.  ONE row launch covers the 4*B*L rows.  The dict is ``graph_stage_search``'s, bit for bit; ``out`` is
+    ``ces_stage_fold_mix`` of the heads' aggregated rows, each ``graph_search_step``'s bits for its head -- the same with ``want_graph``
+    True or False and on every call.  An empty graph with ``explore`` > 0 is populated; with ``explore`` = 0 it gives ``mix_b + x``.
+    ``status``: device int64[2] (the overlong rows and their grid neighbours summed over the heads, the largest candidate count).
+
+    Host reads, ``max_row_edges``, the overlong-row refusal and capture: as ``graph_search_step`` -- one host read with
+    ``want_graph=True``; none with ``want_graph=False``, which needs ``max_row_edges`` and can be captured (``seed`` is a launch
+    argument)."""
+    if b2p4 is None:
+        raise DaglError("graph_stage_search_step: b2p4 must be a sequence of four tensors, one per head")
+    return _graph_stage_search("graph_stage_search_step", "dagl_graph_stage_search_step", wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w,
+                               mix_b, radius, tau4, k, scale, normalize, keep_all, max_row_edges, want_graph, workspace, block_rows,
+                               propagate, explore, seed, head_launches)
+
+
 @_on_device
 def graph_attend_backward(d_weight, wq_rows, x_rows, row_off, key, score, weight, tau=None, scale: float = 10.0,
                           normalize: str = "reference", transposed=None, need_wq: bool = True, need_x: bool = True, need_tau: bool = True,

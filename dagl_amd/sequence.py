@@ -1,6 +1,7 @@
 """``SequenceState`` -- the patch graphs a ``CES`` carries from frame to frame: one ``PatchGraph`` per stage over the stage's four heads.
 
-``CES.forward_with_graphs`` / ``RR.forward_with_graphs`` return one for the key frame, ``step_graphs`` takes it and returns the next.  Plain
+``CES.forward_with_graphs`` / ``RR.forward_with_graphs`` return one for the key frame, ``step_graphs`` / ``search_graphs`` take it and
+return the next; ``SequenceState.start`` is the trivial state ``build_graphs`` searches from.  Plain
 bookkeeping over ``PatchGraph`` (graph.py): it works on CPU tensors.
 """
 from __future__ import annotations
@@ -43,6 +44,14 @@ class SequenceState:
         state = cls(PatchGraph.cat(graphs[s * HEADS:(s + 1) * HEADS]) for s in range(STAGES))
         state._heads = {(s, h): graphs[s * HEADS + h] for s in range(STAGES) for h in range(HEADS)}
         return state
+
+    @classmethod
+    def start(cls, B: int, H: int, W: int, device=None, mode: str = "adaptive") -> "SequenceState":
+        """The state a search starts from (``CES.build_graphs``): twelve trivial graphs over ``B`` images of ``H x W`` -- one edge per
+        query at the query's own position, ``CE.build_graph``'s start (``graph.trivial_graph``).  The heads share the arrays."""
+        from .graph import trivial_graph
+        g = trivial_graph(B, H, W, device, mode)
+        return cls.from_heads([g] * (STAGES * HEADS))
 
     def head(self, s: int, h: int) -> PatchGraph:
         """The graph of head ``h`` (0..3) of stage ``s`` (0..2): ``stages[s].images(h * B, (h + 1) * B)``, kept on the object."""

@@ -170,7 +170,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * the workspace layout carries the top-k policy words; 403: dagl_ce_core_wide_forward / _backward; 404:
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
- * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*, dagl_graph_search*,
+ * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*, dagl_graph_search*, dagl_graph_stage_search*,
  * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
  * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan, dagl_ce_prologue16_debug*, dagl_project16_plan and dagl_ce_project16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
@@ -591,6 +591,45 @@ int    dagl_graph_stage_step(void* stream, int B, int H, int W, const float* con
                              const float* x, const float* mix_w, const float* mix_b, float* out,
                              int64_t* row_off_out /* [4 B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
                              int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
+
+/* ---- the search step of a whole CES stage: csrc/graph_refresh.hip (detected by symbol) ---------------------------------------------------
+ * dagl_graph_stage_search / dagl_graph_stage_search_step: dagl_graph_search / dagl_graph_search_step for the four heads of a stage, on
+ * the operands of dagl_graph_stage_step (HOST tables of four device pointers, ONE CSR over the 4 B L head-major rows, x, mix_w, mix_b,
+ * out [B,64,H,W]) plus propagate, explore, seed.  Rows h B L .. (h + 1) B L of the graph outputs hold, bit for bit, what
+ * dagl_graph_search / dagl_graph_search_step write when called with head h's operands, its slice of the input graph with rebased
+ * offsets and the same propagate, explore and seed; the offsets continue from head to head.  out = dagl_ces_stage_fold_mix of the four
+ * heads' aggregated rows, each row dagl_graph_search_step's bits -- the same with or without the graph outputs, in the wavefront and the
+ * block form, and on every call.  Two consequences:
+ *   - the random keys of row (h B + b) L + i come from the hash of the HEAD-LOCAL row r = b L + i of (c) above, not of the CSR row: the
+ *     four heads explore the same keys, as they do head by head with one seed;
+ *   - propagation never crosses an image, so it never crosses a head: the 4 B images of the CSR are images to rule (b).
+ * status_out[0] is the sum over the heads, status_out[1] the maximum.  Limits, error codes and the capacity rule are
+ * dagl_graph_search's with 4 B in the place of B (capacity_edges >= (1 + 4 propagate) total_edges wd^2 + 4 B L explore, or 4 B L k).
+ * total_edges = 0 with explore > 0 populates the graph; with explore = 0 it gives an empty graph and out = mix_b + x.  propagate =
+ * explore = 0 is allowed: the plain entries' bits per head.  tau4 as dagl_graph_stage_step (all or none).  The step's four graph outputs
+ * may ALL be NULL (the output alone).  Workspace: dagl_graph_stage_search_workspace_bytes (k: 0 with KEEP_ALL) -- the staging arrays
+ * hold 4 B L k entries under a rank cut (row r at r k), else (1 + 4 propagate) total_edges wd^2 + 4 B L explore, row r at the prefix sum
+ * of the rows' bounds over the WHOLE CSR (a head's rows can need 5 E_h wd^2 entries: no per-head slice of the array holds them).
+ * Launches: ONE row kernel over the 4 B L rows (the heads' pointers travel by value in its arguments; a wavefront per row when the row
+ * bound is <= 128), (graph outputs) one scan and one ordered copy, (step) the fold + mix.  DAGL_GRAPH_STAGE_SEARCH_HEAD_LAUNCHES runs
+ * that row kernel once per head instead, for measurements: the same bits.  Every argument is checked before the first launch; nothing is
+ * read on the host, so a call without graph outputs can be captured: the CALLER reads row_off_out[4 B L] and status_out. */
+#define DAGL_GRAPH_STAGE_SEARCH_HEAD_LAUNCHES 0x8
+size_t dagl_graph_stage_search_workspace_bytes(int B, int H, int W, int64_t total_edges, int radius, int propagate, int explore, int k,
+                                               int want_graph, int aggregate);
+int    dagl_graph_stage_search(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                               const int64_t* row_off, const int32_t* key, int64_t total_edges, int max_row_edges, int radius,
+                               const float* const* tau4 /* NULL: no margin */, int k /* 0: no rank cut */, float scale, int flags,
+                               int64_t* row_off_out /* [4 B L + 1] */, int32_t* key_out, float* weight_out, float* score_out,
+                               int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes, int propagate,
+                               int explore, uint32_t seed);
+int    dagl_graph_stage_search_step(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                                    const float* const* b2p4, const int64_t* row_off, const int32_t* key, int64_t total_edges,
+                                    int max_row_edges, int radius, const float* const* tau4 /* NULL: no margin */,
+                                    int k /* 0: no rank cut */, float scale, int flags, const float* x, const float* mix_w,
+                                    const float* mix_b, float* out, int64_t* row_off_out /* [4 B L + 1] or NULL */, int32_t* key_out,
+                                    float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out /* [2] */,
+                                    void* workspace, size_t ws_bytes, int propagate, int explore, uint32_t seed);
 
 /* ---- stage profile: hipEvents recorded at the stage boundaries on the caller's stream ---------
  * The benchmark times its steps with these (no synchronisation is added to the timed region;

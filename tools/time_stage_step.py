@@ -8,6 +8,14 @@ Per case, ms per call (median of event-timed windows after warm-up calls, lowest
 convolution); the fused step (``ops.graph_stage_step``) with and without the graphs; the four heads' features alone; and the fold + mix
 kernel (``ops.ces_stage_fold_mix``) against ``fold`` + ``stage_mix`` -- the two launches it replaces: ``ops.fold_normalize`` on the four
 heads as a batch, ``ops.ces_stage_mix`` on the stored concat map -- on the same aggregated rows.
+
+    python tools/time_stage_step.py --search [1024 1024]    # the search step of a stage (``CES.search_graphs``), the same two cases
+
+One stage, ``features="split16"``, radius 1, ``propagate``, ``explore=8``: the fused search step (``ops.graph_stage_search_step``) against
+head by head (``step_graphs(..., fused=False, propagate=True, explore=8)``), with and without the graphs; its ONE row launch against the
+same kernel launched once per head (``head_launches``), on stored features; ``iters=3`` against three ``iters=1`` calls; and, on the whole
+module, ``CES.build_graphs`` (4 iterations from the trivial start) against ``CES.forward_with_graphs``.  Noise-like maps carry no spatial
+coherence: the times say what a search step costs, not what it finds.
 """
 import os
 import sys
@@ -35,10 +43,9 @@ def _events(fn, warmup=3, repeats=7, inner=10):
     return times[len(times) // 2], times[0], times[-1]
 
 
-def stage_leg(H, W, big):
-    from dagl_amd import ops
+def _case(H, W, big):
+    """The module and the two frames of a case -> (name, mode, ces, x, x2)."""
     from dagl_amd.net import CES
-    from dagl_amd.sequence import SequenceState
     from dagl_amd.synth import make_ce_params, make_features
     dev = torch.device("cuda:0")
     name, mode, k, variant, gain = ("adaptive AND top-16 (sparse, gain 1.7)", "adaptive_topk", 16, "sparse", 1.7) if big else \
@@ -51,8 +58,81 @@ def stage_leg(H, W, big):
         hd.select_mode, hd.select_k = mode, k
     ces = ces.to(dev).eval()
     x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
-    x2 = torch.roll(x, (1, 1), (2, 3))
-    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    return name, mode, ces, x, torch.roll(x, (1, 1), (2, 3))
+
+
+def _fmt(t):
+    return f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+
+
+def search_leg(H, W, big):
+    from dagl_amd import ops
+    from dagl_amd.sequence import SequenceState
+    name, mode, ces, x, x2 = _case(H, W, big)
+    feat, fmt = "split16", _fmt
+    search = dict(propagate=True, explore=8, seed=0)
+    with torch.no_grad():
+        heads, mix = ces._stage_modules(1)
+        graphs = [hd.graph(x) for hd in heads]
+        state = SequenceState.from_heads(graphs * 3)          # the state of stage 1 alone is timed
+        for g in state.stages:
+            g.validate().max_degree()
+        for g in graphs:
+            g.max_degree()
+        plan_u = ces._plan_step(x2, state, 1, feat, True, False, search)[1]
+        plan_f = ces._plan_step(x2, state, 1, feat, True, True, search, what="CES.search_graphs")[1]
+        # 1. the fused search step against head by head (step_graphs(..., fused=False, propagate=True, explore=8))
+        by_head = _events(lambda: ces._step_stage(1, x2, state, plan_u, feat, True, search))
+        by_head_alone = _events(lambda: ces._step_stage(1, x2, state, plan_u, feat, False, search))
+        fused = _events(lambda: ces._search_stage(1, x2, state, plan_f, 1, feat, True, search))
+        alone = _events(lambda: ces._search_stage(1, x2, state, plan_f, 1, feat, False, search))
+        o_u, g_u = ces._step_stage(1, x2, state, plan_u, feat, True, search)
+        o_f, g_f = ces._search_stage(1, x2, state, plan_f, 1, feat, True, search)
+        same = all(torch.equal(getattr(g_u, n), getattr(g_f, n)) for n in ("row_off", "key", "weight", "score"))
+        gap = float((o_u - o_f).abs().max() / o_u.abs().max())
+        # 2. the ONE row launch against the same kernel once per head, on stored features, without the graphs (no host read)
+        radius, k_eff, margin, longest = plan_f[1]
+        feats = [hd._graph_features(x2, margin, True, False) for hd in heads]
+        stage = state.stages[0]
+        ws = ops.Workspace()
+        args = ([f[0].contiguous() for f in feats], [f[1].contiguous() for f in feats], [f[3].contiguous() for f in feats], stage.row_off,
+                stage.key, x2.contiguous(), mix.weight.detach().contiguous(), mix.bias.detach().contiguous())
+        kw = dict(radius=radius, tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff, max_row_edges=longest,
+                  want_graph=False, workspace=ws, propagate=True, explore=8, seed=0)
+        one = _events(lambda: ops.graph_stage_search_step(*args, **kw), inner=20)
+        four = _events(lambda: ops.graph_stage_search_step(*args, head_launches=True, **kw), inner=20)
+        # 3. three iterations on features computed once against three calls
+        it3 = _events(lambda: ces._search_stage(1, x2, state, plan_f, 3, feat, True, search))
+
+        def three_calls():
+            cur = state
+            for i in range(3):
+                _, g = ces._search_stage(1, x2, cur, plan_f, 1, feat, True, dict(search, seed=i))
+                cur = SequenceState([g, state.stages[1], state.stages[2]])
+
+        calls3 = _events(three_calls)
+        # 4. a key frame of the whole module: four search iterations from the trivial start against the L N scans
+        built = _events(lambda: ces.build_graphs(x2, iters=4, features=feat), inner=3)
+        keyframe = _events(lambda: ces.forward_with_graphs(x2), inner=3)
+    bound = ops.graph_search_row_bound(longest, radius, True, 8)
+    print(f"[1,64,{H},{W}] {name}, search step (radius 1, propagate, explore 8, split16): stage graphs {stage.n_edges} -> {g_f.n_edges} edges "
+          f"over 4 heads, largest degree {longest}, row bound {bound} ({'a wavefront' if bound <= 128 else 'a block'} per row)\n"
+          f"    search step head by head (step_graphs fused=False) {fmt(by_head)}; without the graphs {fmt(by_head_alone)}\n"
+          f"    search step fused {fmt(fused)} = {fused[0] / by_head[0]:.2f} of head by head; without the graphs {fmt(alone)} = "
+          f"{alone[0] / by_head_alone[0]:.2f} of head by head; fused graphs equal head by head: {same}; outputs differ by {gap:.1e} of "
+          f"the largest\n"
+          f"    ops.graph_stage_search_step on stored features, no graphs: one row launch {fmt(one)}, the same kernel once per head "
+          f"{fmt(four)}: {one[0] / four[0]:.2f}\n"
+          f"    iters=3 {fmt(it3)} against three iters=1 calls {fmt(calls3)}: {it3[0] / calls3[0]:.2f}\n"
+          f"    whole CES: build_graphs(iters=4) {fmt(built)} against forward_with_graphs {fmt(keyframe)}: {built[0] / keyframe[0]:.2f}",
+          flush=True)
+
+
+def stage_leg(H, W, big):
+    from dagl_amd import ops
+    from dagl_amd.sequence import SequenceState
+    name, mode, ces, x, x2 = _case(H, W, big)
+    dev, fmt = x.device, _fmt
     feat = "split16"
     with torch.no_grad():
         heads, mix = ces._stage_modules(1)
@@ -97,9 +177,11 @@ def stage_leg(H, W, big):
 
 
 def main():
-    if len(sys.argv) > 2:
-        return stage_leg(int(sys.argv[1]), int(sys.argv[2]), True)
-    return stage_leg(256, 256, False)
+    argv = [a for a in sys.argv[1:] if a != "--search"]
+    leg = search_leg if "--search" in sys.argv[1:] else stage_leg
+    if len(argv) > 1:
+        return leg(int(argv[0]), int(argv[1]), True)
+    return leg(256, 256, False)
 
 
 if __name__ == "__main__":
