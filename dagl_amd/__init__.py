@@ -4,6 +4,6 @@
 ``include/dagl_ce.h`` stage by stage; ``dagl_amd.PatchGraph`` is what ``CE.graph`` returns; ``dagl_amd.build.build()`` compiles the HIP library in-tree.
 """
 from ._lib import DaglError  # noqa: F401
-from .graph import PatchGraph  # noqa: F401
+from .graph import FixedGraph, PatchGraph  # noqa: F401
 
 __version__ = "0.1.0"

@@ -99,6 +99,9 @@ SIGNATURES = {
                           + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
     "dagl_graph_search_step": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _i, _i, _vp, _i, C.c_float, _i] + [_vp] * 5
                                + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),
+    "dagl_graph_step_fixed_workspace_bytes": (_sz, [_i] * 4),
+    "dagl_graph_step_fixed": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [_i, _i, _vp, _i, C.c_float, _i, _i, _i, C.c_uint32] + [_vp] * 5
+                              + [_i, _vp, _vp, _sz]),
     "dagl_ces_stage_fold_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
     "dagl_ces_stage_mix": (_i, [_vp, _i, _i, _i] + [_vp] * 5),
     "dagl_graph_stage_step_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64, _i, _i]),

@@ -669,7 +669,10 @@ class CE(nn.Module):
     def _check_given_graph(self, b: torch.Tensor, graph, what: str):
         """The refusals of a call on a given graph (``apply_graph``, ``attend_graph``, ``forward_on_graph``), raised before any launch;
         then ``graph.validate()`` (one host read, once per graph; refused under capture)."""
-        from .graph import PatchGraph
+        from .graph import FixedGraph, PatchGraph
+        if isinstance(graph, FixedGraph):
+            raise DaglError(f"CE.{what}: a FixedGraph serves refresh_graph and step_graph; this route walks CSR edges: pass "
+                            "graph.to_csr()")
         if b.dim() != 4 or b.shape[1] != self.in_channels:
             raise DaglError(f"CE.{what}: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
         if not b.is_cuda:
@@ -901,7 +904,14 @@ class CE(nn.Module):
         dtype, shape), a stream under capture (the edge count is read on the host), ``select_k < 1`` in the top-k modes, ``radius``
         outside 0..8, and a graph whose largest degree times ``(2 radius + 1)^2`` exceeds ``ops.graph_refresh_max_candidates()``.  The
         largest degree is read once per graph (kept on the object, as ``validate``'s verdict).  The module's state (packed weights,
-        top-k policy, range verdicts, ``_train_dense``) is untouched: the call has a workspace of its own."""
+        top-k policy, range verdicts, ``_train_dense``) is untouched: the call has a workspace of its own.
+
+        A ``FixedGraph`` (``graph.to_fixed()``) gives a ``FixedGraph``: the same rows bit for bit (``result.to_csr()``), from one row
+        launch that reads NOTHING on the host -- no ``validate()``, no ``max_degree()``, no edge count -- and is served under stream
+        capture.  See ``step_graph``."""
+        from .graph import FixedGraph
+        if isinstance(graph, FixedGraph):
+            return self._step_fixed(b, graph, "refresh_graph", radius, margin, normalize, features, propagate, explore, seed, False)[1]
         radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "refresh_graph", radius, margin, normalize, features,
                                                                  propagate=propagate, explore=explore, seed=seed)
         B, _, H, W = b.shape
@@ -994,7 +1004,21 @@ class CE(nn.Module):
         Always under ``torch.no_grad()``, ``out.requires_grad`` is False: gradients are ``forward_on_graph``'s job on the returned graph.
         Arguments, selection, the ``features="split16"`` range contract (both results NaN-filled, never wrong numbers) and refusals are
         ``refresh_graph``'s, all raised before any launch.  The module's state (packed weights, top-k policy, range verdicts,
-        ``_train_dense``) is untouched: the call has a workspace of its own."""
+        ``_train_dense``) is untouched: the call has a workspace of its own.
+
+        On a ``FixedGraph`` (``graph.to_fixed()``: ``width`` slots per row) the call returns ``(out, FixedGraph | None)`` from ONE row
+        launch and the fold (``ops.graph_step_fixed``): ``out`` and the rows of the new graph carry the bits of the call on the CSR
+        (``new.to_csr()``).  The output width is ``k`` in the rank-cut modes ("topk", "adaptive_topk") and ``graph.width`` in
+        "adaptive".  Nothing is read on the host -- no ``validate()``, no ``max_degree()``, no edge count --, so the call is served
+        under stream capture WITH ``want_graph=True``: capture ``out, g_new = ce.step_graph(x, g); g.copy_(g_new)`` once and replay it
+        per frame.  In "adaptive" mode a row that keeps more than ``graph.width`` entries comes out EMPTY (never truncated); such rows
+        are counted on the device, not reported: choose the width with room, or use a rank-cut mode, where no row can overflow.
+        Refused before any launch: a graph that does not fit the input, and ``ops.graph_search_row_bound(graph.width, radius,
+        propagate, explore)`` above ``ops.graph_refresh_max_candidates()``."""
+        from .graph import FixedGraph
+        if isinstance(graph, FixedGraph):
+            out, new = self._step_fixed(b, graph, "step_graph", radius, margin, normalize, features, propagate, explore, seed, True)
+            return out, (new if want_graph else None)
         want_graph = bool(want_graph)
         radius, k_eff, margin, longest = self._refresh_arguments(b, graph, "step_graph", radius, margin, normalize, features,
                                                                  host_read=want_graph, propagate=propagate, explore=explore, seed=seed)
@@ -1015,6 +1039,72 @@ class CE(nn.Module):
             if b.dtype != torch.float32:
                 out = out.to(b.dtype)
             return out, (self._refreshed(graph, csr, poisoned, k_eff) if want_graph else None)
+
+    def _fixed_arguments(self, b: torch.Tensor, graph, what: str, radius, margin, normalize: str, features: str, propagate=False,
+                         explore=0, seed=0):
+        """The refusals of ``refresh_graph`` / ``step_graph`` on a ``FixedGraph``, raised before any launch -> (radius, k_eff, margin,
+        width_out, propagate, explore, seed).  None of them reads the graph's arrays: no host read, served under capture."""
+        propagate, explore, seed = ops._graph_search_operands(f"CE.{what}", propagate, explore, seed)
+        if b.dim() != 4 or b.shape[1] != self.in_channels:
+            raise DaglError(f"CE.{what}: expected [B,{self.in_channels},H,W], got {tuple(b.shape)}")
+        if not b.is_cuda:
+            raise DaglError(f"CE.{what}: input must be on the GPU; dagl_amd has no CPU path")
+        if self._generic:
+            raise DaglError(f"CE.{what}: a graph step serves the default patch geometry (ksize 7, stride_1 4, stride_2 1, "
+                            f"inter_channels 16) only; this module was built with ({self.ksize}, {self.stride_1}, {self.stride_2}, "
+                            f"{self.inter_channels}), which is out of its scope")
+        B, _, H, W = b.shape
+        if (graph.B, graph.H, graph.W) != (B, H, W):
+            raise DaglError(f"CE.{what}: the graph was built for B={graph.B} H={graph.H} W={graph.W}, the input is B={B} H={H} W={W}")
+        if graph.device != b.device:
+            raise DaglError(f"CE.{what}: the graph lives on {graph.device}, the input on {b.device} (FixedGraph.to moves a graph)")
+        if b.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise DaglError(f"CE.{what}: unsupported dtype {b.dtype}")
+        if normalize not in ("reference", "edges"):
+            raise DaglError(f"CE.{what}: normalize={normalize!r}, expected 'reference' or 'edges'")
+        if features not in ("fp32", "split16"):
+            raise DaglError(f"CE.{what}: features={features!r}, expected 'fp32' or 'split16'")
+        if self.select_mode not in ("adaptive", "topk", "adaptive_topk"):
+            raise DaglError(f"CE.select_mode {self.select_mode!r}: expected 'adaptive', 'topk' or 'adaptive_topk'")
+        radius = int(radius)
+        if not 0 <= radius <= 8:
+            raise DaglError(f"CE.{what}: radius={radius} outside [0, 8]")
+        k_eff = 0
+        if self.select_mode != "adaptive":
+            if int(self.select_k) < 1:
+                raise DaglError(f"CE: select_k={self.select_k} < 1")
+            k_eff = min(int(self.select_k), H * W)
+        margin = self.select_mode != "topk" if margin is None else bool(margin)
+        bound, cap = ops.graph_search_row_bound(graph.width, radius, propagate, explore), ops.graph_refresh_max_candidates()
+        if bound > cap:
+            err = DaglError(f"CE.{what}: a row of {graph.width} slots at radius {radius} with propagate={bool(propagate)} and "
+                            f"explore={explore} may expand into {bound} candidates, more than {cap}")
+            err.code = ERR_UNSUPPORTED
+            raise err
+        return radius, k_eff, margin, (k_eff if k_eff > 0 else graph.width), propagate, explore, seed
+
+    def _step_fixed(self, b: torch.Tensor, graph, what: str, radius, margin, normalize: str, features: str, propagate, explore, seed,
+                    apply: bool):
+        """``refresh_graph`` / ``step_graph`` (``apply``) on a ``FixedGraph`` -> (out | None, FixedGraph): ``ops.graph_step_fixed`` on
+        the module's features."""
+        from .graph import FixedGraph
+        radius, k_eff, margin, width_out, propagate, explore, seed = self._fixed_arguments(b, graph, what, radius, margin, normalize,
+                                                                                           features, propagate, explore, seed)
+        B, _, H, W = b.shape
+        with torch.no_grad():
+            wq_rows, x_rows, tau, b2p, poisoned = self._graph_features(b.detach(), margin, features == "split16", False)
+            out, arrays, _status = ops.graph_step_fixed(wq_rows.contiguous(), x_rows.contiguous(), b2p.contiguous() if apply else None,
+                                                        graph.key, graph.deg, width_out=width_out, radius=radius,
+                                                        tau=tau.contiguous() if tau is not None else None, k=k_eff,
+                                                        scale=float(self.softmax_scale), normalize=normalize, propagate=bool(propagate),
+                                                        explore=explore, seed=seed, workspace=self._ws_step, hw=(H, W))
+            new = FixedGraph._like(graph, arrays["key"], poisoned(arrays["weight"]), poisoned(arrays["score"]), arrays["deg"])
+            new.mode, new.k = self.select_mode, k_eff
+            if apply:
+                out = poisoned(out)
+                if b.dtype != torch.float32:
+                    out = out.to(b.dtype)
+            return out, new
 
     def build_graph(self, b: torch.Tensor, *, iters: int = 4, radius: int = 1, explore: int = 8, seed: int = 0, features: str = "fp32",
                     normalize: str = "reference"):

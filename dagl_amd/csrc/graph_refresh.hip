@@ -47,6 +47,13 @@
 // graph_search_compact_kernel and launch_stage_fold_mix.  The random keys are hashed from the head-local row: the four heads explore
 // the same keys, as four calls with one seed do.
 //
+// The fixed-width entry, dagl_graph_step_fixed, is the step (or, without a value map, the refresh; with propagate / explore the search
+// forms) on a graph held as `width` slots per row and a degree per row: rf_row's FIXED flavour reads row r's edges at r width_in
+// (deg_in[r] of them, clamped to [0, width_in]) and writes the kept entries straight to r width_out, the degree, and (-1, 0, 0) into the
+// slots behind them -- every exit writes the whole row, the outputs are never cleared.  No staging, no scan, no copy: the sizes are
+// known before the launch, nothing is read on the host and the call with its graph output can be captured.  A row that keeps more
+// than width_out entries (possible only without a rank cut) comes out EMPTY and is counted in status[0].
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -78,6 +85,19 @@ struct RsArgs {
     int k_region;                             // > 0: row r stages at r k_region (it keeps at most k);  0: at rs_region_start's prefix sum
     long long staged;                         // entries of each staging array
 };
+
+// what the FIXED flavour of the row body adds (dagl_graph_step_fixed).  The graph comes as width_in slots per row and a degree per row:
+// GtArgs::key is the slot array, GtArgs::E = rows width_in, GtArgs::row_off is not used.  It leaves as width_out slots per row:
+// RfArgs::st_key / st_score / st_weight are the OUTPUT arrays [rows, width_out] and RfArgs::deg the output degrees
+struct RxArgs {
+    const int32_t* deg_in;                    // [B L], read clamped to [0, width_in]
+    int width_in, width_out;
+};
+
+__device__ __forceinline__ int rx_deg(const RxArgs& fx, int row) {
+    const int d = fx.deg_in[row];
+    return d < 0 ? 0 : (d > fx.width_in ? fx.width_in : d);
+}
 
 // lowbias32: the counter hash of the random candidates
 __device__ __forceinline__ unsigned rs_hash(unsigned x) {
@@ -174,6 +194,17 @@ __device__ __forceinline__ void rf_zero_row(float* agg, int row) {
     for (int c = threadIdx.x; c < GA_C4; c += T) o[c] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+// the slots from..width_out-1 of a FIXED output row: key -1, score 0, weight 0
+template <int T>
+__device__ __forceinline__ void rx_fill(const RfArgs& f, const RxArgs& fx, int row, int from) {
+    const long long base = (long long)row * fx.width_out;
+    for (int i = from + (int)threadIdx.x; i < fx.width_out; i += T) {
+        f.st_key[base + i] = -1;
+        f.st_score[base + i] = 0.f;
+        f.st_weight[base + i] = 0.f;
+    }
+}
+
 // the row body of the kernels below.  AGG (dagl_graph_step): the row's weighted sum of value patches goes to v.out [B L, 784] as well,
 // and the graph outputs may be absent (f.st_key null: no degree, no staging writes).  SEARCH (dagl_graph_search*): step 1 takes the
 // row's candidates from up to three sources -- (a) the windows around its own edges, as without SEARCH; (b) sr.propagate: the windows
@@ -183,10 +214,13 @@ __device__ __forceinline__ void rf_zero_row(float* agg, int row) {
 // (lowbias32(lowbias32(row ^ seed) + t) N) >> 32 of the row's image, no window -- and the row stages at rs_region_start; every step
 // after the expansion is the same code.  `row` is the row of the CSR (row_off, deg, the staging region, v.out); `lrow` the row of the
 // head's own operands (a.wq, a.x, a.tau, the value map, the hash of the random keys): the same row but in the stage kernel below, where
-// the CSR holds four heads' rows and lrow = row - h B L
-template <int T, int CAP, bool AGG, bool SEARCH = false>
+// the CSR holds four heads' rows and lrow = row - h B L.  FIXED (dagl_graph_step_fixed; RxArgs above): the input row is the slots
+// row width_in .. + deg_in[row] (the adjacent queries' rows likewise), the kept entries go straight to row width_out + pos of the
+// output arrays with the filler behind them, and every exit writes degree 0 and a whole filler row; a row that keeps more than
+// width_out entries leaves empty, counted in status[0].  No staging region: rs_region_start, sr.staged and the room test are not used
+template <int T, int CAP, bool AGG, bool SEARCH = false, bool FIXED = false>
 __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const GaArgs& v, const int row, const int lrow,
-                                       const RsArgs& sr = RsArgs{}) {
+                                       const RsArgs& sr = RsArgs{}, const RxArgs& fx = RxArgs{}) {
     __shared__ long long s_of[CAP];           // two int arrays (below); AGG: at the end the float4 offset of each kept entry's value patch
                                               // in the map, compacted -- no array of its own: at 2048 candidates 16 KiB more LDS halve the
                                               // blocks per CU, and the row body lives on them
@@ -197,9 +231,10 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     __shared__ double sh_d[T / 64];
     int* const s_sort = reinterpret_cast<int*>(s_of);     // the expanded candidates, sorted; then the order word of a passing candidate
     int* const s_key = s_sort + CAP;                      // the distinct candidates, ascending
-    const bool graph_out = !AGG || f.st_key != nullptr;
+    const bool graph_out = FIXED || !AGG || f.st_key != nullptr;
     const int t = threadIdx.x;
-    const long long lo = gt_clamp(a.row_off[row], a.E), hi = gt_clamp(a.row_off[row + 1], a.E);
+    const long long lo = FIXED ? (long long)row * fx.width_in : gt_clamp(a.row_off[row], a.E);
+    const long long hi = FIXED ? lo + rx_deg(fx, row) : gt_clamp(a.row_off[row + 1], a.E);
     const long long deg_in = hi - lo;
     const int wd = 2 * f.radius + 1, w2 = wd * wd;
     // SEARCH: the sources' first edges and the running sums of their degrees (0 the row itself, 1-4 the adjacent queries; a source that
@@ -215,8 +250,8 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
                 const int dqy = s == 3 ? -1 : (s == 4 ? 1 : 0), dqx = s == 1 ? -1 : (s == 2 ? 1 : 0);
                 if ((unsigned)(qy + dqy) < (unsigned)Lh && (unsigned)(qx + dqx) < (unsigned)sr.Lw) {
                     const int r2 = row + dqy * sr.Lw + dqx;                      // (the same image: in [0, n_rows))
-                    src_lo[s] = gt_clamp(a.row_off[r2], a.E);
-                    const long long d = gt_clamp(a.row_off[r2 + 1], a.E) - src_lo[s];
+                    src_lo[s] = FIXED ? (long long)r2 * fx.width_in : gt_clamp(a.row_off[r2], a.E);
+                    const long long d = FIXED ? (long long)rx_deg(fx, r2) : gt_clamp(a.row_off[r2 + 1], a.E) - src_lo[s];
                     dg[s] = d > 0 ? d : 0;
                 }
             }
@@ -229,14 +264,15 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
             sum += dg[s];
         }
         const long long raw_ll = overlong ? 0 : sum * w2 + sr.explore;           // (<= 5 max_row_edges w2 + 256: no overflow)
-        stage_at = graph_out ? rs_region_start(a.row_off, a.n_rows, a.E, w2, sr, row) : 0;
+        stage_at = !FIXED && graph_out ? rs_region_start(a.row_off, a.n_rows, a.E, w2, sr, row) : 0;
         const long long region = sr.k_region > 0 ? sr.k_region : raw_ll;
-        const bool room = !graph_out || (stage_at >= 0 && stage_at + region <= sr.staged);
+        const bool room = FIXED || !graph_out || (stage_at >= 0 && stage_at + region <= sr.staged);
         if (overlong || raw_ll <= 0 || raw_ll > CAP || !room) {                  // (the same in every thread)
             if (t == 0) {
                 if (graph_out) f.deg[row] = 0;
                 if (overlong || raw_ll > CAP) atomicAdd(f.status, 1ull);
             }
+            if (FIXED) rx_fill<T>(f, fx, row, 0);
             if (AGG) rf_zero_row<T>(v.out, row);
             return;
         }
@@ -252,6 +288,7 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
             if (graph_out) f.deg[row] = 0;
             if (deg_in > 0) atomicAdd(f.status, 1ull);
         }
+        if (FIXED) rx_fill<T>(f, fx, row, 0);
         if (AGG) rf_zero_row<T>(v.out, row);
         return;
     }
@@ -379,8 +416,18 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     for (int c = c0; c < c1; ++c) cnt += (s_flag[c] >> 2) & 1;
     int kept;
     pos = rf_scan<T>(cnt, sh_i, kept);
+    if (FIXED && kept > fx.width_out) {                          // (the same in every thread) more than the output row holds: empty, counted
+        if (t == 0) {
+            f.deg[row] = 0;
+            atomicAdd(f.status, 1ull);
+        }
+        rx_fill<T>(f, fx, row, 0);
+        if (AGG) rf_zero_row<T>(v.out, row);
+        return;
+    }
     if (t == 0 && graph_out) f.deg[row] = kept;
     if (kept == 0) {                                             // (the same in every thread)
+        if (FIXED) rx_fill<T>(f, fx, row, 0);
         if (AGG) rf_zero_row<T>(v.out, row);
         return;
     }
@@ -400,8 +447,8 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
     sum = rf_sum<T>(sum, sh_d);
     if (off_graph) sum += (double)(a.N - kept) * exp(-(double)M);
     // 7. the kept entries, ascending keys, to the front of the row's staging region (kept <= n <= raw = its size; SEARCH with a rank
-    //    cut: kept <= k = its size)
-    const long long base = SEARCH ? stage_at : lo * w2;
+    //    cut: kept <= k = its size).  FIXED: to the front of the row's own width_out slots (kept <= width_out), the filler behind them
+    const long long base = FIXED ? (long long)row * fx.width_out : (SEARCH ? stage_at : lo * w2);
     //    AGG: a thread also keeps the weight and the patch offset of its kept entries (at most PER = CAP / T >= pr of them) in registers
     constexpr int PER = CAP / T;
     float my_w[AGG ? PER : 1];
@@ -426,6 +473,7 @@ __device__ __forceinline__ void rf_row(const GtArgs& a, const RfArgs& f, const G
         }
         ++pos;
     }
+    if (FIXED) rx_fill<T>(f, fx, row, kept);
     if (!AGG) return;
     // 8. the kept entries' weights and patch offsets to the LDS in compacted (ascending-key) order, over the scores and the two int
     //    arrays -- every thread has read its own entries of those above: a barrier, the stores (pos0 .. < kept <= n <= CAP), a barrier
@@ -470,6 +518,28 @@ __global__ __launch_bounds__(T) void graph_search_rows_kernel(GtArgs a, RfArgs f
 template <int T, int CAP>
 __global__ __launch_bounds__(T) void graph_search_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr) {
     rf_row<T, CAP, true, true>(a, f, v, blockIdx.x, blockIdx.x, sr);
+}
+
+// dagl_graph_step_fixed's: the FIXED flavour of the four bodies above (kernels of their own: those keep their arguments and their
+// device code)
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_fixed_rows_kernel(GtArgs a, RfArgs f, RxArgs fx) {
+    rf_row<T, CAP, false, false, true>(a, f, GaArgs{}, blockIdx.x, blockIdx.x, RsArgs{}, fx);
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_fixed_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RxArgs fx) {
+    rf_row<T, CAP, true, false, true>(a, f, v, blockIdx.x, blockIdx.x, RsArgs{}, fx);
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_fixed_search_rows_kernel(GtArgs a, RfArgs f, RsArgs sr, RxArgs fx) {
+    rf_row<T, CAP, false, true, true>(a, f, GaArgs{}, blockIdx.x, blockIdx.x, sr, fx);
+}
+
+template <int T, int CAP>
+__global__ __launch_bounds__(T) void graph_fixed_search_step_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr, RxArgs fx) {
+    rf_row<T, CAP, true, true, true>(a, f, v, blockIdx.x, blockIdx.x, sr, fx);
 }
 
 // dagl_graph_stage_search's and dagl_graph_stage_search_step's: the SEARCH flavour over the 4 B L head-major rows of a CES stage's CSR in
@@ -931,6 +1001,55 @@ static int graph_stage_search_entry(const char* who, void* stream, int B, int H,
     return launch_graph_stage_search((hipStream_t)stream, B, g, r, st, workspace, (flags & DAGL_GRAPH_STAGE_SEARCH_HEAD_LAUNCHES) != 0);
 }
 
+// ---- the fixed-width step (dagl_graph_step_fixed) ----------------------------------------------------------------------------------
+struct FixedCall {
+    GraphAttendCall c;                        // row_off null, key = key_in, E = B L width_in
+    const int32_t* deg_in; int width_in, width_out, radius, k; bool keep_all, block_rows;
+    int propagate, explore; uint32_t seed;
+    const float* b2p; float* out;             // both null: the refresh alone
+    int32_t* key_out; float* weight_out; float* score_out; int32_t* deg_out; int64_t* status;
+};
+
+#define DAGL_FIXED_LAUNCH(kernel, ...)                                                                                          \
+    do {                                                                                                                        \
+        if (wave) hipLaunchKernelGGL((kernel<64, RF_WAVE_CAP>), dim3((unsigned)n_rows), dim3(64), 0, s, __VA_ARGS__);           \
+        else hipLaunchKernelGGL((kernel<256, RF_CAP>), dim3((unsigned)n_rows), dim3(256), 0, s, __VA_ARGS__);                   \
+        DAGL_LAUNCH_CHECK(#kernel);                                                                                             \
+    } while (0)
+
+// one row launch (every row leaves whole, also from an empty input: nothing to clear, no count to know), then the fold
+static int launch_graph_step_fixed(hipStream_t s, int B, const Grid& g, const FixedCall& r, void* workspace) {
+    const int n_rows = B * g.L;
+    const bool agg = r.out != nullptr, search = r.propagate || r.explore;
+    DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, 0, agg, false);
+    const GtArgs a = gt_args(B, g, r.c);
+    RfArgs f{};
+    f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.width_in; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
+    f.deg = r.deg_out; f.st_key = r.key_out; f.st_score = r.score_out; f.st_weight = r.weight_out;
+    f.status = reinterpret_cast<unsigned long long*>(r.status);
+    const RxArgs fx{r.deg_in, r.width_in, r.width_out};
+    RsArgs sr{};
+    sr.propagate = r.propagate; sr.explore = r.explore; sr.seed = r.seed; sr.Lw = g.Lw;
+    GaArgs v{};
+    if (agg) {
+        v = ga_map_args(B, g, r.b2p, nullptr, nullptr, nullptr, 0);
+        v.out = w.agg;
+    }
+    const bool wave = !r.block_rows && rf_row_bound(r.width_in, r.radius, r.propagate, r.explore) <= RF_WAVE_CAP;
+    if (search && agg) DAGL_FIXED_LAUNCH(graph_fixed_search_step_rows_kernel, a, f, v, sr, fx);
+    else if (search) DAGL_FIXED_LAUNCH(graph_fixed_search_rows_kernel, a, f, sr, fx);
+    else if (agg) DAGL_FIXED_LAUNCH(graph_fixed_step_rows_kernel, a, f, v, fx);
+    else DAGL_FIXED_LAUNCH(graph_fixed_rows_kernel, a, f, fx);
+    return agg ? launch_fold(s, B, g, w.agg, r.out) : DAGL_OK;
+}
+#undef DAGL_FIXED_LAUNCH
+
+static bool ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + qn && b < a + pn;
+}
+
 }  // namespace dagl
 
 using namespace dagl;
@@ -1112,6 +1231,67 @@ int dagl_graph_stage_search_step(void* stream, int B, int H, int W, const float*
     return graph_stage_search_entry("dagl_graph_stage_search_step", stream, B, H, W, wq_rows4, x_rows4, b2p4, row_off, key, total_edges,
                                     max_row_edges, radius, tau4, k, scale, flags, x, mix_w, mix_b, out, row_off_out, key_out, weight_out,
                                     score_out, capacity_edges, status_out, workspace, ws_bytes, true, propagate, explore, seed);
+}
+
+// the step on a fixed-width graph: one row launch, the graph output at a size known before the call (no ABI bump: found by symbol)
+size_t dagl_graph_step_fixed_workspace_bytes(int B, int H, int W, int want_out) {
+    if (graph_dims_ok("dagl_graph_step_fixed_workspace_bytes", B, H, W)) return 0;
+    return refresh_carve(nullptr, (size_t)B * make_grid(H, W).L, 0, want_out != 0, false).bytes;
+}
+
+int dagl_graph_step_fixed(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows, const float* b2p,
+                          const int32_t* key_in, const int32_t* deg_in, int width_in, int radius, const float* tau, int k, float scale,
+                          int flags, int propagate, int explore, uint32_t seed, float* out, int32_t* key_out, float* weight_out,
+                          float* score_out, int32_t* deg_out, int width_out, int64_t* status, void* workspace, size_t workspace_bytes) {
+    const char* who = "dagl_graph_step_fixed";
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    DAGL_REQUIRE(radius >= 0 && radius <= RF_MAX_RADIUS, "%s: radius=%d outside [0, %d]", who, radius, RF_MAX_RADIUS);
+    DAGL_REQUIRE(width_in >= 1 && width_out >= 1, "%s: width_in=%d, width_out=%d: each at least 1", who, width_in, width_out);
+    const Grid g = make_grid(H, W);
+    const int64_t n_rows = (int64_t)B * g.L;
+    DAGL_REQUIRE(n_rows * width_in < (1ll << 31) && n_rows * width_out < (1ll << 31), "%s: B L width = %lld slots, 2^31 or more", who,
+                 (long long)(n_rows * (width_in > width_out ? width_in : width_out)));
+    if ((rc = search_args_ok(who, propagate, explore))) return rc;
+    DAGL_REQUIRE((b2p == nullptr) == (out == nullptr), "%s: b2p and out come together (both null: the refresh alone)", who);
+    static const int64_t no_offsets = 0;      // (the shared null test asks for offsets; this form has none)
+    if ((rc = graph_operands_ok(who, wq_rows, x_rows, &no_offsets, key_in, n_rows * width_in, scale, flags,
+                                deg_in && key_out && weight_out && score_out && deg_out && status,
+                                DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
+        return rc;
+    if (b2p) DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    if (k > 0 && !keep_all) {
+        const int most = k < g.N ? k : g.N;
+        DAGL_REQUIRE(width_out >= most, "%s: width_out=%d < min(k, N) = %d entries a row may keep", who, width_out, most);
+    }
+    if (rf_row_bound(width_in, radius, propagate, explore) > RF_CAP) {
+        set_error("%s: (1 + 4 propagate) width_in (2 radius + 1)^2 + explore = %lld candidates per row, more than the %d a row may "
+                  "expand into", who, rf_row_bound(width_in, radius, propagate, explore), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    {
+        const size_t rows = (size_t)n_rows;
+        const void* in_p[6] = {wq_rows, x_rows, b2p, key_in, deg_in, tau};
+        const size_t in_n[6] = {rows * D * sizeof(float), (size_t)B * g.N * D * sizeof(float), (size_t)B * g.Hp * g.Wp * CH * sizeof(float),
+                                rows * width_in * sizeof(int32_t), rows * sizeof(int32_t), rows * sizeof(float)};
+        const void* out_p[5] = {out, key_out, weight_out, score_out, deg_out};
+        const size_t out_n[5] = {(size_t)B * CH * g.N * sizeof(float), rows * width_out * sizeof(int32_t), rows * width_out * sizeof(float),
+                                 rows * width_out * sizeof(float), rows * sizeof(int32_t)};
+        for (int i = 0; i < 5; ++i)
+            for (int j = 0; j < 6; ++j)
+                DAGL_REQUIRE(!ranges_overlap(out_p[i], out_n[i], in_p[j], in_n[j]), "%s: an output array overlaps an input array", who);
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)n_rows, 0, out != nullptr, false).bytes;
+    if (need > 0 && (rc = check_workspace(who, workspace, workspace_bytes, need))) return rc;
+    FixedCall r{};
+    r.c = graph_attend_call(wq_rows, x_rows, nullptr, key_in, n_rows * width_in, tau, scale, flags);
+    r.deg_in = deg_in; r.width_in = width_in; r.width_out = width_out; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.propagate = propagate; r.explore = explore; r.seed = seed; r.b2p = b2p; r.out = out;
+    r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.deg_out = deg_out; r.status = status;
+    return launch_graph_step_fixed((hipStream_t)stream, B, g, r, workspace);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""``PatchGraph`` -- the patch graph a ``CE`` block learns, as CSR over its query rows.
+"""``PatchGraph`` -- the patch graph a ``CE`` block learns, as CSR over its query rows -- and ``FixedGraph``, the same graph as a fixed
+number of slots per row: the form whose size is known before a step runs, so that a step can hand back its graph under stream capture.
 
 What ``CE.graph`` returns (``dagl_ce_graph_count`` / ``dagl_ce_graph_fill``, csrc/graph.hip): for every image and query patch the
 keys with ``mask_b != 0`` and their weights ``A = softmax(10 S m) * mask_b`` -- the non-zeros of ``yi``, dagl.py:256-261.  The
@@ -248,6 +249,167 @@ class PatchGraph:
             self._transposed = (col_off.contiguous(), rows[perm].int().contiguous(), perm.int().contiguous())
         return self._transposed
 
+    def to_fixed(self, width: Optional[int] = None) -> "FixedGraph":
+        """This graph as ``width`` slots per row (``FixedGraph``): row r's edges, verbatim and in their order (repeats, ``-1`` and ``N``
+        included), in slots ``0 .. deg - 1``, then ``(-1, 0, 0)``.  ``width=None``: ``max_degree()``, at least 1.  A row longer than
+        ``width`` is refused.  A gather, no boolean-mask indexing: no host read beyond ``max_degree()``.  A graph without scores gives
+        zero scores."""
+        longest = self.max_degree()
+        width = max(longest, 1) if width is None else int(width)
+        if width < 1:
+            raise DaglError(f"PatchGraph.to_fixed: width={width} < 1")
+        if longest > width:
+            raise DaglError(f"PatchGraph.to_fixed: a row holds {longest} edges, more than width = {width} (rows are never truncated)")
+        dev = self.row_off.device
+        deg = self.row_off[1:] - self.row_off[:-1]
+        slot = torch.arange(width, device=dev)
+        live = slot[None, :] < deg[:, None]
+        at = (self.row_off[:-1, None] + slot[None, :]).clamp_(0, max(self.n_edges - 1, 0))
+
+        def rows_of(values, filler):
+            if self.n_edges == 0:
+                return torch.full((deg.numel(), width), filler, dtype=values.dtype, device=dev)
+            return torch.where(live, values[at], torch.full((), filler, dtype=values.dtype, device=dev))
+
+        score = self.score if self.score is not None else torch.zeros_like(self.weight)
+        return FixedGraph(rows_of(self.key, -1), rows_of(self.weight, 0.0), rows_of(score, 0.0), deg.to(torch.int32), self.B, self.H,
+                          self.W, self.mode, self.k)
+
     def __repr__(self):
         return (f"PatchGraph(B={self.B}, L={self.L}, N={self.N}, edges={self.n_edges}, mode={self.mode!r}, k={self.k}, "
                 f"score={'yes' if self.score is not None else 'no'}, device={self.row_off.device})")
+
+
+class FixedGraph:
+    """A patch graph as ``width`` slots per query row (``rows = B * L``, row ``b * L + i`` = query ``i`` of image ``b``; ``B`` counts
+    head-major images for a ``CES`` stage, as in ``PatchGraph.cat``):
+
+    ``key`` [rows, width] int32, ``weight`` / ``score`` [rows, width] fp32, ``deg`` [rows] int32.  Row r holds its edges in slots
+    ``0 .. deg[r] - 1`` -- in ascending key order when a step produced it -- and ``key = -1, weight = 0, score = 0`` from ``deg[r]`` on:
+    every byte is defined, two graphs compare with ``torch.equal``.  ``mode`` / ``k`` as on ``PatchGraph``.
+
+    Every array has a size known without looking at the graph, so ``CE.step_graph`` / ``refresh_graph`` on a ``FixedGraph`` read nothing
+    on the host and run under stream capture WITH their graph output; ``copy_`` moves a new graph into a captured one's storage.
+    ``PatchGraph.to_fixed`` / ``to_csr`` convert (plain torch, off the hot path); the routes that walk edges (``apply_graph``,
+    ``attend_graph``, ``forward_on_graph``) take the CSR."""
+
+    def __init__(self, key: torch.Tensor, weight: torch.Tensor, score: torch.Tensor, deg: torch.Tensor, B: int, H: int, W: int,
+                 mode: str = "adaptive", k: int = 0):
+        B, H, W, k = int(B), int(H), int(W), int(k)
+        if B < 1 or H < 1 or W < 1:
+            raise DaglError(f"FixedGraph: bad shape B={B} H={H} W={W}")
+        if mode not in MODES:
+            raise DaglError(f"FixedGraph: unknown mode {mode!r}")
+        L, N = (-(-H // 4)) * (-(-W // 4)), H * W
+        for name, t, dtype, dim in (("key", key, torch.int32, 2), ("weight", weight, torch.float32, 2), ("score", score, torch.float32, 2),
+                                    ("deg", deg, torch.int32, 1)):
+            if not isinstance(t, torch.Tensor) or t.dim() != dim:
+                raise DaglError(f"FixedGraph: {name} must be a {dim}-d tensor")
+            if t.dtype != dtype:
+                raise DaglError(f"FixedGraph: {name} has dtype {t.dtype}, expected {dtype}")
+            if t.device != key.device:
+                raise DaglError(f"FixedGraph: {name} lives on {t.device}, key on {key.device}")
+            if not t.is_contiguous():
+                raise DaglError(f"FixedGraph: {name} must be contiguous")
+        if key.shape[0] != B * L or key.shape[1] < 1:
+            raise DaglError(f"FixedGraph: key is {tuple(key.shape)}, expected [B*L = {B * L}, width >= 1]")
+        if weight.shape != key.shape or score.shape != key.shape or deg.numel() != B * L:
+            raise DaglError("FixedGraph: weight and score must have key's shape, deg one entry per row")
+        self.key, self.weight, self.score, self.deg = key, weight, score, deg
+        self.B, self.L, self.N, self.H, self.W, self.mode, self.k = B, L, N, H, W, mode, k
+
+    @property
+    def width(self) -> int:
+        return self.key.shape[1]
+
+    @property
+    def device(self):
+        return self.key.device
+
+    def _like(self, key, weight, score, deg, B=None) -> "FixedGraph":
+        g = object.__new__(FixedGraph)
+        g.key, g.weight, g.score, g.deg = key, weight, score, deg
+        g.B, g.L, g.N, g.H, g.W, g.mode, g.k = (self.B if B is None else B), self.L, self.N, self.H, self.W, self.mode, self.k
+        return g
+
+    def n_edges(self) -> int:
+        """The edges the graph holds (``deg`` clamped to [0, width]): one reduction and one host read."""
+        return int(self.deg.clamp(0, self.width).sum())
+
+    def degrees(self) -> torch.Tensor:
+        """[B, L] int64: keys per query."""
+        return self.deg.clamp(0, self.width).long().view(self.B, self.L)
+
+    def row(self, b: int, i: int):
+        """(key, weight, score) of query ``i`` of image ``b``: views of the row's first ``deg`` slots (one host read of the degree)."""
+        b, i = int(b), int(i)
+        if not (0 <= b < self.B and 0 <= i < self.L):
+            raise IndexError(f"FixedGraph: row ({b}, {i}) outside [0, {self.B}) x [0, {self.L})")
+        r = b * self.L + i
+        d = min(max(int(self.deg[r]), 0), self.width)
+        return self.key[r, :d], self.weight[r, :d], self.score[r, :d]
+
+    def to(self, device) -> "FixedGraph":
+        device = torch.device(device)
+        return self._like(self.key.to(device), self.weight.to(device), self.score.to(device), self.deg.to(device))
+
+    def cpu(self) -> "FixedGraph":
+        return self.to("cpu")
+
+    def images(self, lo: int, hi: int) -> "FixedGraph":
+        """The sub-graph of images ``lo .. hi - 1``: row views of the four arrays.  Never reads on the host."""
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo < hi <= self.B:
+            raise DaglError(f"FixedGraph.images: [{lo}, {hi}) is not a non-empty range of the {self.B} images")
+        r0, r1 = lo * self.L, hi * self.L
+        return self._like(self.key[r0:r1], self.weight[r0:r1], self.score[r0:r1], self.deg[r0:r1], B=hi - lo)
+
+    @staticmethod
+    def cat(graphs) -> "FixedGraph":
+        """The graphs one after the other along the image axis (``B`` adds up): what a ``CES`` stage keeps of its four heads,
+        head-major.  They must share ``width``, H, W and the device; ``mode`` / ``k`` come from the first.  No host read."""
+        graphs = list(graphs)
+        if not graphs or not all(isinstance(g, FixedGraph) for g in graphs):
+            raise DaglError("FixedGraph.cat: a non-empty sequence of FixedGraphs expected")
+        first = graphs[0]
+        for g in graphs[1:]:
+            if (g.H, g.W) != (first.H, first.W):
+                raise DaglError(f"FixedGraph.cat: maps of {first.H}x{first.W} and {g.H}x{g.W}")
+            if g.width != first.width:
+                raise DaglError(f"FixedGraph.cat: widths {first.width} and {g.width}")
+            if g.device != first.device:
+                raise DaglError(f"FixedGraph.cat: graphs on {first.device} and {g.device}")
+        return first._like(torch.cat([g.key for g in graphs]), torch.cat([g.weight for g in graphs]),
+                           torch.cat([g.score for g in graphs]), torch.cat([g.deg for g in graphs]), B=sum(g.B for g in graphs))
+
+    def copy_(self, other: "FixedGraph") -> "FixedGraph":
+        """``other``'s four arrays into this graph's storage, in place: four device copies, no host read (capturable).  ``B``, H, W and
+        ``width`` must agree; ``mode`` / ``k`` are taken over."""
+        if not isinstance(other, FixedGraph):
+            raise DaglError(f"FixedGraph.copy_: a FixedGraph expected, got {type(other).__name__}")
+        if (other.B, other.H, other.W) != (self.B, self.H, self.W):
+            raise DaglError(f"FixedGraph.copy_: B={other.B} H={other.H} W={other.W} into B={self.B} H={self.H} W={self.W}")
+        if other.width != self.width:
+            raise DaglError(f"FixedGraph.copy_: width {other.width} into width {self.width}")
+        self.key.copy_(other.key); self.weight.copy_(other.weight); self.score.copy_(other.score); self.deg.copy_(other.deg)
+        self.mode, self.k = other.mode, other.k
+        return self
+
+    def to_csr(self) -> PatchGraph:
+        """This graph as a ``PatchGraph`` with scores: row r's first ``deg[r]`` slots (``deg`` clamped to [0, width]) in their order.
+        One host read, of the edge count.  ``g.to_fixed(w).to_csr()`` gives ``g``'s arrays back bit for bit."""
+        dev = self.device
+        deg = self.deg.clamp(0, self.width).long()
+        row_off = torch.cat([deg.new_zeros(1), deg.cumsum(0)])
+        E = int(row_off[-1])                                                     # the one host read
+        rows = torch.repeat_interleave(torch.arange(deg.numel(), device=dev), deg, output_size=E)
+        at = rows * self.width + (torch.arange(E, device=dev) - row_off[rows])
+        g = object.__new__(PatchGraph)
+        g.row_off, g.key, g.weight, g.score = row_off, self.key.reshape(-1)[at], self.weight.reshape(-1)[at], self.score.reshape(-1)[at]
+        g.B, g.L, g.N, g.H, g.W, g.mode, g.k = self.B, self.L, self.N, self.H, self.W, self.mode, self.k
+        g._valid, g._transposed, g._max_degree = False, None, None
+        return g
+
+    def __repr__(self):
+        return (f"FixedGraph(B={self.B}, L={self.L}, N={self.N}, width={self.width}, mode={self.mode!r}, k={self.k}, "
+                f"device={self.device})")

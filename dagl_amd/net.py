@@ -194,6 +194,12 @@ class CES(nn.Module):
         then exactly the one above).  The stage-fused launch of THIS method has no search flavour (``search_graphs`` is the
         stage-fused search step): with any of them set ``fused=None`` runs head by head and ``fused=True`` is refused, before any launch.
 
+        A state of ``FixedGraph``s (``state.to_fixed()``) runs head by head -- ``CE.step_graph`` on each head's row views,
+        ``FixedGraph.cat``, ``torch.cat`` and the mix convolution, as ``fused=False`` does -- and returns a fixed state; the whole call,
+        ``want_graphs=True`` included, reads nothing on the host and can be captured (``state.copy_(new_state)`` inside the capture
+        carries the graphs to the next replay).  ``fused=True`` is refused there (a stage-fused fixed-width launch does not exist),
+        ``fused=None`` means head by head; heads of a stage whose output widths differ are refused before any launch.
+
         Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
         the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
         does not fit the input -- is raised before any launch of the call."""
@@ -217,12 +223,43 @@ class CES(nn.Module):
         if (state.stages[0].B, state.stages[0].H, state.stages[0].W) != (4 * B, x.shape[2], x.shape[3]):
             g0 = state.stages[0]
             raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={B} H={x.shape[2]} W={x.shape[3]}")
+        if state.fixed:
+            return self._step_graphs_fixed(x, state, radius, features, want_graphs, fused, search)
         plan = self._plan_step(x, state, radius, features, want_graphs, fused, search)
         out, new = x, []
         for s in (1, 2, 3):
             out, g = self._step_stage(s, out, state, plan[s], features, want_graphs, search)
             new.append(g)
             out = self._between_stages(s, out)
+        return out, (SequenceState(new) if want_graphs else None)
+
+    def _step_graphs_fixed(self, x, state, radius, features, want_graphs, fused, search):
+        """``step_graphs`` on a state of ``FixedGraph``s: the refusals of every head of every stage first (no launch, no host read), then
+        head by head."""
+        from ._lib import DaglError
+        from .graph import FixedGraph
+        from .sequence import SequenceState
+        what = "CES.step_graphs"
+        if fused:
+            raise DaglError(f"{what}: fused=True on a state of FixedGraphs: a stage-fused fixed-width launch does not exist; leave fused "
+                            "at None (head by head) or pass fused=False")
+        for s in (1, 2, 3):
+            widths = []
+            for h, hd in enumerate(self._stage_modules(s)[0]):
+                if not isinstance(hd, CE):
+                    raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it steps no graph")
+                widths.append(hd._fixed_arguments(x, state.head(s - 1, h), "step_graph", radius, None, "reference", features, **search)[3])
+            if len(set(widths)) != 1:
+                raise DaglError(f"{what}: the heads of stage {s} give graphs of widths {widths}: one FixedGraph per stage needs one width "
+                                "(heads that share select_mode and select_k)")
+        out, new = x, []
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            pairs = [hd.step_graph(out, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs, **search)
+                     for h, hd in enumerate(heads)]
+            if want_graphs:
+                new.append(FixedGraph.cat([g for _, g in pairs]))
+            out = self._between_stages(s, mix(torch.cat([o for o, _ in pairs], dim=1)) + out)
         return out, (SequenceState(new) if want_graphs else None)
 
     def forward_on_graphs(self, x, state, *, features: str = "fp32", backward: str = "two_ops"):
@@ -375,6 +412,8 @@ class CES(nn.Module):
             raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise DaglError(f"{what}: expected [B,C,H,W]")
+        if state.fixed:
+            raise DaglError(f"{what}: a state of FixedGraphs serves step_graphs only; pass state.to_csr()")
         B = x.shape[0]
         g0 = state.stages[0]
         if (g0.B, g0.H, g0.W) != (4 * B, x.shape[2], x.shape[3]):

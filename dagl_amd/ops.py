@@ -929,6 +929,82 @@ def graph_search_step(wq_rows, x_rows, b2p, row_off, key, *, radius: int = 1, ta
     return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges, adjacent=bool(propagate)), status
 
 
+@_on_device
+def graph_step_fixed(wq_rows, x_rows, b2p, key, deg, *, width_out: int, radius: int = 1, tau=None, k: int = 0, scale: float = 10.0,
+                     normalize: str = "reference", keep_all: bool = False, propagate=False, explore: int = 0, seed: int = 0,
+                     workspace: "Workspace | None" = None, hw=None, block_rows: bool = False):
+    """``graph_step`` (``b2p`` given), ``graph_refresh`` (``b2p`` None) and -- ``propagate`` / ``explore`` -- their search forms on a
+    FIXED-WIDTH graph (``dagl_graph_step_fixed``, csrc/graph_refresh.hip) -> (out [B,16,H,W] | None, dict(key, weight, score, deg),
+    status).  ``key`` [B*L, width_in] int32 and ``deg`` [B*L] int32 hold row r's edges in slots ``0 .. deg[r] - 1`` (``deg`` is read
+    clamped to [0, width_in]); the dict holds ``key`` / ``weight`` / ``score`` [B*L, width_out] and ``deg`` [B*L]: the kept entries in
+    ascending key order, then ``(-1, 0, 0)`` -- every slot is written.  For the same rows the kept entries and ``out`` carry the bits
+    the CSR calls give with ``max_row_edges = width_in``.  A row that keeps more than ``width_out`` entries (possible only without a
+    rank cut) comes out EMPTY and is counted in ``status[0]`` (device int64[2], left for the caller to read); it is never truncated.
+    With ``k`` > 0 and no ``keep_all``, ``width_out >= min(k, N)`` is required.
+
+    One row launch and the fold: no staging, scan or copy.  NOTHING is read on the host in any form of the call, so it can be captured
+    into a HIP graph with its graph output.  ``hw`` as in ``graph_refresh`` (``b2p`` names the map when given)."""
+    lib = _lib.load()
+    who = "graph_step_fixed"
+    propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
+    _need(wq_rows, "wq_rows"); _need(x_rows, "x_rows"); _need(key, "key", torch.int32); _need(deg, "deg", torch.int32)
+    if b2p is not None:
+        _need(b2p, "b2p")
+        map_hw = _value_map(who, b2p)[1:]
+        if hw is not None and tuple(int(v) for v in hw) != tuple(map_hw):
+            raise DaglError(f"{who}: hw={tuple(hw)} but b2p is the value map of a {map_hw[0]}x{map_hw[1]} image")
+        hw = map_hw
+    if key.dim() != 2 or key.shape[1] < 1 or deg.dim() != 1:
+        raise DaglError(f"{who}: expected key [B*L, width >= 1] and deg [B*L], got {tuple(key.shape)} and {tuple(deg.shape)}")
+    n_rows, width_in = key.shape
+    width_out = int(width_out)
+    if width_out < 1:
+        raise DaglError(f"{who}: width_out={width_out} < 1")
+    # (``_graph_refresh_operands``' checks without the offsets: this form has none)
+    if wq_rows.dim() != 3 or x_rows.dim() != 3 or wq_rows.shape[2] != D or x_rows.shape[2] != D or wq_rows.shape[0] != x_rows.shape[0]:
+        raise DaglError(f"{who}: expected wq_rows [B,L,{D}] and x_rows [B,N,{D}], got {tuple(wq_rows.shape)} and {tuple(x_rows.shape)}")
+    B, L, N = wq_rows.shape[0], wq_rows.shape[1], x_rows.shape[1]
+    if hw is None:
+        maps = list(_maps_of(L, N))
+        if len(maps) != 1:
+            raise DaglError(f"{who}: {len(maps)} maps have {N} keys and {L} queries: pass hw=(H, W)")
+        hw = maps[0]
+    H, W = (int(v) for v in hw)
+    if H * W != N or math.prod(query_grid(H, W)) != L:
+        raise DaglError(f"{who}: a {H}x{W} map has {math.prod(query_grid(H, W))} queries and {H * W} keys, the feature rows hold {L} "
+                        f"and {N}")
+    if n_rows != B * L or deg.numel() != n_rows:
+        raise DaglError(f"{who}: key holds {n_rows} rows and deg {deg.numel()} degrees, expected B*L = {B * L}")
+    if tau is not None:
+        _need(tau, "tau")
+        if tau.numel() != B * L:
+            raise DaglError(f"{who}: tau holds {tau.numel()} values, expected B*L = {B * L}")
+    if normalize not in _GRAPH_NORMALIZE:
+        raise DaglError(f"{who}: normalize={normalize!r}, expected 'reference' or 'edges'")
+    flags = _GRAPH_NORMALIZE[normalize] | (_lib.GRAPH_REFRESH_KEEP_ALL if keep_all else 0) \
+        | (_lib.GRAPH_REFRESH_BLOCK_ROWS if block_rows else 0)
+    radius, k = int(radius), int(k)
+    if b2p is not None and b2p.shape[0] != B:
+        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    if k > 0 and not keep_all and width_out < min(k, H * W):
+        raise DaglError(f"{who}: width_out={width_out} < min(k, N) = {min(k, H * W)} entries a row may keep")
+    dev = wq_rows.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_step_fixed_workspace_bytes", B, H, W, 1) if b2p is not None \
+        else (None, None, 0)
+    out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32) if b2p is not None else None
+    key_out = torch.empty(n_rows, width_out, device=dev, dtype=torch.int32)
+    weight = torch.empty(n_rows, width_out, device=dev, dtype=torch.float32)
+    score = torch.empty(n_rows, width_out, device=dev, dtype=torch.float32)
+    deg_out = torch.empty(n_rows, device=dev, dtype=torch.int32)
+    status = torch.empty(2, device=dev, dtype=torch.int64)
+    check(lib.dagl_graph_step_fixed(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), _ptr(b2p), key.data_ptr(), deg.data_ptr(),
+                                    width_in, radius, _ptr(tau), k, float(scale), flags, propagate, explore, seed, _ptr(out),
+                                    key_out.data_ptr(), weight.data_ptr(), score.data_ptr(), deg_out.data_ptr(), width_out,
+                                    status.data_ptr(), a, nbytes), "dagl_graph_step_fixed")
+    del buf
+    return out, dict(key=key_out, weight=weight, score=score, deg=deg_out), status
+
+
 def _stage_mix_operands(who: str, x, mix_w, mix_b):
     """x [B,64,H,W], the stage's 1x1 mix weights [64,64] or [64,64,1,1] and bias [64] -> (B, H, W)."""
     _need(x, "x"); _need(mix_w, "mix_w"); _need(mix_b, "mix_b")

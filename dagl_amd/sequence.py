@@ -7,19 +7,22 @@ bookkeeping over ``PatchGraph`` (graph.py): it works on CPU tensors.
 from __future__ import annotations
 
 from ._lib import DaglError
-from .graph import PatchGraph
+from .graph import FixedGraph, PatchGraph
 
 STAGES, HEADS = 3, 4
 
 
 class SequenceState:
     """``stages[s]`` (s = 0, 1, 2): the graphs of stage ``s + 1``'s four heads as ONE ``PatchGraph`` over ``4 * B`` images, head-major --
-    row ``(h * B + b) * L + i`` is query ``i`` of image ``b`` under head ``h`` (``PatchGraph.cat`` of the heads' graphs)."""
+    row ``(h * B + b) * L + i`` is query ``i`` of image ``b`` under head ``h`` (``PatchGraph.cat`` of the heads' graphs).
+
+    The three stages may be ``FixedGraph``s instead (``to_fixed``; all three, never mixed): the state ``step_graphs`` moves without a host
+    read and under stream capture, ``copy_`` taking the new state into the captured one's storage."""
 
     def __init__(self, stages):
         stages = list(stages)
-        if len(stages) != STAGES or not all(isinstance(g, PatchGraph) for g in stages):
-            raise DaglError(f"SequenceState: {STAGES} PatchGraphs expected, one per stage")
+        if len(stages) != STAGES or not (all(isinstance(g, PatchGraph) for g in stages) or all(isinstance(g, FixedGraph) for g in stages)):
+            raise DaglError(f"SequenceState: {STAGES} PatchGraphs or {STAGES} FixedGraphs expected, one per stage (never mixed)")
         for g in stages:
             if g.B % HEADS:
                 raise DaglError(f"SequenceState: a stage graph over {g.B} images does not hold {HEADS} heads of a batch")
@@ -32,6 +35,31 @@ class SequenceState:
     def B(self) -> int:
         """Images per head."""
         return self.stages[0].B // HEADS
+
+    @property
+    def fixed(self) -> bool:
+        """Whether the stages are ``FixedGraph``s."""
+        return isinstance(self.stages[0], FixedGraph)
+
+    def to_fixed(self, width=None) -> "SequenceState":
+        """The state with every stage as a ``FixedGraph`` of ``width`` slots per row (None: each stage's own largest degree)."""
+        if self.fixed:
+            raise DaglError("SequenceState.to_fixed: the stages are FixedGraphs already")
+        return SequenceState(g.to_fixed(width) for g in self.stages)
+
+    def to_csr(self) -> "SequenceState":
+        """The state with every stage as a ``PatchGraph`` (one host read per stage)."""
+        if not self.fixed:
+            raise DaglError("SequenceState.to_csr: the stages are PatchGraphs already")
+        return SequenceState(g.to_csr() for g in self.stages)
+
+    def copy_(self, other: "SequenceState") -> "SequenceState":
+        """``other``'s arrays into this state's storage, stage by stage (``FixedGraph.copy_``: no host read, capturable)."""
+        if not isinstance(other, SequenceState) or not (self.fixed and other.fixed):
+            raise DaglError("SequenceState.copy_: two states of FixedGraphs expected (a CSR's size depends on its content)")
+        for mine, theirs in zip(self.stages, other.stages):
+            mine.copy_(theirs)
+        return self
 
     @classmethod
     def from_heads(cls, graphs) -> "SequenceState":
@@ -53,8 +81,9 @@ class SequenceState:
         g = trivial_graph(B, H, W, device, mode)
         return cls.from_heads([g] * (STAGES * HEADS))
 
-    def head(self, s: int, h: int) -> PatchGraph:
-        """The graph of head ``h`` (0..3) of stage ``s`` (0..2): ``stages[s].images(h * B, (h + 1) * B)``, kept on the object."""
+    def head(self, s: int, h: int):
+        """The graph of head ``h`` (0..3) of stage ``s`` (0..2): ``stages[s].images(h * B, (h + 1) * B)``, kept on the object.  Of a
+        fixed state: row views of the stage's arrays, no host read."""
         s, h = int(s), int(h)
         if not (0 <= s < STAGES and 0 <= h < HEADS):
             raise IndexError(f"SequenceState.head: ({s}, {h}) outside [0, {STAGES}) x [0, {HEADS})")
@@ -63,8 +92,8 @@ class SequenceState:
         return self._heads[(s, h)]
 
     def has_head(self, s: int, h: int) -> bool:
-        """Whether ``head(s, h)`` is at hand without a host read."""
-        return (int(s), int(h)) in self._heads
+        """Whether ``head(s, h)`` is at hand without a host read (a fixed state: always)."""
+        return self.fixed or (int(s), int(h)) in self._heads
 
     def to(self, device) -> "SequenceState":
         return SequenceState(g.to(device) for g in self.stages)

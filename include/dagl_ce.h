@@ -552,6 +552,34 @@ int    dagl_graph_search_step(void* stream, int B, int H, int W, const float* wq
                               float* weight_out, float* score_out, int64_t capacity_edges, int64_t* status_out, void* workspace,
                               size_t ws_bytes, int propagate, int explore, uint32_t seed);
 
+/* ---- the step on a fixed-width patch graph: csrc/graph_refresh.hip (detected by symbol, no ABI bump) -----------------------------------
+ * dagl_graph_step_fixed: dagl_graph_step (b2p / out given), dagl_graph_refresh (both NULL) and, with propagate / explore set, their
+ * search forms, on a graph held as `width` slots per row instead of a CSR -- so that the graph output has a size known before the call,
+ * nothing is read on the host and the call can be captured into a HIP graph WITH its graph output.
+ *   input   key_in [B L, width_in] int32, deg_in [B L] int32: row r holds its edges in slots 0 .. deg_in[r] - 1 (deg_in is read clamped
+ *           to [0, width_in]; slots behind the degree are never read; keys as in the CSR entries: any order, repeats count once, keys
+ *           outside [0, N) contribute nothing).
+ *   output  key_out / weight_out / score_out [B L, width_out], deg_out [B L]: the kept entries of row r in ascending key order in slots
+ *           0 .. deg_out[r] - 1, then key -1, weight 0, score 0 up to width_out.  EVERY slot and degree is written by every call: the
+ *           arrays need no clearing.  out [B,16,H,W] as dagl_graph_step's.
+ * Candidates, scores, selection, weights and the aggregation are the CSR entries': for the same rows the kept (key, score, weight) and
+ * out carry the same bits as dagl_graph_refresh / _step / _search / _search_step give with max_row_edges = width_in.  A row that keeps
+ * more than width_out entries comes out EMPTY (degree 0, filler, zeros to out), never truncated, and is counted in status[0] -- possible
+ * only without a rank cut (k = 0) or with DAGL_GRAPH_REFRESH_KEEP_ALL.  status[1]: the largest number of distinct candidates of a row.
+ * One row launch (a wavefront per row when (1 + 4 propagate) width_in (2 radius + 1)^2 + explore <= 128, else a block per row), then
+ * the fold when out is wanted: no staging, no scan, no copy.  flags: DAGL_GRAPH_ATTEND_EDGES_ONLY, DAGL_GRAPH_REFRESH_KEEP_ALL,
+ * DAGL_GRAPH_REFRESH_BLOCK_ROWS.  Refused before any launch: the shape and operand checks of dagl_graph_step; width_in or width_out < 1;
+ * B L width >= 2^31; propagate not 0 / 1, explore outside 0..256; exactly one of b2p and out NULL; k > 0 without KEEP_ALL and
+ * width_out < min(k, N); an output array that overlaps an input array (DAGL_ERR_INVALID); that row bound above
+ * dagl_graph_refresh_max_candidates() (DAGL_ERR_UNSUPPORTED); too small a workspace (DAGL_ERR_WORKSPACE).  Workspace:
+ * dagl_graph_step_fixed_workspace_bytes -- the [B L, 784] aggregated rows when out is wanted, else 0 (workspace may then be NULL). */
+size_t dagl_graph_step_fixed_workspace_bytes(int B, int H, int W, int want_out);
+int    dagl_graph_step_fixed(void* stream, int B, int H, int W, const float* wq_rows, const float* x_rows,
+                             const float* b2p /* NULL: the refresh alone */, const int32_t* key_in, const int32_t* deg_in, int width_in,
+                             int radius, const float* tau, int k, float scale, int flags, int propagate, int explore, uint32_t seed,
+                             float* out /* NULL iff b2p NULL */, int32_t* key_out, float* weight_out, float* score_out, int32_t* deg_out,
+                             int width_out, int64_t* status /* [2] */, void* workspace, size_t workspace_bytes);
+
 /* ---- the sequence step of a whole CES stage: csrc/graph_refresh.hip, csrc/aggregate.hip (detected by symbol) ---------------------------
  * dagl_ces_stage_fold_mix: the end of a stage from its four heads' aggregated rows, in one launch:
  *     out = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x

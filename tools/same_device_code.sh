@@ -5,6 +5,8 @@
 # move within its file; basic-block labels lose their function number; comments, the compilation unit's id (a
 # hash that covers the source text) and which text section a function sits in (a template instantiation has its
 # own) are not compared: every instruction, directive and .amdhsa_ resource line is.  SED_EXPR maps OTHER's names of renamed symbols.
+# COMMON=1: a file that gained or lost functions is compared over the functions and kernel metadata both trees have (the others are
+# listed by name), for a change that adds kernels next to pinned ones.
 set -u
 here=$(cd "$(dirname "$0")/.." && pwd); other=$(cd "$1" && pwd); map=${2:-}
 out=$(mktemp -d); trap 'rm -rf "$out"' EXIT; tab=$(printf '\t'); bad=0
@@ -20,11 +22,19 @@ blocks() { sed -E "$map; s/\.LBB[0-9]+_/.LBB_/g; s/\.L(func_begin|func_end|tmp)[
     meta && /^[a-z]/ && !/^amdhsa\.kernels:/ { flush(); key = "4" }
     meta && /^    \.name:/                   { key = "3 " $2 }
     { sub(/[ \t]*;.*$/, ""); if ($0 != "") buf[n++] = $0 }                 # (comments are notes of the compiler: no code)
-    END { flush() }' | LC_ALL=C sort -s -t "$tab" -k1,1 | cut -f2-; }
+    END { flush() }' | LC_ALL=C sort -s -t "$tab" -k1,1; }
+keys() { cut -f1 "$1" | grep -E '^[13] ' | LC_ALL=C sort -u; }
 asm "$here" "$out/new" && asm "$other" "$out/old" || { echo "compile failed"; exit 2; }
 for s in $( (cd "$out/new" && ls; cd "$out/old" && ls) | sort -u); do
     [ -f "$out/new/$s" ] && [ -f "$out/old/$s" ] || { echo "$s: in one tree only"; bad=1; continue; }
-    map= blocks "$out/new/$s" > "$out/a"; blocks "$out/old/$s" > "$out/b"
+    map= blocks "$out/new/$s" > "$out/ka"; blocks "$out/old/$s" > "$out/kb"
+    if [ -n "${COMMON:-}" ] && ! diff <(keys "$out/ka") <(keys "$out/kb") > /dev/null; then
+        LC_ALL=C comm -3 <(keys "$out/kb") <(keys "$out/ka") | sed "s/^\t/  new only: /; t; s/^/  old only: /" | sed "s/: [13] /: /" | sort -u
+        LC_ALL=C comm -12 <(keys "$out/ka") <(keys "$out/kb") > "$out/both"
+        for f in ka kb; do awk -F "$tab" 'NR == FNR { keep[$0] = 1; next } $1 in keep' "$out/both" "$out/$f" > "$out/$f.c"; mv "$out/$f.c" "$out/$f"; done
+        echo "$s: compared over the $(grep -c '^1 ' "$out/both") functions both trees have"
+    fi
+    cut -f2- "$out/ka" > "$out/a"; cut -f2- "$out/kb" > "$out/b"
     if diff "$out/b" "$out/a" > "$out/d"; then echo "$s: same ($(grep -c '^[[:space:]]*\.amdhsa_kernel ' "$out/a") kernels, $(wc -l < "$out/a") lines)"
     else echo "$s: DIFFERS"; head -40 "$out/d"; bad=1; fi
 done

@@ -13,6 +13,9 @@
     python tools/time_patch_graph.py --search [H W]   # the search step: ``refresh_graph`` alone, + propagate, + explore 8, both, on a
                                                       # shifted frame -- time and recall against ``graph``; ``build_graph`` per
                                                       # iteration next to the forward that selects; the two cases of --refresh
+    python tools/time_patch_graph.py --fixed [H W]    # the step on a ``FixedGraph`` (eager, and replayed from a captured HIP graph with
+                                                      # ``g.copy_(g_new)`` inside) next to the CSR step with and without its graph;
+                                                      # interleaved repeats; the two cases of --refresh
 """
 import os
 import sys
@@ -49,6 +52,30 @@ def _events(fn, warmup=3, repeats=5, inner=10):
         times.append(t0.elapsed_time(t1) / inner)
     times.sort()
     return times[len(times) // 2], times[0], times[-1]
+
+
+def _interleaved(legs, warmup=3, repeats=7, inner=10):
+    """``_events`` for several legs measured in turn -- every repeat times each leg once, so that a drift of the clocks meets all of them
+    alike -> {name: (median, min, max)} in ms per call."""
+    for fn in legs.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in legs}
+    for _ in range(repeats):
+        for name, fn in legs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(inner):
+                fn()
+            t1.record()
+            torch.cuda.synchronize()
+            times[name].append(t0.elapsed_time(t1) / inner)
+    out = {}
+    for name, t in times.items():
+        t.sort()
+        out[name] = (t[len(t) // 2], t[0], t[-1])
+    return out
 
 
 def _long_tailed(g, n_rows=16):
@@ -347,6 +374,73 @@ def step_leg(H, W, big):
           f"ops.graph_forward alone on the result {fmt(k_fwd)}", flush=True)
 
 
+def fixed_leg(H, W, big):
+    """One head, a next frame, radius 1, split-fp16 features (the cases of ``step_leg``): ``step_graph`` on the CSR with and without its
+    graph, on the ``FixedGraph`` eager, and the fixed step replayed from a captured HIP graph that holds ``out, g_new = step_graph(x, g);
+    g.copy_(g_new)`` -- the form a sequence runs per frame.  Then the library calls alone on given features.  Interleaved repeats."""
+    from dagl_amd import ops
+    from dagl_amd.ce import CE
+    from dagl_amd.synth import make_ce_params, make_features
+    dev = torch.device("cuda:0")
+    x = torch.from_numpy(make_features(7, 1, 64, H, W)).to(dev)
+    x2 = torch.roll(x, (1, 1), (2, 3))
+    name, mode, k, variant, gain = ("adaptive AND top-16 (sparse, gain 1.7)", "adaptive_topk", 16, "sparse", 1.7) if big else \
+        ("top-k 8", "topk", 8, "default", 1.65)
+    prm = {n: torch.from_numpy(a) for n, a in make_ce_params(7, variant=variant, sparse_gain=gain).items()}
+    ce = CE(in_channels=64)
+    ce.load_state_dict(prm, strict=True)
+    ce.select_mode, ce.select_k = mode, k
+    ce = ce.to(dev).eval()
+    fmt = lambda t: f"{t[0]:.3f} ms ({t[1]:.3f}-{t[2]:.3f})"
+    f16 = dict(radius=1, features="split16")
+    with torch.no_grad():
+        g = ce.graph(x)
+        g.max_degree()
+        fg = g.to_fixed(k)
+        out_csr, g_csr = ce.step_graph(x2, g, **f16)
+        out_fix, g_fix = ce.step_graph(x2, fg, **f16)
+        back = g_fix.to_csr()
+        same = torch.equal(out_csr, out_fix) and all(torch.equal(getattr(back, n), getattr(g_csr, n)) for n in ("row_off", "key", "weight"))
+        # the captured frame: static input, static graph, the new graph copied over the old one inside the HIP graph
+        xs, gs = x2.clone(), fg._like(fg.key.clone(), fg.weight.clone(), fg.score.clone(), fg.deg.clone())
+        torch.cuda.synchronize()
+        hip_graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(hip_graph):
+            out_s, g_new = ce.step_graph(xs, gs, **f16)
+            gs.copy_(g_new)
+        hip_graph.replay()
+        torch.cuda.synchronize()
+        replay_same = torch.equal(out_s, out_fix) and torch.equal(gs.key, g_fix.key)
+
+        def eager_frame():
+            o, n = ce.step_graph(xs, gs, **f16)
+            gs.copy_(n)
+
+        legs = _interleaved({"csr": lambda: ce.step_graph(x2, g, **f16), "csr_alone": lambda: ce.step_graph(x2, g, want_graph=False, **f16),
+                             "fixed": lambda: ce.step_graph(x2, fg, **f16), "fixed_copy": eager_frame, "replay": hip_graph.replay,
+                             "features": lambda: ce._graph_features(x2, mode != "topk", True, False)})
+        wq, xk, tau, b2p, _ = ce._graph_features(x2, mode != "topk", True, False)
+        wq, xk, b2p, tau = wq.contiguous(), xk.contiguous(), b2p.contiguous(), (tau.contiguous() if tau is not None else None)
+        ws, wsf = ops.Workspace(), ops.Workspace()
+        call = dict(radius=1, tau=tau, k=k, scale=float(ce.softmax_scale))
+        lib = _interleaved({
+            "csr": lambda: ops.graph_step(wq, xk, b2p, g.row_off, g.key, workspace=ws, max_row_edges=g.max_degree(), **call),
+            "csr_alone": lambda: ops.graph_step(wq, xk, b2p, g.row_off, g.key, want_graph=False, workspace=ws, max_row_edges=g.max_degree(),
+                                                **call),
+            "fixed": lambda: ops.graph_step_fixed(wq, xk, b2p, fg.key, fg.deg, width_out=k, workspace=wsf, **call)})
+    print(f"[1,64,{H},{W}] {name}: graph(x) {g.n_edges} edges, degree max {g.max_degree()}, {fg.width} slots per row; the fixed step gives the "
+          f"CSR step's bits: {same}; the replayed one: {replay_same}\n"
+          f"    step_graph on the CSR, with its graph {fmt(legs['csr'])}; without its graph {fmt(legs['csr_alone'])}\n"
+          f"    step_graph on the FixedGraph, eager {fmt(legs['fixed'])} = {legs['fixed'][0] / legs['csr'][0]:.2f} of the CSR step with its "
+          f"graph; eager with g.copy_(g_new) {fmt(legs['fixed_copy'])}\n"
+          f"    the captured frame (step_graph + g.copy_(g_new)) replayed {fmt(legs['replay'])} = "
+          f"{legs['replay'][0] / legs['fixed_copy'][0]:.2f} of the same frame eager, {legs['replay'][0] / legs['csr'][0]:.2f} of the CSR step "
+          f"with its graph (the two frames with the copy run on the graph as it moves: {gs.n_edges()} edges after the first frame); "
+          f"the features alone (_graph_features) {fmt(legs['features'])}\n"
+          f"    the library calls on given features: ops.graph_step with its graph {fmt(lib['csr'])}, without {fmt(lib['csr_alone'])}; "
+          f"ops.graph_step_fixed {fmt(lib['fixed'])}", flush=True)
+
+
 def _recall(r, full):
     """Edges of ``full`` that ``r`` holds, over the edges of ``full`` (as ``refresh_leg`` counts it)."""
     hit = torch.isin(r.rows() * r.N + r.key.long(), full.rows() * full.N + full.key.long()).sum()
@@ -481,6 +575,8 @@ def main():
         return train_graph_leg(*((int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (256, 256)))
     if len(sys.argv) > 1 and sys.argv[1] == "--search":
         return search_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
+    if len(sys.argv) > 1 and sys.argv[1] == "--fixed":
+        return fixed_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--step":
         return step_leg(*((int(sys.argv[2]), int(sys.argv[3]), True) if len(sys.argv) > 3 else (256, 256, False)))
     if len(sys.argv) > 1 and sys.argv[1] == "--refresh":
