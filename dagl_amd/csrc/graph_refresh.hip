@@ -54,6 +54,11 @@
 // known before the launch, nothing is read on the host and the call with its graph output can be captured.  A row that keeps more
 // than width_out entries (possible only without a rank cut) comes out EMPTY and is counted in status[0].
 //
+// The fixed-width stage entry, dagl_graph_stage_step_fixed, is that entry for the four heads of a CES stage: graph_stage_fixed_rows_kernel
+// runs rf_row's FIXED flavour over the 4 B L head-major rows of the stage's slot arrays in ONE launch (the heads' operands by value, as in
+// the stage search; the hash and the features from the head-local row), then launch_stage_fold_mix -- or, without the value operands,
+// the graph alone.  The memset of the status words, the row launch, the fold + mix: capturable with its graph output.
+//
 // A row longer than max_row_edges comes out EMPTY and is counted in status[0] (integer atomics on the two status words are the only
 // atomics); it is never truncated.  Every offset is clamped to [0, E], every key is range-tested before an address is formed, a row's
 // candidates are bounded by the LDS arrays and its kept entries by its own staging region, the compaction by `capacity`: no array content
@@ -562,6 +567,24 @@ __global__ __launch_bounds__(T) void graph_stage_search_rows_kernel(GtArgs a, Rf
     rf_row<T, CAP, AGG, true>(a, f, v, row, row - h * head_rows, sr);
 }
 
+// dagl_graph_stage_step_fixed's: the FIXED flavour over the 4 B L head-major rows of a CES stage's fixed-width graph in ONE launch (a
+// kernel of its own: those above keep their arguments and their device code).  The heads' operands come as in the kernel above; row r
+// addresses its input slots, the adjacent rows' (r +- 1, r +- Lw: the grid position is r % L and head_rows is a multiple of L, so a
+// source never lies in another image or head), its output slots, its degree and its aggregated row; lrow = r - h head_rows the features,
+// the margin, the value map and the hash.  a.n_rows = 4 head_rows
+template <int T, int CAP, bool AGG, bool SEARCH>
+__global__ __launch_bounds__(T) void graph_stage_fixed_rows_kernel(GtArgs a, RfArgs f, GaArgs v, RsArgs sr, RxArgs fx, RsHeads hd,
+                                                                   int head_rows) {
+    const int row = (int)blockIdx.x;                             // < 4 head_rows (the launch)
+    const int h = row / head_rows;
+    // (selects, not an index: the table stays in scalar registers)
+    a.wq = h == 0 ? hd.wq[0] : (h == 1 ? hd.wq[1] : (h == 2 ? hd.wq[2] : hd.wq[3]));
+    a.x = h == 0 ? hd.x[0] : (h == 1 ? hd.x[1] : (h == 2 ? hd.x[2] : hd.x[3]));
+    a.tau = h == 0 ? hd.tau[0] : (h == 1 ? hd.tau[1] : (h == 2 ? hd.tau[2] : hd.tau[3]));
+    if (AGG) v.src = h == 0 ? hd.b2p[0] : (h == 1 ? hd.b2p[1] : (h == 2 ? hd.b2p[2] : hd.b2p[3]));
+    rf_row<T, CAP, AGG, SEARCH, true>(a, f, v, row, row - h * head_rows, sr, fx);
+}
+
 // graph_refresh_compact_kernel (below) for the SEARCH flavour: a row's staged entries start at rs_region_start.  deg[row] > 0 only where
 // rf_row found the whole region inside the staging arrays
 __global__ __launch_bounds__(RF_COPY_ROWS * 64) void graph_search_compact_kernel(int n_rows, int w2, long long E, RsArgs sr,
@@ -1045,9 +1068,146 @@ static int launch_graph_step_fixed(hipStream_t s, int B, const Grid& g, const Fi
 }
 #undef DAGL_FIXED_LAUNCH
 
+template <bool AGG, bool SEARCH>
+static void launch_stage_fixed_rows(hipStream_t s, int n_rows, bool wave, const GtArgs& a, const RfArgs& f, const GaArgs& v, const RsArgs& sr,
+                                    const RxArgs& fx, const RsHeads& hd, int head_rows) {
+    if (wave) {
+        hipLaunchKernelGGL((graph_stage_fixed_rows_kernel<64, RF_WAVE_CAP, AGG, SEARCH>), dim3((unsigned)n_rows), dim3(64), 0, s, a, f, v, sr,
+                           fx, hd, head_rows);
+    } else {
+        hipLaunchKernelGGL((graph_stage_fixed_rows_kernel<256, RF_CAP, AGG, SEARCH>), dim3((unsigned)n_rows), dim3(256), 0, s, a, f, v, sr,
+                           fx, hd, head_rows);
+    }
+}
+
+// The fixed-width step of a whole CES stage (dagl_graph_stage_step_fixed): r's slot arrays and degrees run over the 4 B L head-major
+// rows, st holds the heads' operands (st.b2p4 / r.out null: the graph alone).  The status words, ONE row launch
+// (graph_stage_fixed_rows_kernel: every row leaves whole, nothing to clear), then the fold + mix + residual of the four heads' rows
+static int launch_graph_stage_step_fixed(hipStream_t s, int B, const Grid& g, const FixedCall& r, const StageStepCall& st, void* workspace) {
+    const int head_rows = B * g.L, n_rows = 4 * head_rows;
+    const bool agg = r.out != nullptr, search = r.propagate || r.explore;
+    DAGL_HIP_TRY(hipMemsetAsync(r.status, 0, 2 * sizeof(int64_t), s));
+    const RefreshWs w = refresh_carve(workspace, (size_t)n_rows, 0, agg, false);
+    GraphAttendCall c = r.c;
+    c.wq_rows = st.wq4[0]; c.x_rows = st.x4[0];                  // (the kernel takes every head's from the table)
+    const GtArgs a = gt_args(4 * B, g, c);                       // n_rows = 4 B L
+    RfArgs f{};
+    f.W = g.W; f.H = g.H; f.radius = r.radius; f.max_row_edges = r.width_in; f.k = r.keep_all ? 0 : r.k; f.keep_all = r.keep_all ? 1 : 0;
+    f.deg = r.deg_out; f.st_key = r.key_out; f.st_score = r.score_out; f.st_weight = r.weight_out;
+    f.status = reinterpret_cast<unsigned long long*>(r.status);
+    const RxArgs fx{r.deg_in, r.width_in, r.width_out};
+    RsArgs sr{};
+    sr.propagate = r.propagate; sr.explore = r.explore; sr.seed = r.seed; sr.Lw = g.Lw;
+    RsHeads hd{};
+    for (int h = 0; h < 4; ++h) {
+        hd.wq[h] = st.wq4[h]; hd.x[h] = st.x4[h]; hd.tau[h] = st.tau4 ? st.tau4[h] : nullptr; hd.b2p[h] = agg ? st.b2p4[h] : nullptr;
+    }
+    GaArgs v{};
+    if (agg) {
+        v = ga_map_args(B, g, st.b2p4[0], nullptr, nullptr, nullptr, 0);      // (L, the map geometry: a head's; src from the table)
+        v.out = w.agg;
+    }
+    const bool wave = !r.block_rows && rf_row_bound(r.width_in, r.radius, r.propagate, r.explore) <= RF_WAVE_CAP;
+    if (search && agg) launch_stage_fixed_rows<true, true>(s, n_rows, wave, a, f, v, sr, fx, hd, head_rows);
+    else if (search) launch_stage_fixed_rows<false, true>(s, n_rows, wave, a, f, v, sr, fx, hd, head_rows);
+    else if (agg) launch_stage_fixed_rows<true, false>(s, n_rows, wave, a, f, v, sr, fx, hd, head_rows);
+    else launch_stage_fixed_rows<false, false>(s, n_rows, wave, a, f, v, sr, fx, hd, head_rows);
+    DAGL_LAUNCH_CHECK("graph_stage_fixed_rows_kernel");
+    return agg ? launch_stage_fold_mix(s, B, g, w.agg, st.x, st.mix_w, st.mix_b, r.out) : DAGL_OK;
+}
+
 static bool ranges_overlap(const void* p, size_t pn, const void* q, size_t qn) {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return p && q && a < b + qn && b < a + pn;
+}
+
+// the checks and the call of the fixed-width entries, written once.  heads = 1: dagl_graph_step_fixed -- the tables hold one pointer,
+// mix_x / mix_w / mix_b are not looked at; heads = 4: dagl_graph_stage_step_fixed -- the slot arrays run over the 4 B L head-major rows.
+// b2p / out null: the graph alone.  tau: null, or a table (heads = 4: set for all the heads or for none)
+static int graph_fixed_entry(const char* who, void* stream, int heads, int B, int H, int W, const float* const* wq, const float* const* x,
+                             const float* const* b2p, const int32_t* key_in, const int32_t* deg_in, int width_in, int radius,
+                             const float* const* tau, int k, float scale, int flags, int propagate, int explore, uint32_t seed,
+                             const float* mix_x, const float* mix_w, const float* mix_b, float* out, int32_t* key_out, float* weight_out,
+                             float* score_out, int32_t* deg_out, int width_out, int64_t* status, void* workspace, size_t workspace_bytes) {
+    const bool stage = heads == 4;
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    if (stage) DAGL_REQUIRE((int64_t)4 * B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    DAGL_REQUIRE(radius >= 0 && radius <= RF_MAX_RADIUS, "%s: radius=%d outside [0, %d]", who, radius, RF_MAX_RADIUS);
+    DAGL_REQUIRE(width_in >= 1 && width_out >= 1, "%s: width_in=%d, width_out=%d: each at least 1", who, width_in, width_out);
+    const Grid g = make_grid(H, W);
+    const int64_t n_rows = (int64_t)heads * B * g.L;
+    DAGL_REQUIRE(n_rows * width_in < (1ll << 31) && n_rows * width_out < (1ll << 31), "%s: %sB L width = %lld slots, 2^31 or more", who,
+                 stage ? "4 " : "", (long long)(n_rows * (width_in > width_out ? width_in : width_out)));
+    if ((rc = search_args_ok(who, propagate, explore))) return rc;
+    if (stage) {
+        DAGL_REQUIRE(wq && x, "%s: null pointer table", who);
+        const int given = (b2p != nullptr) + (mix_x != nullptr) + (mix_w != nullptr) + (mix_b != nullptr) + (out != nullptr);
+        DAGL_REQUIRE(given == 0 || given == 5, "%s: b2p4, x, mix_w, mix_b and out come together (all null: the graph alone)", who);
+    } else {
+        DAGL_REQUIRE((b2p == nullptr) == (out == nullptr), "%s: b2p and out come together (both null: the refresh alone)", who);
+    }
+    const bool step = out != nullptr;
+    static const int64_t no_offsets = 0;      // (the shared null test asks for offsets; this form has none)
+    int with_tau = 0;
+    for (int h = 0; h < heads; ++h) {
+        if ((rc = graph_operands_ok(who, wq[h], x[h], &no_offsets, key_in, n_rows * width_in, scale, flags,
+                                    deg_in && key_out && weight_out && score_out && deg_out && status && (!step || b2p[h]),
+                                    DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
+            return rc;
+        if (step) DAGL_REQUIRE(((uintptr_t)b2p[h] % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+        with_tau += tau && tau[h];
+    }
+    DAGL_REQUIRE(with_tau == 0 || with_tau == heads, "%s: tau given for %d of the four heads (all or none)", who, with_tau);
+    if (stage && step && (rc = stage_mix_operands_ok(who, mix_x, mix_w, mix_b, out))) return rc;
+    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
+    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
+    if (k > 0 && !keep_all) {
+        const int most = k < g.N ? k : g.N;
+        DAGL_REQUIRE(width_out >= most, "%s: width_out=%d < min(k, N) = %d entries a row may keep", who, width_out, most);
+    }
+    if (rf_row_bound(width_in, radius, propagate, explore) > RF_CAP) {
+        set_error("%s: (1 + 4 propagate) width_in (2 radius + 1)^2 + explore = %lld candidates per row, more than the %d a row may "
+                  "expand into", who, rf_row_bound(width_in, radius, propagate, explore), RF_CAP);
+        return DAGL_ERR_UNSUPPORTED;
+    }
+    {
+        // every output array against every input array (every head's; the stage's mix operands too)
+        const size_t rows = (size_t)n_rows, head_rows = (size_t)B * g.L;
+        const void* in_p[4 * 4 + 5];
+        size_t in_n[4 * 4 + 5];
+        int n_in = 0;
+        for (int h = 0; h < heads; ++h) {
+            in_p[n_in] = wq[h]; in_n[n_in++] = head_rows * D * sizeof(float);
+            in_p[n_in] = x[h]; in_n[n_in++] = (size_t)B * g.N * D * sizeof(float);
+            in_p[n_in] = step ? b2p[h] : nullptr; in_n[n_in++] = (size_t)B * g.Hp * g.Wp * CH * sizeof(float);
+            in_p[n_in] = with_tau ? tau[h] : nullptr; in_n[n_in++] = head_rows * sizeof(float);
+        }
+        in_p[n_in] = key_in; in_n[n_in++] = rows * width_in * sizeof(int32_t);
+        in_p[n_in] = deg_in; in_n[n_in++] = rows * sizeof(int32_t);
+        if (stage) {
+            in_p[n_in] = mix_x; in_n[n_in++] = (size_t)B * 4 * CH * g.N * sizeof(float);
+            in_p[n_in] = mix_w; in_n[n_in++] = (size_t)(4 * CH) * (4 * CH) * sizeof(float);
+            in_p[n_in] = mix_b; in_n[n_in++] = (size_t)(4 * CH) * sizeof(float);
+        }
+        const void* out_p[5] = {out, key_out, weight_out, score_out, deg_out};
+        const size_t out_n[5] = {(size_t)B * heads * CH * g.N * sizeof(float), rows * width_out * sizeof(int32_t),
+                                 rows * width_out * sizeof(float), rows * width_out * sizeof(float), rows * sizeof(int32_t)};
+        for (int i = 0; i < 5; ++i)
+            for (int j = 0; j < n_in; ++j)
+                DAGL_REQUIRE(!ranges_overlap(out_p[i], out_n[i], in_p[j], in_n[j]), "%s: an output array overlaps an input array", who);
+    }
+    const size_t need = refresh_carve(nullptr, (size_t)n_rows, 0, step, false).bytes;
+    if (need > 0 && (rc = check_workspace(who, workspace, workspace_bytes, need))) return rc;
+    FixedCall r{};
+    r.c = graph_attend_call(wq[0], x[0], nullptr, key_in, n_rows * width_in, with_tau ? tau[0] : nullptr, scale, flags);
+    r.deg_in = deg_in; r.width_in = width_in; r.width_out = width_out; r.radius = radius; r.k = k; r.keep_all = keep_all;
+    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
+    r.propagate = propagate; r.explore = explore; r.seed = seed; r.b2p = step ? b2p[0] : nullptr; r.out = out;
+    r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.deg_out = deg_out; r.status = status;
+    if (!stage) return launch_graph_step_fixed((hipStream_t)stream, B, g, r, workspace);
+    const StageStepCall st{wq, x, step ? b2p : nullptr, with_tau ? tau : nullptr, mix_x, mix_w, mix_b};
+    return launch_graph_stage_step_fixed((hipStream_t)stream, B, g, r, st, workspace);
 }
 
 }  // namespace dagl
@@ -1243,55 +1403,29 @@ int dagl_graph_step_fixed(void* stream, int B, int H, int W, const float* wq_row
                           const int32_t* key_in, const int32_t* deg_in, int width_in, int radius, const float* tau, int k, float scale,
                           int flags, int propagate, int explore, uint32_t seed, float* out, int32_t* key_out, float* weight_out,
                           float* score_out, int32_t* deg_out, int width_out, int64_t* status, void* workspace, size_t workspace_bytes) {
-    const char* who = "dagl_graph_step_fixed";
-    int rc = graph_dims_ok(who, B, H, W);
-    if (rc) return rc;
-    DAGL_REQUIRE(radius >= 0 && radius <= RF_MAX_RADIUS, "%s: radius=%d outside [0, %d]", who, radius, RF_MAX_RADIUS);
-    DAGL_REQUIRE(width_in >= 1 && width_out >= 1, "%s: width_in=%d, width_out=%d: each at least 1", who, width_in, width_out);
-    const Grid g = make_grid(H, W);
-    const int64_t n_rows = (int64_t)B * g.L;
-    DAGL_REQUIRE(n_rows * width_in < (1ll << 31) && n_rows * width_out < (1ll << 31), "%s: B L width = %lld slots, 2^31 or more", who,
-                 (long long)(n_rows * (width_in > width_out ? width_in : width_out)));
-    if ((rc = search_args_ok(who, propagate, explore))) return rc;
-    DAGL_REQUIRE((b2p == nullptr) == (out == nullptr), "%s: b2p and out come together (both null: the refresh alone)", who);
-    static const int64_t no_offsets = 0;      // (the shared null test asks for offsets; this form has none)
-    if ((rc = graph_operands_ok(who, wq_rows, x_rows, &no_offsets, key_in, n_rows * width_in, scale, flags,
-                                deg_in && key_out && weight_out && score_out && deg_out && status,
-                                DAGL_GRAPH_REFRESH_KEEP_ALL | DAGL_GRAPH_REFRESH_BLOCK_ROWS)))
-        return rc;
-    if (b2p) DAGL_REQUIRE(((uintptr_t)b2p % 16) == 0, "%s: b2p must be 16-byte aligned", who);
-    DAGL_REQUIRE(k >= 0, "%s: k=%d < 0", who, k);
-    const bool keep_all = (flags & DAGL_GRAPH_REFRESH_KEEP_ALL) != 0;
-    if (k > 0 && !keep_all) {
-        const int most = k < g.N ? k : g.N;
-        DAGL_REQUIRE(width_out >= most, "%s: width_out=%d < min(k, N) = %d entries a row may keep", who, width_out, most);
-    }
-    if (rf_row_bound(width_in, radius, propagate, explore) > RF_CAP) {
-        set_error("%s: (1 + 4 propagate) width_in (2 radius + 1)^2 + explore = %lld candidates per row, more than the %d a row may "
-                  "expand into", who, rf_row_bound(width_in, radius, propagate, explore), RF_CAP);
-        return DAGL_ERR_UNSUPPORTED;
-    }
-    {
-        const size_t rows = (size_t)n_rows;
-        const void* in_p[6] = {wq_rows, x_rows, b2p, key_in, deg_in, tau};
-        const size_t in_n[6] = {rows * D * sizeof(float), (size_t)B * g.N * D * sizeof(float), (size_t)B * g.Hp * g.Wp * CH * sizeof(float),
-                                rows * width_in * sizeof(int32_t), rows * sizeof(int32_t), rows * sizeof(float)};
-        const void* out_p[5] = {out, key_out, weight_out, score_out, deg_out};
-        const size_t out_n[5] = {(size_t)B * CH * g.N * sizeof(float), rows * width_out * sizeof(int32_t), rows * width_out * sizeof(float),
-                                 rows * width_out * sizeof(float), rows * sizeof(int32_t)};
-        for (int i = 0; i < 5; ++i)
-            for (int j = 0; j < 6; ++j)
-                DAGL_REQUIRE(!ranges_overlap(out_p[i], out_n[i], in_p[j], in_n[j]), "%s: an output array overlaps an input array", who);
-    }
-    const size_t need = refresh_carve(nullptr, (size_t)n_rows, 0, out != nullptr, false).bytes;
-    if (need > 0 && (rc = check_workspace(who, workspace, workspace_bytes, need))) return rc;
-    FixedCall r{};
-    r.c = graph_attend_call(wq_rows, x_rows, nullptr, key_in, n_rows * width_in, tau, scale, flags);
-    r.deg_in = deg_in; r.width_in = width_in; r.width_out = width_out; r.radius = radius; r.k = k; r.keep_all = keep_all;
-    r.block_rows = (flags & DAGL_GRAPH_REFRESH_BLOCK_ROWS) != 0;
-    r.propagate = propagate; r.explore = explore; r.seed = seed; r.b2p = b2p; r.out = out;
-    r.key_out = key_out; r.weight_out = weight_out; r.score_out = score_out; r.deg_out = deg_out; r.status = status;
-    return launch_graph_step_fixed((hipStream_t)stream, B, g, r, workspace);
+    return graph_fixed_entry("dagl_graph_step_fixed", stream, 1, B, H, W, &wq_rows, &x_rows, b2p ? &b2p : nullptr, key_in, deg_in, width_in,
+                             radius, tau ? &tau : nullptr, k, scale, flags, propagate, explore, seed, nullptr, nullptr, nullptr, out, key_out,
+                             weight_out, score_out, deg_out, width_out, status, workspace, workspace_bytes);
+}
+
+// the fixed-width step of a whole CES stage: the four heads' rows in ONE row launch, the fused fold + mix; no staging, scan, copy or
+// host read, so the call with its graph output can be captured (no ABI bump: found by symbol)
+size_t dagl_graph_stage_step_fixed_workspace_bytes(int B, int H, int W, int want_out) {
+    const char* who = "dagl_graph_stage_step_fixed_workspace_bytes";
+    if (graph_dims_ok(who, B, H, W)) return 0;
+    if ((int64_t)4 * B * H * W >= (1ll << 30)) { set_error("%s: batch too large for 32-bit row ids", who); return 0; }
+    return refresh_carve(nullptr, (size_t)4 * B * make_grid(H, W).L, 0, want_out != 0, false).bytes;
+}
+
+int dagl_graph_stage_step_fixed(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                                const float* const* b2p4, const int32_t* key_in, const int32_t* deg_in, int width_in, int radius,
+                                const float* const* tau4, int k, float scale, int flags, int propagate, int explore, uint32_t seed,
+                                const float* x, const float* mix_w, const float* mix_b, float* out, int32_t* key_out, float* weight_out,
+                                float* score_out, int32_t* deg_out, int width_out, int64_t* status, void* workspace,
+                                size_t workspace_bytes) {
+    return graph_fixed_entry("dagl_graph_stage_step_fixed", stream, 4, B, H, W, wq_rows4, x_rows4, b2p4, key_in, deg_in, width_in, radius,
+                             tau4, k, scale, flags, propagate, explore, seed, x, mix_w, mix_b, out, key_out, weight_out, score_out, deg_out,
+                             width_out, status, workspace, workspace_bytes);
 }
 
 }  // extern "C"

@@ -197,8 +197,14 @@ class CES(nn.Module):
         A state of ``FixedGraph``s (``state.to_fixed()``) runs head by head -- ``CE.step_graph`` on each head's row views,
         ``FixedGraph.cat``, ``torch.cat`` and the mix convolution, as ``fused=False`` does -- and returns a fixed state; the whole call,
         ``want_graphs=True`` included, reads nothing on the host and can be captured (``state.copy_(new_state)`` inside the capture
-        carries the graphs to the next replay).  ``fused=True`` is refused there (a stage-fused fixed-width launch does not exist),
-        ``fused=None`` means head by head; heads of a stage whose output widths differ are refused before any launch.
+        carries the graphs to the next replay).  ``fused="stage"`` is the stage-fused form there: the heads' features from
+        ``CE._graph_features``, then ONE ``ops.graph_stage_step_fixed`` per stage -- the four heads' rows in one row launch, fold + mix +
+        residual in one launch, the stage's new ``FixedGraph`` made of the call's arrays (no ``cat``); the graphs are the head-by-head
+        ones bit for bit, ``out`` differs by the fp32 roundings of the mix product alone, and the search keywords are served (the launch
+        has the search flavour).  It is refused on a stage that does not qualify (as ``fused=True`` is on a CSR state).  ``fused=None``
+        and ``fused=False`` mean head by head, ``fused=True`` is refused on a fixed state (it names the CSR launch; the fixed-width one
+        is ``fused="stage"``); on a CSR state ``fused="stage"`` means ``True``.  Heads of a stage whose output widths differ are
+        refused before any launch.
 
         Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
         the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
@@ -209,7 +215,11 @@ class CES(nn.Module):
         what = "CES.step_graphs"
         search = dict(propagate=propagate, explore=explore, seed=seed)
         ops._graph_search_operands(what, propagate, explore, seed)
-        if bool(propagate) or explore != 0:
+        self._fused_value(what, fused)
+        stage_fixed = isinstance(fused, str) and isinstance(state, SequenceState) and state.fixed
+        if isinstance(fused, str) and not stage_fixed:
+            fused = True                            # (a CSR state: the stage-fused step it has)
+        if (bool(propagate) or explore != 0) and not stage_fixed:
             if fused:
                 raise DaglError(f"{what}: fused=True with propagate / explore set: the stage-fused step (ops.graph_stage_step) has no "
                                 "search flavour; leave fused at None (head by head) or pass fused=False")
@@ -233,34 +243,98 @@ class CES(nn.Module):
             out = self._between_stages(s, out)
         return out, (SequenceState(new) if want_graphs else None)
 
-    def _step_graphs_fixed(self, x, state, radius, features, want_graphs, fused, search):
-        """``step_graphs`` on a state of ``FixedGraph``s: the refusals of every head of every stage first (no launch, no host read), then
-        head by head."""
+    @staticmethod
+    def _fused_value(what, fused):
+        """``fused`` is None, a bool or "stage"."""
         from ._lib import DaglError
-        from .graph import FixedGraph
-        from .sequence import SequenceState
-        what = "CES.step_graphs"
-        if fused:
-            raise DaglError(f"{what}: fused=True on a state of FixedGraphs: a stage-fused fixed-width launch does not exist; leave fused "
-                            "at None (head by head) or pass fused=False")
+        if not (fused is None or isinstance(fused, bool) or (isinstance(fused, str) and fused == "stage")):
+            raise DaglError(f"{what}: fused={fused!r}, expected None, False, True or 'stage'")
+
+    def _plan_fixed(self, what, x, state, radius, features, fused, search, iters=1):
+        """Every refusal of ``step_graphs`` / ``search_graphs`` on a state of ``FixedGraph``s that depends on a stage, raised before the
+        first launch and without a host read -- every stage sees an input of x's shape, dtype and device -- -> {stage: (radius, k_eff,
+        margin, width_out)}.  ``iters`` > 1: the row bound of the later iterations too, from the width the first one leaves."""
+        from ._lib import ERR_UNSUPPORTED, DaglError
+        from . import ops
+        if fused is True:
+            raise DaglError(f"{what}: fused=True on a state of FixedGraphs: the stage-fused fixed-width launch is fused='stage' "
+                            "(ops.graph_stage_step_fixed); leave fused at None (head by head) or pass fused=False")
+        plan = {}
         for s in (1, 2, 3):
-            widths = []
+            args = []
             for h, hd in enumerate(self._stage_modules(s)[0]):
                 if not isinstance(hd, CE):
                     raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it steps no graph")
-                widths.append(hd._fixed_arguments(x, state.head(s - 1, h), "step_graph", radius, None, "reference", features, **search)[3])
+                args.append(hd._fixed_arguments(x, state.head(s - 1, h), "step_graph", radius, None, "reference", features, **search))
+            widths = [a[3] for a in args]
             if len(set(widths)) != 1:
                 raise DaglError(f"{what}: the heads of stage {s} give graphs of widths {widths}: one FixedGraph per stage needs one width "
                                 "(heads that share select_mode and select_k)")
+            if fused == "stage" and not self._stage_step_fusable(s, x):
+                raise DaglError(f"{what}: fused='stage', but stage {s} does not qualify (four plain CE heads sharing select_mode, "
+                                "select_k, softmax_scale and the default patch geometry, an fp32 input on the GPU)")
+            radius_s, _k, _margin, width_out, propagate, explore, _seed = args[0]
+            bound, cap = ops.graph_search_row_bound(width_out, radius_s, propagate, explore), ops.graph_refresh_max_candidates()
+            if iters > 1 and bound > cap:
+                err = DaglError(f"{what}: after 1 iteration a row of stage {s} holds {width_out} slots: with propagate={bool(propagate)}, "
+                                f"explore={explore} and radius {radius_s} it may expand into {bound} candidates, more than {cap}")
+                err.code = ERR_UNSUPPORTED
+                raise err
+            plan[s] = args[0][:4]
+        return plan
+
+    def _step_graphs_fixed(self, x, state, radius, features, want_graphs, fused, search):
+        """``step_graphs`` on a state of ``FixedGraph``s: the refusals of every head of every stage first (no launch, no host read), then
+        head by head or (``fused="stage"``) one ``ops.graph_stage_step_fixed`` per stage."""
+        from .graph import FixedGraph
+        from .sequence import SequenceState
+        plan = self._plan_fixed("CES.step_graphs", x, state, radius, features, fused, search)
         out, new = x, []
         for s in (1, 2, 3):
             heads, mix = self._stage_modules(s)
-            pairs = [hd.step_graph(out, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs, **search)
-                     for h, hd in enumerate(heads)]
-            if want_graphs:
-                new.append(FixedGraph.cat([g for _, g in pairs]))
-            out = self._between_stages(s, mix(torch.cat([o for o, _ in pairs], dim=1)) + out)
+            if fused == "stage":
+                out_s, g = self._stage_fixed_fused(s, out, state.stages[s - 1], plan[s], features, search, 1)
+            else:
+                pairs = [hd.step_graph(out, state.head(s - 1, h), radius=radius, features=features, want_graph=want_graphs, **search)
+                         for h, hd in enumerate(heads)]
+                g = FixedGraph.cat([g for _, g in pairs]) if want_graphs else None
+                out_s = mix(torch.cat([o for o, _ in pairs], dim=1)) + out
+            new.append(g)
+            out = self._between_stages(s, out_s)
         return out, (SequenceState(new) if want_graphs else None)
+
+    def _stage_fixed_fused(self, s, x, stage, plan, features, search, iters):
+        """Stage ``s`` on its input ``x`` and its ``FixedGraph`` by ``ops.graph_stage_step_fixed`` -> (the stage's output, its new graph):
+        ``iters - 1`` graph-only calls with seeds ``seed + i``, then the step with ``seed + iters - 1``.  The new graph is made of the
+        call's arrays as they are; nothing is read on the host."""
+        from . import ops
+        heads, mix = self._stage_modules(s)
+        radius, k_eff, margin, width_out = plan
+        fast = features == "split16"
+        x = x.contiguous()
+        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        wq4, x4, b2p4 = ([f[i].contiguous() for f in feats] for i in (0, 1, 3))
+        common = dict(width_out=width_out, radius=radius, tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff,
+                      scale=float(heads[0].softmax_scale), workspace=self._ws_step[s], propagate=bool(search["propagate"]),
+                      explore=search["explore"], hw=(x.shape[2], x.shape[3]))
+        key, deg = stage.key, stage.deg
+        for i in range(iters - 1):
+            arrays = ops.graph_stage_step_fixed(wq4, x4, None, key, deg, seed=search["seed"] + i, **common)[1]
+            key, deg = arrays["key"], arrays["deg"]
+        out, arrays, _status = ops.graph_stage_step_fixed(wq4, x4, b2p4, key, deg, x, mix.weight.detach().contiguous(),
+                                                          mix.bias.detach().contiguous(), seed=search["seed"] + iters - 1, **common)
+        weight, score = arrays["weight"], arrays["score"]
+        if fast:
+            # a head that left the split-fp16 range NaN-fills the stage's output and its own rows of the graph, filler included: 0 or NaN
+            # per head, added to the head's quarter of the arrays
+            for f in feats:
+                out = f[4](out)
+            verdict = torch.cat([f[4](weight.new_zeros(1)) for f in feats])[:, None]
+            weight = (weight.view(4, -1) + verdict).view_as(weight)
+            score = (score.view(4, -1) + verdict).view_as(score)
+        g = stage._like(arrays["key"], weight, score, arrays["deg"])
+        g.mode, g.k = heads[0].select_mode, k_eff
+        return out, g
 
     def forward_on_graphs(self, x, state, *, features: str = "fp32", backward: str = "two_ops"):
         """The module's output for ``x`` on the FROZEN graphs of ``state`` -> ``out``: ``forward``'s wiring with every head run as
@@ -396,7 +470,18 @@ class CES(nn.Module):
         ``CE._refresh_arguments``, a state that does not fit the input, and ``ops.graph_search_row_bound`` above
         ``ops.graph_refresh_max_candidates()`` (``code == ERR_UNSUPPORTED``) -- that bound is looked at again before every iteration, on
         the graph the previous one left.  Always under ``torch.no_grad()``; the modules' state is untouched; each stage has one workspace
-        (``step_graphs``'s)."""
+        (``step_graphs``'s).
+
+        A state of ``FixedGraph``s (``state.to_fixed()``) is served without a host read, so the whole call -- any ``iters``,
+        ``want_graphs=True`` included -- can be captured: ``SequenceState.start(...).to_fixed(k)`` followed by
+        ``search_graphs(iters=n, fused="stage")`` is a capturable key frame.  The form is asked for by name there: ``fused=False``
+        runs head by head (``CE.refresh_graph`` / ``CE.step_graph`` on each head's row views: the definition), ``fused="stage"`` runs
+        ``ops.graph_stage_step_fixed`` once per iteration and stage (``iters - 1`` graph-only calls, then the step), ``fused=True`` is
+        refused as in ``step_graphs``.  ``fused=None`` on a fixed state keeps the refusal callers have met so far -- it names the two
+        served values and ``state.to_csr()`` --: the default of this method means "the CSR's fused search where a stage qualifies", and
+        no fixed-width form is what that default has ever returned.  On a CSR state ``fused="stage"`` means ``True``.  Every
+        iteration's row bound is looked at before the first launch, from the widths alone: a rank-cut mode leaves ``k`` slots per row
+        after the first iteration, "adaptive" keeps the state's width."""
         from ._lib import DaglError
         from . import ops
         from .sequence import SequenceState
@@ -412,18 +497,51 @@ class CES(nn.Module):
             raise DaglError(f"{what}: a SequenceState expected, got {type(state).__name__}")
         if not isinstance(x, torch.Tensor) or x.dim() != 4:
             raise DaglError(f"{what}: expected [B,C,H,W]")
-        if state.fixed:
-            raise DaglError(f"{what}: a state of FixedGraphs serves step_graphs only; pass state.to_csr()")
+        self._fused_value(what, fused)
+        if state.fixed and fused is None:
+            raise DaglError(f"{what}: a state of FixedGraphs is searched by name: pass fused='stage' (ops.graph_stage_step_fixed) or "
+                            "fused=False (head by head); the default form serves the CSR: pass state.to_csr()")
         B = x.shape[0]
         g0 = state.stages[0]
         if (g0.B, g0.H, g0.W) != (4 * B, x.shape[2], x.shape[3]):
             raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={B} H={x.shape[2]} W={x.shape[3]}")
+        if state.fixed:
+            return self._search_graphs_fixed(x, state, iters, radius, features, want_graphs, fused, search)
+        if isinstance(fused, str):
+            fused = True                            # (a CSR state: the stage-fused search step it has)
         plan = self._plan_step(x, state, radius, features, want_graphs, fused, search, what=what)
         out, new = x, []
         for s in (1, 2, 3):
             out, g = self._search_stage(s, out, state, plan[s], iters, features, want_graphs, search)
             new.append(g)
             out = self._between_stages(s, out)
+        return out, (SequenceState(new) if want_graphs else None)
+
+    def _search_graphs_fixed(self, x, state, iters, radius, features, want_graphs, fused, search):
+        """``search_graphs`` on a state of ``FixedGraph``s: the refusals first (every iteration's row bound from the widths alone: no
+        launch, no host read), then head by head -- ``CE.refresh_graph`` / ``CE.step_graph`` on each head's row views -- or
+        (``fused="stage"``) ``ops.graph_stage_step_fixed`` once per iteration and stage."""
+        from .graph import FixedGraph
+        from .sequence import SequenceState
+        plan = self._plan_fixed("CES.search_graphs", x, state, radius, features, fused, search, iters)
+        seed = search["seed"]
+        kw = dict(radius=radius, features=features, propagate=search["propagate"], explore=search["explore"])
+        out, new = x, []
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            if fused == "stage":
+                out_s, g = self._stage_fixed_fused(s, out, state.stages[s - 1], plan[s], features, search, iters)
+            else:
+                pairs = []
+                for h, hd in enumerate(heads):
+                    g = state.head(s - 1, h)
+                    for i in range(iters - 1):
+                        g = hd.refresh_graph(out, g, seed=seed + i, **kw)
+                    pairs.append(hd.step_graph(out, g, seed=seed + iters - 1, want_graph=want_graphs, **kw))
+                g = FixedGraph.cat([g for _, g in pairs]) if want_graphs else None
+                out_s = mix(torch.cat([o for o, _ in pairs], dim=1)) + out
+            new.append(g)
+            out = self._between_stages(s, out_s)
         return out, (SequenceState(new) if want_graphs else None)
 
     def _search_stage(self, s, x, state, plan, iters, features, want_graphs, search):
@@ -539,15 +657,15 @@ class RR(nn.Module):
     @torch.no_grad()
     def step_graphs(self, x, state, **kw):
         """A sequence step of the network -> ``(out, SequenceState | None)``: ``forward`` with ``CES.step_graphs(., state, **kw)`` where the
-        ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused``, ``propagate``, ``explore``, ``seed`` as there); always under ``torch.no_grad()``.  The ``CES``'s
+        ``CES`` sits (``radius``, ``features``, ``want_graphs``, ``fused`` -- ``"stage"`` on a fixed state included --, ``propagate``, ``explore``, ``seed`` as there); always under ``torch.no_grad()``.  The ``CES``'s
         refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
         return self._forward_around_ces(x, lambda ces, t: ces.step_graphs(t, state, **kw))
 
     @torch.no_grad()
     def search_graphs(self, x, state, **kw):
         """The search step of the network -> ``(out, SequenceState | None)``: ``forward`` with ``CES.search_graphs(., state, **kw)`` where
-        the ``CES`` sits (``iters``, ``radius``, ``propagate``, ``explore``, ``seed``, ``features``, ``want_graphs``, ``fused`` as there);
-        always under ``torch.no_grad()``.  The ``CES``'s refusals are raised when it is reached."""
+        the ``CES`` sits (``iters``, ``radius``, ``propagate``, ``explore``, ``seed``, ``features``, ``want_graphs``, ``fused`` as there, a
+        fixed state and ``fused="stage"`` included); always under ``torch.no_grad()``.  The ``CES``'s refusals are raised when it is reached."""
         return self._forward_around_ces(x, lambda ces, t: ces.search_graphs(t, state, **kw))
 
     @torch.no_grad()

@@ -947,20 +947,45 @@ def graph_step_fixed(wq_rows, x_rows, b2p, key, deg, *, width_out: int, radius: 
     lib = _lib.load()
     who = "graph_step_fixed"
     propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
-    _need(wq_rows, "wq_rows"); _need(x_rows, "x_rows"); _need(key, "key", torch.int32); _need(deg, "deg", torch.int32)
+    n_rows, width_in, width_out = _graph_fixed_slots(who, key, deg, width_out)
+    B, H, W, L = _graph_fixed_head(who, wq_rows, x_rows, b2p, tau, hw)
+    if n_rows != B * L or deg.numel() != n_rows:
+        raise DaglError(f"{who}: key holds {n_rows} rows and deg {deg.numel()} degrees, expected B*L = {B * L}")
+    flags, radius, k = _graph_fixed_flags(who, normalize, keep_all, block_rows, radius, k, width_out, H * W)
+    dev = wq_rows.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_step_fixed_workspace_bytes", B, H, W, 1) if b2p is not None \
+        else (None, None, 0)
+    out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32) if b2p is not None else None
+    key_out, weight, score, deg_out, status = _graph_fixed_arrays(dev, n_rows, width_out)
+    check(lib.dagl_graph_step_fixed(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), _ptr(b2p), key.data_ptr(), deg.data_ptr(),
+                                    width_in, radius, _ptr(tau), k, float(scale), flags, propagate, explore, seed, _ptr(out),
+                                    key_out.data_ptr(), weight.data_ptr(), score.data_ptr(), deg_out.data_ptr(), width_out,
+                                    status.data_ptr(), a, nbytes), "dagl_graph_step_fixed")
+    del buf
+    return out, dict(key=key_out, weight=weight, score=score, deg=deg_out), status
+
+
+def _graph_fixed_slots(who: str, key, deg, width_out):
+    """The slot array and the degrees of a fixed-width call -> (rows, width_in, width_out)."""
+    _need(key, "key", torch.int32); _need(deg, "deg", torch.int32)
+    if key.dim() != 2 or key.shape[1] < 1 or deg.dim() != 1:
+        raise DaglError(f"{who}: expected key [B*L, width >= 1] and deg [B*L], got {tuple(key.shape)} and {tuple(deg.shape)}")
+    width_out = int(width_out)
+    if width_out < 1:
+        raise DaglError(f"{who}: width_out={width_out} < 1")
+    return key.shape[0], key.shape[1], width_out
+
+
+def _graph_fixed_head(who: str, wq_rows, x_rows, b2p, tau, hw):
+    """What a fixed-width call asks of one head's operands (``_graph_refresh_operands``' checks without the offsets: this form has
+    none) -> (B, H, W, L).  ``b2p`` None: no value map, ``hw`` names the map where L and N leave it open."""
+    _need(wq_rows, "wq_rows"); _need(x_rows, "x_rows")
     if b2p is not None:
         _need(b2p, "b2p")
         map_hw = _value_map(who, b2p)[1:]
         if hw is not None and tuple(int(v) for v in hw) != tuple(map_hw):
             raise DaglError(f"{who}: hw={tuple(hw)} but b2p is the value map of a {map_hw[0]}x{map_hw[1]} image")
         hw = map_hw
-    if key.dim() != 2 or key.shape[1] < 1 or deg.dim() != 1:
-        raise DaglError(f"{who}: expected key [B*L, width >= 1] and deg [B*L], got {tuple(key.shape)} and {tuple(deg.shape)}")
-    n_rows, width_in = key.shape
-    width_out = int(width_out)
-    if width_out < 1:
-        raise DaglError(f"{who}: width_out={width_out} < 1")
-    # (``_graph_refresh_operands``' checks without the offsets: this form has none)
     if wq_rows.dim() != 3 or x_rows.dim() != 3 or wq_rows.shape[2] != D or x_rows.shape[2] != D or wq_rows.shape[0] != x_rows.shape[0]:
         raise DaglError(f"{who}: expected wq_rows [B,L,{D}] and x_rows [B,N,{D}], got {tuple(wq_rows.shape)} and {tuple(x_rows.shape)}")
     B, L, N = wq_rows.shape[0], wq_rows.shape[1], x_rows.shape[1]
@@ -973,36 +998,32 @@ def graph_step_fixed(wq_rows, x_rows, b2p, key, deg, *, width_out: int, radius: 
     if H * W != N or math.prod(query_grid(H, W)) != L:
         raise DaglError(f"{who}: a {H}x{W} map has {math.prod(query_grid(H, W))} queries and {H * W} keys, the feature rows hold {L} "
                         f"and {N}")
-    if n_rows != B * L or deg.numel() != n_rows:
-        raise DaglError(f"{who}: key holds {n_rows} rows and deg {deg.numel()} degrees, expected B*L = {B * L}")
     if tau is not None:
         _need(tau, "tau")
         if tau.numel() != B * L:
             raise DaglError(f"{who}: tau holds {tau.numel()} values, expected B*L = {B * L}")
+    if b2p is not None and b2p.shape[0] != B:
+        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
+    return B, H, W, L
+
+
+def _graph_fixed_flags(who: str, normalize, keep_all, block_rows, radius, k, width_out: int, N: int):
+    """The flags of a fixed-width call and the room a rank cut needs -> (flags, radius, k)."""
     if normalize not in _GRAPH_NORMALIZE:
         raise DaglError(f"{who}: normalize={normalize!r}, expected 'reference' or 'edges'")
     flags = _GRAPH_NORMALIZE[normalize] | (_lib.GRAPH_REFRESH_KEEP_ALL if keep_all else 0) \
         | (_lib.GRAPH_REFRESH_BLOCK_ROWS if block_rows else 0)
     radius, k = int(radius), int(k)
-    if b2p is not None and b2p.shape[0] != B:
-        raise DaglError(f"{who}: b2p holds {b2p.shape[0]} images, the feature rows {B}")
-    if k > 0 and not keep_all and width_out < min(k, H * W):
-        raise DaglError(f"{who}: width_out={width_out} < min(k, N) = {min(k, H * W)} entries a row may keep")
-    dev = wq_rows.device
-    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_step_fixed_workspace_bytes", B, H, W, 1) if b2p is not None \
-        else (None, None, 0)
-    out = torch.empty(B, 16, H, W, device=dev, dtype=torch.float32) if b2p is not None else None
-    key_out = torch.empty(n_rows, width_out, device=dev, dtype=torch.int32)
-    weight = torch.empty(n_rows, width_out, device=dev, dtype=torch.float32)
-    score = torch.empty(n_rows, width_out, device=dev, dtype=torch.float32)
-    deg_out = torch.empty(n_rows, device=dev, dtype=torch.int32)
-    status = torch.empty(2, device=dev, dtype=torch.int64)
-    check(lib.dagl_graph_step_fixed(_stream(), B, H, W, wq_rows.data_ptr(), x_rows.data_ptr(), _ptr(b2p), key.data_ptr(), deg.data_ptr(),
-                                    width_in, radius, _ptr(tau), k, float(scale), flags, propagate, explore, seed, _ptr(out),
-                                    key_out.data_ptr(), weight.data_ptr(), score.data_ptr(), deg_out.data_ptr(), width_out,
-                                    status.data_ptr(), a, nbytes), "dagl_graph_step_fixed")
-    del buf
-    return out, dict(key=key_out, weight=weight, score=score, deg=deg_out), status
+    if k > 0 and not keep_all and width_out < min(k, N):
+        raise DaglError(f"{who}: width_out={width_out} < min(k, N) = {min(k, N)} entries a row may keep")
+    return flags, radius, k
+
+
+def _graph_fixed_arrays(dev, n_rows: int, width_out: int):
+    """The output arrays of a fixed-width call -> (key, weight, score, deg, status): sizes known before the launch."""
+    return (torch.empty(n_rows, width_out, device=dev, dtype=torch.int32), torch.empty(n_rows, width_out, device=dev, dtype=torch.float32),
+            torch.empty(n_rows, width_out, device=dev, dtype=torch.float32), torch.empty(n_rows, device=dev, dtype=torch.int32),
+            torch.empty(2, device=dev, dtype=torch.int64))
 
 
 def _stage_mix_operands(who: str, x, mix_w, mix_b):
@@ -1111,6 +1132,64 @@ def graph_stage_step(wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, *, 
     if not want_graph:
         return out, None, status
     return out, _graph_refresh_result(who, head, key_out, weight, score, max_row_edges), status
+
+
+@_on_device
+def graph_stage_step_fixed(wq_rows4, x_rows4, b2p4, key, deg, x=None, mix_w=None, mix_b=None, *, width_out: int, radius: int = 1,
+                           tau4=None, k: int = 0, scale: float = 10.0, normalize: str = "reference", keep_all: bool = False,
+                           propagate=False, explore: int = 0, seed: int = 0, workspace: "Workspace | None" = None, hw=None,
+                           block_rows: bool = False):
+    """``graph_step_fixed`` for the four heads of a ``CES`` stage in ONE row launch and the stage's mix on the result
+    (``dagl_graph_stage_step_fixed``, csrc/graph_refresh.hip) -> (out [B,64,H,W] | None, dict(key, weight, score, deg), status).
+    wq_rows4 / x_rows4 / b2p4 / tau4, x, mix_w, mix_b as ``graph_stage_step``; ``key`` [4*B*L, width_in] int32 and ``deg`` [4*B*L]
+    int32 the stage's fixed-width graph over the head-major rows, row ``(h * B + b) * L + i`` = query ``i`` of image ``b`` under head
+    ``h``.  The dict's arrays run over the same rows at ``width_out``: rows ``h*B*L .. (h+1)*B*L`` are, bit for bit and filler
+    included, what ``graph_step_fixed`` returns for head h's operands and its rows of the input with the same arguments (the random
+    keys are hashed from the head-local row, propagation never leaves an image); ``out`` is ``ces_stage_fold_mix`` of the heads'
+    aggregated rows.  ``status``: device int64[2] -- the rows that came out empty for their length summed over the heads, the largest
+    candidate count.
+
+    ``b2p4``, ``x``, ``mix_w`` and ``mix_b`` all None: the graph alone (``out`` is None) -- the graph-only iterations of a search;
+    ``hw`` then names the map where L and N leave it open.  The memset of the status words, one row launch, the fold + mix: no
+    staging, scan or copy, and NOTHING is read on the host, so every form of the call can be captured with its graph output."""
+    lib = _lib.load()
+    who = "graph_stage_step_fixed"
+    propagate, explore, seed = _graph_search_operands(who, propagate, explore, seed)
+    step = b2p4 is not None
+    if (x is not None, mix_w is not None, mix_b is not None) != (step,) * 3:
+        raise DaglError(f"{who}: b2p4, x, mix_w and mix_b come together (all None: the graph alone)")
+    tables = (("wq_rows4", wq_rows4), ("x_rows4", x_rows4)) + ((("b2p4", b2p4),) if step else ()) \
+        + ((("tau4", tau4),) if tau4 is not None else ())
+    for name, seq in tables:
+        if not isinstance(seq, (list, tuple)) or len(seq) != 4:
+            raise DaglError(f"{who}: {name} must be a sequence of four tensors, one per head")
+    n_rows, width_in, width_out = _graph_fixed_slots(who, key, deg, width_out)
+    if step:
+        B, H, W = _stage_mix_operands(who, x, mix_w, mix_b)
+        if hw is not None and tuple(int(v) for v in hw) != (H, W):
+            raise DaglError(f"{who}: hw={tuple(hw)} but x is a {H}x{W} map")
+        hw = (H, W)
+    shapes = {_graph_fixed_head(who, wq_rows4[h], x_rows4[h], b2p4[h] if step else None, tau4[h] if tau4 is not None else None, hw)
+              for h in range(4)}
+    if len(shapes) != 1 or (step and next(iter(shapes))[:3] != (B, H, W)):
+        raise DaglError(f"{who}: the four heads' operands must share B, H and W" + (f" with x {tuple(x.shape)}" if step else "")
+                        + f", got {sorted(shapes)}")
+    B, H, W, L = next(iter(shapes))
+    if n_rows != 4 * B * L or deg.numel() != n_rows:
+        raise DaglError(f"{who}: key holds {n_rows} rows and deg {deg.numel()} degrees, expected 4*B*L = {4 * B * L}")
+    flags, radius, k = _graph_fixed_flags(who, normalize, keep_all, block_rows, radius, k, width_out, H * W)
+    dev = key.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_stage_step_fixed_workspace_bytes", B, H, W, 1) if step else (None, None, 0)
+    out = torch.empty_like(x) if step else None
+    key_out, weight, score, deg_out, status = _graph_fixed_arrays(dev, n_rows, width_out)
+    table = lambda seq: (C.c_void_p * 4)(*[t.data_ptr() for t in seq])
+    check(lib.dagl_graph_stage_step_fixed(_stream(), B, H, W, table(wq_rows4), table(x_rows4), table(b2p4) if step else None,
+                                          key.data_ptr(), deg.data_ptr(), width_in, radius, table(tau4) if tau4 is not None else None, k,
+                                          float(scale), flags, propagate, explore, seed, _ptr(x), _ptr(mix_w), _ptr(mix_b), _ptr(out),
+                                          key_out.data_ptr(), weight.data_ptr(), score.data_ptr(), deg_out.data_ptr(), width_out,
+                                          status.data_ptr(), a, nbytes), "dagl_graph_stage_step_fixed")
+    del buf
+    return out, dict(key=key_out, weight=weight, score=score, deg=deg_out), status
 
 
 def _graph_stage_search(who: str, entry: str, wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, radius, tau4, k, scale, normalize,

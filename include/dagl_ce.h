@@ -620,6 +620,38 @@ int    dagl_graph_stage_step(void* stream, int B, int H, int W, const float* con
                              int64_t* row_off_out /* [4 B L + 1] or NULL */, int32_t* key_out, float* weight_out, float* score_out,
                              int64_t capacity_edges, int64_t* status_out /* [2] */, void* workspace, size_t ws_bytes);
 
+/* ---- the fixed-width step of a whole CES stage: csrc/graph_refresh.hip (detected by symbol, no ABI bump) ---------------------------------
+ * dagl_graph_stage_step_fixed: dagl_graph_step_fixed for the four heads of a stage in ONE row launch, ending in dagl_ces_stage_fold_mix --
+ * the stage-fused step that hands back its graph at a size known before the call: nothing is read on the host and the call can be
+ * captured into a HIP graph WITH its graph output.
+ *   wq_rows4, x_rows4, b2p4, tau4: HOST tables of four device pointers as dagl_graph_stage_step takes them (tau4 NULL or four NULL
+ *     entries: no margin; some entries NULL is DAGL_ERR_INVALID).
+ *   key_in [4 B L, width_in], deg_in [4 B L]: the stage's graph over the head-major rows, row (h B + b) L + i = query i of image b under
+ *     head h, slots and degrees as dagl_graph_step_fixed reads them (deg_in clamped to [0, width_in]).
+ *   key_out / weight_out / score_out [4 B L, width_out], deg_out [4 B L]: rows h B L .. (h + 1) B L hold, bit for bit and filler included,
+ *     what dagl_graph_step_fixed writes for head h's operands, its rows of the input and the same radius, k, scale, flags, propagate,
+ *     explore and seed.  EVERY slot and degree is written by every call.  The random keys of a row come from the hash of the HEAD-LOCAL
+ *     row; propagation reads rows r +- 1 and r +- Lw of the input inside the row's own image, so never another head's.
+ *   b2p4, x, mix_w, mix_b, out [B,64,H,W]: all given -- out = dagl_ces_stage_fold_mix of the four heads' aggregated rows, each row
+ *     dagl_graph_step_fixed's bits for its head -- or ALL NULL: the graph alone (the graph-only iterations of a search).
+ *   status [2] int64 (device): the rows that came out empty for their length summed over the heads, the largest number of distinct
+ *     candidates over all rows.
+ * Launches: the status words' memset, ONE row kernel over the 4 B L rows (the heads' pointers travel by value in its arguments; a
+ * wavefront per row when (1 + 4 propagate) width_in (2 radius + 1)^2 + explore <= 128 and DAGL_GRAPH_REFRESH_BLOCK_ROWS is not set, else
+ * a block per row), then the fold + mix + residual when out is wanted: no staging, no scan, no copy.  Refused before any launch: what
+ * dagl_graph_step_fixed refuses with 4 B L rows (4 B H W >= 2^30, 4 B L width >= 2^31), a NULL table, b2p4 / x / mix_w / mix_b / out
+ * given in part, tau for some heads, a b2p4 entry that is not 16-byte aligned, an output array that overlaps an input array of any head
+ * or a mix operand (DAGL_ERR_INVALID); the row bound above dagl_graph_refresh_max_candidates() (DAGL_ERR_UNSUPPORTED); too small a
+ * workspace (DAGL_ERR_WORKSPACE).  Workspace: dagl_graph_stage_step_fixed_workspace_bytes -- the [4 B L, 784] aggregated rows when out
+ * is wanted, else 0 (workspace may then be NULL). */
+size_t dagl_graph_stage_step_fixed_workspace_bytes(int B, int H, int W, int want_out);
+int    dagl_graph_stage_step_fixed(void* stream, int B, int H, int W, const float* const* wq_rows4, const float* const* x_rows4,
+                                   const float* const* b2p4 /* NULL: the graph alone */, const int32_t* key_in, const int32_t* deg_in,
+                                   int width_in, int radius, const float* const* tau4 /* NULL: no margin */, int k, float scale, int flags,
+                                   int propagate, int explore, uint32_t seed, const float* x, const float* mix_w, const float* mix_b,
+                                   float* out /* NULL iff b2p4 NULL */, int32_t* key_out, float* weight_out, float* score_out,
+                                   int32_t* deg_out, int width_out, int64_t* status /* [2] */, void* workspace, size_t workspace_bytes);
+
 /* ---- the search step of a whole CES stage: csrc/graph_refresh.hip (detected by symbol) ---------------------------------------------------
  * dagl_graph_stage_search / dagl_graph_stage_search_step: dagl_graph_search / dagl_graph_search_step for the four heads of a stage, on
  * the operands of dagl_graph_stage_step (HOST tables of four device pointers, ONE CSR over the 4 B L head-major rows, x, mix_w, mix_b,

@@ -16,6 +16,14 @@ head by head (``step_graphs(..., fused=False, propagate=True, explore=8)``), wit
 same kernel launched once per head (``head_launches``), on stored features; ``iters=3`` against three ``iters=1`` calls; and, on the whole
 module, ``CES.build_graphs`` (4 iterations from the trivial start) against ``CES.forward_with_graphs``.  Noise-like maps carry no spatial
 coherence: the times say what a search step costs, not what it finds.
+
+    python tools/time_stage_step.py --fixed [--search] [1024 1024]    # the same stage on a fixed-width state (``FixedGraph``)
+
+``fused="stage"`` (``ops.graph_stage_step_fixed``: the four heads' rows in one row launch, fold + mix in one) against head by head
+(``CE.step_graph`` x 4 on the heads' row views, ``FixedGraph.cat``, ``torch.cat``, the mix convolution), each eager and per replayed
+frame of a captured HIP graph -- a frame is the stage's step and ``copy_`` of the new graph into the captured one's storage --, with the
+stage-fused step on the CSR state (one host read, not capturable with its graph) next to them.  ``--search``: the same with
+``propagate``, ``explore=8``.
 """
 import os
 import sys
@@ -176,9 +184,72 @@ def stage_leg(H, W, big):
           f"{fmt(k_mix)}): {k_fm[0] / k_two[0]:.2f} of the two launches", flush=True)
 
 
+def fixed_leg(H, W, big, search_on):
+    from dagl_amd.graph import FixedGraph
+    from dagl_amd.sequence import SequenceState
+    name, mode, ces, x, x2 = _case(H, W, big)
+    feat, fmt = "split16", _fmt
+    search = dict(propagate=True, explore=8, seed=0) if search_on else dict(propagate=False, explore=0, seed=0)
+    with torch.no_grad():
+        heads, mix = ces._stage_modules(1)
+        graphs = [hd.graph(x) for hd in heads]
+        state = SequenceState.from_heads(graphs * 3)          # the state of stage 1 alone is timed
+        for g in state.stages:
+            g.validate().max_degree()
+        width = heads[0].select_k
+        fixed = state.to_fixed(width)
+        plan = ces._plan_fixed("CES.step_graphs", x2, fixed, 1, feat, "stage", search)[1]
+        B = x.shape[0]
+
+        def by_heads(x_in, stage):
+            pairs = [hd.step_graph(x_in, stage.images(h * B, (h + 1) * B), radius=1, features=feat, **search) for h, hd in enumerate(heads)]
+            return mix(torch.cat([o for o, _ in pairs], dim=1)) + x_in, FixedGraph.cat([g for _, g in pairs])
+
+        def fused(x_in, stage):
+            return ces._stage_fixed_fused(1, x_in, stage, plan, feat, search, 1)
+
+        def frames(form):
+            """(eager, replayed) ms per frame: the step and the copy of its graph into the stage's storage."""
+            g0 = fixed.stages[0]
+            stage = g0._like(g0.key.clone(), g0.weight.clone(), g0.score.clone(), g0.deg.clone())
+            x_in = x2.clone()
+            eager = _events(lambda: stage.copy_(form(x_in, stage)[1]))
+            stage.copy_(g0)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out, g = form(x_in, stage)
+                stage.copy_(g)
+            return eager, _events(graph.replay)
+
+        o_u, g_u = by_heads(x2, fixed.stages[0])
+        o_f, g_f = fused(x2, fixed.stages[0])
+        same = all(torch.equal(getattr(g_u, n), getattr(g_f, n)) for n in ("key", "weight", "score", "deg"))
+        gap = float((o_u - o_f).abs().max() / o_u.abs().max())
+        heads_eager, heads_replay = frames(by_heads)
+        fused_eager, fused_replay = frames(fused)
+        if search_on:
+            plan_c = ces._plan_step(x2, state, 1, feat, True, True, search, what="CES.search_graphs")[1]
+            csr = _events(lambda: ces._search_stage(1, x2, state, plan_c, 1, feat, True, search))
+        else:
+            plan_c = ces._plan_step(x2, state, 1, feat, True, True)[1]
+            csr = _events(lambda: ces._step_stage(1, x2, state, plan_c, feat, True))
+    what = "search step (propagate, explore 8)" if search_on else "step"
+    print(f"[1,64,{H},{W}] {name}, {what} of one stage on a fixed-width state ({width} slots per row, radius 1, split16), per frame = the "
+          f"step + copy_ of its graph\n"
+          f"    head by head: eager {fmt(heads_eager)}, replayed {fmt(heads_replay)}\n"
+          f"    fused='stage': eager {fmt(fused_eager)} = {fused_eager[0] / heads_eager[0]:.2f} of head by head, replayed {fmt(fused_replay)} = "
+          f"{fused_replay[0] / heads_replay[0]:.2f} of head by head; graphs equal head by head: {same}; outputs differ by {gap:.1e} of the "
+          f"largest\n"
+          f"    the stage-fused {what} on the CSR state, eager with its graph (one host read): {fmt(csr)}", flush=True)
+
+
 def main():
-    argv = [a for a in sys.argv[1:] if a != "--search"]
-    leg = search_leg if "--search" in sys.argv[1:] else stage_leg
+    search = "--search" in sys.argv[1:]
+    argv = [a for a in sys.argv[1:] if a not in ("--search", "--fixed")]
+    if "--fixed" in sys.argv[1:]:
+        return fixed_leg(int(argv[0]), int(argv[1]), True, search) if len(argv) > 1 else fixed_leg(256, 256, False, search)
+    leg = search_leg if search else stage_leg
     if len(argv) > 1:
         return leg(int(argv[0]), int(argv[1]), True)
     return leg(256, 256, False)
