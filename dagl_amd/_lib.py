@@ -110,6 +110,8 @@ SIGNATURES = {
     "dagl_graph_stage_step_fixed_workspace_bytes": (_sz, [_i] * 4),
     "dagl_graph_stage_step_fixed": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 3 + [_vp, _vp, _i, _i, C.POINTER(_vp), _i, C.c_float, _i, _i, _i,
                                          C.c_uint32] + [_vp] * 8 + [_i, _vp, _vp, _sz]),
+    "dagl_graph_stage_features16_workspace_bytes": (_sz, [_i] * 5),
+    "dagl_graph_stage_features16": (_i, [_vp, _i, _i, _i, _i, _vp, C.POINTER(CeWeights), _i] + [_vp] * 5 + [_sz]),
     "dagl_graph_stage_search_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64] + [_i] * 6),
     "dagl_graph_stage_search": (_i, [_vp, _i, _i, _i] + [C.POINTER(_vp)] * 2 + [_vp, _vp, C.c_int64, _i, _i, C.POINTER(_vp), _i, C.c_float, _i]
                                 + [_vp] * 4 + [C.c_int64, _vp, _vp, _sz, _i, _i, C.c_uint32]),

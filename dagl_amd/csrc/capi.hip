@@ -12,7 +12,7 @@ namespace dagl {
 static thread_local char g_err[512] = "";
 // tags the calls of this process for the range guard (RangeTag): the only process-wide state of the library
 static std::atomic<uint32_t> g_call_tag{1};
-static int32_t next_call_tag() {
+int32_t next_call_tag() {
     uint32_t t = g_call_tag.fetch_add(1, std::memory_order_relaxed) & 0x7fffffffu;
     return (int32_t)(t ? t : 1u);
 }

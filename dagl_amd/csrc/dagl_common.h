@@ -293,6 +293,7 @@ struct RangeTag {
                                      // in-stream kernels did NOT serve (too many / too heavy overflowed queries): same poison
 };
 constexpr float RANGE_LIMIT = 60000.0f;
+int32_t next_call_tag();             // the next tag of this process's calls, never 0 (capi.hip)
 
 // The statistics block of a forward's workspace: 16 int64 words at Plan::o_stats (capi.hip).  The first STAT_N_COUNTERS words
 // are the per-call counters, cleared at the start of every call; the others outlive the call.  The int32 words (range, done,

@@ -57,6 +57,7 @@ class CES(nn.Module):
         from . import ops
         self._ws = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # one per stage: packed weights persist
         self._ws_step = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # step_graphs' own: _ws keeps its packed weights
+        self._ws_feat = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # features="stage16": the stage's feature launches
         self._pack_key = {1: None, 2: None, 3: None}
         self._skip_fused = {1: 0, 2: 0, 3: 0}     # calls for which a stage stays on the per-head path after it met dense masks
         self._fused_calls = {1: 0, 2: 0, 3: 0}    # fused calls since the stage's range word was last looked at
@@ -206,6 +207,17 @@ class CES(nn.Module):
         is ``fused="stage"``); on a CSR state ``fused="stage"`` means ``True``.  Heads of a stage whose output widths differ are
         refused before any launch.
 
+        ``features="stage16"``: the stage's features in ONE pass (``ops.graph_stage_features16``: the inference forward's heads-as-batch
+        prologue and projection, one copy-out launch that also forms ``tau``) instead of ``CE._graph_features`` head by head.  Served
+        wherever a stage runs fused -- a CSR state with ``fused`` None (on a stage that qualifies) or True, a fixed state with
+        ``fused="stage"`` -- and refused before any launch, naming those forms, on every head-by-head path (``fused=False``, a fixed
+        state under ``fused=None``, a stage that does not qualify, the search keywords on a CSR state); the heads' own checks are made
+        with ``"split16"``.  Graphs and output are the stage-fused call's on those features bit for bit; against ``"split16"`` key rows
+        differ in last bits (another launch plan of the same projection kernel), so a fixed-k cut may flip on a tie.  Range: the map
+        side has the forward's (both tiers of g(x), the input's per-block scale), the word still trips on weights beyond the split's
+        range or a non-finite input, and a tripped word NaN-fills the WHOLE stage -- ``out`` and all four heads' rows of the new
+        graph --: one word per call, not one per head.
+
         Always under ``torch.no_grad()``; the modules' state (packed weights, top-k policy, range verdicts, ``_pack_key``) is untouched:
         the fused calls have workspaces of their own, one per stage.  Every refusal -- ``CE.step_graph``'s, per head, and a state that
         does not fit the input -- is raised before any launch of the call."""
@@ -243,6 +255,25 @@ class CES(nn.Module):
             out = self._between_stages(s, out)
         return out, (SequenceState(new) if want_graphs else None)
 
+    _STAGE16_FUSED_ONLY = ("features='stage16' belongs to the stage-fused forms (a CSR state with fused=None or True on a stage that "
+                           "qualifies, a state of FixedGraphs with fused='stage'); {why}: pass features='split16' or 'fp32'")
+
+    def _stage_features(self, s, x, margin, features):
+        """The four heads' features of stage ``s`` on its input ``x`` -> [(wq_rows, x_rows, tau | None, b2p, poisoned)] per head: the
+        one place the stage-fused calls get them.  ``"fp32"`` / ``"split16"``: ``CE._graph_features`` head by head.  ``"stage16"``: ONE
+        ``ops.graph_stage_features16`` for the stage (its own workspace per stage), the heads' operands as views of its ``[4, ...]``
+        arrays; ``poisoned`` reads the first elements of those arrays, which the call NaN-fills -- all four heads' -- once an operand
+        of any head leaves the split-fp16 range."""
+        heads, _mix = self._stage_modules(s)
+        if features != "stage16":
+            fast = features == "split16"
+            return [hd._graph_features(x, margin, fast, False) for hd in heads]
+        from . import ops
+        wq4, x4, b2p4, tau4 = ops.graph_stage_features16(x, [hd._params_f32(scaled=False) for hd in heads], margin,
+                                                         workspace=self._ws_feat[s])
+        poisoned = lambda t: torch.addcmul(t, wq4.reshape(-1)[:1], x4.reshape(-1)[:1], value=0.0)
+        return [(wq4[h], x4[h], tau4[h] if margin else None, b2p4[h], poisoned) for h in range(4)]
+
     @staticmethod
     def _fused_value(what, fused):
         """``fused`` is None, a bool or "stage"."""
@@ -259,13 +290,16 @@ class CES(nn.Module):
         if fused is True:
             raise DaglError(f"{what}: fused=True on a state of FixedGraphs: the stage-fused fixed-width launch is fused='stage' "
                             "(ops.graph_stage_step_fixed); leave fused at None (head by head) or pass fused=False")
+        if features == "stage16" and fused != "stage":
+            raise DaglError(f"{what}: " + self._STAGE16_FUSED_ONLY.format(why=f"fused={fused!r} on a state of FixedGraphs runs head by head"))
+        head_features = "split16" if features == "stage16" else features      # (the heads' own checks know their two routes)
         plan = {}
         for s in (1, 2, 3):
             args = []
             for h, hd in enumerate(self._stage_modules(s)[0]):
                 if not isinstance(hd, CE):
                     raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it steps no graph")
-                args.append(hd._fixed_arguments(x, state.head(s - 1, h), "step_graph", radius, None, "reference", features, **search))
+                args.append(hd._fixed_arguments(x, state.head(s - 1, h), "step_graph", radius, None, "reference", head_features, **search))
             widths = [a[3] for a in args]
             if len(set(widths)) != 1:
                 raise DaglError(f"{what}: the heads of stage {s} give graphs of widths {widths}: one FixedGraph per stage needs one width "
@@ -310,9 +344,9 @@ class CES(nn.Module):
         from . import ops
         heads, mix = self._stage_modules(s)
         radius, k_eff, margin, width_out = plan
-        fast = features == "split16"
+        fast = features != "fp32"                   # (the split-fp16 routes carry a range verdict)
         x = x.contiguous()
-        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        feats = self._stage_features(s, x, margin, features)                        # (wq_rows, x_rows, tau, b2p, poisoned) per head
         wq4, x4, b2p4 = ([f[i].contiguous() for f in feats] for i in (0, 1, 3))
         common = dict(width_out=width_out, radius=radius, tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff,
                       scale=float(heads[0].softmax_scale), workspace=self._ws_step[s], propagate=bool(search["propagate"]),
@@ -385,6 +419,10 @@ class CES(nn.Module):
                 raise DaglError(f"{what}: fused=True, but stage {s} does not qualify (four plain CE heads sharing select_mode, select_k, "
                                 "softmax_scale and the default patch geometry, an fp32 input on the GPU)")
             use = ok if fused is None else bool(fused)
+            if features == "stage16" and not use:
+                why = f"stage {s} runs head by head here (" + ("fused=False or a search keyword of step_graphs" if ok else "it does not qualify") + ")"
+                raise DaglError(f"{what}: " + self._STAGE16_FUSED_ONLY.format(why=why))
+            head_features = "split16" if features == "stage16" else features      # (the heads' own checks know their two routes)
             for h, hd in enumerate(heads):
                 if not isinstance(hd, CE):
                     raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it steps no graph")
@@ -400,7 +438,8 @@ class CES(nn.Module):
                         raise DaglError(f"{what}: head by head under capture needs state.head({s - 1}, {h}) taken before the capture "
                                         "(it reads two offsets on the host)")
                     g = state.head(s - 1, h)
-                args = hd._refresh_arguments(x, g, "step_graph", radius, None, "reference", features, host_read=want_graphs, **(search or {}))
+                args = hd._refresh_arguments(x, g, "step_graph", radius, None, "reference", head_features, host_read=want_graphs,
+                                             **(search or {}))
             plan[s] = (use, args)
         return plan
 
@@ -420,9 +459,9 @@ class CES(nn.Module):
         """One ``ops.graph_stage_step`` on the four heads' features -> (out, the stage's new graph | None)."""
         from . import ops
         heads, mix = self._stage_modules(s)
-        fast = features == "split16"
+        fast = features != "fp32"                   # (the split-fp16 routes carry a range verdict)
         x = x.contiguous()
-        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        feats = self._stage_features(s, x, margin, features)                        # (wq_rows, x_rows, tau, b2p, poisoned) per head
         out, csr, _status = ops.graph_stage_step([f[0].contiguous() for f in feats], [f[1].contiguous() for f in feats],
                                                  [f[3].contiguous() for f in feats], stage.row_off, stage.key, x,
                                                  mix.weight.detach().contiguous(), mix.bias.detach().contiguous(), radius=radius,
@@ -481,7 +520,11 @@ class CES(nn.Module):
         served values and ``state.to_csr()`` --: the default of this method means "the CSR's fused search where a stage qualifies", and
         no fixed-width form is what that default has ever returned.  On a CSR state ``fused="stage"`` means ``True``.  Every
         iteration's row bound is looked at before the first launch, from the widths alone: a rank-cut mode leaves ``k`` slots per row
-        after the first iteration, "adaptive" keeps the state's width."""
+        after the first iteration, "adaptive" keeps the state's width.
+
+        ``features="stage16"`` as in ``step_graphs``: the stage's features in one pass, served by the fused forms (a CSR state under
+        ``fused`` None / True on a stage that qualifies, a fixed state under ``fused="stage"``), refused before any launch on the
+        head-by-head ones; a tripped range word NaN-fills the whole stage."""
         from ._lib import DaglError
         from . import ops
         from .sequence import SequenceState
@@ -561,9 +604,9 @@ class CES(nn.Module):
                     g = hd.refresh_graph(x, g, seed=seed + i, **kw)
                 pairs.append(hd.step_graph(x, g, seed=seed + iters - 1, want_graph=want_graphs, **kw))
             return mix(torch.cat([o for o, _ in pairs], dim=1)) + x, (PatchGraph.cat([g for _, g in pairs]) if want_graphs else None)
-        fast = features == "split16"
+        fast = features != "fp32"                   # (the split-fp16 routes carry a range verdict)
         x = x.contiguous()
-        feats = [hd._graph_features(x, margin, fast, False) for hd in heads]       # (wq_rows, x_rows, tau, b2p, poisoned) per head
+        feats = self._stage_features(s, x, margin, features)                        # (wq_rows, x_rows, tau, b2p, poisoned) per head
         wq4, x4, b2p4 = ([f[i].contiguous() for f in feats] for i in (0, 1, 3))
         common = dict(radius=radius, tau4=[f[2].contiguous() for f in feats] if margin else None, k=k_eff,
                       scale=float(heads[0].softmax_scale), workspace=self._ws_step[s], propagate=search["propagate"],

@@ -1192,6 +1192,60 @@ def graph_stage_step_fixed(wq_rows4, x_rows4, b2p4, key, deg, x=None, mix_w=None
     return out, dict(key=key_out, weight=weight, score=score, deg=deg_out), status
 
 
+_HEAD_SHAPES = {"g.weight": (16, 64, 3, 3), "g.bias": (16,), "theta.weight": (16, 64, 1, 1), "theta.bias": (16,),
+                "thr_conv.weight": (1, 64, 7, 7), "thr_conv.bias": (1,), "bias_conv.weight": (1, 64, 7, 7), "bias_conv.bias": (1,),
+                "fc1.0.weight": (D, P), "fc1.0.bias": (D,), "fc2.0.weight": (D, P), "fc2.0.bias": (D,)}
+
+
+@_on_device
+def graph_stage_features16(x, heads, margin: bool, workspace: "Workspace | None" = None):
+    """The features of a whole ``CES`` stage for the stage-fused patch-graph calls in one launch set
+    (``dagl_graph_stage_features16``, csrc/stage_features.hip) -> ``(wq4 [n,B,L,196], x4 [n,B,N,196], b2p4 [n,B,H+6,W+6,16],
+    tau4 [n,B,L] | None)`` for the ``n`` = 1..4 (a stage: four) heads of ``heads``: dicts of state_dict names -> contiguous fp32 GPU
+    tensors of the default head (ksize 7, 16 inner channels, 64 input channels; ``thr_conv.*`` / ``bias_conv.*`` are looked at with
+    ``margin`` only), all on the shared input ``x`` [B,64,H,W].  ``t[h]`` is head h's operand as ``graph_stage_step`` /
+    ``graph_stage_step_fixed`` / ``graph_stage_search*`` take it, already contiguous.
+
+    The inference forward's heads-as-batch kernels: ONE g / theta launch, ONE split-fp16 projection launch for keys and queries of all
+    heads, ONE copy-out launch that also forms ``tau`` (the mean over keys from the projection's fp64 column sums).  The map side has
+    the forward's range (both tiers of g(x), the input's per-block scale); weights beyond the split's range or a non-finite ``x``
+    NaN-fill EVERY element of all the arrays, of every head -- one range word per call -- never wrong numbers.  Nothing is read on
+    the host: the call can be captured (the workspace must then have its size before the capture: one eager call)."""
+    lib = _lib.load()
+    who = "graph_stage_features16"
+    _need(x, "x")
+    if x.dim() != 4 or x.shape[1] != 64:
+        raise DaglError(f"{who}: expected x [B,64,H,W], got {tuple(x.shape)}")
+    if not isinstance(heads, (list, tuple)) or not 1 <= len(heads) <= 4:
+        raise DaglError(f"{who}: heads must be a sequence of one to four parameter dicts, one per head")
+    margin = bool(margin)
+    n = len(heads)
+    arr = (_lib.CeWeights * n)()
+    for h, prm in enumerate(heads):
+        for field, name in zip([f for f, _ in _lib.CeWeights._fields_], _lib.CeWeights.NAMES):
+            if not margin and name.startswith(("thr_conv.", "bias_conv.")):
+                continue
+            if name not in prm:
+                raise DaglError(f"{who}: head {h} has no {name}")
+            t = prm[name]
+            _need(t, name)
+            if tuple(t.shape) != _HEAD_SHAPES[name]:
+                raise DaglError(f"{who}: head {h} {name} is {tuple(t.shape)}, expected {_HEAD_SHAPES[name]}")
+            setattr(arr[h], field, t.data_ptr())
+    B, _, H, W = x.shape
+    Lh, Lw = query_grid(H, W)
+    L, N, dev = Lh * Lw, H * W, x.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_stage_features16_workspace_bytes", n, B, H, W, int(margin))
+    wq4 = torch.empty(n, B, L, D, device=dev, dtype=torch.float32)
+    x4 = torch.empty(n, B, N, D, device=dev, dtype=torch.float32)
+    b2p4 = torch.empty(n, B, H + 6, W + 6, 16, device=dev, dtype=torch.float32)
+    tau4 = torch.empty(n, B, L, device=dev, dtype=torch.float32) if margin else None
+    check(lib.dagl_graph_stage_features16(_stream(), n, B, H, W, x.data_ptr(), arr, int(margin), wq4.data_ptr(), x4.data_ptr(),
+                                          b2p4.data_ptr(), _ptr(tau4), a, nbytes), "dagl_graph_stage_features16")
+    del buf
+    return wq4, x4, b2p4, tau4
+
+
 def _graph_stage_search(who: str, entry: str, wq_rows4, x_rows4, b2p4, row_off, key, x, mix_w, mix_b, radius, tau4, k, scale, normalize,
                         keep_all, max_row_edges, want_graph, workspace, block_rows, propagate, explore, seed, head_launches):
     """The body of ``graph_stage_search`` (``b2p4`` None: x names the shape alone) and ``graph_stage_search_step``."""

@@ -652,6 +652,35 @@ int    dagl_graph_stage_step_fixed(void* stream, int B, int H, int W, const floa
                                    float* out /* NULL iff b2p4 NULL */, int32_t* key_out, float* weight_out, float* score_out,
                                    int32_t* deg_out, int width_out, int64_t* status /* [2] */, void* workspace, size_t workspace_bytes);
 
+/* ---- the features of a whole CES stage for the patch-graph routes: csrc/stage_features.hip (detected by symbol, no ABI bump) -------------
+ * dagl_graph_stage_features16: what the stage entries above read -- dense feature rows, value maps, tau -- for `heads` (1..4) heads that
+ * share the input x, by the inference forward's heads-as-batch kernels: the g / theta maps of all heads in ONE launch, their keys and
+ * queries in ONE split-fp16 projection launch, ONE copy-out launch.
+ *   x [B,64,H,W] fp32, shared by the heads; heads_w [heads]: HOST array of the heads' device pointers (thr_* / bias_* are looked at with
+ *     margin != 0 only).
+ *   wq_rows [heads,B,L,196], x_rows [heads,B,N,196]: fc1 / fc2 + ReLU of the 7x7x16 patches of g(x), rows post-ReLU; head h's slice is a
+ *     contiguous [B,n,196] array, as dagl_graph_stage_step* take it.
+ *   b2p [heads,B,H+6,W+6,16]: theta(x), NHWC, with a zero 3-pixel border (every element is written by every call).
+ *   tau [heads,B,L] with margin != 0 (else NULL): mean_j S_ij * thr_i - bias_i, the mean as an fp64 dot of the query row with the fp64
+ *     column sums of its image's keys, thr / bias from the four channel-group partial sums in the order of the forward's kernel.
+ * Range: the planes carry both tiers of g(x) and the input its per-block scale, as in dagl_ces_stage_forward, so activations are served
+ * up to |g(x)| < 1.5e7; weights beyond the split's range (|256 w_conv|, |1024 w_fc| < 65504) or a non-finite input set the call's range
+ * word, and the copy-out then writes NaN into EVERY element of the four outputs (b2p[0] of every head with them): one word per call,
+ * the whole stage, never numbers computed from inf halves.
+ * Launches: two memsets (the call's words, the column sums), three weight packs per head, the border and guard-row zeroing, the conv
+ * launch, the thr / bias heads (margin != 0 only; inside the projection's launch when W % 4 == 0 and x is 16-byte aligned), the
+ * projection (+ its column-sum reduce with margin != 0), the copy-out.  Nothing is allocated and nothing is read on the host: the call
+ * can be captured into a HIP graph.
+ * Refused before any launch, in this order: B, H or W < 1, heads outside 1..4, heads B H W >= 2^30; a NULL array or a NULL weight of
+ * head h; tau without margin or margin without tau; an array that is not 16-byte aligned (DAGL_ERR_INVALID); a workspace that is NULL or
+ * not 256-byte aligned (DAGL_ERR_INVALID) or smaller than dagl_graph_stage_features16_workspace_bytes (DAGL_ERR_WORKSPACE, the size
+ * named).  The size function returns 0 for a shape the entry refuses. */
+size_t dagl_graph_stage_features16_workspace_bytes(int heads, int B, int H, int W, int margin);
+int    dagl_graph_stage_features16(void* stream, int heads, int B, int H, int W, const float* x /* [B,64,H,W], shared by the heads */,
+                                   const dagl_ce_weights* heads_w /* [heads] */, int margin, float* wq_rows /* [heads,B,L,196] */,
+                                   float* x_rows /* [heads,B,N,196] */, float* b2p /* [heads,B,H+6,W+6,16] */,
+                                   float* tau /* [heads,B,L] or NULL with margin = 0 */, void* workspace, size_t workspace_bytes);
+
 /* ---- the search step of a whole CES stage: csrc/graph_refresh.hip (detected by symbol) ---------------------------------------------------
  * dagl_graph_stage_search / dagl_graph_stage_search_step: dagl_graph_search / dagl_graph_search_step for the four heads of a stage, on
  * the operands of dagl_graph_stage_step (HOST tables of four device pointers, ONE CSR over the 4 B L head-major rows, x, mix_w, mix_b,

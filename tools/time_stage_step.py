@@ -24,6 +24,10 @@ coherence: the times say what a search step costs, not what it finds.
 frame of a captured HIP graph -- a frame is the stage's step and ``copy_`` of the new graph into the captured one's storage --, with the
 stage-fused step on the CSR state (one host read, not capturable with its graph) next to them.  ``--search``: the same with
 ``propagate``, ``explore=8``.
+
+Every table also has the ``features="stage16"`` column (``ops.graph_stage_features16``: the four heads' prologue and projections in one
+launch each) next to ``"split16"``: the features alone, the fused step with and without the graphs, the fused search step, and
+``--fixed [--search]`` eager and replayed.
 """
 import os
 import sys
@@ -94,6 +98,10 @@ def search_leg(H, W, big):
         by_head_alone = _events(lambda: ces._step_stage(1, x2, state, plan_u, feat, False, search))
         fused = _events(lambda: ces._search_stage(1, x2, state, plan_f, 1, feat, True, search))
         alone = _events(lambda: ces._search_stage(1, x2, state, plan_f, 1, feat, False, search))
+        # ... and with the stage's features in one pass (features="stage16")
+        plan_s = ces._plan_step(x2, state, 1, "stage16", True, True, search, what="CES.search_graphs")[1]
+        fused16 = _events(lambda: ces._search_stage(1, x2, state, plan_s, 1, "stage16", True, search))
+        alone16 = _events(lambda: ces._search_stage(1, x2, state, plan_s, 1, "stage16", False, search))
         o_u, g_u = ces._step_stage(1, x2, state, plan_u, feat, True, search)
         o_f, g_f = ces._search_stage(1, x2, state, plan_f, 1, feat, True, search)
         same = all(torch.equal(getattr(g_u, n), getattr(g_f, n)) for n in ("row_off", "key", "weight", "score"))
@@ -129,6 +137,8 @@ def search_leg(H, W, big):
           f"    search step fused {fmt(fused)} = {fused[0] / by_head[0]:.2f} of head by head; without the graphs {fmt(alone)} = "
           f"{alone[0] / by_head_alone[0]:.2f} of head by head; fused graphs equal head by head: {same}; outputs differ by {gap:.1e} of "
           f"the largest\n"
+          f"    search step fused, features='stage16' {fmt(fused16)} = {fused16[0] / fused[0]:.2f} of split16; without the graphs {fmt(alone16)} = "
+          f"{alone16[0] / alone[0]:.2f} of split16\n"
           f"    ops.graph_stage_search_step on stored features, no graphs: one row launch {fmt(one)}, the same kernel once per head "
           f"{fmt(four)}: {one[0] / four[0]:.2f}\n"
           f"    iters=3 {fmt(it3)} against three iters=1 calls {fmt(calls3)}: {it3[0] / calls3[0]:.2f}\n"
@@ -160,6 +170,11 @@ def stage_leg(H, W, big):
         by_head_alone = _events(lambda: ces._step_stage(1, x2, state, plan_u, feat, False))
         margin = mode != "topk"
         feats = _events(lambda: [hd._graph_features(x2, margin, True, False) for hd in heads])
+        # the stage's features in one pass (features="stage16"): alone, and under the fused step
+        plan_s = ces._plan_step(x2, state, 1, "stage16", True, True)[1]
+        feats16 = _events(lambda: ces._stage_features(1, x2, margin, "stage16"))
+        fused16 = _events(lambda: ces._step_stage(1, x2, state, plan_s, "stage16", True))
+        alone16 = _events(lambda: ces._step_stage(1, x2, state, plan_s, "stage16", False))
         o_u, g_u = ces._step_stage(1, x2, state, plan_u, feat, True)
         o_f, g_f = ces._step_stage(1, x2, state, plan_f, feat, True)
         same = all(torch.equal(getattr(g_u, n), getattr(g_f, n)) for n in ("row_off", "key", "weight", "score"))
@@ -180,6 +195,8 @@ def stage_leg(H, W, big):
           f"    step fused {fmt(fused)} = {fused[0] / by_head[0]:.2f} of head by head, {fused[0] / fwd[0]:.2f} of _stage; without the graphs "
           f"{fmt(alone)} = {alone[0] / by_head_alone[0]:.2f} of head by head, {alone[0] / fwd[0]:.2f} of _stage\n"
           f"    the four heads' features alone {fmt(feats)}; fused graphs equal head by head: {same}; outputs differ by {gap:.1e} of the largest\n"
+          f"    features='stage16': the features alone {fmt(feats16)} = {feats16[0] / feats[0]:.2f} of split16; step fused {fmt(fused16)} = "
+          f"{fused16[0] / fused[0]:.2f} of split16; without the graphs {fmt(alone16)} = {alone16[0] / alone[0]:.2f} of split16\n"
           f"    ops.ces_stage_fold_mix {fmt(k_fm)} against fold + stage_mix {fmt(k_two)} (fold alone {fmt(k_fold)}, stage_mix alone "
           f"{fmt(k_mix)}): {k_fm[0] / k_two[0]:.2f} of the two launches", flush=True)
 
@@ -228,6 +245,11 @@ def fixed_leg(H, W, big, search_on):
         gap = float((o_u - o_f).abs().max() / o_u.abs().max())
         heads_eager, heads_replay = frames(by_heads)
         fused_eager, fused_replay = frames(fused)
+        # ... and with the stage's features in one pass (features="stage16")
+        plan16 = ces._plan_fixed("CES.step_graphs", x2, fixed, 1, "stage16", "stage", search)[1]
+        fused16_eager, fused16_replay = frames(lambda x_in, stage: ces._stage_fixed_fused(1, x_in, stage, plan16, "stage16", search, 1))
+        o_s, _g = ces._stage_fixed_fused(1, x2, fixed.stages[0], plan16, "stage16", search, 1)
+        gap16 = float((o_s - o_f).abs().max() / o_f.abs().max())
         if search_on:
             plan_c = ces._plan_step(x2, state, 1, feat, True, True, search, what="CES.search_graphs")[1]
             csr = _events(lambda: ces._search_stage(1, x2, state, plan_c, 1, feat, True, search))
@@ -241,6 +263,8 @@ def fixed_leg(H, W, big, search_on):
           f"    fused='stage': eager {fmt(fused_eager)} = {fused_eager[0] / heads_eager[0]:.2f} of head by head, replayed {fmt(fused_replay)} = "
           f"{fused_replay[0] / heads_replay[0]:.2f} of head by head; graphs equal head by head: {same}; outputs differ by {gap:.1e} of the "
           f"largest\n"
+          f"    fused='stage', features='stage16': eager {fmt(fused16_eager)} = {fused16_eager[0] / fused_eager[0]:.2f} of split16, replayed "
+          f"{fmt(fused16_replay)} = {fused16_replay[0] / fused_replay[0]:.2f} of split16; outputs differ from split16 by {gap16:.1e} of the largest\n"
           f"    the stage-fused {what} on the CSR state, eager with its graph (one host read): {fmt(csr)}", flush=True)
 
 
