@@ -85,6 +85,10 @@ SIGNATURES = {
     "dagl_graph_forward_train": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _vp, C.c_float, _i] + [_vp] * 4 + [_sz]),
     "dagl_graph_forward_backward_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64]),
     "dagl_graph_forward_backward": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _vp, C.c_float, _i] + [_vp] * 11 + [_sz]),
+    "dagl_graph_stage_forward_workspace_bytes": (_sz, [_i, _i, _i, C.c_int64]),
+    "dagl_graph_stage_forward": (_i, [_vp, _i, _i, _i] + [_vp] * 5 + [C.c_int64, _vp, C.c_float, _i] + [_vp] * 8 + [_sz]),
+    "dagl_ces_stage_mix_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dagl_ces_stage_mix_backward": (_i, [_vp, _i, _i, _i] + [_vp] * 7 + [_sz]),
     "dagl_graph_from_lists_workspace_bytes": (_sz, [_i, _i, _i]),
     "dagl_graph_from_lists": (_i, [_vp, _i, _i, _i, _i] + [_vp] * 8 + [C.c_int64, _vp, _sz]),
     "dagl_graph_refresh_max_candidates": (_i, []),

@@ -191,6 +191,46 @@ class _GraphForward(torch.autograd.Function):
         return d_wq, d_x, d_tau, d_b2p, None, None, None, None, None
 
 
+class _GraphStageForward(torch.autograd.Function):
+    """A whole ``CES`` stage on its frozen graph (``ops.graph_stage_forward(train=True)``): the four heads' features and value maps
+    stacked head-major, the stage's input and its 1x1 mix -> the stage's output.  Differentiable in all of them: the backward is
+    ``ops.ces_stage_mix_backward`` (d cat head-major, d mix_w, d mix_b), then ``_GraphForward``'s ``ops.graph_forward_backward`` ONCE on
+    the stacked operands as those of 4 B images, with the stage graph's transposed CSR; the gradient of the residual input is ``d_out``.
+    Saved between forward and backward: the operands, (M, D) per row and the head-major concat map ``cat4`` (B * 64 * H * W floats, what
+    a convolution's autograd keeps as its input) -- no per-edge array, no 784-float row array; the structure is a constant."""
+
+    @staticmethod
+    def forward(ctx, wq4, x4, tau4, b2p4, x, mix_w, mix_b, graph, scale, normalize, ws_f, ws_b, ws_mix):
+        wq4, x4, b2p4, x = wq4.contiguous(), x4.contiguous(), b2p4.contiguous(), x.contiguous()
+        tau_c = tau4.contiguous() if tau4 is not None else None
+        mix_w_c, mix_b_c = mix_w.contiguous(), mix_b.contiguous()
+        out, row_max, row_sum, cat4 = ops.graph_stage_forward(wq4, x4, b2p4, graph.row_off, graph.key, x, mix_w_c, mix_b_c, tau4=tau_c,
+                                                              scale=scale, normalize=normalize, train=True, workspace=ws_f)
+        ctx.graph, ctx.call, ctx.ws = graph, (scale, normalize), (ws_b, ws_mix)
+        ctx.save_for_backward(wq4, x4, tau_c, b2p4, mix_w_c, row_max, row_sum, cat4)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        wq4, x4, tau4, b2p4, mix_w, row_max, row_sum, cat4 = ctx.saved_tensors
+        g = ctx.graph
+        need_wq, need_x, need_tau, need_map, need_in, need_w, need_b = ctx.needs_input_grad[:7]
+        need_tau = need_tau and tau4 is not None
+        d_out = d_out.contiguous().float()
+        d_cat4, d_w, d_b = ops.ces_stage_mix_backward(d_out, cat4, mix_w, need_w=need_w, need_b=need_b, workspace=ctx.ws[1])
+        d_wq = d_x = d_tau = d_b2p = None
+        if need_wq or need_x or need_tau or need_map:
+            flat = lambda t: t.flatten(0, 1) if t is not None else None
+            d_wq, d_x, d_tau, d_b2p = ops.graph_forward_backward(flat(d_cat4), flat(wq4), flat(x4), flat(b2p4), g.row_off, g.key, row_max,
+                                                                 row_sum, flat(tau4), scale=ctx.call[0], normalize=ctx.call[1],
+                                                                 transposed=g.transpose() if need_x or need_map else None,
+                                                                 need_wq=need_wq, need_x=need_x, need_tau=need_tau, need_b2p=need_map,
+                                                                 workspace=ctx.ws[0])
+        like = lambda d, t: d.view(t.shape) if d is not None else None
+        return (like(d_wq, wq4), like(d_x, x4), like(d_tau, tau4) if d_tau is not None else None, like(d_b2p, b2p4),
+                d_out if need_in else None, like(d_w, mix_w), d_b, None, None, None, None, None, None)
+
+
 _CONV_WEIGHTS = ("g.weight", "theta.weight", "thr_conv.weight", "bias_conv.weight")
 
 

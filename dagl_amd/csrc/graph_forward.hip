@@ -23,6 +23,11 @@
 // Training (dagl_graph_forward_train / dagl_graph_forward_backward): the forward above, unchanged, plus one launch that leaves (M, D) per
 // row -- twelve bytes a row are all that is kept between forward and backward --, and a backward that recomputes S_e, w_e and
 // g_e = <dAgg[r], V[key_e]> in one crossing of the edges: the kernels and their order are written out in front of the backward below.
+//
+// A whole CES stage (dagl_graph_stage_forward): the kernels take the image of a row as row / L and the image of a key's features as
+// (row / L) N + key, and a stage's graph is one CSR over 4 B head-major images -- with B' = 4 B and the four heads' operands stacked
+// head-major they serve the stage unchanged; the entry stops at the aggregated rows and ends in launch_stage_fold_mix (aggregate.hip).
+// Its backward starts in stage_mix_grad.hip and continues in dagl_graph_forward_backward with B' = 4 B.
 #include "dagl_common.h"
 #include "graph_rows.h"
 
@@ -385,10 +390,10 @@ static GfWs gf_carve(void* ws, int B, const Grid& g, int64_t E) {
 }
 static size_t graph_forward_workspace_bytes(int B, const Grid& g, int64_t E) { return gf_carve(nullptr, B, g, E).bytes; }
 
+// the forward up to its fold: the aggregated rows agg [B L, 784] are left in the workspace (gf_carve(...).agg).
 // row_max_out / row_sum_out: the training forward's row statistics (both or neither); the forward's own launches are the same either way
-static int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace,
-                                float* row_max_out = nullptr, double* row_sum_out = nullptr) {
-    const GfWs w = gf_carve(workspace, B, g, c.E);
+static int launch_graph_forward_rows(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, const GfWs& w,
+                                     float* row_max_out = nullptr, double* row_sum_out = nullptr) {
     const GtArgs a = gt_args(B, g, c);
     GaArgs v = ga_map_args(B, g, b2p, c.row_off, c.key, nullptr, c.E);
     v.out = w.agg; v.part = w.part;
@@ -403,7 +408,27 @@ static int launch_graph_forward(hipStream_t s, int B, const Grid& g, const Graph
                            row_sum_out);
         DAGL_LAUNCH_CHECK("graph_forward_row_stats_kernel");
     }
-    return launch_fold(s, B, g, w.agg, out);
+    return DAGL_OK;
+}
+
+static int launch_graph_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p, float* out, void* workspace,
+                                float* row_max_out = nullptr, double* row_sum_out = nullptr) {
+    const GfWs w = gf_carve(workspace, B, g, c.E);
+    const int rc = launch_graph_forward_rows(s, B, g, c, b2p, w, row_max_out, row_sum_out);
+    return rc ? rc : launch_fold(s, B, g, w.agg, out);
+}
+
+// a whole CES stage on its frozen graph: the rows of the four heads as 4 B images (the kernels take the image of a row as row / L: the
+// head-major operands [4, B, ...] ARE those of 4 B images), then the stage's fold + mix + residual on the rows.  cat_out (training, with
+// the row statistics): the pre-mix concat map [4, B, 16, H, W] head-major, fold_kernel's bits -- what the fused kernel forms per pixel
+static int launch_graph_stage_forward(hipStream_t s, int B, const Grid& g, const GraphAttendCall& c, const float* b2p4, const float* x,
+                                      const float* mix_w, const float* mix_b, float* out, float* row_max_out, double* row_sum_out,
+                                      float* cat_out, void* workspace) {
+    const GfWs w = gf_carve(workspace, 4 * B, g, c.E);
+    int rc = launch_graph_forward_rows(s, 4 * B, g, c, b2p4, w, row_max_out, row_sum_out);
+    if (rc) return rc;
+    if (cat_out != nullptr && (rc = launch_fold(s, 4 * B, g, w.agg, cat_out))) return rc;
+    return launch_stage_fold_mix(s, B, g, w.agg, x, mix_w, mix_b, out);
 }
 
 // backward: dAgg [B L, 784], d V rows [B N, 784], the products' partial rows, S / w / g per edge, three sums per row and per segment
@@ -547,6 +572,38 @@ int dagl_graph_forward_backward(void* stream, int B, int H, int W, const float* 
     const GraphAttendCall c = graph_attend_call(wq_rows, x_rows, row_off, key, total_edges, tau, scale, flags);
     return launch_graph_forward_backward((hipStream_t)stream, B, g, c, b2p, row_max, row_sum, d_out, col_off, src_row, perm,
                                          GfGrads{d_wq_rows, d_x_rows, d_tau, d_b2p}, workspace);
+}
+
+// a CES stage on its frozen graph, four heads in one launch set, ending in the fused fold + mix (no ABI bump: found by symbol)
+static int graph_stage_shape_ok(const char* who, int B, int H, int W, int64_t total_edges) {
+    int rc = graph_dims_ok(who, B, H, W);
+    if (rc) return rc;
+    DAGL_REQUIRE((int64_t)4 * B * H * W < (1ll << 30), "%s: batch too large for 32-bit row ids", who);
+    return graph_shape_ok(who, 4 * B, H, W, total_edges);
+}
+
+size_t dagl_graph_stage_forward_workspace_bytes(int B, int H, int W, int64_t total_edges) {
+    if (graph_stage_shape_ok("dagl_graph_stage_forward_workspace_bytes", B, H, W, total_edges)) return 0;
+    return graph_forward_workspace_bytes(4 * B, make_grid(H, W), total_edges);
+}
+
+int dagl_graph_stage_forward(void* stream, int B, int H, int W, const float* wq_rows4, const float* x_rows4, const float* b2p4,
+                             const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau4, float scale, int flags,
+                             const float* x, const float* mix_w, const float* mix_b, float* out, float* row_max_out, double* row_sum_out,
+                             float* cat_out, void* workspace, size_t ws_bytes) {
+    const char* who = "dagl_graph_stage_forward";
+    int rc = graph_stage_shape_ok(who, B, H, W, total_edges);
+    if (rc || (rc = graph_operands_ok(who, wq_rows4, x_rows4, row_off, key, total_edges, scale, flags, b2p4 != nullptr))) return rc;
+    DAGL_REQUIRE(((uintptr_t)b2p4 % 16) == 0, "%s: b2p must be 16-byte aligned", who);
+    DAGL_REQUIRE(x && mix_w && mix_b && out, "%s: null tensor pointer", who);
+    const int training = (row_max_out != nullptr) + (row_sum_out != nullptr) + (cat_out != nullptr);
+    DAGL_REQUIRE(training == 0 || training == 3, "%s: the training outputs come together (row_max_out, row_sum_out, cat_out: %d of 3 given)",
+                 who, training);
+    const Grid g = make_grid(H, W);
+    if ((rc = check_workspace(who, workspace, ws_bytes, graph_forward_workspace_bytes(4 * B, g, total_edges)))) return rc;
+    const GraphAttendCall c = graph_attend_call(wq_rows4, x_rows4, row_off, key, total_edges, tau4, scale, flags);
+    return launch_graph_stage_forward((hipStream_t)stream, B, g, c, b2p4, x, mix_w, mix_b, out, row_max_out, row_sum_out, cat_out,
+                                      workspace);
 }
 
 }  // extern "C"

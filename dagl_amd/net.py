@@ -41,6 +41,11 @@ class ResBlock(nn.Module):
         return self.body(x).mul(self.res_scale) + x
 
 
+class _StageFeatures(list):
+    """``CES._stage_features``' per-head list where the operands were made head-major in one piece: ``stacked`` holds the arrays."""
+    stacked = None
+
+
 class CES(nn.Module):
     """Three stages of four patch-graph heads, each stage mixed by a 1x1 conv + residual (dagl.py:74-119)."""
 
@@ -58,6 +63,8 @@ class CES(nn.Module):
         self._ws = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # one per stage: packed weights persist
         self._ws_step = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # step_graphs' own: _ws keeps its packed weights
         self._ws_feat = {1: ops.Workspace(), 2: ops.Workspace(), 3: ops.Workspace()}     # features="stage16": the stage's feature launches
+        # forward_on_graphs(fused=True), per stage: the forward's rows; the graph backward's rows and edges; the mix backward's slots
+        self._ws_frozen = {s: (ops.Workspace(), ops.Workspace(), ops.Workspace()) for s in (1, 2, 3)}
         self._pack_key = {1: None, 2: None, 3: None}
         self._skip_fused = {1: 0, 2: 0, 3: 0}     # calls for which a stage stays on the per-head path after it met dense masks
         self._fused_calls = {1: 0, 2: 0, 3: 0}    # fused calls since the stage's range word was last looked at
@@ -258,21 +265,25 @@ class CES(nn.Module):
     _STAGE16_FUSED_ONLY = ("features='stage16' belongs to the stage-fused forms (a CSR state with fused=None or True on a stage that "
                            "qualifies, a state of FixedGraphs with fused='stage'); {why}: pass features='split16' or 'fp32'")
 
-    def _stage_features(self, s, x, margin, features):
+    def _stage_features(self, s, x, margin, features, grad=False):
         """The four heads' features of stage ``s`` on its input ``x`` -> [(wq_rows, x_rows, tau | None, b2p, poisoned)] per head: the
-        one place the stage-fused calls get them.  ``"fp32"`` / ``"split16"``: ``CE._graph_features`` head by head.  ``"stage16"``: ONE
+        one place the stage-fused calls get them.  ``"fp32"`` / ``"split16"``: ``CE._graph_features`` head by head (``grad``: on the
+        modules' own parameters, for the caller's autograd graph).  ``"stage16"``: ONE
         ``ops.graph_stage_features16`` for the stage (its own workspace per stage), the heads' operands as views of its ``[4, ...]``
         arrays; ``poisoned`` reads the first elements of those arrays, which the call NaN-fills -- all four heads' -- once an operand
-        of any head leaves the split-fp16 range."""
+        of any head leaves the split-fp16 range.  The list then carries the head-major arrays themselves as ``stacked`` =
+        (wq4, x4, tau4 | None, b2p4): what ``ops.graph_stage_forward`` takes, without a copy."""
         heads, _mix = self._stage_modules(s)
         if features != "stage16":
             fast = features == "split16"
-            return [hd._graph_features(x, margin, fast, False) for hd in heads]
+            return [hd._graph_features(x, margin, fast, grad) for hd in heads]
         from . import ops
         wq4, x4, b2p4, tau4 = ops.graph_stage_features16(x, [hd._params_f32(scaled=False) for hd in heads], margin,
                                                          workspace=self._ws_feat[s])
         poisoned = lambda t: torch.addcmul(t, wq4.reshape(-1)[:1], x4.reshape(-1)[:1], value=0.0)
-        return [(wq4[h], x4[h], tau4[h] if margin else None, b2p4[h], poisoned) for h in range(4)]
+        feats = _StageFeatures((wq4[h], x4[h], tau4[h] if margin else None, b2p4[h], poisoned) for h in range(4))
+        feats.stacked = (wq4, x4, tau4 if margin else None, b2p4)
+        return feats
 
     @staticmethod
     def _fused_value(what, fused):
@@ -370,7 +381,7 @@ class CES(nn.Module):
         g.mode, g.k = heads[0].select_mode, k_eff
         return out, g
 
-    def forward_on_graphs(self, x, state, *, features: str = "fp32", backward: str = "two_ops"):
+    def forward_on_graphs(self, x, state, *, features: str = "fp32", backward: str = "two_ops", fused=None):
         """The module's output for ``x`` on the FROZEN graphs of ``state`` -> ``out``: ``forward``'s wiring with every head run as
         ``hd.forward_on_graph(stage input, state.head(s, h), features=..., backward=...)`` -- its weights recomputed on the head's
         structure, no selection --, the stage's own mix and residual, ``RBS1`` / ``RBS2`` between the stages.  Not under
@@ -378,10 +389,24 @@ class CES(nn.Module):
         structures are constants.  For fine-tuning on a sequence: ``_, state = ces.step_graphs(frame, state)`` moves the graphs without
         gradients, ``ces.forward_on_graphs(frame, state, backward="fused")`` trains on the result.
 
-        Head by head; a stage-fused training launch does not exist.  Refused before the first launch: a ``state`` that is no
+        ``fused=None`` / ``False``: head by head, the definition of the result.  Refused before the first launch: a ``state`` that is no
         ``SequenceState`` or was built for another ``B``, ``H`` or ``W``, a head that is not a ``CE``, and every head's own refusals
         (``CE.forward_on_graph``'s; those that depend on whether a gradient is wanted are looked at with ``x`` as every stage's input and
-        once more when the head runs).  The modules' state is untouched."""
+        once more when the head runs).  The modules' state is untouched.
+
+        ``fused=True``: per stage the heads' features from ``_stage_features`` (``"fp32"`` / ``"split16"``: ``CE._graph_features`` head
+        by head and a ``torch.stack`` of the operands; ``"stage16"``: one ``ops.graph_stage_features16``, whose arrays are head-major
+        already), then ONE ``ops.graph_stage_forward`` on the stage's own CSR: ``ops.graph_forward``'s launches over the ``4 B L`` rows
+        and the fused fold + mix + residual -- no per-head fold, no concat map, no convolution.  With a gradient wanted the same launches
+        run as an autograd op (``ce._GraphStageForward``) whose backward is ``ops.ces_stage_mix_backward`` and ONE
+        ``ops.graph_forward_backward`` on the stacked operands; it needs ``backward="fused"`` (the default ``"two_ops"`` contradicts it
+        and is refused) and ``features`` ``"fp32"`` or ``"split16"`` (the split-fp16 training kernels keep their per-head form).  Every
+        row is the head-by-head fused call's bit for bit; ``out`` differs by the fp32 roundings of the mix product.  A tripped range
+        word of any feature route NaN-fills the stage's output.  A stage that does not qualify (``_stage_step_fusable``) is refused,
+        there is no silent fallback; so is ``fused="stage"``, which names the fixed-width forms.  ``features="stage16"`` without
+        ``fused=True`` is refused.  A state of ``FixedGraph``s is refused whatever ``fused`` is: pass ``state.to_csr()``.  After
+        ``state.stages[s].validate()`` and, for training, ``.transpose()`` (host reads, cached on the graph) the call reads nothing on
+        the host; without a gradient it can be captured.  All refusals are raised before the first launch."""
         from ._lib import DaglError
         from .sequence import SequenceState
         what = "CES.forward_on_graphs"
@@ -393,6 +418,21 @@ class CES(nn.Module):
         if (g0.B, g0.H, g0.W) != (4 * x.shape[0], x.shape[2], x.shape[3]):
             raise DaglError(f"{what}: the state was built for B={g0.B // 4} H={g0.H} W={g0.W}, the input is B={x.shape[0]} H={x.shape[2]} "
                             f"W={x.shape[3]}")
+        if not state.fixed:                         # (a fixed state meets the heads' own refusal below, whatever ``fused`` is)
+            if isinstance(fused, str) and fused == "stage":
+                raise DaglError(f"{what}: fused='stage' names the fixed-width forms (step_graphs / search_graphs on a state of "
+                                "FixedGraphs); a call on frozen graphs takes fused=None, False or True")
+            if not (fused is None or isinstance(fused, bool)):
+                raise DaglError(f"{what}: fused={fused!r}, expected None, False or True")
+            if fused:
+                plan = self._plan_forward_fused(what, x, state, features, backward)
+                out = x
+                for s in (1, 2, 3):
+                    out = self._between_stages(s, self._stage_forward_fused(s, out, state.stages[s - 1], plan[s], features))
+                return out
+            if features == "stage16":
+                raise DaglError(f"{what}: " + self._STAGE16_FUSED_ONLY.format(why=f"fused={fused!r} runs head by head here (the frozen-graph "
+                                                                               "call serves it with fused=True)"))
         for s in (1, 2, 3):
             for h, hd in enumerate(self._stage_modules(s)[0]):
                 if not isinstance(hd, CE):
@@ -403,6 +443,90 @@ class CES(nn.Module):
             heads, mix = self._stage_modules(s)
             outs = [hd.forward_on_graph(out, state.head(s - 1, h), features=features, backward=backward) for h, hd in enumerate(heads)]
             out = self._between_stages(s, mix(torch.cat(outs, dim=1)) + out)
+        return out
+
+    def _why_not_fusable(self, s, x) -> str:
+        """The first condition of ``_stage_step_fusable`` that stage ``s`` misses on the input ``x``."""
+        heads, mix = self._stage_modules(s)
+        if not self.fuse_stage:
+            return "the module was not built on 64 channels"
+        if not all(type(hd) is CE and not hd._generic and hd.in_channels == 64 for hd in heads):
+            return "its heads are not four plain CE modules of the default patch geometry on 64 channels"
+        if len({(hd.select_mode, int(hd.select_k), float(hd.softmax_scale)) for hd in heads}) != 1:
+            return "its heads do not share select_mode, select_k and softmax_scale"
+        if not x.is_cuda:
+            return "the input is not on the GPU"
+        if x.dtype != torch.float32:
+            return f"the input is {x.dtype}, not fp32"
+        return f"its mix is {mix.weight.dtype}, not fp32"
+
+    def _plan_forward_fused(self, what, x, state, features, backward):
+        """Every refusal of ``forward_on_graphs(fused=True)`` on a CSR state, raised before the first launch -- every stage sees an input
+        of x's shape, dtype and device, and a gradient counts as wanted when ``x`` or any parameter of the module asks for one --
+        -> {stage: margin}.  The stages' graphs are validated here (one host read per graph, once)."""
+        from ._lib import DaglError
+        if features not in ("fp32", "split16", "stage16"):
+            raise DaglError(f"{what}: features={features!r}, expected 'fp32', 'split16' or 'stage16'")
+        if backward not in ("two_ops", "fused"):
+            raise DaglError(f"{what}: backward={backward!r}, expected 'two_ops' or 'fused'")
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if grad and backward != "fused":
+            raise DaglError(f"{what}: fused=True contradicts backward='two_ops' (a gradient is wanted for the input or a parameter, and "
+                            "the stage-fused forward has the fused backward alone); pass backward='fused'")
+        if grad and features == "stage16":
+            raise DaglError(f"{what}: features='stage16' has no backward (a gradient is wanted for the input or a parameter; the "
+                            "split-fp16 training kernels keep their per-head form): pass features='split16' or 'fp32'")
+        for s in (1, 2, 3):
+            heads, mix = self._stage_modules(s)
+            for hd in heads:
+                if not isinstance(hd, CE):
+                    raise DaglError(f"{what}: head {type(hd).__name__} of stage {s} is not a CE: it runs on no graph")
+            if not self._stage_step_fusable(s, x):
+                raise DaglError(f"{what}: fused=True, but stage {s} does not qualify: {self._why_not_fusable(s, x)} (fused=None or False "
+                                "runs head by head)")
+            if grad and any(p.dtype != torch.float32 for m in heads + [mix] for p in m.parameters()):
+                raise DaglError(CE._FP32_ONLY)
+        head_features = "split16" if features == "stage16" else features      # (the heads' own checks know their two routes)
+        capturing = x.is_cuda and torch.cuda.is_current_stream_capturing()
+        plan = {}
+        for s in (1, 2, 3):
+            stage = state.stages[s - 1]
+            if not capturing and x.is_cuda and stage.row_off.device == x.device:
+                stage.validate()
+            g = stage._like(stage.row_off, stage.key, stage.weight, stage.score)      # the stage's arrays under a head's shape
+            g.B = x.shape[0]
+            for hd in self._stage_modules(s)[0]:
+                margin = hd._attend_arguments(x, g, "forward_on_graph", None, "reference", True, head_features, None, backward)[0]
+            plan[s] = margin
+        return plan
+
+    def _stage_forward_fused(self, s, x, stage, margin, features):
+        """Stage ``s`` on its input ``x`` and its frozen graph by ONE ``ops.graph_stage_forward`` -- under autograd, with a gradient
+        wanted for ``x`` or a parameter of the stage, as ``ce._GraphStageForward`` -> the stage's output."""
+        from . import ops
+        from .ce import _GraphStageForward
+        heads, mix = self._stage_modules(s)
+        x = x.contiguous()
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for m in heads + [mix] for p in m.parameters()))
+        ws_f, ws_b, ws_mix = self._ws_frozen[s]
+        with torch.enable_grad() if grad else torch.no_grad():
+            # (wq_rows, x_rows, tau, b2p, poisoned) per head
+            feats = self._stage_features(s, x, margin, features, grad=True) if grad else self._stage_features(s, x, margin, features)
+            stacked = getattr(feats, "stacked", None)
+            verdicts = feats[:1] if stacked is not None else feats          # (one range word per call there, one per head here)
+            if stacked is None:
+                stacked = tuple(torch.stack([f[i] for f in feats]) if i != 2 or margin else None for i in range(4))
+            wq4, x4, tau4, b2p4 = stacked
+            scale = float(heads[0].softmax_scale)
+            if grad:
+                out = _GraphStageForward.apply(wq4, x4, tau4, b2p4, x, mix.weight, mix.bias, stage, scale, "reference", ws_f, ws_b, ws_mix)
+            else:
+                out = ops.graph_stage_forward(wq4, x4, b2p4, stage.row_off, stage.key, x, mix.weight.detach().contiguous(),
+                                              mix.bias.detach().contiguous(), tau4=tau4, scale=scale, normalize="reference",
+                                              workspace=ws_f)
+            if features != "fp32":
+                for f in verdicts:
+                    out = f[4](out)                 # a feature route that left the split-fp16 range NaN-fills the stage's output
         return out
 
     def _plan_step(self, x, state, radius, features, want_graphs, fused, search=None, what="CES.step_graphs"):
@@ -719,7 +843,7 @@ class RR(nn.Module):
 
     def forward_on_graphs(self, x, state, **kw):
         """The network's output for ``x`` on the frozen graphs of ``state`` -> ``out``: ``forward`` with
-        ``CES.forward_on_graphs(., state, **kw)`` where the ``CES`` sits (``features``, ``backward`` as there).  Not under
+        ``CES.forward_on_graphs(., state, **kw)`` where the ``CES`` sits (``features``, ``backward``, ``fused`` as there).  Not under
         ``torch.no_grad()``: with autograd enabled the result trains the trunk and the heads on constant structures.  The ``CES``'s
         refusals are raised when it is reached: the head convolution and the ResBlocks in front of it have run by then."""
         return self._forward_around_ces(x, lambda ces, t: (ces.forward_on_graphs(t, state, **kw), None))[0]

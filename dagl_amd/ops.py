@@ -1026,13 +1026,17 @@ def _graph_fixed_arrays(dev, n_rows: int, width_out: int):
             torch.empty(2, device=dev, dtype=torch.int64))
 
 
-def _stage_mix_operands(who: str, x, mix_w, mix_b):
-    """x [B,64,H,W], the stage's 1x1 mix weights [64,64] or [64,64,1,1] and bias [64] -> (B, H, W)."""
-    _need(x, "x"); _need(mix_w, "mix_w"); _need(mix_b, "mix_b")
+def _stage_mix_operands(who: str, x, mix_w, mix_b, bias: bool = True):
+    """x [B,64,H,W], the stage's 1x1 mix weights [64,64] or [64,64,1,1] and bias [64] -> (B, H, W).  ``bias`` False: a call that takes
+    no bias (the mix's backward, x = d_out)."""
+    _need(x, "x"); _need(mix_w, "mix_w")
+    if bias:
+        _need(mix_b, "mix_b")
     if x.dim() != 4 or x.shape[1] != 64:
         raise DaglError(f"{who}: expected x [B,64,H,W], got {tuple(x.shape)}")
-    if tuple(mix_w.shape) not in ((64, 64), (64, 64, 1, 1)) or tuple(mix_b.shape) != (64,):
-        raise DaglError(f"{who}: expected mix_w [64,64] and mix_b [64], got {tuple(mix_w.shape)} and {tuple(mix_b.shape)}")
+    if tuple(mix_w.shape) not in ((64, 64), (64, 64, 1, 1)) or (bias and tuple(mix_b.shape) != (64,)):
+        raise DaglError(f"{who}: expected mix_w [64,64] and mix_b [64], got {tuple(mix_w.shape)}"
+                        + (f" and {tuple(mix_b.shape)}" if bias else ""))
     return x.shape[0], x.shape[2], x.shape[3]
 
 
@@ -1067,6 +1071,74 @@ def ces_stage_mix(cat, x, mix_w, mix_b) -> torch.Tensor:
     check(_lib.load().dagl_ces_stage_mix(_stream(), B, H, W, cat.data_ptr(), x.data_ptr(), mix_w.data_ptr(), mix_b.data_ptr(),
                                          out.data_ptr()), "dagl_ces_stage_mix")
     return out
+
+
+@_on_device
+def graph_stage_forward(wq4, x4, b2p4, row_off, key, x, mix_w, mix_b, *, tau4=None, scale: float = 10.0, normalize: str = "reference",
+                        train: bool = False, workspace: "Workspace | None" = None):
+    """A whole ``CES`` stage on its FROZEN graph in one launch set (``dagl_graph_stage_forward``, csrc/graph_forward.hip) -> ``out``
+    [B,64,H,W], or ``(out, row_max [4*B*L] fp32, row_sum [4*B*L] fp64, cat4 [4,B,16,H,W])`` with ``train=True``.  wq4 [4,B,L,196], x4
+    [4,B,N,196], b2p4 [4,B,H+6,W+6,16], tau4 [4,B,L] | None: the four heads' ``graph_forward`` operands stacked head-major (what
+    ``graph_stage_features16`` hands out); (row_off [4*B*L+1], key [E]) ONE CSR over the head-major rows, row ``(h * B + b) * L + i`` =
+    query ``i`` of image ``b`` under head ``h`` (a ``SequenceState`` stage); x [B,64,H,W] the stage's input, mix_w / mix_b its 1x1 mix.
+
+    ``graph_forward``'s segment and combine launches run once over the 4*B*L rows, then ``ces_stage_fold_mix`` on the aggregated rows:
+    every row is ``graph_forward``'s for its head bit for bit, an empty graph gives ``mix_b + x``.  ``train=True`` adds the row
+    statistics of ``graph_forward_train`` and ``cat4``, the pre-mix concat map head-major (``graph_forward``'s output of the stacked
+    operands) -- what ``ces_stage_mix_backward`` and ``graph_forward_backward`` need next to the operands; ``out`` keeps its bits.
+    Nothing is read on the host; the same arrays give the same bits on every call."""
+    lib = _lib.load()
+    who = "graph_stage_forward"
+    B, H, W = _stage_mix_operands(who, x, mix_w, mix_b)
+    for name, t in (("wq4", wq4), ("x4", x4), ("b2p4", b2p4)) + ((("tau4", tau4),) if tau4 is not None else ()):
+        _need(t, name)
+        if t.dim() < 2 or t.shape[0] != 4 or t.shape[1] != B:
+            raise DaglError(f"{who}: {name} must be head-major [4,{B},...] for x {tuple(x.shape)}, got {tuple(t.shape)}")
+    # the stacked operands are those of 4 B images: graph_forward's own checks on that view
+    B4, H4, W4, E, flags = _graph_forward_operands(who, wq4.flatten(0, 1), x4.flatten(0, 1), b2p4.flatten(0, 1), row_off, key,
+                                                   tau4.flatten(0, 1) if tau4 is not None else None, normalize)
+    if (H4, W4) != (H, W):
+        raise DaglError(f"{who}: b2p4 is the value map of {H4}x{W4} images, x holds {H}x{W}")
+    dev = x.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_graph_stage_forward_workspace_bytes", B, H, W, E)
+    out = torch.empty_like(x)
+    row_max = row_sum = cat4 = None
+    if train:
+        row_max = torch.empty(B4 * wq4.shape[2], device=dev, dtype=torch.float32)
+        row_sum = torch.empty(B4 * wq4.shape[2], device=dev, dtype=torch.float64)
+        cat4 = torch.empty(4, B, 16, H, W, device=dev, dtype=torch.float32)
+    check(lib.dagl_graph_stage_forward(_stream(), B, H, W, wq4.data_ptr(), x4.data_ptr(), b2p4.data_ptr(), row_off.data_ptr(),
+                                       _ptr(key, E > 0), E, _ptr(tau4), float(scale), flags, x.data_ptr(), mix_w.data_ptr(),
+                                       mix_b.data_ptr(), out.data_ptr(), _ptr(row_max), _ptr(row_sum), _ptr(cat4), a, nbytes),
+          "dagl_graph_stage_forward")
+    del buf
+    return (out, row_max, row_sum, cat4) if train else out
+
+
+@_on_device
+def ces_stage_mix_backward(d_out, cat4, mix_w, need_w: bool = True, need_b: bool = True, workspace: "Workspace | None" = None):
+    """The backward of a stage's 1x1 mix + residual on the head-major concat map (``dagl_ces_stage_mix_backward``,
+    csrc/stage_mix_grad.hip) -> ``(d_cat4 [4,B,16,H,W], d_mix_w [64,64] | None, d_mix_b [64] | None)`` from d_out [B,64,H,W], the
+    ``cat4`` [4,B,16,H,W] that ``graph_stage_forward(train=True)`` left and mix_w [64,64] (or [64,64,1,1]).
+    ``d_cat4[h,b,c] = sum_o mix_w[o][16 h + c] d_out[b,o]``: viewed as [4*B,16,H,W] it is ``graph_forward_backward``'s ``d_out`` on the
+    stacked operands (which divides by the overlap count; nothing is divided here).  ``d_mix_w = sum_{b,p} d_out[b,o,p] cat[b,c,p]``,
+    ``d_mix_b = sum_{b,p} d_out[b,o,p]``: per-wave partial tiles on the fp32 matrix cores, added in a fixed order in fp64.  The gradient
+    of the residual input is ``d_out``.  The same operands give the same bits on every call, whatever ``need_w`` / ``need_b``."""
+    lib = _lib.load()
+    who = "ces_stage_mix_backward"
+    B, H, W = _stage_mix_operands(who, d_out, mix_w, None, bias=False)
+    _need(cat4, "cat4")
+    if tuple(cat4.shape) != (4, B, 16, H, W):
+        raise DaglError(f"{who}: expected cat4 [4,{B},16,{H},{W}] for d_out {tuple(d_out.shape)}, got {tuple(cat4.shape)}")
+    dev = d_out.device
+    buf, a, nbytes = _sized_region(workspace, dev, "dagl_ces_stage_mix_backward_workspace_bytes", B, H, W)
+    d_cat4 = torch.empty_like(cat4)
+    d_w = torch.empty(64, 64, device=dev, dtype=torch.float32) if need_w else None
+    d_b = torch.empty(64, device=dev, dtype=torch.float32) if need_b else None
+    check(lib.dagl_ces_stage_mix_backward(_stream(), B, H, W, d_out.data_ptr(), cat4.data_ptr(), mix_w.data_ptr(), d_cat4.data_ptr(),
+                                          _ptr(d_w), _ptr(d_b), a, nbytes), "dagl_ces_stage_mix_backward")
+    del buf
+    return d_cat4, d_w, d_b
 
 
 @_on_device

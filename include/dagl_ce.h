@@ -171,7 +171,7 @@ int dagl_ce_range_check(void* stream, int B, int H, int W, int mode, int k, void
  * dagl_ce_info.dense_rerun_blocks in the place of `reserved`; 405: dagl_fc_grad16_dmap; 408: dagl_ce_graph_*; 409: dagl_graph_apply*;
  * 410: dagl_ce_core_dense_chunk_floats, dagl_ce_core_dense_plan; 411: dagl_ce_pivot_debug; 412: dagl_graph_attend*;
  * workspace sizes unchanged).  dagl_graph_forward* (the training pair dagl_graph_forward_train / _backward included), dagl_ce_wide_debug, dagl_graph_from_lists*, dagl_graph_refresh*, dagl_graph_step*, dagl_graph_stage_step*, dagl_graph_search*, dagl_graph_stage_search*,
- * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_fc_grad16_plan,
+ * dagl_ces_stage_fold_mix, dagl_ces_stage_mix, dagl_graph_stage_forward*, dagl_ces_stage_mix_backward*, dagl_fc_grad16_plan,
  * dagl_conv_pair_backward_plan, dagl_ce_prologue16_plan, dagl_ce_prologue16_debug*, dagl_project16_plan and dagl_ce_project16_debug* came in without a bump -- no declared signature or struct changed --: a caller that
  * wants them detects them by symbol (dlsym), as dagl_amd/_lib.py does for every entry of its table.  A caller compares
  * dagl_version() with the DAGL_ABI_VERSION it was built against and refuses a mismatch (dagl_amd/_lib.py does).           */
@@ -433,6 +433,37 @@ int dagl_graph_forward_backward(void* stream, int B, int H, int W, const float* 
                                 const int32_t* src_row, const int32_t* perm, float* d_wq_rows /* may be NULL */,
                                 float* d_x_rows /* may be NULL */, float* d_tau /* may be NULL */, float* d_b2p /* may be NULL */,
                                 void* workspace, size_t ws_bytes);
+
+/* ---- a whole CES stage on its FROZEN graph, forward and backward: csrc/graph_forward.hip, csrc/stage_mix_grad.hip (ABI 412, by symbol) --
+ * dagl_graph_stage_forward: dagl_graph_forward for the four heads of a stage in ONE launch set, ending in dagl_ces_stage_fold_mix.  The
+ * kernels of dagl_graph_forward take the image of a row as row / L, so the heads' operands stacked head-major are those of 4 B images:
+ *   wq_rows4 [4,B,L,196], x_rows4 [4,B,N,196] (16-byte aligned), b2p4 [4,B,H+6,W+6,16] (16-byte aligned), tau4 [4,B,L] or NULL: contiguous,
+ *   (row_off [4 B L + 1], key [E]) ONE CSR over the head-major rows, row (h B + b) L + i = query i of image b under head h, keys in [0, N);
+ *   x [B,64,H,W] the stage's input, mix_w [64,64], mix_b [64], out [B,64,H,W] = conv1x1(cat_h(fold(agg_h) / cnt)) + mix_b + x.
+ * Launches: the segment and combine launches of dagl_graph_forward with B' = 4 B, then the fused fold + mix on the aggregated rows; every
+ * row is dagl_graph_forward's for its head bit for bit.  total_edges = 0 gives mix_b + x.  The three training outputs come together or not
+ * at all (refused otherwise) and leave `out` bit for bit: row_max_out [4 B L] fp32 / row_sum_out [4 B L] fp64 (dagl_graph_forward_train's,
+ * one more launch) and cat_out [4,B,16,H,W], the pre-mix concat map head-major (one fold launch with B' = 4 B: dagl_graph_forward's `out`
+ * of the stacked operands, the values the fused kernel forms per pixel).  Workspace: dagl_graph_forward_workspace_bytes of 4 B images.
+ * Checks: the shape (4 B H W < 2^30), dagl_graph_forward's on the stacked operands, the mix operands, the training outputs, the workspace.
+ *
+ * dagl_ces_stage_mix_backward: the backward of that last launch from d_out [B,64,H,W] and the saved cat4 [4,B,16,H,W]:
+ *   d_cat4 [4,B,16,H,W][h,b,c,p] = sum_o mix_w[o][16 h + c] d_out[b,o,p] -- head-major and NOT divided by the overlap count: viewed as
+ *     [4 B,16,H,W] it is the d_out of dagl_graph_forward_backward on the stacked operands, which divides;
+ *   d_mix_w [64,64][o][c] = sum_{b,p} d_out[b,o,p] cat[b,c,p], d_mix_b [64][o] = sum_{b,p} d_out[b,o,p]   (each may be NULL; cat4 may be
+ *     NULL when both are).  The gradient of the residual input x is d_out itself.
+ * fp32 MFMA 16x16x4 throughout; the weight gradient is split over contiguous pixel ranges -- the number of blocks depends on B H W alone
+ * and is capped --, every wave leaves its 64 x 64 tile and bias sums in a slot of its own and one more launch adds the slots in slot order
+ * in fp64: no float atomics, the same operands give the same bits on every call.  d_out, cat4 and d_cat4 must be 16-byte aligned. */
+size_t dagl_graph_stage_forward_workspace_bytes(int B, int H, int W, int64_t total_edges);
+int dagl_graph_stage_forward(void* stream, int B, int H, int W, const float* wq_rows4, const float* x_rows4, const float* b2p4,
+                             const int64_t* row_off, const int32_t* key, int64_t total_edges, const float* tau4 /* NULL: no margin */,
+                             float scale, int flags /* bit 0: edges-only normalisation */, const float* x, const float* mix_w,
+                             const float* mix_b, float* out, float* row_max_out /* may be NULL */, double* row_sum_out /* may be NULL */,
+                             float* cat_out /* may be NULL */, void* workspace, size_t ws_bytes);
+size_t dagl_ces_stage_mix_backward_workspace_bytes(int B, int H, int W);
+int dagl_ces_stage_mix_backward(void* stream, int B, int H, int W, const float* d_out, const float* cat4, const float* mix_w, float* d_cat4,
+                                float* d_mix_w /* may be NULL */, float* d_mix_b /* may be NULL */, void* workspace, size_t ws_bytes);
 
 /* ---- the patch graph of a differentiable forward, from its own neighbour lists: csrc/graph_lists.hip (ABI 412, detected by symbol) ---
  * dagl_ce_core_forward leaves each query's neighbours as fixed-width lists in selection order; nb_wgt = exp(l_t) / Z_l with the unlisted

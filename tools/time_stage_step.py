@@ -25,6 +25,13 @@ frame of a captured HIP graph -- a frame is the stage's step and ``copy_`` of th
 stage-fused step on the CSR state (one host read, not capturable with its graph) next to them.  ``--search``: the same with
 ``propagate``, ``explore=8``.
 
+    python tools/time_stage_step.py --frozen [1024 1024]    # frozen graphs (``CES.forward_on_graphs``), the same two cases
+
+One stage and the whole ``CES`` on graphs that do not move, head by head against ``fused=True`` (``ops.graph_stage_forward``; under
+autograd ``ce._GraphStageForward``), the two legs of every line interleaved window by window: without a gradient on ``"fp32"``,
+``"split16"`` and ``"stage16"`` (the last against head by head on ``"split16"``: it has no head-by-head form), a training step
+(forward + backward, ``backward="fused"``) on ``"fp32"`` and ``"split16"``, and what the ``torch.stack`` of the per-head operands costs.
+
 Every table also has the ``features="stage16"`` column (``ops.graph_stage_features16``: the four heads' prologue and projections in one
 launch each) next to ``"split16"``: the features alone, the fused step with and without the graphs, the fused search step, and
 ``--fixed [--search]`` eager and replayed.
@@ -268,9 +275,91 @@ def fixed_leg(H, W, big, search_on):
           f"    the stage-fused {what} on the CSR state, eager with its graph (one host read): {fmt(csr)}", flush=True)
 
 
+def _interleaved(fns, warmup=2, rounds=7, inner=3):
+    """``_events`` for legs that are compared with each other: every round times each leg once, in turn, so that a drift of the
+    clocks or of the device's state meets all of them alike -> [(median, lowest, highest) ms per call] per leg."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(rounds):
+        for fn, ts in zip(fns, times):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(inner):
+                fn()
+            t1.record()
+            torch.cuda.synchronize()
+            ts.append(t0.elapsed_time(t1) / inner)
+    return [(sorted(ts)[len(ts) // 2], min(ts), max(ts)) for ts in times]
+
+
+def frozen_leg(H, W, big):
+    """``CES.forward_on_graphs``: one stage and the whole module on frozen graphs, head by head against ``fused=True``."""
+    from dagl_amd.sequence import SequenceState
+    name, mode, ces, x, x2 = _case(H, W, big)
+    fmt = _fmt
+    margin = mode != "topk"
+    with torch.no_grad():
+        heads, mix = ces._stage_modules(1)
+        graphs = [hd.graph(x) for hd in heads]
+        state = SequenceState.from_heads(graphs * 3)          # every stage runs on the graphs of stage 1
+        for g in state.stages:
+            g.validate().transpose()
+        for g in graphs:
+            g.validate().transpose()
+        stage = state.stages[0]
+
+    def stage_by_head(feat, backward="two_ops"):
+        outs = [hd.forward_on_graph(x2, state.head(0, h), features=feat, backward=backward) for h, hd in enumerate(heads)]
+        return mix(torch.cat(outs, dim=1)) + x2
+
+    def train(forward):
+        def step():
+            ces.zero_grad(set_to_none=True)
+            forward().square().sum().backward()
+        return step
+
+    print(f"[1,64,{H},{W}] {name}, frozen graphs: stage graph {stage.n_edges} edges over 4 heads; ms per call, legs of a line interleaved",
+          flush=True)
+    with torch.no_grad():
+        for feat in ("fp32", "split16"):
+            by_head, fused = _interleaved([lambda: stage_by_head(feat), lambda: ces._stage_forward_fused(1, x2, stage, margin, feat)])
+            gap = float((stage_by_head(feat) - ces._stage_forward_fused(1, x2, stage, margin, feat)).abs().max() / stage_by_head(feat).abs().max())
+            print(f"    one stage, no grad, {feat}: head by head {fmt(by_head)}, fused=True {fmt(fused)} = {fused[0] / by_head[0]:.2f}; outputs "
+                  f"differ by {gap:.1e} of the largest", flush=True)
+        by_head, fused = _interleaved([lambda: stage_by_head("split16"), lambda: ces._stage_forward_fused(1, x2, stage, margin, "stage16")])
+        print(f"    one stage, no grad, stage16: fused=True {fmt(fused)} = {fused[0] / by_head[0]:.2f} of head by head on split16 {fmt(by_head)}",
+              flush=True)
+        for feat in ("fp32", "split16"):
+            by_head, fused = _interleaved([lambda: ces.forward_on_graphs(x2, state, features=feat),
+                                           lambda: ces.forward_on_graphs(x2, state, features=feat, fused=True)])
+            print(f"    whole CES, no grad, {feat}: head by head {fmt(by_head)}, fused=True {fmt(fused)} = {fused[0] / by_head[0]:.2f}", flush=True)
+        by_head, fused = _interleaved([lambda: ces.forward_on_graphs(x2, state, features="split16"),
+                                       lambda: ces.forward_on_graphs(x2, state, features="stage16", fused=True)])
+        print(f"    whole CES, no grad, stage16: fused=True {fmt(fused)} = {fused[0] / by_head[0]:.2f} of head by head on split16 {fmt(by_head)}",
+              flush=True)
+        # what the stack of the per-head features costs (the stage-fused kernels take one head-major array per operand)
+        feats = ces._stage_features(1, x2, margin, "split16")
+        stack = _events(lambda: [torch.stack([f[i] for f in feats]) for i in ((0, 1, 2, 3) if margin else (0, 1, 3))])
+        print(f"    torch.stack of the four heads' operands (wq, x, b2p" + (", tau" if margin else "") + f"): {fmt(stack)}", flush=True)
+        del feats
+    for feat in ("fp32", "split16"):
+        by_head, fused = _interleaved([train(lambda: stage_by_head(feat, "fused")),
+                                       train(lambda: ces._stage_forward_fused(1, x2, stage, margin, feat))])
+        print(f"    one stage, training step (forward + backward, backward='fused'), {feat}: head by head {fmt(by_head)}, fused=True {fmt(fused)} "
+              f"= {fused[0] / by_head[0]:.2f}", flush=True)
+        by_head, fused = _interleaved([train(lambda: ces.forward_on_graphs(x2, state, features=feat, backward="fused")),
+                                       train(lambda: ces.forward_on_graphs(x2, state, features=feat, backward="fused", fused=True))])
+        print(f"    whole CES, training step, {feat}: head by head {fmt(by_head)}, fused=True {fmt(fused)} = {fused[0] / by_head[0]:.2f}", flush=True)
+
+
 def main():
     search = "--search" in sys.argv[1:]
-    argv = [a for a in sys.argv[1:] if a not in ("--search", "--fixed")]
+    argv = [a for a in sys.argv[1:] if a not in ("--search", "--fixed", "--frozen")]
+    if "--frozen" in sys.argv[1:]:
+        return frozen_leg(int(argv[0]), int(argv[1]), True) if len(argv) > 1 else frozen_leg(256, 256, False)
     if "--fixed" in sys.argv[1:]:
         return fixed_leg(int(argv[0]), int(argv[1]), True, search) if len(argv) > 1 else fixed_leg(256, 256, False, search)
     leg = search_leg if search else stage_leg
